@@ -18,6 +18,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
                  the issue rates measured by scripts/ubench_valu.hip); "bound" names the lower one;
   cpu_baseline — the CPU oracle in reference-literal mode (single thread, the reference CLI is
                  single-threaded) on a bounded sample of the same workload.
+
+--dump-outputs DIR writes what the timed path returned in its last step (dump_outputs below), so that two
+builds can be compared output for output: the inputs are a pure function of the arguments.
 """
 import argparse
 import json
@@ -61,6 +64,8 @@ def workload_desc(cfg):
 
 DEFAULT_WORKLOAD = "cfg3p"
 BPS = {0: 8, 1: 2, 2: 2, 3: 4}
+DUMP_SEED = 0x5EED0003       # --dump-outputs: which windows of a larger output are written
+DUMP_BUDGET = 32 << 20      # --dump-outputs: bytes of norms (+ 8 bytes of index per row) at most, well inside 64 MB
 FMT_NAMES = {0: "cf32", 1: "cs8", 2: "cu8", 3: "cs16"}
 STREAM_SEED = 0x5EED0002     # ONE seed for the whole stream: the generator is keyed by absolute sample index, not by rank
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E data-sheet peak (MI355X_MICROARCH.md); ~6300 measured copy
@@ -332,9 +337,37 @@ def spawn_ranks(n, argv):
     return 0
 
 
+# ------------------------------------------------------------------ --dump-outputs
+
+def dump_windows(n_windows, width):
+    """Window indices --dump-outputs writes: all of them when their norms fit DUMP_BUDGET, otherwise a fixed seeded sample of that
+    size plus the first and the last window.  A pure function of (n_windows, width): two builds dump the same rows."""
+    import numpy as np
+    k = DUMP_BUDGET // (width * 4 + 8)
+    if n_windows <= k:
+        return np.arange(n_windows, dtype=np.int64)
+    pick = np.random.default_rng(DUMP_SEED).choice(n_windows, size=k - 2, replace=False)
+    return np.union1d(pick, [0, n_windows - 1]).astype(np.int64)
+
+
+def dump_outputs(dump_dir, out, n_windows, w0, rank, world):
+    """The norms the timed path returned in its last step (`out`: this rank's windows [w0, w0 + rows), float32), written as
+    <dump_dir>/norms.npy (float32, one row per dumped window) and windows.npy (their absolute window indices, float64); with
+    several ranks every rank writes the dumped windows it owns, under a _rank<r> suffix."""
+    import numpy as np
+    import torch
+    idx = dump_windows(n_windows, out.shape[1])
+    idx = idx[(idx >= w0) & (idx < w0 + out.shape[0])]
+    rows = out[torch.from_numpy(idx - w0).to(out.device)].cpu().numpy()
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, f"norms{sfx}.npy"), np.ascontiguousarray(rows, dtype=np.float32))
+    np.save(os.path.join(dump_dir, f"windows{sfx}.npy"), idx.astype(np.float64))
+
+
 # ------------------------------------------------------------------ one measurement
 
-def measure(args, name, cfg, rank, world, device, dist, steps, warmup, with_cpu):
+def measure(args, name, cfg, rank, world, device, dist, steps, warmup, with_cpu, dump_dir=None):
     import numpy as np
     import torch
     import quadrs_amd as Q
@@ -463,6 +496,8 @@ def measure(args, name, cfg, rank, world, device, dist, steps, warmup, with_cpu)
         elapsed = float(t.item())
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev.values()]))
     finite = bool(torch.isfinite(out).all().item())
+    if dump_dir:                    # before the power sampling below launches the step again
+        dump_outputs(dump_dir, out, plan.n_windows, me.w0, rank, world)
     power = None
     if rank == 0 and world == 1 and getattr(args, "power_sample", False):
         power = sample_power(step, torch, getattr(args, "power_seconds", 2.5))
@@ -748,7 +783,14 @@ def main():
                     help="multi-rank rehearsal on ONE GPU: gloo backend, every rank on cuda:0, halo staged through the host")
     ap.add_argument("--stub", action="store_true", help="launch-path rehearsal on the CPU: no GPU work, gloo, a sleep per step")
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help="(tests) this rank of a --stub run exits non-zero at the end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the norms of the last step as DIR/norms.npy (float32; a fixed seeded sample of the "
+                         "windows when the output exceeds 32 MiB) and their window indices as DIR/windows.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.stub and args.dump_outputs:
+        ap.error("--dump-outputs: a --stub run computes nothing")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -780,7 +822,7 @@ def main():
         cfg["n"] = 1 << args.samples_log2
     args.power_sample = world == 1 and not args.no_power and not args.stub
     main_res = measure(args, args.workload, cfg, rank, world, device, dist, args.steps, args.warmup,
-                       with_cpu=(world == 1 and not args.no_cpu_baseline))
+                       with_cpu=(world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
     args.power_sample = False
     bad = rank == 0 and (main_res.get("seams_verified") is False or not main_res["outputs_finite"])
     others = None

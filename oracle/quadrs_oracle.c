@@ -1,7 +1,7 @@
 /*
  * quadrs_oracle.c — CPU restatement of the quadrs hot path.  TEST INFRASTRUCTURE ONLY.
  * See quadrs_oracle.h for the pinning status.  Every function cites the reference
- * file:line (paths relative to /root/reference) it follows.
+ * file:line (paths relative to the reference repository's root) it follows.
  *
  * Build: gcc -O2 -fno-fast-math -ffp-contract=off  (no FMA contraction: Rust never
  * contracts a*b+c, and the reference's results depend on separately rounded mul/add).
@@ -710,7 +710,7 @@ int qo_take_fft(const qo_node *n, int has_slice, uint64_t start, uint64_t end, s
     if (!(visible > (uint64_t)output_len)) return 1;   /* ensure!, :45-48 */
     /* :25 FftPlanner::plan_fft_forward(W) takes ANY length.  A power of two goes to the Radix4 restatement (what the
      * planner itself picks on a scalar target).  For every other length rustfft's planner composes mixed-radix / Rader /
-     * Bluestein steps chosen by its host-SIMD build, and its source is not in /root/reference: PARITY UNPINNED.  The oracle
+     * Bluestein steps chosen by its host-SIMD build, and its source is not in the reference: PARITY UNPINNED.  The oracle
      * then gives the mathematically exact answer instead — an f64 DFT rounded once to f32 — and the tests compare the
      * GPU against it with an explicit error bound, not bit for bit. */
     qo_fft *fft = qo_fft_new(W);

@@ -15,7 +15,7 @@
  *     the README OOK string (README.md:113-116,167), which tests/test_oracle_golden.py
  *     reproduces exactly through this oracle.
  *   - FFT rounding order: the arithmetic lives in rustfft 6.4.0 (Cargo.lock:3207-3219),
- *     whose source is NOT in /root/reference.  qo_fft_radix4() restates rustfft's published
+ *     whose source is NOT in the reference.  qo_fft_radix4() restates rustfft's published
  *     scalar Radix4 algorithm (Butterfly1/2/4/8/16 base + radix-4 DIT cross layers,
  *     twiddles = (f32)cos/sin of an f64 angle).  No reference fixture pins its internal
  *     rounding => "parity unpinned" for FFT bit patterns; it is bounded against an f64 DFT.

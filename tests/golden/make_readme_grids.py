@@ -1,8 +1,9 @@
-"""Decodes the reference's README screenshots (terminal pictures of `sparkfft` output, /root/reference/screenshots/
+"""Decodes the reference's README screenshots (terminal pictures of `sparkfft` output, screenshots/
 fsk-{1..5}.png and ook-1.png, README.md:27-97,113-118) into grids of glyph codes — 0 blank, 1..8 = '▁'..'█' — and writes
 tests/golden/readme_glyph_grids.npz.  These are OUTPUTS OF THE REAL REFERENCE on its two committed example recordings, i.e.
 externally authored known answers for the whole chain (shift, lowpass, FFT, hypot, glyph ladder), unlike the oracle's own
-vectors.  Run in the build container (needs /root/reference and PIL); the .npz is the committed fixture.
+vectors.  Needs a checkout of the reference and PIL; the .npz is the committed fixture.
+    python tests/golden/make_readme_grids.py <reference checkout>
 
 A terminal cell is `cw` x `pitch` pixels; a glyph of code k is a bar of ceil(k * pitch / 8) pixel rows at the bottom of its
 cell (measured: the only heights that occur are 2,3,5,6,8,12 at pitch 12; 2,3,4,6,9 at pitch 9; 3 at pitch 19), so
@@ -14,7 +15,7 @@ import sys
 import numpy as np
 from PIL import Image
 
-SHOTS = "/root/reference/screenshots"
+SHOTS = None          # <reference checkout>/screenshots, from the command line
 HERE = os.path.dirname(os.path.abspath(__file__))
 # name: (cell width, row pitch, has the │ border columns)
 SPEC = {"fsk-1": (5, 12, False), "fsk-2": (5, 9, False), "fsk-3": (5, 12, False), "fsk-4": (5, 12, False), "fsk-5": (10, 19, False),
@@ -66,6 +67,10 @@ def decode(name):
 
 
 def main():
+    global SHOTS
+    if len(sys.argv) != 2:
+        sys.exit("usage: make_readme_grids.py <reference checkout>")
+    SHOTS = os.path.join(sys.argv[1], "screenshots")
     out = {}
     for name in SPEC:
         g = decode(name)

@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -47,3 +49,44 @@ def test_valu_roof_model():
         assert f32 >= 4.0 * cfg["lp"][2] / cfg["lp"][1]
     assert roofs["cfg2"][0] > roofs["cfg2"][1] and roofs["cfg3p"][0] > roofs["cfg3p"][1]     # hbm-bound
     assert roofs["cfg3"][0] < roofs["cfg3"][1] and roofs["cfg4"][0] < roofs["cfg4"][1]       # valu-bound
+
+
+def test_steps_below_one_are_refused():
+    r = _run("--steps", "0")
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_dump_windows_are_fixed_and_bounded():
+    """--dump-outputs: every window of a small output; of a large one a sample that depends on nothing but the shape, keeps the first
+    and the last window and stays inside the budget (float32 norms + float64 indices)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    assert np.array_equal(bench.dump_windows(1000, 128), np.arange(1000))
+    for n, w in ((1 << 19, 128), (1 << 22, 64), (1 << 19, 1024)):
+        a, b = bench.dump_windows(n, w), bench.dump_windows(n, w)
+        assert np.array_equal(a, b) and a[0] == 0 and a[-1] == n - 1
+        assert np.all(np.diff(a) > 0) and a.size * (w * 4 + 8) <= bench.DUMP_BUDGET < 64 * 10**6
+
+
+@pytest.mark.gpu
+@pytest.mark.spawns_gpu_ranks
+def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """bench.py --dump-outputs on a small cfg2 stream: every window's norms, and the same bytes whatever the number of timed steps
+    (the input is a pure function of the arguments).  Child processes only: this process never touches the GPU."""
+    import numpy as np
+    dumps = []
+    for steps in (1, 5):
+        d = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--samples-log2", "20", "--steps", str(steps),
+                            "--warmup", "1", "--settle", "0", "--no-cpu-baseline", "--no-power", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps
+        norms, windows = np.load(d / "norms.npy"), np.load(d / "windows.npy")
+        assert norms.dtype == np.float32 and windows.dtype == np.float64
+        assert norms.shape[1] == 128 and np.array_equal(windows, np.arange(norms.shape[0]))
+        assert norms.shape[0] == (1 << 20) // (16 * 128) - 1 and np.isfinite(norms).all()
+        dumps.append(norms)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))

@@ -1,6 +1,6 @@
 """The reference's README pictures as known answers.
 
-/root/reference/screenshots/fsk-{1..5}.png and ook-1.png are terminal pictures of the REAL reference's `sparkfft` output on its
+The reference's screenshots/fsk-{1..5}.png and ook-1.png are terminal pictures of the REAL reference's `sparkfft` output on its
 two committed example recordings (README.md:27-97, 113-118).  tests/golden/make_readme_grids.py decoded them into grids of
 glyph codes (tests/golden/readme_glyph_grids.npz); the recordings are tests/golden/{fsk-example.sr21M.fc32,
 cupboard-superdec.sr400.cf32}.  A picture is a crop: which output row / FFT bin its first cell is, is found by search.

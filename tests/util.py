@@ -2,7 +2,7 @@ import numpy as np
 
 import os
 
-# /root/reference/README.md:167, copied verbatim as an expected-output fixture
+# the reference's README.md:167, copied verbatim as an expected-output fixture
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "readme_ook_line167.txt")) as _f:
     README_OOK = _f.read().strip()
 
