@@ -245,6 +245,48 @@ int qd_plan_shard_info(const qd_plan *plan, uint32_t shard, qd_shard_info *info)
 int qd_plan_run_sharded(qd_plan *plan, const void *src, int src_mem, void *out, int out_mem);
 int qd_plan_run_sharded_device(qd_plan *plan, void *const *slabs, void *const *outs, int sync);
 
+/* ------------------------------------------------------------------ stage lists (cascades)
+ *
+ * The CLI grammar takes `shift` and `lowpass` in any order and number (src/args.rs:19-45); Operation::exec nests them
+ * (src/lib.rs:83-175).  qd_chain_desc holds at most one shift ahead of at most one lowpass; a stage list describes the rest.
+ * Each stage is validated at ITS OWN input rate, in list order, with the one-stage plan's codes: a shift with
+ * |f| >= rate / 2 (src/shift.rs:20-24), decimate 0, taps < 2 and inner len < taps (src/filter.rs:45-48,74) are QD_ERR_PANIC,
+ * and so is a sink len < width.  A lowpass's taps are designed for its input rate; its output rate is rate / decimate
+ * (integer division, src/filter.rs:51).
+ *   [shift] [lowpass]                     routed to the one-stage plan (qd_plan_create_ex): the same kernels, bytes and name;
+ *   [shift] lowpass [shift] [lowpass [shift]]  otherwise (e.g. `lowpass shift`, `lowpass lowpass`, `shift lowpass shift
+ *                                         lowpass shift`): the fused cascade kernel.  Its envelope: an intermediate block of
+ *                                         W*D2 + T2 <= 8192 samples per window (W without a second lowpass), a first stage of
+ *                                         at most 4096 taps, any stride; the window's source span (W*D2 + T2)*D1 + T1 is
+ *                                         streamed through the workgroup in sub-tiles.  QD_MODE_FAST runs its exact arithmetic.
+ *   anything else (three lowpasses, two shifts in a row, shift-only cascades, a block past the envelope): QD_ERR_UNSUPPORTED.
+ * A cascade plan's qd_plan_info composes through the stages: raw_per_window / raw_step are the source span / step of a
+ * window, decimated_len / out_sample_rate are the sink's, ratio is the first shift's.  qd_plan_src_range, qd_plan_run
+ * (device buffers, host buffers in chunks, slabs, window sub-ranges) and qd_plan_run_sharded (any shard devices) work and give
+ * the bytes of the whole-stream run; qd_plan_run_sharded_device and QD_EPI_CF32_BLOCKS return QD_ERR_UNSUPPORTED.
+ * With two lowpass stages LowPass::len over-reports (src/filter.rs:45-48) and the sink's last window(s) may fail
+ * read_exact_at (src/samples.rs:17-27): qd_plan_complete_windows gives the leading windows that succeed, and a run whose range
+ * reaches past them writes every complete window of the range and returns QD_ERR_SHORT. */
+typedef enum { QD_STAGE_SHIFT = 1, QD_STAGE_LOWPASS = 2 } qd_stage_kind;
+typedef struct {                 /* one Operation::Shift / Operation::LowPass, src/lib.rs:102-121 */
+    int32_t  kind;               /* qd_stage_kind */
+    int32_t  _pad;
+    int64_t  shift_hz;           /* QD_STAGE_SHIFT */
+    uint64_t lowpass_hz, decimate, taps;   /* QD_STAGE_LOWPASS */
+} qd_stage;
+#define QD_MAX_STAGES 8
+/* desc: source and sink fields (has_shift = has_lowpass = 0, else QD_ERR_INVALID); stages in source-to-sink order */
+int qd_plan_create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages,
+                          const qd_plan_options *options, qd_plan **plan);
+/* taps of lowpass stage `stage` (an index into the plan's stage list); QD_ERR_INVALID for a shift stage */
+int qd_plan_get_stage_taps(const qd_plan *plan, uint32_t stage, float *taps, size_t cap);
+/* leading windows of the sink's loop whose read_exact_at succeeds (== n_windows for every one-stage plan) */
+int qd_plan_complete_windows(const qd_plan *plan, uint64_t *n);
+/* host arithmetic only (no device): validates like qd_plan_create_stages and fills n_windows, decimated_len, out_sample_rate,
+ * out_bytes_per_window, raw_per_window, raw_step and ratio of the plan it would make (other fields 0), and *complete its
+ * qd_plan_complete_windows */
+int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, qd_plan_info *info, uint64_t *complete);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

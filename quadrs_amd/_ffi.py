@@ -23,8 +23,11 @@ SYMBOLS = [
     "qd_device_alloc", "qd_device_free", "qd_device_copy",
     "qd_set_stream", "qd_release_workspaces", "qd_plan_create_ex", "qd_plan_shard_info", "qd_plan_run_sharded",
     "qd_plan_run_sharded_device", "qd_plan_get_stats", "qd_host_alloc", "qd_host_free", "qd_host_register",
-    "qd_host_unregister", "qd_plan_kernel_name",
+    "qd_host_unregister", "qd_plan_kernel_name", "qd_plan_create_stages", "qd_plan_get_stage_taps",
+    "qd_plan_complete_windows", "qd_stages_geometry",
 ]
+STAGE_SHIFT, STAGE_LOWPASS = 1, 2
+MAX_STAGES = 8
 
 
 class ChainDesc(C.Structure):
@@ -45,6 +48,13 @@ class PlanInfo(C.Structure):
         ("out_bytes_per_window", C.c_uint64), ("raw_per_window", C.c_uint64), ("raw_step", C.c_uint64),
         ("ratio", C.c_double), ("tile_windows", C.c_uint32), ("threads", C.c_uint32),
         ("lds_bytes", C.c_uint32), ("kernel_kind", C.c_uint32), ("kernel_flags", C.c_uint32), ("_reserved", C.c_uint32),
+    ]
+
+
+class Stage(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("_pad", C.c_int32), ("shift_hz", C.c_int64),
+        ("lowpass_hz", C.c_uint64), ("decimate", C.c_uint64), ("taps", C.c_uint64),
     ]
 
 
@@ -134,6 +144,10 @@ def lib():
             "qd_host_free": (i32, [vp]),
             "qd_host_register": (i32, [vp, sz]),
             "qd_host_unregister": (i32, [vp]),
+            "qd_plan_create_stages": (i32, [C.POINTER(ChainDesc), C.POINTER(Stage), sz, C.POINTER(PlanOptions), C.POINTER(vp)]),
+            "qd_plan_get_stage_taps": (i32, [vp, C.c_uint32, vp, sz]),
+            "qd_plan_complete_windows": (i32, [vp, C.POINTER(u64)]),
+            "qd_stages_geometry": (i32, [C.POINTER(ChainDesc), C.POINTER(Stage), sz, C.POINTER(PlanInfo), C.POINTER(u64)]),
         }
         for name, (res, args) in sig.items():
             try:

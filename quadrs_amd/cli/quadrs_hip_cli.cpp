@@ -7,8 +7,10 @@
 // stdout is byte-identical to the reference's for the same command line; diagnostics go to stderr.
 //
 // Chains of the shape  from|gen [shift] [lowpass]  ->  sparkfft|bucket  run as ONE fused plan
-// (qd_plan_*).  Anything else (e.g. two lowpasses, write) falls back to the block iterator, whose
-// read_at() calls the fine-grained entry points exactly where the reference's read_at() computes.
+// (qd_plan_*); other shift / lowpass stage lists in front of sparkfft|bucket (a shift after the filter, two cascaded
+// lowpasses) go to a fused cascade plan (qd_plan_create_stages).  Anything else (e.g. three lowpasses, write after a
+// cascade) falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the
+// reference's read_at() computes.
 #include <cerrno>
 #include <cinttypes>
 #include <cstdio>
@@ -345,6 +347,8 @@ struct LowPass : Samples {                                              // src/f
 struct ChainSpec {          // what a fused plan can express
     bool fusable = false;
     const Op *src = nullptr, *shift = nullptr, *lowpass = nullptr;
+    std::vector<const Op *> stages;      // every shift / lowpass since the source, in order (cascade plans)
+    bool cascade = false;                // the stages are not  [shift] [lowpass]: qd_plan_create_stages
 };
 
 // The whole source file for a fused plan: mapped, not read — and registered with the HIP runtime when it allows it, so the
@@ -381,15 +385,15 @@ int g_gpus = 1;      // `-gpus N` in front of the chain: shard the sink's window
 
 // plan for the CLI: the library's defaults, plus window-range shards over g_gpus devices (repeating devices when the
 // machine has fewer: the shards then run as independent streams of one device)
-int create_plan(const qd_chain_desc &d, qd_plan **plan) {
-    if (g_gpus <= 1) return qd_plan_create(&d, plan);
+int create_plan(const qd_chain_desc &d, qd_plan **plan, const std::vector<qd_stage> *stages = nullptr) {
+    if (g_gpus <= 1) return stages ? qd_plan_create_stages(&d, stages->data(), stages->size(), nullptr, plan) : qd_plan_create(&d, plan);
     qd_plan_options o{};
     o.struct_size = sizeof o;
     int n_dev = 1;
     if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
     o.n_shards = (uint32_t)(g_gpus > QD_MAX_SHARDS ? QD_MAX_SHARDS : g_gpus);
     for (uint32_t g = 0; g < o.n_shards; ++g) o.shard_device[g] = (int32_t)(g % (uint32_t)n_dev);
-    return qd_plan_create_ex(&d, &o, plan);
+    return stages ? qd_plan_create_stages(&d, stages->data(), stages->size(), &o, plan) : qd_plan_create_ex(&d, &o, plan);
 }
 
 // device buffer that frees itself (the `gen` source of a fused chain lives in HBM)
@@ -402,7 +406,11 @@ struct DeviceBuf {
 // (src/gen.rs:30-47) and never crosses PCIe: only the glyph codes / digits come back
 // returns false when the library has no fused plan for the chain (QD_ERR_UNSUPPORTED: e.g. overlapping windows whose FIR input exceeds one
 // workgroup's LDS); the header line is printed by then, the caller pulls the windows through the iterator chain instead
-bool run_fused(const ChainSpec &cs, const Op &sink, uint64_t out_rate) {
+// A cascade whose last window(s) fail read_exact_at (two lowpasses: LowPass::len over-reports, src/filter.rs:45-48): the complete
+// windows' rows are printed, then the first failing window is read through the iterator chain, which stops with the reference's
+// error (src/samples.rs:17-27) — sparkfft prints inside its loop (src/fft.rs:28-65), bucket unwraps before printing anything.
+bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
+    const uint64_t out_rate = samples.sample_rate();
     const bool from_gen = cs.src->kind == OP_GEN;
     std::unique_ptr<MappedFile> data;
     if (!from_gen) data.reset(new MappedFile(cs.src->filename));
@@ -411,24 +419,40 @@ bool run_fused(const ChainSpec &cs, const Op &sink, uint64_t out_rate) {
     d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
     d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate)          // Gen::len, src/gen.rs:32
                            : data->size / qd_pair_bytes(cs.src->format);
-    if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
-    if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
+    std::vector<qd_stage> stages;
+    if (cs.cascade) {
+        for (const Op *op : cs.stages) {
+            qd_stage st{};
+            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
+            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
+            stages.push_back(st);
+        }
+    } else {
+        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
+        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
+    }
     d.width = sink.width; d.stride = sink.stride;
     d.epilogue = sink.kind == OP_BUCKET ? QD_EPI_BUCKET2_U8 : QD_EPI_GLYPH_U8;
     d.has_range = sink.has_range; d.range_min = sink.rmin; d.range_max = sink.rmax;
     if (sink.kind == OP_SPARKFFT) printf("sparkfft sample_rate=%" PRIu64 "\n", out_rate);   // printed before any read (src/fft.rs:19)
     qd_plan *plan = nullptr;
     {
-        const int rc = from_gen ? qd_plan_create(&d, &plan) : create_plan(d, &plan);
+        const int rc = from_gen && !cs.cascade ? qd_plan_create(&d, &plan)
+                     : from_gen ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan)
+                     : create_plan(d, &plan, cs.cascade ? &stages : nullptr);
         if (rc == QD_ERR_UNSUPPORTED) return false;
         qd_check(rc, "plan");
     }
     qd_plan_info info;
     qd_check(qd_plan_get_info(plan, &info), "plan info");
+    uint64_t complete = info.n_windows;
+    qd_check(qd_plan_complete_windows(plan, &complete), "plan complete windows");
+    // a range past the complete windows returns QD_ERR_SHORT after writing every complete window
+    auto check_run = [&](int rc, const char *what) { if (!(rc == QD_ERR_SHORT && complete < info.n_windows)) qd_check(rc, what); };
     std::vector<uint8_t> out(info.n_windows * info.out_bytes_per_window + 1);
     if (info.n_windows && !from_gen) {
-        if (g_gpus > 1) qd_check(qd_plan_run_sharded(plan, data->p, data->mem, out.data(), QD_MEM_HOST), "run (sharded)");
-        else qd_check(qd_plan_run(plan, data->p, data->mem, 0, d.n_samples, 0, info.n_windows, out.data(), QD_MEM_HOST, nullptr), "run");
+        if (g_gpus > 1) check_run(qd_plan_run_sharded(plan, data->p, data->mem, out.data(), QD_MEM_HOST), "run (sharded)");
+        else check_run(qd_plan_run(plan, data->p, data->mem, 0, d.n_samples, 0, info.n_windows, out.data(), QD_MEM_HOST, nullptr), "run");
     }
     if (info.n_windows && from_gen) {
         DeviceBuf src, dst;
@@ -441,14 +465,14 @@ bool run_fused(const ChainSpec &cs, const Op &sink, uint64_t out_rate) {
             qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, a, (size_t)n,
                             static_cast<qd_c32 *>(src.p) + a, QD_MEM_DEVICE), "gen");
         }
-        qd_check(qd_plan_run(plan, src.p, QD_MEM_DEVICE, 0, d.n_samples, 0, info.n_windows, dst.p, QD_MEM_DEVICE, nullptr), "run");
+        check_run(qd_plan_run(plan, src.p, QD_MEM_DEVICE, 0, d.n_samples, 0, info.n_windows, dst.p, QD_MEM_DEVICE, nullptr), "run");
         qd_check(qd_device_copy(out.data(), QD_MEM_HOST, dst.p, QD_MEM_DEVICE, ob), "copy back");   // synchronises with the launch
     }
     qd_plan_destroy(plan);
     if (sink.kind == OP_SPARKFFT) {
         // header already printed; rows only
         std::string line;
-        for (uint64_t w = 0; w < info.n_windows; ++w) {
+        for (uint64_t w = 0; w < complete; ++w) {
             line.assign("\xE2\x94\x82");
             for (size_t b = 0; b < sink.width; ++b) {
                 uint8_t c = out[w * sink.width + b];
@@ -459,7 +483,13 @@ bool run_fused(const ChainSpec &cs, const Op &sink, uint64_t out_rate) {
             line += "\xE2\x94\x82\n";
             fwrite(line.data(), 1, line.size(), stdout);
         }
-    } else {
+    }
+    if (complete < info.n_windows) {
+        std::vector<qd_c32> buf(sink.width);
+        samples.read_exact_at(complete * sink.stride, buf.data(), sink.width);       // fails: the reference's error
+        bail("complete-window count disagrees with the iterator chain");
+    }
+    if (sink.kind != OP_SPARKFFT) {
         std::string digits;
         for (uint64_t w = 0; w < info.n_windows; ++w) digits.push_back((char)('0' + out[w]));
         printf("%s\n", digits.c_str());                                   // src/lib.rs:144-158
@@ -625,7 +655,7 @@ int main(int argc, char **argv) {
         // fold the commands left to right (src/bin/quadrs.rs:48-56)
         std::unique_ptr<Samples> samples;
         ChainSpec cs;
-        bool chain_clean = true;        // from [shift] [lowpass] so far, each at most once, in that order
+        bool chain_clean = true;        // from [shift] [lowpass] so far, each at most once, in that order (else: a cascade)
         for (size_t i = 0; i < ops.size(); ++i) {
             const Op &op = ops[i];
             switch (op.kind) {
@@ -642,19 +672,22 @@ int main(int argc, char **argv) {
                 if (cs.shift || cs.lowpass) chain_clean = false;
                 samples.reset(new Shift(std::move(samples), op.shift));
                 cs.shift = &op;
+                cs.stages.push_back(&op);
                 break;
             case OP_LOWPASS:
                 if (!samples) bail("lowpass requires an input");
                 if (cs.lowpass) chain_clean = false;
                 samples.reset(new LowPass(std::move(samples), op.lp_freq, op.decimate, op.size));
                 cs.lowpass = &op;
+                cs.stages.push_back(&op);
                 break;
             case OP_SPARKFFT:
             case OP_BUCKET:
                 if (!samples) bail(op.kind == OP_SPARKFFT ? "sparkfft requires an input" : "bucket -by freq requires an input");
                 if (op.kind == OP_BUCKET && op.levels != 2) bail("only supporting two levels for now");
-                if (cs.fusable && chain_clean && !getenv("QUADRS_HIP_NO_FUSE")) {
-                    if (!run_fused(cs, op, samples->sample_rate())) run_iter_sink(*samples, op, true);
+                if (cs.fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+                    cs.cascade = !chain_clean;
+                    if (!run_fused(cs, op, *samples)) run_iter_sink(*samples, op, true);
                 } else run_iter_sink(*samples, op);
                 break;
             case OP_WRITE:

@@ -27,6 +27,7 @@
 
 #include "../../include/quadrs_hip.h"
 #include "qd_chain.h"
+#include "qd_cascade.h"
 #include "qd_registry.h"
 
 using namespace qd;
@@ -676,6 +677,7 @@ constexpr size_t kLdsMax = 160 * 1024;
 struct RowTab {
     RowBase *d = nullptr;
     uint64_t cap = 0, row0 = 0, rows = 0, off = 0;
+    double ratio_bits = 0.0;                 // cascade tables (cascade_rowtab): the NCO ratio the rows were made for
     bool used = false;
 };
 // tables one launch context needs: the main kernel's rows and, for plans whose main kernel is not 256 threads wide,
@@ -746,6 +748,20 @@ struct qd_plan {
     size_t cmp_tmp_bytes = 0, cmp_in_bytes = 0, cmp_out_bytes = 0;
     hipEvent_t cmp_done = nullptr;
     bool cmp_used = false;
+    // cascade plans (qd_plan_create_stages, qd_cascade.h): [shift] lowpass [shift] [lowpass [shift]].  W, S, n_windows, ratio are the
+    // sink's; D = D1 D2 and T = T2 D1 + T1 are the EFFECTIVE source step and span, so that W D + T / S D (src_range, shards, host chunks)
+    // are the source figures of a window
+    bool casc = false;
+    uint32_t c_D1 = 1, c_T1 = 0, c_D2 = 1, c_T2 = 0, c_n2 = 0, c_M = 0, c_flags = 0, c_inter = 0, c_src = 0;
+    double c_ratio[3] = {0, 0, 0};
+    uint64_t c_complete = 0;              // leading windows whose read_exact_at succeeds (qd_plan_complete_windows)
+    size_t c_lds = 0;
+    int c_wg_per_cu = 1;
+    float *c_h1 = nullptr, *c_h2 = nullptr;
+    double2 *c_jtab = nullptr;
+    // the stage list the plan was made from (qd_plan_create_stages; routed plans too) and each lowpass stage's taps
+    std::vector<qd_stage> stages;
+    std::vector<std::vector<float>> stage_taps;
     // sharded plans (options.n_shards > 1): one child plan per shard, created on that shard's device
     std::vector<qd_plan *> shards;
     std::vector<qd_shard_info> shard_info;
@@ -876,9 +892,84 @@ int launch_spark_phases(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t s
     return QD_OK;
 }
 
+// windows [first_window, +n_windows) of a cascade plan (qd_cascade.h); the caller has clipped them to the complete windows
+// one NCO's row table of a cascade (kCascadeRow-sample rows of its own stage's index) covering samples [n_lo, n_hi), enqueued on
+// `st` behind every earlier reader (the caller has ordered `st` behind the launch context's previous launch)
+int cascade_rowtab(RowTab *t, double ratio, uint64_t n_lo, uint64_t n_hi, hipStream_t st) {
+    const uint64_t r_lo = n_lo / kCascadeRow, r_hi = (n_hi + kCascadeRow - 1) / kCascadeRow;
+    if (t->d && r_lo >= t->row0 && r_hi <= t->row0 + t->rows && t->ratio_bits == ratio) return QD_OK;
+    const uint64_t rows = r_hi - r_lo;
+    if (rows > t->cap) {
+        if (t->d) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(t->d)); t->d = nullptr; t->cap = 0; }
+        const uint64_t cap = rows + rows / 8 + 16;
+        HIPCHK(hipMalloc(&t->d, cap * sizeof(RowBase)));
+        t->cap = cap;
+    }
+    t->row0 = r_lo; t->rows = rows; t->used = true; t->off = 0; t->ratio_bits = ratio;
+    hipLaunchKernelGGL(k_rowtab, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, ratio, kCascadeRow, r_lo, rows, (uint64_t)0, t->d);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+
+int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                   uint64_t out_window0, void *out_d, hipStream_t st) {
+    const uint64_t need0 = first_window * p->S * p->D, need1 = (first_window + n_windows - 1) * p->S * p->D + (uint64_t)p->W * p->D + p->T;
+    if (need0 < src_first || need1 > src_first + src_count)
+        return fail(QD_ERR_INVALID, "src slab [%llu,+%llu) does not cover samples [%llu,%llu) needed by windows [%llu,+%llu)",
+                    (unsigned long long)src_first, (unsigned long long)src_count, (unsigned long long)need0,
+                    (unsigned long long)need1, (unsigned long long)first_window, (unsigned long long)n_windows);
+    CascadeParams P{};
+    plan_params(p, &P.c);
+    P.c.src = static_cast<const uint8_t *>(src_d);
+    P.c.src_first = src_first; P.c.src_count = src_count;
+    P.c.first_window = first_window; P.c.n_windows = n_windows; P.c.out_window0 = out_window0;
+    P.c.out = out_d;
+    P.h1 = p->c_h1; P.h2 = p->c_h2 ? p->c_h2 : p->c_h1; P.jtab = p->c_jtab;
+    P.ratio0 = p->c_ratio[0]; P.ratio1 = p->c_ratio[1]; P.ratio2 = p->c_ratio[2];
+    P.S = p->S;
+    P.D1 = p->c_D1; P.T1 = p->c_T1; P.D2 = p->c_D2; P.T2 = p->c_T2;
+    P.n2 = p->c_n2; P.M = p->c_M; P.inter_elems = p->c_inter; P.src_elems = p->c_src;
+    P.dmagic1 = p->c_D1 % 2 == 0 ? (uint32_t)((1ull << 32) / p->c_D1 + 1) : 0u;
+    P.dmagic2 = (p->c_flags & kCascL2) && p->c_D2 % 2 == 0 ? (uint32_t)((1ull << 32) / p->c_D2 + 1) : 0u;
+    P.phi2 = (p->c_flags & kCascL2) ? (p->c_D2 - (p->c_T2 - p->c_T2 / 2) % p->c_D2) % p->c_D2 : 0u;
+    P.flags = p->c_flags;
+    // row tables of the NCOs over this launch's range, on `st`.  One launch context (`tabs`) = one set of tables: a launch arriving
+    // on another stream waits for the context's previous launch before its k_rowtab rewrites them (see NcoTabs)
+    if (tabs->launched) HIPCHK(hipStreamWaitEvent(st, tabs->done, 0));
+    if (tabs->phase.size() < 3) tabs->phase.resize(3);
+    const uint64_t last = first_window + n_windows - 1, l2 = (p->c_flags & kCascL2) ? p->c_D2 : 1;
+    const uint64_t lo[3] = {need0, first_window * p->S * l2, first_window * p->S}, hi[3] = {need1, last * p->S * l2 + p->c_n2, last * p->S + p->W};
+    const uint32_t sflag[3] = {kCascS0, kCascS1, kCascS2};
+    for (int k = 0; k < 3; ++k) {
+        if (!(p->c_flags & sflag[k])) continue;
+        const int rc = cascade_rowtab(&tabs->phase[k], p->c_ratio[k], lo[k], hi[k], st);
+        if (rc) return rc;
+        P.rows[k] = tabs->phase[k].d; P.row0[k] = tabs->phase[k].row0;
+    }
+    const uint64_t cap = (uint64_t)p->n_cu * p->c_wg_per_cu;
+    const uint32_t grid = (uint32_t)(n_windows < cap ? n_windows : cap);
+    if (p->timing) {
+        if (!p->ev_made) { HIPCHK(hipEventCreate(&p->ev0)); HIPCHK(hipEventCreate(&p->ev1)); p->ev_made = true; }
+        HIPCHK(hipEventRecord(p->ev0, st));
+    }
+    switch (p->d.format) {
+    case QD_FMT_CF32: hipLaunchKernelGGL(k_cascade<0>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+    case QD_FMT_CS8: hipLaunchKernelGGL(k_cascade<1>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+    case QD_FMT_CU8: hipLaunchKernelGGL(k_cascade<2>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+    default: hipLaunchKernelGGL(k_cascade<3>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+    }
+    HIPCHK(hipGetLastError());
+    if (p->timing) { HIPCHK(hipEventRecord(p->ev1, st)); p->ev_recorded = true; }
+    if (!tabs->done) HIPCHK(hipEventCreateWithFlags(&tabs->done, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(tabs->done, st));
+    tabs->last_stream = st; tabs->launched = true;
+    return QD_OK;
+}
+
 int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window,
                  uint64_t n_windows, uint64_t out_window0, void *out_d, hipStream_t st) {
     if (n_windows == 0) return QD_OK;
+    if (p->casc) return launch_cascade(p, tabs, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st);
     const int fmt = p->d.format;
     const int spl = spl_of(fmt), bps = bps_of(fmt);
     uint64_t need0 = first_window * p->S * p->D;
@@ -1661,6 +1752,272 @@ int qd_plan_create_ex(const qd_chain_desc *desc, const qd_plan_options *options,
 
 int qd_plan_create(const qd_chain_desc *desc, qd_plan **out) { return qd_plan_create_ex(desc, nullptr, out); }
 
+// ------------------------------------------------------------------ stage lists (cascades)
+
+namespace {
+constexpr uint32_t kCascadeMaxInter = 8192;     // intermediate samples per window (W D2 + T2): the kernel's LDS envelope
+constexpr uint32_t kCascadeMaxSub = 8192;       // source samples per sub-tile
+constexpr uint32_t kCascadeMaxT1 = 4096;
+
+struct StageGeo {
+    bool routed = false;                        // [shift] [lowpass]: the one-stage plan
+    int s0 = -1, l1 = -1, s1 = -1, l2 = -1, s2 = -1;     // stage indexes of the cascade shape
+    uint64_t len = 0, rate = 0;                 // Samples::len() / sample_rate() the sink sees
+    std::vector<uint64_t> in_rate;              // input rate of every stage
+    uint64_t n_windows = 0, complete = 0;
+    uint32_t D1 = 1, T1 = 0, D2 = 1, T2 = 0, n2 = 0;
+    double ratio = 0.0;                         // the first shift's
+};
+
+// the reference's constructors and len() asserts, stage by stage at each stage's rate, then the shape
+int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo *g) {
+    if (!desc || (n && !st)) return fail(QD_ERR_INVALID, "desc/stages is NULL");
+    if (desc->struct_size != sizeof(qd_chain_desc)) return fail(QD_ERR_INVALID, "qd_chain_desc size mismatch");
+    const qd_chain_desc &d = *desc;
+    if (d.has_shift || d.has_lowpass) return fail(QD_ERR_INVALID, "a stage list carries the shift / lowpass stages: has_shift = has_lowpass = 0");
+    if (n > QD_MAX_STAGES) return fail(QD_ERR_INVALID, "%zu stages > QD_MAX_STAGES (%d)", n, QD_MAX_STAGES);
+    if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
+    if (d.epilogue < 0 || d.epilogue > 3) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
+    if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
+    if (!is_pow2(d.width))
+        return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
+    if (d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "width too large");
+    if (d.stride == 0) return fail(QD_ERR_INVALID, "stride 0 never terminates in the reference (src/fft.rs:65)");
+    if (d.stride > 0xffffffffull) return fail(QD_ERR_UNSUPPORTED, "stride too large");
+    uint64_t len = d.n_samples, rate = d.sample_rate;
+    g->in_rate.assign(n, 0);
+    std::string shape;
+    for (size_t i = 0; i < n; ++i) {
+        const qd_stage &q = st[i];
+        g->in_rate[i] = rate;
+        if (q.kind == QD_STAGE_SHIFT) {
+            const int64_t af = q.shift_hz < 0 ? -q.shift_hz : q.shift_hz;
+            if (rate == 0 || !(af < (int64_t)(rate / 2)))
+                return fail(QD_ERR_PANIC, "stage %zu: frequency must be under half the sample rate %llu (src/shift.rs:20-24)", i, (unsigned long long)rate);
+            if (g->ratio == 0.0) g->ratio = qd_shift_ratio(q.shift_hz, rate);
+            shape += 'S';
+        } else if (q.kind == QD_STAGE_LOWPASS) {
+            if (q.decimate == 0) return fail(QD_ERR_PANIC, "stage %zu: decimate 0 divides by zero (src/filter.rs:47)", i);
+            if (q.taps < 2) return fail(QD_ERR_PANIC, "stage %zu: lowpass size < 2 underflows (src/filter.rs:74)", i);
+            if (q.taps > 65536 || q.decimate > 65536) return fail(QD_ERR_UNSUPPORTED, "stage %zu: taps/decimate too large", i);
+            if (len < q.taps) return fail(QD_ERR_PANIC, "stage %zu: inner.len() %llu < filter.len() %llu (src/filter.rs:46)", i, (unsigned long long)len,
+                                          (unsigned long long)q.taps);
+            len = 1 + (len - q.taps) / q.decimate;     // LowPass::len, src/filter.rs:47
+            rate = rate / q.decimate;                  // src/filter.rs:51
+            shape += 'L';
+        } else {
+            return fail(QD_ERR_INVALID, "stage %zu: unknown kind %d", i, q.kind);
+        }
+    }
+    if (d.epilogue != QD_EPI_CF32_BLOCKS && len < d.width)
+        return fail(QD_ERR_PANIC, "len %llu < width %llu: u64 underflow at src/fft.rs:28,86", (unsigned long long)len, (unsigned long long)d.width);
+    g->len = len; g->rate = rate;
+    g->routed = shape.empty() || shape == "S" || shape == "L" || shape == "SL";
+    size_t k = 0;
+    auto take = [&](char c) { if (k < shape.size() && shape[k] == c) return (int)k++; return -1; };
+    g->s0 = take('S'); g->l1 = take('L'); g->s1 = take('S');
+    if (g->l1 >= 0) { g->l2 = take('L'); if (g->l2 >= 0) g->s2 = take('S'); }
+    if (g->routed) return QD_OK;
+    if (g->l1 < 0 || k != shape.size())
+        return fail(QD_ERR_UNSUPPORTED, "stage list %s is not a fused shape ([shift] lowpass [shift] [lowpass [shift]]): the caller runs it stage by stage",
+                    shape.c_str());
+    if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "write (QD_EPI_CF32_BLOCKS) after a cascade is not built");
+    g->D1 = (uint32_t)st[g->l1].decimate; g->T1 = (uint32_t)st[g->l1].taps;
+    if (g->l2 >= 0) { g->D2 = (uint32_t)st[g->l2].decimate; g->T2 = (uint32_t)st[g->l2].taps; }
+    const uint64_t n2 = g->l2 >= 0 ? d.width * g->D2 + g->T2 : d.width;
+    if (n2 > kCascadeMaxInter)
+        return fail(QD_ERR_UNSUPPORTED, "cascade: a window's intermediate block of %llu samples exceeds the kernel's LDS budget (%u)", (unsigned long long)n2,
+                    kCascadeMaxInter);
+    if (g->T1 > kCascadeMaxT1) return fail(QD_ERR_UNSUPPORTED, "cascade: a first stage of %u taps exceeds the kernel's sub-tile (%u taps)", g->T1, kCascadeMaxT1);
+    g->n2 = (uint32_t)n2;
+    const uint64_t lim = len - d.width;
+    g->n_windows = d.epilogue == QD_EPI_BUCKET2_U8 ? lim / d.stride : (lim == 0 ? 0 : (lim - 1) / d.stride + 1);   // src/fft.rs:86 / :28,65
+    // window w reads source samples [w S D2 D1, + n2 D1 + T1): complete while they exist (src/samples.rs:17-27)
+    const uint64_t span = n2 * g->D1 + g->T1, step = d.stride * g->D2 * g->D1;
+    const uint64_t fit = d.n_samples >= span ? (d.n_samples - span) / step + 1 : 0;
+    g->complete = fit < g->n_windows ? fit : g->n_windows;
+    return QD_OK;
+}
+
+// the device half of a cascade plan: tables, taps, launch figures
+int cascade_init(qd_plan *p, const StageGeo &g, const qd_stage *st) {
+    const qd_chain_desc &d = p->d;
+    (void)hipGetDevice(&p->device);
+    p->casc = true;
+    p->W = (uint32_t)d.width; p->logW = ilog2(d.width); p->S = (uint32_t)d.stride;
+    p->c_D1 = g.D1; p->c_T1 = g.T1; p->c_D2 = g.D2; p->c_T2 = g.T2; p->c_n2 = g.n2;
+    p->D = g.D1 * g.D2; p->T = g.T2 * g.D1 + g.T1;
+    p->dec_len = g.len; p->out_rate = g.rate; p->n_windows = g.n_windows; p->c_complete = g.complete;
+    p->ratio = g.ratio;
+    p->geo.G = 1;
+    p->c_flags = (g.s0 >= 0 ? kCascS0 : 0) | (g.s1 >= 0 ? kCascS1 : 0) | (g.l2 >= 0 ? kCascL2 : 0) | (g.s2 >= 0 ? kCascS2 : 0);
+    const int sidx[3] = {g.s0, g.s1, g.s2};
+    for (int k = 0; k < 3; ++k) p->c_ratio[k] = sidx[k] >= 0 ? qd_shift_ratio(st[sidx[k]].shift_hz, g.in_rate[sidx[k]]) : 0.0;
+    // LDS: inter block | source sub-tile (>= the FFT buffer).  Sub-tiles of up to 512 FIR1 outputs.
+    const bool l2 = g.l2 >= 0;
+    auto lds_of = [&](uint32_t M, uint32_t *inter, uint32_t *src) {
+        const uint64_t n2 = g.n2, ns = (uint64_t)(M - 1) * g.D1 + g.T1;
+        uint64_t ie = n2 + ((l2 && g.D2 % 2 == 0) ? n2 / g.D2 + 1 : 0) + 1;
+        uint64_t se = ns + (g.D1 % 2 == 0 ? ns / g.D1 + 1 : 0) + 1;
+        if (se < p->W) se = p->W;
+        ie = (ie + 3) & ~3ull; se = (se + 3) & ~3ull;         // row bases on a 32-byte boundary
+        *inter = (uint32_t)ie; *src = (uint32_t)se;
+        return (size_t)((ie + se) * 8);
+    };
+    uint32_t M = g.n2 < 512 ? g.n2 : 512;
+    while (M > 1 && ((uint64_t)(M - 1) * g.D1 + g.T1 > kCascadeMaxSub || lds_of(M, &p->c_inter, &p->c_src) > kLdsMax)) M = (M + 1) / 2;
+    p->c_M = M;
+    p->c_lds = lds_of(M, &p->c_inter, &p->c_src);
+    if (p->c_lds > kLdsMax || (uint64_t)(M - 1) * g.D1 + g.T1 > kCascadeMaxSub)
+        return fail(QD_ERR_UNSUPPORTED, "cascade: %zu bytes of LDS per workgroup exceed the %zu available", p->c_lds, kLdsMax);
+    int by_lds = (int)(kLdsMax / p->c_lds);
+    p->c_wg_per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->n_cu = prop.multiProcessorCount;
+    for (const void *f : {reinterpret_cast<const void *>(k_cascade<0>), reinterpret_cast<const void *>(k_cascade<1>),
+                          reinterpret_cast<const void *>(k_cascade<2>), reinterpret_cast<const void *>(k_cascade<3>)})
+        if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax); e != hipSuccess)
+            return fail(QD_ERR_HIP, "hipFuncSetAttribute(k_cascade, max dynamic LDS %zu): %s", kLdsMax, hipGetErrorString(e));
+    p->fft = fft_layout(d.width);
+    if (!p->fft.tw.empty()) {
+        HIPCHK(hipMalloc(&p->tw_d, p->fft.tw.size() * sizeof(float2)));
+        HIPCHK(hipMemcpy(p->tw_d, p->fft.tw.data(), p->fft.tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    }
+    p->taps_h = p->stage_taps[g.l1];
+    HIPCHK(hipMalloc(&p->c_h1, g.T1 * sizeof(float)));
+    HIPCHK(hipMemcpy(p->c_h1, p->stage_taps[g.l1].data(), g.T1 * sizeof(float), hipMemcpyHostToDevice));
+    if (l2) {
+        HIPCHK(hipMalloc(&p->c_h2, g.T2 * sizeof(float)));
+        HIPCHK(hipMemcpy(p->c_h2, p->stage_taps[g.l2].data(), g.T2 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMalloc(&p->c_jtab, 3 * kCascadeRow * sizeof(double2)));
+    HIPCHK(hipMemset(p->c_jtab, 0, 3 * kCascadeRow * sizeof(double2)));
+    for (int k = 0; k < 3; ++k)
+        if (sidx[k] >= 0) {
+            hipLaunchKernelGGL(k_jtab, dim3((kCascadeRow + 255) / 256), dim3(256), 0, 0, p->c_ratio[k], kCascadeRow, p->c_jtab + k * kCascadeRow);
+            HIPCHK(hipGetLastError());
+        }
+    HIPCHK(hipDeviceSynchronize());
+    return QD_OK;
+}
+
+void stage_taps_of(const qd_stage *st, size_t n, const StageGeo &g, std::vector<std::vector<float>> *t) {
+    t->assign(n, {});
+    for (size_t i = 0; i < n; ++i)
+        if (st[i].kind == QD_STAGE_LOWPASS) { (*t)[i].resize(st[i].taps); design_taps(st[i].lowpass_hz, g.in_rate[i], st[i].taps, (*t)[i].data()); }
+}
+}  // namespace
+
+int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, qd_plan_info *info, uint64_t *complete) {
+    if (!info || !complete) return fail(QD_ERR_INVALID, "info/complete is NULL");
+    StageGeo g;
+    int rc = stages_geo(desc, stages, n_stages, &g);
+    if (rc) return rc;
+    const qd_chain_desc &d = *desc;
+    if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "qd_stages_geometry: the write sink's blocks are the one-stage plan's (qd_plan_get_info)");
+    if (g.routed) {                  // the one-stage plan's figures: a single lowpass never fails a read
+        uint64_t D = 1, T = 0;
+        if (g.l1 >= 0) { D = stages[g.l1].decimate; T = stages[g.l1].taps; }
+        g.D1 = (uint32_t)D; g.T1 = (uint32_t)T;
+        const uint64_t lim = g.len - d.width;
+        g.n_windows = d.epilogue == QD_EPI_BUCKET2_U8 ? lim / d.stride : (lim == 0 ? 0 : (lim - 1) / d.stride + 1);
+        g.complete = g.n_windows;
+        g.n2 = (uint32_t)d.width;
+    }
+    memset(info, 0, sizeof *info);
+    info->n_windows = g.n_windows;
+    info->decimated_len = g.len;
+    info->out_sample_rate = g.rate;
+    info->out_bytes_per_window = d.epilogue == QD_EPI_NORMS_F32 ? d.width * 4 : (d.epilogue == QD_EPI_GLYPH_U8 ? d.width : 1);
+    info->raw_per_window = (uint64_t)g.n2 * g.D1 + g.T1;
+    info->raw_step = d.stride * g.D2 * g.D1;
+    info->ratio = g.ratio;
+    *complete = g.complete;
+    return QD_OK;
+}
+
+namespace {
+int create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, qd_plan **out) {
+    if (!out) return fail(QD_ERR_INVALID, "plan is NULL");
+    StageGeo g;
+    int rc = stages_geo(desc, stages, n_stages, &g);
+    if (rc) return rc;
+    if (g.routed) {                  // the one-stage description holds it: today's plan, kernels and bytes
+        qd_chain_desc d = *desc;
+        if (g.s0 >= 0) { d.has_shift = 1; d.shift_hz = stages[g.s0].shift_hz; }
+        if (g.l1 >= 0) { d.has_lowpass = 1; d.lowpass_hz = stages[g.l1].lowpass_hz; d.decimate = stages[g.l1].decimate; d.taps = stages[g.l1].taps; }
+        qd_plan *p = nullptr;
+        rc = qd_plan_create_ex(&d, options, &p);
+        if (rc) return rc;
+        p->stages.assign(stages, stages + n_stages);
+        stage_taps_of(stages, n_stages, g, &p->stage_taps);
+        *out = p;
+        return QD_OK;
+    }
+    qd_plan_options opt{};
+    opt.struct_size = sizeof opt;
+    if (options) {
+        if (options->struct_size != sizeof(qd_plan_options)) return fail(QD_ERR_INVALID, "qd_plan_options size mismatch");
+        opt = *options;
+        if (opt.kernel_policy < QD_KERNEL_AUTO || opt.kernel_policy > QD_KERNEL_NO_PLAN_TIME) return fail(QD_ERR_INVALID, "unknown kernel_policy %d", opt.kernel_policy);
+        if (opt.nco_order < 0 || opt.nco_order > 2) return fail(QD_ERR_INVALID, "nco_order must be 0, 1 or 2");
+        if (opt.copy_threads > 64) return fail(QD_ERR_INVALID, "copy_threads > 64");
+        if (opt.chunk_bytes && (opt.chunk_bytes < (1u << 16) || opt.chunk_bytes > (1ull << 34))) return fail(QD_ERR_INVALID, "chunk_bytes outside [64 KiB, 16 GiB]");
+        if (opt.n_shards > QD_MAX_SHARDS) return fail(QD_ERR_INVALID, "n_shards > %d", QD_MAX_SHARDS);
+    }
+    if (opt.n_shards > 1) {
+        int n_dev = 0;
+        HIPCHK(hipGetDeviceCount(&n_dev));
+        for (uint32_t s = 0; s < opt.n_shards; ++s)
+            if (opt.shard_device[s] < 0 || opt.shard_device[s] >= n_dev)
+                return fail(QD_ERR_INVALID, "shard %u: device %d does not exist (%d visible)", s, opt.shard_device[s], n_dev);
+    }
+    qd_plan *p = new qd_plan();
+    p->d = *desc;
+    p->opt = opt;
+    p->stages.assign(stages, stages + n_stages);
+    stage_taps_of(stages, n_stages, g, &p->stage_taps);
+    rc = cascade_init(p, g, stages);
+    if (rc) { qd_plan_destroy(p); return rc; }
+    const uint32_t n_shards = opt.n_shards > 1 ? opt.n_shards : 1;
+    partition_windows(p->n_windows, n_shards, (uint64_t)p->S * p->D, (uint64_t)p->W * p->D + p->T, 1, &p->shard_info);
+    for (uint32_t s = 0; s < n_shards; ++s) p->shard_info[s].device = n_shards > 1 ? opt.shard_device[s] : p->device;
+    if (n_shards > 1) {
+        qd_plan_options copt = opt;
+        copt.n_shards = 0;
+        for (uint32_t s = 0; s < n_shards && rc == QD_OK; ++s) {
+            DeviceGuard guard(opt.shard_device[s]);
+            qd_plan *c = nullptr;
+            rc = create_stages(desc, stages, n_stages, &copt, &c);
+            if (rc == QD_OK) p->shards.push_back(c);
+        }
+        if (rc) { qd_plan_destroy(p); return rc; }
+    }
+    *out = p;
+    return QD_OK;
+}
+}  // namespace
+
+int qd_plan_create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, qd_plan **plan) {
+    return create_stages(desc, stages, n_stages, options, plan);
+}
+
+int qd_plan_get_stage_taps(const qd_plan *p, uint32_t stage, float *taps, size_t cap) {
+    if (!p || !taps) return fail(QD_ERR_INVALID, "plan/taps is NULL");
+    if (stage >= p->stages.size() || p->stages[stage].kind != QD_STAGE_LOWPASS)
+        return fail(QD_ERR_INVALID, "stage %u is not a lowpass stage of the plan's stage list (%zu stages)", stage, p->stages.size());
+    const std::vector<float> &t = p->stage_taps[stage];
+    if (cap < t.size()) return fail(QD_ERR_INVALID, "taps buffer too small");
+    memcpy(taps, t.data(), t.size() * sizeof(float));
+    return QD_OK;
+}
+
+int qd_plan_complete_windows(const qd_plan *p, uint64_t *n) {
+    if (!p || !n) return fail(QD_ERR_INVALID, "plan/n is NULL");
+    *n = p->casc ? p->c_complete : p->n_windows;
+    return QD_OK;
+}
+
 int qd_plan_destroy(qd_plan *p) {
     if (!p) return QD_OK;
     for (qd_plan *c : p->shards) (void)qd_plan_destroy(c);
@@ -1673,6 +2030,7 @@ int qd_plan_destroy(qd_plan *p) {
     for (void *q : {p->cmp_tmp, p->cmp_in, p->cmp_out}) if (q) (void)hipFree(q);
     if (p->cmp_done) (void)hipEventDestroy(p->cmp_done);
     free_streaming(p);
+    for (void *q : {(void *)p->c_h1, (void *)p->c_h2, (void *)p->c_jtab}) if (q) (void)hipFree(q);
     if (p->taps_d) (void)hipFree(p->taps_d);
     if (p->tw_d) (void)hipFree(p->tw_d);
     if (p->jtab_d) (void)hipFree(p->jtab_d);
@@ -1701,6 +2059,10 @@ int qd_plan_get_info(const qd_plan *p, qd_plan_info *info) {
         info->threads = ia.threads; info->lds_bytes = ia.lds_bytes; info->kernel_kind = ia.kernel_kind; info->kernel_flags = ia.kernel_flags;
         return QD_OK;
     }
+    if (p->casc) {                                    // cascade plan: runtime-geometry kernel, exact arithmetic whatever the mode
+        info->threads = kCascadeThreads; info->lds_bytes = (uint32_t)p->c_lds;
+        return QD_OK;
+    }
     info->threads = (uint32_t)p->launch_nt;
     info->lds_bytes = (uint32_t)(p->geo.lds_main ? p->geo.lds_main : p->geo.lds_bytes);
     info->kernel_kind = p->jit_fn ? 2u : ((p->fixed || p->spark) ? 1u : 0u);
@@ -1715,6 +2077,11 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
         char a[256], b[256];
         (void)qd_plan_kernel_name(p->cmp_a, a, sizeof a); (void)qd_plan_kernel_name(p->cmp_b, b, sizeof b);
         snprintf(buf, cap, "two stages: %s | %s", a, b);
+        return QD_OK;
+    }
+    if (p->casc) {
+        snprintf(buf, cap, "qd::k_cascade<%d>(D1 %u, T1 %u, D2 %u, T2 %u, W %u, S %u, shifts %u%u%u), %u threads, generic", p->d.format, p->c_D1, p->c_T1,
+                 p->c_D2, p->c_T2, p->W, p->S, p->c_flags & kCascS0 ? 1 : 0, p->c_flags & kCascS1 ? 1 : 0, p->c_flags & kCascS2 ? 1 : 0, kCascadeThreads);
         return QD_OK;
     }
     const int fmt = p->d.format;
@@ -1972,6 +2339,15 @@ int qd_plan_run(qd_plan *p, const void *src, int src_mem, uint64_t src_first, ui
         return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
                     (unsigned long long)n_windows, (unsigned long long)p->n_windows);
     if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    if (p->casc && first_window + n_windows > p->c_complete) {
+        // a cascade's last windows may fail read_exact_at (LowPass::len over-reports, src/filter.rs:45-48): every complete window
+        // of the range is written, then the run reports the short read
+        const uint64_t done = first_window < p->c_complete ? p->c_complete - first_window : 0;
+        int rc = done ? qd_plan_run(p, src, src_mem, src_first, src_count, first_window, done, out, out_mem, stream) : QD_OK;
+        if (rc) return rc;
+        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
+                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
+    }
     std::lock_guard<std::mutex> lock(p->mu);
     DeviceGuard guard(p->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2031,6 +2407,7 @@ int qd_plan_run_sharded(qd_plan *p, const void *src, int src_mem, void *out, int
 int qd_plan_run_sharded_device(qd_plan *p, void *const *slabs, void *const *outs, int sync) {
     if (!p || !slabs || !outs) return fail(QD_ERR_INVALID, "NULL argument");
     if (p->cmp_a) return fail(QD_ERR_UNSUPPORTED, "a two-stage plan (window larger than the LDS tile) has no pre-split device path");
+    if (p->casc) return fail(QD_ERR_UNSUPPORTED, "a cascade plan (qd_plan_create_stages) has no pre-split device path");
     const size_t n = p->shard_info.size();
     const int bps = bps_of(p->d.format);
     std::vector<qd_plan *> plans(n, p);

@@ -170,11 +170,50 @@ class PinnedBuffer:
             pass
 
 
+def stage_array(stages):
+    """[("shift", f), ("lowpass", (frequency, decimate, size)), ...] (source to sink) -> a ctypes qd_stage array"""
+    arr = (_ffi.Stage * max(len(stages), 1))()
+    for i, (kind, arg) in enumerate(stages):
+        if kind == "shift":
+            arr[i].kind, arr[i].shift_hz = _ffi.STAGE_SHIFT, int(arg)
+        elif kind == "lowpass":
+            freq, decimate, size = arg
+            arr[i].kind, arr[i].lowpass_hz, arr[i].decimate, arr[i].taps = _ffi.STAGE_LOWPASS, int(freq), int(decimate), int(size)
+        else:
+            raise ValueError(f"unknown stage kind {kind!r}")
+    return arr
+
+
+def _sink_desc(fmt, sample_rate, n_samples, width, stride, epilogue, rng, mode):
+    d = _ffi.ChainDesc()
+    d.struct_size = C.sizeof(_ffi.ChainDesc)
+    d.format, d.sample_rate, d.n_samples = fmt, sample_rate, n_samples
+    d.width = width
+    d.stride = width if stride is None else stride
+    d.epilogue, d.mode = epilogue, mode
+    if rng is not None:
+        d.has_range, d.range_min, d.range_max = 1, rng[0], rng[1]
+    return d
+
+
+def stages_geometry(fmt, sample_rate, n_samples, stages, width=128, stride=None, epilogue=_ffi.EPI_NORMS_F32):
+    """qd_stages_geometry: the figures of the plan a stage list makes, from host arithmetic alone (no device).
+    Returns (PlanInfo, complete_windows)."""
+    d = _sink_desc(fmt, sample_rate, n_samples, width, stride, epilogue, None, _ffi.MODE_EXACT)
+    info, done = _ffi.PlanInfo(), C.c_uint64()
+    check(lib().qd_stages_geometry(C.byref(d), stage_array(stages), len(stages), C.byref(info), C.byref(done)))
+    return info, done.value
+
+
 class Plan:
-    """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175)."""
+    """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
+    stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
 
     def __init__(self, fmt, sample_rate, n_samples, shift_hz=None, lowpass=None, width=128, stride=None,
-                 epilogue=_ffi.EPI_NORMS_F32, rng=None, options=None, mode=_ffi.MODE_EXACT, **option_kw):
+                 epilogue=_ffi.EPI_NORMS_F32, rng=None, options=None, mode=_ffi.MODE_EXACT, stages=None, **option_kw):
+        if stages is not None and (shift_hz is not None or lowpass is not None):
+            raise ValueError("stages= describes the whole chain: it does not combine with shift_hz= / lowpass=")
+        self.stages = list(stages) if stages is not None else None
         d = _ffi.ChainDesc()
         d.struct_size = C.sizeof(_ffi.ChainDesc)
         d.format = fmt
@@ -203,11 +242,15 @@ class Plan:
             else:
                 kw = dict(option_kw)
             options = plan_options(**kw)
-        rc = lib().qd_plan_create_ex(C.byref(d), C.byref(options), C.byref(self._h))
+        def create(opts):
+            if self.stages is None:
+                return lib().qd_plan_create_ex(C.byref(d), C.byref(opts), C.byref(self._h))
+            return lib().qd_plan_create_stages(C.byref(d), stage_array(self.stages), len(self.stages), C.byref(opts), C.byref(self._h))
+        rc = create(options)
         if rc == _ffi.ERR_INVALID and hint_from_env and b"tile_hint" in lib().qd_last_error():
             kw.pop("tile_hint")                      # a sweep's tiling that does not fit this chain: the library's own choice
             options = plan_options(**kw)
-            rc = lib().qd_plan_create_ex(C.byref(d), C.byref(options), C.byref(self._h))
+            rc = create(options)
         check(rc)
         self.options = options
         info = _ffi.PlanInfo()
@@ -233,6 +276,19 @@ class Plan:
         if out.size:
             check(lib().qd_plan_get_taps(self._h, _np_ptr(out), out.size))
         return out
+
+    def stage_taps(self, stage):
+        """taps of lowpass stage `stage` (index into stages=)"""
+        kind, arg = self.stages[stage]
+        out = np.zeros(int(arg[2]) if kind == "lowpass" else 1, dtype=np.float32)
+        check(lib().qd_plan_get_stage_taps(self._h, stage, _np_ptr(out), out.size))
+        return out
+
+    def complete_windows(self):
+        """leading windows whose read_exact_at succeeds (qd_plan_complete_windows)"""
+        n = C.c_uint64()
+        check(lib().qd_plan_complete_windows(self._h, C.byref(n)))
+        return n.value
 
     def kernel_name(self):
         """the main kernel's name as rocprofv3 lists it (qd_plan_kernel_name)"""
