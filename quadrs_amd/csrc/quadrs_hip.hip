@@ -1787,6 +1787,7 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     uint64_t len = d.n_samples, rate = d.sample_rate;
     g->in_rate.assign(n, 0);
     std::string shape;
+    bool seen_shift = false;
     for (size_t i = 0; i < n; ++i) {
         const qd_stage &q = st[i];
         g->in_rate[i] = rate;
@@ -1794,7 +1795,8 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
             const int64_t af = q.shift_hz < 0 ? -q.shift_hz : q.shift_hz;
             if (rate == 0 || !(af < (int64_t)(rate / 2)))
                 return fail(QD_ERR_PANIC, "stage %zu: frequency must be under half the sample rate %llu (src/shift.rs:20-24)", i, (unsigned long long)rate);
-            if (g->ratio == 0.0) g->ratio = qd_shift_ratio(q.shift_hz, rate);
+            if (!seen_shift) g->ratio = qd_shift_ratio(q.shift_hz, rate);     // the FIRST shift's, whatever its value (0 Hz included)
+            seen_shift = true;
             shape += 'S';
         } else if (q.kind == QD_STAGE_LOWPASS) {
             if (q.decimate == 0) return fail(QD_ERR_PANIC, "stage %zu: decimate 0 divides by zero (src/filter.rs:47)", i);
@@ -2080,8 +2082,9 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
         return QD_OK;
     }
     if (p->casc) {
-        snprintf(buf, cap, "qd::k_cascade<%d>(D1 %u, T1 %u, D2 %u, T2 %u, W %u, S %u, shifts %u%u%u), %u threads, generic", p->d.format, p->c_D1, p->c_T1,
-                 p->c_D2, p->c_T2, p->W, p->S, p->c_flags & kCascS0 ? 1 : 0, p->c_flags & kCascS1 ? 1 : 0, p->c_flags & kCascS2 ? 1 : 0, kCascadeThreads);
+        snprintf(buf, cap, "qd::k_cascade<%d>(D1 %u, T1 %u, D2 %u, T2 %u, W %u, S %u, shifts %u%u%u, M %u), %u threads, generic", p->d.format, p->c_D1, p->c_T1,
+                 p->c_D2, p->c_T2, p->W, p->S, p->c_flags & kCascS0 ? 1 : 0, p->c_flags & kCascS1 ? 1 : 0, p->c_flags & kCascS2 ? 1 : 0, p->c_M,
+                 kCascadeThreads);
         return QD_OK;
     }
     const int fmt = p->d.format;

@@ -338,11 +338,12 @@ class Plan:
         check(lib().qd_plan_shard_info(self._h, g, C.byref(si)))
         return si
 
-    def run_sharded_host(self, data, pinned=False):
-        """qd_plan_run_sharded: the whole stream from one host buffer over the plan's shards (one thread per shard)."""
+    def run_sharded_host(self, data, pinned=False, out=None):
+        """qd_plan_run_sharded: the whole stream from one host buffer over the plan's shards (one thread per shard).
+        out: an optional host array to write into (a run that ends in QD_ERR_SHORT leaves its complete windows there)."""
         buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1))
         shape, dt = self._out_shape_dtype(self.n_windows)
-        out = np.zeros(shape, dtype=dt)
+        out = np.zeros(shape, dtype=dt) if out is None else out.view(dt)[:int(np.prod(shape))].reshape(shape)
         check(lib().qd_plan_run_sharded(self._h, _np_ptr(buf), _ffi.MEM_HOST_PINNED if pinned else MEM_HOST, _np_ptr(out), MEM_HOST))
         return out
 

@@ -23,7 +23,7 @@ import os
 import numpy as np
 import pytest
 
-from util import README_OOK, bits_equal, complex_ulp_err, ook_pipeline, ulp_diff, ulp_of
+from util import README_OOK, bits_equal, codes_edge_ok, complex_ulp_err, ook_pipeline, ulp_diff, ulp_of
 
 pytestmark = pytest.mark.gpu
 
@@ -66,15 +66,9 @@ def assert_codes_edge_aware(ref_codes, got_codes, ref_norms, rmin, rmax, what, k
     """Glyph codes (src/fft.rs:54-60) must equal the oracle's; a cell may differ only where the oracle's own norm lies
     within k ulp of one of the nine decision thresholds min + i*(max-min)/7."""
     assert ref_codes.shape == got_codes.shape
-    diff = ref_codes != got_codes
-    step = (np.float32(rmax) - np.float32(rmin)) / np.float32(7.0)
-    edges = np.array([np.float32(rmin) + np.float32(i) * step for i in range(8)] + [np.float32(rmax)], dtype=np.float32)
-    nd = ref_norms[diff].astype(np.float64)
-    near = np.zeros(nd.shape, dtype=bool)
-    for e in edges:
-        near |= np.abs(nd - float(e)) <= k_ulp * float(np.spacing(np.float32(e)))
-    record_observed(what, cells=int(ref_codes.size), differing=int(diff.sum()), differing_near_threshold=int(near.sum()))
-    assert near.all(), f"{what}: {int((~near).sum())} glyph cells differ away from any threshold"
+    ok, differing, near = codes_edge_ok(ref_codes, got_codes, ref_norms, rmin, rmax, k_ulp)
+    record_observed(what, cells=int(ref_codes.size), differing=differing, differing_near_threshold=near)
+    assert ok, f"{what}: {differing - near} glyph cells differ away from any threshold"
 
 
 # ------------------------------------------------------------------ A1 unpack

@@ -301,3 +301,175 @@ def full_size_census(Q, O, bench, name):
             if f is not None and first is None:
                 first = f
     return total, int(p.info.kernel_kind), nw, nb, worst, first, t_gpu, time.perf_counter() - t0, cores
+
+
+def casc_fir_class(D):
+    """the FIR class of a cascade decimation (qd_cascade.h casc_fir_class): 0 odd D, 2, 4, 8 a multiple of 8, -1 any other even D"""
+    return 0 if D & 1 else (2 if D == 2 else (4 if D == 4 else (8 if D % 8 == 0 else -1)))
+
+
+def codes_edge_ok(ref_codes, got_codes, ref_norms, rmin, rmax, k_ulp=4):
+    """glyph codes (src/fft.rs:54-60) equal the oracle's except where the oracle's own norm lies within k ulp of one of the nine
+    decision thresholds min + i*(max-min)/7.  Returns (ok, differing cells, of them near a threshold)."""
+    diff = ref_codes != got_codes
+    step = (np.float32(rmax) - np.float32(rmin)) / np.float32(7.0)
+    edges = np.array([np.float32(rmin) + np.float32(i) * step for i in range(8)] + [np.float32(rmax)], dtype=np.float32)
+    nd = ref_norms[diff].astype(np.float64)
+    near = np.zeros(nd.shape, dtype=bool)
+    for e in edges:
+        near |= np.abs(nd - float(e)) <= k_ulp * float(np.spacing(np.float32(e)))
+    return bool(near.all()), int(diff.sum()), int(near.sum())
+
+
+def bucket_digits_ok(ref_norms, got_digits):
+    """bucket digits (src/fft.rs:95-97: two sequential f32 half sums of the norms in natural bin order) against the oracle's norms
+    of the same windows; a digit may differ only where the two sums tie within 8 ulp"""
+    W = ref_norms.shape[1]
+    nat = np.roll(ref_norms, W // 2, axis=1)                       # the sparkfft rows' fftshift undone
+    first = np.cumsum(nat[:, : W // 2], axis=1, dtype=np.float32)[:, -1] if W > 1 else np.zeros(len(nat), np.float32)
+    second = np.cumsum(nat[:, W // 2:], axis=1, dtype=np.float32)[:, -1]
+    want = np.where(first < second, 0, 1).astype(np.uint8)
+    tie = np.abs(first.astype(np.float64) - second) <= 8 * np.spacing(np.maximum(first, second)).astype(np.float64)
+    return not ((want != got_digits) & ~tie).any()
+
+
+def fuzz_cascade_shapes(Q, n_shapes, seed, oracle, log=None, cov=None, observed=None):
+    """Random cascaded stage lists (qd_plan_create_stages, k_cascade: every fused shape [S] L [S] [L [S]], every format and sink,
+    D 1 ... 32 of every FIR class, T not a multiple of 8, W 1 ... 8192 up to the n2 <= 8192 envelope, any stride, sample rates the
+    decimations do not divide, shifts of 0 and +-(rate/2 - 1) at each stage's rate) against the CPU oracle's nested Samples on the
+    first and the last 16 complete windows: norms bit-exact without a shift, within 1 ulp of the window maximum with one (the
+    aggregate bit-exact fraction goes to `observed`); glyph codes edge-aware, bucket digits up to ties.  Each shape also runs a
+    window sub-range from an offset slab and a 64 KiB-chunk host run, which must give the whole run's bytes.
+    `cov` (a dict) collects the FIR classes, T % 8 != 0, the sub-tile sizes (M, min(n2, 512)) and the shapes reached.  Returns (checked, mismatching descriptions)."""
+    import re
+    rng = np.random.default_rng(seed)
+    checked, bad = 0, []
+    cov = {} if cov is None else cov
+    for key in ("cls1", "cls2", "t1_mod8", "t2_mod8", "M", "shapes", "short"):
+        cov.setdefault(key, set() if key != "short" else 0)
+    observed = {} if observed is None else observed
+    observed.setdefault("bins", 0)
+    observed.setdefault("exact", 0)
+    observed.setdefault("worst_ulp", 0.0)
+    DS = [1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 24, 32]
+    TS = [2, 4, 6, 10, 16, 22, 40, 42, 64, 90, 100, 128, 200, 258, 400]
+    for _ in range(n_shapes):
+        fmt = int(rng.integers(0, 4))
+        epi = int(rng.choice([0, 0, 1, 2]))
+        l2 = rng.random() < 0.6
+        s0, s1 = rng.random() < 0.5, rng.random() < 0.5 or not l2
+        s2 = l2 and rng.random() < 0.5
+        D1, T1 = int(rng.choice(DS)), int(rng.choice(TS))
+        D2, T2 = (int(rng.choice(DS)), int(rng.choice(TS))) if l2 else (1, 0)
+        if rng.random() < 0.15:                       # long first stages: with D1 large, the sub-tile halves below 512 outputs
+            T1, D1 = int(rng.choice([1000, 2050, 4096])), int(rng.choice([6, 10, 16, 24, 32]))
+        lim = 8192 if rng.random() < 0.15 else 1024
+        W = 1 << int(rng.integers(0, 14))
+        while W > 1 and ((W * D2 + T2 if l2 else W) > lim or (W * D2 + T2 if l2 else W) * T1 > 3_000_000):
+            W //= 2
+        n2 = W * D2 + T2 if l2 else W
+        if n2 > 8192:
+            continue
+        S = int(rng.choice([W, max(1, W // 4), 2 * W, int(rng.integers(1, 2 * W + 1))]))
+        sr = int(rng.integers(1_000_000, 30_000_000))
+        r1 = sr // D1
+        r2 = r1 // D2
+        if r2 < 4:
+            continue
+
+        def shift_at(rate):
+            lim2 = rate // 2
+            return int(rng.choice([0, lim2 - 1, -(lim2 - 1), int(rng.integers(-(lim2 - 1), lim2))]))
+        stages = []
+        if s0:
+            stages.append(("shift", shift_at(sr)))
+        stages.append(("lowpass", (int(rng.integers(1, sr // 2)), D1, T1)))
+        if s1:
+            stages.append(("shift", shift_at(r1)))
+        if l2:
+            stages.append(("lowpass", (int(rng.integers(1, r1 // 2)), D2, T2)))
+            if s2:
+                stages.append(("shift", shift_at(r2)))
+        span, step = n2 * D1 + T1, S * D2 * D1
+        N = span + int(rng.integers(20, 80)) * step + int(rng.integers(0, 2 * D1 * D2 + 1))
+        bps = {0: 8, 1: 2, 2: 2, 3: 4}[fmt]
+        data = rng.integers(0, 256, N * bps, dtype=np.uint8)
+        if fmt == 0:
+            data = (rng.standard_normal((N, 2)).astype(np.float32) * 0.05).view(np.uint8).reshape(-1)
+        raw = data.tobytes()
+        u_w0, u_cnt = rng.random(), rng.random()      # the sub-range, drawn up front: what a shape draws never depends on a result
+        shape = "".join(k[0].upper() for k, _ in stages)
+        shifted = any(k == "shift" and a != 0 for k, a in stages)
+        desc = f"fmt={fmt} epi={epi} {shape} stages={stages} sr={sr} W={W} S={S} N={N}"
+        done = total = 0
+        try:
+            ch = oracle.Chain.from_bytes(raw, fmt, sr)
+            for kind, arg in stages:
+                ch = ch.shift(arg) if kind == "shift" else ch.lowpass(*arg)
+            p0 = Q.Plan(fmt, sr, N, stages=stages, width=W, stride=S, epilogue=2 if epi == 2 else 0)
+            done, total = p0.complete_windows(), p0.n_windows          # the bucket sink's loop is one window shorter or equal
+            # the windows compared with the oracle: the first and the last 16 complete ones
+            heads = [(0, min(16, done))] + ([(max(16, done - 16), done - max(16, done - 16))] if done > 16 else [])
+            refs = [ch.spark_fft(W, S, first_window=a, max_windows=c, want_codes=False)[0] for a, c in heads]
+            rng_g = None
+            if epi == 1:
+                allr = np.concatenate(refs).ravel()
+                lo, hi = np.percentile(allr, [20, 90])
+                rng_g = (float(lo), float(max(hi, lo * 1.5 + 1e-6)))
+            p = p0 if epi != 1 else Q.Plan(fmt, sr, N, stages=stages, width=W, stride=S, epilogue=epi, rng=rng_g)
+            M = int(re.search(r"M (\d+)\)", p.kernel_name()).group(1))
+            whole = p.run_host(raw, n_windows=done)
+            ok = whole.shape[0] == done
+            for (a, c), ref in zip(heads, refs):
+                if not ok or c == 0:
+                    break
+                got = whole[a:a + c]
+                if epi == 0:
+                    ex = ref.view(np.uint32) == got.view(np.uint32)
+                    scale = ulp_of(ref.max(axis=-1, keepdims=True)).astype(np.float64)
+                    worst = float((np.abs(ref.astype(np.float64) - got.astype(np.float64)) / scale).max())
+                    observed["bins"] += int(ex.size)
+                    observed["exact"] += int(ex.sum())
+                    observed["worst_ulp"] = max(observed["worst_ulp"], worst)
+                    ok = bool(ex.all()) if not shifted else worst <= 1.0
+                elif epi == 1:
+                    rn, rc = ch.spark_fft(W, S, rng=rng_g, first_window=a, max_windows=c)
+                    ok = codes_edge_ok(rc, got, rn, *rng_g)[0]
+                else:
+                    ok = bucket_digits_ok(ref, got)
+                if not ok:
+                    desc += f" ORACLE windows [{a}, +{c})"
+            if ok and done > 1:
+                w0 = 1 + int(u_w0 * (done - 1))
+                cnt = 1 + int(u_cnt * (done - w0))
+                first, count = p.src_range(w0, cnt)
+                sub = p.run_host(raw[first * bps:(first + count) * bps], w0, cnt, src_first=first)
+                ok = sub.tobytes() == whole[w0:w0 + cnt].tobytes()
+                if not ok:
+                    desc += f" SUB-RANGE w0={w0} cnt={cnt}"
+            if ok:
+                small = Q.Plan(fmt, sr, N, stages=stages, width=W, stride=S, epilogue=epi, rng=rng_g, chunk_bytes=1 << 16)
+                ok = small.run_host(raw, n_windows=done).tobytes() == whole.tobytes()
+                small.close()
+                if not ok:
+                    desc += " CHUNKED"
+            if p is not p0:
+                p.close()
+            p0.close()
+        except (Q.QuadrsError, RuntimeError) as e:
+            ok, M = False, None
+            desc += f" ERROR {e}"
+        cov["cls1"].add(casc_fir_class(D1))
+        if l2:
+            cov["cls2"].add(casc_fir_class(D2))
+            cov["t2_mod8"].add(T2 % 8 != 0)
+        cov["t1_mod8"].add(T1 % 8 != 0)
+        cov["M"].add((M, min(n2, 512)))                # the sub-tile against the one it starts from: below it, cascade_init halved
+        cov["shapes"].add(shape)
+        cov["short"] += ok and done < total
+        if log:
+            log(("ok  " if ok else "BAD ") + desc + f" M={M} complete={done}/{total}")
+        checked += 1
+        if not ok:
+            bad.append(desc)
+    return checked, bad
