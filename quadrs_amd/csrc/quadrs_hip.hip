@@ -677,8 +677,7 @@ constexpr size_t kLdsMax = 160 * 1024;
 struct RowTab {
     RowBase *d = nullptr;
     uint64_t cap = 0, row0 = 0, rows = 0, off = 0;
-    double ratio_bits = 0.0;                 // cascade tables (cascade_rowtab): the NCO ratio the rows were made for
-    bool used = false;
+    double ratio = 0.0;                      // the NCO ratio the rows were made for
 };
 // tables one launch context needs: the main kernel's rows and, for plans whose main kernel is not 256 threads wide,
 // rows laid out for the 256-thread per-sample kernel that takes the windows at an unaligned slab end
@@ -686,12 +685,13 @@ struct NcoTabs {
     RowTab main, tail;
     std::vector<RowTab> phase;               // interleaved launches with a shift: one row grid per launch (offset phi S)
     unsigned long long *work = nullptr;      // the launch context's tile-queue counters (ChainParams::work), zero between launches
-    // One launch context = one set of tile-queue counters + row tables, so launches that use it are ORDERED even when they
-    // come on different streams: every launch records `done` behind itself, and a launch arriving on another stream waits
-    // for it first (hipStreamWaitEvent, device side).  Two kernels of one context therefore never claim tiles from the same
-    // counters at the same time, and `done` transitively covers every earlier reader of the row tables.
+    void *cmp_tmp = nullptr;                 // two-stage plans: the carrier of the decimated samples stage A writes and stage B reads
+    size_t cmp_tmp_bytes = 0;
+    // One launch context = one set of tile-queue counters, row tables and carrier, so launches that use it are ORDERED even when
+    // they come on different streams: launch_windows waits for the context's previous launch first (hipStreamWaitEvent, device
+    // side) and records `done` behind every launch, the failed ones included.  Two kernels of one context therefore never claim
+    // tiles from the same counters at the same time, and `done` transitively covers every earlier reader of its buffers.
     hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;
     bool launched = false;
 };
 
@@ -742,12 +742,8 @@ struct qd_plan {
     qd_plan_stats stats{};
     // composite plans (a window whose FIR input W*D + T exceeds the 160 KiB LDS tile, stride == width): stage A filters and decimates the
     // stream in read_at blocks of W outputs (the write sink's kernels: per-block truncation == the sink's per-window truncation,
-    // src/filter.rs:68-83), stage B transforms the W-point windows of that decimated stream; `cmp_tmp` carries it through HBM
+    // src/filter.rs:68-83), stage B transforms the W-point windows of that decimated stream; the launch context's `cmp_tmp` carries it
     qd_plan *cmp_a = nullptr, *cmp_b = nullptr;
-    void *cmp_tmp = nullptr, *cmp_in = nullptr, *cmp_out = nullptr;
-    size_t cmp_tmp_bytes = 0, cmp_in_bytes = 0, cmp_out_bytes = 0;
-    hipEvent_t cmp_done = nullptr;
-    bool cmp_used = false;
     // cascade plans (qd_plan_create_stages, qd_cascade.h): [shift] lowpass [shift] [lowpass [shift]].  W, S, n_windows, ratio are the
     // sink's; D = D1 D2 and T = T2 D1 + T1 are the EFFECTIVE source step and span, so that W D + T / S D (src_range, shards, host chunks)
     // are the source figures of a window
@@ -779,24 +775,65 @@ uint64_t out_bytes_per_window(const qd_plan *p) {
     }
 }
 
-int ensure_rowtab_for(qd_plan *p, uint32_t ROW, RowTab *t, uint64_t n_lo, uint64_t n_hi, hipStream_t st, uint64_t n_off = 0) {
-    const uint64_t r_lo = n_lo / ROW, r_hi = (n_hi + ROW - 1) / ROW + 1;
-    if (t->d && t->off == n_off && r_lo >= t->row0 && r_hi <= t->row0 + t->rows) { t->used = true; return QD_OK; }
-    // The table is about to be rewritten: whatever read it last must have finished.  launch_chain has already ordered `st` behind
+// the sink's windows over a stream of `len` samples: the reference's loop count (src/fft.rs:28,65; the bucket sink's :86)
+uint64_t sink_windows(int epilogue, uint64_t len, uint64_t W, uint64_t S) {
+    const uint64_t lim = len >= W ? len - W : 0;
+    return epilogue == QD_EPI_BUCKET2_U8 ? lim / S : (lim == 0 ? 0 : (lim - 1) / S + 1);
+}
+
+// the only place plan options are checked and defaulted
+int check_options(const qd_plan_options *options, qd_plan_options *out) {
+    qd_plan_options opt{};
+    opt.struct_size = sizeof opt;
+    if (options) {
+        if (options->struct_size != sizeof(qd_plan_options)) return fail(QD_ERR_INVALID, "qd_plan_options size mismatch");
+        opt = *options;
+        if (opt.kernel_policy < QD_KERNEL_AUTO || opt.kernel_policy > QD_KERNEL_NO_PLAN_TIME) return fail(QD_ERR_INVALID, "unknown kernel_policy %d", opt.kernel_policy);
+        if (opt.nco_order < 0 || opt.nco_order > 2) return fail(QD_ERR_INVALID, "nco_order must be 0, 1 or 2");
+        if (opt.copy_threads > 64) return fail(QD_ERR_INVALID, "copy_threads > 64");
+        if (opt.chunk_bytes && (opt.chunk_bytes < (1u << 16) || opt.chunk_bytes > (1ull << 34))) return fail(QD_ERR_INVALID, "chunk_bytes outside [64 KiB, 16 GiB]");
+        if (opt.n_shards > QD_MAX_SHARDS) return fail(QD_ERR_INVALID, "n_shards > %d", QD_MAX_SHARDS);
+    }
+    *out = opt;
+    return QD_OK;
+}
+
+// the sink's fields of a chain description (the stages are checked by stages_geo)
+int check_sink(const qd_chain_desc &d) {
+    if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
+    if (d.epilogue < 0 || d.epilogue > 3) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
+    if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
+    if (!is_pow2(d.width))
+        return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
+    if (d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "width too large");
+    if (d.stride == 0) return fail(QD_ERR_INVALID, "stride 0 never terminates in the reference (src/fft.rs:65)");
+    if (d.stride > 0xffffffffull) return fail(QD_ERR_UNSUPPORTED, "stride too large");
+    return QD_OK;
+}
+
+// One NCO row table: rows of ROW samples at `ratio` (on the grid offset by n_off samples) covering samples [n_lo, n_hi).
+int ensure_rowtab(RowTab *t, double ratio, uint32_t ROW, uint64_t n_lo, uint64_t n_hi, hipStream_t st, uint64_t n_off = 0) {
+    const uint64_t r_lo = n_lo / ROW, r_hi = (n_hi + ROW - 1) / ROW;
+    if (t->d && t->off == n_off && t->ratio == ratio && r_lo >= t->row0 && r_hi <= t->row0 + t->rows) return QD_OK;
+    // The table is about to be rewritten: whatever read it last must have finished.  launch_windows has already ordered `st` behind
     // the context's previous launch (NcoTabs::done — an event, not the earlier caller's stream handle, which may be destroyed by
     // now), so k_rowtab on `st` runs after every earlier reader.
     const uint64_t rows = r_hi - r_lo;
     if (rows > t->cap) {
-        if (t->d) { if (t->used) HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(t->d)); t->d = nullptr; t->cap = 0; }
+        if (t->d) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(t->d)); t->d = nullptr; t->cap = 0; }
         const uint64_t cap = rows + rows / 8 + 16;            // chunks of a run differ by a row or two: grow once
         HIPCHK(hipMalloc(&t->d, cap * sizeof(RowBase)));
         t->cap = cap;
     }
-    t->row0 = r_lo; t->rows = rows; t->used = true; t->off = n_off;
-    const uint32_t blocks = (uint32_t)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_rowtab, dim3(blocks), dim3(256), 0, st, p->ratio, ROW, r_lo, rows, n_off, t->d);
+    t->row0 = r_lo; t->rows = rows; t->off = n_off; t->ratio = ratio;
+    hipLaunchKernelGGL(k_rowtab, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, ratio, ROW, r_lo, rows, n_off, t->d);
     HIPCHK(hipGetLastError());
     return QD_OK;
+}
+
+// the chain kernels' tables: the plan's ratio, and a row beyond the last sample's
+int ensure_rowtab_for(qd_plan *p, uint32_t ROW, RowTab *t, uint64_t n_lo, uint64_t n_hi, hipStream_t st, uint64_t n_off = 0) {
+    return ensure_rowtab(t, p->ratio, ROW, n_lo, n_hi + ROW, st, n_off);
 }
 
 int ensure_work(NcoTabs *tabs) {
@@ -849,16 +886,11 @@ int launch_spark_phases(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t s
                         uint64_t n_windows, uint64_t out_window0, void *out_d, hipStream_t st) {
     const int bps = bps_of(p->d.format);
     const uint64_t R = p->spark_R, W = p->W, S = p->S, obw = out_bytes_per_window(p);
-    if (tabs->launched) HIPCHK(hipStreamWaitEvent(st, tabs->done, 0));
     ChainParams P{};
     plan_params(p, &P);
     P.S = p->W;                                 // each launch's own geometry: windows side by side
     P.lds_dyn = (uint32_t)p->geo.lds_main;
     P.out_row_stride = (uint32_t)R;
-    if (p->timing) {
-        if (!p->ev_made) { HIPCHK(hipEventCreate(&p->ev0)); HIPCHK(hipEventCreate(&p->ev1)); p->ev_made = true; }
-        HIPCHK(hipEventRecord(p->ev0, st));
-    }
     const uint64_t cap = (uint64_t)p->n_cu * p->wg_per_cu, last = first_window + n_windows - 1;
     for (uint64_t phi = 0; phi < R; ++phi) {
         if (last < phi) break;
@@ -885,32 +917,10 @@ int launch_spark_phases(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t s
         void *args[] = {&P};
         HIPCHK(hipModuleLaunchKernel(p->jit_fn, grid, 1, 1, (unsigned)p->launch_nt, 1, 1, (unsigned)p->geo.lds_main, st, args, nullptr));
     }
-    if (p->timing) { HIPCHK(hipEventRecord(p->ev1, st)); p->ev_recorded = true; }
-    if (!tabs->done) HIPCHK(hipEventCreateWithFlags(&tabs->done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(tabs->done, st));
-    tabs->last_stream = st; tabs->launched = true;
     return QD_OK;
 }
 
 // windows [first_window, +n_windows) of a cascade plan (qd_cascade.h); the caller has clipped them to the complete windows
-// one NCO's row table of a cascade (kCascadeRow-sample rows of its own stage's index) covering samples [n_lo, n_hi), enqueued on
-// `st` behind every earlier reader (the caller has ordered `st` behind the launch context's previous launch)
-int cascade_rowtab(RowTab *t, double ratio, uint64_t n_lo, uint64_t n_hi, hipStream_t st) {
-    const uint64_t r_lo = n_lo / kCascadeRow, r_hi = (n_hi + kCascadeRow - 1) / kCascadeRow;
-    if (t->d && r_lo >= t->row0 && r_hi <= t->row0 + t->rows && t->ratio_bits == ratio) return QD_OK;
-    const uint64_t rows = r_hi - r_lo;
-    if (rows > t->cap) {
-        if (t->d) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(t->d)); t->d = nullptr; t->cap = 0; }
-        const uint64_t cap = rows + rows / 8 + 16;
-        HIPCHK(hipMalloc(&t->d, cap * sizeof(RowBase)));
-        t->cap = cap;
-    }
-    t->row0 = r_lo; t->rows = rows; t->used = true; t->off = 0; t->ratio_bits = ratio;
-    hipLaunchKernelGGL(k_rowtab, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, ratio, kCascadeRow, r_lo, rows, (uint64_t)0, t->d);
-    HIPCHK(hipGetLastError());
-    return QD_OK;
-}
-
 int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
                    uint64_t out_window0, void *out_d, hipStream_t st) {
     const uint64_t need0 = first_window * p->S * p->D, need1 = (first_window + n_windows - 1) * p->S * p->D + (uint64_t)p->W * p->D + p->T;
@@ -933,25 +943,19 @@ int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_fi
     P.dmagic2 = (p->c_flags & kCascL2) && p->c_D2 % 2 == 0 ? (uint32_t)((1ull << 32) / p->c_D2 + 1) : 0u;
     P.phi2 = (p->c_flags & kCascL2) ? (p->c_D2 - (p->c_T2 - p->c_T2 / 2) % p->c_D2) % p->c_D2 : 0u;
     P.flags = p->c_flags;
-    // row tables of the NCOs over this launch's range, on `st`.  One launch context (`tabs`) = one set of tables: a launch arriving
-    // on another stream waits for the context's previous launch before its k_rowtab rewrites them (see NcoTabs)
-    if (tabs->launched) HIPCHK(hipStreamWaitEvent(st, tabs->done, 0));
+    // row tables of the NCOs over this launch's range, on `st` (ordered behind the context's previous launch, see NcoTabs)
     if (tabs->phase.size() < 3) tabs->phase.resize(3);
     const uint64_t last = first_window + n_windows - 1, l2 = (p->c_flags & kCascL2) ? p->c_D2 : 1;
     const uint64_t lo[3] = {need0, first_window * p->S * l2, first_window * p->S}, hi[3] = {need1, last * p->S * l2 + p->c_n2, last * p->S + p->W};
     const uint32_t sflag[3] = {kCascS0, kCascS1, kCascS2};
     for (int k = 0; k < 3; ++k) {
         if (!(p->c_flags & sflag[k])) continue;
-        const int rc = cascade_rowtab(&tabs->phase[k], p->c_ratio[k], lo[k], hi[k], st);
+        const int rc = ensure_rowtab(&tabs->phase[k], p->c_ratio[k], kCascadeRow, lo[k], hi[k], st);      // rows of its own stage's index
         if (rc) return rc;
         P.rows[k] = tabs->phase[k].d; P.row0[k] = tabs->phase[k].row0;
     }
     const uint64_t cap = (uint64_t)p->n_cu * p->c_wg_per_cu;
     const uint32_t grid = (uint32_t)(n_windows < cap ? n_windows : cap);
-    if (p->timing) {
-        if (!p->ev_made) { HIPCHK(hipEventCreate(&p->ev0)); HIPCHK(hipEventCreate(&p->ev1)); p->ev_made = true; }
-        HIPCHK(hipEventRecord(p->ev0, st));
-    }
     switch (p->d.format) {
     case QD_FMT_CF32: hipLaunchKernelGGL(k_cascade<0>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
     case QD_FMT_CS8: hipLaunchKernelGGL(k_cascade<1>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
@@ -959,17 +963,11 @@ int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_fi
     default: hipLaunchKernelGGL(k_cascade<3>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
     }
     HIPCHK(hipGetLastError());
-    if (p->timing) { HIPCHK(hipEventRecord(p->ev1, st)); p->ev_recorded = true; }
-    if (!tabs->done) HIPCHK(hipEventCreateWithFlags(&tabs->done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(tabs->done, st));
-    tabs->last_stream = st; tabs->launched = true;
     return QD_OK;
 }
 
 int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window,
                  uint64_t n_windows, uint64_t out_window0, void *out_d, hipStream_t st) {
-    if (n_windows == 0) return QD_OK;
-    if (p->casc) return launch_cascade(p, tabs, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st);
     const int fmt = p->d.format;
     const int spl = spl_of(fmt), bps = bps_of(fmt);
     uint64_t need0 = first_window * p->S * p->D;
@@ -989,9 +987,6 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
             return launch_spark_phases(p, tabs, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st);
         phases_unaligned = true;
     }
-    // see NcoTabs.  ALWAYS wait: a stream handle compared with the previous caller's may be a new stream at a recycled address (the old one
-    // destroyed with its kernels still running); a wait on an event recorded in the same stream costs nothing
-    if (tabs->launched) HIPCHK(hipStreamWaitEvent(st, tabs->done, 0));
     if (p->has_shift) {
         // row-aligned phase 1: rows of a short last tile's missing windows (and a half-window pass's read-ahead) get table entries too
         // (the streaming kernel parks one more step of rows behind a run's last tile)
@@ -1044,10 +1039,6 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
         if (rc) return rc;
     }
     const uint64_t cap = (uint64_t)p->n_cu * p->wg_per_cu;
-    if (p->timing) {
-        if (!p->ev_made) { HIPCHK(hipEventCreate(&p->ev0)); HIPCHK(hipEventCreate(&p->ev1)); p->ev_made = true; }
-        HIPCHK(hipEventRecord(p->ev0, st));
-    }
     for (int part = 0; part < 2; ++part) {
         const uint64_t w_begin = part == 0 ? first_window : first_window + n_aligned;
         const uint64_t w_count = part == 0 ? n_aligned : n_windows - n_aligned;
@@ -1069,10 +1060,6 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
             HIPCHK(hipGetLastError());
         }
     }
-    if (p->timing) { HIPCHK(hipEventRecord(p->ev1, st)); p->ev_recorded = true; }
-    if (!tabs->done) HIPCHK(hipEventCreateWithFlags(&tabs->done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(tabs->done, st));
-    tabs->last_stream = st; tabs->launched = true;
 #ifdef QD_WGTIME
     {
         std::vector<unsigned long long> h(kStampWords);
@@ -1115,6 +1102,50 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
     }
 #endif
     return QD_OK;
+}
+
+int launch_windows(qd_plan *p, NcoTabs *ctx, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window,
+                   uint64_t n_windows, uint64_t out_window0, void *out_d, hipStream_t st);
+
+// windows [w0, +nw) of a two-stage plan: stage A filters their read_at blocks into the context's carrier, stage B transforms them.
+// Each stage runs on its own plan's launch context of the same role (device path or host ring slot) as `ctx`.
+int launch_composite(qd_plan *p, NcoTabs *ctx, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t w0, uint64_t nw,
+                     uint64_t out_window0, void *out_d, hipStream_t st) {
+    qd_plan *a = p->cmp_a, *b = p->cmp_b;
+    const uint64_t W = p->W;
+    const size_t need = (size_t)(nw * W + 16) * 8;
+    if (need > ctx->cmp_tmp_bytes) {
+        if (ctx->cmp_tmp) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(ctx->cmp_tmp)); ctx->cmp_tmp = nullptr; ctx->cmp_tmp_bytes = 0; }
+        HIPCHK(hipMalloc(&ctx->cmp_tmp, need));
+        ctx->cmp_tmp_bytes = need;
+    }
+    NcoTabs *ca = &a->tabs_dev, *cb = &b->tabs_dev;
+    if (ctx != &p->tabs_dev) { const ptrdiff_t k = ctx - p->tabs_slot; ca = &a->tabs_slot[k]; cb = &b->tabs_slot[k]; }
+    const int rc = launch_windows(a, ca, src_d, src_first, src_count, w0 * a->blk_subs, nw * a->blk_subs, w0 * a->blk_subs, ctx->cmp_tmp, st);
+    if (rc) return rc;
+    return launch_windows(b, cb, ctx->cmp_tmp, w0 * W, nw * W, w0, nw, out_window0, out_d, st);
+}
+
+// The one way device-resident windows of any plan are launched: windows [first_window, +n_windows) of a slab holding source samples
+// [src_first, +src_count) into out_d, which holds the windows from out_window0 on.  It keeps the launch-context protocol of NcoTabs
+// and the plan's timing events for every kind of plan; the kind's body does the rest.
+int launch_windows(qd_plan *p, NcoTabs *ctx, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window,
+                   uint64_t n_windows, uint64_t out_window0, void *out_d, hipStream_t st) {
+    if (n_windows == 0) return QD_OK;
+    if (!ctx->done) HIPCHK(hipEventCreateWithFlags(&ctx->done, hipEventDisableTiming));
+    // ALWAYS wait: a stream handle compared with the previous caller's may be a new stream at a recycled address (the old one destroyed
+    // with its kernels still running); a wait on an event recorded in the same stream costs nothing
+    if (ctx->launched) HIPCHK(hipStreamWaitEvent(st, ctx->done, 0));
+    if (p->timing && !p->ev_made) { HIPCHK(hipEventCreate(&p->ev0)); HIPCHK(hipEventCreate(&p->ev1)); p->ev_made = true; }
+    if (p->timing) HIPCHK(hipEventRecord(p->ev0, st));
+    const int rc = p->cmp_a ? launch_composite(p, ctx, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st)
+                 : p->casc ? launch_cascade(p, ctx, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st)
+                 : launch_chain(p, ctx, src_d, src_first, src_count, first_window, n_windows, out_window0, out_d, st);
+    // whatever the body enqueued before it returned, an error included, is now behind `done`
+    HIPCHK(hipEventRecord(ctx->done, st));
+    ctx->launched = true;
+    if (p->timing) { HIPCHK(hipEventRecord(p->ev1, st)); p->ev_recorded = true; }
+    return rc;
 }
 
 void free_streaming(qd_plan *p) {
@@ -1188,10 +1219,8 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
     p->D = p->has_fir ? (uint32_t)d.decimate : 1;
     p->T = p->has_fir ? (uint32_t)d.taps : 0;
     p->dec_len = len; p->out_rate = rate;
-    uint64_t lim = len >= d.width ? len - d.width : 0;
     if (d.epilogue == QD_EPI_CF32_BLOCKS) p->n_windows = (d.n_samples - d.taps) / (d.width * d.decimate);   // full read_at blocks
-    else if (d.epilogue == QD_EPI_BUCKET2_U8) p->n_windows = lim / d.stride;            // src/fft.rs:86
-    else p->n_windows = lim == 0 ? 0 : (lim - 1) / d.stride + 1;                        // src/fft.rs:28,65
+    else p->n_windows = sink_windows(d.epilogue, len, d.width, d.stride);
     p->ratio = p->has_shift ? qd_shift_ratio(d.shift_hz, d.sample_rate) : 0.0;
 
     // |place| = n*|ratio| over the whole stream decides the NCO order once per plan: the dropped
@@ -1646,113 +1675,7 @@ void partition_windows(uint64_t n_windows, uint32_t n_shards, uint64_t step, uin
 }
 }  // namespace
 
-int qd_plan_create_ex(const qd_chain_desc *desc, const qd_plan_options *options, qd_plan **out) {
-    if (!desc || !out) return fail(QD_ERR_INVALID, "desc/plan is NULL");
-    if (desc->struct_size != sizeof(qd_chain_desc)) return fail(QD_ERR_INVALID, "qd_chain_desc size mismatch");
-    qd_plan_options opt{};
-    opt.struct_size = sizeof opt;
-    if (options) {
-        if (options->struct_size != sizeof(qd_plan_options)) return fail(QD_ERR_INVALID, "qd_plan_options size mismatch");
-        opt = *options;
-        if (opt.kernel_policy < QD_KERNEL_AUTO || opt.kernel_policy > QD_KERNEL_NO_PLAN_TIME) return fail(QD_ERR_INVALID, "unknown kernel_policy %d", opt.kernel_policy);
-        if (opt.nco_order < 0 || opt.nco_order > 2) return fail(QD_ERR_INVALID, "nco_order must be 0, 1 or 2");
-        if (opt.copy_threads > 64) return fail(QD_ERR_INVALID, "copy_threads > 64");
-        if (opt.chunk_bytes && (opt.chunk_bytes < (1u << 16) || opt.chunk_bytes > (1ull << 34))) return fail(QD_ERR_INVALID, "chunk_bytes outside [64 KiB, 16 GiB]");
-        if (opt.n_shards > QD_MAX_SHARDS) return fail(QD_ERR_INVALID, "n_shards > %d", QD_MAX_SHARDS);
-    }
-    const qd_chain_desc &d = *desc;
-    if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
-    if (d.epilogue < 0 || d.epilogue > 3) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
-    if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
-    if (d.epilogue == QD_EPI_CF32_BLOCKS && !d.has_lowpass) return fail(QD_ERR_INVALID, "QD_EPI_CF32_BLOCKS needs a lowpass in the chain");
-    if (!is_pow2(d.width))
-        return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
-    if (d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "width too large");
-    if (d.stride == 0) return fail(QD_ERR_INVALID, "stride 0 never terminates in the reference (src/fft.rs:65)");
-    if (d.stride > 0xffffffffull) return fail(QD_ERR_UNSUPPORTED, "stride too large");
-    uint64_t len = d.n_samples, rate = d.sample_rate;
-    if (d.has_shift) {
-        // Shift::new asserts, src/shift.rs:20-24
-        int64_t af = d.shift_hz < 0 ? -d.shift_hz : d.shift_hz;
-        if (!(af < (int64_t)(d.sample_rate / 2)) || d.sample_rate == 0)
-            return fail(QD_ERR_PANIC, "frequency must be under half the sample rate (src/shift.rs:20-24)");
-    }
-    if (d.has_lowpass) {
-        if (d.decimate == 0) return fail(QD_ERR_PANIC, "decimate 0 divides by zero (src/filter.rs:47)");
-        if (d.taps < 2) return fail(QD_ERR_PANIC, "lowpass size < 2 underflows (src/filter.rs:74)");
-        if (d.taps > 65536 || d.decimate > 65536) return fail(QD_ERR_UNSUPPORTED, "taps/decimate too large");
-        if (len < d.taps) return fail(QD_ERR_PANIC, "inner.len() < filter.len() (src/filter.rs:46)");
-        len = 1 + (len - d.taps) / d.decimate;     // LowPass::len, src/filter.rs:47
-        rate = rate / d.decimate;                  // src/filter.rs:51
-    }
-    if (d.epilogue != QD_EPI_CF32_BLOCKS && len < d.width) return fail(QD_ERR_PANIC, "len %llu < width %llu: u64 underflow at src/fft.rs:28,86",
-                                   (unsigned long long)len, (unsigned long long)d.width);
-    if (opt.n_shards > 1) {
-        int n_dev = 0;
-        HIPCHK(hipGetDeviceCount(&n_dev));
-        for (uint32_t g = 0; g < opt.n_shards; ++g)
-            if (opt.shard_device[g] < 0 || opt.shard_device[g] >= n_dev)
-                return fail(QD_ERR_INVALID, "shard %u: device %d does not exist (%d visible)", g, opt.shard_device[g], n_dev);
-    }
-    qd_plan *p = new qd_plan();
-    p->d = d;
-    p->opt = opt;
-    int rc = plan_init(p, d, len, rate);
-    if (rc == kNeedComposite) {
-        if (opt.n_shards > 1) rc = fail(QD_ERR_UNSUPPORTED, "a window larger than the LDS tile runs as a two-stage plan, which is not sharded inside one process");
-        else {
-            qd_plan_options copt = opt;
-            copt.n_shards = 0;
-            memset(copt.tile_hint, 0, sizeof copt.tile_hint);
-            qd_chain_desc a = d;                         // stage A: the same source chain into read_at blocks of W decimated samples
-            a.stride = d.width; a.epilogue = QD_EPI_CF32_BLOCKS; a.has_range = 0;
-            rc = qd_plan_create_ex(&a, &copt, &p->cmp_a);
-            if (rc == QD_OK) {
-                qd_chain_desc b{};                       // stage B: W-point windows side by side over the decimated stream
-                b.struct_size = sizeof b;
-                b.format = QD_FMT_CF32; b.sample_rate = rate ? rate : 1;
-                b.n_samples = d.epilogue == QD_EPI_BUCKET2_U8 ? (p->n_windows + 1) * d.width : p->n_windows * d.width + 1;      // exactly n_windows windows (src/fft.rs:28,65 / :86)
-                b.width = d.width; b.stride = d.width; b.epilogue = d.epilogue; b.mode = d.mode;
-                b.has_range = d.has_range; b.range_min = d.range_min; b.range_max = d.range_max;
-                rc = qd_plan_create_ex(&b, &copt, &p->cmp_b);
-            }
-            if (rc == QD_OK && (p->cmp_a->n_windows < p->n_windows || p->cmp_b->n_windows != p->n_windows))
-                rc = fail(QD_ERR_UNSUPPORTED, "two-stage plan: stage window counts disagree (%llu blocks, %llu / %llu windows)", (unsigned long long)p->cmp_a->n_windows,
-                          (unsigned long long)p->cmp_b->n_windows, (unsigned long long)p->n_windows);
-            p->geo.G = 1;
-        }
-    }
-    if (rc) { qd_plan_destroy(p); return rc; }
-    // sharded plans: the parent describes the whole stream; each shard gets a plan of its own on its device
-    const uint32_t n_shards = opt.n_shards > 1 ? opt.n_shards : 1;
-    const uint64_t step = (uint64_t)(p->blk_len ? p->blk_len : p->S) * p->D, rpw = (uint64_t)(p->blk_len ? p->blk_len : p->W) * p->D + p->T;
-    // API windows of the write sink are whole blocks; interleaved launches take any window range, and keep their speed when it starts on a load vector
-    uint32_t tile_api = p->blk_len ? 1u : p->geo.G;
-    if (p->spark_R > 1) {
-        tile_api = (uint32_t)spl_of(d.format); while (tile_api > 1 && ((uint64_t)(tile_api / 2) * p->S) % spl_of(d.format) == 0) tile_api /= 2;
-        if (p->has_shift) tile_api = p->spark_R * (p->W < kSparkRow ? kSparkRow / p->W : 1u);      // ... and with a shift on the launches' NCO row grids
-        p->phase_unit = tile_api;
-    }
-    partition_windows(p->n_windows, n_shards, step, rpw, tile_api, &p->shard_info);
-    for (uint32_t g = 0; g < n_shards; ++g) p->shard_info[g].device = n_shards > 1 ? opt.shard_device[g] : p->device;
-    if (n_shards > 1) {
-        qd_plan_options copt = opt;
-        copt.n_shards = 0;
-        for (uint32_t g = 0; g < n_shards && rc == QD_OK; ++g) {
-            DeviceGuard guard(opt.shard_device[g]);
-            qd_plan *c = nullptr;
-            rc = qd_plan_create_ex(desc, &copt, &c);
-            if (rc == QD_OK) p->shards.push_back(c);
-        }
-        if (rc) { qd_plan_destroy(p); return rc; }
-    }
-    *out = p;
-    return QD_OK;
-}
-
-int qd_plan_create(const qd_chain_desc *desc, qd_plan **out) { return qd_plan_create_ex(desc, nullptr, out); }
-
-// ------------------------------------------------------------------ stage lists (cascades)
+// ------------------------------------------------------------------ plan creation: stage lists, cascades
 
 namespace {
 constexpr uint32_t kCascadeMaxInter = 8192;     // intermediate samples per window (W D2 + T2): the kernel's LDS envelope
@@ -1776,14 +1699,7 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     const qd_chain_desc &d = *desc;
     if (d.has_shift || d.has_lowpass) return fail(QD_ERR_INVALID, "a stage list carries the shift / lowpass stages: has_shift = has_lowpass = 0");
     if (n > QD_MAX_STAGES) return fail(QD_ERR_INVALID, "%zu stages > QD_MAX_STAGES (%d)", n, QD_MAX_STAGES);
-    if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
-    if (d.epilogue < 0 || d.epilogue > 3) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
-    if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
-    if (!is_pow2(d.width))
-        return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
-    if (d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "width too large");
-    if (d.stride == 0) return fail(QD_ERR_INVALID, "stride 0 never terminates in the reference (src/fft.rs:65)");
-    if (d.stride > 0xffffffffull) return fail(QD_ERR_UNSUPPORTED, "stride too large");
+    if (const int rc = check_sink(d)) return rc;
     uint64_t len = d.n_samples, rate = d.sample_rate;
     g->in_rate.assign(n, 0);
     std::string shape;
@@ -1814,17 +1730,18 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     if (d.epilogue != QD_EPI_CF32_BLOCKS && len < d.width)
         return fail(QD_ERR_PANIC, "len %llu < width %llu: u64 underflow at src/fft.rs:28,86", (unsigned long long)len, (unsigned long long)d.width);
     g->len = len; g->rate = rate;
+    g->n_windows = sink_windows(d.epilogue, len, d.width, d.stride);
     g->routed = shape.empty() || shape == "S" || shape == "L" || shape == "SL";
     size_t k = 0;
     auto take = [&](char c) { if (k < shape.size() && shape[k] == c) return (int)k++; return -1; };
     g->s0 = take('S'); g->l1 = take('L'); g->s1 = take('S');
     if (g->l1 >= 0) { g->l2 = take('L'); if (g->l2 >= 0) g->s2 = take('S'); }
+    if (g->l1 >= 0) { g->D1 = (uint32_t)st[g->l1].decimate; g->T1 = (uint32_t)st[g->l1].taps; }
     if (g->routed) return QD_OK;
     if (g->l1 < 0 || k != shape.size())
         return fail(QD_ERR_UNSUPPORTED, "stage list %s is not a fused shape ([shift] lowpass [shift] [lowpass [shift]]): the caller runs it stage by stage",
                     shape.c_str());
     if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "write (QD_EPI_CF32_BLOCKS) after a cascade is not built");
-    g->D1 = (uint32_t)st[g->l1].decimate; g->T1 = (uint32_t)st[g->l1].taps;
     if (g->l2 >= 0) { g->D2 = (uint32_t)st[g->l2].decimate; g->T2 = (uint32_t)st[g->l2].taps; }
     const uint64_t n2 = g->l2 >= 0 ? d.width * g->D2 + g->T2 : d.width;
     if (n2 > kCascadeMaxInter)
@@ -1832,8 +1749,6 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
                     kCascadeMaxInter);
     if (g->T1 > kCascadeMaxT1) return fail(QD_ERR_UNSUPPORTED, "cascade: a first stage of %u taps exceeds the kernel's sub-tile (%u taps)", g->T1, kCascadeMaxT1);
     g->n2 = (uint32_t)n2;
-    const uint64_t lim = len - d.width;
-    g->n_windows = d.epilogue == QD_EPI_BUCKET2_U8 ? lim / d.stride : (lim == 0 ? 0 : (lim - 1) / d.stride + 1);   // src/fft.rs:86 / :28,65
     // window w reads source samples [w S D2 D1, + n2 D1 + T1): complete while they exist (src/samples.rs:17-27)
     const uint64_t span = n2 * g->D1 + g->T1, step = d.stride * g->D2 * g->D1;
     const uint64_t fit = d.n_samples >= span ? (d.n_samples - span) / step + 1 : 0;
@@ -1918,11 +1833,6 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
     const qd_chain_desc &d = *desc;
     if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "qd_stages_geometry: the write sink's blocks are the one-stage plan's (qd_plan_get_info)");
     if (g.routed) {                  // the one-stage plan's figures: a single lowpass never fails a read
-        uint64_t D = 1, T = 0;
-        if (g.l1 >= 0) { D = stages[g.l1].decimate; T = stages[g.l1].taps; }
-        g.D1 = (uint32_t)D; g.T1 = (uint32_t)T;
-        const uint64_t lim = g.len - d.width;
-        g.n_windows = d.epilogue == QD_EPI_BUCKET2_U8 ? lim / d.stride : (lim == 0 ? 0 : (lim - 1) / d.stride + 1);
         g.complete = g.n_windows;
         g.n2 = (uint32_t)d.width;
     }
@@ -1939,33 +1849,76 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
 }
 
 namespace {
-int create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, qd_plan **out) {
-    if (!out) return fail(QD_ERR_INVALID, "plan is NULL");
+int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, bool list, qd_plan **out);
+
+// a window larger than the LDS tile, windows side by side (plan_init's kNeedComposite): two plans behind the parent's handle
+int composite_init(qd_plan *p, uint64_t rate) {
+    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a window larger than the LDS tile runs as a two-stage plan, which is not sharded inside one process");
+    const qd_chain_desc &d = p->d;
+    qd_plan_options copt = p->opt;
+    copt.n_shards = 0;
+    memset(copt.tile_hint, 0, sizeof copt.tile_hint);
+    qd_chain_desc a = d;                         // stage A: the same source chain into read_at blocks of W decimated samples
+    a.stride = d.width; a.epilogue = QD_EPI_CF32_BLOCKS; a.has_range = 0;
+    int rc = qd_plan_create_ex(&a, &copt, &p->cmp_a);
+    if (rc) return rc;
+    qd_chain_desc b{};                           // stage B: W-point windows side by side over the decimated stream
+    b.struct_size = sizeof b;
+    b.format = QD_FMT_CF32; b.sample_rate = rate ? rate : 1;
+    b.n_samples = d.epilogue == QD_EPI_BUCKET2_U8 ? (p->n_windows + 1) * d.width : p->n_windows * d.width + 1;      // exactly n_windows windows (src/fft.rs:28,65 / :86)
+    b.width = d.width; b.stride = d.width; b.epilogue = d.epilogue; b.mode = d.mode;
+    b.has_range = d.has_range; b.range_min = d.range_min; b.range_max = d.range_max;
+    rc = qd_plan_create_ex(&b, &copt, &p->cmp_b);
+    if (rc) return rc;
+    p->geo.G = 1;
+    if (p->cmp_a->n_windows < p->n_windows || p->cmp_b->n_windows != p->n_windows)
+        return fail(QD_ERR_UNSUPPORTED, "two-stage plan: stage window counts disagree (%llu blocks, %llu / %llu windows)", (unsigned long long)p->cmp_a->n_windows,
+                    (unsigned long long)p->cmp_b->n_windows, (unsigned long long)p->n_windows);
+    return QD_OK;
+}
+
+// sharded plans (options.n_shards > 1): the parent describes the whole stream; each shard gets a plan of its own, made from the same
+// stage list on that shard's device
+int make_shards(qd_plan *p, const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, bool list) {
+    const uint32_t n_shards = p->opt.n_shards > 1 ? p->opt.n_shards : 1;
+    const uint64_t step = (uint64_t)(p->blk_len ? p->blk_len : p->S) * p->D, rpw = (uint64_t)(p->blk_len ? p->blk_len : p->W) * p->D + p->T;
+    // API windows of the write sink are whole blocks; interleaved launches take any window range, and keep their speed when it starts on a load vector
+    uint32_t tile_api = p->blk_len ? 1u : p->geo.G;
+    if (p->spark_R > 1) {
+        tile_api = (uint32_t)spl_of(p->d.format); while (tile_api > 1 && ((uint64_t)(tile_api / 2) * p->S) % spl_of(p->d.format) == 0) tile_api /= 2;
+        if (p->has_shift) tile_api = p->spark_R * (p->W < kSparkRow ? kSparkRow / p->W : 1u);      // ... and with a shift on the launches' NCO row grids
+        p->phase_unit = tile_api;
+    }
+    partition_windows(p->n_windows, n_shards, step, rpw, tile_api, &p->shard_info);
+    for (uint32_t g = 0; g < n_shards; ++g) p->shard_info[g].device = n_shards > 1 ? p->opt.shard_device[g] : p->device;
+    qd_plan_options copt = p->opt;
+    copt.n_shards = 0;
+    for (uint32_t g = 0; g < n_shards && n_shards > 1; ++g) {
+        DeviceGuard guard(p->opt.shard_device[g]);
+        qd_plan *c = nullptr;
+        const int rc = create_plan(desc, stages, n_stages, &copt, list, &c);
+        if (rc) return rc;
+        p->shards.push_back(c);
+    }
+    return QD_OK;
+}
+
+// The one creator behind qd_plan_create_ex and qd_plan_create_stages: a chain given as a stage list (desc's own has_shift /
+// has_lowpass clear).  The reference's asserts and the stage list's shape come first (stages_geo), then the options, and every
+// argument check before the first HIP call.  A routed list ([shift] [lowpass]) is the one-stage plan — a two-stage plan where a
+// window exceeds the LDS tile —, any other fused list a cascade.  `list`: the plan records the list (qd_plan_get_stage_taps).
+int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, bool list, qd_plan **out) {
     StageGeo g;
     int rc = stages_geo(desc, stages, n_stages, &g);
     if (rc) return rc;
-    if (g.routed) {                  // the one-stage description holds it: today's plan, kernels and bytes
-        qd_chain_desc d = *desc;
+    qd_plan_options opt;
+    rc = check_options(options, &opt);
+    if (rc) return rc;
+    qd_chain_desc d = *desc;
+    if (g.routed) {                  // the one-stage description holds it: the same plan, kernels and bytes whichever entry point
         if (g.s0 >= 0) { d.has_shift = 1; d.shift_hz = stages[g.s0].shift_hz; }
         if (g.l1 >= 0) { d.has_lowpass = 1; d.lowpass_hz = stages[g.l1].lowpass_hz; d.decimate = stages[g.l1].decimate; d.taps = stages[g.l1].taps; }
-        qd_plan *p = nullptr;
-        rc = qd_plan_create_ex(&d, options, &p);
-        if (rc) return rc;
-        p->stages.assign(stages, stages + n_stages);
-        stage_taps_of(stages, n_stages, g, &p->stage_taps);
-        *out = p;
-        return QD_OK;
-    }
-    qd_plan_options opt{};
-    opt.struct_size = sizeof opt;
-    if (options) {
-        if (options->struct_size != sizeof(qd_plan_options)) return fail(QD_ERR_INVALID, "qd_plan_options size mismatch");
-        opt = *options;
-        if (opt.kernel_policy < QD_KERNEL_AUTO || opt.kernel_policy > QD_KERNEL_NO_PLAN_TIME) return fail(QD_ERR_INVALID, "unknown kernel_policy %d", opt.kernel_policy);
-        if (opt.nco_order < 0 || opt.nco_order > 2) return fail(QD_ERR_INVALID, "nco_order must be 0, 1 or 2");
-        if (opt.copy_threads > 64) return fail(QD_ERR_INVALID, "copy_threads > 64");
-        if (opt.chunk_bytes && (opt.chunk_bytes < (1u << 16) || opt.chunk_bytes > (1ull << 34))) return fail(QD_ERR_INVALID, "chunk_bytes outside [64 KiB, 16 GiB]");
-        if (opt.n_shards > QD_MAX_SHARDS) return fail(QD_ERR_INVALID, "n_shards > %d", QD_MAX_SHARDS);
+        if (d.epilogue == QD_EPI_CF32_BLOCKS && !d.has_lowpass) return fail(QD_ERR_INVALID, "QD_EPI_CF32_BLOCKS needs a lowpass in the chain");
     }
     if (opt.n_shards > 1) {
         int n_dev = 0;
@@ -1975,33 +1928,42 @@ int create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_st
                 return fail(QD_ERR_INVALID, "shard %u: device %d does not exist (%d visible)", s, opt.shard_device[s], n_dev);
     }
     qd_plan *p = new qd_plan();
-    p->d = *desc;
+    p->d = d;
     p->opt = opt;
-    p->stages.assign(stages, stages + n_stages);
-    stage_taps_of(stages, n_stages, g, &p->stage_taps);
-    rc = cascade_init(p, g, stages);
-    if (rc) { qd_plan_destroy(p); return rc; }
-    const uint32_t n_shards = opt.n_shards > 1 ? opt.n_shards : 1;
-    partition_windows(p->n_windows, n_shards, (uint64_t)p->S * p->D, (uint64_t)p->W * p->D + p->T, 1, &p->shard_info);
-    for (uint32_t s = 0; s < n_shards; ++s) p->shard_info[s].device = n_shards > 1 ? opt.shard_device[s] : p->device;
-    if (n_shards > 1) {
-        qd_plan_options copt = opt;
-        copt.n_shards = 0;
-        for (uint32_t s = 0; s < n_shards && rc == QD_OK; ++s) {
-            DeviceGuard guard(opt.shard_device[s]);
-            qd_plan *c = nullptr;
-            rc = create_stages(desc, stages, n_stages, &copt, &c);
-            if (rc == QD_OK) p->shards.push_back(c);
-        }
-        if (rc) { qd_plan_destroy(p); return rc; }
+    if (list) {
+        p->stages.assign(stages, stages + n_stages);
+        stage_taps_of(stages, n_stages, g, &p->stage_taps);
     }
+    if (!g.routed) rc = cascade_init(p, g, stages);
+    else if ((rc = plan_init(p, d, g.len, g.rate)) == kNeedComposite) rc = composite_init(p, g.rate);
+    if (rc == QD_OK) rc = make_shards(p, desc, stages, n_stages, list);
+    if (rc) { qd_plan_destroy(p); return rc; }
     *out = p;
     return QD_OK;
 }
 }  // namespace
 
+int qd_plan_create_ex(const qd_chain_desc *desc, const qd_plan_options *options, qd_plan **out) {
+    if (!desc || !out) return fail(QD_ERR_INVALID, "desc/plan is NULL");
+    if (desc->struct_size != sizeof(qd_chain_desc)) return fail(QD_ERR_INVALID, "qd_chain_desc size mismatch");
+    // this entry point has always checked the options, and the write sink's lowpass, before the chain
+    qd_plan_options opt;
+    if (const int rc = check_options(options, &opt)) return rc;
+    if (desc->epilogue == QD_EPI_CF32_BLOCKS && !desc->has_lowpass) return fail(QD_ERR_INVALID, "QD_EPI_CF32_BLOCKS needs a lowpass in the chain");
+    qd_chain_desc d = *desc;         // the stage list [shift] [lowpass]
+    qd_stage st[2] = {};
+    size_t n = 0;
+    if (d.has_shift) { st[n].kind = QD_STAGE_SHIFT; st[n++].shift_hz = d.shift_hz; }
+    if (d.has_lowpass) { st[n].kind = QD_STAGE_LOWPASS; st[n].lowpass_hz = d.lowpass_hz; st[n].decimate = d.decimate; st[n++].taps = d.taps; }
+    d.has_shift = d.has_lowpass = 0;
+    return create_plan(&d, st, n, &opt, false, out);
+}
+
+int qd_plan_create(const qd_chain_desc *desc, qd_plan **out) { return qd_plan_create_ex(desc, nullptr, out); }
+
 int qd_plan_create_stages(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, qd_plan **plan) {
-    return create_stages(desc, stages, n_stages, options, plan);
+    if (!plan) return fail(QD_ERR_INVALID, "plan is NULL");
+    return create_plan(desc, stages, n_stages, options, true, plan);
 }
 
 int qd_plan_get_stage_taps(const qd_plan *p, uint32_t stage, float *taps, size_t cap) {
@@ -2029,15 +1991,13 @@ int qd_plan_destroy(qd_plan *p) {
     p->cmp_a = p->cmp_b = nullptr;
     DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();
-    for (void *q : {p->cmp_tmp, p->cmp_in, p->cmp_out}) if (q) (void)hipFree(q);
-    if (p->cmp_done) (void)hipEventDestroy(p->cmp_done);
     free_streaming(p);
     for (void *q : {(void *)p->c_h1, (void *)p->c_h2, (void *)p->c_jtab}) if (q) (void)hipFree(q);
     if (p->taps_d) (void)hipFree(p->taps_d);
     if (p->tw_d) (void)hipFree(p->tw_d);
     if (p->jtab_d) (void)hipFree(p->jtab_d);
     if (p->jtab256_d) (void)hipFree(p->jtab256_d);
-    for (NcoTabs *t : {&p->tabs_dev, &p->tabs_slot[0], &p->tabs_slot[1]}) { free_rowtab(&t->main); free_rowtab(&t->tail); for (RowTab &q : t->phase) free_rowtab(&q); t->phase.clear(); if (t->work) (void)hipFree(t->work); t->work = nullptr; if (t->done) (void)hipEventDestroy(t->done); t->done = nullptr; t->launched = false; }
+    for (NcoTabs *t : {&p->tabs_dev, &p->tabs_slot[0], &p->tabs_slot[1]}) { free_rowtab(&t->main); free_rowtab(&t->tail); for (RowTab &q : t->phase) free_rowtab(&q); t->phase.clear(); if (t->work) (void)hipFree(t->work); t->work = nullptr; if (t->cmp_tmp) (void)hipFree(t->cmp_tmp); t->cmp_tmp = nullptr; if (t->done) (void)hipEventDestroy(t->done); t->done = nullptr; t->launched = false; }
     if (p->ev_made) { (void)hipEventDestroy(p->ev0); (void)hipEventDestroy(p->ev1); }
     delete p;
     return QD_OK;
@@ -2172,8 +2132,8 @@ bool host_kind(int m) { return m == QD_MEM_HOST || m == QD_MEM_HOST_PINNED; }
 
 // Host-resident stream: chunked, double-buffered H2D / kernel / D2H on two streams (slot = chunk parity).  A pageable
 // buffer (QD_MEM_HOST) is staged through a pinned ring with a multi-threaded memcpy; QD_MEM_HOST_PINNED memory is the
-// DMA source / target itself.  Each slot owns its device buffers AND its NCO row table, so nothing a kernel in flight on
-// the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
+// DMA source / target itself.  Each slot owns its device buffers AND its launch context (row tables, a two-stage plan's
+// carrier), so nothing a kernel in flight on the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
 int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window,
              uint64_t n_windows, void *out, int out_mem, uint64_t obw) {
     const double t_begin = now_ms();
@@ -2257,7 +2217,7 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
         }
         if (hipError_t e = hipMemcpyAsync(p->dev_in[slot], hsrc, cnta * bps, hipMemcpyHostToDevice, p->streams[slot]); e != hipSuccess)
             return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(e)));
-        rc = launch_chain(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
+        rc = launch_windows(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
         if (rc) return quiesce(rc);
         void *hdst = stage_out ? p->pin_out[slot] : static_cast<void *>(static_cast<uint8_t *>(out) + (w - first_window) * obw);
         if (hipError_t e = hipMemcpyAsync(hdst, p->dev_out[slot], nw * obw, hipMemcpyDeviceToHost, p->streams[slot]); e != hipSuccess)
@@ -2272,65 +2232,6 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
     p->stats.stage_ms = stage_ms;
     p->stats.wall_ms = now_ms() - t_begin;
     return rc;
-}
-}  // namespace
-
-namespace {
-int grow(void **buf, size_t *have, size_t need) {
-    if (need <= *have) return QD_OK;
-    if (*buf) { HIPCHK(hipFree(*buf)); *buf = nullptr; *have = 0; }       // (hipFree waits for the device)
-    HIPCHK(hipMalloc(buf, need));
-    *have = need;
-    return QD_OK;
-}
-
-// windows [w0, w0 + nw) of a two-stage plan on device buffers: A filters blocks into the carrier, B transforms them; one stream, in order
-int composite_device(qd_plan *p, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t w0, uint64_t nw, void *out_d, hipStream_t st) {
-    qd_plan *a = p->cmp_a, *b = p->cmp_b;
-    const uint64_t W = p->W;
-    int rc = grow(&p->cmp_tmp, &p->cmp_tmp_bytes, (size_t)(nw * W + 16) * 8);
-    if (rc) return rc;
-    // the carrier is shared by every call on this plan: a call on another stream waits for the previous one's last kernel
-    if (p->cmp_used) HIPCHK(hipStreamWaitEvent(st, p->cmp_done, 0));
-    rc = launch_chain(a, &a->tabs_dev, src_d, src_first, src_count, w0 * a->blk_subs, nw * a->blk_subs, w0 * a->blk_subs, p->cmp_tmp, st);
-    if (rc) return rc;
-    rc = launch_chain(b, &b->tabs_dev, p->cmp_tmp, w0 * W, nw * W, w0, nw, w0, out_d, st);
-    if (rc) return rc;
-    if (!p->cmp_done) HIPCHK(hipEventCreateWithFlags(&p->cmp_done, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(p->cmp_done, st));
-    p->cmp_used = true;
-    return QD_OK;
-}
-
-int run_composite(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
-                  void *out, int out_mem, hipStream_t st) {
-    if (n_windows == 0) return QD_OK;
-    if (src_mem == QD_MEM_DEVICE && out_mem == QD_MEM_DEVICE) return composite_device(p, src, src_first, src_count, first_window, n_windows, out, st);
-    if (!host_kind(src_mem) || !host_kind(out_mem))
-        return fail(QD_ERR_UNSUPPORTED, "mixed host/device buffers are not supported; use both host or both device");
-    // host-resident stream: plain chunks (copy in, two launches, copy out) — this path serves windows of tens of thousands of source
-    // samples, where a chunk is a handful of windows; no double buffering
-    const int bps = bps_of(p->d.format);
-    const uint64_t step = (uint64_t)p->W * p->D, rpw = step + p->T, obw = out_bytes_per_window(p);
-    uint64_t cw = (64ull << 20) / (step * bps);
-    if (cw < 1) cw = 1;
-    if (cw > n_windows) cw = n_windows;
-    int rc = grow(&p->cmp_in, &p->cmp_in_bytes, (size_t)(((cw - 1) * step + rpw) * bps + 64));
-    if (rc == QD_OK) rc = grow(&p->cmp_out, &p->cmp_out_bytes, (size_t)(cw * obw + 64));
-    if (rc) return rc;
-    for (uint64_t w = first_window; w < first_window + n_windows; w += cw) {
-        const uint64_t nw = std::min<uint64_t>(cw, first_window + n_windows - w);
-        const uint64_t s0 = w * step, sc = (nw - 1) * step + rpw;
-        if (s0 < src_first || s0 + sc > src_first + src_count)
-            return fail(QD_ERR_INVALID, "src slab [%llu,+%llu) does not cover samples [%llu,+%llu) needed by windows [%llu,+%llu)", (unsigned long long)src_first,
-                        (unsigned long long)src_count, (unsigned long long)s0, (unsigned long long)sc, (unsigned long long)w, (unsigned long long)nw);
-        HIPCHK(hipMemcpyAsync(p->cmp_in, static_cast<const uint8_t *>(src) + (s0 - src_first) * bps, (size_t)(sc * bps), hipMemcpyHostToDevice, st));
-        rc = composite_device(p, p->cmp_in, s0, sc, w, nw, p->cmp_out, st);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(static_cast<uint8_t *>(out) + (w - first_window) * obw, p->cmp_out, (size_t)(nw * obw), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return QD_OK;
 }
 }  // namespace
 
@@ -2354,9 +2255,8 @@ int qd_plan_run(qd_plan *p, const void *src, int src_mem, uint64_t src_first, ui
     std::lock_guard<std::mutex> lock(p->mu);
     DeviceGuard guard(p->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->cmp_a) return run_composite(p, src, src_mem, src_first, src_count, first_window, n_windows, out, out_mem, st);
     if (src_mem == QD_MEM_DEVICE && out_mem == QD_MEM_DEVICE)
-        return launch_chain(p, &p->tabs_dev, src, src_first, src_count, first_window * subs, n_windows * subs, first_window * subs, out, st);
+        return launch_windows(p, &p->tabs_dev, src, src_first, src_count, first_window * subs, n_windows * subs, first_window * subs, out, st);
     if (!host_kind(src_mem) || !host_kind(out_mem))
         return fail(QD_ERR_UNSUPPORTED, "mixed host/device buffers are not supported; use both host or both device");
     const uint64_t obw = out_bytes_per_window(p) / subs;      // per kernel window (a sub-block for QD_EPI_CF32_BLOCKS)
@@ -2433,7 +2333,7 @@ int qd_plan_run_sharded_device(qd_plan *p, void *const *slabs, void *const *outs
             HIPCHK(hipMemcpyPeerAsync(static_cast<uint8_t *>(slabs[g]) + si.own_count * bps, si.device, slabs[g + 1],
                                       p->shard_info[g + 1].device, si.halo * bps, c->streams[0]));
         const uint64_t subs = c->blk_subs;
-        int rc = launch_chain(c, &c->tabs_dev, slabs[g], si.own_first, si.own_count + si.halo, si.w0 * subs, (si.w1 - si.w0) * subs,
+        int rc = launch_windows(c, &c->tabs_dev, slabs[g], si.own_first, si.own_count + si.halo, si.w0 * subs, (si.w1 - si.w0) * subs,
                               si.w0 * subs, outs[g], c->streams[0]);
         if (rc) return rc;
     }
@@ -2812,7 +2712,7 @@ int qd_fft_norm_batch(const qd_c32 *in, size_t W, size_t n_fft, size_t in_stride
         HIPCHK(hipMemcpyAsync(di, in, have * 8, hipMemcpyHostToDevice, st));
         src = di; dst = dout;
     }
-    rc = launch_chain(p, &p->tabs_dev, src, 0, have, 0, n_fft, 0, dst, st);
+    rc = launch_windows(p, &p->tabs_dev, src, 0, have, 0, n_fft, 0, dst, st);
     if (rc) return rc;
     if (mem != QD_MEM_DEVICE) HIPCHK(hipMemcpyAsync(norms, dst, n_fft * W * 4, hipMemcpyDeviceToHost, st));
     return finish_call(mem, st);
@@ -2880,7 +2780,7 @@ int qd_take_fft(const qd_c32 *in, uint64_t in_first, size_t n_in, uint64_t sampl
         p->row_offsets_d = static_cast<const uint64_t *>(doffs);
         p->window_d = static_cast<const float *>(dwin);
         p->d.n_samples = in_first + n_in;
-        rc = launch_chain(p, &p->tabs_dev, src, in_first, n_in, 0, output_len, 0, dst, st);
+        rc = launch_windows(p, &p->tabs_dev, src, in_first, n_in, 0, output_len, 0, dst, st);
         p->row_offsets_d = nullptr; p->window_d = nullptr;
     } else {
         rc = bluestein_rows(static_cast<const float2 *>(src), in_first, static_cast<const uint64_t *>(doffs), static_cast<const float *>(dwin),

@@ -407,6 +407,11 @@ def test_windows_larger_than_the_lds_tile(engine, oracle, fmt, D, T, W, shift):
     first, count = p.src_range(w0, cnt)
     sub = p.run_host(data[first * bps:(first + count) * bps], w0, cnt, src_first=first)
     assert np.array_equal(sub.view(np.uint32), got[w0:w0 + cnt].view(np.uint32))
+    # the host ring in 64 KiB chunks: one window per chunk, the two slots (and their carriers) alternate
+    small = engine.Plan(fmt, sr, n, chunk_bytes=1 << 16, **kw)
+    assert np.array_equal(small.run_host(data).view(np.uint32), got.view(np.uint32))
+    st = small.stats()
+    assert st.chunks > 1 and st.bytes_h2d > 0 and st.wall_ms > 0, (st.chunks, st.bytes_h2d, st.wall_ms)
     src = torch.frombuffer(bytearray(data[first * bps:(first + count) * bps]), dtype=torch.uint8).cuda()
     out = torch.empty(cnt, W, dtype=torch.float32, device="cuda")
     for _ in range(2):                                     # twice: the carrier buffer is reused

@@ -114,6 +114,44 @@ def test_concurrent_runs_on_one_plan(engine):
     assert not errors and all(bits_equal(r, want) for r in results)
 
 
+@pytest.mark.parametrize("kind", ["two-stage", "cascade"])
+def test_concurrent_device_runs_of_two_stage_and_cascade_plans(engine, kind):
+    """One two-stage plan (a window beyond the LDS tile: its carrier lives in the launch context) and one cascade plan, each run on
+    device buffers from two threads on two streams: every result equals a lone run, bit for bit."""
+    import torch
+    rng = np.random.default_rng(12)
+    if kind == "two-stage":
+        W, N = 1024, 6 * 1024 * 32 + 300
+        kw = dict(shift_hz=280000, lowpass=(150_000, 32, 200), width=W)
+    else:
+        W, N = 64, 400_000
+        kw = dict(stages=[("shift", 280000), ("lowpass", (2_000_000, 4, 40)), ("shift", -50000), ("lowpass", (200_000, 4, 24))], width=W, stride=16)
+    x = (rng.standard_normal((N, 2)) * 0.05).astype(np.float32)
+    p = engine.Plan(0, 21_000_000, N, **kw)
+    nw = p.complete_windows()
+    src = torch.from_numpy(x).cuda()
+    want = torch.empty(nw, W, dtype=torch.float32, device="cuda")
+    p.run_device(src, want, 0, nw)
+    torch.cuda.synchronize()
+    outs, errors = [torch.empty_like(want) for _ in range(2)], []
+
+    def work(i):
+        try:
+            s = torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                for _ in range(3):
+                    p.run_device(src, outs[i], 0, nw)
+            s.synchronize()
+        except Exception as e:       # noqa: BLE001
+            errors.append(e)
+
+    ts = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert not errors, errors
+    assert nw > 0 and all(torch.equal(o.view(torch.int32), want.view(torch.int32)) for o in outs)
+
+
 def test_caller_streams_may_be_destroyed_between_calls(engine):
     """The library remembers the last stream of a launch context / workspace only to COMPARE it; ordering across streams is an event.
     A caller that destroys its stream after a call and comes back on a new one (a table rewrite, a workspace regrow in between)
