@@ -53,6 +53,8 @@ def lib():
             "qo_shift_ratio": (f64, [i64, u64]),
             "qo_shift_multiplier": (None, [f64, u64, vp, vp]),
             "qo_shift_apply": (None, [vp, sz, u64, f64]),
+            "qo_shift_multipliers_f64": (None, [f64, u64, sz, vp, vp]),
+            "qo_shift_override": (i32, [vp, vp, vp, vp, sz]),
             "qo_cutoff": (f32, [u64, u64]),
             "qo_lowpass_taps": (None, [f32, sz, vp]),
             "qo_complex_convolve": (sz, [vp, sz, vp, sz, vp]),
@@ -102,6 +104,8 @@ class Chain:
     def __init__(self):
         self._node = None
         self._keep = []
+        self.shift_nodes = []          # the shift nodes, source to sink (for override_shift), and their ratios
+        self.shift_ratios = []
 
     @classmethod
     def from_bytes(cls, data, fmt, sample_rate):
@@ -123,11 +127,25 @@ class Chain:
         return self
 
     def shift(self, frequency):
+        ratio = lib().qo_shift_ratio(int(frequency), self.sample_rate())
         node = lib().qo_shift(self._node, int(frequency))
         if not node:
             raise AssertionError("Shift::new would panic")
         self._node = node
+        self.shift_nodes.append(node)
+        self.shift_ratios.append(ratio)
         return self
+
+    def override_shift(self, k, n, c, s):
+        """NOT reference behaviour (test hook): the k-th shift node, source to sink, uses the f32 multipliers (c[i], s[i]) at
+        absolute indices n[i] of its own stream; empty n removes every override of that node."""
+        n = np.ascontiguousarray(n, dtype=np.uint64)
+        c = np.ascontiguousarray(c, dtype=np.float32)
+        s = np.ascontiguousarray(s, dtype=np.float32)
+        assert n.shape == c.shape == s.shape
+        rc = lib().qo_shift_override(self.shift_nodes[k], _p(n), _p(c), _p(s), n.size)
+        if rc != 0:
+            raise ValueError("qo_shift_override: repeated index (or out of memory)")
 
     def lowpass(self, frequency, decimate=8, size=40):
         self._node = lib().qo_lowpass(self._node, int(frequency), int(decimate), int(size))
@@ -173,10 +191,12 @@ class Chain:
         _, codes = self.spark_fft(width, stride, rng, want_norms=False)
         return render(self.sample_rate(), codes)
 
-    def freq_levels(self, width=128, stride=None):
+    def freq_levels(self, width=128, stride=None, max_windows=None):
         stride = width if stride is None else stride
         ln = self.len()
         cap = (ln - width) // stride
+        if max_windows is not None:                 # the leading windows only (a chain whose last window fails read_exact)
+            cap = min(cap, max_windows)
         vals = np.zeros(max(cap, 1), dtype=np.uint8)
         got = lib().qo_freq_levels(self._node, width, stride, cap, _p(vals))
         if got == U64_MAX:
@@ -232,6 +252,16 @@ def shift_multipliers(ratio, ns):
         lib().qo_shift_multiplier(ratio, int(n), C.byref(c), C.byref(s))
         out[i] = (c.value, s.value)
     return out
+
+
+def shift_multipliers_f64(ratio, n0, count):
+    """NOT reference behaviour: the f64 cos(place), sin(place) of samples n0 .. n0+count-1 before src/shift.rs:49-50 casts them
+    to f32 (same place = (n as f64) * ratio, same glibc calls).  Returns (c, s), float64[count] each."""
+    c = np.empty(count, dtype=np.float64)
+    s = np.empty(count, dtype=np.float64)
+    if count:
+        lib().qo_shift_multipliers_f64(ratio, int(n0), count, _p(c), _p(s))
+    return c, s
 
 
 def shift_apply(x, abs_off, ratio):

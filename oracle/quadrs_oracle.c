@@ -161,6 +161,15 @@ void qo_shift_multiplier(double ratio, uint64_t n, float *c, float *s) {
     *s = (float)sin(place);
 }
 
+/* NOT reference code: the f64 values of src/shift.rs:49-50 before the `as f32` casts, same place and same glibc calls */
+void qo_shift_multipliers_f64(double ratio, uint64_t n0, size_t count, double *c, double *s) {
+    for (size_t i = 0; i < count; i++) {
+        double place = (double)(n0 + (uint64_t)i) * ratio;
+        c[i] = cos(place);
+        s[i] = sin(place);
+    }
+}
+
 /* src/shift.rs:48-52 */
 void qo_shift_apply(qo_c32 *buf, size_t n, uint64_t abs_off, double ratio) {
     for (size_t i = 0; i < n; i++) {
@@ -268,6 +277,7 @@ struct qo_node {
     int64_t *cos_hz; size_t n_cos; double seconds;
     /* shift */
     double ratio;
+    uint64_t *ov_n; qo_c32 *ov_m; size_t ov_k;      /* qo_shift_override: sorted absolute indices and their multipliers */
     /* lowpass */
     float *taps; size_t T; uint64_t D;
 };
@@ -313,8 +323,55 @@ qo_node *qo_lowpass(qo_node *inner, uint64_t frequency, uint64_t decimate, size_
 void qo_free(qo_node *n) {
     while (n) {
         qo_node *in = n->inner;
-        free(n->cos_hz); free(n->taps); free(n);
+        free(n->cos_hz); free(n->taps); free(n->ov_n); free(n->ov_m); free(n);
         n = in;
+    }
+}
+
+static int cmp_ov(const void *a, const void *b) {
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : (x > y);
+}
+
+/* NOT reference code: replace the multipliers of shift node `node` at absolute indices n[0..k) of its own stream by (c, s);
+ * k = 0 removes every override.  Returns 0, or -1 when `node` is no shift node, an index repeats or memory runs out
+ * (the node is then left without overrides). */
+int qo_shift_override(qo_node *node, const uint64_t *n, const float *c, const float *s, size_t k) {
+    if (!node || node->kind != K_SHIFT) return -1;
+    free(node->ov_n); free(node->ov_m);
+    node->ov_n = NULL; node->ov_m = NULL; node->ov_k = 0;
+    if (k == 0) return 0;
+    struct ov { uint64_t n; qo_c32 m; } *t = (struct ov *)malloc(sizeof(*t) * k);
+    if (!t) return -1;
+    for (size_t i = 0; i < k; i++) { t[i].n = n[i]; t[i].m.re = c[i]; t[i].m.im = s[i]; }
+    qsort(t, k, sizeof(*t), cmp_ov);
+    for (size_t i = 1; i < k; i++)
+        if (t[i].n == t[i - 1].n) { free(t); return -1; }
+    node->ov_n = (uint64_t *)malloc(sizeof(uint64_t) * k);
+    node->ov_m = (qo_c32 *)malloc(sizeof(qo_c32) * k);
+    if (!node->ov_n || !node->ov_m) {
+        free(node->ov_n); free(node->ov_m); free(t);
+        node->ov_n = NULL; node->ov_m = NULL;
+        return -1;
+    }
+    for (size_t i = 0; i < k; i++) { node->ov_n[i] = t[i].n; node->ov_m[i] = t[i].m; }
+    node->ov_k = k;
+    free(t);
+    return 0;
+}
+
+/* qo_shift_apply with the node's overridden multipliers in place of the computed ones */
+static void shift_apply_overridden(const qo_node *n, qo_c32 *buf, size_t valid, uint64_t off) {
+    size_t lo = 0, hi = n->ov_k;                    /* first override at or past `off` */
+    while (lo < hi) {
+        size_t mid = lo + (hi - lo) / 2;
+        if (n->ov_n[mid] < off) lo = mid + 1; else hi = mid;
+    }
+    for (size_t i = 0; i < valid; i++) {
+        qo_c32 m;
+        if (lo < n->ov_k && n->ov_n[lo] == off + (uint64_t)i) m = n->ov_m[lo++];
+        else qo_shift_multiplier(n->ratio, off + (uint64_t)i, &m.re, &m.im);
+        buf[i] = c_mul(buf[i], m);
     }
 }
 
@@ -373,6 +430,10 @@ size_t qo_read_at(const qo_node *n, uint64_t off, qo_c32 *buf, size_t len) {
     case K_SHIFT: {                                 /* src/shift.rs:46-54 */
         size_t valid = qo_read_at(n->inner, off, buf, len);
         if (valid == QO_PANIC) return QO_PANIC;
+        if (n->ov_k) {                              /* test hook, never set by a reference path */
+            shift_apply_overridden(n, buf, valid, off);
+            return valid;
+        }
         qo_shift_apply(buf, valid, off, n->ratio);
         return valid;
     }

@@ -71,6 +71,12 @@ void     qo_set_lowpass_closed_form(int on);
 double   qo_shift_ratio(int64_t frequency, uint64_t sample_rate);     /* src/shift.rs:28 */
 void     qo_shift_multiplier(double ratio, uint64_t n, float *c, float *s); /* src/shift.rs:49-50 */
 void     qo_shift_apply(qo_c32 *buf, size_t n, uint64_t abs_off, double ratio);
+/* NOT reference code, for the NCO rule of the tests: the f64 cos/sin(place) of samples n0 .. n0+count-1 before the f32 casts
+ * (same place, same glibc calls as qo_shift_multiplier) */
+void     qo_shift_multipliers_f64(double ratio, uint64_t n0, size_t count, double *c, double *s);
+/* NOT reference code: shift node `node` uses (c[i], s[i]) as the multiplier of absolute index n[i] of its own stream; k = 0
+ * removes every override (and a node without one pays nothing per sample).  0 ok, -1 not a shift node / repeated index / out of memory. */
+int      qo_shift_override(qo_node *node, const uint64_t *n, const float *c, const float *s, size_t k);
 
 /* ---- A4: taps (src/filter.rs:86-105,126-128) ---- */
 float    qo_cutoff(uint64_t frequency, uint64_t sample_rate);

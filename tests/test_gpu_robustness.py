@@ -50,6 +50,82 @@ def test_far_offset_slab_uses_second_order_nco(engine, oracle, lp, W, S):
     from test_gpu_parity import record_observed
     record_observed(f"deep-stream windows W={W} S={S}", exact_fraction=float(exact), worst_ulp_of_window_max=float(worst))
     assert exact >= 0.9999 and worst <= 1.0, (exact, worst)
+    from test_gpu_parity import assert_explained
+    assert_explained(ref, got, (p, w0), f"deep-stream windows W={W} S={S}")
+
+
+def _deep_nofir_windows(engine, oracle, sr, freq, W, nco_order, w0, nwin, seed=77):
+    """(plan, GPU norms, oracle norms) of windows w0 ... of a lowpass-free cf32 plan over a 2^34-sample stream, the reference
+    from the oracle's primitives at absolute indices (shift, Radix4, hypotf, fftshift)"""
+    import ctypes as C
+    p = engine.Plan(0, sr, 1 << 34, shift_hz=freq, width=W, stride=W, nco_order=nco_order)
+    first, count = p.src_range(w0, nwin)
+    x = (np.random.default_rng(seed).standard_normal((count, 2)) * 0.03).astype(np.float32)
+    got = p.run_host(x.tobytes(), w0, nwin, src_first=first)
+    y = np.ascontiguousarray(oracle.shift_apply(x, first, oracle.shift_ratio(freq, sr))[:nwin * W])
+    L = oracle.lib()
+    f = L.qo_fft_new(W)
+    base = y.ctypes.data
+    for i in range(nwin):
+        L.qo_fft_process(f, C.c_void_p(base + i * W * 8))
+    L.qo_fft_free(f)
+    ref = oracle.norm(y).reshape(nwin, W)[:, np.r_[W // 2:W, 0:W // 2]]
+    return p, got, ref
+
+
+def test_cascade_deep_shift_obeys_the_nco_rule(engine, oracle):
+    """k_cascade's NCO (casc_nco) deep in a 2^34-sample stream with a shift of sr/2 - 1 after a two-tap lowpass (|place| ~ 5e10
+    rad, where only the second-order form is within NCO_ABS_ERR): every differing window must be explained.  The same windows
+    on a first-order NCO leave dozens unexplained (test_nco_rule_catches_first_order_far_out)."""
+    import ctypes as C
+    from test_gpu_parity import assert_explained
+    sr, W = 21_000_000, 4
+    freq = sr // 2 - 1
+    stages = [("lowpass", (5_000_000, 1, 2)), ("shift", freq)]
+    nwin = 1 << 18
+    w0 = ((1 << 34) - (1 << 21)) // W
+    p = engine.Plan(0, sr, 1 << 34, stages=stages, width=W, stride=W)
+    assert "k_cascade" in p.kernel_name(), p.kernel_name()
+    first, count = p.src_range(w0, nwin)
+    x = (np.random.default_rng(78).standard_normal((count, 2)) * 0.03).astype(np.float32)
+    got = p.run_host(x.tobytes(), w0, nwin, src_first=first)
+    k, y = oracle.lowpass_block(oracle.taps(5_000_000, sr, 2), 1, x)
+    assert k == nwin * W and first == w0 * W
+    y = np.ascontiguousarray(oracle.shift_apply(y, w0 * W, oracle.shift_ratio(freq, sr)))
+    L = oracle.lib()
+    f = L.qo_fft_new(W)
+    for i in range(nwin):
+        L.qo_fft_process(f, C.c_void_p(y.ctypes.data + i * W * 8))
+    L.qo_fft_free(f)
+    ref = oracle.norm(y).reshape(nwin, W)[:, np.r_[W // 2:W, 0:W // 2]]
+    assert_explained(ref, got, (p, w0), "cascade deep shift W=4")
+    p.close()
+
+
+def test_nco_rule_catches_first_order_far_out(engine, oracle):
+    """The rule's negative control, in every suite run: deep in a 2^34-sample stream with a shift of sr/2 - 1 (|place| ~ 5e10 rad)
+    a forced first-order NCO drops r^2/2 up to 7e-12, which flips about one multiplier component in 10^4 -- far more than
+    the rule explains; the same slab on the automatic (second-order) NCO has no unexplained window."""
+    from util import explain_check
+    from test_gpu_parity import record_observed
+    sr, W = 21_000_000, 4
+    freq = sr // 2 - 1
+    nwin = 1 << 18
+    w0 = ((1 << 34) - (1 << 21)) // W
+    res = {}
+    for order in (1, 0):
+        p, got, ref = _deep_nofir_windows(engine, oracle, sr, freq, W, order, w0, nwin)
+        assert ("nco 1" if order == 1 else "nco 2") in p.kernel_name(), p.kernel_name()
+        detail = {}
+        bad = explain_check(p, ref, got, w0, detail)
+        scale = ulp_of(ref.max(axis=-1, keepdims=True)).astype(np.float64)
+        worst = float((np.abs(ref.astype(np.float64) - got.astype(np.float64)) / scale).max())
+        res[order] = dict(windows=nwin, differing=len(detail), unexplained=len(bad), worst_ulp_of_window_max=worst,
+                          old_bound_passes=bool(worst <= 1.0 and (ref.view(np.uint32) == got.view(np.uint32)).mean() >= 0.9999))
+        record_observed(f"negative control nco_order={order}", **res[order])
+        p.close()
+    assert res[1]["unexplained"] >= 10, res
+    assert res[0]["unexplained"] == 0, res
 
 
 def test_fine_grained_calls_on_device_memory(engine, oracle):
@@ -963,8 +1039,10 @@ def test_overlapping_windows_with_a_shift_as_interleaved_launches(engine, oracle
                 assert j.info.tile_windows == R * max(1, 512 // W)
             a, b = j.run_host(data), g.run_host(data)
             assert a.shape == b.shape
+            from test_gpu_parity import assert_explained
             if epi != engine.EPI_NORMS_F32:
                 assert (a != b).mean() <= 2e-3, (fmt, W, S, float((a != b).mean()))      # glyph cells next to a threshold
+                assert_explained(b, a, (j, 0), f"interleaved glyph fmt={fmt} W={W} S={S} vs generic")   # ... of explained windows
                 j.close(); g.close()
                 continue
             for other, what in ((b, "generic"), (ref, "oracle")):
@@ -972,6 +1050,7 @@ def test_overlapping_windows_with_a_shift_as_interleaved_launches(engine, oracle
                 mx = np.maximum(np.abs(other).max(axis=1, keepdims=True), 1e-30)
                 assert (np.abs(a.astype(np.float64) - other) / np.spacing(mx.astype(np.float32))).max() <= 1.0, (fmt, W, S, what)
                 assert (a.view(np.uint32) == other.astype(np.float32).view(np.uint32)).mean() >= 0.999, (fmt, W, S, what)
+                assert_explained(other, a, (j, 0), f"interleaved fmt={fmt} W={W} S={S} vs {what}")
             # the host path in many chunks: chunk boundaries fall on the launches' row grids, so the bytes are the one-chunk run's
             jc = engine.Plan(fmt, sr, n, kernel_policy=_ffi.KERNEL_SPECIALISE, chunk_bytes=1 << 16, **kw)
             assert np.array_equal(jc.run_host(data), a), (fmt, W, S, "chunked host path")
@@ -990,6 +1069,7 @@ def test_overlapping_windows_with_a_shift_as_interleaved_launches(engine, oracle
                 sub = j.run_host(data[first * bps:(first + count) * bps], w0, nw - w0, src_first=first)
                 mx = np.maximum(np.abs(a[w0:]).max(axis=1, keepdims=True), 1e-30)
                 assert (np.abs(sub.astype(np.float64) - a[w0:]) / np.spacing(mx)).max() <= 1.0, (fmt, W, S, "off-grid range")
+                assert_explained(a[w0:], sub, (j, w0), f"interleaved fmt={fmt} W={W} S={S} off-grid range")
             j.close(); g.close()
 
 

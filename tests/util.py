@@ -139,7 +139,22 @@ def fuzz_chain_shapes(Q, n_shapes, seed, log=None, oracle=None, variants_only=Fa
                     with np.errstate(invalid="ignore"):
                         scale = ulp_of(np.nanmax(np.where(np.isnan(ref), -np.inf, ref), axis=-1, keepdims=True)).astype(np.float64)
                         close = np.abs(ref.astype(np.float64) - got.astype(np.float64)) <= 1.0 * scale
-                    ok = bool((close | both_nan).all())
+                    ok = bool((close | both_nan).all()) and not explain_check(
+                        ([("shift", shift), ("lowpass", (1_000_000, D, T))], W, S, 21_000_000), ref, got)
+            if ok and epi != 0 and oracle is not None and not isinstance(a, str) and a.shape[0] > 0:
+                # glyph cells / bucket digits against the oracle's: equal, except (with a shift) in windows the NCO rule explains
+                ch = oracle.Chain.from_bytes(data.tobytes(), fmt, 21_000_000)
+                if shift is not None:
+                    ch = ch.shift(shift)
+                ch = ch.lowpass(1_000_000, D, T)
+                if epi == 1:
+                    ref = ch.spark_fft(W, S, max_windows=24, want_norms=False)[1]
+                else:
+                    ref = ch.freq_levels(W, S, max_windows=24)
+                got = a[:ref.shape[0]]
+                n_ = ref.shape[0]
+                chain = (([("shift", shift)] if shift is not None else []) + [("lowpass", (1_000_000, D, T))], W, S, 21_000_000)
+                ok = got.shape == ref.shape and not explain_check(chain, ref.reshape(n_, -1), got.reshape(n_, -1))
             desc = f"fmt={fmt} W={W} S={S} D={D} T={T} shift={shift} N={N} epi={epi} tune={tune} kinds={info}"
             if log:
                 log(("ok  " if ok else "BAD ") + desc)
@@ -198,11 +213,16 @@ def fuzz_nofir_shapes(Q, n_shapes, seed, log=None, oracle=None, stats=None):
         # interleaved launch) — DESIGN section 4.  Sinks that quantise then differ in a cell next to a threshold at most.
         exact = shift is None or (fmt == 0 and S >= W)
 
-        def same(x, y):
+        chain = ([("shift", shift)] if shift is not None else [], W, S, 21_000_000)
+
+        def same(x, y, w0=0):
             if x.shape != y.shape:
                 return False
             if exact:
                 return x.tobytes() == y.tobytes()
+            # both within NCO_ABS_ERR of the truth: they may differ only in windows that read an ambiguous multiplier
+            if explain_check(chain, y.reshape(y.shape[0], -1), x.reshape(x.shape[0], -1), w0):
+                return False
             if x.dtype != np.float32:
                 return float((x != y).mean()) <= 5e-3
             scale = ulp_of(np.maximum(np.abs(y).max(axis=-1, keepdims=True), 1e-30)).astype(np.float64)
@@ -214,7 +234,7 @@ def fuzz_nofir_shapes(Q, n_shapes, seed, log=None, oracle=None, stats=None):
             cnt = int(rng.integers(1, nw - w0 + 1))
             first, count = j.src_range(w0, cnt)
             sub = j.run_host(raw[first * bps:(first + count) * bps], w0, cnt, src_first=first)
-            ok = same(sub, a[w0:w0 + cnt])
+            ok = same(sub, a[w0:w0 + cnt], w0)
             if not ok:
                 desc += f" SUB-RANGE w0={w0} cnt={cnt}"
         if ok and epi == 0 and oracle is not None and nw > 0:
@@ -227,7 +247,7 @@ def fuzz_nofir_shapes(Q, n_shapes, seed, log=None, oracle=None, stats=None):
                 ok = bits_equal(ref, got)
             else:
                 scale = ulp_of(np.maximum(np.abs(ref).max(axis=-1, keepdims=True), 1e-30)).astype(np.float64)
-                ok = bool((np.abs(ref.astype(np.float64) - got.astype(np.float64)) <= scale).all())
+                ok = bool((np.abs(ref.astype(np.float64) - got.astype(np.float64)) <= scale).all()) and not explain_check(chain, ref, got)
             if not ok:
                 desc += " ORACLE"
         j.close(); g.close()
@@ -243,7 +263,8 @@ def full_size_census(Q, O, bench, name):
     """EVERY window of BASELINE workload `name` at its full size: HIP chain kernel against the CPU oracle in its cheapest exact
     form (FIR at the decimated positions only, same products, same order) on all host cores, same input bytes, absolute sample
     indices.  Returns (n_windows, kernel_kind, windows_differing, bins_differing, worst deviation in ulp of the window maximum,
-    first differing window or None, seconds on the GPU side, seconds in the oracle, threads)."""
+    every differing window as a dict (index, explained by the NCO rule, its replay and the flips the replay found), seconds
+    on the GPU side, seconds in the oracle (the comparison pass), threads)."""
     import concurrent.futures as cf
     import os
     import time
@@ -290,17 +311,39 @@ def full_size_census(Q, O, bench, name):
         scale = np.spacing(np.abs(ref).max(axis=1, keepdims=True).astype(np.float32)).astype(np.float64)
         err = (np.abs(ref.astype(np.float64) - g.astype(np.float64)) / scale).max()
         rows = np.nonzero(ne.any(axis=1))[0]
-        return len(rows), int(ne.sum()), float(err), int(a + rows[0])
+        return len(rows), int(ne.sum()), float(err), [int(a + r) for r in rows]
 
     nw = nb = 0
-    worst, first = 0.0, None
+    worst, diff = 0.0, []
     t0 = time.perf_counter()
     with cf.ThreadPoolExecutor(cores) as ex:
         for a, b, err, f in ex.map(work, jobs):
             nw += a; nb += b; worst = max(worst, err)
-            if f is not None and first is None:
-                first = f
-    return total, int(p.info.kernel_kind), nw, nb, worst, first, t_gpu, time.perf_counter() - t0, cores
+            if f:
+                diff += f
+    t_cpu = time.perf_counter() - t0
+    # every differing window under the NCO rule, and its replay through the oracle's override hook
+    stages = ([("shift", cfg["shift"])] if cfg["shift"] is not None else []) + [("lowpass", tuple(cfg["lp"]))]
+    desc = (stages, cfg["W"], cfg["S"], cfg["sr"])
+    windows = []
+    for w in diff:
+        ref, _ = ch.spark_fft(cfg["W"], cfg["S"], first_window=w, max_windows=1, want_codes=False)
+        detail = {}
+        bad = unexplained_windows(ref, got[w:w + 1], lambda v: shift_spans(desc, v), shift_ratios(desc), w, detail)
+        combo = replay_window(ch, w, detail.get(w, []), got[w], cfg["W"], cfg["S"]) if not bad else None
+        rec = dict(window=w, explained=not bad, ambiguous=len(detail.get(w, [])), replay=combo)
+        if combo:
+            # what flipped: sample, component, distance of the f64 value to its f32 rounding boundary in f32 ulp
+            rec["flips"] = []
+            for k, n, comp, v in combo:
+                c, s_ = O.shift_multipliers_f64(shift_ratios(desc)[k], n, 1)
+                v64 = (c, s_)[comp][0]
+                if np.float32(v64) != np.float32(v):
+                    mid = (float(np.float32(v64)) + float(np.float32(v))) / 2
+                    rec["flips"].append(dict(stage=k, sample=n, comp="cos" if comp == 0 else "sin",
+                                             boundary_distance_ulp=abs(v64 - mid) / abs(float(np.spacing(np.float32(v64))))))
+        windows.append(rec)
+    return total, int(p.info.kernel_kind), nw, nb, worst, windows, t_gpu, t_cpu, cores
 
 
 def casc_fir_class(D):
@@ -431,12 +474,16 @@ def fuzz_cascade_shapes(Q, n_shapes, seed, oracle, log=None, cov=None, observed=
                     observed["bins"] += int(ex.size)
                     observed["exact"] += int(ex.sum())
                     observed["worst_ulp"] = max(observed["worst_ulp"], worst)
-                    ok = bool(ex.all()) if not shifted else worst <= 1.0
+                    ok = bool(ex.all()) if not shifted else (worst <= 1.0 and not explain_check((stages, W, S, sr), ref, got, a))
                 elif epi == 1:
                     rn, rc = ch.spark_fft(W, S, rng=rng_g, first_window=a, max_windows=c)
                     ok = codes_edge_ok(rc, got, rn, *rng_g)[0]
+                    # a differing cell is also in a window the NCO rule explains (shift-free: no cell differs)
+                    ok = ok and not explain_check((stages, W, S, sr), rc, got, a)
                 else:
                     ok = bucket_digits_ok(ref, got)
+                    lv = ch.freq_levels(W, S, max_windows=a + c)[a:a + c]
+                    ok = ok and lv.shape == got.shape and not explain_check((stages, W, S, sr), lv.reshape(c, 1), got.reshape(c, 1), a)
                 if not ok:
                     desc += f" ORACLE windows [{a}, +{c})"
             if ok and done > 1:
@@ -473,3 +520,262 @@ def fuzz_cascade_shapes(Q, n_shapes, seed, oracle, log=None, cov=None, observed=
         if not ok:
             bad.append(desc)
     return checked, bad
+
+
+# ------------------------------------------------------------------ the NCO rule
+#
+# A shifted result may differ from the oracle only where the NCO explains it: in a window that reads a sample whose reference
+# multiplier component is ambiguous, i.e. whose glibc f64 value lies within NCO_ABS_ERR of an f32 rounding boundary.
+
+NCO_ABS_ERR = 2e-15
+"""Absolute bound on |device f64 multiplier component - glibc f64 cos/sin(place)| before the f32 casts (qd_device.h, nco_*).
+Every value involved has magnitude <= 1, where 1 ulp of f64 is <= 2^-53 = 1.1e-16 and a rounding costs <= 0.56e-16.
+  * table entries (nco_table_entry): the device sincos of the rounded product, <= 2 ulp = 2.2e-16, plus the final rounding of
+    the lo-correction, 0.56e-16 (its dropped lo^4/24 is < 1e-23 for |lo| <= 2^-18): <= 2.8e-16 per entry;
+  * rotation (nco_mul: C = rb.c lr.c - rb.s lr.s, S alike): the entries' errors weighted by |lr.c| + |lr.s| <= sqrt 2 and
+    |rb.c| + |rb.s| <= sqrt 2, 2 sqrt 2 * 2.8e-16 = 7.9e-16, plus the product's and the fma's roundings, 1.1e-16: <= 9.0e-16;
+  * residual correction (c = C + r S - ...): at most two roundings, 1.1e-16; r times the rotation's error is < 1e-21;
+  * the dropped term: r^2/2 <= 1.1e-16 on the first-order form (|place| <= 2^28 rad, |r| <= 2^-26); r^3/6 < 1e-17 on the
+    second-order form (|place| < 2^36 rad, |r| <= 2^-18: every 2^34-sample stream at any shift);
+  * glibc's own cos/sin, < 1 ulp: 1.1e-16.
+Sum 1.23e-15; the bound keeps a margin of 1.6x.  The rule's mutation tests need it below 1e-14: never raise it to pass a test."""
+
+
+def _f32_round_exact(t, e):
+    """f32 round-to-nearest-even of the exact reals t + e (t float64, e the exact residual of t with |e| <= ulp(t)/2)"""
+    f = t.astype(np.float32)
+    f64 = f.astype(np.float64)
+    up = np.nextafter(f, np.float32(np.inf))
+    dn = np.nextafter(f, np.float32(-np.inf))
+    mid_up = (f64 + up.astype(np.float64)) * 0.5            # exact in f64
+    mid_dn = (f64 + dn.astype(np.float64)) * 0.5
+    # t lies exactly on a midpoint: the residual's sign decides; otherwise t + e rounds like t (a midpoint is >= 1 f64 ulp away)
+    f = np.where((t == mid_up) & (e > 0), up, f)
+    f = np.where((t == mid_dn) & (e < 0), dn, f)
+    return f
+
+
+def nco_candidates(v64, eps=NCO_ABS_ERR):
+    """(lo32, hi32): the smallest and the largest f32 that round-to-nearest gives for any real x in [v - eps, v + eps], per
+    element of the f64 array v64.  Every f32 in [lo32, hi32] is such a value (rounding is monotone).  A component is
+    ambiguous where lo32 != hi32."""
+    v = np.asarray(v64, dtype=np.float64)
+    out = []
+    for b in (-eps, eps):
+        t = v + b                                            # TwoSum: v + b == t + e exactly
+        bb = t - v
+        e = (v - (t - bb)) + (b - bb)
+        out.append(_f32_round_exact(t, e))
+    return out[0], out[1]
+
+
+def _chain_of(desc):
+    """(stages, W, S, sample_rate) of a Plan, or of a tuple (stages, W, S[, sample_rate])"""
+    if isinstance(desc, tuple):
+        stages, W, S = desc[0], desc[1], desc[2]
+        return list(stages), int(W), int(S), (int(desc[3]) if len(desc) > 3 else None)
+    d = desc.desc
+    stages = desc.stages
+    if stages is None:
+        stages = ([("shift", int(d.shift_hz))] if d.has_shift else []) + \
+                 ([("lowpass", (int(d.lowpass_hz), int(d.decimate), int(d.taps)))] if d.has_lowpass else [])
+    return list(stages), int(d.width), int(d.stride), int(d.sample_rate)
+
+
+def shift_ratios(desc):
+    """the ratio of each shift stage, source to sink: TAU * f / (that stage's input rate) (src/shift.rs:28)"""
+    import math
+    stages, _, _, sr = _chain_of(desc)
+    out = []
+    for kind, arg in stages:
+        if kind == "shift":
+            out.append(math.tau * float(arg) / float(sr))
+        else:
+            sr //= int(arg[1])
+    return out
+
+
+def shift_spans(desc, window):
+    """For each shift stage (source to sink): the half-open range [lo, hi) of absolute indices, at that stage's rate, that
+    sink window `window` (an int or an int array) reads — window w reads [w S, w S + W) of the last stage (spark_fft, and the
+    write sink's blocks with S = W = B).  A lowpass (D, T) serves a read of outputs [b0, b1) with ONE block read [b0 D, b1 D + T)
+    of its input, and output k of it reads inputs k D + c ... k D + c + T - 1 (c = T - T/2, src/filter.rs:68-83,
+    complex_convolve's kept outputs) that lie inside that block.  So the block and the dependency range [lo, hi) are carried
+    separately: lo' = lo D + c, hi' = min((hi - 1) D + c + T, b1 D + T), block' = [b0 D, b1 D + T).  Exact, up to the tail
+    truncation of a block, which only removes samples: never inward, outward by less than one FIR length per stage.  With a
+    Plan the source-rate spans are checked to lie in its src_range."""
+    stages, W, S, _ = _chain_of(desc)
+    w = np.asarray(window, dtype=np.int64)
+    lo, hi = w * S, w * S + W
+    b0, b1 = lo, hi                                          # the block read at this stage's rate
+    spans = []
+    for kind, arg in reversed(stages):
+        if kind == "shift":
+            spans.append((lo, hi))
+        else:
+            D, T = int(arg[1]), int(arg[2])
+            c = T - T // 2
+            lo, hi = lo * D + c, np.minimum((hi - 1) * D + c + T, b1 * D + T)
+            b0, b1 = b0 * D, b1 * D + T
+    spans.reverse()
+    if not isinstance(desc, tuple) and np.ndim(window) == 0 and stages and stages[0][0] == "shift":
+        a, n = desc.src_range(int(window), 1)
+        assert a <= int(spans[0][0]) and int(spans[0][1]) <= a + n, (spans[0], a, n)
+    if np.ndim(window) == 0:
+        spans = [(int(a), int(b)) for a, b in spans]
+    return spans
+
+
+def ambiguous_components(ratio, lo, hi, eps=NCO_ABS_ERR):
+    """the ambiguous multiplier components of samples [lo, hi) of a shift with `ratio`: a list of (n, comp, candidates),
+    comp 0 = cos / 1 = sin, candidates the f32 values round-to-nearest may give (float32 array; None past 64 of them)"""
+    from oracle import oracle as O
+    out = []
+    if hi <= lo:
+        return out
+    c, s = O.shift_multipliers_f64(ratio, lo, hi - lo)
+    for comp, v in ((0, c), (1, s)):
+        a, b = nco_candidates(v, eps)
+        for i in np.nonzero(a != b)[0]:
+            ia, ib = int(a[i:i + 1].view(np.int32)[0]), int(b[i:i + 1].view(np.int32)[0])
+            cand = None                                      # a zero crossing, or too many values to enumerate
+            if (a[i] > 0 or b[i] < 0) and abs(ib - ia) <= 64:
+                cand = np.arange(min(ia, ib), max(ia, ib) + 1, dtype=np.int64).astype(np.int32).view(np.float32)
+            out.append((int(lo + i), comp, cand))
+    return out
+
+
+def differing_windows(ref, got):
+    """rows (windows) whose bytes differ, NaN-aware: a NaN against a NaN is no difference"""
+    ref = np.ascontiguousarray(ref)
+    got = np.ascontiguousarray(got)
+    assert ref.shape == got.shape, (ref.shape, got.shape)
+    n = ref.shape[0]
+    a = ref.reshape(n, -1)
+    b = got.reshape(n, -1)
+    ne = a.view(np.uint8).reshape(n, -1) != b.view(np.uint8).reshape(n, -1)
+    if a.dtype.kind == "f":
+        ne = (a.view(np.uint32 if a.itemsize == 4 else np.uint64) != b.view(np.uint32 if a.itemsize == 4 else np.uint64)) & \
+             ~(np.isnan(a) & np.isnan(b))
+    return np.nonzero(ne.any(axis=1))[0]
+
+
+def unexplained_windows(ref, got, spans_fn, ratios, first_window=0, detail=None, eps=NCO_ABS_ERR):
+    """The NCO rule.  The windows (absolute indices first_window + row) in which ref and got differ at all (bytes, NaN-aware) but
+    whose spans_fn(w) (one [lo, hi) per shift stage, see shift_spans) hold no ambiguous multiplier component of that stage's
+    ratio.  Ambiguity is computed over the differing windows' spans only.  With `detail` (a dict) every differing window maps
+    to its ambiguous components [(stage, n, comp, candidates), ...]."""
+    bad = []
+    for r in differing_windows(ref, got):
+        w = first_window + int(r)
+        amb = []
+        for k, ((lo, hi), ratio) in enumerate(zip(spans_fn(w), ratios)):
+            amb += [(k,) + a for a in ambiguous_components(ratio, int(lo), int(hi), eps)]
+        if detail is not None:
+            detail[w] = amb
+        if not amb:
+            bad.append(w)
+    return bad
+
+
+def explain_check(desc, ref, got, first_window=0, detail=None):
+    """unexplained_windows for a Plan (or (stages, W, S, sample_rate)) whose windows first_window ... are ref / got"""
+    return unexplained_windows(ref, got, lambda w: shift_spans(desc, w), shift_ratios(desc), first_window, detail)
+
+
+def _window_eval(chain, w, width, stride, sink):
+    if sink == "blocks":
+        n, out = chain.read_at(w * width, width)
+        return out if n == width else None
+    return chain.spark_fft(width, stride, first_window=w, max_windows=1, want_codes=False)[0]
+
+
+def replay_window(chain, w, ambiguous, got_w, width, stride=None, sink="norms", limit=256):
+    """Replay window w of the oracle Chain through the shift override hook with other candidate values of its ambiguous
+    components (as unexplained_windows reports them in `detail`): first every single component changed to each of its other
+    candidates, then every pair, the components of largest magnitude first, at most `limit` replays.  Components with too
+    many candidates to enumerate (zero crossings) keep the reference's value.  Returns the combination
+    [(stage, n, comp, value), ...] of every enumerated component whose output equals got_w bit for bit (NaN-aware), or
+    None.  The hook is cleared on return."""
+    import itertools
+    from oracle import oracle as O
+    stride = width if stride is None else stride
+    amb = sorted((a for a in ambiguous if a[3] is not None), key=lambda a: -float(np.abs(a[3]).max()))
+    if not amb:
+        return None
+    got_w = np.asarray(got_w).reshape(1, -1)
+    base = {}
+    for k, n, comp, cand in amb:
+        if (k, n) not in base:
+            c, s = O.shift_multipliers_f64(chain.shift_ratios[k], n, 1)
+            base[(k, n)] = [np.float32(c[0]), np.float32(s[0])]
+    alts = [[v for v in a[3] if v != base[(a[0], a[1])][a[2]]] for a in amb]
+
+    def combos():
+        for r in (1, 2):
+            for idx in itertools.combinations(range(len(amb)), r):
+                for vals in itertools.product(*[alts[i] for i in idx]):
+                    yield dict(zip(idx, vals))
+    try:
+        for tried, change in enumerate(combos()):
+            if tried >= limit:
+                return None
+            mults = {key: list(v) for key, v in base.items()}
+            for i, val in change.items():
+                k, n, comp, _ = amb[i]
+                mults[(k, n)][comp] = val
+            for k in {key[0] for key in mults}:
+                ns = [n for (kk, n) in mults if kk == k]
+                chain.override_shift(k, ns, [mults[(k, n)][0] for n in ns], [mults[(k, n)][1] for n in ns])
+            out = _window_eval(chain, w, width, stride, sink)
+            if out is not None and len(differing_windows(np.asarray(out).reshape(1, -1), got_w)) == 0:
+                return [(a[0], a[1], a[2], float(change.get(i, base[(a[0], a[1])][a[2]]))) for i, a in enumerate(amb)]
+    finally:
+        for k in range(len(chain.shift_nodes)):
+            chain.override_shift(k, [], [], [])
+    return None
+
+
+def _two_prod_err(a, b):
+    """the exact rounding error of the f64 product a*b (Dekker): a*b == fl(a*b) + err"""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah = ca - (ca - a)
+    al = a - ah
+    bh = cb - (cb - b)
+    bl = b - bh
+    return ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def nco_sensitive_samples(ratio, n0, count, chunk=1 << 22, eps=NCO_ABS_ERR):
+    """Samples n in [n0, n0 + count) with a component that is NOT ambiguous and yet lies closer to its f32 rounding boundary
+    than the second-order term r^2/2 |v| of the reference's residual r = n ratio - fl(n ratio): an NCO that drops that term
+    rounds it the other way, a correct one must give the reference's bits.  Returns the sorted indices (numpy int64)."""
+    from oracle import oracle as O
+    found = []
+    for a in range(n0, n0 + count, chunk):
+        n = np.arange(a, min(a + chunk, n0 + count), dtype=np.float64)
+        r = _two_prod_err(n, np.float64(ratio))
+        place = n * ratio
+        d = 0.5 * r * r                                      # relative size of the dropped term
+        keep = d > 4 * eps
+        n, place, d = n[keep], place[keep], d[keep]
+        for v in (np.cos(place), np.sin(place)):            # a pre-selection; the survivors are re-checked on glibc's values
+            f = v.astype(np.float32)
+            out = np.nextafter(f, np.where(v < 0, np.float32(-np.inf), np.float32(np.inf)).astype(np.float32))
+            dist = np.abs((f.astype(np.float64) + out.astype(np.float64)) / 2) - np.abs(v)
+            sel = (dist > 3 * eps) & (dist < np.abs(v) * d - 3 * eps)
+            found += [int(x) for x in n[sel]]
+    out = []
+    for k in sorted(set(found)):
+        c, s = O.shift_multipliers_f64(ratio, k, 1)
+        r = float(_two_prod_err(np.float64(k), np.float64(ratio)))
+        for v in (c[0], s[0]):
+            lo, hi = nco_candidates(np.array([v]), eps)
+            f = np.float32(v)
+            nb = np.nextafter(f, np.float32(-np.inf) if v < 0 else np.float32(np.inf))
+            dist = abs((float(f) + float(nb)) / 2) - abs(v)
+            if lo[0] == hi[0] and 2 * eps < dist < abs(v) * 0.5 * r * r - 2 * eps:
+                out.append(k)
+                break
+    return np.array(out, dtype=np.int64)
