@@ -4,8 +4,7 @@
 One "step" = one pass of the hot path over this rank's slab of a synthetic IQ stream that is
 already resident in HBM.  Default workload = the configuration BASELINE.json's north_star target is
 quoted on ("cfg3p"): a 16 GiB cf32 stream per GPU, shift -> 200-tap FIR decimate 32 -> 128-pt FFT.
-The other BASELINE configs (cfg2 / cfg3 / cfg4) are `--workload` choices and, in the default
-one-GPU run, are also timed briefly and reported under "others".
+The other BASELINE configs (cfg2 / cfg3 / cfg4 / cfg5) are `--workload` choices.
 
 With --gpus N the stream is N slabs (weak scaling), sharded by contiguous window ranges with a
 (W-S)*D+T-sample halo fetched once from the next rank over RCCL.  `python bench.py --gpus N` with no
@@ -15,9 +14,17 @@ launcher starts its own N rank processes (before anything touches the GPU); unde
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline     — both roofs of the chain kernel: HBM (algorithmic bytes per launch / mean kernel time
                  from HIP events on the launch stream, peak 8 TB/s) and VALU (the chain's arithmetic at
-                 the issue rates measured by scripts/ubench_valu.hip); "bound" names the lower one;
+                 the issue rates measured by scripts/ubench_valu.hip); "bound" names the lower one.
+A plain run does only that: set up, warm up, time the steps, dump (--dump-outputs) and print.
+--full adds everything that takes runs of its own:
   cpu_baseline — the CPU oracle in reference-literal mode (single thread, the reference CLI is
-                 single-threaded) on a bounded sample of the same workload.
+                 single-threaded) on a bounded sample of the same workload, and cpu_allcores;
+  others       — the other BASELINE configs, timed briefly (default workload only);
+  fast_mode, write_sink, no_lowpass, end_to_end — informational legs on the default workload (one GPU);
+  roofline.power — board power and shader clock while the kernel runs back to back (one GPU);
+  seams_verified, halo_exchange — multi-rank runs: the halo and each rank's edge windows checked
+                 against a local regeneration, and the exchange timed on its own.
+--no-cpu-baseline / --no-others / --no-power drop a part of --full.
 
 --dump-outputs DIR writes what the timed path returned in its last step (dump_outputs below), so that two
 builds can be compared output for output: the inputs are a pure function of the arguments.
@@ -48,7 +55,7 @@ WORKLOADS = {
     # BASELINE.json configs[4]: the cfg3 chain on a cf32 stream sharded over the node, 16 GiB per GPU (128 GiB at 8 GPUs)
     "cfg5": dict(fmt=0, n=1 << 31, sr=21_000_000, shift=280000, lp=(200_000, 32, 400), W=64, S=16,
                  desc="{size} cf32 per GPU: shift 280000 -> lowpass -power 200 -decimate 32 200000 -> sparkfft -width 64 -stride 16 (configs[4])"),
-    # chains WITHOUT a lowpass (README example 1 / configs[0]'s chain at scale; the default run reports them under "no_lowpass"): here as
+    # chains WITHOUT a lowpass (README example 1 / configs[0]'s chain at scale; a --full run reports them under "no_lowpass"): here as
     # workloads so that the profile scripts can put rocprofv3 around them
     "nolp": dict(fmt=0, n=1 << 31, sr=21_000_000, shift=None, lp=None, W=128, S=128, desc="{size} cf32: sparkfft -width 128 (no shift, no lowpass)"),
     "nolp_shift": dict(fmt=0, n=1 << 31, sr=21_000_000, shift=280000, lp=None, W=128, S=128, desc="{size} cf32: shift 280000 -> sparkfft -width 128 (no lowpass)"),
@@ -412,6 +419,8 @@ def measure(args, name, cfg, rank, world, device, dist, steps, warmup, with_cpu,
             del host
         else:
             SH.exchange(slab, shards, rank, bps, dist)                                # halo over RCCL/xGMI, once, in place
+    exchange_ms = None
+    if world > 1 and args.full:
         # the exchange step priced on its own (informational): the same exchange once more — it lands the same bytes — between
         # barriers; the first call above also built the communicator's point-to-point channels
         torch.cuda.synchronize()
@@ -428,14 +437,12 @@ def measure(args, name, cfg, rank, world, device, dist, steps, warmup, with_cpu,
     def step():
         plan.run_device(slab, out, me.w0, nw, src_first=me.need_first, src_count=me.need_count)
 
-    # ---- seam verification (multi-rank runs; outside the timed region).  (1) The halo this rank RECEIVED is compared, byte for
-    # byte, with the same samples regenerated locally (the generator is keyed by absolute index).  (2) The rank's first and last
-    # four windows — the last ones read the halo — are recomputed by a FRESH plan from a small slab generated from scratch, and
+    # ---- seam verification (multi-rank runs with --full; outside the timed region).  (1) The halo this rank RECEIVED is compared,
+    # byte for byte, with the same samples regenerated locally (the generator is keyed by absolute index).  (2) The rank's first and
+    # last four windows — the last ones read the halo — are recomputed by a FRESH plan from a small slab generated from scratch, and
     # compared with the rows of the sharded run.  Every rank's verdict is AND-reduced into "seams_verified".
     seams = None
-    if world == 1:
-        exchange_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         ok = True
         if me.halo:
             regen = torch.empty(me.halo * bps, dtype=torch.uint8, device=device)
@@ -773,9 +780,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other BASELINE configs (default one-GPU run only)")
-    ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power / clock reading after the timed region (one-GPU runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run what takes runs of its own: CPU baselines, the other BASELINE configs, the "
+                         "informational legs, the power / clock reading and, with several ranks, the seam checks and the halo-exchange timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-others", action="store_true",
+                    help="with --full: skip the short runs of the other BASELINE configs and the informational legs (default workload only)")
+    ap.add_argument("--no-power", action="store_true", help="with --full: skip the sysfs power / clock reading after the timed region (one-GPU runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--settle", type=float, default=0.3, help="seconds of untimed launches before the warmup steps (clock ramp)")
     ap.add_argument("--samples-log2", type=int, default=None, help="override samples per GPU (2^k); rehearsals only")
@@ -820,13 +831,14 @@ def main():
     cfg = dict(WORKLOADS[args.workload])
     if args.samples_log2 is not None:
         cfg["n"] = 1 << args.samples_log2
-    args.power_sample = world == 1 and not args.no_power and not args.stub
+    args.power_sample = args.full and world == 1 and not args.no_power
     main_res = measure(args, args.workload, cfg, rank, world, device, dist, args.steps, args.warmup,
-                       with_cpu=(world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
+                       with_cpu=(args.full and world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
     args.power_sample = False
     bad = rank == 0 and (main_res.get("seams_verified") is False or not main_res["outputs_finite"])
     others = None
-    if args.workload == DEFAULT_WORKLOAD and not args.no_others and (world > 1 or args.samples_log2 is None):
+    legs = args.full and args.workload == DEFAULT_WORKLOAD and not args.no_others
+    if legs and (world > 1 or args.samples_log2 is None):
         # the other BASELINE configs, briefly (same protocol, fewer steps, no CPU leg): parity-test cases first, bench lines second.
         # One GPU: configs[1..3]; several GPUs: configs[4] (the cfg3 chain on a cf32 stream sharded over the ranks).
         others = {}
@@ -875,22 +887,22 @@ def main():
                 line[k] = main_res[k]
         if others:
             line["others"] = others
-        if world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_others:
+        if world == 1 and legs:
             try:
                 line["fast_mode"] = fast_mode_leg(cfg, device)
             except Exception as e:                       # informational leg: never takes the bench line down
                 line["fast_mode"] = {"error": str(e)[:200]}
-        if world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_others:
+        if world == 1 and legs:
             try:
                 line["write_sink"] = write_sink_leg(cfg, device)
             except Exception as e:                       # informational leg
                 line["write_sink"] = {"error": str(e)[:200]}
-        if world == 1 and args.workload == DEFAULT_WORKLOAD and args.samples_log2 is None and not args.no_others:
+        if world == 1 and legs and args.samples_log2 is None:
             try:
                 line["no_lowpass"] = no_lowpass_leg(device)
             except Exception as e:                       # informational leg
                 line["no_lowpass"] = {"error": str(e)[:200]}
-        if world == 1 and args.workload == DEFAULT_WORKLOAD and args.samples_log2 is None and not args.no_others:
+        if world == 1 and legs and args.samples_log2 is None:
             try:
                 line["end_to_end"] = end_to_end_host(device)
             except Exception as e:                       # the PCIe leg never takes the bench line down

@@ -5,7 +5,7 @@
 wl=$1; shift
 for rep in 1 2 3; do
   for lib in "$@"; do
-    QD_LIB_PATH=$PWD/$lib python bench.py --workload $wl --no-cpu-baseline --no-others 2>/dev/null > /tmp/ab_line.json
+    QD_LIB_PATH=$PWD/$lib python bench.py --full --workload $wl --no-cpu-baseline --no-others 2>/dev/null > /tmp/ab_line.json
     python - "$wl" "$lib" <<'PY'
 import sys, json
 d = json.loads(open("/tmp/ab_line.json").read().strip().splitlines()[-1])

@@ -1,11 +1,11 @@
-"""Copies the summaries scripts/profile_round.sh left under gpurun_out/profiles_out into profiles/<round>/ and
+"""Copies the summaries scripts/profile_round.sh left under $OUT_DIR/profiles_out (default out/) into profiles/<round>/ and
 rebuilds profiles/traffic_latest.json (what bench.py reports as roofline.traffic, per workload).
 The factor 2 on FETCH_SIZE (MI355X_MICROARCH.md, HBM section, stated there for 16 B/lane) was calibrated here for the widths this
 kernel uses: scripts/ubench_fetch.hip streams a known byte count with 16, 8 and 4 bytes per lane and FETCH_SIZE*1024 comes out
 at exactly 0.5000 of the bytes for all three (scripts/fetch_cal.py), so the cs8 workload's traffic is reported too."""
 import json, os, shutil, sys
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
-src, dst = "gpurun_out/profiles_out", f"profiles/{rnd}"
+src, dst = os.path.join(os.environ.get("OUT_DIR", "out"), "profiles_out"), f"profiles/{rnd}"
 os.makedirs(dst, exist_ok=True)
 traffic = {"workloads": {}, "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes; hbm bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 "
            "(gfx950 reports half of a 16 B/lane streaming read); per launch, like roofline.achieved"}

@@ -4,13 +4,13 @@
 #   (TCC slots: both do not fit in one pass; never combined with trace domains other than kernel-trace).
 #   The counter passes are restricted to the chain kernel (--kernel-include-regex): collecting counters over the thousands of
 #   torch kernels that generate the 16 GiB synthetic slab crashed the profiler on cfg3 (round 3).
-# usage: [BENCH_SCRIPT=scripts/bench_cascade.py] scripts/profile_round.sh <tag> [bench.py args...]
+# usage: [BENCH_SCRIPT=scripts/bench_cascade.py] [OUT_DIR=dir] scripts/profile_round.sh <tag> [bench.py args...]   (default out/)
 #   BENCH_SCRIPT: the benchmark to profile (default bench.py; scripts/bench_cascade.py takes the same flags)
 set -e
 export TMPDIR=/tmp
 tag=$1; shift
 bench=${BENCH_SCRIPT:-bench.py}
-out=gpurun_out/prof_$tag
+out=${OUT_DIR:-out}/prof_$tag
 rm -rf $out; mkdir -p $out
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 $bench --steps 40 --warmup 3 --no-cpu-baseline --no-others --no-power "$@" > $out/kt.log 2>&1
 rocprofv3 --kernel-include-regex 'k_chain|k_spark|k_cascade' --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 $bench --steps 5 --warmup 1 --no-cpu-baseline --no-others --no-power "$@" > $out/fetch.log 2>&1

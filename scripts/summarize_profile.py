@@ -50,8 +50,9 @@ if m:
 if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
     res["hbm_bytes_per_launch"] = 2 * pmc["FETCH_SIZE"] * 1024 + pmc["WRITE_SIZE"] * 1024
     res["hbm_note"] = "2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 correction for wide coalesced reads)"
-os.makedirs("gpurun_out/profiles_out", exist_ok=True)
-json.dump(res, open(f"gpurun_out/profiles_out/{tag}.json", "w"), indent=1)
-with open(f"gpurun_out/profiles_out/{tag}_kernel_stats.csv", "w") as f:
+summ = os.path.join(os.path.dirname(os.path.abspath(out)), "profiles_out")       # beside the run's own directory
+os.makedirs(summ, exist_ok=True)
+json.dump(res, open(f"{summ}/{tag}.json", "w"), indent=1)
+with open(f"{summ}/{tag}_kernel_stats.csv", "w") as f:
     f.write(open(ks[0]).read())
 print(json.dumps(res, indent=1)[:1500])

@@ -90,3 +90,22 @@ def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
         assert norms.shape[0] == (1 << 20) // (16 * 128) - 1 and np.isfinite(norms).all()
         dumps.append(norms)
     assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.spawns_gpu_ranks
+def test_plain_run_is_lean_and_full_adds_the_rest():
+    """A plain run prints the headline and the roofline of its own timed steps and nothing that takes runs of its own; --full adds
+    the CPU baselines and the informational legs.  Child processes only: this process never touches the GPU."""
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-power", "--cpu-seconds", "0.5"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--samples-log2", "20", "--steps", "2", "--warmup", "1",
+                            "--settle", "0", *extra], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[mode] = json.loads(r.stdout.strip().splitlines()[-1])
+    for d in lines.values():
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["roofline"]["kernel_ms"] > 0
+    extras = ("cpu_baseline", "cpu_allcores", "fast_mode", "write_sink")
+    assert not any(k in lines["plain"] for k in extras) and "power" not in lines["plain"]["roofline"]
+    assert all(k in lines["full"] for k in extras) and lines["full"]["cpu_baseline"]["value"] > 0
