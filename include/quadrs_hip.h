@@ -53,7 +53,10 @@ typedef enum {
                                 LowPass::read_at block of `width` decimated samples (0x1000 for do_write, a power
                                 of two), `stride` is ignored, the output is width qd_c32 per block with the block's
                                 own tail truncation.  n_windows counts the FULL blocks, floor((n-T)/(width*D));
-                                the ragged end of the stream is left to qd_lowpass_block.  Needs has_lowpass. */
+                                the ragged end of the stream is left to qd_lowpass_block.  Needs has_lowpass.
+                                Behind a cascade (qd_plan_create_stages) a block is the outer read_at(b*width, width)
+                                of the nested stages, every stage truncating against its own read of it; n_windows
+                                counts the blocks whose source span fits the stream (see the stage lists below). */
 } qd_epilogue;
 
 const char *qd_last_error(void);
@@ -259,11 +262,18 @@ int qd_plan_run_sharded_device(qd_plan *plan, void *const *slabs, void *const *o
  *                                         W*D2 + T2 <= 8192 samples per window (W without a second lowpass), a first stage of
  *                                         at most 4096 taps, any stride; the window's source span (W*D2 + T2)*D1 + T1 is
  *                                         streamed through the workgroup in sub-tiles.  QD_MODE_FAST runs its exact arithmetic.
- *   anything else (three lowpasses, two shifts in a row, shift-only cascades, a block past the envelope): QD_ERR_UNSUPPORTED.
+ *                                         The write sink (QD_EPI_CF32_BLOCKS) runs on its own kernel: read_at blocks of
+ *                                         B = width outer outputs (a power of two up to 2^20, stride ignored), computed in
+ *                                         sub-blocks; its envelope is a first stage of at most 4096 taps, a second of at most
+ *                                         8192, and a block source span (B*D2 + T2)*D1 + T1 of at most 2^31 samples — there
+ *                                         is no W*D2 + T2 limit.  n_windows = complete = the full blocks (the ragged end is the
+ *                                         caller's), out_bytes_per_window = 8*B, raw_step = B*D2*D1.
+ *   anything else (three lowpasses, two shifts in a row, shift-only cascades, a block past the envelope): QD_ERR_UNSUPPORTED;
+ *   a write sink without a lowpass (an empty list or a lone shift): QD_ERR_INVALID.
  * A cascade plan's qd_plan_info composes through the stages: raw_per_window / raw_step are the source span / step of a
  * window, decimated_len / out_sample_rate are the sink's, ratio is the first shift's.  qd_plan_src_range, qd_plan_run
  * (device buffers, host buffers in chunks, slabs, window sub-ranges) and qd_plan_run_sharded (any shard devices) work and give
- * the bytes of the whole-stream run; qd_plan_run_sharded_device and QD_EPI_CF32_BLOCKS return QD_ERR_UNSUPPORTED.
+ * the bytes of the whole-stream run, for every sink; qd_plan_run_sharded_device returns QD_ERR_UNSUPPORTED.
  * With two lowpass stages LowPass::len over-reports (src/filter.rs:45-48) and the sink's last window(s) may fail
  * read_exact_at (src/samples.rs:17-27): qd_plan_complete_windows gives the leading windows that succeed, and a run whose range
  * reaches past them writes every complete window of the range and returns QD_ERR_SHORT. */

@@ -8,9 +8,9 @@
 //
 // Chains of the shape  from|gen [shift] [lowpass]  ->  sparkfft|bucket  run as ONE fused plan
 // (qd_plan_*); other shift / lowpass stage lists in front of sparkfft|bucket (a shift after the filter, two cascaded
-// lowpasses) go to a fused cascade plan (qd_plan_create_stages).  Anything else (e.g. three lowpasses, write after a
-// cascade) falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the
-// reference's read_at() computes.
+// lowpasses) go to a fused cascade plan (qd_plan_create_stages), in front of write too.  Anything else (e.g. three lowpasses)
+// falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the reference's read_at()
+// computes.
 #include <cerrno>
 #include <cinttypes>
 #include <cstdio>
@@ -556,9 +556,10 @@ void run_iter_sink(const Samples &s, const Op &sink, bool header_printed = false
     if (sink.kind == OP_BUCKET) printf("%s\n", digits.c_str());
 }
 
-// do_write (src/lib.rs:178-213).  When the chain is  from [shift] lowpass  the full 0x1000-sample
-// read_at blocks come from ONE fused plan (QD_EPI_CF32_BLOCKS); the ragged end of the stream — where
-// every read_at has its own `valid` — and any other chain go through the block iterator.
+// do_write (src/lib.rs:178-213).  When the chain is  from [shift] lowpass , or a cascade the library fuses
+// (qd_plan_create_stages), the full 0x1000-sample read_at blocks come from ONE fused plan (QD_EPI_CF32_BLOCKS);
+// the ragged end of the stream — where every read_at has its own `valid` — and any other chain go through the
+// block iterator.
 void do_write(const Samples &s, bool overwrite, const std::string &prefix, const ChainSpec *cs) {
     if (prefix == "-") bail("not implemented");
     std::string fn = prefix + ".sr" + std::to_string(s.sample_rate()) + ".cf32";
@@ -573,11 +574,21 @@ void do_write(const Samples &s, bool overwrite, const std::string &prefix, const
         d.struct_size = sizeof d;
         d.format = cs->src->format; d.sample_rate = cs->src->sample_rate;
         d.n_samples = data.size / qd_pair_bytes(cs->src->format);
-        if (cs->shift) { d.has_shift = 1; d.shift_hz = cs->shift->shift; }
-        d.has_lowpass = 1; d.lowpass_hz = cs->lowpass->lp_freq; d.decimate = cs->lowpass->decimate; d.taps = cs->lowpass->size;
+        std::vector<qd_stage> stages;
+        if (cs->cascade) {
+            for (const Op *op : cs->stages) {
+                qd_stage st{};
+                if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
+                else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
+                stages.push_back(st);
+            }
+        } else {
+            if (cs->shift) { d.has_shift = 1; d.shift_hz = cs->shift->shift; }
+            d.has_lowpass = 1; d.lowpass_hz = cs->lowpass->lp_freq; d.decimate = cs->lowpass->decimate; d.taps = cs->lowpass->size;
+        }
         d.width = 0x1000; d.stride = 0x1000; d.epilogue = QD_EPI_CF32_BLOCKS;
         qd_plan *plan = nullptr;
-        int rc = create_plan(d, &plan);
+        int rc = create_plan(d, &plan, cs->cascade ? &stages : nullptr);
         if (rc == QD_OK) {
             qd_plan_info info;
             qd_check(qd_plan_get_info(plan, &info), "plan info");
@@ -692,7 +703,8 @@ int main(int argc, char **argv) {
                 break;
             case OP_WRITE:
                 if (!samples) bail("write requires an input");
-                do_write(*samples, op.overwrite, op.prefix, chain_clean ? &cs : nullptr);
+                cs.cascade = !chain_clean;
+                do_write(*samples, op.overwrite, op.prefix, &cs);
                 break;
             }
         }

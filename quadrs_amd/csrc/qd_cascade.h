@@ -20,6 +20,13 @@
 // qd_device.h (second order), laid out on 512-sample rows of each stage's OWN absolute index (row bases from k_rowtab, one table
 // per NCO over the launch's range): a window's bytes do not depend on the launch, slab, chunk or shard that computes it.
 //
+// The write sink (QD_EPI_CF32_BLOCKS, k_cascade_write): the sink's window is a read_at block of B outer outputs (src/lib.rs:178-213),
+// whose inter block (B D2 + T2) is far larger than the LDS.  A kernel window is a SUB-BLOCK of K outputs [k0, k0 + K) of block b
+// (ChainParams W = K, blk_len = B, blk_sub_mask = B / K - 1): FIR1 forms only the inter samples the sub-block's FIR2 reads,
+// [k0 D2 + c2, (k0 + K - 1) D2 + c2 + T2) clipped to the block's n2, each still truncated against the BLOCK's n1; FIR2 truncates
+// against the block's n2.  The outputs go straight to global memory (a lane per output, consecutive lanes consecutive float2).
+// Without a second lowpass the sub-block's FIR1 outputs are the outputs and nothing is parked.  No FFT: the source sub-tile only.
+//
 // LDS (dynamic): inter block (n2 plus one pad per D2 when D2 is even: FIR2's lanes stride D2 + 1, odd; the pads are phased so that
 // every output's first sample starts a pad period) | source sub-tile (one pad per D1 when D1 is even; the FFT buffer and the bucket
 // sums reuse it once FIR1 is done).  An untruncated output's FIR walks its taps in blocks of 8 with
@@ -214,6 +221,72 @@ __global__ __launch_bounds__(kCascadeThreads) void k_cascade(const CascadeParams
             }
         }
         __syncthreads();                                                     // the next window rewrites the row bases, tile and inter block
+    }
+}
+
+// Write sink behind a cascade: kernel window w = sub-block (w & blk_sub_mask) of read_at block w / (blk_sub_mask + 1), K = W outputs
+// each, written as cf32 to out + (w - out_window0) K.  The same arithmetic, truncation and NCO rows as k_cascade (see the top of the file).
+template <int FMT>
+__global__ __launch_bounds__(kCascadeThreads) void k_cascade_write(const CascadeParams P) {
+    extern __shared__ __attribute__((aligned(16))) float2 casc_lds[];
+    float2 *inter = casc_lds;                                                // the sub-block's inter samples (second lowpass only)
+    float2 *tile = casc_lds + P.inter_elems;                                 // source sub-tile
+    const uint32_t tid = threadIdx.x;
+    const ChainParams &C = P.c;
+    const uint32_t D1 = P.D1, T1 = P.T1, D2 = P.D2, T2 = P.T2, n2 = P.n2, K = C.W;
+    const uint32_t c1 = T1 - T1 / 2, c2 = T2 - T2 / 2;
+    const uint64_t n1 = (uint64_t)n2 * D1 + T1;
+    const bool l2 = (P.flags & kCascL2) != 0;
+    const uint32_t log_subs = (uint32_t)__popc(C.blk_sub_mask);            // B / K is a power of two
+    const_f32_p h1 = (const_f32_p)P.h1;
+    const_f32_p h2 = (const_f32_p)P.h2;
+    const int cls1 = casc_fir_class(D1), cls2 = casc_fir_class(D2);
+    float2 *out = reinterpret_cast<float2 *>(C.out);
+    for (uint64_t w = C.first_window + blockIdx.x; w < C.first_window + C.n_windows; w += gridDim.x) {
+        const uint32_t k0 = (uint32_t)(w & C.blk_sub_mask) * K;             // the sub-block's first output within its block
+        const uint64_t o = (w >> log_subs) * C.blk_len;                     // outer index of the block's first output
+        const uint64_t b2 = l2 ? o * D2 : o;                                 // inter index of the block's inter sample 0
+        const uint64_t b1 = b2 * D1;                                         // source index of the block's first read
+        const uint32_t i_lo = l2 ? k0 * D2 + c2 : k0;                        // inter samples [i_lo, i_hi) of the block
+        const uint32_t i_end = l2 ? (k0 + K - 1) * D2 + c2 + T2 : k0 + K;
+        const uint32_t i_hi = i_end < n2 ? i_end : n2;
+        float2 *ow = out + (w - C.out_window0) * K;
+        // ---- 1: FIR1 over source sub-tiles: inter samples i_lo .. i_hi - 1 (the outputs themselves without a second lowpass)
+        for (uint32_t i0 = 0; i0 < i_hi - i_lo; i0 += P.M) {
+            const uint32_t m = i_hi - i_lo - i0 < P.M ? i_hi - i_lo - i0 : P.M;
+            const uint64_t is = (uint64_t)i_lo + i0;                         // block index of the sub-tile's first output
+            const uint64_t s0 = b1 + is * D1 + c1;                           // first source sample any output of the sub-tile reads
+            const uint64_t want = (uint64_t)(m - 1) * D1 + T1, left = n1 - (is * D1 + c1);
+            const uint32_t ns = (uint32_t)(want < left ? want : left);
+            __syncthreads();                                                 // the previous sub-tile's readers are done
+            for (uint32_t q = tid; q < ns; q += kCascadeThreads) {
+                const uint64_t s = s0 + q;
+                float2 x = make_float2(0.f, 0.f);
+                if (s >= C.src_first && s < C.src_first + C.src_count) x = casc_load<FMT>(C.src, s - C.src_first);
+                if (P.flags & kCascS0) x = cmul(x, casc_nco(P.rows[0], P.row0[0], s, P.jtab, P.ratio0));
+                tile[casc_pad(q, P.dmagic1)] = x;
+            }
+            __syncthreads();
+            for (uint32_t k = tid; k < m; k += kCascadeThreads) {
+                const uint64_t i = is + k;
+                const uint64_t lim = n1 - (i * D1 + c1);
+                const uint32_t jmax = lim < T1 ? (uint32_t)lim : T1;
+                float2 v = casc_fir(cls1, tile, k * D1, jmax, T1, D1, h1, P.dmagic1, 0);
+                if (P.flags & kCascS1) v = cmul(v, casc_nco(P.rows[1], P.row0[1], b2 + i, P.jtab + kCascadeRow, P.ratio1));
+                if (l2) inter[casc_pad(i0 + k, P.dmagic2)] = v;            // output k of the sub-block starts at k D2: a pad period
+                else ow[i0 + k] = v;
+            }
+        }
+        if (!l2) continue;                                                   // the next window's first barrier orders the tile
+        __syncthreads();
+        // ---- 2: FIR2 (truncated against the block's n2) + its NCO on the absolute outer index, straight to global memory
+        for (uint32_t k = tid; k < K; k += kCascadeThreads) {
+            const uint32_t lim = n2 - ((k0 + k) * D2 + c2), jmax = lim < T2 ? lim : T2;
+            float2 v = casc_fir(cls2, inter, k * D2, jmax, T2, D2, h2, P.dmagic2, 0);
+            if (P.flags & kCascS2) v = cmul(v, casc_nco(P.rows[2], P.row0[2], o + k0 + k, P.jtab + 2 * kCascadeRow, P.ratio2));
+            ow[k] = v;
+        }
+        // the next window writes the inter block only after the barriers of its first sub-tile, which every reader has passed
     }
 }
 

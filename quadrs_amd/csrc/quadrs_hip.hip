@@ -921,9 +921,14 @@ int launch_spark_phases(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t s
 }
 
 // windows [first_window, +n_windows) of a cascade plan (qd_cascade.h); the caller has clipped them to the complete windows
+// (the write sink's kernel windows are sub-blocks: the source, inter and outer ranges are those of the read_at blocks they lie in)
 int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
                    uint64_t out_window0, void *out_d, hipStream_t st) {
-    const uint64_t need0 = first_window * p->S * p->D, need1 = (first_window + n_windows - 1) * p->S * p->D + (uint64_t)p->W * p->D + p->T;
+    const uint64_t last = first_window + n_windows - 1, l2 = (p->c_flags & kCascL2) ? p->c_D2 : 1;
+    // windows [w_lo, w_hi] of the sink (blocks of the write sink), each window_len outer outputs, step apart
+    const uint64_t subs = p->blk_subs, w_lo = first_window / subs, w_hi = last / subs;
+    const uint64_t step = p->blk_len ? p->blk_len : p->S, window_len = p->blk_len ? p->blk_len : p->W;
+    const uint64_t need0 = w_lo * step * p->D, need1 = w_hi * step * p->D + window_len * p->D + p->T;
     if (need0 < src_first || need1 > src_first + src_count)
         return fail(QD_ERR_INVALID, "src slab [%llu,+%llu) does not cover samples [%llu,%llu) needed by windows [%llu,+%llu)",
                     (unsigned long long)src_first, (unsigned long long)src_count, (unsigned long long)need0,
@@ -945,8 +950,7 @@ int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_fi
     P.flags = p->c_flags;
     // row tables of the NCOs over this launch's range, on `st` (ordered behind the context's previous launch, see NcoTabs)
     if (tabs->phase.size() < 3) tabs->phase.resize(3);
-    const uint64_t last = first_window + n_windows - 1, l2 = (p->c_flags & kCascL2) ? p->c_D2 : 1;
-    const uint64_t lo[3] = {need0, first_window * p->S * l2, first_window * p->S}, hi[3] = {need1, last * p->S * l2 + p->c_n2, last * p->S + p->W};
+    const uint64_t lo[3] = {need0, w_lo * step * l2, w_lo * step}, hi[3] = {need1, w_hi * step * l2 + p->c_n2, w_hi * step + window_len};
     const uint32_t sflag[3] = {kCascS0, kCascS1, kCascS2};
     for (int k = 0; k < 3; ++k) {
         if (!(p->c_flags & sflag[k])) continue;
@@ -956,11 +960,20 @@ int launch_cascade(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_fi
     }
     const uint64_t cap = (uint64_t)p->n_cu * p->c_wg_per_cu;
     const uint32_t grid = (uint32_t)(n_windows < cap ? n_windows : cap);
-    switch (p->d.format) {
-    case QD_FMT_CF32: hipLaunchKernelGGL(k_cascade<0>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
-    case QD_FMT_CS8: hipLaunchKernelGGL(k_cascade<1>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
-    case QD_FMT_CU8: hipLaunchKernelGGL(k_cascade<2>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
-    default: hipLaunchKernelGGL(k_cascade<3>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+    if (p->blk_len) {
+        switch (p->d.format) {
+        case QD_FMT_CF32: hipLaunchKernelGGL(k_cascade_write<0>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        case QD_FMT_CS8: hipLaunchKernelGGL(k_cascade_write<1>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        case QD_FMT_CU8: hipLaunchKernelGGL(k_cascade_write<2>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        default: hipLaunchKernelGGL(k_cascade_write<3>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        }
+    } else {
+        switch (p->d.format) {
+        case QD_FMT_CF32: hipLaunchKernelGGL(k_cascade<0>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        case QD_FMT_CS8: hipLaunchKernelGGL(k_cascade<1>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        case QD_FMT_CU8: hipLaunchKernelGGL(k_cascade<2>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        default: hipLaunchKernelGGL(k_cascade<3>, dim3(grid), dim3(kCascadeThreads), p->c_lds, st, P); break;
+        }
     }
     HIPCHK(hipGetLastError());
     return QD_OK;
@@ -1681,6 +1694,8 @@ namespace {
 constexpr uint32_t kCascadeMaxInter = 8192;     // intermediate samples per window (W D2 + T2): the kernel's LDS envelope
 constexpr uint32_t kCascadeMaxSub = 8192;       // source samples per sub-tile
 constexpr uint32_t kCascadeMaxT1 = 4096;
+constexpr uint64_t kCascadeMaxBlockSpan = 1ull << 31;     // write sink: source samples per read_at block ((B D2 + T2) D1 + T1)
+constexpr uint32_t kCascadeMaxK = 512;                    // write sink: outputs per sub-block
 
 struct StageGeo {
     bool routed = false;                        // [shift] [lowpass]: the one-stage plan
@@ -1741,8 +1756,22 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     if (g->l1 < 0 || k != shape.size())
         return fail(QD_ERR_UNSUPPORTED, "stage list %s is not a fused shape ([shift] lowpass [shift] [lowpass [shift]]): the caller runs it stage by stage",
                     shape.c_str());
-    if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "write (QD_EPI_CF32_BLOCKS) after a cascade is not built");
     if (g->l2 >= 0) { g->D2 = (uint32_t)st[g->l2].decimate; g->T2 = (uint32_t)st[g->l2].taps; }
+    if (d.epilogue == QD_EPI_CF32_BLOCKS) {
+        // the write sink: read_at blocks of B = width outer outputs, side by side whatever the stride (src/lib.rs:178-213), run as
+        // sub-blocks (k_cascade_write): a sub-block of one output reads T2 inter samples, a block's source span is indexed in 32 bits
+        if (g->T1 > kCascadeMaxT1) return fail(QD_ERR_UNSUPPORTED, "cascade: a first stage of %u taps exceeds the kernel's sub-tile (%u taps)", g->T1, kCascadeMaxT1);
+        if (g->T2 > kCascadeMaxInter)
+            return fail(QD_ERR_UNSUPPORTED, "cascade write: a second stage of %u taps exceeds one sub-block's intermediate budget (%u)", g->T2, kCascadeMaxInter);
+        const uint64_t n2 = g->l2 >= 0 ? d.width * g->D2 + g->T2 : d.width, span = n2 * g->D1 + g->T1;
+        if (span > kCascadeMaxBlockSpan)
+            return fail(QD_ERR_UNSUPPORTED, "cascade write: a block's source span of %llu samples exceeds %llu", (unsigned long long)span,
+                        (unsigned long long)kCascadeMaxBlockSpan);
+        g->n2 = (uint32_t)n2;
+        // full blocks: block b reads source samples [b B D2 D1, + span), every nested read returns its full length while they exist
+        g->n_windows = g->complete = d.n_samples >= span ? (d.n_samples - span) / (d.width * g->D2 * g->D1) + 1 : 0;
+        return QD_OK;
+    }
     const uint64_t n2 = g->l2 >= 0 ? d.width * g->D2 + g->T2 : d.width;
     if (n2 > kCascadeMaxInter)
         return fail(QD_ERR_UNSUPPORTED, "cascade: a window's intermediate block of %llu samples exceeds the kernel's LDS budget (%u)", (unsigned long long)n2,
@@ -1771,31 +1800,60 @@ int cascade_init(qd_plan *p, const StageGeo &g, const qd_stage *st) {
     const int sidx[3] = {g.s0, g.s1, g.s2};
     for (int k = 0; k < 3; ++k) p->c_ratio[k] = sidx[k] >= 0 ? qd_shift_ratio(st[sidx[k]].shift_hz, g.in_rate[sidx[k]]) : 0.0;
     // LDS: inter block | source sub-tile (>= the FFT buffer).  Sub-tiles of up to 512 FIR1 outputs.
-    const bool l2 = g.l2 >= 0;
-    auto lds_of = [&](uint32_t M, uint32_t *inter, uint32_t *src) {
-        const uint64_t n2 = g.n2, ns = (uint64_t)(M - 1) * g.D1 + g.T1;
-        uint64_t ie = n2 + ((l2 && g.D2 % 2 == 0) ? n2 / g.D2 + 1 : 0) + 1;
+    const bool l2 = g.l2 >= 0, write = d.epilogue == QD_EPI_CF32_BLOCKS;
+    auto lds_of = [&](uint64_t n_inter, uint32_t M, uint32_t *inter, uint32_t *src) {
+        const uint64_t ns = (uint64_t)(M - 1) * g.D1 + g.T1;
+        uint64_t ie = n_inter ? n_inter + ((l2 && g.D2 % 2 == 0) ? n_inter / g.D2 + 1 : 0) + 1 : 0;
         uint64_t se = ns + (g.D1 % 2 == 0 ? ns / g.D1 + 1 : 0) + 1;
-        if (se < p->W) se = p->W;
+        if (!write && se < p->W) se = p->W;
         ie = (ie + 3) & ~3ull; se = (se + 3) & ~3ull;         // row bases on a 32-byte boundary
         *inter = (uint32_t)ie; *src = (uint32_t)se;
         return (size_t)((ie + se) * 8);
     };
-    uint32_t M = g.n2 < 512 ? g.n2 : 512;
-    while (M > 1 && ((uint64_t)(M - 1) * g.D1 + g.T1 > kCascadeMaxSub || lds_of(M, &p->c_inter, &p->c_src) > kLdsMax)) M = (M + 1) / 2;
-    p->c_M = M;
-    p->c_lds = lds_of(M, &p->c_inter, &p->c_src);
-    if (p->c_lds > kLdsMax || (uint64_t)(M - 1) * g.D1 + g.T1 > kCascadeMaxSub)
-        return fail(QD_ERR_UNSUPPORTED, "cascade: %zu bytes of LDS per workgroup exceed the %zu available", p->c_lds, kLdsMax);
+    auto sub_tile = [&](uint64_t n_inter, uint64_t n_fir1) {   // the largest M (<= 512) whose sub-tile and LDS fit
+        uint32_t M = n_fir1 < 512 ? (uint32_t)n_fir1 : 512;
+        while (M > 1 && ((uint64_t)(M - 1) * g.D1 + g.T1 > kCascadeMaxSub || lds_of(n_inter, M, &p->c_inter, &p->c_src) > kLdsMax)) M = (M + 1) / 2;
+        p->c_M = M;
+        p->c_lds = lds_of(n_inter, M, &p->c_inter, &p->c_src);
+        return p->c_lds <= kLdsMax && (uint64_t)(M - 1) * g.D1 + g.T1 <= kCascadeMaxSub;
+    };
+    bool fits = false;
+    if (write) {
+        // read_at blocks of B outputs in sub-blocks of K (the kernel's windows): the largest power of two K <= min(B, 512) whose inter
+        // samples (K - 1) D2 + T2 fit the budget and whose LDS, with a sub-tile of 64 or more FIR1 outputs, leaves room for four
+        // workgroups per CU (the kernel waits on LDS and barriers, not on issue); else the largest K that fits at all (K = 1 always
+        // does: stages_geo's envelope)
+        const uint32_t B = (uint32_t)d.width, K_max = B < kCascadeMaxK ? B : kCascadeMaxK;
+        auto pick = [&](size_t lds_cap, uint32_t M_min) {
+            for (uint32_t K = K_max; K >= 1; K /= 2) {
+                const uint64_t ni = l2 ? (uint64_t)(K - 1) * g.D2 + g.T2 : 0, n_fir1 = l2 ? ni : K;
+                if (ni > kCascadeMaxInter) continue;
+                for (uint32_t M = 512; M >= M_min; M /= 2) {
+                    if (!sub_tile(ni, M < n_fir1 ? M : n_fir1) || p->c_lds > lds_cap) continue;
+                    p->W = K;
+                    return true;
+                }
+            }
+            return false;
+        };
+        fits = pick(kLdsMax / 4, 64) || pick(kLdsMax, 1);
+        p->blk_len = B; p->blk_subs = B / p->W;
+        p->logW = ilog2(p->W); p->S = p->W;
+    } else {
+        fits = sub_tile(g.n2, g.n2);
+    }
+    if (!fits) return fail(QD_ERR_UNSUPPORTED, "cascade: %zu bytes of LDS per workgroup exceed the %zu available", p->c_lds, kLdsMax);
     int by_lds = (int)(kLdsMax / p->c_lds);
     p->c_wg_per_cu = by_lds < 1 ? 1 : (by_lds > 8 ? 8 : by_lds);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->n_cu = prop.multiProcessorCount;
     for (const void *f : {reinterpret_cast<const void *>(k_cascade<0>), reinterpret_cast<const void *>(k_cascade<1>),
-                          reinterpret_cast<const void *>(k_cascade<2>), reinterpret_cast<const void *>(k_cascade<3>)})
+                          reinterpret_cast<const void *>(k_cascade<2>), reinterpret_cast<const void *>(k_cascade<3>),
+                          reinterpret_cast<const void *>(k_cascade_write<0>), reinterpret_cast<const void *>(k_cascade_write<1>),
+                          reinterpret_cast<const void *>(k_cascade_write<2>), reinterpret_cast<const void *>(k_cascade_write<3>)})
         if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax); e != hipSuccess)
             return fail(QD_ERR_HIP, "hipFuncSetAttribute(k_cascade, max dynamic LDS %zu): %s", kLdsMax, hipGetErrorString(e));
-    p->fft = fft_layout(d.width);
+    if (!write) p->fft = fft_layout(d.width);          // the write sink has no transform
     if (!p->fft.tw.empty()) {
         HIPCHK(hipMalloc(&p->tw_d, p->fft.tw.size() * sizeof(float2)));
         HIPCHK(hipMemcpy(p->tw_d, p->fft.tw.data(), p->fft.tw.size() * sizeof(float2), hipMemcpyHostToDevice));
@@ -1831,7 +1889,8 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
     int rc = stages_geo(desc, stages, n_stages, &g);
     if (rc) return rc;
     const qd_chain_desc &d = *desc;
-    if (d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_UNSUPPORTED, "qd_stages_geometry: the write sink's blocks are the one-stage plan's (qd_plan_get_info)");
+    const bool write = d.epilogue == QD_EPI_CF32_BLOCKS;
+    if (write && g.routed) return fail(QD_ERR_UNSUPPORTED, "qd_stages_geometry: the write sink's blocks are the one-stage plan's (qd_plan_get_info)");
     if (g.routed) {                  // the one-stage plan's figures: a single lowpass never fails a read
         g.complete = g.n_windows;
         g.n2 = (uint32_t)d.width;
@@ -1840,9 +1899,9 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
     info->n_windows = g.n_windows;
     info->decimated_len = g.len;
     info->out_sample_rate = g.rate;
-    info->out_bytes_per_window = d.epilogue == QD_EPI_NORMS_F32 ? d.width * 4 : (d.epilogue == QD_EPI_GLYPH_U8 ? d.width : 1);
+    info->out_bytes_per_window = write ? d.width * 8 : d.epilogue == QD_EPI_NORMS_F32 ? d.width * 4 : (d.epilogue == QD_EPI_GLYPH_U8 ? d.width : 1);
     info->raw_per_window = (uint64_t)g.n2 * g.D1 + g.T1;
-    info->raw_step = d.stride * g.D2 * g.D1;
+    info->raw_step = (write ? d.width : d.stride) * g.D2 * g.D1;      // the write sink's blocks lie side by side
     info->ratio = g.ratio;
     *complete = g.complete;
     return QD_OK;
@@ -2041,6 +2100,12 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
         snprintf(buf, cap, "two stages: %s | %s", a, b);
         return QD_OK;
     }
+    if (p->casc && p->blk_len) {
+        snprintf(buf, cap, "qd::k_cascade_write<%d>(D1 %u, T1 %u, D2 %u, T2 %u, B %u, K %u, shifts %u%u%u, M %u), %u threads, generic", p->d.format,
+                 p->c_D1, p->c_T1, p->c_D2, p->c_T2, p->blk_len, p->W, p->c_flags & kCascS0 ? 1 : 0, p->c_flags & kCascS1 ? 1 : 0,
+                 p->c_flags & kCascS2 ? 1 : 0, p->c_M, kCascadeThreads);
+        return QD_OK;
+    }
     if (p->casc) {
         snprintf(buf, cap, "qd::k_cascade<%d>(D1 %u, T1 %u, D2 %u, T2 %u, W %u, S %u, shifts %u%u%u, M %u), %u threads, generic", p->d.format, p->c_D1, p->c_T1,
                  p->c_D2, p->c_T2, p->W, p->S, p->c_flags & kCascS0 ? 1 : 0, p->c_flags & kCascS1 ? 1 : 0, p->c_flags & kCascS2 ? 1 : 0, p->c_M,
@@ -2160,6 +2225,8 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
         }
         if (first_window % grid == 0 && cw >= unit) cw = (cw / unit) * unit;
     }
+    // a cascade's write sink: chunks of whole read_at blocks (a sub-block reads past its own window's span, within its block's)
+    if (p->casc && p->blk_subs > 1) cw = cw < p->blk_subs ? p->blk_subs : cw / p->blk_subs * p->blk_subs;
     if (cw > n_windows) cw = n_windows ? n_windows : 1;
     const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps), ob = (size_t)(cw * obw);
     const bool stage_in = src_mem == QD_MEM_HOST, stage_out = out_mem == QD_MEM_HOST;

@@ -5,6 +5,10 @@ sparkfft -width 128 — the output rate and algorithmic bytes of bench.py's defa
 Same synthetic stream, same HIP-event timing and the same instruction-class VALU model as bench.py (its issue rates, helpers
 and constants are imported, not restated), extended with the first stage's FIR and the window-overlap recompute.  Prints one
 JSON line.  Accepts bench.py's profiling flags so that scripts/profile_round.sh can run it (BENCH_SCRIPT=scripts/bench_cascade.py).
+
+--sink write: the same stream and stages into the write sink (read_at blocks of 4096 decimated cf32 samples, k_cascade_write), timed
+alternately with the sparkfft cascade in one process over one HBM-resident slab; one JSON line with both legs' kernel ms,
+Gsamples/s of input and (bytes read + bytes written) / s.
 """
 import argparse
 import json
@@ -47,6 +51,60 @@ def ops_per_sample(cfg):
     return f32, f64, pk
 
 
+def run_write_sink(args, cfg):
+    """the write sink and the sparkfft cascade on the same slab, step for step alternating; kernel time from HIP events"""
+    import numpy as np
+    import torch
+    import quadrs_amd as Q
+    device = torch.device("cuda:0")
+    torch.cuda.set_device(device)
+    bps, B_ = B.BPS[cfg["fmt"]], 4096
+    spark = Q.Plan(cfg["fmt"], cfg["sr"], cfg["n"], stages=cfg["stages"], width=cfg["W"], stride=cfg["S"])
+    write = Q.Plan(cfg["fmt"], cfg["sr"], cfg["n"], stages=cfg["stages"], width=B_, stride=B_, epilogue=Q.EPI_CF32_BLOCKS)
+    nws, nww = spark.complete_windows(), write.complete_windows()
+    count = max(sum(spark.src_range(0, nws)), sum(write.src_range(0, nww)))
+    slab = B.synth_slab(torch, cfg["fmt"], 0, count, B.STREAM_SEED, device)
+    out_s = torch.empty(nws, cfg["W"], dtype=torch.float32, device=device)
+    out_w = torch.empty(nww * B_, 2, dtype=torch.float32, device=device)
+    legs = {"write": (write, out_w, nww), "sparkfft": (spark, out_s, nws)}
+
+    def step(name):
+        plan, out, nw = legs[name]
+        plan.run_device(slab, out, 0, nw, src_first=0, src_count=count)
+
+    t_settle = time.perf_counter()
+    while time.perf_counter() - t_settle < args.settle:
+        step("write"); step("sparkfft")
+        torch.cuda.synchronize()
+    for _ in range(args.warmup):
+        step("write"); step("sparkfft")
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for i in range(args.steps):
+        for name in (("write", "sparkfft") if i % 2 == 0 else ("sparkfft", "write")):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); step(name); b.record()
+            torch.cuda.synchronize()
+            ms[name].append(a.elapsed_time(b))
+    finite = bool(torch.isfinite(out_w).all().item()) and bool(torch.isfinite(out_s).all().item())
+    res = {"workload": "cascade-write", "unit": "ms",
+           "config": {"chain": "16 GiB cf32 @21Msps: shift 280000 -> lowpass -decimate 4 2000000 (40 taps) -> lowpass -power 100 -decimate 8 200000"
+                      if cfg["n"] == CFG["n"] else f"2^{args.samples_log2} samples of the same chain",
+                      "samples": cfg["n"], "steps": args.steps, "block": B_}, "outputs_finite": finite}
+    for name, (plan, out, nw) in legs.items():
+        kms = float(np.median(ms[name]))
+        samples = nw * plan.info.raw_step
+        read_b, written_b = plan.src_range(0, nw)[1] * bps, out.numel() * 4
+        res[name] = {"kernel": plan.kernel_name(), "windows": nw, "ms_median": kms, "ms_min": float(np.min(ms[name])),
+                     "ms_max": float(np.max(ms[name])), "gsamples_per_s": samples / (kms * 1e-3) / 1e9,
+                     "bytes_read": read_b, "bytes_written": written_b, "gbytes_per_s": (read_b + written_b) / (kms * 1e-3) / 1e9,
+                     "lds_bytes": plan.info.lds_bytes}
+    res["value"] = res["write"]["ms_median"]
+    res["write_over_sparkfft"] = res["write"]["ms_median"] / res["sparkfft"]["ms_median"]
+    print(json.dumps(res), flush=True)
+    return 0 if finite else 4
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -57,6 +115,7 @@ def main():
     ap.add_argument("--no-power", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="(accepted for scripts/profile_round.sh; there is no CPU leg)")
     ap.add_argument("--no-others", action="store_true", help="(accepted for scripts/profile_round.sh)")
+    ap.add_argument("--sink", default="sparkfft", choices=["sparkfft", "write"], help="write: the write sink against the sparkfft cascade")
     args = ap.parse_args()
 
     import numpy as np
@@ -65,6 +124,8 @@ def main():
     cfg = dict(CFG)
     if args.samples_log2:
         cfg["n"] = 1 << args.samples_log2
+    if args.sink == "write":
+        return run_write_sink(args, cfg)
     device = torch.device("cuda:0")
     torch.cuda.set_device(device)
     bps = B.BPS[cfg["fmt"]]
