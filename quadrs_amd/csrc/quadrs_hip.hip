@@ -364,16 +364,16 @@ const FixedEntry kFixed[] = {
     // phase 1 and 25 % of its FIR).  cf32 (cfg5, 16 GiB per GPU): one-tile-per-CU kernel 7.50 ms -> three-stage 6.71 -> streaming,
     // 14-window steps 5.7 ms; cs8 (cfg3): 25.6 -> 22 ms (12-window steps: 16 would need 174 KiB of LDS).  Identical bytes
     // (profiles/r03/sweep_stream.log).  nt = 512: rows of 512 producer threads; the launch adds 512 consumer threads.
-    { 0, 1, 64, 16, 32, 400, 14, 4, 512, 2, 1, 164128, 7, true, 8, 1,
+    { 0, 1, 64, 16, 32, 400, 14, 4, 512, 2, 1, 164128,
       qd::k_chain_pipe3s<0, 1, qd::FixedGeo<64, 16, 32, 400, 14, 8, 1, 2, 1, 164128>, 7, 4>, "fsk5" },
-    { 0, 2, 64, 16, 32, 400, 14, 4, 512, 2, 1, 164128, 7, true, 8, 1,
+    { 0, 2, 64, 16, 32, 400, 14, 4, 512, 2, 1, 164128,
       qd::k_chain_pipe3s<0, 2, qd::FixedGeo<64, 16, 32, 400, 14, 8, 1, 2, 1, 164128>, 7, 4>, "fsk5" },
 #ifndef QD_DEV_FAST
     // cs8 input (HackRF) of the same chain: four producer waves (rows of 256 threads x 4 samples = 1024 samples, seven per step) so that
     // 14-window steps start on row boundaries like the cf32 form's (rows of 2048 samples admit 12 or 16 windows, and 16 do not fit)
-    { 1, 1, 64, 16, 32, 400, 14, 4, 256, 2, 1, 164128, 7, true, 8, 1,
+    { 1, 1, 64, 16, 32, 400, 14, 4, 256, 2, 1, 164128,
       qd::k_chain_pipe3s<1, 1, qd::FixedGeo<64, 16, 32, 400, 14, 8, 1, 2, 1, 164128>, 7, 4, 256>, "cfg3" },
-    { 1, 2, 64, 16, 32, 400, 14, 4, 256, 2, 1, 164128, 7, true, 8, 1,
+    { 1, 2, 64, 16, 32, 400, 14, 4, 256, 2, 1, 164128,
       qd::k_chain_pipe3s<1, 2, qd::FixedGeo<64, 16, 32, 400, 14, 8, 1, 2, 1, 164128>, 7, 4, 256>, "cfg3" },
 #endif
     // configs[3]  512-tap FIR decimate 8 -> 1024-pt FFT (no shift)
@@ -386,7 +386,7 @@ const FixedEntry kFixed[] = {
     // one FFT slot; 512 threads (4 FIR waves + the four-wave deferred FFT), 74 KiB, so TWO workgroups share a CU and one's phase 1 +
     // barriers (8 k of its 29 k cycles per window) run under the other's FIR: 23.1 -> 22.0 ms, now at the package power cap too
     // (1390 W; the clock went from 2.32 to 2.19 GHz — profiles/r03/sweep_cfg4_half.log)
-    { 0, 0, 1024, 1024, 8, 512, 1, 4, 512, 2, 2, 8392, 5, true, 4, 2,
+    { 0, 0, 1024, 1024, 8, 512, 1, 4, 512, 2, 2, 8392,
       qd::k_chain<0, 0, qd::FixedGeo<1024, 1024, 8, 512, 1, 4, 2, 2, 2, 8392>, true, 5, true, true, 4, 512>, "cfg4" },
 };
 
@@ -398,8 +398,9 @@ const FixedEntry *find_fixed(int fmt, int nco, uint32_t W, uint32_t S, uint32_t 
 
 // ---- plan-time specialisation (hiprtc): any chain shape gets a FixedGeo build of the same kernel source.
 // The headers are read from <dir of this .so>/csrc (the in-tree layout); compiled modules are cached per
-// process.  QD_JIT=0 disables, QD_JIT=1 forces it for every plan; by default only streams whose chain
-// input is >= 16 MiB pay the ~0.3 s compile.
+// process and on disk (below).  qd_plan_options.kernel_policy decides whether a plan builds: QD_KERNEL_NO_PLAN_TIME /
+// QD_KERNEL_GENERIC never; by default a cached build is always used, and a new one is compiled (~0.3-1 s) for
+// streams of 1 GiB and more, for tile hints and for QD_MODE_FAST (QD_KERNEL_SPECIALISE: always).
 struct JitKey {
     int fmt, nco, fir, rch, whole, lb, nt; uint32_t W, S, D, T, G; uint32_t firb = 8, firr = 1; int noslp = 0; uint32_t pad = 1, batch = 1, flags = 0;
     uint64_t taps_hash = 0;        // baked-taps builds: FNV-1a of the filter (the code depends on it)
@@ -712,15 +713,11 @@ struct qd_plan {
     Geometry geo;
     chain_fn fn = nullptr, fn_unaligned = nullptr;
     const FixedEntry *fixed = nullptr;
-    uint32_t spark_ts = 0;               // ... its tile: samples per wave (512, 1024 or 2048)
-    int spark_lb = 4;                    // ... waves per SIMD it is register-budgeted for (= workgroups per CU)
-    bool spark_jt_lds = false;           // ... plan-time k_spark with a shift: the lane table sits in LDS (8 KiB more)
-    uint32_t phase_unit = 1;             // ... window ranges that start on multiples of it start on a load vector
-    bool spark_ov = false;               // ... overlapping windows without a lowpass or a shift on the wave-local kernels (plan-time builds only)
-    uint32_t spark_R = 0;                // ... as W / S interleaved launches of side-by-side windows (k_spark; stride divides width); <= 1: one launch (k_spark2)
     bool spark = false;                  // the wave-local kernel of chains without a lowpass (k_spark) is this plan's main kernel
+    uint32_t spark_ts = 0;               // ... its tile: samples per wave (512, 1024 or 2048)
+    uint32_t spark_R = 0;                // ... overlapping windows as W / S interleaved launches of side-by-side windows (stride divides width); <= 1: one launch
+    uint32_t phase_unit = 1;             // ... window ranges that start on multiples of it start on a load vector
     hipFunction_t jit_fn = nullptr;      // plan-time specialised kernel (hiprtc), replaces fn for aligned launches
-    std::string jit_note;
     int wg_per_cu = 1, n_cu = 256, prefetch_mode = 2, nco = 0, nt = kThreads;      // nt: threads that share a row of phase 1 (row = nt * SPL samples)
     int launch_nt = kThreads;            // workgroup size of the main kernel: nt, plus the consumer wave of the role-split kernel
     uint32_t kflags = 0;                 // FixedGeo FLAGS_ of the main kernel
@@ -1174,6 +1171,307 @@ void free_streaming(qd_plan *p) {
     p->stage_in_bytes = p->stage_out_bytes = p->pin_in_bytes = p->pin_out_bytes = 0;
 }
 
+
+// ---- choosing a one-stage chain plan's main kernel.  chain_candidates lists, for the plan's chain class, the ways its kernel can be
+// had, best first; plan_init takes the first whose kernel it can have (a plan-time build may not be: not cached and too small a stream
+// to compile for, or the build failed — failures are memoised, so the order of the builds is part of the behaviour) and commits it.
+struct Candidate {
+    enum Source { kTable, kBuiltinSpark, kBuild, kGeneric } src = kGeneric;
+    // tiling: windows per tile, threads that share a row of phase 1, LDS pad per row, tiles per FFT batch, FixedGeo FLAGS_, the
+    // register budget a build targets (waves per SIMD), scalar accumulate chains (-fno-slp-vectorize), FIR knobs
+    uint32_t G = 1; int nt = kThreads; uint32_t pad = 1, batch = 1, flags = 0; int lb = 4, noslp = 0; uint32_t firr = 1, firb = 8;
+    // the wave-local kernels of chains without a lowpass (qd_plan::spark_ts / spark_R; the lane table in LDS)
+    uint32_t spark_ts = 0, spark_R = 0; bool spark_jt_lds = false;
+    const FixedEntry *fixed = nullptr;      // kTable
+    JitKey key{};                           // kBuild
+    bool required = false;                  // kBuild: failure is an error, not a step down the list (tile hints)
+    int wg_regs = 0;                        // workgroups per CU its register budget admits (0: no bound of its own)
+};
+
+// workgroup size of a chain kernel: nt, plus the consumer waves of the role-split and three-stage kernels; the wave-local kernels
+// run four waves per workgroup whatever their row geometry (their nt = 512 / SPL only lays out the NCO tables)
+int launch_threads(int nt, uint32_t flags) {
+    if (flags & kGeoSpark) return kThreads;
+    return nt + ((flags & kGeoPipe3) ? ((flags & kGeoWriteSink) ? 256 : 512) : ((flags & kGeoPipe) ? ((flags & kGeoPipeFftWave) ? 128 : 64) : 0));
+}
+
+bool lut8_of(int fmt) { return fmt == QD_FMT_CS8 || fmt == QD_FMT_CU8; }
+
+// the plain tiling: windows per tile of the generic kernels and of the plain plan-time build (256 threads, pad 1, batch 1, flags 0)
+uint32_t plain_tiles(const qd_plan *p, uint32_t T_lds) {
+    const bool lut8 = lut8_of(p->d.format);
+    auto fits = [&](uint32_t g, size_t cap) { return lds_for(g, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= cap; };
+    uint32_t G = 1;
+    while (G < 64 && (uint64_t)G * p->W < 256 && fits(G * 2, 40 * 1024)) G *= 2;
+    while (G < 64 && (uint64_t)G * p->W < 1024 && fits(G * 2, 36 * 1024)) G *= 2;
+    // chains without a lowpass (every sample is an FFT input), windows of 128 points and more: 2048 samples per tile while four
+    // workgroups still share a CU — fewer barriers per sample (16 GiB cf32, profiles/r03/nofir_rate.log: W = 128 7.16 -> 6.74 ms,
+    // W = 256 10.50 -> 9.57, cs16 W = 512 10.18 -> 9.07; 4096 samples per tile: 9.04 at W = 128; W = 64 loses with 32 windows: 8.23 -> 9.65)
+    if (!p->has_fir && p->S >= p->W && p->W >= 128) while (G < 64 && (uint64_t)G * p->W < 2048 && fits(G * 2, 40 * 1024)) G *= 2;
+    if (p->n_windows && G > p->n_windows) { while (G > 1 && G / 2 >= p->n_windows) G /= 2; }
+    return G;
+}
+
+// the plan-time build of a chain kernel (k_chain and its role-split / three-stage forms) with this tiling; `capped`: its register budget
+// bounds the workgroups per CU (lb waves per SIMD)
+Candidate chain_build(const qd_plan *p, Candidate c, bool capped) {
+    const uint64_t ROW = (uint64_t)c.nt * spl_of(p->d.format), step = (uint64_t)p->S * p->D;
+    uint64_t tile_raw = (uint64_t)(c.G - 1) * step + (uint64_t)p->W * p->D + p->T;
+    if ((c.flags & kGeoHalfTile) && c.G == 1 && p->S >= p->W) tile_raw = (p->T - p->T / 2) + (uint64_t)(p->W / 2 - 1) * p->D + p->T;      // rows of ONE pass
+    // a run may start at any window, so a tile starts on a row boundary only if S*D is a multiple of ROW
+    const bool tiles_on_rows = step % ROW == 0 || ((c.flags & (kGeoFastP1 | kGeoPipe3)) && (c.G * step) % ROW == 0);
+    uint64_t rows = (tile_raw + ROW - 1) / ROW + (tiles_on_rows ? 0 : 1);
+    if ((c.flags & kGeoPipe3) && (c.flags & kGeoStream)) rows = (c.G * step) / ROW;      // rows per step of the streaming kernel
+    // the unrolled FIR's scalar accumulate chains must stay scalar (the three-stage kernel's FIR is the packed asm form)
+    const int noslp = c.noslp || ((c.flags & kGeoUnrolledFir) && !(c.flags & kGeoPipe3));
+    c.src = Candidate::kBuild;
+    c.key = JitKey{p->d.format, p->nco, p->has_fir ? 1 : 0, rows <= 10 ? (int)rows : 4, rows <= 10 ? 1 : 0, c.lb, c.nt,
+                   p->W, p->S, p->D, p->T, c.G, c.firb, c.firr, noslp, c.pad, c.batch, c.flags,
+                   (c.flags & kGeoBakedTaps) ? fnv1a(p->taps_h.data(), p->taps_h.size() * sizeof(float)) : 0ull};
+    c.wg_regs = capped ? std::max(1, c.lb * 4 * 64 / launch_threads(c.nt, c.flags)) : 0;
+    return c;
+}
+
+// ---- kernel variant from GEOMETRY (plan-time builds): the variants of the built-in cfg3' / cfg4 kernels as predicates of the shape
+// (profiles/r03/shape_sweep.log).  The predicates restate FixedGeo's own static conditions (qd_chain.h), so
+// the build takes the path asked for.  Returns false for shapes without a recipe.
+bool geometry_recipe(const qd_plan *p, uint32_t T_lds, Candidate *r) {
+    const uint32_t W = p->W, S = p->S, D = p->D, T = p->T, c_half = T - T / 2;
+    const int spl = spl_of(p->d.format);
+    const bool lut8 = lut8_of(p->d.format);
+    r->pad = 2;
+    if (p->d.epilogue == QD_EPI_CF32_BLOCKS) {
+        // The `write` sink (N1: shift -> lowpass -> decimated cf32 in read_at blocks): the streaming kernel with producers and FIR waves
+        // only — a step is one sub-block of W = min(block, 256) outputs on as many FIR lanes, which store their outputs themselves;
+        // truncation is relative to the block (ChainParams::blk_len).  The conditions restate Pipe3S<>::ok for side-by-side windows.
+        const bool pk_geo = T % 4 == 0 && (T / 2) % 4 == 0 && T / 4 > 3 && D % 4 == 0 && (c_half % D) % 2 == 0 && D % spl == 0 && is_pow2(W) && W <= 256 &&
+                            p->blk_len % W == 0 && is_pow2(p->blk_subs);
+        for (int snt : {512, 256}) {
+            if (!pk_geo) break;
+            const uint64_t SROW = (uint64_t)snt * spl, n_new = (uint64_t)W * D;
+            if (n_new % SROW != 0 || SROW % D != 0 || n_new < (uint64_t)c_half + T || n_new / SROW > 10) continue;
+            const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
+            if (f0 > W || mird * D > SROW) continue;
+            const uint32_t fl = kGeoNoSplit | kGeoNtLoads | kGeoPipe3 | kGeoStream | kGeoWriteSink;
+            if (lds_for(1, W, W, D, T, nullptr, 2, 1, lut8, fl, nullptr, spl, snt) > kLdsMax ||        // the kernel's own layout (its T, no tile_extra) ...
+                lds_for(1, W, W, D, T_lds, nullptr, 1, 1, lut8) > kLdsMax) continue;                        // ... and the generic kernels' tile for an unaligned tail
+            r->G = 1; r->nt = snt; r->flags = fl;
+            return true;
+        }
+        return false;
+    }
+    if (S < W) {
+        // Overlapping windows with a long filter (>= 8 taps per input sample): the three-stage kernel (shared FIR on 16-byte rows, at most
+        // 256 outputs per tile, tiles on rows of 512 producer threads), streaming where its geometry holds.  cfg5: 7.50 -> 6.71 ms.
+        const uint32_t ntrunc = c_half ? (c_half + D - 1) / D - 1 : 0;
+        if ((uint64_t)T < 8ull * D || !(ntrunc <= S && D % 2 == 0 && c_half % 2 == 0 && T % 4 == 0 && (c_half % D) % 2 == 0 && D % 4 == 0 && T >= 32 &&
+                                        D % spl == 0 && is_pow2(W) && W <= 1024))
+            return false;
+        const uint64_t ROW = 512ull * spl, step = (uint64_t)S * D;
+        uint64_t a = ROW, b = step; while (b) { const uint64_t t = a % b; a = b; b = t; }      // gcd
+        const uint32_t g_unit = (uint32_t)(ROW / a);                                              // tiles start on rows when G is a multiple of this
+        // (1) the STREAMING form (k_chain_pipe3s): the step of G S new outputs with the most outputs the rings leave room for (the FIR is
+        // bound by one wave's pass over the T taps), rows of 512 producer threads or of 256 where that admits a larger step (8-bit
+        // formats).  The conditions restate Pipe3S<>::ok (qd_chain.h).
+        uint32_t best_s = 0; int best_nt = 512;
+        for (int snt : {512, 256}) {
+            const uint64_t SROW = (uint64_t)snt * spl;
+            uint64_t a2 = SROW, b2 = step; while (b2) { const uint64_t t = a2 % b2; a2 = b2; b2 = t; }
+            const uint32_t su = (uint32_t)(SROW / a2);
+            for (uint32_t g = su; g >= 1 && g <= 64 && (uint64_t)g * S <= 256; g += su) {
+                const uint64_t n_new = (uint64_t)g * S * D, gs = (uint64_t)g * S;
+                if (n_new < (uint64_t)c_half + T) continue;
+                const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
+                if (!(SROW % D == 0 && f0 <= gs && f0 > W - S && mird * D <= SROW && (uint64_t)(g - 1) * S + W <= 2 * gs && n_new / SROW <= 10)) continue;
+                if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3 | kGeoStream, nullptr, spl, snt) > kLdsMax) break;
+                if (p->n_windows < g) break;
+                if (g > best_s) { best_s = g; best_nt = snt; }
+            }
+        }
+        if (best_s) { r->G = best_s; r->nt = best_nt; r->flags = kGeoUnrolledFir | kGeoPipe3 | kGeoStream | kGeoNtLoads; return true; }
+        // (2) the tile-at-a-time three-stage kernel, where the streaming form's geometry fails
+        uint32_t best = 0;
+        for (uint32_t g = g_unit; g >= 1 && g <= 64 && (uint64_t)(g - 1) * S + W <= 256; g += g_unit) {
+            const uint64_t tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
+            if ((tile_raw + ROW - 1) / ROW > 10) break;
+            if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3) > kLdsMax) break;
+            if (p->n_windows < g) break;
+            best = g;
+        }
+        if (best) { r->G = best; r->nt = 512; r->flags = kGeoUnrolledFir | kGeoPipe3; return true; }
+        return false;
+    }
+    auto rows_aligned = [&](uint32_t nt, uint32_t g) {            // fast phase 1: tiles start on a row boundary, <= 10 rows, whole-tile prefetch
+        const uint64_t ROW = (uint64_t)nt * spl, tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
+        return ((uint64_t)S * D) % ROW == 0 && (tile_raw + ROW - 1) / ROW <= 10 && D % spl == 0;
+    };
+    const bool pk_geo = T >= 64 && T % 4 == 0 && D % 4 == 0 && is_pow2(D) && c_half % 2 == 0 && (c_half % D) % 2 == 0;
+    const bool tile2_geo = pk_geo && (T / 2) % 4 == 0 && c_half % 4 == 0 && D / 4 <= 8 && T > D + 16 && W % 2 == 0;
+    if (tile2_geo && W >= 512 && (uint64_t)T >= 4ull * D) {
+        // one long window per tile (cfg4's recipe): two outputs per lane as straight-line packed code with in-chain
+        // snapshots, the previous window's FFT + epilogue on idle waves, as many threads as the FIR has lanes for
+        // half-window tiles (two passes per window, two workgroups per CU) where a pass is a whole number of rows of 512 threads
+        const uint64_t half_raw = (uint64_t)c_half + (uint64_t)(W / 2 - 1) * D + T, ROW512 = 512ull * spl;
+        const bool half_ok = W >= 1024 && W % 4 == 0 && ((uint64_t)(W / 2) * D) % ROW512 == 0 && ((uint64_t)S * D) % ROW512 == 0 &&
+                             (half_raw + ROW512 - 1) / ROW512 <= 10 && D % spl == 0;
+        const int nt = half_ok ? 512 : (W >= 1024 ? 1024 : 512);
+        const uint32_t fl = kGeoPackedTile | kGeoDeferFft | (half_ok ? (kGeoHalfTile | kGeoFastP1 | kGeoNtLoads) : (rows_aligned(nt, 1) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u));
+        if (lds_for(1, W, S, D, T_lds, nullptr, 2, 2, lut8, fl) > kLdsMax) return false;
+        r->G = 1; r->nt = nt; r->batch = 2; r->flags = fl; r->firr = 2; r->firb = 4;
+        return true;
+    }
+    if (pk_geo && W <= 256) {
+        // 64..256 outputs per tile of 256 threads (cfg3' recipe): packed lane-per-output FIR on a 16-byte-row tile; where the
+        // FIR leaves a wave idle, the previous tile's FFT + epilogue runs there
+        const uint32_t g = W >= 128 ? 1u : 128u / W;
+        const bool defer = (g * W) % 64 == 0 && g * W + 64 <= 256;
+        const uint32_t fl = kGeoNoSplit | (defer ? kGeoDeferFft : 0u) | (rows_aligned(256, g) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u);
+        const uint32_t bt = defer ? 2u : 1u;
+        if (p->n_windows < g || lds_for(g, W, S, D, T_lds, nullptr, 2, bt, lut8, fl) > kLdsMax / 2) return false;      // at least two workgroups per CU
+        r->G = g; r->nt = 256; r->batch = bt; r->flags = fl;
+        return true;
+    }
+    return false;
+}
+
+// The candidates of a chain plan without a tile hint, best first; every list ends in a kernel that is always to be had.
+std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
+    const qd_chain_desc &d = p->d;
+    const int policy = p->opt.kernel_policy, spl = spl_of(d.format), bps = bps_of(d.format);
+    const uint32_t W = p->W, S = p->S;
+    const bool write_sink = d.epilogue == QD_EPI_CF32_BLOCKS;
+    // plan-time builds: QD_KERNEL_NO_PLAN_TIME / QD_KERNEL_GENERIC never
+    const bool jit_ok = policy != QD_KERNEL_GENERIC && policy != QD_KERNEL_NO_PLAN_TIME;
+    Candidate plain;
+    plain.G = plain_tiles(p, T_lds);
+    Candidate generic = plain;
+    generic.wg_regs = dyn_lb(p->nco);
+    // shape-specialised built-in kernels (kFixed): exact arithmetic; QD_MODE_FAST prefers a fused build of the shape's recipe
+    const FixedEntry *fixed = (p->has_fir && !write_sink && policy != QD_KERNEL_GENERIC) ? find_fixed(d.format, p->nco, W, S, p->D, p->T) : nullptr;
+    const bool fast = d.mode == QD_MODE_FAST && p->has_fir && jit_ok && !write_sink;
+    Candidate recipe;
+    const bool has_recipe = jit_ok && p->has_fir && (!fixed || fast) && geometry_recipe(p, T_lds, &recipe);
+    Candidate table;
+    if (fixed) {
+        table.src = Candidate::kTable; table.fixed = fixed;
+        table.G = fixed->G; table.nt = fixed->nt; table.pad = (uint32_t)fixed->pad; table.batch = (uint32_t)fixed->batch;
+        table.flags = (uint32_t)fixed->flags; table.lb = fixed->lb; table.wg_regs = std::max(1, fixed->lb * 256 / fixed->nt);
+        if (!has_recipe) return {table};
+    }
+    if (has_recipe) {
+        if (fast) recipe.flags |= kGeoFastFma;
+        // no fused build to be had: the exact built-in kernel with ITS tiling, not the plain one
+        if (fixed) return {chain_build(p, recipe, true), table};
+        // (the write sink's only other kernel is the generic one)
+        if (write_sink) return {chain_build(p, recipe, true), generic};
+        return {chain_build(p, recipe, true), chain_build(p, plain, false), generic};
+    }
+    if (jit_ok && !write_sink && p->has_fir && (uint64_t)p->T >= 8ull * p->D) {
+        // FIR-dominated shapes (>= 8 taps per input sample): a tile's FIR phase is latency-bound — one wave walks all T taps however
+        // few outputs the tile has — so take the largest tile with <= 512 FIR outputs that LDS allows, 512 threads, a 256-VGPR budget
+        // and scalar accumulate chains (measured 1.3-2.9x over the small-tile default on six such shapes, scripts/policy_probe.py;
+        // DESIGN.md section 7); 16-byte aligned LDS rows (pad 2): ds_read_b128 sample pairs in the tap loop (FixedGeo::kPad)
+        auto outs = [&](uint32_t g) { return S < W ? (uint64_t)(g - 1) * S + W : (uint64_t)g * W; };
+        Candidate lf;
+        lf.nt = 512; lf.pad = 2; lf.lb = 2; lf.noslp = 1;
+        while (lf.G < 64 && outs(lf.G + 1) <= 512 && lds_for(lf.G + 1, W, S, p->D, T_lds, nullptr, 2, 1, lut8_of(d.format)) <= kLdsMax) ++lf.G;
+        if (p->n_windows && lf.G > p->n_windows) lf.G = (uint32_t)p->n_windows;
+        return {chain_build(p, lf, true), chain_build(p, plain, false), generic};
+    }
+    // chains without a lowpass: the wave-local kernels (qd_chain.h).  Their row tables and lane table are laid out for NCO rows of
+    // 512 samples.  Plan-time builds: cached ones always, a new one for streams of 1 GiB and more.
+    auto spark = [&](uint32_t ts, uint32_t flags, int lb) {
+        Candidate c;
+        c.src = Candidate::kBuiltinSpark; c.spark_ts = ts; c.G = ts / W; c.nt = (int)(kSparkRow / spl); c.flags = kGeoSpark | flags; c.lb = c.wg_regs = lb;
+        return c;
+    };
+    auto spark_build = [&](Candidate c, int nco, uint32_t key_S, int rch) {      // (their keys are not chain_build's)
+        c.src = Candidate::kBuild;
+        c.key = JitKey{d.format, nco, 0, rch, 1, c.lb, kThreads, W, key_S, 1, 0, c.G, 8, 1, 0, 1, 1, c.flags, 0ull, d.epilogue};
+        return c;
+    };
+    const bool pow2_spark2 = W == 128 || W == 256 || W == 512 || W == 1024;
+    // width 16 or 64 columns: the plan-time kernel that runs the base butterflies out of the row registers (k_spark2);
+    // tile = 64 lanes x 2 columns x base rows
+    auto spark2 = [&](bool ov_shift) {
+        const uint32_t fbase = (ilog2(W) & 1) ? 8u : 16u;
+        const int lb2 = p->has_shift ? (fbase == 8 ? 3 : 2) : (fbase == 8 ? 4 : 3);
+        Candidate c = spark(128u * fbase, kGeoSparkReg, lb2);
+        c.spark_R = ov_shift ? W / S : 0;
+        // (the kernel's own geometry is windows side by side: S = W also where the plan's windows overlap with a shift, see spark_R)
+        return spark_build(c, p->nco, ov_shift ? W : S, 0);
+    };
+    // the built-in k_spark with the width a compile-time constant (one base butterfly instead of five; with a shift the lane constants
+    // come out of an LDS copy of the lane table: four waves per SIMD at either tile size); rch = chunks per tile
+    auto spark_jit = [&](uint32_t R) {
+        Candidate c = spark(spark_tile(W, p->nco), 0, 4);
+        c.spark_R = R; c.spark_jt_lds = p->has_shift;
+        return spark_build(c, p->nco, W, (int)(c.spark_ts / (64u * (uint32_t)spl)));
+    };
+    const bool spark_ok = !p->has_fir && W <= kSparkMaxW && !write_sink && policy != QD_KERNEL_GENERIC;
+    if (spark_ok && S == W) {
+        const uint32_t ts = spark_tile(W, p->nco);
+        if (!jit_ok) return {spark(ts, 0, spark_lb(ts, p->nco))};
+        if (!pow2_spark2) return {spark_jit(0), spark(ts, 0, spark_lb(ts, p->nco))};
+        return {spark2(false), spark_jit(0), spark(ts, 0, spark_lb(ts, p->nco))};
+    }
+    // OVERLAPPING windows (`sparkfft -width 4 -stride 2`: README example 1), plan-time builds only: W = 128 ... 1024 in ONE launch of
+    // k_spark2 built for the stride (the overlap comes out of the caches; with a shift, the S = W build in interleaved launches);
+    // W = 2 ... 8 without a shift on k_spark0, a window per lane, no LDS (W = 16 is bit-exact too but 2x slower: quarter-filled stores);
+    // where the stride divides the width, R = W / S launches of k_spark over the windows phi, phi + R, ... (side by side in the stream
+    // shifted by phi S), each writing every R-th output row (the lean norms and glyph sinks)
+    if (spark_ok && S < W && jit_ok && ((uint64_t)S * bps) % 4 == 0) {
+        const bool direct = !p->has_shift && W >= 2 && W <= 8 && ((uint64_t)W * bps) % 4 == 0;
+        const bool one_launch = !p->has_shift && pow2_spark2;
+        const bool lean_sink = d.epilogue == QD_EPI_NORMS_F32 || d.epilogue == QD_EPI_GLYPH_U8;
+        const bool phases = W % S == 0 && W / S <= 32 && lean_sink && W >= (uint32_t)spl;
+        if (direct || one_launch || phases) {
+            std::vector<Candidate> list;
+            if (pow2_spark2 && (!p->has_shift || lean_sink)) list.push_back(spark2(p->has_shift));
+            if (direct) {
+                Candidate c = spark(spark_tile(W, p->nco), kGeoSparkDirect, 4);
+                c.G = 64;
+                list.push_back(spark_build(c, 0, S, 0));
+            }
+            if (phases) list.push_back(spark_jit(W / S));
+            list.push_back(chain_build(p, plain, false));
+            list.push_back(generic);
+            return list;
+        }
+    }
+    if (jit_ok && !write_sink) return {chain_build(p, plain, false), generic};
+    return {generic};
+}
+
+// Commits the chosen candidate to the plan: tiling, LDS sizes, kernels (jit_fn: the plan-time build, when it is one).
+int commit_candidate(qd_plan *p, const Candidate &c, hipFunction_t jit_fn, uint32_t T_lds) {
+    const int fmt = p->d.format;
+    p->fixed = c.fixed;
+    p->jit_fn = jit_fn;
+    p->spark = (c.flags & kGeoSpark) != 0;
+    p->spark_ts = c.spark_ts; p->spark_R = c.spark_R;
+    p->geo.G = c.G; p->nt = c.nt; p->kflags = c.flags;
+    p->launch_nt = launch_threads(c.nt, c.flags);
+    // the generic kernels (pad 1, batch 1) fit inside the same allocation; the streaming write kernel is laid out for T, the generic
+    // kernels' tile (an unaligned tail) for T + tile_extra
+    const bool ws = (c.flags & kGeoWriteSink) != 0;
+    uint32_t raw_elems = 0;
+    p->geo.lds_bytes = lds_for(c.G, p->W, p->S, p->D, ws ? p->T : T_lds, &raw_elems, c.pad, c.batch, lut8_of(fmt), c.flags, &p->geo.lds_main, spl_of(fmt), c.nt);
+    if (ws) p->geo.lds_bytes = std::max(p->geo.lds_bytes, lds_for(c.G, p->W, p->S, p->D, T_lds, &raw_elems, 1, 1, lut8_of(fmt)));
+    if (!(c.flags & (kGeoHalfTile | kGeoPipe3))) p->geo.lds_main = p->geo.lds_bytes;
+    if (p->spark) p->geo.lds_main = ((size_t)(p->W < 32 ? 32 : p->W) + 4 * (size_t)c.spark_ts) * 8 +     // twiddles | four waves' transform buffers (k_spark)
+                                    ((((c.flags & kGeoSparkReg) && p->has_shift) || c.spark_jt_lds) ? (size_t)kSparkRow * 16 : 0);   // plan-time builds with a shift: + the NCO lane table
+    if (c.flags & kGeoSparkDirect) p->geo.lds_main = 16;                 // k_spark0 uses no LDS (a token size: 0 means "the generic layout's")
+    p->geo.lds_raw_elems = raw_elems;
+    p->geo.Dp = p->D + ((p->D % 2 == 0) ? 1 : 0);
+    if ((uint64_t)raw_elems * p->D >= (1ull << 32)) return fail(QD_ERR_UNSUPPORTED, "tile too large");
+    // (a k_spark2 plan's built-in kernel is the runtime-width k_spark of its tile: take_fft's row-offset launches run it)
+    p->fn = c.fixed ? c.fixed->fn : (p->spark ? pick_spark(fmt, p->nco, c.spark_ts) : pick_generic(fmt, p->nco, p->has_fir, true));
+    p->fn_unaligned = pick_generic(fmt, p->nco, p->has_fir, false);
+    if (!p->fn || !p->fn_unaligned) return fail(QD_ERR_UNSUPPORTED, "no kernel built for this format (QD_DEV_FAST build?)");
+    return QD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1225,7 +1523,7 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
         const uint32_t c = (uint32_t)(d.taps - d.taps / 2);
         p->tile_extra = c > d.decimate ? c - (uint32_t)d.decimate : 0;
         // a sub-block's FIR input (W D + T + extra samples) must fit the LDS tile: long decimations take shorter sub-blocks
-        while (p->W > 1 && lds_for(1, p->W, p->W, (uint64_t)d.decimate, d.taps + p->tile_extra, nullptr, 1, 1, d.format == QD_FMT_CS8 || d.format == QD_FMT_CU8) > kLdsMax) p->W /= 2;
+        while (p->W > 1 && lds_for(1, p->W, p->W, (uint64_t)d.decimate, d.taps + p->tile_extra, nullptr, 1, 1, lut8_of(d.format)) > kLdsMax) p->W /= 2;
         p->logW = ilog2(p->W); p->S = p->W;
         p->blk_subs = p->blk_len / p->W;
     }
@@ -1244,376 +1542,61 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
     if (const char *e = dev_env("QD_DEBUG_SKIP")) p->dbg = (uint32_t)atoi(e);     // development builds: timing-only ablation
     const int policy = p->opt.kernel_policy;
 
-    // tile geometry: a shape-specialised kernel dictates G; otherwise pick G for LDS / lane use
-    uint32_t G = 1, raw_elems = 0;
     const uint32_t T_lds = p->T + p->tile_extra;     // LDS sizing sees the extended tile
-    if (lds_for(1, p->W, p->S, p->D, T_lds, &raw_elems, 1, 1, d.format == QD_FMT_CS8 || d.format == QD_FMT_CU8) > kLdsMax) {
+    if (lds_for(1, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8_of(d.format)) > kLdsMax) {
         // LowPass::read_at allocates whatever buf.len() * D + T asks for (src/filter.rs:68-69); one workgroup's LDS does not.  Windows that
         // lie side by side run as a two-stage (composite) plan instead — qd_plan_create_ex builds it on this status
         if (p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && p->S == p->W) return kNeedComposite;
         return fail(QD_ERR_UNSUPPORTED, "one window (W*D+T = %llu samples) exceeds the 160 KiB LDS tile and the windows overlap or leave gaps (stride != width)",
                     (unsigned long long)((uint64_t)d.width * (d.has_lowpass ? d.decimate : 1) + (d.has_lowpass ? d.taps : 0)));
     }
-    p->fixed = (p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && policy != QD_KERNEL_GENERIC) ? find_fixed(d.format, p->nco, p->W, p->S, p->D, p->T) : nullptr;
     // qd_plan_options.tile_hint = {G, NT, FIRR, FIRB, LB, PAD}: force a plan-time build with this tiling instead of the table /
     // heuristics (LB = waves per SIMD the build is register-budgeted for: 4 -> 128 VGPRs, 2 -> 256; PAD = LDS pad elements per row)
-    // [6] = tiles per FFT batch (FixedGeo::kBatch), [7] = workgroups per CU (0: as many as LDS / registers admit, at most 4)
-    const bool lut8 = d.format == QD_FMT_CS8 || d.format == QD_FMT_CU8;
-    // chains without a lowpass whose windows lie side by side: the wave-local kernel (k_spark), for every width it holds in a tile
-    p->spark = !p->has_fir && p->S == p->W && p->W <= kSparkMaxW && d.epilogue != QD_EPI_CF32_BLOCKS && policy != QD_KERNEL_GENERIC;
-    // ... and OVERLAPPING windows without a lowpass or a shift (`sparkfft -width 4 -stride 2`: README example 1, BASELINE configs[0]'s chain),
-    // as plan-time builds only:
-    //   * W = 128 ... 1024, any stride: ONE launch of k_spark2 built for the stride — every window's rows are loaded for it, the overlap
-    //     comes out of the caches;
-    //   * W = 2 ... 8, any stride: k_spark0 — a lane owns a window from load to store (one base butterfly), no LDS;
-    //   * the widths between whose stride divides them: the windows phi, phi + R, phi + 2R ... (R = W / S) lie side by side in the stream
-    //     shifted by phi * S samples, so the chain is R launches of k_spark, each writing every R-th output row (the row stride lives in
-    //     its lean epilogue: norms and glyph sinks).
-    // Everything else stays on k_chain.
-    if (!p->has_fir && p->S < p->W && p->W <= kSparkMaxW && d.epilogue != QD_EPI_CF32_BLOCKS &&
-        policy != QD_KERNEL_GENERIC && policy != QD_KERNEL_NO_PLAN_TIME && ((uint64_t)p->S * bps_of(d.format)) % 4 == 0) {
-        // k_spark0: a window per lane, no LDS.  (W = 16 builds and is bit-exact too, but a lane's 64-byte output piece makes quarter-filled
-        // store instructions: 2^28 cf32 samples at S = 4 took 5.2 ms against 2.6 for the interleaved launches)
-        const bool direct = !p->has_shift && p->W >= 2 && p->W <= 8 && ((uint64_t)p->W * bps_of(d.format)) % 4 == 0;
-        const bool one_launch = !p->has_shift && (p->W == 128 || p->W == 256 || p->W == 512 || p->W == 1024);
-        const bool phases = p->W % p->S == 0 && p->W / p->S <= 32 && (d.epilogue == QD_EPI_NORMS_F32 || d.epilogue == QD_EPI_GLYPH_U8) && p->W >= (uint32_t)spl_of(d.format);
-        if (direct || one_launch || phases) { p->spark = true; p->spark_ov = true; p->spark_R = phases ? p->W / p->S : 1; }
+    // [6] = tiles per FFT batch (FixedGeo::kBatch) | kernel variant flags << 8, [7] = workgroups per CU (0: as many as LDS / registers
+    // admit, at most 4)
+    const uint32_t *h = p->opt.tile_hint;
+    const bool hinted = h[0] || h[1];
+    Candidate hint;
+    if (hinted) {
+        hint.G = h[0]; hint.nt = (int)h[1]; hint.firr = h[2] ? h[2] : 1u; hint.firb = h[3] ? h[3] : 8u; hint.lb = (int)(h[4] ? h[4] : 4u);
+        hint.pad = h[5] ? h[5] : 1u; hint.batch = (h[6] & 0xffu) ? (h[6] & 0xffu) : 1u; hint.flags = h[6] >> 8;
+        hint.required = true;
+        if (!(p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && hint.lb >= 1 && hint.lb <= 8 && hint.G >= 1 &&
+              (hint.nt == 256 || hint.nt == 512 || hint.nt == 1024) && (hint.pad == 1 || hint.pad == 2) && hint.batch <= 64 && h[7] <= 8 &&
+              hint.flags <= 524287 &&
+              lds_for(hint.G, p->W, p->S, p->D, T_lds, nullptr, hint.pad, hint.batch, lut8_of(d.format), hint.flags, nullptr, spl_of(d.format), hint.nt) <= kLdsMax))
+            return fail(QD_ERR_INVALID, "tile_hint {%u,%u,%u,%u,%u,%u,%u,%u} does not fit this chain", hint.G, (uint32_t)hint.nt, hint.firr, hint.firb,
+                        (uint32_t)hint.lb, hint.pad, hint.batch, h[7]);
     }
-    uint32_t tune[8] = {0, 0, 1, 8, 4, 1, 1, 0};
-    uint32_t hint_flags = 0;
-    bool tuned = false;
-    if (p->opt.tile_hint[0] || p->opt.tile_hint[1]) {
-        const uint32_t *h = p->opt.tile_hint;
-        const uint32_t t8[8] = {h[0], h[1], h[2] ? h[2] : 1u, h[3] ? h[3] : 8u, h[4] ? h[4] : 4u, h[5] ? h[5] : 1u, (h[6] & 0xffu) ? (h[6] & 0xffu) : 1u, h[7]};
-        hint_flags = h[6] >> 8;          // bits 8+ of slot 6: kernel variant flags (1 planar LDS tile, 2 taps baked into the code)
-        if (!(p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && t8[4] >= 1 && t8[4] <= 8 && t8[0] >= 1 &&
-              (t8[1] == 256 || t8[1] == 512 || t8[1] == 1024) && (t8[5] == 1 || t8[5] == 2) && t8[6] <= 64 && t8[7] <= 8 && hint_flags <= 524287 &&
-              lds_for(t8[0], p->W, p->S, p->D, T_lds, nullptr, t8[5], t8[6], lut8, hint_flags, nullptr, spl_of(d.format), (int)t8[1]) <= kLdsMax))
-            return fail(QD_ERR_INVALID, "tile_hint {%u,%u,%u,%u,%u,%u,%u,%u} does not fit this chain", t8[0], t8[1], t8[2], t8[3], t8[4], t8[5], t8[6], t8[7]);
-        for (int i = 0; i < 8; ++i) tune[i] = t8[i];
-        tuned = true;
-        p->fixed = nullptr;
-    }
-    // Plan-time specialisation is wanted for shapes without a built-in kernel once the stream is big enough to
-    // repay the ~0.3 s compile (qd_plan_options.kernel_policy: QD_KERNEL_SPECIALISE always, QD_KERNEL_NO_PLAN_TIME /
-    // QD_KERNEL_GENERIC never).
+    // Plan-time specialisation (qd_plan_options.kernel_policy): a cached build is always used; a NEW build only when forced, for tile
+    // hints and QD_MODE_FAST, or when the stream is at least 1 GiB
     const uint64_t in_bytes = (uint64_t)d.n_samples * bps_of(d.format);
-    // (the write sink, QD_EPI_CF32_BLOCKS, has exactly one specialised kernel: the streaming one, chosen further down from the geometry)
-    const bool write_sink = d.epilogue == QD_EPI_CF32_BLOCKS;
-    const bool jit_ok = policy != QD_KERNEL_GENERIC && policy != QD_KERNEL_NO_PLAN_TIME;
-    // a cached build is always used; a NEW build only when forced or when the stream is at least 1 GiB
-    const bool may_compile = policy == QD_KERNEL_SPECIALISE || tuned || in_bytes >= (1ull << 30) || d.mode == QD_MODE_FAST;
-    uint32_t batch = 1, kflags = 0;    // tiles per FFT batch / variant flags the main kernel is built with (FixedGeo BATCH_, FLAGS_)
+    const bool may_compile = policy == QD_KERNEL_SPECIALISE || hinted || in_bytes >= (1ull << 30) || d.mode == QD_MODE_FAST;
     if (p->has_fir) { p->taps_h.resize(p->T); design_taps(d.lowpass_hz, d.sample_rate, p->T, p->taps_h.data()); }
-    auto make_key = [&](uint32_t g, int nt, int lb, int noslp, uint32_t padv, uint32_t batchv = 1, uint32_t flagsv = 0) {
-        const uint64_t ROW = (uint64_t)nt * spl_of(d.format);
-        uint64_t tile_raw = (uint64_t)(g - 1) * p->S * p->D + (uint64_t)p->W * p->D + p->T;
-        if ((flagsv & kGeoHalfTile) && g == 1 && p->S >= p->W) tile_raw = (p->T - p->T / 2) + (uint64_t)(p->W / 2 - 1) * p->D + p->T;      // rows of ONE pass
-        // a run may start at any window, so a tile starts on a row boundary only if S*D is a multiple of ROW
-        const bool tiles_on_rows = (((uint64_t)p->S * p->D) % ROW) == 0 || ((flagsv & (kGeoFastP1 | kGeoPipe3)) && (((uint64_t)g * p->S * p->D) % ROW) == 0);
-        uint64_t rows = (tile_raw + ROW - 1) / ROW + (tiles_on_rows ? 0 : 1);
-        if ((flagsv & kGeoPipe3) && (flagsv & kGeoStream)) rows = ((uint64_t)g * p->S * p->D) / ROW;      // rows per step of the streaming kernel
-        if ((flagsv & kGeoUnrolledFir) && !(flagsv & kGeoPipe3)) noslp = 1;       // its scalar accumulate chains must stay scalar (the three-stage kernel's FIR is the packed asm form)
-        return JitKey{d.format, p->nco, p->has_fir ? 1 : 0, rows <= 10 ? (int)rows : 4, rows <= 10 ? 1 : 0, lb, nt,
-                      p->W, p->S, p->D, p->T, g, tune[3], tune[2], noslp, padv, batchv, flagsv,
-                      (flagsv & kGeoBakedTaps) ? fnv1a(p->taps_h.data(), p->taps_h.size() * sizeof(float)) : 0ull};
-    };
-    // FIR-dominated shapes (>= 8 taps per input sample): a tile's FIR phase is latency-bound — one wave walks
-    // all T taps however few outputs the tile has — so take the largest tile with <= 512 FIR outputs that LDS
-    // allows, 512 threads, a 256-VGPR budget and scalar accumulate chains (measured 1.3-2.9x over the small-tile
-    // default on six such shapes, scripts/policy_probe.py)
-    bool auto_variant = false;     // variant flags derived from the geometry, not from the table or a hint
-    // ---- kernel variant from GEOMETRY (plan-time builds of shapes without a built-in kernel).  The variants the built-in
-    // cfg3' / cfg4 kernels use are predicates of the shape, not of a table entry: a chain of 192 taps or W = 256 gets the same
-    // packed FIR, row-aligned phase 1 with non-temporal loads, deferred FFT and (long windows) two-output register tiling
-    // (profiles/r03/shape_sweep.log: 0.45-0.47 of the VALU roof on 160 / 192 / 256 / 384-tap neighbours of cfg3', where the
-    // long-filter policy below reached 0.30-0.35).  The predicates restate FixedGeo's own static conditions (qd_chain.h), so the
-    // build takes the path asked for; if no variant build is to be had the plan falls back to the plain tiling further down.
-    struct { bool valid = false; uint32_t G = 1, batch = 1, flags = 0, firr = 1, firb = 8; int nt = kThreads; } autosel;
-    // QD_MODE_FAST (qd_chain_desc.mode): the built-in kernels are exact-order; a fused build is the geometry recipe + bit 14, made
-    // at plan time whatever the stream's size.  No recipe for the shape (overlapping windows, short filters): the exact kernels.
-    const bool fast_mode = d.mode == QD_MODE_FAST && p->has_fir && jit_ok && !tuned && !write_sink;
-    const FixedEntry *fixed_exact = p->fixed;
-    if (fast_mode) p->fixed = nullptr;
-    if (jit_ok && !tuned && !p->fixed && p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && p->S < p->W && (uint64_t)p->T >= 8ull * p->D) {
-        // Overlapping windows with a long filter (the long-filter class below): the THREE-STAGE kernel (k_chain_pipe3) where its geometry
-        // holds — straight-line shared FIR on 16-byte rows, at most 256 outputs per tile, tiles on row boundaries of 512 producer
-        // threads, two tile buffers in LDS — with the largest such tile.  cfg5's shape: 7.50 -> 6.71 ms against the one-tile-per-CU form.
-        const uint32_t W = p->W, S = p->S, D = p->D, T = p->T, c_half = T - T / 2;
-        const int spl = spl_of(d.format);
-        const uint32_t ntrunc = c_half ? (c_half + D - 1) / D - 1 : 0;
-        const bool geo_ok = ntrunc <= S && D % 2 == 0 && c_half % 2 == 0 && T % 4 == 0 && (c_half % D) % 2 == 0 && D % 4 == 0 && T >= 32 && D % spl == 0 &&
-                            is_pow2(W) && W <= 1024;
-        if (geo_ok) {
-            const uint64_t ROW = 512ull * spl, step = (uint64_t)S * D;
-            uint64_t a = ROW, b = step; while (b) { const uint64_t t = a % b; a = b; b = t; }      // gcd
-            const uint32_t g_unit = (uint32_t)(ROW / a);                                              // tiles start on rows when G is a multiple of this
-            // (1) the STREAMING form (k_chain_pipe3s): a step adds G S new outputs on G S FIR lanes and G S D new samples; the step with
-            // the most outputs that the rings leave room for (the FIR stage is bound by the latency of one wave's pass over the T taps,
-            // so outputs per pass is what counts).  Rows of 512 producer threads, or of 256 where the shorter row admits a larger step
-            // (the 8-bit formats: four samples per lane).  The conditions restate Pipe3S<>::ok (qd_chain.h).
-            uint32_t best_s = 0; int best_nt = 512;
-            for (int snt : {512, 256}) {
-                const uint64_t SROW = (uint64_t)snt * spl;
-                uint64_t a2 = SROW, b2 = step; while (b2) { const uint64_t t = a2 % b2; a2 = b2; b2 = t; }
-                const uint32_t su = (uint32_t)(SROW / a2);
-                for (uint32_t g = su; g >= 1 && g <= 64 && (uint64_t)g * S <= 256; g += su) {
-                    const uint64_t n_new = (uint64_t)g * S * D, gs = (uint64_t)g * S;
-                    if (n_new < (uint64_t)c_half + T) continue;
-                    const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
-                    if (!(SROW % D == 0 && f0 <= gs && f0 > W - S && mird * D <= SROW && (uint64_t)(g - 1) * S + W <= 2 * gs && n_new / SROW <= 10)) continue;
-                    if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3 | kGeoStream, nullptr, spl, snt) > kLdsMax) break;
-                    if (p->n_windows < g) break;
-                    if (g > best_s) { best_s = g; best_nt = snt; }
-                }
-            }
-            // (2) the tile-at-a-time three-stage kernel, where the streaming form's geometry fails
-            uint32_t best = 0;
-            for (uint32_t g = g_unit; !best_s && g >= 1 && g <= 64 && (uint64_t)(g - 1) * S + W <= 256; g += g_unit) {
-                const uint64_t tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
-                if ((tile_raw + ROW - 1) / ROW > 10) break;
-                if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3) > kLdsMax) break;
-                if (p->n_windows < g) break;
-                best = g;
-            }
-            if (best_s) { autosel.valid = true; autosel.G = best_s; autosel.nt = best_nt; autosel.batch = 1; autosel.flags = kGeoUnrolledFir | kGeoPipe3 | kGeoStream | kGeoNtLoads; }
-            else if (best) { autosel.valid = true; autosel.G = best; autosel.nt = 512; autosel.batch = 1; autosel.flags = kGeoUnrolledFir | kGeoPipe3; }
+    const std::vector<Candidate> cands = hinted ? std::vector<Candidate>{chain_build(p, hint, true)} : chain_candidates(p, T_lds);
+    const Candidate *won = nullptr;
+    std::string why;
+    for (const Candidate &c : cands) {
+        hipFunction_t fn = nullptr;
+        if (c.src == Candidate::kBuild && !(fn = jit_chain_kernel(c.key, &why, may_compile, &p->taps_h))) {
+            if (c.required) return fail(QD_ERR_UNSUPPORTED, "tile_hint build failed: %s", why.c_str());
+            continue;
         }
+        const int rc = commit_candidate(p, c, fn, T_lds);
+        if (rc) return rc;
+        won = &c;
+        break;
     }
-    if (jit_ok && !tuned && !p->fixed && p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && p->S >= p->W) {
-        const uint32_t W = p->W, S = p->S, D = p->D, T = p->T, c_half = T - T / 2;
-        const int spl = spl_of(d.format);
-        auto rows_aligned = [&](uint32_t nt, uint32_t g) {            // fast phase 1: tiles start on a row boundary, <= 10 rows, whole-tile prefetch
-            const uint64_t ROW = (uint64_t)nt * spl, tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
-            return ((uint64_t)S * D) % ROW == 0 && (tile_raw + ROW - 1) / ROW <= 10 && D % spl == 0;
-        };
-        const bool pk_geo = T >= 64 && T % 4 == 0 && D % 4 == 0 && is_pow2(D) && c_half % 2 == 0 && (c_half % D) % 2 == 0;
-        const bool tile2_geo = pk_geo && (T / 2) % 4 == 0 && c_half % 4 == 0 && D / 4 <= 8 && T > D + 16 && W % 2 == 0;
-        if (tile2_geo && W >= 512 && (uint64_t)T >= 4ull * D) {
-            // one long window per tile (cfg4's recipe): two outputs per lane as straight-line packed code with in-chain
-            // snapshots, the previous window's FFT + epilogue on idle waves, as many threads as the FIR has lanes for
-            // half-window tiles (two passes per window, two workgroups per CU) where a pass is a whole number of rows of 512 threads
-            const uint64_t half_raw = (uint64_t)c_half + (uint64_t)(W / 2 - 1) * D + T, ROW512 = 512ull * spl;
-            const bool half_ok = W >= 1024 && W % 4 == 0 && ((uint64_t)(W / 2) * D) % ROW512 == 0 && ((uint64_t)S * D) % ROW512 == 0 &&
-                                 (half_raw + ROW512 - 1) / ROW512 <= 10 && D % spl == 0;
-            const int nt = half_ok ? 512 : (W >= 1024 ? 1024 : 512);
-            const uint32_t fl = kGeoPackedTile | kGeoDeferFft | (half_ok ? (kGeoHalfTile | kGeoFastP1 | kGeoNtLoads) : (rows_aligned(nt, 1) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u));
-            if (lds_for(1, W, S, D, T_lds, nullptr, 2, 2, lut8, fl) <= kLdsMax) {
-                autosel.valid = true; autosel.G = 1; autosel.nt = nt; autosel.batch = 2; autosel.flags = fl; autosel.firr = 2; autosel.firb = 4;
-            }
-        } else if (pk_geo && W <= 256) {
-            // 64..256 outputs per tile of 256 threads (cfg3' recipe): packed lane-per-output FIR on a 16-byte-row tile; where the
-            // FIR leaves a wave idle, the previous tile's FFT + epilogue runs there
-            const uint32_t g = W >= 128 ? 1u : 128u / W;
-            const bool defer = (g * W) % 64 == 0 && g * W + 64 <= 256;
-            const uint32_t fl = kGeoNoSplit | (defer ? kGeoDeferFft : 0u) | (rows_aligned(256, g) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u);
-            const uint32_t bt = defer ? 2u : 1u;
-            if (p->n_windows >= g && lds_for(g, W, S, D, T_lds, nullptr, 2, bt, lut8, fl) <= kLdsMax / 2) {      // at least two workgroups per CU
-                autosel.valid = true; autosel.G = g; autosel.nt = 256; autosel.batch = bt; autosel.flags = fl;
-            }
-        }
-    }
-    if (jit_ok && write_sink && !tuned && p->has_fir) {
-        // The `write` sink (N1: shift -> lowpass -> decimated cf32 in read_at blocks): the streaming kernel with producers and FIR waves
-        // only — a step is one sub-block of W = min(block, 256) outputs on as many FIR lanes, which store their outputs themselves;
-        // truncation is relative to the block (ChainParams::blk_len).  The conditions restate Pipe3S<>::ok for side-by-side windows.
-        const uint32_t W = p->W, D = p->D, T = p->T, c_half = T - T / 2;
-        const int spl = spl_of(d.format);
-        const bool pk_geo = T % 4 == 0 && (T / 2) % 4 == 0 && T / 4 > 3 && D % 4 == 0 && (c_half % D) % 2 == 0 && D % spl == 0 && is_pow2(W) && W <= 256 &&
-                            p->blk_len % W == 0 && is_pow2(p->blk_subs);
-        for (int snt : {512, 256}) {
-            if (!pk_geo || autosel.valid) break;
-            const uint64_t SROW = (uint64_t)snt * spl, n_new = (uint64_t)W * D;
-            if (n_new % SROW != 0 || SROW % D != 0 || n_new < (uint64_t)c_half + T || n_new / SROW > 10) continue;
-            const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
-            if (f0 > W || mird * D > SROW) continue;
-            const uint32_t fl = kGeoNoSplit | kGeoNtLoads | kGeoPipe3 | kGeoStream | kGeoWriteSink;
-            if (lds_for(1, W, W, D, T, nullptr, 2, 1, lut8, fl, nullptr, spl, snt) > kLdsMax ||        // the kernel's own layout (its T, no tile_extra) ...
-                lds_for(1, W, W, D, T_lds, nullptr, 1, 1, lut8) > kLdsMax) continue;                        // ... and the generic kernels' tile for an unaligned tail
-            autosel.valid = true; autosel.G = 1; autosel.nt = snt; autosel.batch = 1; autosel.flags = fl;
-        }
-    }
-    if (fast_mode) {
-        if (autosel.valid) autosel.flags |= kGeoFastFma;
-        else p->fixed = fixed_exact;                                   // nothing to fuse in: the exact built-in kernel, if any
-    }
-    // the long-filter policy serves overlapping windows (shared FIR) and whatever the packed variants above do not take
-    bool heavy = jit_ok && !write_sink && !tuned && !p->fixed && p->has_fir && (uint64_t)p->T >= 8ull * p->D && !autosel.valid;
-    int jit_lb = 4, jit_noslp = 0;
-    uint32_t pad = 1;              // LDS pad elements per row the main kernel is built with (FixedGeo PAD_)
-    if (heavy) {
-        auto outs = [&](uint32_t g) { return p->S < p->W ? (uint64_t)(g - 1) * p->S + p->W : (uint64_t)g * p->W; };
-        uint32_t gh = 1;           // 16-byte aligned LDS rows (pad 2): ds_read_b128 sample pairs in the tap loop (FixedGeo::kPad)
-        while (gh < 64 && outs(gh + 1) <= 512 && lds_for(gh + 1, p->W, p->S, p->D, T_lds, nullptr, 2, 1, lut8) <= kLdsMax) ++gh;
-        if (p->n_windows && gh > p->n_windows) gh = (uint32_t)p->n_windows;
-        p->jit_fn = jit_chain_kernel(make_key(gh, 512, 2, 1, 2), &p->jit_note, may_compile);
-        heavy = p->jit_fn != nullptr;                  // else: the default tiling below, on whatever kernel is available
-        if (heavy) { G = gh; pad = 2; p->nt = 512; jit_lb = 2; jit_noslp = 1; }
-    }
-    if (heavy) {
-    } else if (tuned) {
-        G = tune[0];
-        p->nt = (int)tune[1];
-        jit_lb = (int)tune[4];
-        pad = tune[5];
-        batch = tune[6];
-        kflags = hint_flags;
-    } else if (p->fixed) {
-        G = p->fixed->G;
-        p->nt = p->fixed->nt;
-        pad = (uint32_t)p->fixed->pad;
-        batch = (uint32_t)p->fixed->batch;
-        kflags = (uint32_t)p->fixed->flags;
-    } else if (p->spark) {
-        p->spark_ts = spark_tile(p->W, p->nco);
-        G = p->spark_ts / p->W;                // windows per wave tile (the kernel derives the same number from its tile size)
-        p->nt = (int)(kSparkRow / spl_of(d.format));      // NCO rows of 512 samples: row table and lane table are laid out for that
-        kflags = kGeoSpark;
-        p->spark_lb = spark_lb(p->spark_ts, p->nco);
-        if (jit_ok && (p->W == 128 || p->W == 256 || p->W == 512 || p->W == 1024)) {
-            // width 16 or 64 columns: the plan-time kernel that runs the base butterflies out of the row registers (k_spark2);
-            // tile = 64 lanes x 2 columns x base rows.  Cached builds always, a new one for streams of 1 GiB and more.
-            // (the kernel's own geometry is windows side by side: S = W also where the plan's windows overlap, see spark_R)
-            const uint32_t fbase = (ilog2(p->W) & 1) ? 8u : 16u, ts2 = 128u * fbase, g2 = ts2 / p->W;
-            const int lb2 = p->has_shift ? (fbase == 8 ? 3 : 2) : (fbase == 8 ? 4 : 3);
-            // (overlapping windows, spark_R: this kernel takes them in ONE launch — every window's rows are loaded for it, the overlap is
-            // served by the caches —, so the stride goes into the build and the interleaved launches are off)
-            // (... without a shift; with one the NCO rows are laid out for whole tiles of side-by-side windows: the S = W build, interleaved)
-            const bool ov_shift = p->spark_ov && p->has_shift;
-            JitKey k{d.format, p->nco, 0, 0, 1, lb2, kThreads, p->W, ov_shift ? p->W : p->S, 1, 0, g2, 8, 1, 0, 1, 1, kGeoSpark | kGeoSparkReg, 0ull, d.epilogue};
-            if ((!ov_shift || d.epilogue == QD_EPI_NORMS_F32 || d.epilogue == QD_EPI_GLYPH_U8) && (p->jit_fn = jit_chain_kernel(k, &p->jit_note, may_compile)) != nullptr) {
-                p->spark_ts = ts2; G = g2; kflags |= kGeoSparkReg; p->spark_lb = lb2;
-                if (!ov_shift) p->spark_R = 0;
-            }
-        }
-        if (p->spark_ov && !p->has_shift && !p->jit_fn && jit_ok && p->W >= 2 && p->W <= 8 && ((uint64_t)p->W * bps_of(d.format)) % 4 == 0) {
-            JitKey k{d.format, 0, 0, 0, 1, 4, kThreads, p->W, p->S, 1, 0, 64, 8, 1, 0, 1, 1, kGeoSpark | kGeoSparkDirect, 0ull, d.epilogue};
-            if (hipFunction_t f = jit_chain_kernel(k, &p->jit_note, may_compile)) {
-                p->jit_fn = f; G = 64; kflags |= kGeoSparkDirect; p->spark_lb = 4; p->spark_R = 0;
-            }
-        }
-        if (p->spark_ov && !p->jit_fn) {
-            // interleaved launches need a plan-time build (k_spark with the sink as a template argument); none to be had: back to k_chain
-            const int lbj = 4;
-            JitKey k{d.format, p->nco, 0, (int)(p->spark_ts / (64u * (uint32_t)spl_of(d.format))), 1, lbj, kThreads,
-                     p->W, p->W, 1, 0, G, 8, 1, 0, 1, 1, kGeoSpark, 0ull, d.epilogue};
-            p->jit_fn = jit_ok && p->spark_R > 1 ? jit_chain_kernel(k, &p->jit_note, may_compile) : nullptr;
-            if (p->jit_fn) { p->spark_lb = lbj; p->spark_jt_lds = p->has_shift; }
-            else {
-                p->spark = false; p->spark_ov = false; p->spark_R = 0; p->spark_ts = 0; kflags = 0; p->nt = kThreads; G = 1;
-                while (G < 64 && (uint64_t)G * p->W < 256 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 40 * 1024) G *= 2;
-                while (G < 64 && (uint64_t)G * p->W < 1024 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 36 * 1024) G *= 2;
-                if (p->n_windows && G > p->n_windows) { while (G > 1 && G / 2 >= p->n_windows) G /= 2; }
-            }
-        }
-    } else {
-        while (G < 64 && (uint64_t)G * p->W < 256 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 40 * 1024) G *= 2;
-        while (G < 64 && (uint64_t)G * p->W < 1024 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 36 * 1024) G *= 2;
-        // chains without a lowpass (every sample is an FFT input), windows of 128 points and more: 2048 samples per tile while four
-        // workgroups still share a CU — fewer barriers per sample (16 GiB cf32, profiles/r03/nofir_rate.log: W = 128 7.16 -> 6.74 ms,
-        // W = 256 10.50 -> 9.57, cs16 W = 512 10.18 -> 9.07; 4096 samples per tile: 9.04 at W = 128; W = 64 loses with 32 windows: 8.23 -> 9.65)
-        if (!p->has_fir && p->S >= p->W && p->W >= 128) while (G < 64 && (uint64_t)G * p->W < 2048 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 40 * 1024) G *= 2;
-        if (p->n_windows && G > p->n_windows) { while (G > 1 && G / 2 >= p->n_windows) G /= 2; }
-        if (autosel.valid) {
-            G = autosel.G; p->nt = autosel.nt; jit_lb = 4; pad = 2; batch = autosel.batch; kflags = autosel.flags; tune[2] = autosel.firr; tune[3] = autosel.firb;
-            auto_variant = true;
-        }
-    }
-    p->geo.G = G;
-    p->kflags = kflags;
-    p->launch_nt = p->nt + ((kflags & kGeoPipe3) ? ((kflags & kGeoWriteSink) ? 256 : 512) : ((kflags & kGeoPipe) ? ((kflags & kGeoPipeFftWave) ? 128 : 64) : 0));
-    if (p->spark) p->launch_nt = kThreads;         // four waves per workgroup whatever the row geometry (p->nt = 512 / SPL only lays out the NCO tables)
-    p->geo.lds_bytes = lds_for(G, p->W, p->S, p->D, (kflags & kGeoWriteSink) ? p->T : T_lds, &raw_elems, pad, batch, lut8, kflags, &p->geo.lds_main, spl_of(d.format), p->nt);     // the generic kernels (pad 1, batch 1) fit inside the same allocation
-    if (kflags & kGeoWriteSink) {      // the streaming write kernel is laid out for T; the generic kernels' tile (an unaligned tail) for T + tile_extra
-        uint32_t re_gen = 0;
-        const size_t gen_b = lds_for(G, p->W, p->S, p->D, T_lds, &re_gen, 1, 1, lut8);
-        if (gen_b > p->geo.lds_bytes) p->geo.lds_bytes = gen_b;
-        raw_elems = re_gen;
-    }
-    if (!(kflags & (kGeoHalfTile | kGeoPipe3))) p->geo.lds_main = p->geo.lds_bytes;
-    if (p->spark) p->geo.lds_main = ((size_t)(p->W < 32 ? 32 : p->W) + 4 * (size_t)p->spark_ts) * 8 +     // twiddles | four waves' transform buffers (k_spark)
-                                    ((((kflags & kGeoSparkReg) && p->has_shift) || p->spark_jt_lds) ? (size_t)kSparkRow * 16 : 0);   // plan-time builds with a shift: + the NCO lane table
-    if (kflags & kGeoSparkDirect) p->geo.lds_main = 16;                 // k_spark0 uses no LDS (a token size: 0 means "the generic layout's")
-    p->geo.lds_raw_elems = raw_elems;
-    p->geo.Dp = p->D + ((p->D % 2 == 0) ? 1 : 0);
-    if ((uint64_t)raw_elems * p->D >= (1ull << 32)) return fail(QD_ERR_UNSUPPORTED, "tile too large");
+    if (!won) return fail(QD_ERR_UNSUPPORTED, "no kernel for this chain");      // (every list ends in a kernel that is always to be had)
 
-    p->fn = p->fixed ? p->fixed->fn : (p->spark ? pick_spark(d.format, p->nco, p->spark_ts) : pick_generic(d.format, p->nco, p->has_fir, true));
-    p->fn_unaligned = pick_generic(d.format, p->nco, p->has_fir, false);
-    if (!p->fn || !p->fn_unaligned) return fail(QD_ERR_UNSUPPORTED, "no kernel built for this format (QD_DEV_FAST build?)");
-    {
-        // plan-time specialisation for shapes without a built-in FixedGeo kernel
-        if (p->spark && jit_ok && !p->jit_fn) {
-            // the same kernel with the width as a compile-time constant (butterfly loops unroll, one base butterfly instead of five,
-            // index arithmetic folds): cached builds always, a new one for streams of 1 GiB and more.  Falls back to the built-in
-            // runtime-width kernel — same tiling, same bytes.
-            // (with the width a constant one base butterfly is compiled instead of five, and with a shift the lane constants come out of an LDS
-            // copy of the lane table: 82-112 VGPRs, four waves per SIMD at either tile size)
-            const int lbj = 4;
-            JitKey k{d.format, p->nco, 0, (int)(p->spark_ts / (64u * (uint32_t)spl_of(d.format))), 1, lbj, kThreads,
-                     p->W, p->W, 1, 0, G, 8, 1, 0, 1, 1, kGeoSpark, 0ull, d.epilogue};
-            p->jit_fn = jit_chain_kernel(k, &p->jit_note, may_compile);
-            if (p->jit_fn) {
-                p->spark_lb = lbj; p->spark_jt_lds = p->has_shift;
-                if (p->spark_jt_lds) p->geo.lds_main += (size_t)kSparkRow * 16;       // (lds_main was sized above for the built-in kernel)
-            }
-        }
-        const bool want = !heavy && !p->spark && (tuned || (!p->fixed && jit_ok && (!write_sink || auto_variant)));
-        if (want) {
-            p->jit_fn = jit_chain_kernel(make_key(G, p->nt, jit_lb, jit_noslp, pad, batch, kflags), &p->jit_note, may_compile, &p->taps_h);
-            if (tuned && !p->jit_fn) return fail(QD_ERR_UNSUPPORTED, "tile_hint build failed: %s", p->jit_note.c_str());
-            if (!p->jit_fn && auto_variant && fast_mode && fixed_exact) {
-                // QD_MODE_FAST had set the exact built-in kernel aside for a fused build that is not to be had: back to the built-in
-                // (exact) kernel with ITS tiling, not down to the generic kernels
-                p->fixed = fixed_exact;
-                G = p->fixed->G; p->nt = p->fixed->nt; pad = (uint32_t)p->fixed->pad; batch = (uint32_t)p->fixed->batch; kflags = (uint32_t)p->fixed->flags;
-                auto_variant = false;
-                uint32_t re2 = 0;
-                p->geo.G = G; p->kflags = kflags;
-                p->launch_nt = p->nt + ((kflags & kGeoPipe3) ? ((kflags & kGeoWriteSink) ? 256 : 512) : ((kflags & kGeoPipe) ? ((kflags & kGeoPipeFftWave) ? 128 : 64) : 0));
-                p->geo.lds_bytes = lds_for(G, p->W, p->S, p->D, T_lds, &re2, pad, batch, lut8, kflags, &p->geo.lds_main, spl_of(d.format), p->nt);
-                if (!(kflags & (kGeoHalfTile | kGeoPipe3))) p->geo.lds_main = p->geo.lds_bytes;
-                p->geo.lds_raw_elems = re2;
-                p->fn = p->fixed->fn;
-            } else
-            if (!p->jit_fn && auto_variant) {
-                // no variant build (not cached and too small a stream to compile for, or the build failed): the plain tiling —
-                // which the generic kernels run in as well
-                G = 1; uint32_t re2 = 0;
-                while (G < 64 && (uint64_t)G * p->W < 256 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 40 * 1024) G *= 2;
-                while (G < 64 && (uint64_t)G * p->W < 1024 && lds_for(G * 2, p->W, p->S, p->D, T_lds, nullptr, 1, 1, lut8) <= 36 * 1024) G *= 2;
-                if (p->n_windows && G > p->n_windows) { while (G > 1 && G / 2 >= p->n_windows) G /= 2; }
-                p->nt = kThreads; jit_lb = 4; pad = 1; batch = 1; kflags = 0; tune[2] = 1; tune[3] = 8; auto_variant = false;
-                p->geo.G = G; p->kflags = 0; p->launch_nt = kThreads;
-                p->geo.lds_bytes = lds_for(G, p->W, p->S, p->D, T_lds, &re2, 1, 1, lut8, 0);
-                p->geo.lds_main = p->geo.lds_bytes;
-                p->geo.lds_raw_elems = re2;
-                if (!write_sink) p->jit_fn = jit_chain_kernel(make_key(G, p->nt, jit_lb, 0, 1, 1, 0), &p->jit_note, may_compile, &p->taps_h);      // (the write sink's only other kernel is the generic one)
-            }
-        }
-        // A built-in straight-line FIR kernel (scalar chains of overlapping-window shapes) re-specialised with the plan's OWN filter
-        // baked in (taps as immediates: no LDS reads, no registers for them; cfg3 27.8 -> 24.6 ms): worth a compile only for
-        // streams of several GiB, falls back silently.  The packed lane-per-output FIR does not need it: it multiplies by the
-        // taps straight out of the register pairs an LDS read delivers (fir_pair), which measures the same as immediates.
-        if (!want && !heavy && !tuned && p->fixed && jit_ok && (p->fixed->flags & kGeoUnrolledFir) && !(p->fixed->flags & kGeoPipe3) &&
-            (policy == QD_KERNEL_SPECIALISE || in_bytes >= (4ull << 30))) {
-            JitKey k = make_key(G, p->nt, p->fixed->lb, 0, pad, batch, kflags | kGeoBakedTaps);
-            // the table's prefetch shape and FIR knobs, not the heuristic ones (e.g. the 4-row chunks of the cf32 FSK kernel)
-            k.rch = p->fixed->rch; k.whole = p->fixed->whole; k.firb = (uint32_t)p->fixed->firb; k.firr = (uint32_t)p->fixed->firr;
-            k.noslp = (p->fixed->flags & kGeoUnrolledFir) ? 1 : 0;
-            p->jit_fn = jit_chain_kernel(k, &p->jit_note, true, &p->taps_h);
-        }
-    }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->n_cu = prop.multiProcessorCount;
-    int by_lds = (int)(kLdsMax / (p->geo.lds_main ? p->geo.lds_main : p->geo.lds_bytes));
-    p->wg_per_cu = by_lds < 1 ? 1 : (by_lds > 4 ? 4 : by_lds);
-    if (p->fixed) { int by_regs = p->fixed->lb * 256 / p->fixed->nt; if (by_regs < 1) by_regs = 1; if (p->wg_per_cu > by_regs) p->wg_per_cu = by_regs; }
-    if (p->spark) { const int by_regs = p->spark_lb; if (p->wg_per_cu > by_regs) p->wg_per_cu = by_regs; }
-    if (!p->fixed && !p->jit_fn && !p->spark) { const int by_regs = dyn_lb(p->nco); if (p->wg_per_cu > by_regs) p->wg_per_cu = by_regs; }      // the generic kernels' own budget
-    if (p->launch_nt > kThreads) { int by_threads = 2048 / p->launch_nt; if (p->wg_per_cu > by_threads) p->wg_per_cu = by_threads; }
-    if (tuned || heavy || auto_variant) { int by_regs = (jit_lb * 4 * 64) / p->launch_nt; if (by_regs < 1) by_regs = 1; if (p->wg_per_cu > by_regs) p->wg_per_cu = by_regs; }
-    if (tuned && tune[7] && (int)tune[7] < p->wg_per_cu) p->wg_per_cu = (int)tune[7];
+    // workgroups per CU: what LDS, the CU's 2048 threads and the kernel's register budget admit, at most 4
+    const int by_lds = (int)(kLdsMax / (p->geo.lds_main ? p->geo.lds_main : p->geo.lds_bytes));
+    p->wg_per_cu = std::min(4, std::max(1, by_lds));
+    if (won->wg_regs) p->wg_per_cu = std::min(p->wg_per_cu, won->wg_regs);
+    if (p->launch_nt > kThreads) p->wg_per_cu = std::min(p->wg_per_cu, 2048 / p->launch_nt);
+    if (hinted && h[7] && (int)h[7] < p->wg_per_cu) p->wg_per_cu = (int)h[7];
     if (const char *e = dev_env("QD_WG_PER_CU")) { int v = atoi(e); if (v >= 1 && v <= 8) p->wg_per_cu = v; }      // development builds
     // Dynamic-LDS limit: the kernels are process-global objects shared by every plan, so the attribute is set to the
     // hardware maximum (160 KiB), never to one plan's tile — a later plan with a smaller tile must not lower the limit
