@@ -1636,6 +1636,10 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             uint64_t tile_pf = tile_n < n_tiles ? tile_n : tile;                   // last tile of this workgroup: harmless re-loads
             if (kHalf && half == 0) tile_pf = tile;                                // the next pass is this window's second half
             const uint64_t ns_n = (P.first_window + tile_pf * GeoT::G) * ((uint64_t)GeoT::S * GeoT::D) + ((kHalf && half == 0) ? kHalfStep : 0u);
+            // No underflow: tile_pf < n_tiles, so ns_n is the first sample of a window of THIS launch (or, on a half pass, kHalfStep =
+            // kHalfOut D < W D + T samples into it), and launch_chain refuses a slab that does not cover [first_window S D,
+            // (first_window + n_windows - 1) S D + W D + T) before anything is launched: src_first <= ns_n < src_first + src_count.
+            // (k_chain_pipe3s addresses the rows of a run, not tiles, and guards the same subtraction with ns < end.)
             const uint64_t left = (P.src_first + P.src_count - ns_n) * FT::BPS;
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(P.src) + (ns_n - P.src_first) * FT::BPS, 0,
                                                                 left > 0xffffffffull ? 0xffffffffu : (uint32_t)left, 0x00020000);
@@ -2323,6 +2327,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain_pipe(const ChainParams P) {
     auto n_start_of = [&](uint64_t t) -> uint64_t { return (P.first_window + t) * ((uint64_t)GeoT::S * D); };
     auto rsrc_of = [&](uint64_t t) {
         const uint64_t ns = n_start_of(t);
+        // t < n_tiles: ns is a window start of this launch, inside the slab launch_chain checked (see k_chain's row-aligned phase 1)
         const uint64_t left = (P.src_first + P.src_count - ns) * FT::BPS;
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(P.src) + (ns - P.src_first) * FT::BPS, 0,
                                                  left > 0xffffffffull ? 0xffffffffu : (uint32_t)left, 0x00020000);
@@ -2622,6 +2627,7 @@ __global__ __launch_bounds__(kPipe3Threads, LB) void k_chain_pipe3(const ChainPa
         auto n_start_of = [&](uint64_t t) -> uint64_t { return (P.first_window + t * G) * ((uint64_t)S * D); };
         auto rsrc_of = [&](uint64_t t) {
             const uint64_t ns = n_start_of(t);
+            // t < n_tiles: ns is a window start of this launch, inside the slab launch_chain checked (see k_chain's row-aligned phase 1)
             const uint64_t left = (P.src_first + P.src_count - ns) * FT::BPS;
             return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(P.src) + (ns - P.src_first) * FT::BPS, 0,
                                                      left > 0xffffffffull ? 0xffffffffu : (uint32_t)left, 0x00020000);

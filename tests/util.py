@@ -779,3 +779,206 @@ def nco_sensitive_samples(ratio, n0, count, chunk=1 << 22, eps=NCO_ABS_ERR):
                 out.append(k)
                 break
     return np.array(out, dtype=np.int64)
+
+
+# ------------------------------------------------------------------ footprints: which memory a run reads and writes
+#
+# A run of windows [w0, w0 + n) may read source samples src_range(w0, n) and nothing else, and write n * out_bytes_per_window
+# bytes and nothing else (include/quadrs_hip.h).  The source slab and the output are laid INSIDE one allocation each, between
+# frames the test owns:  [front frame | slab | back frame]  and  [guard | payload | guard].  Source frames hold a poison
+# pattern, and every case runs twice, once per pattern: cf32 frames are 0x7FC00000 words (a quiet NaN, which survives a
+# multiplication by a zero tap) and then 0x7F7FFFFF words (the largest finite f32).  The integer formats have no NaN: their
+# frames are 0x80 bytes and then 0x7F bytes, and an influence of the frames shows ONLY as a difference between the two runs.
+# Output guards and the payload itself are pre-filled with 0xA5, so a window that was never written does not look like zeros.
+# Reads whose values are discarded cannot be seen by this method.
+
+POISON_WORDS = (0x7FC00000, 0x7F7FFFFF)        # cf32 frames
+POISON_BYTES = (0x80, 0x7F)                    # cs8 / cu8 / cs16 frames
+GUARD_BYTE = 0xA5
+FMT_BYTES = {0: 8, 1: 2, 2: 2, 3: 4}
+
+
+def poison(fmt, nbytes, which):
+    """nbytes (a multiple of 4) of source poison pattern `which` (0 / 1) for sample format fmt, as a uint8 array"""
+    assert nbytes % 4 == 0
+    if fmt == 0:
+        return np.full(nbytes // 4, POISON_WORDS[which], dtype="<u4").view(np.uint8)
+    return np.full(nbytes, POISON_BYTES[which], dtype=np.uint8)
+
+
+def _round_up(x, q):
+    return (int(x) + q - 1) // q * q
+
+
+def src_frame_bytes(info, fmt):
+    """the least size of a source frame: max(1 MiB, 4 x the plan's source span of one tile), kept a multiple of 4 KiB so that
+    the slab keeps the allocation's alignment.  A condition, not a measurement."""
+    tile_span = (max(int(info.tile_windows), 1) - 1) * int(info.raw_step) + int(info.raw_per_window)
+    return _round_up(max(1 << 20, 4 * tile_span * FMT_BYTES[fmt]), 4096)
+
+
+def out_guard_bytes(info):
+    """the least size of an output guard: max(64 KiB, 4 tiles of output), a multiple of 4 KiB"""
+    return _round_up(max(64 << 10, 4 * max(int(info.tile_windows), 1) * int(info.out_bytes_per_window)), 4096)
+
+
+class Framed:
+    """[front | body | back] in ONE allocation of device ("device": a torch uint8 tensor), pageable host ("host": numpy) or
+    pinned host ("pinned": a PinnedBuffer of `engine`) memory.  `body` is what a run is handed (a view that starts at the body's
+    first byte); `uploaded` the bytes the buffer was created with; snapshot() its bytes now."""
+
+    def __init__(self, kind, front, body, back, engine=None):
+        parts = [np.ascontiguousarray(p).view(np.uint8).reshape(-1) for p in (front, body, back)]
+        self.kind = kind
+        self.lo = parts[0].size
+        self.hi = self.lo + parts[1].size
+        self.uploaded = np.concatenate(parts)
+        if kind == "device":
+            import torch
+            self._buf = torch.from_numpy(self.uploaded.copy()).cuda()
+        elif kind == "pinned":
+            self._pin = engine.PinnedBuffer(self.uploaded.size)
+            self._buf = self._pin.array
+            self._buf[:] = self.uploaded
+        else:
+            assert kind == "host", kind
+            self._buf = self.uploaded.copy()
+        self.body = self._buf[self.lo:self.hi]
+
+    def snapshot(self):
+        if self.kind == "device":
+            import torch
+            torch.cuda.synchronize()
+            return self._buf.cpu().numpy()
+        return np.array(self._buf, copy=True)
+
+    def close(self):
+        self.body = self._buf = None
+        if self.kind == "pinned":
+            self._pin.close()
+
+
+def framed(kind, fmt, which, front_bytes, slab, back_bytes, engine=None):
+    """a source slab (bytes / uint8 array) between frames of poison pattern `which`"""
+    slab = np.frombuffer(slab, dtype=np.uint8) if not isinstance(slab, np.ndarray) else slab
+    return Framed(kind, poison(fmt, front_bytes, which), slab, poison(fmt, back_bytes, which), engine)
+
+
+def framed_out(kind, guard_bytes, payload_bytes, engine=None):
+    """an output of payload_bytes between two guards, all three filled with GUARD_BYTE"""
+    g = np.full(guard_bytes, GUARD_BYTE, dtype=np.uint8)
+    return Framed(kind, g, np.full(payload_bytes, GUARD_BYTE, dtype=np.uint8), g, engine)
+
+
+class FootprintRun:
+    """what one framed run left behind: the output buffer's bytes (guards and payload) and, where the source lives in memory a
+    kernel could write (device, pinned), the source buffer's bytes against what was uploaded"""
+
+    def __init__(self, out, src=None):
+        snap = out.snapshot()
+        self.front, self.payload, self.back = snap[:out.lo], snap[out.lo:out.hi], snap[out.hi:]
+        self.src_uploaded = self.src_now = None
+        if src is not None and src.kind != "host":
+            self.src_uploaded, self.src_now = src.uploaded, src.snapshot()
+
+
+def footprint_violations(runs, ref, rule=None, unit=4):
+    """The footprint checker.  runs: the FootprintRun of each poison pattern (two), same windows, same true slab.  ref: the
+    ORACLE's payload for those windows on the true stream (an array whose bytes are laid out like the payload).  rule(got
+    payload bytes) -> a list of complaints holds the payload to the chain's rule against the oracle; None means bit for bit.
+    unit: bytes per output element (4: f32 words, 1: glyph cells / bucket digits).  Returns the violated conditions:
+      1. "poison": the two patterns' payloads differ (memory outside the slab reached an output byte);
+      2. "oracle": the payload breaks the rule;
+      3. "unwritten": an output element still holds the pre-fill where the oracle's value is something else;
+      4. "guard": a byte of an output guard changed;
+      5. "source": a byte of the source buffer (frames or slab) changed."""
+    bad = []
+    ref_b = np.ascontiguousarray(ref).view(np.uint8).reshape(-1)
+    if len(runs) != len(POISON_WORDS):
+        bad.append(f"poison: {len(runs)} runs, one per pattern is {len(POISON_WORDS)}")
+    for r in runs[1:]:
+        if r.payload.size != runs[0].payload.size or not np.array_equal(r.payload, runs[0].payload):
+            d = np.flatnonzero(r.payload != runs[0].payload) if r.payload.size == runs[0].payload.size else []
+            bad.append(f"poison: payloads of the two fills differ in {len(d)} bytes, first at byte {int(d[0]) if len(d) else -1}")
+    for k, r in enumerate(runs):
+        if r.payload.size != ref_b.size:
+            bad.append(f"oracle: fill {k}: payload of {r.payload.size} bytes, the oracle's has {ref_b.size}")
+            continue
+        if rule is None:
+            d = np.flatnonzero(r.payload != ref_b)
+            if d.size:
+                bad.append(f"oracle: fill {k}: {d.size} bytes differ from the oracle, first at byte {int(d[0])}")
+        else:
+            bad += [f"oracle: fill {k}: {c}" for c in rule(r.payload)]
+        fill = np.uint8(GUARD_BYTE) if unit == 1 else np.uint32(0x01010101 * GUARD_BYTE)
+        dt = np.uint8 if unit == 1 else np.uint32
+        stale = np.flatnonzero((r.payload.view(dt) == fill) & (ref_b.view(dt) != fill))
+        if stale.size:
+            bad.append(f"unwritten: fill {k}: {stale.size} output elements still hold the pre-fill, first element {int(stale[0])}")
+        for name, g in (("front", r.front), ("back", r.back)):
+            d = np.flatnonzero(g != GUARD_BYTE)
+            if d.size:
+                where = int(d[0]) if name == "back" else int(d[-1]) - g.size
+                bad.append(f"guard: fill {k}: {d.size} bytes of the {name} guard were written, nearest at {where:+d} bytes from the payload")
+        if r.src_now is not None and not np.array_equal(r.src_now, r.src_uploaded):
+            d = np.flatnonzero(r.src_now != r.src_uploaded)
+            bad.append(f"source: fill {k}: {d.size} bytes of the source buffer changed, first at byte {int(d[0])}")
+    return bad
+
+
+def footprint_reference(oracle_chain, stages, sr, W, S, epi, rng, n_total):
+    """The oracle's outputs of windows [0, n_total) of a chain on the TRUE stream and the rule a run of any sub-range is held to:
+    returns expect(w0, n) -> (ref, rule, unit) for footprint_violations.  Norms (epi 0) and write blocks (3) are bit for bit
+    without a shift stage and obey the NCO rule (explain_check) within 1 ulp of the window maximum / the sample's magnitude
+    with one; glyph cells (1) obey codes_edge_ok, bucket digits (2) bucket_digits_ok, both also the NCO rule behind a shift."""
+    shifted = any(k == "shift" and a != 0 for k, a in stages)
+    desc = (list(stages), W, S, sr)
+    if epi == 3:
+        rows = []
+        for b in range(n_total):
+            got, blk = oracle_chain.read_at(b * W, W)
+            assert got == W, (b, got)
+            rows.append(blk.reshape(-1))
+        ref_all = np.stack(rows) if rows else np.zeros((0, 2 * W), np.float32)
+        norms_all = None
+    else:
+        norms_all, codes_all = oracle_chain.spark_fft(W, S, rng=rng if epi == 1 else None, max_windows=n_total, want_codes=(epi == 1))
+        assert norms_all.shape[0] == n_total, (norms_all.shape, n_total)
+        ref_all = norms_all if epi == 0 else codes_all if epi == 1 else oracle_chain.freq_levels(W, S, max_windows=n_total).reshape(-1, 1)
+        assert ref_all.shape[0] == n_total, (ref_all.shape, n_total)
+
+    def expect(w0, n):
+        ref = np.ascontiguousarray(ref_all[w0:w0 + n])
+
+        def rule(payload):
+            got = payload.view(ref.dtype).reshape(ref.shape)
+            out = []
+            if epi == 0:
+                scale = ulp_of(np.maximum(np.abs(ref).max(axis=-1, keepdims=True), 1e-30)).astype(np.float64)
+                with np.errstate(invalid="ignore"):
+                    worst = np.abs(ref.astype(np.float64) - got.astype(np.float64)) / scale
+                if not (worst <= 1.0).all():
+                    out.append(f"norms further than 1 ulp of the window maximum (or NaN), first window {w0 + int(np.nonzero(~(worst <= 1.0))[0][0])}")
+            elif epi == 3:
+                with np.errstate(invalid="ignore"):
+                    err = complex_ulp_err(ref, got)
+                if not (err <= 1.0).all():
+                    out.append(f"block samples further than 1 ulp, first sample {w0 * W + int(np.nonzero(~(err <= 1.0))[0][0])}")
+            elif epi == 1:
+                ok, differing, near = codes_edge_ok(ref, got, norms_all[w0:w0 + n], rng[0], rng[1])
+                if not ok:
+                    out.append(f"{differing - near} glyph cells differ away from any threshold")
+            else:
+                if not bucket_digits_ok(norms_all[w0:w0 + n], got.reshape(-1)):
+                    out.append("a bucket digit differs where the half sums do not tie")
+            if shifted:
+                bad = explain_check(desc, ref, got, w0)
+                if bad:
+                    out.append(f"{len(bad)} differing windows read no ambiguous NCO multiplier, first {bad[:5]}")
+            elif epi in (0, 3) and not np.array_equal(payload, ref.view(np.uint8).reshape(-1)):
+                out.append("differs from the oracle, and the chain has no shift stage")
+            return out
+
+        exact = not shifted and epi in (0, 3)
+        return ref, (None if exact else rule), (1 if epi in (1, 2) else 4)
+    return expect
