@@ -23,6 +23,7 @@
 #pragma once
 
 #include "qd_device.h"
+#include "qd_geometry.h"
 
 namespace qd {
 
@@ -42,8 +43,6 @@ namespace qd {
 #define QD_STAMP_TILE()
 #define QD_STAMP_ROW(k)
 #endif
-
-constexpr int kThreads = 256;
 
 // Plan-time builds may bake the plan's filter into the code (FixedGeo FLAGS_ bit 1): the host puts
 // `#define QD_BAKED_TAPS_LIST 0x1.8p-7f, ...` (the designed taps, exact hex floats) in front of this header.
@@ -115,7 +114,7 @@ struct ChainParams {
     uint32_t base_len, log_base, layers;   // rustfft Radix4 plan: W = base_len * 4^layers
     uint32_t lds_raw_elems;    // float2 capacity of the raw tile
     uint32_t lds_dyn;          // dynamic LDS bytes of this launch: the kernels with a layout of their own (three-stage kernels) check it
-                               // against their compile-time need and do nothing if the host's restatement of the layout fell short
+                               // against their compile-time need and do nothing if the launch brought less
     uint32_t out_row_stride;   // wave-local kernels (plan-time builds): output rows between consecutive windows of THIS launch (0 / 1: contiguous).
                                // Overlapping windows without a lowpass run as W / S interleaved launches — launch phi takes the windows
                                // phi, phi + R, phi + 2R ... (R = W / S), which lie side by side in the stream shifted by phi * S samples
@@ -131,132 +130,80 @@ __device__ __forceinline__ uint8_t glyph_of(const ChainParams &P, float nm) {
 
 // ---------------------------------------------------------------- geometry policies
 
-constexpr uint32_t ct_log2(uint32_t v) { uint32_t l = 0; while ((1u << l) < v) ++l; return l; }
-constexpr bool ct_pow2(uint32_t v) { return v && !(v & (v - 1)); }
-constexpr uint32_t ct_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-// LDS float2 elements the raw tile needs (same formula as the host's lds_for())
-constexpr uint32_t ct_raw_elems(uint32_t W, uint32_t S, uint32_t D, uint32_t T, uint32_t G, uint32_t pad_per_row = 1) {
-    uint32_t tile_raw = (G - 1) * S * D + W * D + T;
-    uint32_t pad = (D % 2 == 0) ? pad_per_row * (tile_raw / D + 1) : 0;
-    uint32_t elems = tile_raw + pad + 1;
-    uint32_t min_elems = G * W / 2 + 1;
-    if (elems < min_elems) elems = min_elems;
-    return (elems + 1) & ~1u;
-}
-
-// planar raw tile (FixedGeo FLAGS_ bit 0): floats per plane for a tile of tile_raw samples, rows of D floats at pitch DpP
-constexpr uint32_t ct_planar_pitch(uint32_t D) { return ((D / 4) % 2 == 1) ? D : D + 4; }     // 16-byte aligned, pitch/4 odd
-constexpr uint32_t ct_plane_floats(uint32_t W, uint32_t S, uint32_t D, uint32_t T, uint32_t G) {
-    const uint32_t tile_raw = (G - 1) * S * D + W * D + T;
-    return ((tile_raw / D + 1) * ct_planar_pitch(D) + 7) & ~7u;
-}
-
-constexpr uint32_t kGeoPlanar = 1, kGeoBakedTaps = 2, kGeoNoSplit = 4, kGeoFastP1 = 8, kGeoPackedSpan = 16, kGeoUnrolledFir = 32,
-                   kGeoDeferFft = 64, kGeoPackedTile = 128, kGeoNtLoads = 256;   // FixedGeo FLAGS_ bits
-// cache policy (buffer-load aux operand) of the phase-1 stream loads: bit 8 -> nt, bits 11 / 12 -> sc0 / sc1
-constexpr uint32_t kGeoNtInner = 65536;      // FLAGS_ bit 16 (with bit 8): rows a neighbouring tile reads too (the first and the last of a row-aligned tile) keep the default policy
-constexpr uint32_t kGeoFastFma = 16384;      // FLAGS_ bit 14: QD_MODE_FAST — the packed FIRs fuse multiply and add (v_pk_fma_f32), one rounding per tap
-constexpr uint32_t kGeoHalfTile = 8192;      // FLAGS_ bit 13: the tile buffer holds HALF a window's FIR input, two passes per window (see FixedGeo::kHalfTile)
-constexpr int ct_load_aux(uint32_t flags) { return ((flags & 256u) ? 2 : 0) | ((flags & 2048u) ? 1 : 0) | ((flags & 4096u) ? 16 : 0); }
+// (the rules themselves — flag bits, derived constants, predicates, LDS layouts — are qd_geometry.h's; FixedGeo is a view of fixed_rules())
 typedef float v2f __attribute__((ext_vector_type(2)));      // operand type of the v_pk_*_f32 instructions
 
 template <uint32_t W_, uint32_t S_, uint32_t D_, uint32_t T_, uint32_t G_, uint32_t FIRB_ = 8, uint32_t FIRR_ = 1, uint32_t PAD_ = 1, uint32_t BATCH_ = 1,
           uint32_t FLAGS_ = 0>
 struct FixedGeo {
     static constexpr bool kFixed = true;
+    static constexpr FixedRules R = fixed_rules(W_, S_, D_, T_, G_, FIRB_, FIRR_, PAD_, BATCH_, FLAGS_);
     static constexpr uint32_t kFlags = FLAGS_;
     // Planar raw tile: the shifted samples are parked as two f32 planes (re / im) instead of interleaved pairs, rows of D floats
     // at a 16-byte aligned pitch DpP with DpP/4 odd.  The component-split FIR then reads FOUR taps of its component with one
     // conflict-free ds_read_b128 (256 B/clk) instead of two with a ds_read2_b32 (128 B/clk): half the LDS-array cycles and
     // half the LDS instructions of the dominant loop.
-    static constexpr uint32_t DpP = ct_planar_pitch(D_);
-    static constexpr uint32_t plane_floats = ct_plane_floats(W_, S_, D_, T_, G_);
-    static constexpr bool planar_geometry = (FLAGS_ & kGeoPlanar) && ct_pow2(D_) && D_ % 8 == 0 && T_ % 4 == 0 && ((T_ - T_ / 2) % D_) % 4 == 0 && T_ >= 64 &&
-                                            ct_pow2(G_ * W_);
+    static constexpr uint32_t DpP = R.DpP;
+    static constexpr uint32_t plane_floats = R.plane_floats;
+    static constexpr bool planar_geometry = R.planar_geometry;
     // Baked taps (plan-time builds only): the filter is a compile-time table, so every tap is an immediate operand of its
     // multiply — no LDS reads, no registers, no lgkmcnt traffic for the taps at all.
-    static constexpr bool baked_request = (FLAGS_ & kGeoBakedTaps) != 0;
+    static constexpr bool baked_request = R.baked_request;
     // FFT batching: the decimated windows of BATCH_ consecutive tiles of a workgroup are parked in LDS and transformed
     // together.  The FFT + epilogue of ONE 128-point window keeps 16-32 of 256 lanes busy between three barriers and is
     // pure latency; B windows at once cost the same latency for B times the work.
-    static constexpr uint32_t kBatch = BATCH_ ? BATCH_ : 1;
-    static constexpr uint32_t kFirBlock = FIRB_;   // taps per software-pipelined FIR block (register budget knob)
+    static constexpr uint32_t kBatch = R.kBatch;
+    static constexpr uint32_t kFirBlock = R.kFirBlock;   // taps per software-pipelined FIR block (register budget knob)
     // outputs per lane in the FIR (register tiling): each LDS sample read feeds FIRR_ accumulators.
     // Needs 8-aligned geometry; falls back to 1 otherwise.
     // The straight-line packed two-output form (fir_tiled2_pk, FLAGS_ bit 7) walks 4-sample blocks with compile-time offsets
     // and needs 4-aligned geometry only (T = 200: c = 100, T/2 = 100).
-    static constexpr bool kFirTile4 = FIRR_ == 2 && (FLAGS_ & kGeoPackedTile) && PAD_ == 2 && D_ % 4 == 0 && (T_ - T_ / 2) % 4 == 0 && T_ % 4 == 0 &&
-                                      (T_ / 2) % 4 == 0 && W_ % 2 == 0 && S_ % 2 == 0 && ct_pow2(D_) && D_ / 4 <= 8 && T_ > D_ + 16 && !(T_ > 0 && S_ < W_);
-    static constexpr uint32_t kFirTile = kFirTile4 ? 2u :
-                                         (FIRR_ > 1 && D_ % 8 == 0 && ((T_ - T_ / 2) % D_) % 8 == 0 && T_ % 8 == 0 && (T_ / 2) % 8 == 0 &&
-                                          W_ % FIRR_ == 0 && S_ % FIRR_ == 0 && ct_pow2(D_) && ct_pow2(FIRR_) &&
-                                          T_ > (FIRR_ - 1) * D_ + 8) ? FIRR_ : 1;      // at least three interior 4-sample blocks
+    static constexpr bool kFirTile4 = R.kFirTile4;
+    static constexpr uint32_t kFirTile = R.kFirTile;
     // LDS pad period: one pad element per PD samples.  PD = D for the lane-per-output FIR (lane stride D + 1:
     // odd, conflict-free ds_read_b64); the register-tiled FIR strides lanes by kFirTile rows, so it pads once
     // per kFirTile * D samples to keep the lane stride odd.
-    static constexpr uint32_t PD = D_ * kFirTile;
-    static constexpr uint32_t pshift = ct_pow2(PD) ? ct_log2(PD) : 0xffffffffu;
+    static constexpr uint32_t PD = R.PD;
+    static constexpr uint32_t pshift = R.pshift;
     __device__ __forceinline__ explicit FixedGeo(const ChainParams &) {}
     static constexpr uint32_t W = W_, S = S_, D = D_, T = T_, G = G_;
     static constexpr uint32_t G_ct = G_, W_ct = W_;
-    static constexpr uint32_t logW = ct_log2(W_);
+    static constexpr uint32_t logW = R.logW;
     // LDS pad elements per pad period.  1: odd lane stride, conflict-free single ds_read_b64 — but hipcc merges
     // neighbouring reads into ds_read2_b64, which gfx950 serves at half the bytes per clock.  2 (even D, even
     // first column): rows stay 16-byte aligned and the lane stride is 4*odd banks, so the FIR reads sample
     // PAIRS with conflict-free ds_read_b128 at the full 256 B/clk (MI355X_MICROARCH.md, LDS table).
-    static constexpr uint32_t kPad = (D_ % 2 == 0) ? ((PAD_ == 2 && (T_ - T_ / 2) % 2 == 0) ? 2u : 1u) : 0u;
-    static constexpr uint32_t Dp = D_ + kPad;
-    static constexpr uint32_t dshift = ct_pow2(D_) ? ct_log2(D_) : 0xffffffffu;
-    static constexpr uint32_t dmagic = D_ > 1 ? (uint32_t)((1ull << 32) / D_ + 1) : 0u;
-    static constexpr uint32_t c = T_ - T_ / 2;
-    static constexpr uint32_t a0 = c / D_, b0 = c % D_;
-    static constexpr uint32_t T_fast = ct_min(T_, D_ + T_ / 2);
-    static constexpr uint32_t a1 = (c + T_fast) / D_, b1 = (c + T_fast) % D_;
-    static constexpr uint32_t log_base = logW <= 3 ? logW : ((logW & 1) ? 3u : 4u);
-    static constexpr uint32_t base_len = 1u << log_base;
-    static constexpr uint32_t layers = (logW - log_base) / 2;
+    static constexpr uint32_t kPad = R.kPad;
+    static constexpr uint32_t Dp = R.Dp;
+    static constexpr uint32_t dshift = R.dshift;
+    static constexpr uint32_t dmagic = R.dmagic;
+    static constexpr uint32_t c = R.c;
+    static constexpr uint32_t a0 = R.a0, b0 = R.b0;
+    static constexpr uint32_t T_fast = R.T_fast;
+    static constexpr uint32_t a1 = R.a1, b1 = R.b1;
+    static constexpr uint32_t log_base = R.log_base;
+    static constexpr uint32_t base_len = R.base_len;
+    static constexpr uint32_t layers = R.layers;
     // Half-window tiles (FLAGS_ bit 13; one long window per tile, non-overlapping): the raw buffer holds the input of HALF the
     // window's outputs (c + (W/2 - 1) D + T samples) and a window is filtered in two passes — phase 1 + FIR of outputs [0, W/2),
     // then of [W/2, W) — into one FFT slot.  The tile is half as large, so TWO workgroups fit on a CU where one did (cfg4: 97 KiB ->
     // 62 KiB), and one workgroup's phase 1 and barriers run while the other's FIR has the vector units: the 8 k serial cycles in
     // front of every 21 k-cycle FIR of the one-workgroup form overlap.  Every output sees the same samples, taps and order.
-    static constexpr bool kHalfTile = (FLAGS_ & kGeoHalfTile) && G_ == 1 && !(T_ > 0 && S_ < W_) && W_ % 4 == 0 && T_ > 0;
-    static constexpr uint32_t kHalfOut = W_ / 2;
-    static constexpr uint32_t kHalfRaw = (T_ - T_ / 2) + (kHalfOut - 1) * D_ + T_;
-    static constexpr uint32_t ct_half_elems() {
-        const uint32_t pad = (D_ % 2 == 0) ? (kPad ? kPad : 1) * (kHalfRaw / D_ + 1) : 0;
-        uint32_t elems = kHalfRaw + pad + 1;
-        const uint32_t min_elems = G_ * W_ / 2 + 1;
-        if (elems < min_elems) elems = min_elems;
-        return (elems + 1) & ~1u;
-    }
-    static constexpr uint32_t lds_raw_elems_std = kHalfTile ? ct_half_elems() : ct_raw_elems(W_, S_, D_, T_, G_, kPad ? kPad : 1);
-    static constexpr uint32_t kNtrunc = c ? (c + D_ - 1) / D_ - 1 : 0;
-    static constexpr bool kShared = T_ > 0 && S_ < W_ && kNtrunc <= S_;     // shared-FIR mode (see phase 2)
-    // component-split FIR (fir_comp): mid-length filters whose tile leaves at least half the lanes without an output
-    static constexpr bool split_ok(uint32_t nt) {
-        return !(FLAGS_ & kGeoNoSplit) && !kShared && kFirTile == 1 && kPad != 2 && D_ % 8 == 0 && T_ >= 64 && 2u * G_ * W_ <= nt;
-    }
-    // register-tiled kernels: spare waves take the truncated tails (fir_prefix) when main lanes fill whole waves
-    static constexpr bool helper_ok(uint32_t nt) {
-        return kFirTile > 1 && !kShared && (G_ * W_ / kFirTile) % 64 == 0 && G_ * W_ / kFirTile + G_ * kNtrunc <= nt &&
-               (T_ / 2) % 8 == 0 && kNtrunc > 0 && kNtrunc < W_;
-    }
-    static constexpr bool split_ok_shared(uint32_t nt) {      // same, shared-FIR mode: (G-1)*S + W outputs per tile
-        return kShared && kFirTile == 1 && kPad != 2 && D_ % 8 == 0 && T_ >= 64 && 2u * ((G_ - 1) * S_ + W_) <= nt;
-    }
-    // the planar layout serves the component-split FIR of non-overlapping-window tiles (every 256-thread shape that asks for it)
-    // packed lane-per-output FIR (fir_pair): FLAGS_ bit 2 on a 16-byte-row tile
-    static constexpr bool kPairFir = (FLAGS_ & kGeoNoSplit) && !kShared && kFirTile == 1 && kPad == 2 && T_ % 4 == 0 && ((T_ - T_ / 2) % D_) % 2 == 0 &&
-                                     D_ % 4 == 0 && T_ >= 32;
-    static constexpr bool kUnrolledShared = (FLAGS_ & kGeoUnrolledFir) && kShared && kFirTile == 1 && kPad == 2 && T_ % 4 == 0 &&
-                                            ((T_ - T_ / 2) % D_) % 2 == 0 && D_ % 4 == 0 && T_ >= 32;
-    // register-tiled FIR as straight-line packed code with in-chain snapshots (fir_tiled2_pk): FLAGS_ bit 7, two outputs per lane
-    static constexpr bool kPackedTile = (FLAGS_ & kGeoPackedTile) && !kShared && kFirTile == 2 && kPad == 2 && (T_ / 2) % 4 == 0 && D_ / 4 <= 8;
-    static constexpr bool kPlanar = planar_geometry && split_ok(256u);
-    static constexpr bool kBakedTaps = baked_request && kPlanar;       // only the planar FIR takes its taps as immediates
-    static constexpr uint32_t lds_raw_elems = kPlanar ? plane_floats : lds_raw_elems_std;      // float2 elements
+    static constexpr bool kHalfTile = R.kHalfTile;
+    static constexpr uint32_t kHalfOut = R.kHalfOut;
+    static constexpr uint32_t kHalfRaw = R.kHalfRaw;
+    static constexpr uint32_t lds_raw_elems_std = R.lds_raw_elems_std;
+    static constexpr uint32_t kNtrunc = R.kNtrunc;
+    static constexpr bool kShared = R.kShared;     // shared-FIR mode (see phase 2)
+    static constexpr bool split_ok(uint32_t nt) { return R.split_ok(nt); }
+    static constexpr bool helper_ok(uint32_t nt) { return R.helper_ok(nt); }
+    static constexpr bool split_ok_shared(uint32_t nt) { return R.split_ok_shared(nt); }
+    static constexpr bool kPairFir = R.kPairFir;
+    static constexpr bool kUnrolledShared = R.kUnrolledShared;
+    static constexpr bool kPackedTile = R.kPackedTile;
+    static constexpr bool kPlanar = R.kPlanar;
+    static constexpr bool kBakedTaps = R.kBakedTaps;
+    static constexpr uint32_t lds_raw_elems = R.lds_raw_elems;      // float2 elements
 };
 
 struct DynGeo {
@@ -1348,35 +1295,21 @@ __device__ __forceinline__ void wave_fft_epilogue_fn(const ChainParams &P, const
 template <class GeoT, bool HAS_FIR>
 constexpr bool defer_fft_ok(uint32_t nt) {
     if constexpr (!GeoT::kFixed) return false;
-    else {
-        constexpr uint32_t GW = GeoT::kHalfTile ? GeoT::kHalfOut : GeoT::G * GeoT::W, FL = GeoT::kPackedTile ? GW / 2 : GW;       // lanes the FIR occupies
-        return HAS_FIR && (GeoT::kPairFir || GeoT::kPackedTile) && (GeoT::kFlags & kGeoDeferFft) != 0 && GeoT::kBatch == 2 && FL % 64 == 0 && FL + 64 <= nt;
-    }
+    else return GeoT::R.defer_fft_ok(HAS_FIR, nt);
 }
 
 // deferred FFT of one long window on four waves (see quad_fft_epilogue)
 template <class GeoT, bool HAS_FIR>
 constexpr bool quad_fft_ok(uint32_t nt) {
     if constexpr (!GeoT::kFixed) return false;
-    else {
-        constexpr uint32_t GW = GeoT::kHalfTile ? GeoT::kHalfOut : GeoT::G * GeoT::W, FL = GeoT::kPackedTile ? GW / 2 : GW;
-        return defer_fft_ok<GeoT, HAS_FIR>(nt) && GeoT::G == 1 && GeoT::W >= 256 && GeoT::layers >= 1 && GeoT::base_len >= 8 && FL + 4 * 64 <= nt;
-    }
+    else return GeoT::R.quad_fft_ok(HAS_FIR, nt);
 }
 
 // fast phase 1 (see k_chain): the tile starts on a row boundary whatever its index and is exactly RCH rows long
 template <int FMT, int NT, class GeoT>
 constexpr bool fast_p1_ok(int rch, bool whole, bool aligned) {
     if constexpr (!GeoT::kFixed) return false;
-    else {
-        constexpr uint32_t ROW = NT * FmtTraits<FMT>::SPL;
-        constexpr uint32_t tile_raw = GeoT::kHalfTile ? GeoT::kHalfRaw : (GeoT::G - 1) * GeoT::S * GeoT::D + GeoT::W * GeoT::D + GeoT::T;
-        constexpr uint32_t step = GeoT::kHalfTile ? GeoT::kHalfOut * GeoT::D : GeoT::S * GeoT::D;      // raw samples between consecutive passes
-        // tiles start at (first_window + t G) S D: on a row boundary for every t when G S D is a multiple of the row AND the launch's
-        // first window is (the host checks that per launch and sends a misaligned range to the per-sample kernel)
-        return whole && aligned && step % ROW == 0 && (GeoT::G * GeoT::S * GeoT::D) % ROW == 0 && (uint32_t)rch == (tile_raw + ROW - 1) / ROW && GeoT::D % FmtTraits<FMT>::SPL == 0 &&
-               (GeoT::kFlags & kGeoFastP1);
-    }
+    else return GeoT::R.fast_p1_ok(NT, FmtTraits<FMT>::SPL, (uint64_t)rch, whole, aligned);
 }
 
 // ---------------------------------------------------------------- the kernel
@@ -2223,21 +2156,12 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
 //     step 3   consumer: FFT + epilogue (no raw rows)         producers: rows RB .. RA of the next window
 // One s_barrier ends each step (every wave executes the same number of barriers: no flags, no polling, nothing to deadlock).
 // The products, their order and every rounding are k_chain's: the same process_row, fir_pair and wave_fft_epilogue_fn.
-constexpr uint32_t kGeoPipe = 512, kGeoPipeFftWave = 1024;
-constexpr uint32_t kGeoLoadSc0 = 2048, kGeoLoadSc1 = 4096;   // development: cache-policy bits of the phase-1 stream loads (with kGeoNtLoads)
-      // bit 10: a sixth wave takes the FFT + epilogue (384 threads, two FFT slots)
-constexpr int kPipeThreads = 320;
 template <int V> struct IntC { static constexpr int value = V; };
 
 template <int FMT, class GeoT>
 constexpr bool pipe_geometry_ok(int rch) {
     if constexpr (!GeoT::kFixed) return false;
-    else {
-        constexpr uint32_t ROW = 256u * FmtTraits<FMT>::SPL;
-        constexpr uint32_t tile_raw = GeoT::W * GeoT::D + GeoT::T;
-        return GeoT::G == 1 && GeoT::S == GeoT::W && GeoT::kPairFir && GeoT::W == 128 && (GeoT::S * GeoT::D) % ROW == 0 &&
-               (uint32_t)rch == (tile_raw + ROW - 1) / ROW && GeoT::D % FmtTraits<FMT>::SPL == 0 && GeoT::T > GeoT::D;
-    }
+    else return GeoT::R.pipe_geometry_ok(FmtTraits<FMT>::SPL, (uint64_t)rch);
 }
 
 template <int FMT, int NCO, class GeoT, int RCH, int LB, int NT = kPipeThreads>
@@ -2259,7 +2183,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain_pipe(const ChainParams P) {
     const GeoT geo(P);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2 *raw = reinterpret_cast<float2 *>(smem);                                // same layout as k_chain (host: lds_for)
+    float2 *raw = reinterpret_cast<float2 *>(smem);                                // same layout as k_chain (chain_lds_bytes)
     float2 *fb0 = raw + geo.lds_raw_elems;
     float2 *twl = fb0 + (size_t)GeoT::kBatch * W;
     float *tapl = reinterpret_cast<float *>(twl + W);
@@ -2519,22 +2443,14 @@ __global__ __launch_bounds__(NT, LB) void k_chain_pipe(const ChainParams P) {
 //     waves 12-15 (4 waves)      tile i-1: gather from dec / trc[(i-1)&1], FFT, |X|, store — each wave its own windows, wave-local
 // with one s_barrier per tile (every wave executes the same number of barriers: nothing to deadlock).  Same products, order and
 // roundings as k_chain's shared-FIR path; the price is the halo of a 12-window tile (31 % of its samples against 14 %).
-constexpr uint32_t kGeoPipe3 = 32768;
-constexpr int kPipe3Threads = 1024, kPipe3Prod = 512;
 
 template <int FMT, class GeoT>
 constexpr bool pipe3_geometry_ok(int rch) {
     if constexpr (!GeoT::kFixed) return false;
-    else {
-        constexpr uint32_t ROW = (uint32_t)kPipe3Prod * FmtTraits<FMT>::SPL;
-        constexpr uint32_t tile_raw = (GeoT::G - 1) * GeoT::S * GeoT::D + GeoT::W * GeoT::D + GeoT::T;
-        constexpr uint32_t Q = (GeoT::G - 1) * GeoT::S + GeoT::W;
-        return GeoT::kShared && GeoT::kUnrolledShared && Q <= 256 && (GeoT::G * GeoT::S * GeoT::D) % ROW == 0 &&
-               (uint32_t)rch == (tile_raw + ROW - 1) / ROW && GeoT::D % FmtTraits<FMT>::SPL == 0 && GeoT::W <= 64 * 16 && GeoT::G >= 1;
-    }
+    else return GeoT::R.pipe3_geometry_ok(FmtTraits<FMT>::SPL, (uint64_t)rch);
 }
-// LDS of the three-stage kernel, in float2 elements before the taps (the host restates this: lds_for_pipe3)
-template <class GeoT> constexpr uint32_t pipe3_q_pad() { return (((GeoT::G - 1) * GeoT::S + GeoT::W) + 1) & ~1u; }
+// dec / trc entries per set, padded to an even count (the whole layout: pipe3_lds_bytes)
+template <class GeoT> constexpr uint32_t pipe3_q_pad() { return (uint32_t)GeoT::R.pipe3_q_pad(); }
 
 template <int FMT, int NCO, class GeoT, int RCH, int LB>
 __global__ __launch_bounds__(kPipe3Threads, LB) void k_chain_pipe3(const ChainParams P) {
@@ -2906,45 +2822,27 @@ __device__ __forceinline__ void spark_fft_swz(const ChainParams &P, const float2
 // one step apart, one barrier per step, as in k_chain_pipe3.  Runs are a static, equal split of the launch's tiles (no queue: a
 // claimed tile would have to be its predecessor's neighbour).  Products, their order and every rounding are unchanged: output q
 // is the same fir_pair chain over the same shifted samples, computed once instead of up to twice.
-constexpr uint32_t kGeoStream = 131072;
-// bit 18: the streaming kernel as the `write` sink (QD_EPI_CF32_BLOCKS, src/lib.rs:178-213): producers + FIR waves only; the FIR lanes store
+// FLAGS_ bit 18: the streaming kernel as the `write` sink (QD_EPI_CF32_BLOCKS, src/lib.rs:178-213): producers + FIR waves only; the FIR lanes store
 // their decimated outputs themselves (a wave's 64 outputs are 512 contiguous bytes), truncation relative to the read_at block (ChainParams::blk_len)
-constexpr uint32_t kGeoWriteSink = 262144;
 
 template <int FMT, class GeoT, int PT_ = kPipe3Prod>
 struct Pipe3S {
     static_assert(PT_ == 256 || PT_ == 512, "producer threads: 256 or 512");
-    static constexpr uint32_t SPL = FmtTraits<FMT>::SPL, ROW = (uint32_t)PT_ * SPL;      // PT_ producer threads (PT_ / 64 waves), then four FIR and four FFT waves
+    static constexpr Pipe3sRules K = pipe3s_rules(FmtTraits<FMT>::SPL, PT_, GeoT::R);      // every constant's meaning: pipe3s_rules (qd_geometry.h)
+    static constexpr uint32_t SPL = K.SPL, ROW = K.ROW;
     static constexpr uint32_t W = GeoT::W, S = GeoT::S, D = GeoT::D, T = GeoT::T, G = GeoT::G, Dp = GeoT::Dp;
-    static constexpr uint32_t N = G * S * D, RN = N / ROW, GS = G * S;
-    static constexpr uint32_t c_half = T - T / 2, ntrunc = c_half ? (c_half + D - 1) / D - 1 : 0;
-    static constexpr uint32_t f0 = N >= c_half + T ? (N - c_half - T) / D + 1 : 0;          // full outputs the cold start's rows complete
-    static constexpr uint32_t RR = (2 * N + T + 2 * D + ROW - 1) / ROW;                       // ring rows: two steps + a chain's look-back
-    static constexpr uint32_t RINGD = RR * (ROW / D);                                           // ... in LDS rows of D samples
-    static constexpr uint32_t MIRD = (GeoT::b0 + T + D - 1) / D + 1;                            // mirror, in LDS rows
-    static constexpr uint32_t ROWP = (ROW / D) * Dp;                                            // padded elements per row of ROW samples
-    static constexpr uint32_t RAW_ELEMS = ((RINGD + MIRD) * Dp + 1) & ~1u;
-    static constexpr uint32_t DR = 3 * GS;
-    // overlapping windows: the shared FIR keeps a full value AND a truncated snapshot per output (dec + trc); windows side by side
-    // (S == W): every output belongs to one window and keeps the one value that window reads (dec only)
-    static constexpr bool kOverlap = S < W;
-    static constexpr bool fir_ok = kOverlap ? (GeoT::kShared && GeoT::kUnrolledShared)
-                                            : (S == W && GeoT::kPad == 2 && T % 4 == 0 && GeoT::b0 % 2 == 0 && D % 4 == 0 && T / 4 > 3 && (T / 2) % 4 == 0);
-    static constexpr bool ok = fir_ok && GS <= 256 && GS >= 1 && N % ROW == 0 && ROW % D == 0 && D % SPL == 0 &&
-                               W <= 64 * 16 && f0 >= 1 && f0 <= GS && f0 > W - S && ntrunc <= S && MIRD * D <= ROW && (G - 1) * S + W <= 2 * GS;
-    static constexpr bool kWrite = (GeoT::kFlags & kGeoWriteSink) != 0;          // no FFT stage, no output ring
+    static constexpr uint32_t N = K.N, RN = K.RN, GS = K.GS;
+    static constexpr uint32_t c_half = GeoT::c, ntrunc = GeoT::kNtrunc;
+    static constexpr uint32_t f0 = K.f0, RR = K.RR, RINGD = K.RINGD, MIRD = K.MIRD, ROWP = K.ROWP, RAW_ELEMS = K.RAW_ELEMS, DR = K.DR;
+    static constexpr bool kOverlap = K.kOverlap, fir_ok = K.fir_ok, ok = K.ok, kWrite = K.kWrite;
     static_assert(!kWrite || !kOverlap, "the write sink's sub-blocks lie side by side");
-    // the two transform buffers (base pass of step s beside the layers of step s - 1) start on a 256-byte boundary: their swizzled layout
-    // (SparkSwz) XORs into LDS byte addresses
-    static constexpr uint32_t FBX_OFF = (RAW_ELEMS + (kOverlap ? 2u : 1u) * DR + 31u) & ~31u;
-    static constexpr uint32_t kLdsBytes = kWrite ? RAW_ELEMS * 8 + ((T + 3) & ~3u) * 4
-                                                 : (FBX_OFF + 2 * G * W + W) * 8 + ((T + 3) & ~3u) * 4;
+    static constexpr uint32_t FBX_OFF = K.FBX_OFF, kLdsBytes = K.kLdsBytes;
     // swizzled transform buffers: the stage's LDS traffic unswizzled is 3.7x its conflict-free cycle count (the base pass's 16-byte pieces
     // 8-way, the gather and the first layer 2- to 4-way) — a tenth of the LDS array's cycles per step in a kernel whose FIR keeps the array
     // ~80 % busy (rocprofv3, cfg5).  Needs every wave's half of a buffer on a 256-byte boundary.
-    static constexpr uint32_t GH = (G + 1) / 2;
-    static constexpr bool kSwzFft = !kWrite && W >= 8 && (GH * W) % 32 == 0 && (G * W) % 32 == 0;
-    static constexpr uint32_t kConsumerThreads = kWrite ? 256u : 512u;
+    static constexpr uint32_t GH = K.GH;
+    static constexpr bool kSwzFft = K.kSwzFft;
+    static constexpr uint32_t kConsumerThreads = K.kConsumerThreads;
 };
 
 template <int FMT, int NCO, class GeoT, int RN_, int LB, int PT_ = kPipe3Prod>
@@ -3264,9 +3162,6 @@ __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512),
 // NCO row geometry: rows of 512 samples for every format (ChainParams::rowtab, jtab with 512 entries); a tile is two rows, a chunk
 // the quarter (cf32) or half (8-bit, cs16) of a row, so the lane constants of chunk c are those of quarter c % RQ: RQ * SPL = 8
 // (cos, sin) pairs per lane, kept in registers.
-constexpr uint32_t kGeoSpark = 524288;       // FLAGS bit 19 (reported in qd_plan_info.kernel_flags)
-constexpr uint32_t kSparkRow = 512;          // samples per NCO row of this kernel, every format
-constexpr uint32_t kSparkMaxW = 1024;
 
 // Which tiles a wave takes.  Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8), each XCD with an L2 of its own whose
 // channels interleave the address space in 4 KiB steps.  A chip-wide grid-stride walk hands XCD x the 32 KiB chunks x, x + 8, x + 16 ...
@@ -3570,7 +3465,6 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark(const ChainParams P) {
 // selected per lane from the tile's rows; same table entries, same operations as k_chain: bit-identical output.
 // W = 128 ... 1024 (width 16 or 64), every format (the integer formats' rows arrive packed: 4 or 8 bytes per lane and row); everything
 // else stays on k_spark.  Tile: 64 lanes x 2 columns x base rows = 1024 samples (base 8: W = 128, 512) or 2048 (base 16: W = 256, 1024).
-constexpr uint32_t kGeoSparkReg = 1048576;   // FLAGS bit 20
 
 // LDS swizzle of k_spark2's transform buffer: the same GF(2) maps as SparkSwz, searched over this kernel's LDS instructions (the base
 // pass's 16-byte piece writes of lane (g, xp), the layers' reads and writes; scripts/lds_swizzle_search2.py).  Base 16 (W = 256, 1024):
@@ -3588,9 +3482,8 @@ template <class GeoT> struct Spark2 {
     static constexpr uint32_t W = GeoT::W, base = GeoT::base_len, layers = GeoT::layers, width = W / base;
     static constexpr uint32_t LPW = width / 2, GW = 64 / (LPW ? LPW : 1), TS = GW * W, NBF = TS / 256;   // lanes per window, windows per tile, butterflies per lane and layer
     // (S < W: overlapping windows — each window's rows are loaded for it, the overlap comes out of the caches; HBM is read once)
-    static constexpr bool ok = GeoT::kFixed && (base == 8 || base == 16) && layers >= 1 && (width == 16 || width == 64) && GeoT::S <= W && GeoT::S >= 1 && GeoT::D == 1 && GeoT::T == 0;
+    static constexpr bool ok = GeoT::kFixed && GeoT::R.spark2_ok();
     static constexpr uint32_t kRows = TS / kSparkRow;                  // NCO rows per tile (2 or 4)
-    static constexpr uint32_t lds_bytes(bool shift) { return ((W < 16u ? 16u : W) + 4u * TS) * 8u + (shift ? kSparkRow * 16u : 0u); }
 };
 
 template <int FMT, int NCO, class GeoT, int LB, int EPI /* the plan's qd_epilogue, compile-time: the tile loop carries no sink dispatch */>
@@ -3845,13 +3738,12 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
 // contiguous piece per lane — 64 lanes x 16 bytes = one 1-KiB store instruction for W = 4.  No LDS, no barrier; the next tile's loads go
 // into the registers the unpack has just vacated.  Interleaved launches of k_spark (the stride dividing the width) read the stream W / S
 // times and write rows W / S apart — half-filled store instructions: 2^28 cf32 samples at W = 4 / S = 2 took 2.42 ms there.
-constexpr uint32_t kGeoSparkDirect = 2097152;   // FLAGS bit 21
 
 template <int FMT, class GeoT, int LB, int EPI /* the plan's qd_epilogue */>
 __global__ __launch_bounds__(kThreads, LB) void k_spark0(const ChainParams P) {
     using FT = FmtTraits<FMT>;
     constexpr uint32_t W = GeoT::W, S = GeoT::S, BPS = FT::BPS, ND = W * BPS / 4;       // dwords per window
-    static_assert(GeoT::kFixed && W >= 2 && W <= 16 && S >= 1 && S <= W && GeoT::D == 1 && GeoT::T == 0 && (W * BPS) % 4 == 0 && (S * BPS) % 4 == 0,
+    static_assert(GeoT::kFixed && GeoT::R.spark0_ok(BPS),
                   "k_spark0: one base butterfly per window, dword-aligned windows");
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t n_tiles = (P.n_windows + 63) / 64;                      // a tile: 64 windows, one per lane

@@ -8,7 +8,7 @@
 #if !defined(__HIPCC_RTC__)      // hiprtc (plan-time specialisation) supplies the HIP builtins itself
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#else
+#else      // (qd_geometry.h, which stands alone, declares the same fixed-width types: keep the two alike)
 typedef unsigned char uint8_t; typedef signed char int8_t; typedef unsigned short uint16_t; typedef short int16_t;
 typedef unsigned int uint32_t; typedef int int32_t; typedef unsigned long long uint64_t; typedef long long int64_t;
 typedef unsigned long uintptr_t; typedef unsigned long size_t;

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void k_bluestein(const float2 *__restrict__ in
     }
 }
 
-// ------------------------------------------------------------------ host arithmetic restated from the reference
+// ------------------------------------------------------------------ host arithmetic taken over from the reference
 
 // src/filter.rs:86-105 with cutoff from :126-128,:31 — f32 throughout, platform libm
 void design_taps(uint64_t frequency, uint64_t sample_rate, size_t size, float *out) {
@@ -415,8 +415,7 @@ std::mutex g_jit_mu;
 // key).  The on-disk code object is shared, only the load is repeated per device (one-process multi-device plans,
 // qd_plan_options.shard_device[]; that path is unexercised until a multi-GPU box is available — DESIGN.md section 8).
 std::map<std::pair<int, JitKey>, hipFunction_t> g_jit_cache;
-// builds that FAILED in this process (a static_assert of the kernel the host's restatement of its geometry did not foresee, a hiprtc
-// error): remembered with their message, so that every later plan of the shape falls back at once instead of paying the compile again
+// builds that FAILED in this process (a hiprtc error, a static_assert of the kernel): remembered with their message, so that every later plan of the shape falls back at once instead of paying the compile again
 std::map<std::pair<int, JitKey>, std::string> g_jit_failed;
 
 std::string csrc_dir() {
@@ -429,7 +428,7 @@ std::string csrc_dir() {
 
 // ---- on-disk cache of plan-time builds: a compile costs ~0.3-1 s, which a single pass over anything smaller than tens
 // of GiB never repays; a cached code object loads in ~1 ms.  Directory: $QD_JIT_CACHE ("0" / "off" disables), else
-// $XDG_CACHE_HOME/quadrs_hip, else $HOME/.cache/quadrs_hip.  File name: FNV-1a of (kernel name, options, the two kernel
+// $XDG_CACHE_HOME/quadrs_hip, else $HOME/.cache/quadrs_hip.  File name: FNV-1a of (kernel name, options, the kernel
 // headers' contents); file = "QDJIT1\n<lowered name>\n" + code object.  Every failure just means "not cached".
 uint64_t fnv1a(const void *data, size_t n, uint64_t h = 1469598103934665603ull) {
     const unsigned char *p = static_cast<const unsigned char *>(data);
@@ -469,38 +468,27 @@ hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compi
     if (it != g_jit_cache.end()) return it->second;
     if (auto bad = g_jit_failed.find(dk); bad != g_jit_failed.end()) { *why = bad->second; return nullptr; }
     const std::string dir = csrc_dir();
-    std::vector<char> hdr1, hdr2;
-    if (!read_file(dir + "/qd_chain.h", &hdr1) || !read_file(dir + "/qd_device.h", &hdr2)) {
-        *why = "kernel headers not found next to the library (" + dir + ")";
-        return nullptr;
+    std::vector<char> hdrs[3];            // everything a plan-time build includes: the cache key hashes their contents
+    const char *const hdr_names[3] = {"/qd_chain.h", "/qd_device.h", "/qd_geometry.h"};
+    for (int i = 0; i < 3; ++i)
+        if (!read_file(dir + hdr_names[i], &hdrs[i])) {
+            *why = "kernel headers not found next to the library (" + dir + ")";
+            return nullptr;
+        }
+    // "<family><fmt, [nco,] FixedGeo<...>, <the family's own trailing arguments>>"
+    char geo[160], tail[64], name[512];
+    snprintf(geo, sizeof geo, "qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>", k.W, k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags);
+    const Family fam = family_of(k.flags);
+    switch (fam) {
+    case kFamSpark0: case kFamSpark2: snprintf(tail, sizeof tail, "%d, %d", k.lb, k.epi); break;                  // the sink is a template argument
+    case kFamSpark: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, k.epi); break;                          // rch = chunks per tile
+    case kFamPipe3s: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, k.nt); break;                          // rch = rows per step, nt = producer threads
+    case kFamPipe3: snprintf(tail, sizeof tail, "%d, %d", k.rch, k.lb); break;
+    case kFamPipe: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, family_threads(256, k.flags)); break;
+    default: snprintf(tail, sizeof tail, "%s, %d, %s, true, %d, %d", k.fir ? "true" : "false", k.rch, k.whole ? "true" : "false", k.lb, k.nt); break;
     }
-    char name[512];
-    if ((k.flags & kGeoSpark) && (k.flags & kGeoSparkDirect))   // ... overlapping windows of 2 ... 8 points, a window per lane
-        snprintf(name, sizeof name, "qd::k_spark0<%d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d>", k.fmt, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.lb, k.epi);
-    else
-    if ((k.flags & kGeoSpark) && (k.flags & kGeoSparkReg))      // ... with the first FFT pass out of registers (cf32, W = 128 ... 1024)
-        snprintf(name, sizeof name, "qd::k_spark2<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d>", k.fmt, k.nco, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.lb, k.epi);
-    else
-    if (k.flags & kGeoSpark)       // the wave-local kernel of chains without a lowpass: rch = chunks per tile
-        snprintf(name, sizeof name, "qd::k_spark<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d, %d>", k.fmt, k.nco, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.rch, k.lb, k.epi);
-    else
-    if ((k.flags & kGeoPipe3) && (k.flags & kGeoStream))       // ... its streaming form: contiguous runs of tiles, state carried in LDS rings
-        snprintf(name, sizeof name, "qd::k_chain_pipe3s<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d, %d>", k.fmt, k.nco, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.rch, k.lb, k.nt);
-    else
-    if (k.flags & kGeoPipe3)       // the three-stage kernel for overlapping windows (k_chain_pipe3): 512 producer threads + FIR + FFT waves
-        snprintf(name, sizeof name, "qd::k_chain_pipe3<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d>", k.fmt, k.nco, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.rch, k.lb);
-    else
-    if (k.flags & kGeoPipe)        // the role-split kernel (k_chain_pipe): 256 producer threads + one consumer wave
-        snprintf(name, sizeof name, "qd::k_chain_pipe<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %d, %d, %d>", k.fmt, k.nco, k.W,
-                 k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.rch, k.lb, (k.flags & kGeoPipeFftWave) ? 384 : 320);
-    else
-    snprintf(name, sizeof name, "qd::k_chain<%d, %d, qd::FixedGeo<%u, %u, %u, %u, %u, %u, %u, %u, %u, %u>, %s, %d, %s, true, %d, %d>", k.fmt, k.nco, k.W,
-             k.S, k.D, k.T, k.G, k.firb, k.firr, k.pad, k.batch, k.flags, k.fir ? "true" : "false", k.rch, k.whole ? "true" : "false", k.lb, k.nt);
+    if (fam == kFamSpark0) snprintf(name, sizeof name, "%s<%d, %s, %s>", family_name(k.flags), k.fmt, geo, tail);      // (no shift: no NCO argument)
+    else snprintf(name, sizeof name, "%s<%d, %d, %s, %s>", family_name(k.flags), k.fmt, k.nco, geo, tail);
     std::string src;
     if ((k.flags & kGeoBakedTaps) && taps && !taps->empty()) {       // the plan's filter as exact hex-float literals
         src += "#define QD_BAKED_TAPS_LIST ";
@@ -545,8 +533,7 @@ hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compi
         h = fnv1a(&rtc_major, sizeof rtc_major, h);
         h = fnv1a(&rtc_minor, sizeof rtc_minor, h);
         for (const char *o : optv) if (o != inc.c_str()) h = fnv1a(o, strlen(o) + 1, h);
-        h = fnv1a(hdr1.data(), hdr1.size(), h);
-        h = fnv1a(hdr2.data(), hdr2.size(), h);
+        for (const std::vector<char> &hd : hdrs) h = fnv1a(hd.data(), hd.size(), h);
         const std::string cdir = dev_env("QD_JIT_DUMP") ? std::string() : jit_cache_dir();
         if (!cdir.empty()) { char fn[64]; snprintf(fn, sizeof fn, "/%016llx.co", (unsigned long long)h); cache_file = cdir + fn; }
     }
@@ -610,61 +597,27 @@ struct Geometry {
     size_t lds_main = 0;         // the main kernel's own need when it is smaller (half-window tiles): its launch size, and what bounds workgroups per CU
 };
 
-// Dynamic LDS of a chain kernel with this tiling.  Layout (qd_chain.h, k_chain prologue): raw tile | batch x G*W FFT buffers |
-// twiddles | taps | 8-bit LUT | shared-FIR dec/trc | batch bookkeeping.  The generic kernels (interleaved tile, pad 1, batch 1,
-// taps in LDS) run inside the same allocation for the unaligned slab tail, so the size is the larger of the two layouts.
+// Dynamic LDS of a chain kernel with this tiling: its family's layout (qd_geometry.h) plus the historical slack, and the generic
+// kernels' layout, which runs inside the same allocation for the unaligned slab tail — the larger of the two.
 size_t lds_for(uint32_t G, uint64_t W, uint64_t S, uint64_t D, uint64_t T, uint32_t *raw_elems, uint32_t pad_per_row = 1, uint32_t batch = 1,
                bool lut8 = true, uint32_t flags = 0, size_t *main_only = nullptr, int stream_spl = 2 /* samples per lane and row load (streaming kernel) */,
                int stream_nt = 512 /* its producer threads */) {
-    uint64_t tile_raw = (uint64_t)(G - 1) * S * D + W * D + T;
-    const uint64_t full_raw = tile_raw;
-    if ((flags & kGeoHalfTile) && G == 1 && T > 0 && S >= W) tile_raw = (T - T / 2) + (W / 2 - 1) * D + T;     // FixedGeo::kHalfRaw
-    auto interleaved = [&](uint32_t padv) {
-        const uint64_t pad = (D % 2 == 0) ? padv * (tile_raw / D + 1) : 0;
-        uint64_t elems = tile_raw + pad + 1;
-        const uint64_t min_elems = (uint64_t)G * W / 2 + 1;     // bucket epilogue parks G*W f32 norms here
-        if (elems < min_elems) elems = min_elems;
-        return (elems + 1) & ~1ull;                             // keep fb 16-byte aligned
-    };
-    auto gen_elems_of = [&](uint64_t raw) {                       // the runtime-geometry kernels' tile: pad 1, always the full tile
-        const uint64_t pad = (D % 2 == 0) ? (raw / D + 1) : 0;
-        uint64_t elems = raw + pad + 1;
-        const uint64_t min_elems = (uint64_t)G * W / 2 + 1;
-        if (elems < min_elems) elems = min_elems;
-        return (elems + 1) & ~1ull;
-    };
-    const uint64_t shared_fir = (T && S < W) ? 2 * ((uint64_t)(G - 1) * S + W) * 8 : 0;   // dec[] + trc[] of the shared-FIR mode
-    const uint64_t taps_b = ((T + 3) & ~3ull) * 4, lut_b = lut8 ? 256 * 4 : 0;
-    uint64_t elems = interleaved(pad_per_row);
-    // planar tile + immediates for taps (FixedGeo::kPlanar / kBakedTaps; the kernel falls back to the interleaved layout
-    // when its geometry conditions fail, which only needs less)
-    const bool planar = (flags & kGeoPlanar) && tile_raw < (1u << 24);
-    if (planar) { const uint64_t pe = ct_plane_floats((uint32_t)W, (uint32_t)S, (uint32_t)D, (uint32_t)T, G); if (pe > elems) elems = pe; }
+    const FixedRules g = fixed_rules(W, S, D, T, G, 8, 1, pad_per_row, batch, flags);
     // *raw_elems is what the runtime-geometry kernels read (ChainParams::lds_raw_elems): THEIR raw tile, whatever the main kernel's
-    if (raw_elems) *raw_elems = (uint32_t)gen_elems_of(full_raw);
-    const bool baked = planar && (flags & kGeoBakedTaps);
-    const uint64_t main_b = elems * 8 + (uint64_t)batch * G * W * 8 + W * 8 + (baked ? 0 : taps_b) + lut_b + shared_fir + (uint64_t)batch * 16 + 16;
-    const uint64_t generic_b = gen_elems_of(full_raw) * 8 + (uint64_t)G * W * 8 + W * 8 + taps_b + lut_b + shared_fir + 16 + 16;
-    if ((flags & kGeoPipe3) && (flags & kGeoStream)) {
-        // k_chain_pipe3s (qd_chain.h, Pipe3S): sample ring + mirror | dec + trc rings of 3 G S | G*W FFT buffers | twiddles | taps
-        const uint64_t row = (uint64_t)stream_nt * stream_spl, n_new = (uint64_t)G * S * D, dp = D + ((D % 2 == 0) ? pad_per_row : 0);
-        const uint64_t rr = (2 * n_new + T + 2 * D + row - 1) / row, ringd = rr * (row / D);
-        const uint64_t c = T - T / 2, mird = ((c % D) + T + D - 1) / D + 1;
-        const uint64_t raw_e = ((ringd + mird) * dp + 1) & ~1ull;
-        const uint64_t p3 = (flags & kGeoWriteSink) ? raw_e * 8 + taps_b + 64      // the write sink: sample ring | taps
-                                                    : raw_e * 8 + (S < W ? 2 : 1) * 3 * (uint64_t)G * S * 8 + 2 * (uint64_t)G * W * 8 + W * 8 + taps_b + 64 + 256;      // trc: overlapping windows only; two transform buffers, on a 256-byte boundary
-        if (main_only) *main_only = (size_t)p3;
-        return (size_t)(p3 > generic_b ? p3 : generic_b);
+    if (raw_elems) *raw_elems = (uint32_t)generic_raw_elems(g);
+    uint64_t main_b = 0;
+    // (the role-split kernel's layout is k_chain's; a wave-local plan sizes the generic chain kernels here, its own LDS is spark_lds_bytes)
+    switch (family_of(flags & ~(kGeoSpark | kGeoPipe))) {
+    case kFamPipe3s: {
+        const Pipe3sRules k = pipe3s_rules((uint64_t)stream_spl, (uint64_t)stream_nt, g);
+        main_b = k.kLdsBytes + (k.kWrite ? kStreamWriteLdsSlack : kStreamLdsSlack - k.FBX_ALIGN * 8);
+        break;
     }
-    if (flags & kGeoPipe3) {
-        // k_chain_pipe3: two raw tiles | dec + trc of two sets | G*W FFT buffers | twiddles | taps | queue hand-over
-        const uint64_t qp = (((uint64_t)(G - 1) * S + W) + 1) & ~1ull;
-        const uint64_t p3 = 2 * elems * 8 + 4 * qp * 8 + (uint64_t)G * W * 8 + W * 8 + taps_b + 64;
-        if (main_only) *main_only = (size_t)p3;
-        return (size_t)(p3 > generic_b ? p3 : generic_b);
+    case kFamPipe3: main_b = pipe3_lds_bytes(g) + kPipe3LdsSlack; break;
+    default: main_b = chain_lds_bytes(g, lut8); break;
     }
     if (main_only) *main_only = (size_t)main_b;       // what the MAIN kernel needs (half-window tiles: well under the generic kernels' full tile)
-    return (size_t)(main_b > generic_b ? main_b : generic_b);
+    return (size_t)std::max(main_b, generic_lds_bytes(g, lut8));
 }
 
 constexpr size_t kLdsMax = 160 * 1024;
@@ -760,6 +713,11 @@ struct qd_plan {
     std::vector<qd_shard_info> shard_info;
     std::mutex mu;
 };
+// the kernel a committed chain plan launches: its flags' family where a shape-specialised kernel won, the runtime-geometry k_chain otherwise
+// (the flag bits of k_chain_pipe, k_spark2 and k_spark0 — 9, 20, 21 — only ever come from plan-time builds: no table entry carries them)
+static Family plan_family(const qd_plan *p) { return (p->jit_fn || p->fixed || p->spark) ? family_of(p->kflags) : kFamChain; }
+// ... and whether that kernel wants its launches on the row grid
+static bool plan_on_rows(const qd_plan *p) { return (p->jit_fn || p->fixed || p->spark) && row_aligned(p->kflags); }
 
 namespace {
 
@@ -1000,7 +958,7 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
     if (p->has_shift) {
         // row-aligned phase 1: rows of a short last tile's missing windows (and a half-window pass's read-ahead) get table entries too
         // (the streaming kernel parks one more step of rows behind a run's last tile)
-        const uint64_t extra = ((p->kflags & (kGeoFastP1 | kGeoPipe3 | kGeoSpark)) && (p->jit_fn || p->fixed || p->spark)) ? (uint64_t)p->geo.G * p->S * p->D * ((p->kflags & kGeoStream) ? 2 : 1) + p->T : 0;
+        const uint64_t extra = plan_on_rows(p) ? (uint64_t)p->geo.G * p->S * p->D * (plan_family(p) == kFamPipe3s ? 2 : 1) + p->T : 0;
         rc = ensure_rowtab_for(p, p->nt * spl_of(fmt), &tabs->main, need0, need1 + extra, st);
         if (rc) return rc;
     }
@@ -1027,10 +985,10 @@ int launch_chain(qd_plan *p, NcoTabs *tabs, const void *src_d, uint64_t src_firs
                         src_count * (uint64_t)bps >= (uint64_t)vec_bytes;
     uint64_t n_aligned = 0;
     // row-aligned phase 1 with G S D (not S D) a multiple of the row: the launch's first window must sit on a row boundary too
-    bool fast_misaligned = (p->kflags & (kGeoFastP1 | kGeoPipe3)) && (p->jit_fn || p->fixed) && ((first_window * p->S * p->D) % ((uint64_t)p->nt * spl)) != 0;
+    bool fast_misaligned = plan_on_rows(p) && ((first_window * p->S * p->D) % ((uint64_t)p->nt * spl)) != 0;
     // the wave-local kernel: tiles start on NCO rows when the chain shifts, on load vectors otherwise; irregular rows (take_fft) never run on it
     if (p->spark) fast_misaligned = phases_unaligned || p->row_offsets_d != nullptr || ((first_window * p->S) % (p->has_shift ? (uint64_t)kSparkRow : (uint64_t)spl)) != 0;
-    if (p->spark && (p->kflags & kGeoSparkDirect) && p->jit_fn) fast_misaligned = p->row_offsets_d != nullptr;      // a window per lane: any window start (S BPS is a multiple of 4)
+    if (plan_family(p) == kFamSpark0) fast_misaligned = p->row_offsets_d != nullptr;      // a window per lane: any window start (S BPS is a multiple of 4)
     if (vec_ok && !fast_misaligned) {
         // windows [first_window, first_window + n_aligned): need-end rounded up to a vector fits in the slab
         const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T;
@@ -1188,14 +1146,8 @@ struct Candidate {
     int wg_regs = 0;                        // workgroups per CU its register budget admits (0: no bound of its own)
 };
 
-// workgroup size of a chain kernel: nt, plus the consumer waves of the role-split and three-stage kernels; the wave-local kernels
-// run four waves per workgroup whatever their row geometry (their nt = 512 / SPL only lays out the NCO tables)
-int launch_threads(int nt, uint32_t flags) {
-    if (flags & kGeoSpark) return kThreads;
-    return nt + ((flags & kGeoPipe3) ? ((flags & kGeoWriteSink) ? 256 : 512) : ((flags & kGeoPipe) ? ((flags & kGeoPipeFftWave) ? 128 : 64) : 0));
-}
-
 bool lut8_of(int fmt) { return fmt == QD_FMT_CS8 || fmt == QD_FMT_CU8; }
+constexpr uint64_t kWholeRows = 10;      // rows per tile (per step) up to which a build prefetches whole tiles: what every recipe aims for
 
 // the plain tiling: windows per tile of the generic kernels and of the plain plan-time build (256 threads, pad 1, batch 1, flags 0)
 uint32_t plain_tiles(const qd_plan *p, uint32_t T_lds) {
@@ -1215,46 +1167,45 @@ uint32_t plain_tiles(const qd_plan *p, uint32_t T_lds) {
 // the plan-time build of a chain kernel (k_chain and its role-split / three-stage forms) with this tiling; `capped`: its register budget
 // bounds the workgroups per CU (lb waves per SIMD)
 Candidate chain_build(const qd_plan *p, Candidate c, bool capped) {
-    const uint64_t ROW = (uint64_t)c.nt * spl_of(p->d.format), step = (uint64_t)p->S * p->D;
-    uint64_t tile_raw = (uint64_t)(c.G - 1) * step + (uint64_t)p->W * p->D + p->T;
-    if ((c.flags & kGeoHalfTile) && c.G == 1 && p->S >= p->W) tile_raw = (p->T - p->T / 2) + (uint64_t)(p->W / 2 - 1) * p->D + p->T;      // rows of ONE pass
+    const uint64_t spl = spl_of(p->d.format), ROW = (uint64_t)c.nt * spl, step = (uint64_t)p->S * p->D;
+    const FixedRules g = fixed_rules(p->W, p->S, p->D, p->T, c.G, c.firb, c.firr, c.pad, c.batch, c.flags);
+    const Family fam = family_of(c.flags);
     // a run may start at any window, so a tile starts on a row boundary only if S*D is a multiple of ROW
-    const bool tiles_on_rows = step % ROW == 0 || ((c.flags & (kGeoFastP1 | kGeoPipe3)) && (c.G * step) % ROW == 0);
-    uint64_t rows = (tile_raw + ROW - 1) / ROW + (tiles_on_rows ? 0 : 1);
-    if ((c.flags & kGeoPipe3) && (c.flags & kGeoStream)) rows = (c.G * step) / ROW;      // rows per step of the streaming kernel
+    const bool tiles_on_rows = step % ROW == 0 || (row_aligned(c.flags) && (c.G * step) % ROW == 0);
+    uint64_t rows = g.rows(c.nt, spl) + (tiles_on_rows ? 0 : 1);       // (half-window tiles: rows of ONE pass)
+    if (fam == kFamPipe3s) rows = pipe3s_rules(spl, c.nt, g).RN;      // rows per step of the streaming kernel
     // the unrolled FIR's scalar accumulate chains must stay scalar (the three-stage kernel's FIR is the packed asm form)
-    const int noslp = c.noslp || ((c.flags & kGeoUnrolledFir) && !(c.flags & kGeoPipe3));
+    const int noslp = c.noslp || ((c.flags & kGeoUnrolledFir) && fam != kFamPipe3 && fam != kFamPipe3s);
     c.src = Candidate::kBuild;
-    c.key = JitKey{p->d.format, p->nco, p->has_fir ? 1 : 0, rows <= 10 ? (int)rows : 4, rows <= 10 ? 1 : 0, c.lb, c.nt,
+    c.key = JitKey{p->d.format, p->nco, p->has_fir ? 1 : 0, rows <= kWholeRows ? (int)rows : 4, rows <= kWholeRows ? 1 : 0, c.lb, c.nt,
                    p->W, p->S, p->D, p->T, c.G, c.firb, c.firr, noslp, c.pad, c.batch, c.flags,
                    (c.flags & kGeoBakedTaps) ? fnv1a(p->taps_h.data(), p->taps_h.size() * sizeof(float)) : 0ull};
-    c.wg_regs = capped ? std::max(1, c.lb * 4 * 64 / launch_threads(c.nt, c.flags)) : 0;
+    c.wg_regs = capped ? std::max(1, c.lb * 4 * 64 / family_threads(c.nt, c.flags)) : 0;
     return c;
 }
 
-// ---- kernel variant from GEOMETRY (plan-time builds): the variants of the built-in cfg3' / cfg4 kernels as predicates of the shape
-// (profiles/r03/shape_sweep.log).  The predicates restate FixedGeo's own static conditions (qd_chain.h), so
-// the build takes the path asked for.  Returns false for shapes without a recipe.
+// ---- kernel variant from GEOMETRY (plan-time builds): the variants of the built-in cfg3' / cfg4 kernels as recipes for a shape
+// (profiles/r03/shape_sweep.log).  Which tiling to try is decided here; whether a kernel can run it is asked of
+// the kernels' own rules (qd_geometry.h), so the build takes the path asked for.  Returns false for shapes without a recipe.
 bool geometry_recipe(const qd_plan *p, uint32_t T_lds, Candidate *r) {
-    const uint32_t W = p->W, S = p->S, D = p->D, T = p->T, c_half = T - T / 2;
-    const int spl = spl_of(p->d.format);
+    const uint32_t W = p->W, S = p->S, D = p->D, T = p->T;
+    const uint64_t spl = spl_of(p->d.format);
     const bool lut8 = lut8_of(p->d.format);
     r->pad = 2;
+    auto rules = [&](uint32_t g, uint32_t flags, uint32_t batch = 1, uint32_t firr = 1, uint32_t firb = 8, uint32_t stride = 0) {
+        return fixed_rules(W, stride ? stride : S, D, T, g, firb, firr, 2, batch, flags);
+    };
     if (p->d.epilogue == QD_EPI_CF32_BLOCKS) {
         // The `write` sink (N1: shift -> lowpass -> decimated cf32 in read_at blocks): the streaming kernel with producers and FIR waves
         // only — a step is one sub-block of W = min(block, 256) outputs on as many FIR lanes, which store their outputs themselves;
-        // truncation is relative to the block (ChainParams::blk_len).  The conditions restate Pipe3S<>::ok for side-by-side windows.
-        const bool pk_geo = T % 4 == 0 && (T / 2) % 4 == 0 && T / 4 > 3 && D % 4 == 0 && (c_half % D) % 2 == 0 && D % spl == 0 && is_pow2(W) && W <= 256 &&
-                            p->blk_len % W == 0 && is_pow2(p->blk_subs);
+        // truncation is relative to the block (ChainParams::blk_len).
+        if (!(is_pow2(W) && W <= 256 && p->blk_len % W == 0 && is_pow2(p->blk_subs))) return false;
+        const uint32_t fl = kGeoNoSplit | kGeoNtLoads | kGeoPipe3 | kGeoStream | kGeoWriteSink;
         for (int snt : {512, 256}) {
-            if (!pk_geo) break;
-            const uint64_t SROW = (uint64_t)snt * spl, n_new = (uint64_t)W * D;
-            if (n_new % SROW != 0 || SROW % D != 0 || n_new < (uint64_t)c_half + T || n_new / SROW > 10) continue;
-            const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
-            if (f0 > W || mird * D > SROW) continue;
-            const uint32_t fl = kGeoNoSplit | kGeoNtLoads | kGeoPipe3 | kGeoStream | kGeoWriteSink;
-            if (lds_for(1, W, W, D, T, nullptr, 2, 1, lut8, fl, nullptr, spl, snt) > kLdsMax ||        // the kernel's own layout (its T, no tile_extra) ...
-                lds_for(1, W, W, D, T_lds, nullptr, 1, 1, lut8) > kLdsMax) continue;                        // ... and the generic kernels' tile for an unaligned tail
+            const Pipe3sRules k = pipe3s_rules(spl, snt, rules(1, fl));
+            if (!k.ok || k.RN > kWholeRows) continue;
+            if (lds_for(1, W, S, D, T, nullptr, 2, 1, lut8, fl, nullptr, (int)spl, snt) > kLdsMax ||        // the kernel's own layout (its T, no tile_extra) ...
+                lds_for(1, W, S, D, T_lds, nullptr, 1, 1, lut8) > kLdsMax) continue;                        // ... and the generic kernels' tile for an unaligned tail
             r->G = 1; r->nt = snt; r->flags = fl;
             return true;
         }
@@ -1263,70 +1214,70 @@ bool geometry_recipe(const qd_plan *p, uint32_t T_lds, Candidate *r) {
     if (S < W) {
         // Overlapping windows with a long filter (>= 8 taps per input sample): the three-stage kernel (shared FIR on 16-byte rows, at most
         // 256 outputs per tile, tiles on rows of 512 producer threads), streaming where its geometry holds.  cfg5: 7.50 -> 6.71 ms.
-        const uint32_t ntrunc = c_half ? (c_half + D - 1) / D - 1 : 0;
-        if ((uint64_t)T < 8ull * D || !(ntrunc <= S && D % 2 == 0 && c_half % 2 == 0 && T % 4 == 0 && (c_half % D) % 2 == 0 && D % 4 == 0 && T >= 32 &&
-                                        D % spl == 0 && is_pow2(W) && W <= 1024))
-            return false;
-        const uint64_t ROW = 512ull * spl, step = (uint64_t)S * D;
-        uint64_t a = ROW, b = step; while (b) { const uint64_t t = a % b; a = b; b = t; }      // gcd
-        const uint32_t g_unit = (uint32_t)(ROW / a);                                              // tiles start on rows when G is a multiple of this
+        const uint32_t fl3 = kGeoUnrolledFir | kGeoPipe3, fls = fl3 | kGeoStream;
+        if ((uint64_t)T < 8ull * D || !rules(1, fl3).kUnrolledShared) return false;
+        const uint64_t step = (uint64_t)S * D;
         // (1) the STREAMING form (k_chain_pipe3s): the step of G S new outputs with the most outputs the rings leave room for (the FIR is
         // bound by one wave's pass over the T taps), rows of 512 producer threads or of 256 where that admits a larger step (8-bit
-        // formats).  The conditions restate Pipe3S<>::ok (qd_chain.h).
+        // formats)
         uint32_t best_s = 0; int best_nt = 512;
         for (int snt : {512, 256}) {
-            const uint64_t SROW = (uint64_t)snt * spl;
-            uint64_t a2 = SROW, b2 = step; while (b2) { const uint64_t t = a2 % b2; a2 = b2; b2 = t; }
-            const uint32_t su = (uint32_t)(SROW / a2);
-            for (uint32_t g = su; g >= 1 && g <= 64 && (uint64_t)g * S <= 256; g += su) {
-                const uint64_t n_new = (uint64_t)g * S * D, gs = (uint64_t)g * S;
-                if (n_new < (uint64_t)c_half + T) continue;
-                const uint64_t f0 = (n_new - c_half - T) / D + 1, mird = ((c_half % D) + T + D - 1) / D + 1;
-                if (!(SROW % D == 0 && f0 <= gs && f0 > W - S && mird * D <= SROW && (uint64_t)(g - 1) * S + W <= 2 * gs && n_new / SROW <= 10)) continue;
-                if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3 | kGeoStream, nullptr, spl, snt) > kLdsMax) break;
+            const uint32_t su = (uint32_t)(snt * spl / ct_gcd(snt * spl, step));      // steps start on rows when G is a multiple of this
+            for (uint32_t g = su; g <= 64; g += su) {
+                const Pipe3sRules k = pipe3s_rules(spl, snt, rules(g, fls));
+                if (!k.ok || k.RN > kWholeRows) continue;
+                if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, fls, nullptr, (int)spl, snt) > kLdsMax) break;
                 if (p->n_windows < g) break;
                 if (g > best_s) { best_s = g; best_nt = snt; }
             }
         }
-        if (best_s) { r->G = best_s; r->nt = best_nt; r->flags = kGeoUnrolledFir | kGeoPipe3 | kGeoStream | kGeoNtLoads; return true; }
+        if (best_s) { r->G = best_s; r->nt = best_nt; r->flags = fls | kGeoNtLoads; return true; }
         // (2) the tile-at-a-time three-stage kernel, where the streaming form's geometry fails
+        const uint32_t g_unit = (uint32_t)(512 * spl / ct_gcd(512 * spl, step));             // tiles start on rows when G is a multiple of this
         uint32_t best = 0;
-        for (uint32_t g = g_unit; g >= 1 && g <= 64 && (uint64_t)(g - 1) * S + W <= 256; g += g_unit) {
-            const uint64_t tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
-            if ((tile_raw + ROW - 1) / ROW > 10) break;
-            if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, kGeoUnrolledFir | kGeoPipe3) > kLdsMax) break;
+        for (uint32_t g = g_unit; g <= 64; g += g_unit) {
+            const FixedRules t = rules(g, fl3);
+            const uint64_t rows = t.rows(512, spl);
+            if (rows > kWholeRows || !t.pipe3_geometry_ok(spl, rows)) break;
+            if (lds_for(g, W, S, D, T_lds, nullptr, 2, 1, lut8, fl3) > kLdsMax) break;
             if (p->n_windows < g) break;
             best = g;
         }
-        if (best) { r->G = best; r->nt = 512; r->flags = kGeoUnrolledFir | kGeoPipe3; return true; }
+        if (best) { r->G = best; r->nt = 512; r->flags = fl3; return true; }
         return false;
     }
-    auto rows_aligned = [&](uint32_t nt, uint32_t g) {            // fast phase 1: tiles start on a row boundary, <= 10 rows, whole-tile prefetch
-        const uint64_t ROW = (uint64_t)nt * spl, tile_raw = (uint64_t)(g - 1) * S * D + (uint64_t)W * D + T;
-        return ((uint64_t)S * D) % ROW == 0 && (tile_raw + ROW - 1) / ROW <= 10 && D % spl == 0;
-    };
-    const bool pk_geo = T >= 64 && T % 4 == 0 && D % 4 == 0 && is_pow2(D) && c_half % 2 == 0 && (c_half % D) % 2 == 0;
-    const bool tile2_geo = pk_geo && (T / 2) % 4 == 0 && c_half % 4 == 0 && D / 4 <= 8 && T > D + 16 && W % 2 == 0;
-    if (tile2_geo && W >= 512 && (uint64_t)T >= 4ull * D) {
+    // fast phase 1: tiles start on a row boundary and a whole tile is prefetched
+    auto on_rows = [&](const FixedRules &t, int nt) { const uint64_t rows = t.rows(nt, spl); return t.fast_p1_ok(nt, spl, rows, rows <= kWholeRows, true); };
+    if (T < 64 || !is_pow2(D)) return false;      // the recipes below were measured on filters of 64 taps and more, power-of-two decimation
+    const uint32_t fl_tile = kGeoPackedTile | kGeoDeferFft;
+    // Two outcomes of the recipe below are kept as they have always been, although the kernels' rules say otherwise (changing them
+    // changes which kernel a plan runs, which wants a measurement of its own):
+    //  * the stride's parity is not asked about (the rules are asked with the stride rounded down to even): an odd stride S >= W builds
+    //    with the register-tiled FIR falling back to one output per lane (kFirTile4 needs an even stride);
+    //  * half-window tiles are asked for from W = 1024 up, but from W = 2048 the deferred FFT they need has no wave to run on
+    //    (defer_fft_ok: W / 4 + 64 <= 512 lanes), so that build fails its static_assert and the plan steps down the candidate list.
+    if (W >= 512 && (uint64_t)T >= 4ull * D && rules(1, fl_tile, 2, 2, 4, S & ~1u).kPackedTile) {
         // one long window per tile (cfg4's recipe): two outputs per lane as straight-line packed code with in-chain
         // snapshots, the previous window's FFT + epilogue on idle waves, as many threads as the FIR has lanes for
         // half-window tiles (two passes per window, two workgroups per CU) where a pass is a whole number of rows of 512 threads
-        const uint64_t half_raw = (uint64_t)c_half + (uint64_t)(W / 2 - 1) * D + T, ROW512 = 512ull * spl;
-        const bool half_ok = W >= 1024 && W % 4 == 0 && ((uint64_t)(W / 2) * D) % ROW512 == 0 && ((uint64_t)S * D) % ROW512 == 0 &&
-                             (half_raw + ROW512 - 1) / ROW512 <= 10 && D % spl == 0;
+        const uint32_t fl_half = fl_tile | kGeoHalfTile | kGeoFastP1 | kGeoNtLoads, fl_rows = fl_tile | kGeoFastP1 | kGeoNtLoads | kGeoNtInner;
+        const FixedRules h = rules(1, fl_half, 2, 2, 4);
+        const bool half_ok = W >= 1024 && h.kHalfTile && on_rows(h, 512);
         const int nt = half_ok ? 512 : (W >= 1024 ? 1024 : 512);
-        const uint32_t fl = kGeoPackedTile | kGeoDeferFft | (half_ok ? (kGeoHalfTile | kGeoFastP1 | kGeoNtLoads) : (rows_aligned(nt, 1) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u));
+        const uint32_t fl = half_ok ? fl_half : (on_rows(rules(1, fl_rows, 2, 2, 4), nt) ? fl_rows : fl_tile);
         if (lds_for(1, W, S, D, T_lds, nullptr, 2, 2, lut8, fl) > kLdsMax) return false;
         r->G = 1; r->nt = nt; r->batch = 2; r->flags = fl; r->firr = 2; r->firb = 4;
         return true;
     }
-    if (pk_geo && W <= 256) {
+    if (W <= 256) {
         // 64..256 outputs per tile of 256 threads (cfg3' recipe): packed lane-per-output FIR on a 16-byte-row tile; where the
         // FIR leaves a wave idle, the previous tile's FFT + epilogue runs there
         const uint32_t g = W >= 128 ? 1u : 128u / W;
-        const bool defer = (g * W) % 64 == 0 && g * W + 64 <= 256;
-        const uint32_t fl = kGeoNoSplit | (defer ? kGeoDeferFft : 0u) | (rows_aligned(256, g) ? (kGeoFastP1 | kGeoNtLoads | kGeoNtInner) : 0u);
-        const uint32_t bt = defer ? 2u : 1u;
+        const FixedRules d2 = rules(g, kGeoNoSplit | kGeoDeferFft, 2);
+        if (!d2.kPairFir) return false;
+        const bool defer = d2.defer_fft_ok(true, 256);
+        const uint32_t bt = defer ? 2u : 1u, fl_base = kGeoNoSplit | (defer ? kGeoDeferFft : 0u), fl_rows = fl_base | kGeoFastP1 | kGeoNtLoads | kGeoNtInner;
+        const uint32_t fl = on_rows(rules(g, fl_rows, bt), 256) ? fl_rows : fl_base;
         if (p->n_windows < g || lds_for(g, W, S, D, T_lds, nullptr, 2, bt, lut8, fl) > kLdsMax / 2) return false;      // at least two workgroups per CU
         r->G = g; r->nt = 256; r->batch = bt; r->flags = fl;
         return true;
@@ -1449,19 +1400,19 @@ int commit_candidate(qd_plan *p, const Candidate &c, hipFunction_t jit_fn, uint3
     p->fixed = c.fixed;
     p->jit_fn = jit_fn;
     p->spark = (c.flags & kGeoSpark) != 0;
+    const Family fam = family_of(c.flags);
     p->spark_ts = c.spark_ts; p->spark_R = c.spark_R;
     p->geo.G = c.G; p->nt = c.nt; p->kflags = c.flags;
-    p->launch_nt = launch_threads(c.nt, c.flags);
+    p->launch_nt = family_threads(c.nt, c.flags);
     // the generic kernels (pad 1, batch 1) fit inside the same allocation; the streaming write kernel is laid out for T, the generic
     // kernels' tile (an unaligned tail) for T + tile_extra
     const bool ws = (c.flags & kGeoWriteSink) != 0;
     uint32_t raw_elems = 0;
     p->geo.lds_bytes = lds_for(c.G, p->W, p->S, p->D, ws ? p->T : T_lds, &raw_elems, c.pad, c.batch, lut8_of(fmt), c.flags, &p->geo.lds_main, spl_of(fmt), c.nt);
     if (ws) p->geo.lds_bytes = std::max(p->geo.lds_bytes, lds_for(c.G, p->W, p->S, p->D, T_lds, &raw_elems, 1, 1, lut8_of(fmt)));
-    if (!(c.flags & (kGeoHalfTile | kGeoPipe3))) p->geo.lds_main = p->geo.lds_bytes;
-    if (p->spark) p->geo.lds_main = ((size_t)(p->W < 32 ? 32 : p->W) + 4 * (size_t)c.spark_ts) * 8 +     // twiddles | four waves' transform buffers (k_spark)
-                                    ((((c.flags & kGeoSparkReg) && p->has_shift) || c.spark_jt_lds) ? (size_t)kSparkRow * 16 : 0);   // plan-time builds with a shift: + the NCO lane table
-    if (c.flags & kGeoSparkDirect) p->geo.lds_main = 16;                 // k_spark0 uses no LDS (a token size: 0 means "the generic layout's")
+    if (!(c.flags & kGeoHalfTile) && fam != kFamPipe3 && fam != kFamPipe3s) p->geo.lds_main = p->geo.lds_bytes;      // (only those are smaller than the generic layout on purpose)
+    if (p->spark) p->geo.lds_main = (size_t)spark_lds_bytes(p->W, c.spark_ts, (fam == kFamSpark2 && p->has_shift) || c.spark_jt_lds);   // plan-time builds with a shift: + the NCO lane table
+    if (fam == kFamSpark0) p->geo.lds_main = 16;                         // k_spark0 uses no LDS (a token size: 0 means "the generic layout's")
     p->geo.lds_raw_elems = raw_elems;
     p->geo.Dp = p->D + ((p->D % 2 == 0) ? 1 : 0);
     if ((uint64_t)raw_elems * p->D >= (1ull << 32)) return fail(QD_ERR_UNSUPPORTED, "tile too large");
@@ -2100,13 +2051,7 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
     if (p->jit_fn || p->fixed)
         snprintf(geo, sizeof geo, "FixedGeo<%u, %u, %u, %u, %u, ..., %u>", p->W, p->S, p->D, p->T, p->geo.G, p->kflags);
     else snprintf(geo, sizeof geo, "DynGeo");
-    const char *kn = (p->kflags & kGeoSparkDirect) && p->jit_fn ? "qd::k_spark0"
-                   : (p->kflags & kGeoSparkReg) && p->jit_fn ? "qd::k_spark2"
-                   : p->spark ? "qd::k_spark"
-                   : ((p->kflags & kGeoPipe3) && (p->kflags & kGeoStream) && (p->jit_fn || p->fixed)) ? "qd::k_chain_pipe3s"
-                   : ((p->kflags & kGeoPipe3) && (p->jit_fn || p->fixed)) ? "qd::k_chain_pipe3"
-                   : ((p->kflags & kGeoPipe) && p->jit_fn) ? "qd::k_chain_pipe" : "qd::k_chain";
-    snprintf(buf, cap, "%s<fmt %d, nco %d, %s>, %d threads, %s", kn, fmt, p->nco, geo, p->launch_nt,
+    snprintf(buf, cap, "%s<fmt %d, nco %d, %s>, %d threads, %s", kFamilies[plan_family(p)].name, fmt, p->nco, geo, p->launch_nt,
              p->jit_fn ? "plan-time build" : (p->fixed || p->spark ? "built-in" : "generic"));
     return QD_OK;
 }
@@ -2192,18 +2137,15 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
     uint64_t cw = target_bytes / (step * bps ? step * bps : 1);
     if (cw < p->geo.G) cw = p->geo.G;
     cw = (cw / p->geo.G) * p->geo.G;
-    if ((p->kflags & (kGeoFastP1 | kGeoPipe3 | kGeoSpark)) && (p->jit_fn || p->fixed || p->spark)) {
+    if (plan_on_rows(p)) {
         // row-aligned kernels: a launch whose first window is off the row grid goes to the per-sample kernel (launch_chain), so
         // chunks start on windows that are multiples of lcm(G, ROW / gcd(ROW, S D))
         const uint64_t ROW = (uint64_t)p->nt * spl_of(p->d.format);
-        uint64_t a = ROW, b = step % ROW; while (b) { const uint64_t t = a % b; a = b; b = t; }
-        const uint64_t wa = ROW / a;                                    // windows per row-grid period
-        uint64_t g = p->geo.G, h = wa; while (h) { const uint64_t t = g % h; g = h; h = t; }
-        uint64_t unit = (uint64_t)p->geo.G / g * wa;                    // lcm
+        const uint64_t wa = ROW / ct_gcd(ROW, step % ROW);              // windows per row-grid period
+        uint64_t unit = (uint64_t)p->geo.G / ct_gcd(p->geo.G, wa) * wa; // lcm
         uint64_t grid = wa;
         if (p->spark_R > 1) {                                           // interleaved launches: chunks start where every launch's first window sits on its grid
-            uint64_t a2 = unit, b2 = p->phase_unit; while (b2) { const uint64_t t = a2 % b2; a2 = b2; b2 = t; }
-            unit = unit / a2 * p->phase_unit;
+            unit = unit / ct_gcd(unit, p->phase_unit) * p->phase_unit;
             grid = p->phase_unit;
         }
         if (first_window % grid == 0 && cw >= unit) cw = (cw / unit) * unit;
@@ -2821,7 +2763,7 @@ int qd_take_fft(const qd_c32 *in, uint64_t in_first, size_t n_in, uint64_t sampl
     }
     if (is_pow2(W)) {
         // rustfft's planner gives a power-of-two length to its Radix4 as well: the chain kernel's FFT (bit-exact against
-        // the oracle's restatement), rows gathered at irregular offsets by the per-sample kernel
+        // the oracle's own copy), rows gathered at irregular offsets by the per-sample kernel
         std::shared_ptr<CachedPlan> c;
         rc = cached_fft_plan(W, W, 1, &c);
         if (rc) return rc;

@@ -144,3 +144,24 @@ def test_builtin_kernels_do_not_spill(engine):
     bad = {k: v for k, v in bad.items() if not ("FixedGeo" in k and v.get("VGPRs Spill", 0) <= 2 and v.get("ScratchSize", 0) <= 16)}       # (the bound above)
     assert not bad, bad
     assert all(v.get("SGPRs Spill", 0) <= 160 for v in generic.values()), {k: v for k, v in generic.items() if v.get("SGPRs Spill", 0) > 160}
+
+
+def test_geometry_rules_live_in_one_host_clean_header(tmp_path):
+    """quadrs_amd/csrc/qd_geometry.h is the one statement of the chain kernels' geometry rules: plain C++17 that the host compiler
+    accepts on its own and the only place a kGeo* flag bit is defined; the host source no longer speaks of restating the kernels'
+    conditions (a word check: that old and new agree is shown by comparing plans and code against the parent commit)."""
+    import subprocess
+    csrc = os.path.join(ROOT, "quadrs_amd", "csrc")
+    tu = tmp_path / "only_geometry.cpp"
+    tu.write_text('#include "qd_geometry.h"\nstatic_assert(qd::family_of(qd::kGeoPipe3 | qd::kGeoStream) == qd::kFamPipe3s, "decode");\n')
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", csrc, str(tu)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    product = [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(ROOT, "quadrs_amd")) for f in fs if f.endswith((".h", ".hip", ".cpp", ".py"))]
+    product += [os.path.join(ROOT, "include", "quadrs_hip.h")]
+    defs = {}
+    for path in product:
+        for name in re.findall(r"\b(kGeo[A-Z]\w*) =", open(path, encoding="utf-8").read()):
+            defs.setdefault(name, []).append(os.path.relpath(path, ROOT))
+    assert len(defs) >= 22, sorted(defs)
+    assert all(where == [os.path.join("quadrs_amd", "csrc", "qd_geometry.h")] for where in defs.values()), defs
+    assert "restate" not in open(os.path.join(csrc, "quadrs_hip.hip"), encoding="utf-8").read()
