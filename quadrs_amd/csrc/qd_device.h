@@ -97,8 +97,11 @@ __device__ __forceinline__ float norm_ref(float2 v) {
 // 1 / d = hi + lo (hi = RN(1/d), lo = RN(1/d - hi): 1/d to 2^-48), q = fma(f, hi, RN(f * lo)).  f hi + RN(f lo) is the quotient to
 // 2^-47 relative and the fma rounds it ONCE; no quotient of these integers lies that close to an f32 rounding boundary unless it is
 // exact (|f 2^k - d m| >= 1 for integers).  Verified against the IEEE quotient for EVERY input of the three formats (256 / 256 /
-// 65536 values; tests/test_unpack_division.py restates the two operations in rational arithmetic; the GPU suite runs every code
-// through the kernels).  Round 4: was q = f RN(1/d) plus a residual step, three operations.
+// 65536 values; tests/test_unpack_division.py restates the two operations in rational arithmetic).  On the GPU,
+// tests/test_gpu_values.py::test_every_sample_code_at_every_load_position runs every code, in I and in Q at every byte offset of a
+// 16-byte load, through the fused kernels' unpack_cs8_at / unpack_cu8_at / unpack_cs16; test_unpack_exhaustive_bit_exact reaches
+// unpack_cs16 through qd_unpack, whose 8-bit forms are the literal divisions.  Round 4: was q = f RN(1/d) plus a residual step,
+// three operations.
 __device__ __forceinline__ float div_small(float f, float hi, float lo) { return __builtin_fmaf(f, hi, f * lo); }
 constexpr float kInv127Hi = 0x1.020408p-7f, kInv127Lo = 0x1.020408p-35f;
 constexpr float kInv255Hi = 0x1.010102p-8f, kInv255Lo = -0x1.fdfdfep-33f;

@@ -982,3 +982,179 @@ def footprint_reference(oracle_chain, stages, sr, W, S, epi, rng, n_total):
         exact = not shifted and epi in (0, 3)
         return ref, (None if exact else rule), (1 if epi in (1, 2) else 4)
     return expect
+
+
+# ------------------------------------------------------------------ value-domain streams (tests/test_gpu_values.py)
+#
+# Streams chosen for their VALUES, not their shape: every sample code of an integer format at every load position
+# (code_stream), power-of-two scaled cf32 (exact while nothing leaves the normal range: slow_bins says which bins the |X| range
+# switch of qd_device.h norm_fast hands to the IEEE form), and runs of exact zeros (zero_runs).  Finite normal-range values and
+# exact zeros only.  tests/test_value_streams_cpu.py holds the builders to their conditions on the oracle alone.
+
+SLOW_LO, SLOW_HI = 2.0 ** -96, 2.0 ** 96       # norm_fast keeps s = x^2 + y^2 in [2^-96, 2^96); everything else is norm_ieee's
+F32_MIN_NORMAL = float(np.finfo(np.float32).tiny)
+
+
+def code_count(fmt):
+    return {1: 256, 2: 256, 3: 65536}[fmt]
+
+
+def cs8_grades():
+    """the 256 cs8 codes (as bytes) in 8 grades by the binade of |value|: {0}, {+-1}, {+-2, +-3}, ... {+-64 ... +-127, -128}.
+    All values of a grade but the last share one ulp, so a one-ulp error on any of them is not absorbed by its neighbours."""
+    v = np.arange(-128, 128)
+    grade = np.where(v == 0, 0, np.minimum(np.floor(np.log2(np.maximum(np.abs(v), 1))).astype(int) + 1, 7))
+    return [v[grade == g].astype(np.int8).view(np.uint8) for g in range(8)]
+
+
+CS16_COMB = sorted(set(range(0, 65536, 127)) | {0x0000, 0x0001, 0x7FFF, 0x8000, 0x8001, 0xFFFF})
+"""cs16 codes that code_stream repeats behind the first 4 * 65536 samples: the edge codes and every 127th.  A cs16 sample is
+-32767.5 + h / 65535, so a one-ulp error (2^-9) on ONE sample moves a FIR output of magnitude ~32767 by tap * 2^-9, less than
+its ulp: it shows only as a flipped rounding, with a chance of about |tap| / 2 per output.  With the 4 occurrences per
+component that 65536 codes leave room for, a lowpass (/4, 40 taps) + W = 32 misses such an error for 52 % of the codes (12 %
+at /1); with the ~70 further occurrences of a 3e5-sample stream's tail it misses 3 of the comb's 1046 (code, component)
+pairs at /4 and none at /1, the control's chain (tests/test_value_streams_cpu.py).  Without a lowpass the FFT's first
+differences are exact and every occurrence shows."""
+
+
+def code_stream(fmt, n, seed):
+    """n samples of integer format fmt (cs8 1 / cu8 2 / cs16 3) as a uint8 array, holding EVERY code of the format in the I and
+    in the Q component at every byte offset modulo 16 of the stream (sample index modulo 8 for the 8-bit formats, modulo 4 for
+    cs16).  By construction, not by chance: the slots of one component at one offset are filled with whole random permutations
+    of the codes, the first permutation first.  cs8 comes in 8 magnitude-graded segments of n // 8 samples (cs8_grades): each
+    segment holds its grade's codes only, small codes among small codes, so a window inside a segment sums values of one
+    binade.  cu8 and cs16 values all sit near -127 / -32767.5 (src/lib.rs:246-255) and need no grading; cs16 needs
+    n >= 4 * 65536 for one occurrence per offset, and the samples behind those repeat the codes of CS16_COMB."""
+    rng = np.random.default_rng(seed)
+    phases = 8 if fmt in (1, 2) else 4
+    codes = np.zeros((n, 2), dtype=np.uint8 if fmt in (1, 2) else "<u2")
+    if fmt == 1:
+        seg = n // 8
+        parts = [(g * seg, n if g == 7 else (g + 1) * seg, gc) for g, gc in enumerate(cs8_grades())]
+    elif fmt == 2:
+        parts = [(0, n, np.arange(256, dtype=np.uint8))]
+    else:
+        assert n >= 4 * 65536, n
+        parts = [(0, 4 * 65536, np.arange(65536).astype("<u2")), (4 * 65536, n, np.array(CS16_COMB, dtype="<u2"))]
+    for a, b, gc in parts:
+        for comp in range(2):
+            for ph in range(phases):
+                slots = np.arange(a + (ph - a) % phases, b, phases)
+                reps = -(-slots.size // gc.size)
+                codes[slots, comp] = rng.permuted(np.tile(gc, (reps, 1)), axis=1).reshape(-1)[:slots.size]
+    return codes.view(np.uint8).reshape(-1)
+
+
+def stream_codes(fmt, data):
+    """(n, 2) integer codes (the raw bytes / little-endian halfwords) of an integer-format stream"""
+    return np.ascontiguousarray(data).view(np.uint8).view(np.uint8 if fmt in (1, 2) else "<u2").reshape(-1, 2).astype(np.int64)
+
+
+def code_coverage(fmt, data, first, count):
+    """occurrences[component, load position, code] inside samples [first, first + count) of the stream: load position = the
+    sample's byte offset modulo 16 in units of one sample (index modulo 8 / modulo 4)"""
+    phases = 8 if fmt in (1, 2) else 4
+    c = stream_codes(fmt, data)[first:first + count]
+    ph = (np.arange(first, first + c.shape[0]) % phases).astype(np.int64)
+    nc = code_count(fmt)
+    return np.stack([np.bincount(ph * nc + c[:, comp], minlength=phases * nc).reshape(phases, nc) for comp in range(2)])
+
+
+def perturb_code(fmt, data, unpacked, code, comp, sign=1):
+    """`unpacked` (oracle.unpack of `data`) with every occurrence of `code` in component comp moved by one ulp (nextafter towards
+    sign * inf); cs8 code 0 unpacks to 0.0, which no ulp moves, and becomes sign * 2^-24 instead, a wrong quotient of plausible
+    size.  Returns (the perturbed copy, the sample indices changed)."""
+    at = np.flatnonzero(stream_codes(fmt, data)[:, comp] == code)
+    x = unpacked.copy()
+    v = x[at, comp]
+    x[at, comp] = np.where(v == 0, np.float32(sign * 2.0 ** -24), np.nextafter(v, np.float32(sign * np.inf)))
+    assert (x[at, comp] != v).all()
+    return x, at
+
+
+def source_block(stages, W, S, w0, n=1):
+    """[lo, hi): the source samples the reference fetches for sink windows [w0, w0 + n): window w reads [w S, w S + W) of the
+    last stage, and a lowpass (D, T) serves outputs [a, b) with one block read [a D, b D + T) of its input (src/filter.rs:68-71)"""
+    lo, hi = w0 * S, (w0 + n - 1) * S + W
+    for kind, arg in reversed(list(stages)):
+        if kind == "lowpass":
+            lo, hi = lo * int(arg[1]), hi * int(arg[1]) + int(arg[2])
+    return lo, hi
+
+
+def windows_reading(stages, W, S, samples, n_windows):
+    """the sorted sink windows < n_windows whose source_block holds one of `samples`"""
+    step = source_block(stages, W, S, 1)[0]
+    span = source_block(stages, W, S, 0)[1]
+    out = set()
+    for s in np.unique(np.asarray(samples, dtype=np.int64)):
+        out.update(range(max(0, -(-(int(s) - span + 1) // step)), min(n_windows, int(s) // step + 1)))
+    return sorted(out)
+
+
+def contiguous_runs(ws):
+    """[(first, count), ...] of a sorted list of integers"""
+    runs = []
+    for w in ws:
+        if runs and runs[-1][0] + runs[-1][1] == w:
+            runs[-1][1] += 1
+        else:
+            runs.append([w, 1])
+    return [tuple(r) for r in runs]
+
+
+def slow_bins(norms):
+    """bins of reference norms whose x^2 + y^2 lies outside [2^-96, 2^96): norm_fast (qd_device.h) hands exactly those to the IEEE
+    form for their range (zeros included).  Judged on the norm: norm^2 is x^2 + y^2 to 2^-23, so bins within that of a limit
+    are counted as neither (returned as the second array)."""
+    s = np.asarray(norms, dtype=np.float64) ** 2
+    edge = (np.abs(s / SLOW_LO - 1) < 2.0 ** -20) | (np.abs(s / SLOW_HI - 1) < 2.0 ** -20)
+    return ((s < SLOW_LO) | (s >= SLOW_HI)) & ~edge, edge
+
+
+def normal_or_zero(a):
+    """every element finite and either 0 or of normal-range magnitude (no subnormal)"""
+    a = np.abs(np.asarray(a, dtype=np.float32))
+    return bool((np.isfinite(a) & ((a == 0) | (a >= np.float32(F32_MIN_NORMAL)))).all())
+
+
+def zero_runs(x, long_run, window_span, seed):
+    """a copy of the cf32 stream x (n, 2) with runs of exact zeros: ONE run of long_run samples from n // 3 on, in four quarters
+    (+0, +0), (-0, +0), (+0, -0), (-0, -0); and short runs of window_span // 3 + 1 samples every 2.5 window spans outside it,
+    which therefore start and end inside a window: in turn both components, I only, Q only, signs alternating.  Returns
+    (stream, mask of the samples with a zero component).  Through _to_format the zeros become cs8 code 0."""
+    rng = np.random.default_rng(seed)
+    n = x.shape[0]
+    x = x.copy()
+    pz, nz = np.float32(0.0), np.float32(-0.0)
+    a = n // 3
+    assert long_run > 0 and a + long_run + 3 * window_span < n, (n, long_run, window_span)
+    q = -(-long_run // 4)
+    for k, (si, sq) in enumerate(((pz, pz), (nz, pz), (pz, nz), (nz, nz))):
+        lo, hi = a + k * q, min(a + (k + 1) * q, a + long_run)
+        x[lo:hi, 0], x[lo:hi, 1] = si, sq
+    short = window_span // 3 + 1
+    step = (5 * window_span) // 2 + int(rng.integers(1, 8))
+    k = 0
+    for s in list(range(window_span // 2, a - window_span - short, step)) + list(range(a + long_run + window_span, n - short, step)):
+        z = nz if k % 2 else pz
+        if k % 3 != 2:
+            x[s:s + short, 0] = z
+        if k % 3 != 1:
+            x[s:s + short, 1] = z
+        k += 1
+    return x, (x[:, 0] == 0) | (x[:, 1] == 0)
+
+
+def mixed_scale(norms, side=1):
+    """(k, windows): the power of two (k > 0 with side = 1, k < 0 with side = -1) that puts slow and fast bins (slow_bins) inside
+    the same window in the most windows of the reference norms `norms` (n_windows, W), and that count.  Chosen from the
+    reference alone."""
+    base = np.asarray(norms, dtype=np.float64)
+    best = (side * 48, -1)
+    for k in range(30, 70):
+        slow, edge = slow_bins(base * 2.0 ** (side * k))
+        both = int((slow.any(axis=1) & (~slow & ~edge).any(axis=1)).sum())
+        if both > best[1]:
+            best = (side * k, both)
+    return best
