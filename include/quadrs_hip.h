@@ -49,7 +49,7 @@ typedef enum {
     QD_EPI_NORMS_F32 = 0,    /* W f32: hypot(re,im) in fftshift order (src/fft.rs:48-53) */
     QD_EPI_GLYPH_U8 = 1,     /* W u8: 0=' ' 1..7='▁'..'▇' 8='█' 255=reference would panic (src/fft.rs:54-60) */
     QD_EPI_BUCKET2_U8 = 2,   /* 1 u8: freq_levels digit (src/fft.rs:95-97) */
-    QD_EPI_CF32_BLOCKS = 3   /* the write sink (do_write, src/lib.rs:199-210): no FFT; a "window" is one full
+    QD_EPI_CF32_BLOCKS = 3,  /* the write sink (do_write, src/lib.rs:199-210): no FFT; a "window" is one full
                                 LowPass::read_at block of `width` decimated samples (0x1000 for do_write, a power
                                 of two), `stride` is ignored, the output is width qd_c32 per block with the block's
                                 own tail truncation.  n_windows counts the FULL blocks, floor((n-T)/(width*D));
@@ -57,6 +57,12 @@ typedef enum {
                                 Behind a cascade (qd_plan_create_stages) a block is the outer read_at(b*width, width)
                                 of the nested stages, every stage truncating against its own read of it; n_windows
                                 counts the blocks whose source span fits the stream (see the stage lists below). */
+    QD_EPI_MARK_U8 = 4       /* 1 u8 per spark_fft window (the loop of src/fft.rs:28,65: n_windows and qd_plan_src_range are the glyph
+                                sink's): 0 when the reference would print the row blank, i.e. every bin has norm < min in f32
+                                (src/fft.rs:54-55; min = range_min with has_range, else 0.08f; range_max plays no part), 1 otherwise.
+                                A NaN norm or a NaN min compares false: 1.  Equivalently any(code != 0) over the W codes of
+                                QD_EPI_GLYPH_U8 for the same plan parameters: the blank / not-blank step of the README's "OOK in
+                                sed" example, the input of qd_bits_scan.  Needs no lowpass, takes any stride. */
 } qd_epilogue;
 
 const char *qd_last_error(void);
@@ -89,6 +95,16 @@ int qd_shift(qd_c32 *buf, size_t n, uint64_t abs_off, double ratio, int mem);
 /* lowpass_filter(cutoff_from_frequency(f, sr) as f32, size), src/filter.rs:29-31,86-105,126-128.
  * Host arithmetic with the platform libm, exactly as the reference does it (O(size), once). */
 int qd_lowpass_design(uint64_t frequency, uint64_t sample_rate, size_t size, float *taps);
+
+/* bits::scan, src/bits.rs:3-55 (host arithmetic, f64): run-length decode n marks (0 / non-0, e.g. a QD_EPI_MARK_U8 output) at
+ * `scale` marks per bit.  half = round(scale / 2) (halves away from zero); a run of the expected value (0 first, flipping after every
+ * accepted run) ends where the first stretch of more than `half` wrong values began; an accepted run (longer than half) emits
+ * round(run / scale) copies of the value into bits[] (0 / 1) and adds |run / scale - rounded| to *error, in order.
+ * QD_ERR_PANIC: a run of at most `half` ends before the end of the data — the reference `continue`s without flipping (:9-15), its next
+ * run_of returns 0 and the loop never ends; *produced and *error hold what had been emitted up to there.
+ * QD_ERR_INVALID: scale not finite or <= 0; or more than `cap` bits, with *produced = the count needed (bits[] holds the first cap;
+ * this outranks QD_ERR_PANIC). */
+int qd_bits_scan(const uint8_t *marks, size_t n, double scale, uint8_t *bits, size_t cap, size_t *produced, double *error);
 
 /* LowPass::read_at on an already fetched raw block, src/filter.rs:68-83 + complex_convolve
  * :107-124: out[k] = sum_{j<jmax(k)} raw[k*D + c + j]*taps[j], c = T - T/2,

@@ -12,7 +12,7 @@ MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED = 0, 1, 2
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_SPECIALISE, KERNEL_NO_PLAN_TIME = 0, 1, 2, 3
 MODE_EXACT, MODE_FAST = 0, 1
 MAX_SHARDS = 16
-EPI_NORMS_F32, EPI_GLYPH_U8, EPI_BUCKET2_U8, EPI_CF32_BLOCKS = 0, 1, 2, 3
+EPI_NORMS_F32, EPI_GLYPH_U8, EPI_BUCKET2_U8, EPI_CF32_BLOCKS, EPI_MARK_U8 = 0, 1, 2, 3, 4
 
 # every symbol include/quadrs_hip.h declares
 SYMBOLS = [
@@ -24,7 +24,7 @@ SYMBOLS = [
     "qd_set_stream", "qd_release_workspaces", "qd_plan_create_ex", "qd_plan_shard_info", "qd_plan_run_sharded",
     "qd_plan_run_sharded_device", "qd_plan_get_stats", "qd_host_alloc", "qd_host_free", "qd_host_register",
     "qd_host_unregister", "qd_plan_kernel_name", "qd_plan_create_stages", "qd_plan_get_stage_taps",
-    "qd_plan_complete_windows", "qd_stages_geometry",
+    "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan",
 ]
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
@@ -148,6 +148,7 @@ def lib():
             "qd_plan_get_stage_taps": (i32, [vp, C.c_uint32, vp, sz]),
             "qd_plan_complete_windows": (i32, [vp, C.POINTER(u64)]),
             "qd_stages_geometry": (i32, [C.POINTER(ChainDesc), C.POINTER(Stage), sz, C.POINTER(PlanInfo), C.POINTER(u64)]),
+            "qd_bits_scan": (i32, [vp, sz, f64, vp, sz, C.POINTER(sz), C.POINTER(f64)]),
         }
         for name, (res, args) in sig.items():
             try:

@@ -12,6 +12,7 @@
 // falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the reference's read_at()
 // computes.
 #include <cerrno>
+#include <cmath>
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -94,7 +95,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -103,6 +104,7 @@ struct Op {
     uint64_t lp_freq = 0, decimate = 8; size_t size = 40;               // lowpass
     size_t width = 128; uint64_t stride = 128; bool has_range = false; float rmin = 0, rmax = 0;   // sparkfft / bucket
     size_t levels = 2;
+    bool has_scan = false; double scan = 0.0;                           // marks -scan SCALE (bits::scan, src/bits.rs)
     bool overwrite = false; std::string prefix;                         // write
 };
 
@@ -216,6 +218,23 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             op.stride = f ? parse_si_u64(v) : op.width;
             v = take(m, "by", &f);
             if (!f || v != "freq") bail("must bucket -by freq");
+            ensure_empty(m);
+        } else if (cmd == "marks") {
+            // not in the reference's grammar: the blank / not-blank byte per sparkfft row that its README derives with sed
+            // ("Worked example: OOK in sed"), and optionally bits::scan over it
+            auto m = no_duplicates(raw);
+            op.kind = OP_MARKS;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            v = take(m, "min", &f);
+            if (f) { op.has_range = true; op.rmin = strtof(v.c_str(), nullptr); op.rmax = 1.0f; }      // (the maximum plays no part)
+            v = take(m, "scan", &f);
+            if (f) {
+                op.has_scan = true; op.scan = strtod(v.c_str(), nullptr);
+                if (!std::isfinite(op.scan) || !(op.scan > 0.0)) bail("marks -scan takes a scale > 0");
+            }
             ensure_empty(m);
         } else if (cmd == "write") {
             auto m = no_duplicates(raw);
@@ -402,6 +421,32 @@ struct DeviceBuf {
     ~DeviceBuf() { if (p) qd_device_free(p); }
 };
 
+int sink_epilogue(const Op &sink) {
+    return sink.kind == OP_BUCKET ? QD_EPI_BUCKET2_U8 : (sink.kind == OP_MARKS ? QD_EPI_MARK_U8 : QD_EPI_GLYPH_U8);
+}
+
+// the `marks` sink's output: one line of 0 / 1 digits, or with -scan the bits of bits::scan over them and its error on a second line
+void print_marks(const uint8_t *marks, uint64_t n, const Op &sink) {
+    if (!sink.has_scan) {
+        std::string digits;
+        for (uint64_t w = 0; w < n; ++w) digits.push_back((char)('0' + (marks[w] ? 1 : 0)));
+        printf("%s\n", digits.c_str());
+        return;
+    }
+    std::vector<uint8_t> bits((size_t)n + 1);
+    size_t produced = 0;
+    double error = 0.0;
+    int rc = qd_bits_scan(marks, (size_t)n, sink.scan, bits.data(), bits.size(), &produced, &error);
+    if (rc == QD_ERR_INVALID && produced > bits.size()) {                // (a scale below 1 emits more bits than marks)
+        bits.resize(produced);
+        rc = qd_bits_scan(marks, (size_t)n, sink.scan, bits.data(), bits.size(), &produced, &error);
+    }
+    qd_check(rc, "scan");                                                // the non-terminating case: the library's message, exit 1
+    std::string digits;
+    for (size_t b = 0; b < produced; ++b) digits.push_back((char)('0' + bits[b]));
+    printf("%s\n%.17g\n", digits.c_str(), error);
+}
+
 // sparkfft / bucket through ONE fused plan over the whole file — or over a `gen` stream that is produced on the device
 // (src/gen.rs:30-47) and never crosses PCIe: only the glyph codes / digits come back
 // returns false when the library has no fused plan for the chain (QD_ERR_UNSUPPORTED: e.g. overlapping windows whose FIR input exceeds one
@@ -432,7 +477,7 @@ bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
         if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
     }
     d.width = sink.width; d.stride = sink.stride;
-    d.epilogue = sink.kind == OP_BUCKET ? QD_EPI_BUCKET2_U8 : QD_EPI_GLYPH_U8;
+    d.epilogue = sink_epilogue(sink);
     d.has_range = sink.has_range; d.range_min = sink.rmin; d.range_max = sink.rmax;
     if (sink.kind == OP_SPARKFFT) printf("sparkfft sample_rate=%" PRIu64 "\n", out_rate);   // printed before any read (src/fft.rs:19)
     qd_plan *plan = nullptr;
@@ -489,7 +534,8 @@ bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
         samples.read_exact_at(complete * sink.stride, buf.data(), sink.width);       // fails: the reference's error
         bail("complete-window count disagrees with the iterator chain");
     }
-    if (sink.kind != OP_SPARKFFT) {
+    if (sink.kind == OP_MARKS) print_marks(out.data(), info.n_windows, sink);
+    else if (sink.kind != OP_SPARKFFT) {
         std::string digits;
         for (uint64_t w = 0; w < info.n_windows; ++w) digits.push_back((char)('0' + out[w]));
         printf("%s\n", digits.c_str());                                   // src/lib.rs:144-158
@@ -505,7 +551,7 @@ std::vector<uint8_t> sink_batch(const qd_c32 *buf, uint64_t nb, size_t W, const 
     // len such that the sink's own loop yields exactly nb windows at stride W
     d.n_samples = sink.kind == OP_BUCKET ? (nb + 1) * W : nb * W + 1;
     d.width = W; d.stride = W;
-    d.epilogue = sink.kind == OP_BUCKET ? QD_EPI_BUCKET2_U8 : QD_EPI_GLYPH_U8;
+    d.epilogue = sink_epilogue(sink);
     d.has_range = sink.has_range; d.range_min = sink.rmin; d.range_max = sink.rmax;
     qd_plan *plan = nullptr;
     qd_check(qd_plan_create(&d, &plan), "plan");
@@ -532,6 +578,7 @@ void run_iter_sink(const Samples &s, const Op &sink, bool header_printed = false
     const uint64_t batch = 4096;
     std::vector<qd_c32> buf(batch * W);
     std::string digits;
+    std::vector<uint8_t> marks;
     for (uint64_t w0 = 0; w0 < nwin; w0 += batch) {
         uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
         for (uint64_t i = 0; i < nb; ++i) s.read_exact_at((w0 + i) * S, buf.data() + i * W, W);
@@ -549,11 +596,14 @@ void run_iter_sink(const Samples &s, const Op &sink, bool header_printed = false
                 line += "\xE2\x94\x82\n";
                 fwrite(line.data(), 1, line.size(), stdout);
             }
+        } else if (sink.kind == OP_MARKS) {
+            marks.insert(marks.end(), out.begin(), out.begin() + nb);
         } else {
             for (uint64_t w = 0; w < nb; ++w) digits.push_back((char)('0' + out[w]));
         }
     }
     if (sink.kind == OP_BUCKET) printf("%s\n", digits.c_str());
+    if (sink.kind == OP_MARKS) print_marks(marks.data(), marks.size(), sink);
 }
 
 // do_write (src/lib.rs:178-213).  When the chain is  from [shift] lowpass , or a cascade the library fuses
@@ -624,6 +674,7 @@ void usage() {
             " lowpass [-power 20] [-decimate 8] FREQUENCY \\\n"
             "sparkfft [-width 128] [-stride =width] [-range MIN:MAX] \\\n"
             "  bucket [-width 128] [-stride =width] -by freq COUNT \\\n"
+            "   marks [-width 128] [-stride =width] [-min 0.08] [-scan SCALE] \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
             "\n\nFormat for FREQUENCY, SAMPLE_RATE, and other suffixes: 123, 123k, 123M, 123G\n");
@@ -657,6 +708,7 @@ int main(int argc, char **argv) {
                 case OP_LOWPASS: printf("lowpass frequency=%llu decimate=%llu size=%zu\n", (unsigned long long)op.lp_freq, (unsigned long long)op.decimate, op.size); break;
                 case OP_SPARKFFT: printf("sparkfft width=%zu stride=%llu range=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no"); break;
                 case OP_BUCKET: printf("bucket width=%zu stride=%llu levels=%zu\n", op.width, (unsigned long long)op.stride, op.levels); break;
+                case OP_MARKS: printf("marks width=%zu stride=%llu min=%s scan=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no", op.has_scan ? "yes" : "no"); break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 }
             }
@@ -694,7 +746,8 @@ int main(int argc, char **argv) {
                 break;
             case OP_SPARKFFT:
             case OP_BUCKET:
-                if (!samples) bail(op.kind == OP_SPARKFFT ? "sparkfft requires an input" : "bucket -by freq requires an input");
+            case OP_MARKS:
+                if (!samples) bail(op.kind == OP_SPARKFFT ? "sparkfft requires an input" : op.kind == OP_MARKS ? "marks requires an input" : "bucket -by freq requires an input");
                 if (op.kind == OP_BUCKET && op.levels != 2) bail("only supporting two levels for now");
                 if (cs.fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
                     cs.cascade = !chain_clean;

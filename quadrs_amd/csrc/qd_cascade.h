@@ -212,6 +212,8 @@ __global__ __launch_bounds__(kCascadeThreads) void k_cascade(const CascadeParams
                     for (uint32_t b = W / 2; b < W; ++b) second = second + nb[b];
                     reinterpret_cast<uint8_t *>(C.out)[wrel] = first < second ? 0 : 1;
                 }
+            } else if (C.epi == QD_EPI_MARK_U8) {
+                wave_mark_epilogue_fn<DynGeo>(C, geo, [&](uint32_t b) { return fb[b]; }, reinterpret_cast<uint8_t *>(C.out) + wrel, 1, tid);
             } else if (C.epi == QD_EPI_NORMS_F32) {
                 float *outf = reinterpret_cast<float *>(C.out) + wrel * W;
                 for (uint32_t b = tid; b < W; b += 64) outf[b] = norm_ref(fb[b ^ (W >> 1)]);

@@ -1216,6 +1216,35 @@ __device__ __forceinline__ void wave_bucket_epilogue_fn(const ChainParams &P, co
     }
 }
 
+// The mark sink (QD_EPI_MARK_U8) on transformed windows parked in LDS: byte w is 0 when every |X| of window w is below `min` — the row
+// the reference prints blank (src/fft.rs:54-55) — and 1 otherwise; a NaN norm or a NaN min compares false and marks.  An OR has no
+// order, so nothing is parked and summed as freq_levels is: from W = 64 up a wave takes a window, a lane ORs its W / 64 bins and a
+// ballot combines the lanes; below, a lane owns a window.  Either way a window never leaves its wave, so there is no LDS word and no
+// barrier: callers with several waves hand each a share of the units (unit0, unit_step: windows for W >= 64, runs of 64 windows
+// below).  bin(o): element o of the buffer, window o >> logW, bins in any order.
+template <class GeoT, class BinT>
+__device__ __forceinline__ void wave_mark_epilogue_fn(const ChainParams &P, const GeoT &geo, BinT bin, uint8_t *outw /* byte of the buffer's window 0 */,
+                                                      uint32_t pg, uint32_t lane, uint32_t unit0 = 0, uint32_t unit_step = 1) {
+    const uint32_t W = geo.W, logW = geo.logW;
+    if (W >= 64) {
+        for (uint32_t g = unit0; g < pg; g += unit_step) {
+            bool m = false;
+            for (uint32_t k = lane; k < W; k += 64) m |= !(norm_ref(bin((g << logW) + k)) < P.rmin);
+            const bool any = __builtin_amdgcn_ballot_w64(m) != 0;
+            if (lane == 0) outw[g] = any ? 1 : 0;
+        }
+    } else {
+        for (uint32_t wl = 64 * unit0 + lane; wl < pg; wl += 64 * unit_step) {
+            bool m = false;
+            for (uint32_t k = 0; k < W; ++k) m |= !(norm_ref(bin((wl << logW) + k)) < P.rmin);
+            outw[wl] = m ? 1 : 0;
+        }
+    }
+}
+
+// sinks whose epilogue wants the whole window on ONE wave (the ordered half sums; the ballot): not the four-wave quad_fft_epilogue
+__device__ __forceinline__ bool one_wave_sink(uint32_t epi) { return epi == 2 || epi == 4; }
+
 template <class GeoT, uint32_t KB = 0 /* bucket epilogue: bins per lane the caller's buffer may hold (0: from the geometry) */,
           int PART = 0 /* 0: the whole transform + epilogue; 1: the base butterflies only; 2: the radix-4 layers + epilogue of windows whose base pass is done;
                           3: base butterflies + layers, no epilogue (the caller has its own) */>
@@ -1279,6 +1308,8 @@ __device__ __forceinline__ void wave_fft_epilogue_fn(const ChainParams &P, const
     if (P.epi == 2) {
         constexpr uint32_t K = KB ? KB : (GeoT::kFixed ? (GeoT::G_ct * GeoT::W_ct + 63) / 64 : 1);
         wave_bucket_epilogue_fn<GeoT, K>(P, geo, fbp, pw0, pg, lane);
+    } else if (P.epi == 4) {
+        wave_mark_epilogue_fn<GeoT>(P, geo, [&](uint32_t o) { return fbp[o]; }, reinterpret_cast<uint8_t *>(P.out) + wrel, pg, lane);
     } else {
         float *outf = reinterpret_cast<float *>(P.out) + (wrel << geo.logW);
         uint8_t *outb = reinterpret_cast<uint8_t *>(P.out) + (wrel << geo.logW);
@@ -1456,6 +1487,8 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     // One wave transforms the parked tile and writes its output: LDS operations of one wave execute in order, so the passes
     // are separated by a compiler-level fence only.
     auto wave_fft_epilogue = [&](float2 *fbp, uint64_t pw0, uint32_t pg) { wave_fft_epilogue_fn<GeoT>(P, geo, twl, fbp, pw0, pg, tid); };
+    // phase 4 parks the tile's norms in the raw region for these sinks: the bucket sink, and the mark sink of the runtime-geometry kernels
+    auto parks_norms = [](uint32_t epi) { return epi == 2 || (!GeoT::kFixed && epi == 4); };
     // The same on FOUR waves, for one long window (W >= 256): Radix4's last layer combines four contiguous sub-transforms of W/4
     // points, and everything below it stays inside one sub-transform — so wave v transforms quarter v on its own (no workgroup
     // barrier, the FIR waves run on), the four meet ONCE at an arrival counter in LDS, and each then takes a quarter of the last
@@ -1717,7 +1750,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     fb_cur[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
                 }
             } else if (kHalf && half != 0) {                   // the previous window was transformed beside this window's first pass
-            } else if (kQuadFft && P.epi != 2) {               // one long window: four spare waves share its FFT + epilogue
+            } else if (kQuadFft && !one_wave_sink(P.epi)) {   // one long window: four spare waves share its FFT + epilogue
                 if ((tid >> 6) < FL / 64 + 4 && dprev_valid) {
                     __builtin_amdgcn_s_setprio(3);
                     quad_fft_epilogue(fb_prev, dprev_w0, (tid >> 6) - FL / 64);
@@ -1984,7 +2017,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             wq[0] = (uint32_t)t2; wq[1] = (uint32_t)(t2 >> 32);
         }
         const TileGeo tg_next = tile_geo<FMT, NT>(P, geo, tile_n, n_tiles);
-        const uint32_t batch_lim = (kBatch > 1 && P.epi != 2 && !cf32_out) ? kBatch : 1u;   // the bucket / write sinks flush every tile
+        const uint32_t batch_lim = (kBatch > 1 && !parks_norms(P.epi) && !cf32_out) ? kBatch : 1u;   // the sinks that park norms and the write sink flush every tile
         const bool flush = bslot >= batch_lim || !tg_next.valid;                             // wave-uniform
         __syncthreads();
         tile = tile_n;
@@ -2070,20 +2103,32 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             // do_write / LowPass::read_at output (src/lib.rs:206-209): the decimated cf32 samples themselves
             float2 *outc = reinterpret_cast<float2 *>(P.out) + (wrel << logW);
             for (uint32_t o = tid; o < n_out_s; o += NT) outc[o] = fbs[o];
-        } else if (P.epi == 2) {
-            // freq_levels (src/fft.rs:95-97): sequential f32 sums of |X[k]| over each half
+        } else if (parks_norms(P.epi)) {
+            // freq_levels (src/fft.rs:95-97): sequential f32 sums of |X[k]| over each half.  In the runtime-geometry kernels the mark sink
+            // (src/fft.rs:54-55: is any norm at or above `min`) walks the same parked norms: a ballot of its own costs them scalar
+            // registers they do not have (test_builtin_kernels_do_not_spill bounds their spills), the shared walk one compare per bin.
             float *nb = reinterpret_cast<float *>(raw);       // raw tile is dead now
             for (uint32_t o = tid; o < n_out_s; o += NT) nb[o] = norm_ref(fbs[o]);
             __syncthreads();
             if (tid < g_cnt) {
                 const float *p = nb + (tid << logW);
                 float first = 0.f, second = 0.f;
-                for (uint32_t k = 0; k < W / 2; ++k) first = first + p[k];
-                for (uint32_t k = W / 2; k < W; ++k) second = second + p[k];
+                bool mark = false;
+                // (one walk for both sinks: a loop of the mark sink's own, behind a test of P.epi, costs these kernels 10-25 more
+                // scalar spills — measured — and takes them past the bound; the bucket sink pays one compare per bin it does not use)
+                for (uint32_t k = 0; k < W / 2; ++k) { first = first + p[k]; if constexpr (!GeoT::kFixed) mark |= !(p[k] < P.rmin); }
+                for (uint32_t k = W / 2; k < W; ++k) { second = second + p[k]; if constexpr (!GeoT::kFixed) mark |= !(p[k] < P.rmin); }
                 uint32_t tt = tid;
                 asm volatile("" : "+v"(tt));       // opaque lane offset: no hoisted (and spilled) per-lane output pointer, see below
-                reinterpret_cast<uint8_t *>(P.out)[wrel + tt] = first < second ? 0 : 1;
+                reinterpret_cast<uint8_t *>(P.out)[wrel + tt] = (GeoT::kFixed || P.epi == 2) ? (first < second ? 0 : 1) : (mark ? 1 : 0);
             }
+        } else if (GeoT::kFixed && P.epi == 4) {
+            // the mark sink in the shape-specialised kernels: each wave takes whole windows (runs of 64 windows below W = 64), so the OR
+            // never leaves a wave, nothing is parked and the next tile's phase 1 needs no barrier
+            uint32_t ln = tid & 63u;
+            asm volatile("" : "+v"(ln));           // opaque lane offset, as below
+            wave_mark_epilogue_fn<GeoT>(P, geo, [&](uint32_t o) { return fbs[o]; }, reinterpret_cast<uint8_t *>(P.out) + wrel, n_out_s >> logW, ln,
+                                        __builtin_amdgcn_readfirstlane(tid >> 6), NT / 64);
         } else {
             float *outf = reinterpret_cast<float *>(P.out) + (wrel << logW);     // uniform base
             uint8_t *outb = reinterpret_cast<uint8_t *>(P.out) + (wrel << logW);
@@ -2109,14 +2154,14 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
         // No barrier here for the norm / glyph / cf32 epilogues: they only read fb, the next tile's phase 1 only
         // writes the raw region, and barrier 1 of the next tile orders everything before fb (or dec/trc) is
         // written again.  The bucket epilogue parks its norms IN the raw region, so it keeps the barrier.
-        if (P.epi == 2) __syncthreads();
+        if (parks_norms(P.epi)) __syncthreads();
         QD_STAMP_AT(7);
         QD_STAMP_TILE();
         tg = tg_next;
     }
     if constexpr (kDefer) {
         constexpr uint32_t GW = GeoT::G_ct * GeoT::W_ct, GWP = kHalf ? GeoT::kHalfOut : GW, FL = GeoT::kPackedTile ? GWP / 2 : GWP;
-        if (kQuadFft && P.epi != 2) {
+        if (kQuadFft && !one_wave_sink(P.epi)) {
             if (dprev_valid && (tid >> 6) >= FL / 64 && (tid >> 6) < FL / 64 + 4) quad_fft_epilogue(fb0 + (size_t)(dpar ^ 1u) * GW, dprev_w0, (tid >> 6) - FL / 64);
         } else
         if (dprev_valid && (tid >> 6) == FL / 64) wave_fft_epilogue(fb0 + (size_t)(dpar ^ 1u) * GW, dprev_w0, dprev_gcnt);
@@ -3120,6 +3165,9 @@ __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512),
                                 for (uint32_t k = W / 2; k < W; ++k) second = second + q[k];
                                 reinterpret_cast<uint8_t *>(P.out)[wrel + wl] = first < second ? 0 : 1;
                             }
+                        } else if (P.epi == 4) {
+                            wave_mark_epilogue_fn<GeoT>(P, geo, [&](uint32_t o) { return spark_ld2(fb + ((o ^ SZ::delta(o)) << 3)); },
+                                                        reinterpret_cast<uint8_t *>(P.out) + wrel, g1 - g0, lane);
                         } else {
                             float *outf = reinterpret_cast<float *>(P.out) + (wrel << logW);
                             uint8_t *outb = reinterpret_cast<uint8_t *>(P.out) + (wrel << logW);
@@ -3566,7 +3614,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
         // the same number of stores through an EMPTY descriptor: the range check drops them, the counter sees them.
         const auto none = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t *>(P.out), 0, 0, 0x00020000);
 #pragma unroll
-        for (uint32_t q = 0; q < 4 * NBF; ++q) {
+        for (uint32_t q = 0; q < (EPI == 4 ? 1u : 4 * NBF); ++q) {          // (the mark sink: one store per tile)
             if constexpr (EPI == 0) __builtin_amdgcn_raw_buffer_store_b32(0u, none, (int)(lane * 4 + q * 256), 0, 2);       // (distinct addresses: identical stores would be merged)
             else __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, none, (int)(lane + q * 64), 0, 2);
         }
@@ -3576,7 +3624,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
         const uint64_t tile_n = tile + n_waves;
         const uint64_t w0 = P.first_window + tile * GW, left_w = P.first_window + P.n_windows - w0;
         const uint32_t g_cnt = left_w < GW ? (uint32_t)left_w : GW;
-        constexpr uint32_t OBW = EPI == 0 ? 4u * W : W;                     // output bytes per window (norms f32 / glyph u8)
+        constexpr uint32_t OBW = EPI == 0 ? 4u * W : (EPI == 4 ? 1u : W);   // output bytes per window (norms f32 / glyph u8 / mark u8)
         const uint32_t RS = P.out_row_stride ? P.out_row_stride : 1u;      // rows between this launch's windows (interleaved launches of overlapping windows)
         const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t *>(P.out) + (w0 - P.out_window0) * RS * OBW, 0,
                                                              g_cnt ? ((g_cnt - 1) * RS + 1) * OBW : 0u, 0x00020000);
@@ -3629,6 +3677,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
         __builtin_amdgcn_sched_barrier(0);
         // ---- radix-4 layers in place; the last one feeds the epilogue from registers
         uint32_t cols = base, log_cols = GeoT::log_base, tw_off = 0;
+        uint32_t marks = 0;                     // the mark sink: bit gw set when window gw of the tile has a bin at or above `min` (wave-uniform)
         uint32_t lo = lane;
         asm volatile("" : "+v"(lo));            // opaque per tile: the butterflies' LDS / output addresses are rebuilt, not hoisted out of the tile loop and spilled
 #pragma unroll
@@ -3699,6 +3748,16 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
 #if defined(QD_SPARK_ABL) && (QD_SPARK_ABL & 1)
                         if (nm[0] + nm[1] + nm[2] + nm[3] != 12345.678f) continue;     // timing-only ablation: no output stores
 #endif
+                        if constexpr (EPI == 4) {
+                            // the mark sink (src/fft.rs:54-55): the OR of the lane's four bins, then of the window's lanes by ballot — a pass
+                            // of 64 butterflies is one window (cols >= 64) or two (cols == 32: a half-wave each).  Nothing is stored here.
+                            const bool m = !(nm[0] < P.rmin) | !(nm[1] < P.rmin) | !(nm[2] < P.rmin) | !(nm[3] < P.rmin);
+                            const uint64_t b = __builtin_amdgcn_ballot_w64(m);
+                            const uint32_t g_lo = (64 * (k0 + kk)) >> log_cols;            // window of lane 0's butterfly
+                            if (cols >= 64) marks |= (b != 0 ? 1u : 0u) << g_lo;
+                            else marks |= (((uint32_t)b != 0 ? 1u : 0u) | ((uint32_t)(b >> 32) != 0 ? 2u : 0u)) << g_lo;
+                            continue;
+                        }
                         // Stores through a per-tile buffer descriptor that ends with the tile's last VALID window: a store past it (the
                         // short last tile of a launch) is dropped by the range check, so the tile loop has no store branch, every tile
                         // issues the same number of vector-memory operations and the waits for the prefetched rows stay COUNTED
@@ -3721,6 +3780,10 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
         if constexpr (EPI == 2) {                                           // freq_levels: |X| through LDS, one lane per window sums the halves in order (src/fft.rs:95-97)
             wsync();
             wave_bucket_epilogue_fn<GeoT, TS / 64>(P, geo, fbw, w0, g_cnt, lane);
+        }
+        if constexpr (EPI == 4) {                                           // lane gw stores window gw's byte; lanes without a window land past the descriptor's end
+            static_assert(GW <= 32 && (W / 4 >= 64 || W / 4 == 32), "k_spark2 mark sink: a tile's windows fit one mask, a ballot is one or two windows");
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((marks >> (lo & 31u)) & 1u), orsrc, (int)(lo < GW ? lo * RS : 0xffffffu), 0, 2);
         }
         wsync();                                                            // the next tile's base outputs overwrite what this tile's layers read
         if (tile_n >= tile_end) break;
@@ -3836,6 +3899,11 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark0(const ChainParams P) {
             else if constexpr (W == 8) { const v2u_t o = {pk[0], pk[1]}; __builtin_amdgcn_raw_buffer_store_b64(o, orsrc, (int)(lane * OBW), 0, 2); }
             else if constexpr (W == 4) __builtin_amdgcn_raw_buffer_store_b32(pk[0], orsrc, (int)(lane * OBW), 0, 2);
             else __builtin_amdgcn_raw_buffer_store_b16((uint16_t)pk[0], orsrc, (int)(lane * OBW), 0, 2);
+        } else if constexpr (EPI == 4) {
+            bool m = false;                                                 // src/fft.rs:54-55: a row is blank when every norm is below `min`
+#pragma unroll
+            for (uint32_t o = 0; o < W; ++o) m |= !(nm[o] < P.rmin);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(m ? 1 : 0), orsrc, (int)lane, 0, 2);
         } else {
             float first = 0.f, second = 0.f;                                // src/fft.rs:95-97: the halves summed in order
 #pragma unroll

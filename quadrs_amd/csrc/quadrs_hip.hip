@@ -756,7 +756,7 @@ int check_options(const qd_plan_options *options, qd_plan_options *out) {
 // the sink's fields of a chain description (the stages are checked by stages_geo)
 int check_sink(const qd_chain_desc &d) {
     if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
-    if (d.epilogue < 0 || d.epilogue > 3) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
+    if (d.epilogue < 0 || d.epilogue > QD_EPI_MARK_U8) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
     if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
     if (!is_pow2(d.width))
         return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
@@ -1457,6 +1457,51 @@ double qd_shift_ratio(int64_t frequency, uint64_t sample_rate) {
 int qd_lowpass_design(uint64_t frequency, uint64_t sample_rate, size_t size, float *taps) {
     if (!taps) return fail(QD_ERR_INVALID, "taps is NULL");
     design_taps(frequency, sample_rate, size, taps);
+    return QD_OK;
+}
+
+// bits::scan, src/bits.rs:3-55 (host arithmetic, f64)
+int qd_bits_scan(const uint8_t *marks, size_t n, double scale, uint8_t *bits, size_t cap, size_t *produced, double *error) {
+    if (produced) *produced = 0;
+    if (error) *error = 0.0;
+    if ((!marks && n) || (!bits && cap) || !produced || !error) return fail(QD_ERR_INVALID, "qd_bits_scan: NULL argument");
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(QD_ERR_INVALID, "qd_bits_scan: scale must be finite and > 0");
+    auto as_u64 = [](double v) { return v >= 18446744073709551616.0 ? UINT64_MAX : (v > 0.0 ? (uint64_t)v : 0ull); };      // Rust `as u64`: saturating
+    const uint64_t half = as_u64(std::round(scale / 2.0));                   // f64::round: halves away from zero, like std::round
+    // run_of (:40-55): the index where the first stretch of more than `half` consecutive values != val began, else the length
+    auto run_of = [&](size_t from, bool val) -> size_t {
+        uint64_t bad = 0;
+        for (size_t i = from; i < n; ++i) {
+            bad = ((marks[i] != 0) != val) ? bad + 1 : 0;
+            if (bad > half) return i + 1 - (size_t)bad - from;
+        }
+        return n - from;
+    };
+    size_t i = 0;
+    uint64_t count = 0;
+    bool bit = false, stuck = false;
+    double err = 0.0;
+    while (i != n) {
+        const size_t found = run_of(i, bit);
+        i += found;
+        if (found <= half) {
+            // :13-15 `continue`s without flipping `bit`: before the end of the data the next run_of starts on the stretch that stopped
+            // this one and returns 0, for ever
+            if (i != n) { stuck = true; break; }
+            continue;
+        }
+        const double b = (double)found / scale, rounded = std::round(b);
+        err += std::fabs(b - rounded);
+        const uint64_t emit = as_u64(rounded);
+        for (uint64_t k = 0; k < emit && count + k < cap; ++k) bits[count + k] = bit ? 1 : 0;
+        count = emit > UINT64_MAX - count ? UINT64_MAX : count + emit;
+        bit = !bit;
+    }
+    *error = err;
+    *produced = count > (uint64_t)SIZE_MAX ? SIZE_MAX : (size_t)count;
+    if (count > cap) return fail(QD_ERR_INVALID, "qd_bits_scan: %llu bits do not fit cap %zu", (unsigned long long)count, cap);
+    if (stuck) return fail(QD_ERR_PANIC, "bits::scan never terminates here (src/bits.rs:9-15): a run of at most half = %llu ends at mark %zu of %zu and the loop continues without flipping",
+                           (unsigned long long)half, i, n);
     return QD_OK;
 }
 

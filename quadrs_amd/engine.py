@@ -78,6 +78,19 @@ def fft_norm_batch(x, W, n_fft, in_stride):
     return out
 
 
+def bits_scan(marks, scale, cap=None):
+    """bits::scan (src/bits.rs:3-55) over 0 / non-0 marks (e.g. an EPI_MARK_U8 output) at `scale` marks per bit: (error, bits).
+    Raises QuadrsError(ERR_PANIC) where the reference's loop never terminates.  cap: size of the bits buffer (default: enough)."""
+    marks = np.ascontiguousarray(marks).astype(np.uint8, copy=False).reshape(-1)
+    if cap is None:
+        # a run of r marks emits round(r / scale) <= r / scale + 1 / 2 bits and the accepted runs partition at most all marks
+        cap = int(min(marks.size / scale + marks.size / 2 + 2, 1 << 40)) if scale > 0 and np.isfinite(scale) else 0
+    bits = np.zeros(max(cap, 1), dtype=np.uint8)
+    produced, error = C.c_size_t(0), C.c_double(0.0)
+    check(lib().qd_bits_scan(_np_ptr(marks), marks.size, float(scale), _np_ptr(bits), cap, C.byref(produced), C.byref(error)))
+    return error.value, bits[:produced.value].copy()
+
+
 def gen(cos_hz, sample_rate, first, n):
     """Gen::read_at (src/gen.rs:35-47) on the GPU; returns float32 (n,2)."""
     cos = np.ascontiguousarray(cos_hz, dtype=np.int64)
