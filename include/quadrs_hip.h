@@ -57,12 +57,20 @@ typedef enum {
                                 Behind a cascade (qd_plan_create_stages) a block is the outer read_at(b*width, width)
                                 of the nested stages, every stage truncating against its own read of it; n_windows
                                 counts the blocks whose source span fits the stream (see the stage lists below). */
-    QD_EPI_MARK_U8 = 4       /* 1 u8 per spark_fft window (the loop of src/fft.rs:28,65: n_windows and qd_plan_src_range are the glyph
+    QD_EPI_MARK_U8 = 4,      /* 1 u8 per spark_fft window (the loop of src/fft.rs:28,65: n_windows and qd_plan_src_range are the glyph
                                 sink's): 0 when the reference would print the row blank, i.e. every bin has norm < min in f32
                                 (src/fft.rs:54-55; min = range_min with has_range, else 0.08f; range_max plays no part), 1 otherwise.
                                 A NaN norm or a NaN min compares false: 1.  Equivalently any(code != 0) over the W codes of
                                 QD_EPI_GLYPH_U8 for the same plan parameters: the blank / not-blank step of the README's "OOK in
                                 sed" example, the input of qd_bits_scan.  Needs no lowpass, takes any stride. */
+    QD_EPI_ROWS_F32 = 5      /* take_fft's rows behind the chain (src/ffts.rs:18-85): W f32 per row, fftshifted norms.  width = W, any W >= 1: a
+                                power of two runs the chain kernel over rows at irregular offsets, every other width up to 4096 the Bluestein
+                                kernel (larger ones: QD_ERR_UNSUPPORTED); stride, has_range and range_* are ignored.  The plan has no window
+                                loop of its own — n_windows = 0, out_bytes_per_window = 4 W, raw_per_window = W*D + T — and is run by
+                                qd_plan_take_fft (see there); qd_plan_run, qd_plan_src_range, qd_plan_run_sharded* and
+                                qd_plan_complete_windows return QD_ERR_INVALID on it.  A row whose source span W*D + T does not fit the
+                                160 KiB LDS tile is QD_ERR_UNSUPPORTED at plan creation, and so is this sink behind a cascade
+                                (qd_plan_create_stages; a [shift] [lowpass] list is the one-stage plan as for every sink). */
 } qd_epilogue;
 
 const char *qd_last_error(void);
@@ -312,6 +320,38 @@ int qd_plan_complete_windows(const qd_plan *plan, uint64_t *n);
  * out_bytes_per_window, raw_per_window, raw_step and ratio of the plan it would make (other fields 0), and *complete its
  * qd_plan_complete_windows */
 int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, qd_plan_info *info, uint64_t *complete);
+
+/* ------------------------------------------------------------------ spectrogram rows (take_fft) behind a chain
+ *
+ * take_fft(&dyn Samples, ...) (src/ffts.rs:18-85) over the fused chain  from -> [shift] -> [lowpass]  of a QD_EPI_ROWS_F32 plan: output_len
+ * rows at sample start + round(step*i) of the SINK's stream (decimated samples behind a lowpass), step = (end-start)/output_len in f64,
+ * each the W-point forward FFT of the samples a read_exact_at(offset, W) of the chain returns — a LowPass truncates the row's last
+ * outputs against the row's own read (src/filter.rs:68-83) —, under a Blackman-Harris window (windowing 1) or none (0). */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(qd_rows_desc) */
+    int32_t  has_slice;       /* 0: (0, len - W), src/ffts.rs:27-30 */
+    uint64_t start, end;      /* the slice, in the sink's samples */
+    uint64_t output_len;
+    int32_t  windowing;       /* 0 rectangular, 1 Blackman-Harris (src/ffts.rs:110-119) */
+    int32_t  _pad;
+} qd_rows_desc;
+
+/* Host arithmetic only (no device): validates the chain of desc (its has_shift / has_lowpass fields; width = W, the epilogue is not looked
+ * at) with the plan's codes, applies src/ffts.rs:27-48 against the sink's len() with qd_take_fft's codes (QD_ERR_PANIC for the two asserts
+ * and the len < W underflow, QD_ERR_INVALID for the ensure!), writes offsets[i] = start + round(step*i) (cap >= output_len entries, else
+ * QD_ERR_INVALID) and the source range [*src_first, +*src_count) the rows read: row i reads source samples [off_i*D, off_i*D + W*D + T)
+ * ([off_i, off_i + W) without a lowpass).  QD_ERR_SHORT, naming the row, when a row's read_exact_at would fail, i.e. its source span does
+ * not fit n_samples: LowPass::len over-reports by one (src/filter.rs:45-48), so a slice that passes the asserts can still end here. */
+int qd_rows_geometry(const qd_chain_desc *desc, const qd_rows_desc *rows, uint64_t *offsets, size_t cap, uint64_t *src_first, uint64_t *src_count);
+
+/* The rows of a QD_EPI_ROWS_F32 plan: output_len * W f32 into `rows`, row-major.  src holds the raw bytes of source samples
+ * [src_first, src_first + src_count), a slab of the stream that covers every row's span (absolute indices keep the NCO phase); the checks
+ * are qd_rows_geometry's plus QD_ERR_SHORT for a row that is not inside the slab.  Device / host / pinned buffers and `stream` as for
+ * qd_plan_run: device buffers are enqueued on `stream` and the call returns without waiting for the kernels; host buffers return after the
+ * copy back.  Only the slab is read — of a host slab only the stretch the rows span is copied up, in one piece — and only
+ * output_len * 4 * W bytes are written.  output_len == 0 is QD_OK. */
+int qd_plan_take_fft(qd_plan *plan, const qd_rows_desc *rows_desc, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                     float *rows, int out_mem, void *stream);
 
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */

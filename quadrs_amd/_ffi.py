@@ -12,7 +12,7 @@ MEM_HOST, MEM_DEVICE, MEM_HOST_PINNED = 0, 1, 2
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_SPECIALISE, KERNEL_NO_PLAN_TIME = 0, 1, 2, 3
 MODE_EXACT, MODE_FAST = 0, 1
 MAX_SHARDS = 16
-EPI_NORMS_F32, EPI_GLYPH_U8, EPI_BUCKET2_U8, EPI_CF32_BLOCKS, EPI_MARK_U8 = 0, 1, 2, 3, 4
+EPI_NORMS_F32, EPI_GLYPH_U8, EPI_BUCKET2_U8, EPI_CF32_BLOCKS, EPI_MARK_U8, EPI_ROWS_F32 = 0, 1, 2, 3, 4, 5
 
 # every symbol include/quadrs_hip.h declares
 SYMBOLS = [
@@ -24,7 +24,7 @@ SYMBOLS = [
     "qd_set_stream", "qd_release_workspaces", "qd_plan_create_ex", "qd_plan_shard_info", "qd_plan_run_sharded",
     "qd_plan_run_sharded_device", "qd_plan_get_stats", "qd_host_alloc", "qd_host_free", "qd_host_register",
     "qd_host_unregister", "qd_plan_kernel_name", "qd_plan_create_stages", "qd_plan_get_stage_taps",
-    "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan",
+    "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan", "qd_rows_geometry", "qd_plan_take_fft",
 ]
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
@@ -77,6 +77,13 @@ class PlanStats(C.Structure):
     _fields_ = [
         ("wall_ms", C.c_double), ("stage_ms", C.c_double), ("bytes_h2d", C.c_uint64), ("bytes_d2h", C.c_uint64),
         ("chunks", C.c_uint32), ("_pad", C.c_uint32),
+    ]
+
+
+class RowsDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("has_slice", C.c_int32), ("start", C.c_uint64), ("end", C.c_uint64),
+        ("output_len", C.c_uint64), ("windowing", C.c_int32), ("_pad", C.c_int32),
     ]
 
 
@@ -149,6 +156,8 @@ def lib():
             "qd_plan_complete_windows": (i32, [vp, C.POINTER(u64)]),
             "qd_stages_geometry": (i32, [C.POINTER(ChainDesc), C.POINTER(Stage), sz, C.POINTER(PlanInfo), C.POINTER(u64)]),
             "qd_bits_scan": (i32, [vp, sz, f64, vp, sz, C.POINTER(sz), C.POINTER(f64)]),
+            "qd_rows_geometry": (i32, [C.POINTER(ChainDesc), C.POINTER(RowsDesc), vp, sz, C.POINTER(u64), C.POINTER(u64)]),
+            "qd_plan_take_fft": (i32, [vp, C.POINTER(RowsDesc), vp, i32, u64, u64, vp, i32, vp]),
         }
         for name, (res, args) in sig.items():
             try:

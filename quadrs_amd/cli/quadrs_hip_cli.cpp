@@ -95,7 +95,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -106,6 +106,7 @@ struct Op {
     size_t levels = 2;
     bool has_scan = false; double scan = 0.0;                           // marks -scan SCALE (bits::scan, src/bits.rs)
     bool overwrite = false; std::string prefix;                         // write
+    size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
 };
 
 typedef std::map<std::string, std::vector<std::string>> ArgMap;
@@ -236,6 +237,27 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
                 if (!std::isfinite(op.scan) || !(op.scan > 0.0)) bail("marks -scan takes a scale > 0");
             }
             ensure_empty(m);
+        } else if (cmd == "rows") {
+            // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
+            auto m = no_duplicates(raw);
+            op.kind = OP_ROWS;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 512;                // src/eui/mod.rs:66
+            v = take(m, "count", &f);
+            op.count = f ? (size_t)parse_si_u64(v) : 2048;               // :87
+            v = take(m, "slice", &f);
+            if (f) {
+                size_t c = v.find(':');
+                if (c == std::string::npos) bail("slice argument must contain a ':': '" + v + "'");
+                op.has_slice = true;
+                op.slice_start = parse_si_u64(v.substr(0, c));
+                op.slice_end = parse_si_u64(v.substr(c + 1));
+            }
+            v = take(m, "window", &f);
+            if (f && v != "bh" && v != "rect") bail("rows -window takes bh or rect");
+            op.windowing = (f && v == "rect") ? 0 : 1;
+            ensure_empty(m);
+            op.prefix = next("'rows' requires a prefix argument");
         } else if (cmd == "write") {
             auto m = no_duplicates(raw);
             op.kind = OP_WRITE;
@@ -666,6 +688,70 @@ void do_write(const Samples &s, bool overwrite, const std::string &prefix, const
     close(fd);
 }
 
+// The `rows` sink: take_fft's rows (src/ffts.rs:18-85) as PREFIX.sr{rate}.w{W}x{count}.pgm — binary PGM, one row per line of the view,
+// pixel (norm / 10. * 256.) as u8, the blue channel of the reference's texture (src/eui/mod.rs:104).  A fusable  from [shift] [lowpass]
+// chain runs ONE plan (QD_EPI_ROWS_F32) over the mapped file; cascades, and anything the library answers QD_ERR_UNSUPPORTED to, pull
+// each row through the iterator chain and hand the rows, side by side, to qd_take_fft.
+void do_rows(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width, count = sink.count;
+    std::string fn = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "x" + std::to_string(count) + ".pgm";
+    int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+    if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + ")");
+    std::vector<float> rows(W * count);
+    try {
+        bool done = false;
+        if (cs && cs->fusable && !cs->cascade && cs->src->kind == OP_FROM && !getenv("QUADRS_HIP_NO_FUSE")) {
+            MappedFile data(cs->src->filename);
+            qd_chain_desc d{};
+            d.struct_size = sizeof d;
+            d.format = cs->src->format; d.sample_rate = cs->src->sample_rate;
+            d.n_samples = data.size / qd_pair_bytes(cs->src->format);
+            if (cs->shift) { d.has_shift = 1; d.shift_hz = cs->shift->shift; }
+            if (cs->lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs->lowpass->lp_freq; d.decimate = cs->lowpass->decimate; d.taps = cs->lowpass->size; }
+            d.width = W; d.stride = 1; d.epilogue = QD_EPI_ROWS_F32;
+            qd_rows_desc r{};
+            r.struct_size = sizeof r;
+            r.has_slice = sink.has_slice ? 1 : 0; r.start = sink.slice_start; r.end = sink.slice_end;
+            r.output_len = count; r.windowing = sink.windowing;
+            qd_plan *plan = nullptr;
+            int rc = qd_plan_create(&d, &plan);
+            if (rc == QD_OK) {
+                rc = qd_plan_take_fft(plan, &r, data.p, data.mem, 0, d.n_samples, rows.data(), QD_MEM_HOST, nullptr);
+                qd_plan_destroy(plan);
+                if (rc == QD_OK) done = true;
+            }
+            if (rc != QD_OK && rc != QD_ERR_UNSUPPORTED) qd_check(rc, "rows");
+        }
+        if (!done && count) {
+            // src/ffts.rs:27-62 over the iterator chain; the rows' samples side by side are a stream whose rows sit at i W
+            uint64_t start = sink.slice_start, end = sink.slice_end;
+            const uint64_t len = s.len();
+            if (!sink.has_slice) { if (len < W) bail("attempt to subtract with overflow"); start = 0; end = len - W; }
+            if (!(end > start)) bail("Invalid slice: end (" + std::to_string(end) + ") must be greater than start (" + std::to_string(start) + ")");
+            if (!(end < len)) bail("Slice end (" + std::to_string(end) + ") exceeds sample length (" + std::to_string(len) + ")");
+            if (!(end - start > count)) bail("Visible samples (" + std::to_string(end - start) + ") must be greater than output length (" + std::to_string(count) + ")");
+            if (W < 2) bail("rows -width 1 needs a chain the library fuses");
+            const double step = (double)(end - start) / (double)count;
+            std::vector<qd_c32> side(W * count);
+            for (size_t i = 0; i < count; ++i) {
+                const double rr = std::round(step * (double)i);
+                const uint64_t ri = !(rr > 0) ? 0 : (rr >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)rr);
+                s.read_exact_at(start + ri, side.data() + i * W, W);
+            }
+            qd_check(qd_take_fft(side.data(), 0, side.size(), (uint64_t)side.size() + 1, 1, 0, (uint64_t)side.size(), W, sink.windowing, count,
+                                 rows.data(), QD_MEM_HOST), "take_fft");
+        }
+    } catch (...) { close(fd); unlink(fn.c_str()); throw; }
+    std::string head = "P5\n" + std::to_string(W) + " " + std::to_string(count) + "\n255\n";
+    std::vector<uint8_t> px(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) {
+        const float v = rows[i] / 10.f * 256.f;                          // `as u8`: saturating, NaN -> 0
+        px[i] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
+    }
+    if (write(fd, head.data(), head.size()) < 0 || (px.size() && write(fd, px.data(), px.size()) < 0)) { close(fd); bail("write failed"); }
+    close(fd);
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -675,6 +761,7 @@ void usage() {
             "sparkfft [-width 128] [-stride =width] [-range MIN:MAX] \\\n"
             "  bucket [-width 128] [-stride =width] -by freq COUNT \\\n"
             "   marks [-width 128] [-stride =width] [-min 0.08] [-scan SCALE] \\\n"
+            "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
             "\n\nFormat for FREQUENCY, SAMPLE_RATE, and other suffixes: 123, 123k, 123M, 123G\n");
@@ -710,6 +797,10 @@ int main(int argc, char **argv) {
                 case OP_BUCKET: printf("bucket width=%zu stride=%llu levels=%zu\n", op.width, (unsigned long long)op.stride, op.levels); break;
                 case OP_MARKS: printf("marks width=%zu stride=%llu min=%s scan=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no", op.has_scan ? "yes" : "no"); break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
+                case OP_ROWS:
+                    printf("rows width=%zu count=%zu slice=%s window=%s\n", op.width, op.count,
+                           op.has_slice ? (std::to_string(op.slice_start) + ":" + std::to_string(op.slice_end)).c_str() : "all", op.windowing ? "bh" : "rect");
+                    break;
                 }
             }
             return 0;
@@ -753,6 +844,11 @@ int main(int argc, char **argv) {
                     cs.cascade = !chain_clean;
                     if (!run_fused(cs, op, *samples)) run_iter_sink(*samples, op, true);
                 } else run_iter_sink(*samples, op);
+                break;
+            case OP_ROWS:
+                if (!samples) bail("rows requires an input");
+                cs.cascade = !chain_clean;
+                do_rows(*samples, op, &cs);
                 break;
             case OP_WRITE:
                 if (!samples) bail("write requires an input");

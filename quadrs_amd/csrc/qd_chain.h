@@ -137,6 +137,7 @@ template <uint32_t W_, uint32_t S_, uint32_t D_, uint32_t T_, uint32_t G_, uint3
           uint32_t FLAGS_ = 0>
 struct FixedGeo {
     static constexpr bool kFixed = true;
+    static constexpr bool kRows = false;
     static constexpr FixedRules R = fixed_rules(W_, S_, D_, T_, G_, FIRB_, FIRR_, PAD_, BATCH_, FLAGS_);
     static constexpr uint32_t kFlags = FLAGS_;
     // Planar raw tile: the shifted samples are parked as two f32 planes (re / im) instead of interleaved pairs, rows of D floats
@@ -208,6 +209,7 @@ struct FixedGeo {
 
 struct DynGeo {
     static constexpr bool kFixed = false;
+    static constexpr bool kRows = false;
     static constexpr uint32_t kBatch = 1;
     static constexpr uint32_t kFlags = 0, G_ct = 1, W_ct = 1;
     static constexpr bool kPlanar = false, kBakedTaps = false, kPairFir = false, kUnrolledShared = false, kPackedTile = false, kHalfTile = false;
@@ -223,6 +225,17 @@ struct DynGeo {
         : W(P.W), S(P.S), D(P.D), T(P.T), G(P.G), logW(P.logW), Dp(P.Dp), kPad(P.Dp - P.D), dshift(P.dshift), dmagic(P.dmagic), PD(P.D), pshift(P.dshift),
           a0(P.a0), b0(P.b0), T_fast(P.T_fast), a1(P.a1), b1(P.b1), log_base(P.log_base), base_len(P.base_len),
           layers(P.layers), lds_raw_elems(P.lds_raw_elems) {}
+};
+
+// Row mode (QD_EPI_ROWS_F32, take_fft's rows behind a chain, src/ffts.rs:59-62): DynGeo's runtime geometry, but the G windows of a tile are
+// rows that start anywhere — window w reads source samples [row_offsets[w], + blk_len D + T) — so phase 1 fetches every window on its
+// own (per-sample loads) into its own stretch of the raw tile, S D samples apart (the host makes S >= blk_len + T / D).  blk_len <= W is
+// the row's true length: the FFT sink has blk_len == W; the cf32 sink (the read_at blocks a Bluestein width is transformed from) may
+// have a shorter one, truncates against it and stores rows of blk_len samples.  ChainParams::window scales sample k behind the FIR too.
+// Only the kernels instantiated with this policy contain any of it.
+struct RowGeo : DynGeo {
+    static constexpr bool kRows = true;
+    __device__ __forceinline__ explicit RowGeo(const ChainParams &P) : DynGeo(P) {}
 };
 
 // ---------------------------------------------------------------- phase-1 helpers
@@ -264,6 +277,19 @@ __device__ __forceinline__ TileGeo tile_geo(const ChainParams &P, const GeoT &ge
     g.slab_lo0 = (int32_t)(lo < -BIG ? -BIG : (lo > BIG ? BIG : lo));
     g.slab_hi0 = (int32_t)(hi < -BIG ? -BIG : (hi > BIG ? BIG : hi));
     return g;
+}
+
+// row mode: the geometry of window g of the tile on its own (what the per-sample fetch_row and process_row read of a TileGeo)
+template <int FMT, int NT, class GeoT>
+__device__ __forceinline__ TileGeo row_window_geo(const ChainParams &P, const GeoT &geo, const TileGeo &tg, uint32_t g) {
+    constexpr uint32_t ROW = NT * FmtTraits<FMT>::SPL;
+    TileGeo w = tg;
+    w.n_start = P.row_offsets[tg.w0 + g - P.out_window0];                // uniform load
+    w.tile_raw = P.blk_len * geo.D + geo.T;
+    w.r0 = w.n_start / ROW;
+    w.rel0 = (int32_t)(int64_t)(w.r0 * ROW - w.n_start);
+    w.n_rows = (uint32_t)((w.tile_raw - w.rel0 + ROW - 1) / ROW);
+    return w;
 }
 
 // Issue this lane's load for row i of the tile (the result stays in flight until first use).
@@ -1471,9 +1497,11 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     tile_n = walk_tile(walk_local + walk_step);
     TileGeo tg = tile_geo<FMT, NT>(P, geo, tile, n_tiles);
     Vec pf[RCH];
+    if constexpr (!GeoT::kRows) {
     if (tg.valid) {
 #pragma unroll
         for (int i = 0; i < RCH; ++i) pf[i] = fetch_row<FMT, NT, ALIGNED, (GeoT::kFlags & kGeoNtLoads) != 0>(P, tg, (uint32_t)i < tg.n_rows ? i : tg.n_rows - 1, tid);
+    }
     }
 
 #ifdef QD_WGTIME       // diagnostic build: when each workgroup started / finished (100 MHz realtime counter) and on which XCD
@@ -1587,6 +1615,21 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
         }
         unsigned long long claim = 0;
         if (dyn && tid == 0 && (!kHalf || half == 1)) claim = atomicAdd(&P.work[16 * my_x], 1ull);     // the tile after next; the reply is read after the FIR
+        if constexpr (GeoT::kRows) {
+            // rows start anywhere: each of the tile's windows is fetched on its own, row by row of the absolute NCO grid, no prefetch
+            // (a spectrogram is a few thousand rows; the chain's streaming machinery has nothing to stream here)
+            static_assert(!ALIGNED && !WHOLE, "row mode: the per-sample loads");
+            for (uint32_t g = 0; g < g_cnt; ++g) {
+                const TileGeo wg = row_window_geo<FMT, NT>(P, geo, tg, g);
+                float2 *rawg = raw + (size_t)g * S * Dp;                   // sample g S D of the tile (pad_index of a multiple of D)
+                for (uint32_t r = 0; r < wg.n_rows; ++r) {
+                    const Vec v = fetch_row<FMT, NT, false>(P, wg, r, tid);
+                    RowBase rb{};
+                    if constexpr (HAS_SHIFT) rb = load_rowbase(P, wg.r0 + r);
+                    process_row_any<FMT, NT, NCO>(P, geo, wg, r, tid, v, rb, lr, lane_pad, lut, rawg);
+                }
+            }
+        } else
         if constexpr (kFastP1) {
             // Row-aligned tiles (the tile stride G*S*D a multiple of the row length, the tile a compile-time number of rows): every row
             // offset is an immediate, the loads go through a per-tile buffer descriptor whose hardware range check replaces the clamp
@@ -1973,11 +2016,13 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             const uint32_t g = o >> logW, k = o & (W - 1);
             const uint32_t q = g * S + k;
             float accr = 0.f, acci = 0.f;
+            if constexpr (GeoT::kRows) { if (k >= P.blk_len) continue; }      // a row shorter than the kernel's width (cf32 sink)
             if (HAS_FIR && !QD_DBG(P, 2)) {
                 // jmax(k) = min(T, valid - (k*D + c)) with valid = B*D + T (full read of a block of B outputs;
                 // B == W for the FFT sinks, B = 0x1000 > W for the write sink whose tiles are sub-blocks)
                 const uint32_t kb = cf32_out ? (((uint32_t)(w0 + g)) & P.blk_sub_mask) * W + k : k;
                 uint32_t jmax = ((cf32_out ? P.blk_len : W) - kb) * D + T / 2;
+                if constexpr (GeoT::kRows) jmax = (P.blk_len - k) * D + T / 2;       // every row is a read_at of its own (src/ffts.rs:62)
                 if (jmax > T) jmax = T;
                 const float2 *rowp = raw + (size_t)(q + geo.a0) * Dp;
                 if (geo.T_fast == T || __all(jmax == T)) {
@@ -1988,6 +2033,9 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     fir_span<false>(geo, rowp, geo.b0, 0, geo.T_fast, T, tapl, accr, acci);
                     const float2 *rowp1 = raw + (size_t)(q + geo.a1) * Dp;
                     fir_span<true>(geo, rowp1, geo.b1, geo.T_fast, T, jmax, tapl, accr, acci);
+                }
+                if constexpr (GeoT::kRows) {
+                    if (P.window) { const float wv = P.window[k]; accr = accr * wv; acci = acci * wv; }   // Complex<f32> * f32 (src/ffts.rs:64-68)
                 }
             } else {
                 float2 v = raw[HAS_FIR ? q * Dp : q];
@@ -2102,6 +2150,13 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
         if (cf32_out) {
             // do_write / LowPass::read_at output (src/lib.rs:206-209): the decimated cf32 samples themselves
             float2 *outc = reinterpret_cast<float2 *>(P.out) + (wrel << logW);
+            if constexpr (GeoT::kRows) {                      // rows of blk_len samples, side by side
+                outc = reinterpret_cast<float2 *>(P.out) + wrel * P.blk_len;
+                for (uint32_t o = tid; o < n_out_s; o += NT) {
+                    const uint32_t g = o >> logW, k = o & (W - 1);
+                    if (k < P.blk_len) outc[(size_t)g * P.blk_len + k] = fbs[o];
+                }
+            } else
             for (uint32_t o = tid; o < n_out_s; o += NT) outc[o] = fbs[o];
         } else if (parks_norms(P.epi)) {
             // freq_levels (src/fft.rs:95-97): sequential f32 sums of |X[k]| over each half.  In the runtime-geometry kernels the mark sink

@@ -178,7 +178,14 @@ __global__ void k_gen(const int64_t *cos_hz, uint32_t n_cos, uint64_t sample_rat
 __device__ __forceinline__ double2 zmul(double2 a, double2 b) {
     return make_double2(__builtin_fma(a.x, b.x, -(a.y * b.y)), __builtin_fma(a.x, b.y, a.y * b.x));
 }
-__global__ __launch_bounds__(256) void k_bluestein(const float2 *__restrict__ in, uint64_t in_first, const uint64_t *__restrict__ offs,
+// The loader (FMT, NCO): a row behind `from [shift]` is unpacked and shifted while it is loaded, with the chain kernels' operations —
+// unpack_*, nco_mul over the absolute sample index (rows of 512 samples, as k_shift), cmul_pk.  <0, 0> loads cf32 as it always did.
+struct BlueSrc {
+    const uint8_t *in; uint64_t in_first;      // raw bytes of source sample in_first
+    double ratio; const RowBase *rowtab; uint64_t rowtab_row0; const double2 *jtab;     // NCO != 0 only
+};
+template <int FMT, int NCO>
+__global__ __launch_bounds__(256) void k_bluestein(const BlueSrc src, const uint64_t *__restrict__ offs,
                                                    const float *__restrict__ win, uint32_t W, uint32_t M, uint32_t logM,
                                                    const double2 *__restrict__ chirp, const double2 *__restrict__ Bbr,
                                                    const double2 *__restrict__ tw, float *__restrict__ out) {
@@ -186,11 +193,24 @@ __global__ __launch_bounds__(256) void k_bluestein(const float2 *__restrict__ in
     double2 *buf = reinterpret_cast<double2 *>(smem_b);
     const uint32_t tid = threadIdx.x;
     const uint64_t row = blockIdx.x;
-    const float2 *x = in + (offs[row] - in_first);
+    const uint64_t n0 = offs[row];
     for (uint32_t n = tid; n < M; n += 256) {
         double2 v = make_double2(0.0, 0.0);
         if (n < W) {
-            float2 xv = x[n];
+            const uint64_t na = n0 + n;
+            const uint8_t *sp = src.in + (na - src.in_first) * (uint64_t)FmtTraits<FMT>::BPS;
+            float2 xv;
+            if constexpr (FMT == 0) xv = *reinterpret_cast<const float2 *>(sp);
+            else if constexpr (FMT == 1) { const uint32_t w = *reinterpret_cast<const uint16_t *>(sp); xv = make_float2(unpack_cs8(w & 0xff), unpack_cs8(w >> 8)); }
+            else if constexpr (FMT == 2) { const uint32_t w = *reinterpret_cast<const uint16_t *>(sp); xv = make_float2(unpack_cu8(w & 0xff), unpack_cu8(w >> 8)); }
+            else { const uint32_t w = *reinterpret_cast<const uint32_t *>(sp); xv = make_float2(unpack_cs16(w & 0xffffu), unpack_cs16(w >> 16)); }
+            if constexpr (NCO != 0) {
+                const uint32_t j = (uint32_t)(na & 511u);
+                const RowBase rb = src.rowtab[(na >> 9) - src.rowtab_row0];
+                const double2 cs = src.jtab[j];
+                LaneRot lr; lr.jf = (double)j; lr.c = cs.x; lr.s = cs.y;
+                xv = cmul_pk(xv, nco_mul<NCO == 2>(rb, lr, src.ratio));        // buf[i] *= mul (src/shift.rs:51)
+            }
             if (win) xv = cscale(xv, win[n]);         // *sample *= w_val (src/ffts.rs:64-68), Complex<f32> * f32, f32-rounded
             v = zmul(make_double2((double)xv.x, (double)xv.y), chirp[n]);
         }
@@ -308,6 +328,33 @@ chain_fn pick_fmt(int nco, bool fir, bool aligned) {
 
 chain_fn pick_generic(int fmt, int nco, bool fir, bool aligned) {
 #define QD_X(F) pick_fmt<F>(nco, fir, aligned)
+    switch (fmt) { QD_FMT_CASES(QD_X) }
+#undef QD_X
+    return nullptr;
+}
+
+// ---- row mode (QD_EPI_ROWS_F32): the per-sample runtime-geometry kernel over irregular rows (RowGeo, qd_chain.h)
+template <int F>
+chain_fn pick_rows_fmt(int nco, bool fir) {
+    switch (nco) {
+    case 0: return fir ? k_chain<F, 0, RowGeo, true, 4, false, false, dyn_lb(0)> : k_chain<F, 0, RowGeo, false, 4, false, false, dyn_lb(0)>;
+    case 1: return fir ? k_chain<F, 1, RowGeo, true, 4, false, false, dyn_lb(1)> : k_chain<F, 1, RowGeo, false, 4, false, false, dyn_lb(1)>;
+    default: return fir ? k_chain<F, 2, RowGeo, true, 4, false, false, dyn_lb(2)> : k_chain<F, 2, RowGeo, false, 4, false, false, dyn_lb(2)>;
+    }
+}
+chain_fn pick_rows(int fmt, int nco, bool fir) {
+#define QD_X(F) pick_rows_fmt<F>(nco, fir)
+    switch (fmt) { QD_FMT_CASES(QD_X) }
+#undef QD_X
+    return nullptr;
+}
+
+// ---- k_bluestein's loaders
+typedef void (*blue_fn)(const BlueSrc, const uint64_t *, const float *, uint32_t, uint32_t, uint32_t, const double2 *, const double2 *, const double2 *, float *);
+template <int F>
+blue_fn pick_blue_fmt(int nco) { return nco == 0 ? k_bluestein<F, 0> : (nco == 1 ? k_bluestein<F, 1> : k_bluestein<F, 2>); }
+blue_fn pick_blue(int fmt, int nco) {
+#define QD_X(F) pick_blue_fmt<F>(nco)
     switch (fmt) { QD_FMT_CASES(QD_X) }
 #undef QD_X
     return nullptr;
@@ -681,6 +728,9 @@ struct qd_plan {
     // take_fft mode (generic kernels): per-window start offsets and an f32 window, both on the device
     const uint64_t *row_offsets_d = nullptr;
     const float *window_d = nullptr;
+    // QD_EPI_ROWS_F32 (qd_plan_take_fft): blk_len is the row width W (any), W / S the row-mode kernel's power-of-two width and LDS pitch
+    bool rows = false, rows_blue = false;     // rows_blue: W is not a power of two (k_bluestein; behind a lowpass over the rows' read_at blocks)
+    RowTab rows_tab512;                       // k_bluestein's loader behind a shift: NCO rows of 512 samples
     // timing
     bool timing = false, ev_made = false, ev_recorded = false;
     hipEvent_t ev0{}, ev1{};
@@ -726,7 +776,37 @@ uint64_t out_bytes_per_window(const qd_plan *p) {
     case QD_EPI_NORMS_F32: return (uint64_t)p->W * 4;
     case QD_EPI_GLYPH_U8: return p->W;
     case QD_EPI_CF32_BLOCKS: return (uint64_t)p->blk_len * 8;
+    case QD_EPI_ROWS_F32: return (uint64_t)p->blk_len * 4;
     default: return 1;
+    }
+}
+
+// take_fft's slice rules against the viewed stream's len() (src/ffts.rs:27-48), shared by qd_take_fft, qd_rows_geometry and qd_plan_take_fft
+int rows_slice(uint64_t len, uint64_t W, int has_slice, uint64_t *start, uint64_t *end, uint64_t output_len) {
+    if (!has_slice) {                                                             // src/ffts.rs:27-30
+        if (len < W) return fail(QD_ERR_PANIC, "len < width underflows (src/ffts.rs:29)");
+        *start = 0; *end = len - W;
+    }
+    if (!(*end > *start)) return fail(QD_ERR_PANIC, "Invalid slice: end (%llu) must be greater than start (%llu)", (unsigned long long)*end, (unsigned long long)*start);
+    if (!(*end < len)) return fail(QD_ERR_PANIC, "Slice end (%llu) exceeds sample length (%llu)", (unsigned long long)*end, (unsigned long long)len);
+    const uint64_t visible = *end - *start;
+    if (!(visible > output_len)) return fail(QD_ERR_INVALID, "Visible samples (%llu) must be greater than output length (%llu)", (unsigned long long)visible, (unsigned long long)output_len);
+    return QD_OK;
+}
+// row i's offset exactly as the reference forms it (f64 step, round half away from zero, saturating cast; src/ffts.rs:50,60)
+uint64_t rows_offset(uint64_t start, uint64_t end, uint64_t output_len, uint64_t i) {
+    const double step = (double)(end - start) / (double)output_len;
+    const double r = std::round(step * (double)i);
+    const uint64_t ri = !(r > 0) ? 0 : (r >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)r);
+    return start + ri;
+}
+// generate_blackman_harris_window, src/ffts.rs:110-119 (host f32 arithmetic like the reference)
+void blackman_harris(size_t W, std::vector<float> *win) {
+    win->resize(W);
+    const float tau = 6.28318530717958647692528676655900577f;
+    for (size_t i = 0; i < W; ++i) {
+        float x = tau * (float)i / (float)(W - 1);
+        (*win)[i] = 0.35875f - 0.48829f * std::cos(x) + 0.14128f * std::cos(2.0f * x) - 0.01168f * std::cos(3.0f * x);
     }
 }
 
@@ -756,8 +836,12 @@ int check_options(const qd_plan_options *options, qd_plan_options *out) {
 // the sink's fields of a chain description (the stages are checked by stages_geo)
 int check_sink(const qd_chain_desc &d) {
     if (d.format < 0 || d.format > 3) return fail(QD_ERR_INVALID, "unknown format %d", d.format);
-    if (d.epilogue < 0 || d.epilogue > QD_EPI_MARK_U8) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
+    if (d.epilogue < 0 || d.epilogue > QD_EPI_ROWS_F32) return fail(QD_ERR_INVALID, "unknown epilogue %d", d.epilogue);
     if (d.mode != QD_MODE_EXACT && d.mode != QD_MODE_FAST) return fail(QD_ERR_INVALID, "unknown mode %d", d.mode);
+    if (d.epilogue == QD_EPI_ROWS_F32) {               // take_fft: FftPlanner takes any length (src/ffts.rs:25); stride and range are ignored
+        if (d.width < 1 || d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "take_fft width %llu", (unsigned long long)d.width);
+        return QD_OK;
+    }
     if (!is_pow2(d.width))
         return fail(QD_ERR_PANIC, "Radix4 requires a power-of-two width (rustfft API contract), got %llu", (unsigned long long)d.width);
     if (d.width > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "width too large");
@@ -1724,7 +1808,7 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     if (d.epilogue != QD_EPI_CF32_BLOCKS && len < d.width)
         return fail(QD_ERR_PANIC, "len %llu < width %llu: u64 underflow at src/fft.rs:28,86", (unsigned long long)len, (unsigned long long)d.width);
     g->len = len; g->rate = rate;
-    g->n_windows = sink_windows(d.epilogue, len, d.width, d.stride);
+    g->n_windows = d.epilogue == QD_EPI_ROWS_F32 ? 0 : sink_windows(d.epilogue, len, d.width, d.stride);
     g->routed = shape.empty() || shape == "S" || shape == "L" || shape == "SL";
     size_t k = 0;
     auto take = [&](char c) { if (k < shape.size() && shape[k] == c) return (int)k++; return -1; };
@@ -1732,6 +1816,8 @@ int stages_geo(const qd_chain_desc *desc, const qd_stage *st, size_t n, StageGeo
     if (g->l1 >= 0) { g->l2 = take('L'); if (g->l2 >= 0) g->s2 = take('S'); }
     if (g->l1 >= 0) { g->D1 = (uint32_t)st[g->l1].decimate; g->T1 = (uint32_t)st[g->l1].taps; }
     if (g->routed) return QD_OK;
+    if (d.epilogue == QD_EPI_ROWS_F32)
+        return fail(QD_ERR_UNSUPPORTED, "QD_EPI_ROWS_F32 behind a cascade (%s) is not built: the caller pulls the rows through the stages into qd_take_fft", shape.c_str());
     if (g->l1 < 0 || k != shape.size())
         return fail(QD_ERR_UNSUPPORTED, "stage list %s is not a fused shape ([shift] lowpass [shift] [lowpass [shift]]): the caller runs it stage by stage",
                     shape.c_str());
@@ -1878,7 +1964,7 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
     info->n_windows = g.n_windows;
     info->decimated_len = g.len;
     info->out_sample_rate = g.rate;
-    info->out_bytes_per_window = write ? d.width * 8 : d.epilogue == QD_EPI_NORMS_F32 ? d.width * 4 : (d.epilogue == QD_EPI_GLYPH_U8 ? d.width : 1);
+    info->out_bytes_per_window = write ? d.width * 8 : (d.epilogue == QD_EPI_NORMS_F32 || d.epilogue == QD_EPI_ROWS_F32) ? d.width * 4 : (d.epilogue == QD_EPI_GLYPH_U8 ? d.width : 1);
     info->raw_per_window = (uint64_t)g.n2 * g.D1 + g.T1;
     info->raw_step = (write ? d.width : d.stride) * g.D2 * g.D1;      // the write sink's blocks lie side by side
     info->ratio = g.ratio;
@@ -1888,6 +1974,77 @@ int qd_stages_geometry(const qd_chain_desc *desc, const qd_stage *stages, size_t
 
 namespace {
 int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stages, const qd_plan_options *options, bool list, qd_plan **out);
+
+// rows per workgroup of the row-mode kernel and its LDS (QD_EPI_ROWS_F32).  A 256-thread workgroup filters and transforms one output
+// per lane and pass, so G = 256 / W rows keep every lane busy where rows are short (one for W >= 256) — more would only queue behind
+// the same lanes; G is halved while the tile takes more than half the CU's LDS, so that two workgroups still share a CU.
+size_t rows_tile(uint32_t Wk, uint32_t S, uint32_t D, uint32_t T, bool lut8, uint32_t *G, uint32_t *raw_elems) {
+    uint32_t g = Wk < 256 ? 256 / Wk : 1;
+    if (g > 64) g = 64;
+    for (;; g /= 2) {
+        const FixedRules r = fixed_rules(Wk, S, D, T, g, 8, 1, 1, 1, 0);
+        const size_t b = (size_t)generic_lds_bytes(r, lut8);
+        if (g == 1 || b <= kLdsMax / 2) { *G = g; *raw_elems = (uint32_t)generic_raw_elems(r); return b; }
+    }
+}
+
+// QD_EPI_ROWS_F32: the plan behind qd_plan_take_fft.  A power-of-two width runs the row-mode k_chain (unpack -> NCO -> FIR -> window ->
+// Radix4 -> |X|); any other width up to 4096 runs k_bluestein — straight off the source without a lowpass, else over the rows'
+// read_at blocks, which the same row-mode kernel writes as cf32 (its power-of-two width is then the next one above the row's).
+int rows_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t rate) {
+    (void)hipGetDevice(&p->device);
+    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "QD_EPI_ROWS_F32 is not sharded");
+    p->rows = true;
+    p->has_shift = d.has_shift != 0; p->has_fir = d.has_lowpass != 0;
+    p->D = p->has_fir ? (uint32_t)d.decimate : 1;
+    p->T = p->has_fir ? (uint32_t)d.taps : 0;
+    p->dec_len = len; p->out_rate = rate; p->n_windows = 0;
+    p->ratio = p->has_shift ? qd_shift_ratio(d.shift_hz, d.sample_rate) : 0.0;
+    p->nco = !p->has_shift ? 0 : ((std::fabs(p->ratio) * (double)d.n_samples > 268435456.0) ? 2 : 1);      // as plan_init
+    if (p->has_shift && (p->opt.nco_order == 1 || p->opt.nco_order == 2)) p->nco = p->opt.nco_order;
+    const bool pow2 = is_pow2(d.width);
+    if (!pow2 && d.width > 4096)
+        return fail(QD_ERR_UNSUPPORTED, "take_fft width %llu: widths that are not a power of two are built up to 4096 (the reference front end's slider range, src/eui/mod.rs:157)", (unsigned long long)d.width);
+    p->rows_blue = !pow2;
+    p->blk_len = (uint32_t)d.width;
+    p->logW = ilog2(d.width); p->W = 1u << p->logW;
+    p->S = p->W + (p->has_fir ? (p->T + p->D - 1) / p->D : 0);
+    p->nt = kThreads; p->launch_nt = kThreads;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) p->n_cu = prop.multiProcessorCount;
+    const int fmt = d.format;
+    if (pow2 || p->has_fir) {
+        uint32_t raw_elems = 0;
+        p->geo.lds_bytes = rows_tile(p->W, p->S, p->D, p->T, lut8_of(fmt), &p->geo.G, &raw_elems);
+        if (p->geo.lds_bytes > kLdsMax || (uint64_t)raw_elems * p->D >= (1ull << 32))
+            return fail(QD_ERR_UNSUPPORTED, "one row (W*D+T = %llu samples) exceeds the 160 KiB LDS tile", (unsigned long long)((uint64_t)d.width * p->D + p->T));
+        p->geo.lds_main = p->geo.lds_bytes; p->geo.lds_raw_elems = raw_elems;
+        p->geo.Dp = p->D + ((p->D % 2 == 0) ? 1 : 0);
+        p->wg_per_cu = std::min(4, std::max(1, (int)(kLdsMax / p->geo.lds_bytes)));
+        p->fn = p->fn_unaligned = pick_rows(fmt, p->nco, p->has_fir);
+        if (!p->fn) return fail(QD_ERR_UNSUPPORTED, "no kernel built for this format (QD_DEV_FAST build?)");
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(p->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax); e != hipSuccess)
+            return fail(QD_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS %zu): %s", kLdsMax, hipGetErrorString(e));
+        p->fft = fft_layout(p->W);
+        if (!p->fft.tw.empty()) {
+            HIPCHK(hipMalloc(&p->tw_d, p->fft.tw.size() * sizeof(float2)));
+            HIPCHK(hipMemcpy(p->tw_d, p->fft.tw.data(), p->fft.tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+        }
+    }
+    if (p->has_fir) {
+        p->taps_h.resize(p->T); design_taps(d.lowpass_hz, d.sample_rate, p->T, p->taps_h.data());
+        HIPCHK(hipMalloc(&p->taps_d, p->T * sizeof(float)));
+        HIPCHK(hipMemcpy(p->taps_d, p->taps_h.data(), p->T * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (p->has_shift) {                      // the lane table: entries j < 512 serve k_bluestein's rows of 512 samples as well
+        const uint32_t ROW = kThreads * spl_of(fmt);
+        HIPCHK(hipMalloc(&p->jtab_d, ROW * sizeof(double2)));
+        hipLaunchKernelGGL(k_jtab, dim3((ROW + 255) / 256), dim3(256), 0, 0, p->ratio, ROW, p->jtab_d);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return QD_OK;
+}
 
 // a window larger than the LDS tile, windows side by side (plan_init's kNeedComposite): two plans behind the parent's handle
 int composite_init(qd_plan *p, uint64_t rate) {
@@ -1972,9 +2129,10 @@ int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stag
         p->stages.assign(stages, stages + n_stages);
         stage_taps_of(stages, n_stages, g, &p->stage_taps);
     }
-    if (!g.routed) rc = cascade_init(p, g, stages);
+    if (d.epilogue == QD_EPI_ROWS_F32) rc = rows_init(p, d, g.len, g.rate);      // (stages_geo has refused a cascade)
+    else if (!g.routed) rc = cascade_init(p, g, stages);
     else if ((rc = plan_init(p, d, g.len, g.rate)) == kNeedComposite) rc = composite_init(p, g.rate);
-    if (rc == QD_OK) rc = make_shards(p, desc, stages, n_stages, list);
+    if (rc == QD_OK && !p->rows) rc = make_shards(p, desc, stages, n_stages, list);
     if (rc) { qd_plan_destroy(p); return rc; }
     *out = p;
     return QD_OK;
@@ -2016,6 +2174,7 @@ int qd_plan_get_stage_taps(const qd_plan *p, uint32_t stage, float *taps, size_t
 
 int qd_plan_complete_windows(const qd_plan *p, uint64_t *n) {
     if (!p || !n) return fail(QD_ERR_INVALID, "plan/n is NULL");
+    if (p->rows) return fail(QD_ERR_INVALID, "a QD_EPI_ROWS_F32 plan has no window loop: its calls are qd_rows_geometry and qd_plan_take_fft");
     *n = p->casc ? p->c_complete : p->n_windows;
     return QD_OK;
 }
@@ -2035,6 +2194,7 @@ int qd_plan_destroy(qd_plan *p) {
     if (p->tw_d) (void)hipFree(p->tw_d);
     if (p->jtab_d) (void)hipFree(p->jtab_d);
     if (p->jtab256_d) (void)hipFree(p->jtab256_d);
+    free_rowtab(&p->rows_tab512);
     for (NcoTabs *t : {&p->tabs_dev, &p->tabs_slot[0], &p->tabs_slot[1]}) { free_rowtab(&t->main); free_rowtab(&t->tail); for (RowTab &q : t->phase) free_rowtab(&q); t->phase.clear(); if (t->work) (void)hipFree(t->work); t->work = nullptr; if (t->cmp_tmp) (void)hipFree(t->cmp_tmp); t->cmp_tmp = nullptr; if (t->done) (void)hipEventDestroy(t->done); t->done = nullptr; t->launched = false; }
     if (p->ev_made) { (void)hipEventDestroy(p->ev0); (void)hipEventDestroy(p->ev1); }
     delete p;
@@ -2092,6 +2252,12 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
         return QD_OK;
     }
     const int fmt = p->d.format;
+    if (p->rows) {
+        if (p->rows_blue && !p->has_fir) snprintf(buf, cap, "k_bluestein<fmt %d, nco %d>, 256 threads", fmt, p->nco);
+        else snprintf(buf, cap, "qd::k_chain<fmt %d, nco %d, RowGeo>, %d rows per workgroup, %d threads, generic%s", fmt, p->nco, (int)p->geo.G, p->launch_nt,
+                      p->rows_blue ? " | k_bluestein<fmt 0, nco 0>" : "");
+        return QD_OK;
+    }
     char geo[160];
     if (p->jit_fn || p->fixed)
         snprintf(geo, sizeof geo, "FixedGeo<%u, %u, %u, %u, %u, ..., %u>", p->W, p->S, p->D, p->T, p->geo.G, p->kflags);
@@ -2111,6 +2277,7 @@ int qd_plan_get_taps(const qd_plan *p, float *taps, size_t cap) {
 
 int qd_plan_src_range(const qd_plan *p, uint64_t first_window, uint64_t n_windows, uint64_t *first, uint64_t *count) {
     if (!p || !first || !count) return fail(QD_ERR_INVALID, "NULL argument");
+    if (p->rows) return fail(QD_ERR_INVALID, "a QD_EPI_ROWS_F32 plan has no window loop: its calls are qd_rows_geometry and qd_plan_take_fft");
     const uint64_t step = (uint64_t)(p->blk_len ? p->blk_len : p->S) * p->D;
     const uint64_t rpw = (uint64_t)(p->blk_len ? p->blk_len : p->W) * p->D + p->T;
     *first = first_window * step;
@@ -2275,6 +2442,7 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
 int qd_plan_run(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
                 uint64_t first_window, uint64_t n_windows, void *out, int out_mem, void *stream) {
     if (!p || !src || !out) return fail(QD_ERR_INVALID, "NULL argument");
+    if (p->rows) return fail(QD_ERR_INVALID, "a QD_EPI_ROWS_F32 plan has no window loop: its calls are qd_rows_geometry and qd_plan_take_fft");
     const uint64_t subs = p->blk_subs;          // 1 except QD_EPI_CF32_BLOCKS (API windows are whole blocks)
     if (first_window + n_windows > p->n_windows)
         return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
@@ -2348,6 +2516,7 @@ int qd_plan_run_sharded_device(qd_plan *p, void *const *slabs, void *const *outs
     if (!p || !slabs || !outs) return fail(QD_ERR_INVALID, "NULL argument");
     if (p->cmp_a) return fail(QD_ERR_UNSUPPORTED, "a two-stage plan (window larger than the LDS tile) has no pre-split device path");
     if (p->casc) return fail(QD_ERR_UNSUPPORTED, "a cascade plan (qd_plan_create_stages) has no pre-split device path");
+    if (p->rows) return fail(QD_ERR_INVALID, "a QD_EPI_ROWS_F32 plan has no window loop: its calls are qd_rows_geometry and qd_plan_take_fft");
     const size_t n = p->shard_info.size();
     const int bps = bps_of(p->d.format);
     std::vector<qd_plan *> plans(n, p);
@@ -2592,16 +2761,19 @@ int bluestein_tab(uint32_t W, std::shared_ptr<BluesteinTab> *out) {
     return QD_OK;
 }
 
-int bluestein_rows(const float2 *src, uint64_t in_first, const uint64_t *offs_d, const float *win_d, size_t W, size_t n_rows,
+// rows at offs_d[] (source sample indices) of a slab; fmt / nco / src's NCO tables: the loader (cf32 without a shift: qd_take_fft's)
+int bluestein_rows(int fmt, int nco, const BlueSrc &src, const uint64_t *offs_d, const float *win_d, size_t W, size_t n_rows,
                    float *dst, hipStream_t st) {
     if (W > 4096) return fail(QD_ERR_UNSUPPORTED, "take_fft width %zu: widths that are not a power of two are built up to 4096 (the reference front end's slider range, src/eui/mod.rs:157)", W);
     std::shared_ptr<BluesteinTab> tp;                  // held until the launch is enqueued
     int rc = bluestein_tab((uint32_t)W, &tp);
     if (rc) return rc;
     const BluesteinTab &t = *tp;
+    const blue_fn fn = pick_blue(fmt, nco);
+    if (!fn) return fail(QD_ERR_UNSUPPORTED, "no kernel built for this format (QD_DEV_FAST build?)");
     if ((size_t)t.M * 16 > 48 * 1024)     // per device, cheap: raise the dynamic-LDS limit to the hardware maximum
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bluestein), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-    hipLaunchKernelGGL(k_bluestein, dim3((uint32_t)n_rows), dim3(256), (size_t)t.M * 16, st, src, in_first, offs_d, win_d, (uint32_t)W, t.M, t.logM,
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    hipLaunchKernelGGL(fn, dim3((uint32_t)n_rows), dim3(256), (size_t)t.M * 16, st, src, offs_d, win_d, (uint32_t)W, t.M, t.logM,
                        t.chirp, t.Bbr, t.tw, dst);
     HIPCHK(hipGetLastError());
     return QD_OK;
@@ -2759,34 +2931,16 @@ int qd_take_fft(const qd_c32 *in, uint64_t in_first, size_t n_in, uint64_t sampl
                 uint64_t start, uint64_t end, size_t W, int windowing, size_t output_len, float *rows, int mem) {
     if (!in || !rows) return fail(QD_ERR_INVALID, "NULL buffer");
     if (W < 1 || W > (1u << 20)) return fail(QD_ERR_UNSUPPORTED, "take_fft width %zu", W);
-    if (!has_slice) {                                                             // src/ffts.rs:27-30
-        if (samples_len < W) return fail(QD_ERR_PANIC, "len < width underflows (src/ffts.rs:29)");
-        start = 0; end = samples_len - W;
-    }
-    if (!(end > start)) return fail(QD_ERR_PANIC, "Invalid slice: end (%llu) must be greater than start (%llu)", (unsigned long long)end, (unsigned long long)start);
-    if (!(end < samples_len)) return fail(QD_ERR_PANIC, "Slice end (%llu) exceeds sample length (%llu)", (unsigned long long)end, (unsigned long long)samples_len);
-    const uint64_t visible = end - start;
-    if (!(visible > output_len)) return fail(QD_ERR_INVALID, "Visible samples (%llu) must be greater than output length (%zu)", (unsigned long long)visible, output_len);
+    if (const int rcs = rows_slice(samples_len, W, has_slice, &start, &end, output_len)) return rcs;
     if (output_len == 0) return QD_OK;
-    // row offsets exactly as the reference forms them (f64 step, round half away from zero, saturating cast)
-    const double step = (double)visible / (double)output_len;                     // :50
     std::vector<uint64_t> offs(output_len);
     for (size_t i = 0; i < output_len; ++i) {
-        double r = std::round(step * (double)i);
-        uint64_t ri = !(r > 0) ? 0 : (r >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)r);
-        offs[i] = start + ri;                                                     // :60
+        offs[i] = rows_offset(start, end, output_len, i);
         if (offs[i] < in_first || offs[i] + W > in_first + n_in || offs[i] + W > samples_len)
             return fail(QD_ERR_SHORT, "row %zu at sample %llu is not inside the provided block / the stream (read_exact_at, src/ffts.rs:62)", i, (unsigned long long)offs[i]);
     }
     std::vector<float> win;
-    if (windowing == 1) {                                                         // generate_blackman_harris_window, :110-119
-        win.resize(W);
-        const float tau = 6.28318530717958647692528676655900577f;
-        for (size_t i = 0; i < W; ++i) {
-            float x = tau * (float)i / (float)(W - 1);
-            win[i] = 0.35875f - 0.48829f * std::cos(x) + 0.14128f * std::cos(2.0f * x) - 0.01168f * std::cos(3.0f * x);
-        }
-    }
+    if (windowing == 1) blackman_harris(W, &win);
     const hipStream_t st = g_stream;
     WsLease ws(st);
     if (ws.rc) return ws.rc;
@@ -2820,12 +2974,184 @@ int qd_take_fft(const qd_c32 *in, uint64_t in_first, size_t n_in, uint64_t sampl
         rc = launch_windows(p, &p->tabs_dev, src, in_first, n_in, 0, output_len, 0, dst, st);
         p->row_offsets_d = nullptr; p->window_d = nullptr;
     } else {
-        rc = bluestein_rows(static_cast<const float2 *>(src), in_first, static_cast<const uint64_t *>(doffs), static_cast<const float *>(dwin),
+        BlueSrc bs{};
+        bs.in = static_cast<const uint8_t *>(src); bs.in_first = in_first;
+        rc = bluestein_rows(QD_FMT_CF32, 0, bs, static_cast<const uint64_t *>(doffs), static_cast<const float *>(dwin),
                             W, output_len, static_cast<float *>(dst), st);
     }
     if (rc) return rc;
     if (mem != QD_MEM_DEVICE) HIPCHK(hipMemcpyAsync(rows, dst, output_len * W * 4, hipMemcpyDeviceToHost, st));
     return finish_call(mem, st);
+}
+
+namespace {
+// the chain of a one-stage description as stages_geo sees it (validation with the plan's codes), sink = QD_EPI_ROWS_F32
+int rows_chain_geo(const qd_chain_desc *desc, StageGeo *g) {
+    if (!desc) return fail(QD_ERR_INVALID, "desc is NULL");
+    if (desc->struct_size != sizeof(qd_chain_desc)) return fail(QD_ERR_INVALID, "qd_chain_desc size mismatch");
+    qd_chain_desc d = *desc;
+    qd_stage st[2] = {};
+    size_t n = 0;
+    if (d.has_shift) { st[n].kind = QD_STAGE_SHIFT; st[n++].shift_hz = d.shift_hz; }
+    if (d.has_lowpass) { st[n].kind = QD_STAGE_LOWPASS; st[n].lowpass_hz = d.lowpass_hz; st[n].decimate = d.decimate; st[n++].taps = d.taps; }
+    d.has_shift = d.has_lowpass = 0; d.epilogue = QD_EPI_ROWS_F32;
+    return stages_geo(&d, st, n, g);
+}
+
+// slice rules, row offsets (the sink's samples) and the rows' source range [*lo, *hi); a row whose read_exact_at fails: QD_ERR_SHORT
+int rows_layout(uint64_t n_samples, uint64_t len, uint64_t W, uint64_t D, uint64_t T, const qd_rows_desc *r, std::vector<uint64_t> *offs,
+                uint64_t *lo, uint64_t *hi) {
+    if (!r) return fail(QD_ERR_INVALID, "rows is NULL");
+    if (r->struct_size != sizeof(qd_rows_desc)) return fail(QD_ERR_INVALID, "qd_rows_desc size mismatch");
+    if (r->windowing != 0 && r->windowing != 1) return fail(QD_ERR_INVALID, "unknown windowing %d", r->windowing);
+    uint64_t start = r->start, end = r->end;
+    if (const int rc = rows_slice(len, W, r->has_slice, &start, &end, r->output_len)) return rc;
+    if (r->output_len > (1ull << 32)) return fail(QD_ERR_UNSUPPORTED, "output_len too large");
+    offs->resize(r->output_len);
+    const uint64_t span = W * D + T;
+    *lo = UINT64_MAX; *hi = 0;
+    for (uint64_t i = 0; i < r->output_len; ++i) {
+        const uint64_t o = rows_offset(start, end, r->output_len, i);
+        (*offs)[i] = o;
+        if (o > (UINT64_MAX - span) / D || o * D + span > n_samples)
+            return fail(QD_ERR_SHORT, "row %llu at sample %llu reads source samples [%llu, +%llu) past the stream's %llu (read_exact_at, src/ffts.rs:62)",
+                        (unsigned long long)i, (unsigned long long)o, (unsigned long long)(o * D), (unsigned long long)span, (unsigned long long)n_samples);
+        *lo = std::min(*lo, o * D); *hi = std::max(*hi, o * D + span);
+    }
+    if (r->output_len == 0) *lo = *hi = 0;
+    return QD_OK;
+}
+
+// G rows per workgroup of the row-mode kernel over a device slab: rows at source samples srcoffs_d[], epilogue `epi` (norms / cf32)
+int launch_rows(qd_plan *p, const void *src_d, uint64_t src_first, uint64_t src_count, const uint64_t *srcoffs_d, const float *win_d,
+                uint64_t n_rows, uint64_t lo, uint64_t hi, void *out_d, uint32_t epi, hipStream_t st) {
+    NcoTabs *ctx = &p->tabs_dev;
+    if (!ctx->done) HIPCHK(hipEventCreateWithFlags(&ctx->done, hipEventDisableTiming));
+    if (ctx->launched) HIPCHK(hipStreamWaitEvent(st, ctx->done, 0));          // the launch-context protocol of launch_windows
+    int rc = QD_OK;
+    if (p->has_shift) rc = ensure_rowtab_for(p, kThreads * spl_of(p->d.format), &ctx->main, lo, hi, st);
+    if (rc == QD_OK) {
+        ChainParams P{};
+        plan_params(p, &P);
+        P.src = static_cast<const uint8_t *>(src_d);
+        P.src_first = src_first; P.src_count = src_count;
+        P.first_window = 0; P.n_windows = n_rows; P.out_window0 = 0;
+        P.rowtab = ctx->main.d; P.rowtab_row0 = ctx->main.row0;
+        P.out = out_d;
+        P.epi = epi;
+        P.row_offsets = srcoffs_d; P.window = win_d;
+        P.blk_len = p->blk_len; P.blk_sub_mask = 0; P.tile_extra = 0;
+        P.work = nullptr;
+        P.lds_dyn = (uint32_t)p->geo.lds_bytes;
+        const uint64_t n_tiles = (n_rows + P.G - 1) / P.G, cap = (uint64_t)p->n_cu * p->wg_per_cu;
+        hipLaunchKernelGGL(p->fn, dim3((uint32_t)(n_tiles < cap ? n_tiles : cap)), dim3(kThreads), p->geo.lds_bytes, st, P);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) rc = fail(QD_ERR_HIP, "row-mode launch -> %s", hipGetErrorString(e));
+    }
+    HIPCHK(hipEventRecord(ctx->done, st));
+    ctx->launched = true;
+    return rc;
+}
+}  // namespace
+
+int qd_rows_geometry(const qd_chain_desc *desc, const qd_rows_desc *rows, uint64_t *offsets, size_t cap, uint64_t *src_first, uint64_t *src_count) {
+    if (!src_first || !src_count) return fail(QD_ERR_INVALID, "src_first/src_count is NULL");
+    StageGeo g;
+    if (const int rc = rows_chain_geo(desc, &g)) return rc;
+    std::vector<uint64_t> offs;
+    uint64_t lo = 0, hi = 0;
+    const bool fir = desc->has_lowpass != 0;
+    if (const int rc = rows_layout(desc->n_samples, g.len, desc->width, fir ? desc->decimate : 1, fir ? desc->taps : 0, rows, &offs, &lo, &hi)) return rc;
+    if (offs.size() > cap || (!offsets && !offs.empty())) return fail(QD_ERR_INVALID, "offsets holds %zu entries, the rows need %zu", offsets ? cap : (size_t)0, offs.size());
+    if (!offs.empty()) memcpy(offsets, offs.data(), offs.size() * 8);
+    *src_first = lo; *src_count = hi - lo;
+    return QD_OK;
+}
+
+int qd_plan_take_fft(qd_plan *p, const qd_rows_desc *rows, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                     float *out, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "plan is NULL");
+    if (!p->rows) return fail(QD_ERR_INVALID, "qd_plan_take_fft needs a QD_EPI_ROWS_F32 plan");
+    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    const uint64_t W = p->blk_len, D = p->D, T = p->T, span = W * D + T;
+    std::vector<uint64_t> offs;
+    uint64_t lo = 0, hi = 0;
+    if (const int rc = rows_layout(p->d.n_samples, p->dec_len, W, D, T, rows, &offs, &lo, &hi)) return rc;
+    const uint64_t n_rows = offs.size();
+    if (n_rows == 0) return QD_OK;
+    if (!src || !out) return fail(QD_ERR_INVALID, "NULL buffer");
+    for (uint64_t i = 0; i < n_rows; ++i)
+        if (offs[i] * D < src_first || offs[i] * D + span > src_first + src_count)
+            return fail(QD_ERR_SHORT, "row %llu reads source samples [%llu, +%llu), not inside the slab [%llu, +%llu)", (unsigned long long)i,
+                        (unsigned long long)(offs[i] * D), (unsigned long long)span, (unsigned long long)src_first, (unsigned long long)src_count);
+    const bool dev = src_mem == QD_MEM_DEVICE && out_mem == QD_MEM_DEVICE;
+    if (!dev && (!host_kind(src_mem) || !host_kind(out_mem)))
+        return fail(QD_ERR_UNSUPPORTED, "mixed host/device buffers are not supported; use both host or both device");
+    std::vector<float> win;
+    if (rows->windowing == 1) blackman_harris(W, &win);
+    std::vector<uint64_t> soffs(n_rows);
+    for (uint64_t i = 0; i < n_rows; ++i) soffs[i] = offs[i] * D;
+    std::lock_guard<std::mutex> lock(p->mu);
+    DeviceGuard guard(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    WsLease ws(st);
+    if (ws.rc) return ws.rc;
+    const int bps = bps_of(p->d.format);
+    void *doffs = nullptr, *dwin = nullptr;
+    int rc = ws.get(2, n_rows * 8, &doffs); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(doffs, soffs.data(), n_rows * 8, hipMemcpyHostToDevice, st));
+    if (!win.empty()) {
+        rc = ws.get(3, W * 4, &dwin); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(dwin, win.data(), W * 4, hipMemcpyHostToDevice, st));
+    }
+    const bool two_stage = p->rows_blue && p->has_fir;
+    void *dcar = nullptr, *dboffs = nullptr;
+    if (two_stage) {                                  // the carrier of the rows' read_at blocks and their places in it
+        rc = ws.get(4, n_rows * W * 8, &dcar); if (rc) return rc;
+        rc = ws.get(5, n_rows * 8, &dboffs); if (rc) return rc;
+        for (uint64_t i = 0; i < n_rows; ++i) offs[i] = i * W;
+        HIPCHK(hipMemcpyAsync(dboffs, offs.data(), n_rows * 8, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));                 // the tables are locals of this call
+    // host slabs go up in one piece: the stretch the rows read, [lo, hi) — nothing of the slab outside it is touched
+    const void *src_d = src; void *out_d = out;
+    uint64_t d_first = src_first, d_count = src_count;
+    if (!dev) {
+        void *di = nullptr, *dout = nullptr;
+        rc = ws.get(0, (hi - lo) * bps, &di); if (rc) return rc;
+        rc = ws.get(1, n_rows * W * 4, &dout); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(di, static_cast<const uint8_t *>(src) + (lo - src_first) * bps, (hi - lo) * bps, hipMemcpyHostToDevice, st));
+        src_d = di; out_d = dout; d_first = lo; d_count = hi - lo;
+    }
+    if (!p->rows_blue) {
+        rc = launch_rows(p, src_d, d_first, d_count, static_cast<const uint64_t *>(doffs), static_cast<const float *>(dwin), n_rows, lo, hi, out_d,
+                         QD_EPI_NORMS_F32, st);
+    } else if (two_stage) {
+        rc = launch_rows(p, src_d, d_first, d_count, static_cast<const uint64_t *>(doffs), nullptr, n_rows, lo, hi, dcar, QD_EPI_CF32_BLOCKS, st);
+        BlueSrc bs{};
+        bs.in = static_cast<const uint8_t *>(dcar); bs.in_first = 0;
+        if (rc == QD_OK) rc = bluestein_rows(QD_FMT_CF32, 0, bs, static_cast<const uint64_t *>(dboffs), static_cast<const float *>(dwin), W, n_rows,
+                                             static_cast<float *>(out_d), st);
+    } else {
+        BlueSrc bs{};
+        bs.in = static_cast<const uint8_t *>(src_d); bs.in_first = d_first;
+        NcoTabs *ctx = &p->tabs_dev;                  // the row table is the context's: launches that use it are ordered (see NcoTabs)
+        if (!ctx->done) HIPCHK(hipEventCreateWithFlags(&ctx->done, hipEventDisableTiming));
+        if (ctx->launched) HIPCHK(hipStreamWaitEvent(st, ctx->done, 0));
+        if (p->has_shift) {
+            rc = ensure_rowtab(&p->rows_tab512, p->ratio, 512, lo, hi + 512, st);
+            bs.ratio = p->ratio; bs.rowtab = p->rows_tab512.d; bs.rowtab_row0 = p->rows_tab512.row0; bs.jtab = p->jtab_d;
+        }
+        if (rc == QD_OK) rc = bluestein_rows(p->d.format, p->nco, bs, static_cast<const uint64_t *>(doffs), static_cast<const float *>(dwin), W, n_rows,
+                                             static_cast<float *>(out_d), st);
+        HIPCHK(hipEventRecord(ctx->done, st));
+        ctx->launched = true;
+    }
+    if (rc) return rc;
+    if (!dev) {
+        HIPCHK(hipMemcpyAsync(out, out_d, n_rows * W * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return QD_OK;
 }
 
 int qd_device_alloc(size_t bytes, void **ptr) {

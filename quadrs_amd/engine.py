@@ -218,6 +218,31 @@ def stages_geometry(fmt, sample_rate, n_samples, stages, width=128, stride=None,
     return info, done.value
 
 
+def rows_desc(output_len, slice_=None, windowing=1):
+    """qd_rows_desc: take_fft's output_len rows over slice_ = (start, end) of the sink's samples (None: (0, len - W))."""
+    r = _ffi.RowsDesc()
+    r.struct_size = C.sizeof(_ffi.RowsDesc)
+    r.output_len, r.windowing = int(output_len), int(windowing)
+    if slice_ is not None:
+        r.has_slice, r.start, r.end = 1, int(slice_[0]), int(slice_[1])
+    return r
+
+
+def rows_geometry(fmt, sample_rate, n_samples, width, output_len, slice_=None, windowing=1, shift_hz=None, lowpass=None):
+    """qd_rows_geometry (host arithmetic, no device): the row offsets (in the sink's samples) of take_fft over the chain
+    from -> [shift] -> [lowpass] and the source range the rows read.  Returns (offsets, src_first, src_count)."""
+    d = _sink_desc(fmt, sample_rate, n_samples, width, 1, _ffi.EPI_ROWS_F32, None, _ffi.MODE_EXACT)
+    if shift_hz is not None:
+        d.has_shift, d.shift_hz = 1, int(shift_hz)
+    if lowpass is not None:
+        d.has_lowpass, d.lowpass_hz, d.decimate, d.taps = 1, int(lowpass[0]), int(lowpass[1]), int(lowpass[2])
+    r = rows_desc(output_len, slice_, windowing)
+    offs = np.zeros(max(int(output_len), 1), dtype=np.uint64)
+    a, b = C.c_uint64(), C.c_uint64()
+    check(lib().qd_rows_geometry(C.byref(d), C.byref(r), _np_ptr(offs), int(output_len), C.byref(a), C.byref(b)))
+    return offs[:int(output_len)], a.value, b.value
+
+
 class Plan:
     """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
@@ -375,6 +400,25 @@ class Plan:
         st = _cur_stream() if stream is None else C.c_void_p(stream)
         check(lib().qd_plan_run(self._h, C.c_void_p(src.data_ptr()), MEM_DEVICE, src_first, src_count, first_window,
                                 n_windows, C.c_void_p(out.data_ptr()), MEM_DEVICE, st))
+
+    def take_fft(self, data, output_len, slice_=None, windowing=1, src_first=0, out=None):
+        """qd_plan_take_fft of an EPI_ROWS_F32 plan: the (output_len, width) float32 rows of take_fft over the chain.
+        data: bytes / numpy array (host; returns a numpy array) or a torch CUDA tensor (device; enqueued on torch's current
+        stream, returns a float32 CUDA tensor — `out` if given) holding source samples [src_first, ...)."""
+        r = rows_desc(output_len, slice_, windowing)
+        if _is_torch(data):
+            import torch
+            count = data.numel() * data.element_size() // _FMT_BYTES[self.desc.format]
+            if out is None:
+                out = torch.empty((int(output_len), self.width), dtype=torch.float32, device=data.device)
+            check(lib().qd_plan_take_fft(self._h, C.byref(r), C.c_void_p(data.data_ptr()), MEM_DEVICE, src_first, count,
+                                         C.c_void_p(out.data_ptr()), MEM_DEVICE, _cur_stream()))
+            return out
+        buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).reshape(-1))
+        rows = np.zeros((int(output_len), self.width), dtype=np.float32)
+        check(lib().qd_plan_take_fft(self._h, C.byref(r), _np_ptr(buf), MEM_HOST, src_first, buf.size // _FMT_BYTES[self.desc.format],
+                                     _np_ptr(rows), MEM_HOST, None))
+        return rows
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))
