@@ -353,6 +353,52 @@ int qd_rows_geometry(const qd_chain_desc *desc, const qd_rows_desc *rows, uint64
 int qd_plan_take_fft(qd_plan *plan, const qd_rows_desc *rows_desc, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
                      float *rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ level summary of a norms plan
+ *
+ * What `-range` to pass and where in the band the signal sits, without bringing the norms back: FftResult::max / min
+ * (src/ffts.rs:101-107) and the `min max` line of ui::render (src/ui/mod.rs:317-409), per bin and as a histogram.  The summary is defined
+ * over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W and folds exactly the f32 values the norms sink writes for them, in
+ * fftshifted bin order:
+ *   peak[b]   fold of f32::max from 0.0 over the windows, b < W (a NaN is ignored, as f32::max does)
+ *   floor[b]  fold of f32::min from +inf (a NaN is ignored)
+ *   max, min  the same folds over every bin: the max of peak, the min of floor
+ *   hist[i]   values with bits(|x|) >> 20 == i: 8 buckets per octave; zero and the subnormals in bucket 0, +inf in 2040, 2041..2047 stay 0
+ *   n_nan     NaN values;  sum(hist) + n_nan == n_windows * W
+ * Every field is a max, a min or an integer sum: the result does not depend on the batch, chunk, shard or launch order it was folded
+ * in, and parts merge (qd_summary_merge) to exactly the whole.  The values are norms: non-negative or NaN. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(qd_summary); qd_summary_init sets it */
+    uint32_t width;           /* W */
+    uint64_t n_windows;
+    uint64_t n_nan;
+    float    min, max;
+    uint64_t hist[2048];
+} qd_summary;
+
+/* The fold identities: no windows, max = 0.0, min = +inf, peak[b] = 0.0, floor[b] = +inf.  peak and floor are caller-owned arrays of
+ * `width` f32, here and below; either may be NULL (that fold is then not kept). */
+int qd_summary_init(qd_summary *sum, float *peak, float *floor, uint32_t width);
+/* Fold n_rows rows of sum->width host f32 (e.g. a qd_plan_run output) into sum / peak / floor: the CPU twin of the kernel behind
+ * qd_plan_summarize, bit for bit. */
+int qd_summary_fold(qd_summary *sum, float *peak, float *floor, const float *norms, uint64_t n_rows);
+/* dst (+)= src: associative and commutative.  QD_ERR_INVALID: different widths, or a dst array without its src array. */
+int qd_summary_merge(qd_summary *dst, float *dst_peak, float *dst_floor, const qd_summary *src, const float *src_peak, const float *src_floor);
+/* The bucket of the q-quantile (host arithmetic): N = sum(hist), r = max(1, ceil(q N)), j the first bucket whose cumulative count
+ * reaches r; the r-th smallest non-NaN value lies in [*lo, *hi), *lo the f32 of bits j << 20, *hi of (j + 1) << 20 (+inf for j = 2040).
+ * QD_ERR_INVALID: N == 0 or q outside [0, 1]. */
+int qd_summary_quantile(const qd_summary *sum, double q, float *lo, float *hi);
+
+/* The summary of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and `stream` as for
+ * qd_plan_run (device, host and pinned sources).  sum, peak and floor are HOST memory and are OVERWRITTEN, not accumulated; the call
+ * returns after the result is there.  The windows go batch by batch through the plan's own kernel into a device carrier of at most
+ * max(chunk_bytes, one tile of windows) of norms and are folded there; only the summary comes back.
+ * Codes as qd_plan_run: QD_ERR_SHORT past the sink's loop (the identities are left), and for a cascade's range past
+ * qd_plan_complete_windows (the complete windows of the range are folded, n_windows says how many).  QD_ERR_INVALID for any epilogue
+ * other than QD_EPI_NORMS_F32, QD_ERR_UNSUPPORTED for a plan created with shards (summarise each shard's window range on a plan of its
+ * own and qd_summary_merge them).  n_windows == 0: QD_OK and the identities. */
+int qd_plan_summarize(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                      uint64_t first_window, uint64_t n_windows, qd_summary *sum, float *peak, float *floor, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

@@ -25,7 +25,9 @@ SYMBOLS = [
     "qd_plan_run_sharded_device", "qd_plan_get_stats", "qd_host_alloc", "qd_host_free", "qd_host_register",
     "qd_host_unregister", "qd_plan_kernel_name", "qd_plan_create_stages", "qd_plan_get_stage_taps",
     "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan", "qd_rows_geometry", "qd_plan_take_fft",
+    "qd_summary_init", "qd_summary_fold", "qd_summary_merge", "qd_summary_quantile", "qd_plan_summarize",
 ]
+SUMMARY_BUCKETS = 2048
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -84,6 +86,13 @@ class RowsDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("has_slice", C.c_int32), ("start", C.c_uint64), ("end", C.c_uint64),
         ("output_len", C.c_uint64), ("windowing", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+
+class Summary(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("width", C.c_uint32), ("n_windows", C.c_uint64), ("n_nan", C.c_uint64),
+        ("min", C.c_float), ("max", C.c_float), ("hist", C.c_uint64 * SUMMARY_BUCKETS),
     ]
 
 
@@ -158,6 +167,11 @@ def lib():
             "qd_bits_scan": (i32, [vp, sz, f64, vp, sz, C.POINTER(sz), C.POINTER(f64)]),
             "qd_rows_geometry": (i32, [C.POINTER(ChainDesc), C.POINTER(RowsDesc), vp, sz, C.POINTER(u64), C.POINTER(u64)]),
             "qd_plan_take_fft": (i32, [vp, C.POINTER(RowsDesc), vp, i32, u64, u64, vp, i32, vp]),
+            "qd_summary_init": (i32, [C.POINTER(Summary), vp, vp, C.c_uint32]),
+            "qd_summary_fold": (i32, [C.POINTER(Summary), vp, vp, vp, u64]),
+            "qd_summary_merge": (i32, [C.POINTER(Summary), vp, vp, C.POINTER(Summary), vp, vp]),
+            "qd_summary_quantile": (i32, [C.POINTER(Summary), f64, C.POINTER(f32), C.POINTER(f32)]),
+            "qd_plan_summarize": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(Summary), vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             try:

@@ -95,7 +95,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -236,6 +236,16 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
                 op.has_scan = true; op.scan = strtod(v.c_str(), nullptr);
                 if (!std::isfinite(op.scan) || !(op.scan > 0.0)) bail("marks -scan takes a scale > 0");
             }
+            ensure_empty(m);
+        } else if (cmd == "levels") {
+            // not in the reference's grammar: the level summary of the windows sparkfft would print (FftResult::max / min, src/ffts.rs:101-107,
+            // and the `min max` line of src/ui/mod.rs:317-409): what -range to pass and where in the band the signal sits
+            auto m = no_duplicates(raw);
+            op.kind = OP_LEVELS;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
             ensure_empty(m);
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
@@ -752,6 +762,127 @@ void do_rows(const Samples &s, const Op &sink, const ChainSpec *cs) {
     close(fd);
 }
 
+// The `levels` sink: the qd_summary of the windows sparkfft would print (a cascade's complete windows), as text whose floats (%.9g) parse
+// back to the same f32.  A chain the library fuses folds on the device (qd_plan_summarize on a norms plan; with -gpus N one plan per
+// window range, merged); every other chain pulls its windows through the iterator chain and folds their norms with qd_summary_fold —
+// the same bytes either way.
+void print_levels(uint64_t rate, const Op &sink, const qd_summary &sum, const std::vector<float> &peak) {
+    printf("levels sample_rate=%" PRIu64 " width=%zu stride=%" PRIu64 " windows=%" PRIu64 "\n", rate, sink.width, sink.stride, (uint64_t)sum.n_windows);
+    printf("min %.9g\nmax %.9g\nnan %" PRIu64 "\n", sum.min, sum.max, (uint64_t)sum.n_nan);
+    static const char *qname[] = {"q50", "q90", "q99", "q99.9"};
+    static const double qval[] = {0.5, 0.9, 0.99, 0.999};
+    for (int i = 0; i < 4; ++i) {
+        float lo = NAN, hi = NAN;                                         // no values at all: nan nan
+        (void)qd_summary_quantile(&sum, qval[i], &lo, &hi);
+        printf("%s %.9g %.9g\n", qname[i], lo, hi);
+    }
+    size_t best = 0;
+    for (size_t b = 1; b < peak.size(); ++b) if (peak[b] > peak[best]) best = b;      // the lowest index on ties
+    printf("peak_bin %zu %.9g\n", best, peak.empty() ? 0.f : peak[best]);
+}
+
+bool levels_fused(const ChainSpec &cs, const Op &sink, qd_summary *sum, std::vector<float> *peak, std::vector<float> *floor) {
+    const bool from_gen = cs.src->kind == OP_GEN;
+    std::unique_ptr<MappedFile> data;
+    if (!from_gen) data.reset(new MappedFile(cs.src->filename));
+    qd_chain_desc d{};
+    d.struct_size = sizeof d;
+    d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
+    d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate) : data->size / qd_pair_bytes(cs.src->format);
+    std::vector<qd_stage> stages;
+    if (cs.cascade) {
+        for (const Op *op : cs.stages) {
+            qd_stage st{};
+            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
+            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
+            stages.push_back(st);
+        }
+    } else {
+        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
+        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
+    }
+    d.width = sink.width; d.stride = sink.stride; d.epilogue = QD_EPI_NORMS_F32;
+    int n_dev = 1;
+    if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
+    const int parts = from_gen ? 1 : g_gpus;
+    DeviceBuf gen_src;
+    uint64_t complete = 0;
+    for (int g = 0; g < parts; ++g) {
+        // one unsharded plan per window range, made on that range's device
+        if (parts > 1) qd_check(qd_set_device(g % n_dev), "set device");
+        qd_plan *plan = nullptr;
+        const int rc = cs.cascade ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan) : qd_plan_create(&d, &plan);
+        if (rc == QD_ERR_UNSUPPORTED && g == 0) return false;
+        qd_check(rc, "plan");
+        if (g == 0) qd_check(qd_plan_complete_windows(plan, &complete), "plan complete windows");
+        qd_plan_info info;
+        qd_check(qd_plan_get_info(plan, &info), "plan info");
+        const uint64_t tile = info.tile_windows ? info.tile_windows : 1;              // tile-aligned ranges, as the library's own shards
+        const uint64_t per = ((complete + parts - 1) / parts + tile - 1) / tile * tile;
+        const uint64_t w0 = std::min<uint64_t>(complete, per * g), w1 = std::min<uint64_t>(complete, per * (g + 1));
+        qd_summary part;
+        std::vector<float> ppeak(sink.width), pfloor(sink.width);
+        int rr;
+        if (from_gen && w1 > w0) {
+            qd_check(qd_device_alloc((size_t)d.n_samples * 8, &gen_src.p), "device buffer for gen");
+            const uint64_t piece = 1ull << 28;
+            for (uint64_t a = 0; a < d.n_samples; a += piece) {
+                const uint64_t n = d.n_samples - a < piece ? d.n_samples - a : piece;
+                qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, a, (size_t)n, static_cast<qd_c32 *>(gen_src.p) + a, QD_MEM_DEVICE), "gen");
+            }
+            rr = qd_plan_summarize(plan, gen_src.p, QD_MEM_DEVICE, 0, d.n_samples, w0, w1 - w0, &part, ppeak.data(), pfloor.data(), nullptr);
+        } else {
+            rr = qd_plan_summarize(plan, from_gen ? nullptr : data->p, from_gen ? QD_MEM_HOST : data->mem, 0, d.n_samples, w0, w1 - w0, &part, ppeak.data(), pfloor.data(), nullptr);
+        }
+        qd_plan_destroy(plan);
+        qd_check(rr, "summarize");
+        qd_check(qd_summary_merge(sum, peak->data(), floor->data(), &part, ppeak.data(), pfloor.data()), "merge");
+    }
+    if (parts > 1) qd_check(qd_set_device(0), "set device");
+    return true;
+}
+
+void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    if (!W || (W & (W - 1))) bail("Radix4 algorithm requires a power-of-two input size");
+    if (S == 0) bail("stride 0 never terminates");
+    if (W > 0xffffffffull) bail("width too large");
+    qd_summary sum;
+    std::vector<float> peak(W), floor(W);
+    qd_check(qd_summary_init(&sum, peak.data(), floor.data(), (uint32_t)W), "summary");
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = levels_fused(*cs, sink, &sum, &peak, &floor);
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) through read_exact_at, up to the first that fails; their norms from a
+        // side-by-side norms plan, folded on the host
+        uint64_t len = s.len();
+        if (len < W) bail("attempt to subtract with overflow");
+        const uint64_t lim = len - W, nwin = lim == 0 ? 0 : (lim - 1) / S + 1;
+        const uint64_t batch = 4096;
+        std::vector<qd_c32> buf(batch * W);
+        std::vector<float> norms(batch * W);
+        bool short_read = false;
+        for (uint64_t w0 = 0; w0 < nwin && !short_read; w0 += batch) {
+            uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
+            for (uint64_t i = 0; i < nb; ++i) {
+                try { s.read_exact_at((w0 + i) * S, buf.data() + i * W, W); } catch (const Fail &) { nb = i; short_read = true; break; }
+            }
+            if (!nb) break;
+            qd_chain_desc d{};
+            d.struct_size = sizeof d;
+            d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
+            d.width = W; d.stride = W; d.epilogue = QD_EPI_NORMS_F32;
+            qd_plan *plan = nullptr;
+            qd_check(qd_plan_create(&d, &plan), "plan");
+            const int rc = qd_plan_run(plan, buf.data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms.data(), QD_MEM_HOST, nullptr);
+            qd_plan_destroy(plan);
+            qd_check(rc, "run");
+            qd_check(qd_summary_fold(&sum, peak.data(), floor.data(), norms.data(), nb), "fold");
+        }
+    }
+    print_levels(s.sample_rate(), sink, sum, peak);
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -761,6 +892,7 @@ void usage() {
             "sparkfft [-width 128] [-stride =width] [-range MIN:MAX] \\\n"
             "  bucket [-width 128] [-stride =width] -by freq COUNT \\\n"
             "   marks [-width 128] [-stride =width] [-min 0.08] [-scan SCALE] \\\n"
+            "  levels [-width 128] [-stride =width] \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -796,6 +928,7 @@ int main(int argc, char **argv) {
                 case OP_SPARKFFT: printf("sparkfft width=%zu stride=%llu range=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no"); break;
                 case OP_BUCKET: printf("bucket width=%zu stride=%llu levels=%zu\n", op.width, (unsigned long long)op.stride, op.levels); break;
                 case OP_MARKS: printf("marks width=%zu stride=%llu min=%s scan=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no", op.has_scan ? "yes" : "no"); break;
+                case OP_LEVELS: printf("levels width=%zu stride=%llu\n", op.width, (unsigned long long)op.stride); break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 case OP_ROWS:
                     printf("rows width=%zu count=%zu slice=%s window=%s\n", op.width, op.count,
@@ -844,6 +977,11 @@ int main(int argc, char **argv) {
                     cs.cascade = !chain_clean;
                     if (!run_fused(cs, op, *samples)) run_iter_sink(*samples, op, true);
                 } else run_iter_sink(*samples, op);
+                break;
+            case OP_LEVELS:
+                if (!samples) bail("levels requires an input");
+                cs.cascade = !chain_clean;
+                do_levels(*samples, op, &cs);
                 break;
             case OP_ROWS:
                 if (!samples) bail("rows requires an input");

@@ -29,6 +29,7 @@
 #include "qd_chain.h"
 #include "qd_cascade.h"
 #include "qd_registry.h"
+#include "qd_summary.h"
 
 using namespace qd;
 
@@ -2335,18 +2336,12 @@ double now_ms() {
 
 bool host_kind(int m) { return m == QD_MEM_HOST || m == QD_MEM_HOST_PINNED; }
 
-// Host-resident stream: chunked, double-buffered H2D / kernel / D2H on two streams (slot = chunk parity).  A pageable
-// buffer (QD_MEM_HOST) is staged through a pinned ring with a multi-threaded memcpy; QD_MEM_HOST_PINNED memory is the
-// DMA source / target itself.  Each slot owns its device buffers AND its launch context (row tables, a two-stage plan's
-// carrier), so nothing a kernel in flight on the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
-int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window,
-             uint64_t n_windows, void *out, int out_mem, uint64_t obw) {
-    const double t_begin = now_ms();
-    p->stats = qd_plan_stats{};
-    const int bps = bps_of(p->d.format);
-    const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T;
+// Windows per chunk of a run over windows [first_window, +n_windows): the plan's chunk_bytes at `bytes_per_window`, in whole tiles, and
+// for row-aligned kernels in whole periods of the row grid, so that every chunk's launch is the one a whole-range launch would make.
+uint64_t chunk_windows(const qd_plan *p, uint64_t first_window, uint64_t n_windows, uint64_t bytes_per_window) {
+    const uint64_t step = (uint64_t)p->S * p->D;
     const uint64_t target_bytes = p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20);
-    uint64_t cw = target_bytes / (step * bps ? step * bps : 1);
+    uint64_t cw = target_bytes / (bytes_per_window ? bytes_per_window : 1);
     if (cw < p->geo.G) cw = p->geo.G;
     cw = (cw / p->geo.G) * p->geo.G;
     if (plan_on_rows(p)) {
@@ -2365,8 +2360,11 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
     // a cascade's write sink: chunks of whole read_at blocks (a sub-block reads past its own window's span, within its block's)
     if (p->casc && p->blk_subs > 1) cw = cw < p->blk_subs ? p->blk_subs : cw / p->blk_subs * p->blk_subs;
     if (cw > n_windows) cw = n_windows ? n_windows : 1;
-    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps), ob = (size_t)(cw * obw);
-    const bool stage_in = src_mem == QD_MEM_HOST, stage_out = out_mem == QD_MEM_HOST;
+    return cw;
+}
+
+// the host ring's two slots: device buffers of in_bytes / out_bytes each, pinned staging buffers where a side is pageable, a stream per slot
+int ensure_ring(qd_plan *p, size_t in_bytes, size_t ob, bool stage_in, bool stage_out) {
     if (in_bytes > p->stage_in_bytes || ob > p->stage_out_bytes || (stage_in && in_bytes > p->pin_in_bytes) || (stage_out && ob > p->pin_out_bytes)) {
         free_streaming(p);
         for (int i = 0; i < 2; ++i) {
@@ -2379,6 +2377,23 @@ int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint6
         p->stage_in_bytes = in_bytes; p->stage_out_bytes = ob;
         p->pin_in_bytes = stage_in ? in_bytes : 0; p->pin_out_bytes = stage_out ? ob : 0;
     }
+    return QD_OK;
+}
+
+// Host-resident stream: chunked, double-buffered H2D / kernel / D2H on two streams (slot = chunk parity).  A pageable
+// buffer (QD_MEM_HOST) is staged through a pinned ring with a multi-threaded memcpy; QD_MEM_HOST_PINNED memory is the
+// DMA source / target itself.  Each slot owns its device buffers AND its launch context (row tables, a two-stage plan's
+// carrier), so nothing a kernel in flight on the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
+int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window,
+             uint64_t n_windows, void *out, int out_mem, uint64_t obw) {
+    const double t_begin = now_ms();
+    p->stats = qd_plan_stats{};
+    const int bps = bps_of(p->d.format);
+    const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T;
+    const uint64_t cw = chunk_windows(p, first_window, n_windows, step * bps);
+    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps), ob = (size_t)(cw * obw);
+    const bool stage_in = src_mem == QD_MEM_HOST, stage_out = out_mem == QD_MEM_HOST;
+    if (const int rc = ensure_ring(p, in_bytes, ob, stage_in, stage_out)) return rc;
     double stage_ms = 0;
     struct Pending { bool live = false; uint64_t w0 = 0, nw = 0; } pend[2];
     auto drain = [&](int slot) -> int {
@@ -3151,6 +3166,229 @@ int qd_plan_take_fft(qd_plan *p, const qd_rows_desc *rows, const void *src, int 
         HIPCHK(hipMemcpyAsync(out, out_d, n_rows * W * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
+    return QD_OK;
+}
+
+// ------------------------------------------------------------------ level summary
+
+namespace {
+float f32_of_bits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
+uint32_t bits_of_f32(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
+
+int check_summary(const qd_summary *sum) {
+    if (!sum) return fail(QD_ERR_INVALID, "summary is NULL");
+    if (sum->struct_size != sizeof(qd_summary)) return fail(QD_ERR_INVALID, "qd_summary size mismatch (qd_summary_init sets it)");
+    return QD_OK;
+}
+
+#ifdef QD_DEVELOP
+int summary_layout() { const char *e = dev_env("QD_SUMMARY_LAYOUT"); return e ? atoi(e) & 3 : 0; }
+#else
+int summary_layout() { return 0; }
+#endif
+
+// one batch of norms rows (device memory, 16-byte aligned) into the device accumulator, on `st`
+int launch_summary(const qd_plan *p, const float *norms_d, uint64_t n_rows, SumAcc *acc, hipStream_t st) {
+    if (n_rows == 0) return QD_OK;
+    SumParams P{};
+    uint32_t grid = 0;
+    int V = 1;
+    sum_geometry(n_rows, p->W, p->n_cu, &P, &grid, &V);
+    P.norms = norms_d; P.acc = acc;
+    void (*fn)(SumParams) = V == 4 ? k_summary<4, 0> : k_summary<1, 0>;
+#ifdef QD_DEVELOP
+    switch (summary_layout()) {
+    case 1: fn = V == 4 ? k_summary<4, 1> : k_summary<1, 1>; break;
+    case 2: fn = V == 4 ? k_summary<4, 2> : k_summary<1, 2>; break;
+    case 3: fn = V == 4 ? k_summary<4, 3> : k_summary<1, 3>; break;
+    default: break;
+    }
+#endif
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kSumThreads), 0, st, P);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+
+// Host-resident stream: run_host's ring without the way back — each slot's chunk goes up, through the plan's norms kernel into the slot's
+// device buffer and from there into the one accumulator (atomics: the two slots' streams may fold at the same time).
+int summarize_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                   SumAcc *acc) {
+    const int bps = bps_of(p->d.format);
+    const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T, obw = (uint64_t)p->W * 4;
+    const uint64_t cw = chunk_windows(p, first_window, n_windows, std::max<uint64_t>(step * bps, obw));
+    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps);
+    const bool stage_in = src_mem == QD_MEM_HOST;
+    if (const int rc = ensure_ring(p, in_bytes, (size_t)(cw * obw), stage_in, false)) return rc;
+    auto quiesce = [&](int status) -> int {
+        for (int i = 0; i < 2; ++i) if (p->streams[i]) (void)hipStreamSynchronize(p->streams[i]);
+        return status;
+    };
+    int slot = 0;
+    for (uint64_t w = first_window; w < first_window + n_windows; w += cw, slot ^= 1) {
+        // the slot's pinned staging buffer and device buffers are reused: its previous chunk must be through
+        if (hipError_t e = hipStreamSynchronize(p->streams[slot]); e != hipSuccess) return quiesce(fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e)));
+        const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
+        const uint64_t s0 = w * step, cnt = (nw - 1) * step + rpw;
+        uint64_t s0a = s0 & ~7ull;                       // keep vector loads aligned, as run_host does
+        if (s0a < src_first) s0a = src_first;
+        const uint64_t cnta = s0 + cnt - s0a;
+        if (s0 < src_first || s0a + cnta > src_first + src_count)
+            return quiesce(fail(QD_ERR_INVALID, "src slab does not cover the requested windows"));
+        const uint8_t *hsrc = static_cast<const uint8_t *>(src) + (s0a - src_first) * bps;
+        if (stage_in) {
+            par_memcpy(p->pin_in[slot], hsrc, cnta * bps, p->opt.copy_threads);
+            hsrc = static_cast<const uint8_t *>(p->pin_in[slot]);
+        }
+        if (hipError_t e = hipMemcpyAsync(p->dev_in[slot], hsrc, cnta * bps, hipMemcpyHostToDevice, p->streams[slot]); e != hipSuccess)
+            return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(e)));
+        int rc = launch_windows(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
+        if (rc == QD_OK) rc = launch_summary(p, static_cast<const float *>(p->dev_out[slot]), nw, acc, p->streams[slot]);
+        if (rc) return quiesce(rc);
+    }
+    for (int i = 0; i < 2; ++i) HIPCHK(hipStreamSynchronize(p->streams[i]));
+    return QD_OK;
+}
+}  // namespace
+
+int qd_summary_init(qd_summary *sum, float *peak, float *floor, uint32_t width) {
+    if (!sum) return fail(QD_ERR_INVALID, "summary is NULL");
+    memset(sum, 0, sizeof *sum);
+    sum->struct_size = sizeof *sum;
+    sum->width = width;
+    sum->min = INFINITY;
+    sum->max = 0.0f;
+    for (uint32_t b = 0; b < width; ++b) {
+        if (peak) peak[b] = 0.0f;
+        if (floor) floor[b] = INFINITY;
+    }
+    return QD_OK;
+}
+
+int qd_summary_fold(qd_summary *sum, float *peak, float *floor, const float *norms, uint64_t n_rows) {
+    if (const int rc = check_summary(sum)) return rc;
+    if (n_rows == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    const uint32_t W = sum->width;
+    if (W == 0) return fail(QD_ERR_INVALID, "a summary of width 0 holds no rows");
+    float mx = sum->max, mn = sum->min;
+    uint64_t nan = 0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const float *row = norms + r * W;
+        for (uint32_t b = 0; b < W; ++b) {
+            const float x = row[b];
+            if (x != x) { ++nan; continue; }               // f32::max / f32::min ignore a NaN operand (src/ffts.rs:101-107)
+            sum->hist[(bits_of_f32(x) & 0x7fffffffu) >> 20] += 1;
+            if (x > mx) mx = x;
+            if (x < mn) mn = x;
+            if (peak && x > peak[b]) peak[b] = x;
+            if (floor && x < floor[b]) floor[b] = x;
+        }
+    }
+    sum->max = mx; sum->min = mn;
+    sum->n_nan += nan;
+    sum->n_windows += n_rows;
+    return QD_OK;
+}
+
+int qd_summary_merge(qd_summary *dst, float *dst_peak, float *dst_floor, const qd_summary *src, const float *src_peak, const float *src_floor) {
+    if (const int rc = check_summary(dst)) return rc;
+    if (const int rc = check_summary(src)) return rc;
+    if (dst->width != src->width) return fail(QD_ERR_INVALID, "summaries of different widths (%u, %u) do not merge", dst->width, src->width);
+    if ((dst_peak && !src_peak) || (dst_floor && !src_floor)) return fail(QD_ERR_INVALID, "a peak / floor array to merge into needs one to merge from");
+    for (int i = 0; i < 2048; ++i) dst->hist[i] += src->hist[i];
+    dst->n_nan += src->n_nan;
+    dst->n_windows += src->n_windows;
+    if (src->max > dst->max) dst->max = src->max;
+    if (src->min < dst->min) dst->min = src->min;
+    for (uint32_t b = 0; b < dst->width; ++b) {
+        if (dst_peak && src_peak[b] > dst_peak[b]) dst_peak[b] = src_peak[b];
+        if (dst_floor && src_floor[b] < dst_floor[b]) dst_floor[b] = src_floor[b];
+    }
+    return QD_OK;
+}
+
+int qd_summary_quantile(const qd_summary *sum, double q, float *lo, float *hi) {
+    if (const int rc = check_summary(sum)) return rc;
+    if (!(q >= 0.0 && q <= 1.0)) return fail(QD_ERR_INVALID, "quantile %g outside [0, 1]", q);
+    uint64_t N = 0;
+    for (int i = 0; i < 2048; ++i) N += sum->hist[i];
+    if (N == 0) return fail(QD_ERR_INVALID, "the summary holds no values");
+    const double want = std::ceil(q * (double)N);
+    uint64_t r = want < 1.0 ? 1 : (want >= (double)N ? N : (uint64_t)want);
+    uint64_t cum = 0;
+    uint32_t j = 0;
+    for (; j < 2048; ++j) { cum += sum->hist[j]; if (cum >= r) break; }
+    if (lo) *lo = f32_of_bits(j << 20);
+    if (hi) *hi = j >= 2040 ? INFINITY : f32_of_bits((j + 1) << 20);
+    return QD_OK;
+}
+
+int qd_plan_summarize(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                      qd_summary *sum, float *peak, float *floor, void *stream) {
+    if (!p || !sum) return fail(QD_ERR_INVALID, "NULL argument");
+    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_summarize folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
+    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not summarised in one call: summarise each shard's windows on a plan of its own and qd_summary_merge them");
+    const uint32_t W = p->W;
+    (void)qd_summary_init(sum, peak, floor, W);
+    if (first_window + n_windows > p->n_windows)
+        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
+                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
+    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    bool is_short = false;
+    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
+        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
+        is_short = true;
+    }
+    const bool dev = src_mem == QD_MEM_DEVICE;
+    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
+    if (n_windows) {
+        if (!src) return fail(QD_ERR_INVALID, "src is NULL");
+        std::lock_guard<std::mutex> lock(p->mu);
+        DeviceGuard guard(p->device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        WsLease ws(st);
+        if (ws.rc) return ws.rc;
+        // the accumulator starts from the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
+        const size_t acc_bytes = sum_acc_bytes(W);
+        std::vector<uint32_t> image(acc_bytes / 4, 0u);
+        uint32_t *ipeak = image.data() + sizeof(SumAcc) / 4, *ifloor = ipeak + W;
+        for (uint32_t b = 0; b < W; ++b) ifloor[b] = kSumInfBits;
+        void *acc_v = nullptr;
+        int rc = ws.get(1, acc_bytes, &acc_v); if (rc) return rc;
+        SumAcc *acc = static_cast<SumAcc *>(acc_v);
+        HIPCHK(hipMemcpyAsync(acc, image.data(), acc_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));                 // host path: the slots' streams fold into it too
+        if (dev) {
+            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
+            const uint64_t cw = chunk_windows(p, first_window, n_windows, (uint64_t)W * 4);
+            void *car = nullptr;
+            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
+            for (uint64_t w = first_window; w < first_window + n_windows && rc == QD_OK; w += cw) {
+                const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
+                rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, w, nw, w, car, st);
+                if (rc == QD_OK) rc = launch_summary(p, static_cast<const float *>(car), nw, acc, st);
+            }
+        } else {
+            rc = summarize_host(p, src, src_mem, src_first, src_count, first_window, n_windows, acc);
+        }
+        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(image.data(), acc, acc_bytes, hipMemcpyDeviceToHost));
+        const SumAcc *h = reinterpret_cast<const SumAcc *>(image.data());
+        memcpy(sum->hist, h->hist, sizeof sum->hist);
+        sum->n_nan = h->n_nan;
+        sum->n_windows = n_windows;
+        uint32_t mx = 0, mn = kSumInfBits;
+        for (uint32_t b = 0; b < W; ++b) {
+            mx = std::max(mx, ipeak[b]); mn = std::min(mn, ifloor[b]);
+            if (peak) peak[b] = f32_of_bits(ipeak[b]);
+            if (floor) floor[b] = f32_of_bits(ifloor[b]);
+        }
+        sum->max = f32_of_bits(mx); sum->min = f32_of_bits(mn);
+    }
+    if (is_short)
+        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
+                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
     return QD_OK;
 }
 

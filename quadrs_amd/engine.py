@@ -243,6 +243,71 @@ def rows_geometry(fmt, sample_rate, n_samples, width, output_len, slice_=None, w
     return offs[:int(output_len)], a.value, b.value
 
 
+class Summary:
+    """qd_summary with its peak / floor arrays (include/quadrs_hip.h, "level summary"): min, max, n_nan, n_windows, hist (uint64[2048]),
+    peak and floor (float32[width]).  A new one holds the fold identities (qd_summary_init)."""
+
+    def __init__(self, width):
+        self.c = _ffi.Summary()
+        self.peak = np.zeros(int(width), dtype=np.float32)
+        self.floor = np.zeros(int(width), dtype=np.float32)
+        check(lib().qd_summary_init(C.byref(self.c), _np_ptr(self.peak), _np_ptr(self.floor), int(width)))
+
+    width = property(lambda self: self.c.width)
+    n_windows = property(lambda self: self.c.n_windows)
+    n_nan = property(lambda self: self.c.n_nan)
+    min = property(lambda self: np.float32(self.c.min))
+    max = property(lambda self: np.float32(self.c.max))
+
+    @property
+    def hist(self):
+        return np.ctypeslib.as_array(self.c.hist).copy()
+
+    def fold(self, norms):
+        """qd_summary_fold: rows of `width` host float32 into this summary; returns self."""
+        a = np.ascontiguousarray(norms, dtype=np.float32).reshape(-1, self.width)
+        check(lib().qd_summary_fold(C.byref(self.c), _np_ptr(self.peak), _np_ptr(self.floor), _np_ptr(a), a.shape[0]))
+        return self
+
+    def merge(self, other):
+        """qd_summary_merge: self (+)= other; returns self."""
+        check(lib().qd_summary_merge(C.byref(self.c), _np_ptr(self.peak), _np_ptr(self.floor), C.byref(other.c), _np_ptr(other.peak),
+                                     _np_ptr(other.floor)))
+        return self
+
+    def quantile(self, q):
+        """qd_summary_quantile: the (lo, hi) float32 edges of the bucket that holds the q-quantile."""
+        lo, hi = C.c_float(), C.c_float()
+        check(lib().qd_summary_quantile(C.byref(self.c), float(q), C.byref(lo), C.byref(hi)))
+        return np.float32(lo.value), np.float32(hi.value)
+
+    def tobytes(self):
+        """every field, for bit-for-bit comparisons"""
+        return bytes(self.c) + self.peak.tobytes() + self.floor.tobytes()
+
+
+def summary_init(width):
+    """qd_summary_init: the fold identities for rows of `width` bins."""
+    return Summary(width)
+
+
+def summary_fold(norms, width=None, into=None):
+    """qd_summary_fold of host norms rows (a 2-D array, or flat with width=) into `into` or a new Summary."""
+    a = np.asarray(norms, dtype=np.float32)
+    s = into if into is not None else Summary(a.shape[-1] if width is None else width)
+    return s.fold(a)
+
+
+def summary_merge(dst, src):
+    """qd_summary_merge: dst (+)= src."""
+    return dst.merge(src)
+
+
+def summary_quantile(summary, q):
+    """qd_summary_quantile."""
+    return summary.quantile(q)
+
+
 class Plan:
     """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
@@ -419,6 +484,23 @@ class Plan:
         check(lib().qd_plan_take_fft(self._h, C.byref(r), _np_ptr(buf), MEM_HOST, src_first, buf.size // _FMT_BYTES[self.desc.format],
                                      _np_ptr(rows), MEM_HOST, None))
         return rows
+
+    def summarize(self, src, first_window=0, n_windows=None, src_first=0, pinned=False):
+        """qd_plan_summarize of an EPI_NORMS_F32 plan: the Summary (min, max, n_nan, n_windows, hist, peak, floor) of windows
+        [first_window, +n_windows) without bringing the norms back.  src: bytes / numpy array (host; pinned=True for a PinnedBuffer
+        array) or a torch CUDA tensor (device, torch's current stream) holding source samples [src_first, ...)."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        s = Summary(self.width)
+        if _is_torch(src):
+            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
+        else:
+            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+            count = buf.size // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
+        check(lib().qd_plan_summarize(self._h, ptr, mem, src_first, count, first_window, n_windows, C.byref(s.c), _np_ptr(s.peak),
+                                      _np_ptr(s.floor), st))
+        return s
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))
