@@ -399,6 +399,39 @@ int qd_summary_quantile(const qd_summary *sum, double q, float *lo, float *hi);
 int qd_plan_summarize(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
                       uint64_t first_window, uint64_t n_windows, qd_summary *sum, float *peak, float *floor, void *stream);
 
+/* ------------------------------------------------------------------ peak-hold rows of a norms plan
+ *
+ * A spectrum analyser's "max hold" picture of a whole capture: every window is transformed and each group of `pool` consecutive
+ * windows is folded per bin into one row.  Over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W there are R = ceil(n / pool)
+ * rows of W f32; row r folds windows [w0 + r pool, min(w0 + (r+1) pool, w0 + n)) — the last row may be ragged — of exactly the f32
+ * values the norms sink writes, in fftshifted bin order, by the rules of the summary's peak / floor:
+ *   peak_rows[r W + b]   fold of f32::max from 0.0 (a NaN is ignored)
+ *   floor_rows[r W + b]  fold of f32::min from +inf (a NaN is ignored)
+ * Max and min do not depend on the batch, chunk or launch order they were folded in.  pool >= n: one row, qd_plan_summarize's peak /
+ * floor bit for bit; pool == 1: the norms themselves wherever they are not NaN.  Either array may be NULL (that fold is not kept). */
+
+/* The fold identities: peak rows 0.0, floor rows +inf, `rows` rows of `width` host f32 each. */
+int qd_pool_init(float *peak_rows, float *floor_rows, uint32_t width, uint64_t rows);
+/* The CPU twin of the kernel behind qd_plan_pool, bit for bit: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32 in
+ * `norms`) ACCUMULATE into rows (at + i) / pool of peak_rows / floor_rows, which hold the range's rows from row 0 on.  Parts of a
+ * range folded in any order give the whole.  QD_ERR_INVALID: pool == 0, width == 0, both arrays NULL, or norms NULL with n > 0. */
+int qd_pool_fold(float *peak_rows, float *floor_rows, uint32_t width, uint64_t pool, uint64_t at,
+                 const float *norms, uint64_t n);
+/* The pooled rows of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and `stream`
+ * as for qd_plan_run (device, host and pinned sources).  peak_rows / floor_rows are R W f32 each of out_mem memory (host, pinned or
+ * device; either may be NULL, not both) and are OVERWRITTEN, not accumulated; the call returns after they are complete.  The windows
+ * go batch by batch through the plan's own kernel into a device carrier of at most max(chunk_bytes, one tile of windows) of norms and
+ * are folded there into an accumulator of R W words per output: the caller's arrays themselves when out_mem is device memory, else a
+ * workspace that is copied down once.
+ * Codes as qd_plan_summarize: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, pool == 0, both outputs NULL or an unknown
+ * memory kind; QD_ERR_SHORT past the sink's loop (the outputs are not touched), and for a cascade's range past
+ * qd_plan_complete_windows (every complete window of the range is folded; rows without one hold the identities);
+ * QD_ERR_UNSUPPORTED for a plan created with shards (give each device a contiguous range of ROWS on a plan of its own).
+ * n_windows == 0: QD_OK, nothing is touched. */
+int qd_plan_pool(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                 uint64_t first_window, uint64_t n_windows, uint64_t pool,
+                 float *peak_rows, float *floor_rows, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

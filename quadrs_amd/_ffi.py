@@ -26,6 +26,7 @@ SYMBOLS = [
     "qd_host_unregister", "qd_plan_kernel_name", "qd_plan_create_stages", "qd_plan_get_stage_taps",
     "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan", "qd_rows_geometry", "qd_plan_take_fft",
     "qd_summary_init", "qd_summary_fold", "qd_summary_merge", "qd_summary_quantile", "qd_plan_summarize",
+    "qd_pool_init", "qd_pool_fold", "qd_plan_pool",
 ]
 SUMMARY_BUCKETS = 2048
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
@@ -172,6 +173,9 @@ def lib():
             "qd_summary_merge": (i32, [C.POINTER(Summary), vp, vp, C.POINTER(Summary), vp, vp]),
             "qd_summary_quantile": (i32, [C.POINTER(Summary), f64, C.POINTER(f32), C.POINTER(f32)]),
             "qd_plan_summarize": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(Summary), vp, vp, vp]),
+            "qd_pool_init": (i32, [vp, vp, C.c_uint32, u64]),
+            "qd_pool_fold": (i32, [vp, vp, C.c_uint32, u64, u64, vp, u64]),
+            "qd_plan_pool": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, i32, vp]),
         }
         for name, (res, args) in sig.items():
             try:

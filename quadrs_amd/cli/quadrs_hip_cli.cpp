@@ -11,6 +11,7 @@
 // lowpasses) go to a fused cascade plan (qd_plan_create_stages), in front of write too.  Anything else (e.g. three lowpasses)
 // falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the reference's read_at()
 // computes.
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cinttypes>
@@ -95,7 +96,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -106,6 +107,7 @@ struct Op {
     size_t levels = 2;
     bool has_scan = false; double scan = 0.0;                           // marks -scan SCALE (bits::scan, src/bits.rs)
     bool overwrite = false; std::string prefix;                         // write
+    uint64_t pool = 0; bool has_count = false, want_floor = false;      // peaks (-pool P | -count R, count below)
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
 };
 
@@ -247,6 +249,34 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             v = take(m, "stride", &f);
             op.stride = f ? parse_si_u64(v) : op.width;
             ensure_empty(m);
+        } else if (cmd == "peaks") {
+            // not in the reference's grammar: the spectrum analyser's max-hold picture — every window sparkfft would print, each group of
+            // `pool` consecutive windows folded per bin into one row (qd_plan_pool)
+            auto m = no_duplicates(raw);
+            op.kind = OP_PEAKS;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            v = take(m, "pool", &f);
+            if (f) { op.pool = parse_si_u64(v); if (!op.pool) bail("peaks -pool takes a number of windows > 0"); }
+            v = take(m, "count", &f);
+            op.has_count = f;
+            op.count = f ? (size_t)parse_si_u64(v) : 2048;
+            if (op.has_count && op.pool) bail("peaks takes -pool or -count, not both");
+            if (!op.count) bail("peaks -count takes a number of rows > 0");
+            v = take(m, "range", &f);
+            if (f) {
+                size_t c = v.find(':');
+                if (c == std::string::npos) bail("range argument must contain a ':': '" + v + "'");
+                op.has_range = true;
+                op.rmin = strtof(v.substr(0, c).c_str(), nullptr);
+                op.rmax = strtof(v.substr(c + 1).c_str(), nullptr);
+            }
+            v = take(m, "floor", &f);
+            op.want_floor = f ? parse_bool(v) : false;
+            ensure_empty(m);
+            op.prefix = next("'peaks' requires a prefix argument");
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
             auto m = no_duplicates(raw);
@@ -883,6 +913,149 @@ void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
     print_levels(s.sample_rate(), sink, sum, peak);
 }
 
+// The `peaks` sink: the max-hold picture of the windows sparkfft would print (a cascade's complete windows) as
+// PREFIX.sr{rate}.w{W}x{rows}.peak.pgm (and .floor.pgm with -floor yes): row r holds, per bin, the largest (smallest) norm of windows
+// [r pool, (r+1) pool).  -pool P, or -count R for pool = max(1, ceil(windows / R)): at most R rows.  Pixels as `rows` (norm / 10 * 256 as
+// u8), or with -range lo:hi (v - lo) / (hi - lo) * 256 — the range `levels` tells the user to pass.  A chain the library fuses folds on
+// the device (qd_plan_pool on a norms plan; with -gpus N the ROWS are split into contiguous ranges, one plan each); every other chain
+// pulls its windows through the iterator chain and folds their norms with qd_pool_fold — the same bytes either way.
+struct PeakRows {
+    uint64_t windows = 0, pool = 1, rows = 0;
+    std::vector<float> peak, floor;
+    void size_for(const Op &sink, uint64_t n) {
+        windows = n;
+        pool = sink.pool ? sink.pool : std::max<uint64_t>(1, (n + sink.count - 1) / sink.count);
+        if (n && pool > n) pool = n;
+        rows = n ? (n - 1) / pool + 1 : 0;
+        peak.resize(rows * sink.width); floor.resize(rows * sink.width);
+        qd_check(qd_pool_init(peak.data(), floor.data(), (uint32_t)sink.width, rows), "pool init");
+    }
+};
+
+bool peaks_fused(const ChainSpec &cs, const Op &sink, PeakRows *out) {
+    const bool from_gen = cs.src->kind == OP_GEN;
+    std::unique_ptr<MappedFile> data;
+    if (!from_gen) data.reset(new MappedFile(cs.src->filename));
+    qd_chain_desc d{};
+    d.struct_size = sizeof d;
+    d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
+    d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate) : data->size / qd_pair_bytes(cs.src->format);
+    std::vector<qd_stage> stages;
+    if (cs.cascade) {
+        for (const Op *op : cs.stages) {
+            qd_stage st{};
+            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
+            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
+            stages.push_back(st);
+        }
+    } else {
+        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
+        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
+    }
+    d.width = sink.width; d.stride = sink.stride; d.epilogue = QD_EPI_NORMS_F32;
+    int n_dev = 1;
+    if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
+    const int parts = from_gen ? 1 : g_gpus;
+    DeviceBuf gen_src;
+    uint64_t rows_per = 0;
+    for (int g = 0; g < parts; ++g) {
+        // one unsharded plan per range of rows, made on that range's device
+        if (parts > 1) qd_check(qd_set_device(g % n_dev), "set device");
+        qd_plan *plan = nullptr;
+        const int rc = cs.cascade ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan) : qd_plan_create(&d, &plan);
+        if (rc == QD_ERR_UNSUPPORTED && g == 0) return false;
+        qd_check(rc, "plan");
+        if (g == 0) {
+            uint64_t complete = 0;
+            qd_check(qd_plan_complete_windows(plan, &complete), "plan complete windows");
+            out->size_for(sink, complete);
+            qd_plan_info info;
+            qd_check(qd_plan_get_info(plan, &info), "plan info");
+            // ranges of whole rows that start on a tile of windows where the pool allows it, as the library's own shards do
+            uint64_t tile = info.tile_windows ? info.tile_windows : 1, a = tile, b = out->pool;
+            while (b) { const uint64_t t = a % b; a = b; b = t; }
+            const uint64_t q = tile / a;
+            rows_per = ((out->rows + parts - 1) / parts + q - 1) / q * q;
+        }
+        const uint64_t r0 = std::min<uint64_t>(out->rows, rows_per * g), r1 = std::min<uint64_t>(out->rows, rows_per * (g + 1));
+        const uint64_t w0 = r0 * out->pool, w1 = std::min<uint64_t>(out->windows, r1 * out->pool);
+        int rr = QD_OK;
+        if (w1 > w0 && from_gen) {
+            qd_check(qd_device_alloc((size_t)d.n_samples * 8, &gen_src.p), "device buffer for gen");
+            const uint64_t piece = 1ull << 28;
+            for (uint64_t at = 0; at < d.n_samples; at += piece) {
+                const uint64_t n = d.n_samples - at < piece ? d.n_samples - at : piece;
+                qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, at, (size_t)n, static_cast<qd_c32 *>(gen_src.p) + at, QD_MEM_DEVICE), "gen");
+            }
+            rr = qd_plan_pool(plan, gen_src.p, QD_MEM_DEVICE, 0, d.n_samples, w0, w1 - w0, out->pool, out->peak.data(), out->floor.data(), QD_MEM_HOST, nullptr);
+        } else if (w1 > w0) {
+            rr = qd_plan_pool(plan, data->p, data->mem, 0, d.n_samples, w0, w1 - w0, out->pool, out->peak.data() + r0 * sink.width,
+                              out->floor.data() + r0 * sink.width, QD_MEM_HOST, nullptr);
+        }
+        qd_plan_destroy(plan);
+        qd_check(rr, "pool");
+    }
+    if (parts > 1) qd_check(qd_set_device(0), "set device");
+    return true;
+}
+
+void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    if (!W || (W & (W - 1))) bail("Radix4 algorithm requires a power-of-two input size");
+    if (S == 0) bail("stride 0 never terminates");
+    if (W > 0xffffffffull) bail("width too large");
+    if (sink.has_range && !(sink.rmax > sink.rmin)) bail("peaks -range takes lo:hi with lo < hi");
+    PeakRows pr;
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = peaks_fused(*cs, sink, &pr);
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+        uint64_t len = s.len();
+        if (len < W) bail("attempt to subtract with overflow");
+        const uint64_t lim = len - W;
+        uint64_t nwin = lim == 0 ? 0 : (lim - 1) / S + 1;
+        std::vector<qd_c32> buf(W);
+        while (nwin) {
+            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+        }
+        pr.size_for(sink, nwin);
+        // their norms from a side-by-side norms plan, folded on the host
+        const uint64_t batch = 4096;
+        buf.resize(batch * W);
+        std::vector<float> norms(batch * W);
+        for (uint64_t w0 = 0; w0 < nwin; w0 += batch) {
+            const uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
+            for (uint64_t i = 0; i < nb; ++i) s.read_exact_at((w0 + i) * S, buf.data() + i * W, W);
+            qd_chain_desc d{};
+            d.struct_size = sizeof d;
+            d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
+            d.width = W; d.stride = W; d.epilogue = QD_EPI_NORMS_F32;
+            qd_plan *plan = nullptr;
+            qd_check(qd_plan_create(&d, &plan), "plan");
+            const int rc = qd_plan_run(plan, buf.data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms.data(), QD_MEM_HOST, nullptr);
+            qd_plan_destroy(plan);
+            qd_check(rc, "run");
+            qd_check(qd_pool_fold(pr.peak.data(), pr.floor.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
+        }
+    }
+    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "x" + std::to_string(pr.rows);
+    const std::string head = "P5\n" + std::to_string(W) + " " + std::to_string(pr.rows) + "\n255\n";
+    const float lo = sink.has_range ? sink.rmin : 0.f, span = sink.has_range ? sink.rmax - sink.rmin : 10.f;
+    std::vector<uint8_t> px(pr.peak.size());
+    for (int which = 0; which < (sink.want_floor ? 2 : 1); ++which) {
+        const std::vector<float> &rows = which ? pr.floor : pr.peak;
+        const std::string fn = stem + (which ? ".floor.pgm" : ".peak.pgm");
+        int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
+        for (size_t i = 0; i < rows.size(); ++i) {
+            const float v = (sink.has_range ? rows[i] - lo : rows[i]) / span * 256.f;      // `as u8`: saturating, NaN -> 0
+            px[i] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
+        }
+        if (write(fd, head.data(), head.size()) < 0 || (px.size() && write(fd, px.data(), px.size()) < 0)) { close(fd); bail("write failed"); }
+        close(fd);
+    }
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -893,6 +1066,7 @@ void usage() {
             "  bucket [-width 128] [-stride =width] -by freq COUNT \\\n"
             "   marks [-width 128] [-stride =width] [-min 0.08] [-scan SCALE] \\\n"
             "  levels [-width 128] [-stride =width] \\\n"
+            "   peaks [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] [-floor no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -929,6 +1103,10 @@ int main(int argc, char **argv) {
                 case OP_BUCKET: printf("bucket width=%zu stride=%llu levels=%zu\n", op.width, (unsigned long long)op.stride, op.levels); break;
                 case OP_MARKS: printf("marks width=%zu stride=%llu min=%s scan=%s\n", op.width, (unsigned long long)op.stride, op.has_range ? "yes" : "no", op.has_scan ? "yes" : "no"); break;
                 case OP_LEVELS: printf("levels width=%zu stride=%llu\n", op.width, (unsigned long long)op.stride); break;
+                case OP_PEAKS:
+                    printf("peaks width=%zu stride=%llu %s=%llu range=%s floor=%d\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
+                           (unsigned long long)(op.pool ? op.pool : op.count), op.has_range ? "yes" : "no", op.want_floor ? 1 : 0);
+                    break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 case OP_ROWS:
                     printf("rows width=%zu count=%zu slice=%s window=%s\n", op.width, op.count,
@@ -982,6 +1160,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("levels requires an input");
                 cs.cascade = !chain_clean;
                 do_levels(*samples, op, &cs);
+                break;
+            case OP_PEAKS:
+                if (!samples) bail("peaks requires an input");
+                cs.cascade = !chain_clean;
+                do_peaks(*samples, op, &cs);
                 break;
             case OP_ROWS:
                 if (!samples) bail("rows requires an input");

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -30,6 +31,7 @@
 #include "qd_cascade.h"
 #include "qd_registry.h"
 #include "qd_summary.h"
+#include "qd_pool.h"
 
 using namespace qd;
 
@@ -3210,9 +3212,11 @@ int launch_summary(const qd_plan *p, const float *norms_d, uint64_t n_rows, SumA
 }
 
 // Host-resident stream: run_host's ring without the way back — each slot's chunk goes up, through the plan's norms kernel into the slot's
-// device buffer and from there into the one accumulator (atomics: the two slots' streams may fold at the same time).
-int summarize_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
-                   SumAcc *acc) {
+// device buffer and from there, by fold(norms, first window, windows, stream), into the one accumulator (atomics: the two slots' streams
+// may fold at the same time).
+using HostFold = std::function<int(const float *, uint64_t, uint64_t, hipStream_t)>;
+int fold_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+              const HostFold &fold) {
     const int bps = bps_of(p->d.format);
     const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T, obw = (uint64_t)p->W * 4;
     const uint64_t cw = chunk_windows(p, first_window, n_windows, std::max<uint64_t>(step * bps, obw));
@@ -3242,7 +3246,7 @@ int summarize_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first,
         if (hipError_t e = hipMemcpyAsync(p->dev_in[slot], hsrc, cnta * bps, hipMemcpyHostToDevice, p->streams[slot]); e != hipSuccess)
             return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(e)));
         int rc = launch_windows(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
-        if (rc == QD_OK) rc = launch_summary(p, static_cast<const float *>(p->dev_out[slot]), nw, acc, p->streams[slot]);
+        if (rc == QD_OK) rc = fold(static_cast<const float *>(p->dev_out[slot]), w, nw, p->streams[slot]);
         if (rc) return quiesce(rc);
     }
     for (int i = 0; i < 2; ++i) HIPCHK(hipStreamSynchronize(p->streams[i]));
@@ -3369,7 +3373,8 @@ int qd_plan_summarize(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
                 if (rc == QD_OK) rc = launch_summary(p, static_cast<const float *>(car), nw, acc, st);
             }
         } else {
-            rc = summarize_host(p, src, src_mem, src_first, src_count, first_window, n_windows, acc);
+            rc = fold_host(p, src, src_mem, src_first, src_count, first_window, n_windows,
+                           [&](const float *norms_d, uint64_t, uint64_t nw, hipStream_t s) { return launch_summary(p, norms_d, nw, acc, s); });
         }
         if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
         if (rc) return rc;
@@ -3385,6 +3390,126 @@ int qd_plan_summarize(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
             if (floor) floor[b] = f32_of_bits(ifloor[b]);
         }
         sum->max = f32_of_bits(mx); sum->min = f32_of_bits(mn);
+    }
+    if (is_short)
+        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
+                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
+    return QD_OK;
+}
+
+// ------------------------------------------------------------------ peak-hold rows
+
+namespace {
+// one batch of norms rows (device memory, 16-byte aligned) — windows [g0, g0 + nw) of a range of n_total — into the R x W accumulators, on `st`
+int launch_pool(const qd_plan *p, const float *norms_d, uint64_t g0, uint64_t nw, uint64_t n_total, uint64_t pool, uint32_t *peak_d,
+                uint32_t *floor_d, hipStream_t st) {
+    if (nw == 0) return QD_OK;
+    PoolParams P{};
+    uint64_t grid = 0;
+    int V = 1;
+    pool_geometry(g0, nw, n_total, pool, p->W, p->n_cu, &P, &grid, &V);
+    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)nw);
+    P.norms = norms_d; P.peak = peak_d; P.floor = floor_d;
+    P.vec_store = (((uintptr_t)peak_d | (uintptr_t)floor_d) & 15) == 0;
+    hipLaunchKernelGGL(V == 4 ? k_pool<4> : k_pool<1>, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, P);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+}  // namespace
+
+int qd_pool_init(float *peak_rows, float *floor_rows, uint32_t width, uint64_t rows) {
+    const uint64_t n = (uint64_t)width * rows;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (peak_rows) peak_rows[i] = 0.0f;
+        if (floor_rows) floor_rows[i] = INFINITY;
+    }
+    return QD_OK;
+}
+
+int qd_pool_fold(float *peak_rows, float *floor_rows, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!peak_rows && !floor_rows) return fail(QD_ERR_INVALID, "both peak_rows and floor_rows are NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        const uint64_t o = (at + i) / pool * width;
+        for (uint32_t b = 0; b < width; ++b) {
+            const float x = row[b];
+            if (x != x) continue;                                  // f32::max / f32::min ignore a NaN operand (src/ffts.rs:101-107)
+            if (peak_rows && x > peak_rows[o + b]) peak_rows[o + b] = x;
+            if (floor_rows && x < floor_rows[o + b]) floor_rows[o + b] = x;
+        }
+    }
+    return QD_OK;
+}
+
+int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                 uint64_t pool, float *peak_rows, float *floor_rows, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_pool folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (!peak_rows && !floor_rows) return fail(QD_ERR_INVALID, "both peak_rows and floor_rows are NULL");
+    const bool dev = src_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
+    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
+    if (!out_dev && !host_kind(out_mem)) return fail(QD_ERR_INVALID, "unknown out_mem %d", out_mem);
+    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not pooled in one call: give each device a contiguous range of rows on a plan of its own");
+    if (first_window + n_windows > p->n_windows)
+        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
+                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
+    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    if (n_windows == 0) return QD_OK;
+    if (pool > n_windows) pool = n_windows;                          // one row either way
+    const uint32_t W = p->W;
+    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;
+    bool is_short = false;
+    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
+        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
+        is_short = true;
+    }
+    if (n_windows && !src) return fail(QD_ERR_INVALID, "src is NULL");
+    {
+        std::lock_guard<std::mutex> lock(p->mu);
+        DeviceGuard guard(p->device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        WsLease ws(st);
+        if (ws.rc) return ws.rc;
+        // the accumulators: the caller's arrays when they are device memory, else [peak][floor] in the workspace
+        uint32_t *peak_d = reinterpret_cast<uint32_t *>(peak_rows), *floor_d = reinterpret_cast<uint32_t *>(floor_rows);
+        int rc = QD_OK;
+        if (!out_dev) {
+            void *acc = nullptr;
+            rc = ws.get(1, (size_t)(words * 4 * ((peak_rows ? 1 : 0) + (floor_rows ? 1 : 0))), &acc); if (rc) return rc;
+            peak_d = peak_rows ? static_cast<uint32_t *>(acc) : nullptr;
+            floor_d = floor_rows ? static_cast<uint32_t *>(acc) + (peak_rows ? words : 0) : nullptr;
+        }
+        // the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
+        if (peak_d) HIPCHK(hipMemsetAsync(peak_d, 0, (size_t)(words * 4), st));
+        if (floor_d) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(floor_d), (int)kPoolInfBits, (size_t)words, st));
+        if (n_windows && dev) {
+            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
+            const uint64_t cw = chunk_windows(p, first_window, n_windows, (uint64_t)W * 4);
+            void *car = nullptr;
+            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
+            for (uint64_t w = first_window; w < first_window + n_windows && rc == QD_OK; w += cw) {
+                const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
+                rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, w, nw, w, car, st);
+                if (rc == QD_OK) rc = launch_pool(p, static_cast<const float *>(car), w - first_window, nw, n_windows, pool, peak_d, floor_d, st);
+            }
+        } else if (n_windows) {
+            HIPCHK(hipStreamSynchronize(st));             // the slots' streams fold into the accumulators too
+            rc = fold_host(p, src, src_mem, src_first, src_count, first_window, n_windows,
+                           [&](const float *norms_d, uint64_t w, uint64_t nw, hipStream_t s) {
+                               return launch_pool(p, norms_d, w - first_window, nw, n_windows, pool, peak_d, floor_d, s);
+                           });
+        }
+        if (rc == QD_OK && !out_dev) {
+            if (peak_rows) HIPCHK(hipMemcpyAsync(peak_rows, peak_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+            if (floor_rows) HIPCHK(hipMemcpyAsync(floor_rows, floor_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+        }
+        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        if (rc) return rc;
     }
     if (is_short)
         return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",

@@ -308,6 +308,27 @@ def summary_quantile(summary, q):
     return summary.quantile(q)
 
 
+def pool_init(width, rows):
+    """qd_pool_init: (peak_rows, floor_rows), float32[rows, width] each, holding the fold identities 0.0 / +inf."""
+    peak = np.empty((int(rows), int(width)), dtype=np.float32)
+    floor = np.empty((int(rows), int(width)), dtype=np.float32)
+    check(lib().qd_pool_init(_np_ptr(peak), _np_ptr(floor), int(width), int(rows)))
+    return peak, floor
+
+
+def pool_fold(norms, pool, at=0, into=None):
+    """qd_pool_fold: norms rows (n, width) are windows at, at+1, ... of a range and accumulate into rows (at + i) // pool of
+    into=(peak_rows, floor_rows) (either may be None), or of new arrays of ceil((at + n) / pool) rows.  Returns (peak_rows, floor_rows)."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = pool_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
+    peak, floor = into
+    check(lib().qd_pool_fold(_np_ptr(peak) if peak is not None else None, _np_ptr(floor) if floor is not None else None, width, int(pool),
+                             int(at), _np_ptr(a), n))
+    return peak, floor
+
+
 class Plan:
     """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
@@ -501,6 +522,33 @@ class Plan:
         check(lib().qd_plan_summarize(self._h, ptr, mem, src_first, count, first_window, n_windows, C.byref(s.c), _np_ptr(s.peak),
                                       _np_ptr(s.floor), st))
         return s
+
+    def pool(self, src, pool, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None):
+        """qd_plan_pool of an EPI_NORMS_F32 plan: (peak_rows, floor_rows), float32[ceil(n_windows / pool), width] each — per bin the max /
+        min over each group of `pool` consecutive windows of [first_window, +n_windows).  src as for summarize.  device_out: the rows as
+        torch CUDA tensors (the default for a torch src) instead of numpy arrays."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
+        if _is_torch(src):
+            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
+        else:
+            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+            count = buf.size // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
+        if _is_torch(src) if device_out is None else device_out:
+            import torch
+            peak, floor = (torch.empty((rows, self.width), dtype=torch.float32, device="cuda") for _ in range(2))
+            pp, fp, out_mem = C.c_void_p(peak.data_ptr()), C.c_void_p(floor.data_ptr()), MEM_DEVICE
+        else:
+            peak, floor = (np.empty((rows, self.width), dtype=np.float32) for _ in range(2))
+            pp, fp, out_mem = _np_ptr(peak), _np_ptr(floor), MEM_HOST
+        try:
+            check(lib().qd_plan_pool(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), pp, fp, out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = (peak, floor)            # QD_ERR_SHORT of a cascade: the complete windows are folded
+            raise
+        return peak, floor
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))
