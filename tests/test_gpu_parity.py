@@ -440,6 +440,12 @@ def test_fused_chain_matches_oracle(engine, oracle, fmt, N, shift, lp, W, S):
 
 
 def test_glyph_and_bucket_epilogues(engine, oracle, fsk):
+    """Glyph codes and bucket digits of a shifted chain on the fsk capture, and bucket digits of a hopping tone.
+
+    The ulp excuse for bucket digits below (half sums within 4 ulp of each other) exists only because this chain has a shift stage:
+    an NCO multiplier next to an f32 rounding boundary moves a norm by an ulp, and a near-tie with it.  It does not hold the ORDER
+    of the half sums: the streams here put the halves percents apart, where any order gives the same digit.  That the sums are the
+    reference's two ascending sequential f32 sums, and that a tie gives 1, is held by tests/test_gpu_bucket_order.py."""
     n = 40_000
     data = fsk[: n * 8]
     ch = oracle.Chain.from_bytes(data, 0, 21_000_000).shift(280000).lowpass(2_000_000, 16, 40)

@@ -366,7 +366,12 @@ def codes_edge_ok(ref_codes, got_codes, ref_norms, rmin, rmax, k_ulp=4):
 
 def bucket_digits_ok(ref_norms, got_digits):
     """bucket digits (src/fft.rs:95-97: two sequential f32 half sums of the norms in natural bin order) against the oracle's norms
-    of the same windows; a digit may differ only where the two sums tie within 8 ulp"""
+    of the same windows; a digit may differ only where the two sums tie within 8 ulp
+
+    What the excuse is for: chains with a shift stage, where an NCO multiplier next to an f32 rounding boundary moves a norm by an
+    ulp and with it a near-tie (the NCO rule).  It says nothing about the ORDER of the sums — on streams whose halves tie it accepts
+    the digits of a pairwise summation (test_bucket_order_cpu.py asserts that).  Exactness of the sum order and of the tie rule is
+    held by test_gpu_bucket_order.py, on shift-free chains, without any excuse."""
     W = ref_norms.shape[1]
     nat = np.roll(ref_norms, W // 2, axis=1)                       # the sparkfft rows' fftshift undone
     first = np.cumsum(nat[:, : W // 2], axis=1, dtype=np.float32)[:, -1] if W > 1 else np.zeros(len(nat), np.float32)
@@ -1158,3 +1163,220 @@ def mixed_scale(norms, side=1):
         if both > best[1]:
             best = (side * k, both)
     return best
+
+
+# ------------------------------------------------------------------ the bucket sink's half-sum order (test_bucket_order_cpu.py)
+#
+# freq_levels reduces a window to first < second ? 0 : 1 with two sequential f32 sums of |X| over the natural bins 0 ... W/2-1 and
+# W/2 ... W-1 (src/fft.rs:95-97).  On a real-valued stream |X[k]| = |X[W-k]|: `second` is `first`'s multiset with |X[W/2]| in place
+# of |X[0]|, summed in the opposite order.  Where the window's odd-indexed samples sum to zero, X[0] and X[W/2] agree up to the
+# FFT's own rounding, and only the summation order and the tie rule decide the digit.  The builders below make such windows.
+
+SUM_ORDERS = ("sequential", "pairwise", "f64", "reversed", "shifted_halves")
+
+
+def _oracle_chain(oracle, data, fmt, sr, stages):
+    ch = oracle.Chain.from_bytes(data, fmt, sr)
+    for kind, arg in stages:
+        ch = ch.shift(arg) if kind == "shift" else ch.lowpass(*arg)
+    return ch
+
+
+def balanced_geometry(stages, W, S):
+    """(span, step, q) of a list of lowpass triples, composed source to sink: the source samples one window reads
+    ((W D2 + T2) D1 + T1), the source samples between window starts (S D1 D2), and q = ceil(span / step): windows 0, q, 2q, ...
+    read disjoint source spans."""
+    span, step = int(W), int(S)
+    for _, D, T in reversed(list(stages)):
+        span, step = span * int(D) + int(T), step * int(D)
+    return span, step, -(-span // step)
+
+
+def balanced_real_stream(oracle, stages, W, S, n_balanced, seed, sr):
+    """A cf32 stream with zero imaginary part (real part ~ 0.25 N(0, 1)) in which windows 0, q, 2q, ... (n_balanced of them) of the
+    chain  lowpass* | width W stride S  have odd-indexed samples that sum to zero up to f32 rounding.  `stages`: lowpass triples
+    (frequency, decimate, size), possibly none; no shift.  Each balanced window owns one source sample n0 at an odd offset near
+    the middle of its span; the chain is linear, so with L the f64 sum of the window's odd outputs (oracle read_at: what the sink
+    reads, tail truncation included) and G the same sum for a unit impulse at n0, x[n0] - L / G balances the window.  Only the
+    oracle computes here.  Returns (x float32 (n, 2), the balanced windows' indices)."""
+    stages = [tuple(int(v) for v in lp) for lp in stages]
+    span, step, q = balanced_geometry(stages, W, S)
+    balanced = np.arange(n_balanced, dtype=np.int64) * q
+    n = (int(balanced[-1]) + 3) * step + span + step
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, 2), dtype=np.float32)
+    x[:, 0] = (0.25 * rng.standard_normal(n)).astype(np.float32)
+    lps = [("lowpass", lp) for lp in stages]
+    # the offset of n0 in its span: odd, near the middle, and the phase (of the 2 prod(D) a pair of outputs spans) at which a unit
+    # impulse reaches the window's odd outputs with the largest gain |G|; found on window 0 of a probe stream
+    period = 2 * (step // int(S))
+    cands = [((span // 2) | 1) + 2 * j for j in range(period // 2) if ((span // 2) | 1) + 2 * j < span]
+    probe = np.zeros((span + step, 2), dtype=np.float32)
+    gains = []
+    for c in cands:
+        probe[c, 0] = 1.0
+        ng, g = _oracle_chain(oracle, probe, 0, sr, lps).read_at(0, W)
+        assert ng == W, (c, ng)
+        gains.append(abs(float(g[1::2, 0].astype(np.float64).sum())))
+        probe[c, 0] = 0.0
+    off = cands[int(np.argmax(gains))]
+    n0 = balanced * step + off
+    e = np.zeros((n, 2), dtype=np.float32)
+    e[n0, 0] = 1.0
+    cx, ce = _oracle_chain(oracle, x, 0, sr, lps), _oracle_chain(oracle, e, 0, sr, lps)
+    for w, at in zip(balanced, n0):
+        (ny, y), (ng, g) = cx.read_at(int(w) * S, W), ce.read_at(int(w) * S, W)
+        assert ny == W and ng == W, (int(w), ny, ng)
+        L = float(y[1::2, 0].astype(np.float64).sum())
+        G = float(g[1::2, 0].astype(np.float64).sum())
+        assert abs(G) >= 0.999 * max(gains) > 0.0, (int(w), G, max(gains))      # every balanced window sees the probe's gain
+        x[at, 0] = np.float32(float(x[at, 0]) - L / G)
+    return x, balanced
+
+
+def balanced_cs8_stream(n, seed):
+    """cs8 codes (n, 2) int8, n a multiple of 4, with x[4m+1] = a_m, x[4m+3] = -a_m and imaginary codes 0: cs8 unpacks as
+    code / 127 (odd-symmetric, 0 -> 0), so every window of 4k samples that starts at an even sample is balanced exactly."""
+    assert n % 4 == 0
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, 2), dtype=np.int8)
+    x[0::2, 0] = rng.integers(-128, 128, n // 2)
+    a = rng.integers(-127, 128, n // 4)
+    x[1::4, 0], x[3::4, 0] = a, -a
+    return x
+
+
+def _half_sums(half, order):
+    """f32 (f64 for "f64") sums of the rows of `half` (n, m) in the given order"""
+    if half.shape[1] == 0:
+        return np.zeros(half.shape[0], np.float64 if order == "f64" else np.float32)
+    if order == "f64":
+        return half.astype(np.float64).sum(axis=1)
+    if order == "reversed":
+        half = half[:, ::-1]
+    if order == "pairwise":
+        h = half.astype(np.float32)
+        while h.shape[1] > 1:
+            h = h[:, 0::2] + h[:, 1::2]                     # float32 + float32: one rounding per node of the tree
+        return h[:, 0]
+    return np.cumsum(half, axis=1, dtype=np.float32)[:, -1]
+
+
+def digits_from_norms(norms, order):
+    """freq_levels digits from the oracle's sparkfft norms (n_windows, W) (the rows' fftshift undone, as in bucket_digits_ok),
+    with the two half sums formed in `order`:
+      "sequential"      ascending over the natural bins, f32 (src/fft.rs:95-97; what the engine must do)
+      "pairwise"        a balanced f32 tree over adjacent bins (a wave reduction)
+      "f64"             f64 sums, compared in f64
+      "reversed"        descending over the natural bins, f32
+      "shifted_halves"  sequential over the halves of the fftshifted row: the two sums change places
+    first < second gives 0, anything else (a tie included) 1."""
+    assert order in SUM_ORDERS, order
+    norms = np.asarray(norms, dtype=np.float32)
+    W = norms.shape[1]
+    nat = norms if order == "shifted_halves" else np.roll(norms, W // 2, axis=1)
+    first, second = _half_sums(nat[:, : W // 2], order), _half_sums(nat[:, W // 2:], order)
+    return np.where(first < second, 0, 1).astype(np.uint8)
+
+
+def exact_ties(norms):
+    """windows of the oracle's sparkfft norms whose two sequential f32 half sums are equal"""
+    norms = np.asarray(norms, dtype=np.float32)
+    W = norms.shape[1]
+    nat = np.roll(norms, W // 2, axis=1)
+    return _half_sums(nat[:, : W // 2], "sequential") == _half_sums(nat[:, W // 2:], "sequential")
+
+
+class BucketOrderCase:
+    """one chain of test_gpu_bucket_order.py / test_bucket_order_cpu.py: the balanced stream it runs on and the plan it must come
+    out as.  shift: None, or 0 — a `shift 0` stage multiplies by exactly (1, 0), so the stream stays real and the chain exact; it is
+    how the built-in kernels of the shapes that exist only with a shift stage are reached.  policy: "auto" / "generic" /
+    "specialise" / "builtin" (QD_KERNEL_NO_PLAN_TIME: the built-in kernel whatever the code-object cache holds); family(info, kernel name) says whether the plan is the intended kernel."""
+
+    def __init__(self, name, stages, W, S, n_balanced, family, fmt=0, sr=21_000_000, shift=None, policy="auto", tile_hint=None, paths=False,
+                 seed=20261018):
+        self.name, self.stages, self.W, self.S, self.n_balanced, self.family = name, [tuple(lp) for lp in stages], W, S, n_balanced, family
+        self.fmt, self.sr, self.shift, self.policy, self.tile_hint, self.paths, self.seed = fmt, sr, shift, policy, tile_hint, paths, seed
+
+    def __repr__(self):
+        return self.name
+
+    def stream_key(self):
+        return (self.fmt, self.sr, tuple(self.stages), self.W, self.S, self.n_balanced, self.seed)
+
+    def chain_stages(self):
+        return ([("shift", self.shift)] if self.shift is not None else []) + [("lowpass", lp) for lp in self.stages]
+
+
+_BUCKET_STREAMS = {}
+
+
+def bucket_order_stream(oracle, case):
+    """(the stream's bytes as a uint8 array, the balanced windows' indices) of a BucketOrderCase; built once per stream_key"""
+    key = case.stream_key()
+    if key not in _BUCKET_STREAMS:
+        if case.fmt == 0:
+            x, bal = balanced_real_stream(oracle, case.stages, case.W, case.S, case.n_balanced, case.seed, case.sr)
+        else:
+            assert case.fmt == 1 and not case.stages and case.W % 4 == 0 and case.S % 2 == 0, case
+            x = balanced_cs8_stream((case.n_balanced + 1) * case.S + case.W, case.seed)
+            bal = np.arange(case.n_balanced, dtype=np.int64)
+        raw = np.ascontiguousarray(x).view(np.uint8).reshape(-1)
+        raw.setflags(write=False)
+        _BUCKET_STREAMS[key] = (raw, bal)
+    return _BUCKET_STREAMS[key]
+
+
+def _fam(kind=None, kernel=None, flags=0, no_flags=0, eq_flags=None, part=None):
+    def ok(info, name):
+        return ((kind is None or int(info.kernel_kind) == kind) and (kernel is None or name.startswith(f"qd::{kernel}<"))
+                and (int(info.kernel_flags) & flags) == flags and not (int(info.kernel_flags) & no_flags)
+                and (eq_flags is None or int(info.kernel_flags) == eq_flags) and (part is None or part in name))
+    return ok
+
+
+_CFG2, _CFG3P, _CFG3, _CFG4, _D12 = (2_000_000, 16, 40), (200_000, 32, 200), (200_000, 32, 400), (5_000_000, 8, 512), (1_500_000, 12, 48)
+_CASC = [(200_000, 4, 40), (30_000, 4, 64)]
+_SPARK, _SPARK2, _SPARK0 = 524288, 1048576, 2097152
+_GENERIC = _fam(kind=0, part="DynGeo")
+
+# Every place that forms the bucket digit, on the smallest shape that selects it (DESIGN section 4, "the order contract").
+BUCKET_ORDER_CASES = [
+    # built-in FixedGeo kernels.  cfg2, cfg3' and the 64 / 16 FSK chain are built in with a shift stage only: `shift 0` reaches them
+    BucketOrderCase("builtin-cfg2", [_CFG2], 128, 128, 100, _fam(kind=1, kernel="k_chain", eq_flags=65800), shift=0, policy="builtin"),
+    BucketOrderCase("builtin-cfg3p-deferred-fft", [_CFG3P], 128, 128, 100, _fam(kind=1, kernel="k_chain", eq_flags=65868), shift=0, paths=True, policy="builtin"),
+    BucketOrderCase("builtin-cfg4", [_CFG4], 1024, 1024, 40, _fam(kind=1, kernel="k_chain", eq_flags=8392), sr=100_000_000, policy="builtin"),
+    BucketOrderCase("builtin-cfg3-streaming", [_CFG3], 64, 16, 100, _fam(kind=1, kernel="k_chain_pipe3s", eq_flags=164128), shift=0, policy="builtin"),
+    # the streaming three-stage kernel as the plan-time build of the same shape without a shift stage
+    BucketOrderCase("cfg3-streaming", [_CFG3], 64, 16, 100, _fam(kind=2, kernel="k_chain_pipe3s", flags=32768 | 131072), policy="specialise"),
+    # policies: runtime geometry (k_chain phase 4) and plan-time builds; a shape without a built-in kernel
+    BucketOrderCase("cfg2-generic", [_CFG2], 128, 128, 100, _GENERIC, policy="generic"),
+    BucketOrderCase("cfg2-specialise", [_CFG2], 128, 128, 100, _fam(kind=2, kernel="k_chain"), policy="specialise"),
+    BucketOrderCase("cfg3p-generic", [_CFG3P], 128, 128, 100, _GENERIC, policy="generic"),
+    BucketOrderCase("cfg3p-specialise", [_CFG3P], 128, 128, 100, _fam(kind=2, kernel="k_chain", flags=4 | 64), policy="specialise"),
+    BucketOrderCase("d12-specialise", [_D12], 256, 256, 100, _fam(kind=2, kernel="k_chain"), policy="specialise"),
+    # wave-local kernels without a lowpass: the built-in runtime-width k_spark, its plan-time builds (the lean path from W = 8), k_spark2
+    BucketOrderCase("spark-w8", [], 8, 8, 300, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="builtin"),
+    BucketOrderCase("spark-w16", [], 16, 16, 300, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="builtin"),
+    BucketOrderCase("spark-w64", [], 64, 64, 300, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="builtin"),
+    BucketOrderCase("spark-w128", [], 128, 128, 300, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="builtin"),
+    BucketOrderCase("spark-w1024", [], 1024, 1024, 100, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="builtin"),
+    BucketOrderCase("spark-w8-lean", [], 8, 8, 300, _fam(kind=2, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="specialise"),
+    BucketOrderCase("spark-w16-lean", [], 16, 16, 300, _fam(kind=2, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="specialise"),
+    BucketOrderCase("spark-w64-lean", [], 64, 64, 300, _fam(kind=2, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), policy="specialise"),
+    BucketOrderCase("spark2-w128", [], 128, 128, 300, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), policy="specialise"),
+    BucketOrderCase("spark2-w1024", [], 1024, 1024, 100, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), policy="specialise"),
+    BucketOrderCase("spark-cs8-w128", [], 128, 128, 300, _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0), fmt=1, policy="builtin"),
+    BucketOrderCase("spark2-cs8-w128", [], 128, 128, 300, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), fmt=1, policy="specialise"),
+    # overlapping windows without a lowpass: a window per lane (k_spark0); k_spark2 built for the stride; W = 64 / S = 16, which the
+    # interleaved launches serve for the norms and glyph sinks only (chain_candidates): the bucket sink runs it on the chain kernel
+    BucketOrderCase("spark0-w4-s2", [], 4, 2, 300, _fam(kind=2, kernel="k_spark0", flags=_SPARK | _SPARK0), policy="specialise"),
+    BucketOrderCase("spark0-w8-s2", [], 8, 2, 300, _fam(kind=2, kernel="k_spark0", flags=_SPARK | _SPARK0), policy="specialise"),
+    BucketOrderCase("spark2-w128-s32", [], 128, 32, 300, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), policy="specialise"),
+    BucketOrderCase("overlap-w64-s16-specialise", [], 64, 16, 300, _fam(kind=2, kernel="k_chain", no_flags=_SPARK), policy="specialise", paths=True),
+    BucketOrderCase("overlap-w64-s16-generic", [], 64, 16, 300, _GENERIC, policy="generic"),
+    # the cascade kernel (lane 0 sums) and the two-stage plan (a window past the LDS tile: the sink is its second stage's)
+    BucketOrderCase("cascade-w16-s8", _CASC, 16, 8, 200, _fam(part="qd::k_cascade<0>"), sr=2_000_000),
+    BucketOrderCase("cascade-w128", _CASC, 128, 128, 100, _fam(part="qd::k_cascade<0>"), sr=2_000_000),
+    BucketOrderCase("two-stage-w1024", [_CFG3P], 1024, 1024, 40, _fam(part="two stages:"), seed=20261019),      # (the table's seed: no exact tie in 40 windows)
+]
