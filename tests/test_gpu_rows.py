@@ -14,7 +14,7 @@ import pytest
 from test_gpu_footprint import FootprintRun, framed, framed_out
 from test_gpu_parity import assert_explained, record_observed
 from test_gpu_robustness import _synth_bytes
-from util import FMT_BYTES, GUARD_BYTE, POISON_WORDS, bits_equal
+from util import FMT_BYTES, GUARD_BYTE, POISON_WORDS, bits_equal, real_ties
 
 pytestmark = pytest.mark.gpu
 
@@ -170,9 +170,15 @@ def test_bluestein_rows(engine, oracle, fsk, W, out_len, fmt, chain):
 
 
 def test_bluestein_rows_behind_a_shift(engine, oracle, fsk):
-    """cf32, shift 280000, W = 100: the same bound, no excuses (a near-tie among the ~4 800 multipliers read here would show in
-    oracle.shift_multipliers_f64; none does at this frequency)."""
+    """cf32, shift 280000, W = 100: the same bound with no row excluded, on a condition asserted first: the source span of the rows
+    holds no REAL tie, i.e. no multiplier component whose two f32 candidates (util.nco_candidates) lie more than 1e-13 apart —
+    such a tie moves a bin by at most a tenth of the bound's l1 term.  At 280000 / 21 MHz the period is 75 samples, so ambiguous
+    components do occur, the sin of every 75th sample (874 in [0, 65536)): zero crossings, whose candidates are 1e-19 ... 1e-14
+    apart."""
     n = len(fsk) // 8
+    _, first, count = engine.rows_geometry(0, SR, n, 100, 48, None, 1, shift_hz=280000)
+    ambiguous, ties = real_ties(oracle.shift_ratio(280000, SR), first, count)
+    assert ambiguous > 0 and not ties, (ambiguous, ties[:4])
     ch = _chain(oracle, fsk, 0, 280000, None)
     p = _plan(engine, 0, n, 100, 280000, None)
     rc, ref, offs = ch.take_fft(100, 48, None, 1)

@@ -650,6 +650,28 @@ def ambiguous_components(ratio, lo, hi, eps=NCO_ABS_ERR):
     return out
 
 
+REAL_TIE_GAP = 1e-13
+"""A multiplier component is a REAL tie where its nco_candidates pair (lo32, hi32) lies further apart than this.  The bound of the
+Bluestein rows (2 ulp_f32 of the reference norm + 1e-12 of the row's l1 norm) holds without any excuse as long as the rows read no
+real tie: a component that moves by g moves a bin by at most g |x| <= g l1, a tenth of the bound's l1 term at g = 1e-13.  Zero
+crossings (|v| < 3e-8, where the f32 grid is finer than 2 NCO_ABS_ERR) are ambiguous but 1e-19 ... 1e-14 apart: no real ties."""
+
+
+def real_ties(ratio, lo, n, gap=REAL_TIE_GAP, eps=NCO_ABS_ERR):
+    """(number of ambiguous multiplier components, the real ties among them as [(sample, comp, lo32, hi32), ...]) of samples
+    [lo, lo + n) of a shift with `ratio`; comp 0 = cos / 1 = sin"""
+    from oracle import oracle as O
+    ambiguous, ties = 0, []
+    if n <= 0:
+        return ambiguous, ties
+    for comp, v in enumerate(O.shift_multipliers_f64(ratio, int(lo), int(n))):
+        a, b = nco_candidates(v, eps)
+        ambiguous += int((a != b).sum())
+        far = np.nonzero(b.astype(np.float64) - a.astype(np.float64) > gap)[0]
+        ties += [(int(lo) + int(i), comp, float(a[i]), float(b[i])) for i in far]
+    return ambiguous, ties
+
+
 def differing_windows(ref, got):
     """rows (windows) whose bytes differ, NaN-aware: a NaN against a NaN is no difference"""
     ref = np.ascontiguousarray(ref)
