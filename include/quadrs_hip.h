@@ -432,6 +432,54 @@ int qd_plan_pool(qd_plan *plan, const void *src, int src_mem, uint64_t src_first
                  uint64_t first_window, uint64_t n_windows, uint64_t pool,
                  float *peak_rows, float *floor_rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ average-trace rows of a norms plan
+ *
+ * The spectrum analyser's third trace next to max hold and min hold: over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W and
+ * R = ceil(n / pool) rows grouped exactly as qd_plan_pool groups them, per row r and fftshifted bin b over the f32 values the norms
+ * sink writes for the group (a NaN is ignored, the sign bit is dropped: -0.0 counts as 0.0):
+ *   count_rows[r W + b]  u32  the number of non-NaN values, +inf included
+ *   sum_rows[r W + b]    f64  the EXACT real sum S of the values rounded once, to nearest, ties to even; 0.0 with no values
+ *   mean_rows[r W + b]   f32  the rational S / count rounded once to f32, nearest, ties to even, subnormal results included (it is not
+ *                             (float)(sum / count)); the quiet NaN 0x7fc00000 with no values
+ * Any +inf makes sum and mean +inf.  A floating-point sum depends on its order, so the values are accumulated exactly, in fixed point,
+ * and the results depend on no batch, chunk, memory kind, launch or arrival order.  pool == 1: mean is the norm bit for bit wherever
+ * it is not NaN and sum == (double)norm.  A group holds at most 2^31 windows.
+ *
+ * The accumulator is public so that parts merge: rows * width * QD_MEAN_WORDS caller-owned uint64_t, cell (r, b) at
+ * (r width + b) QD_MEAN_WORDS.  Words 0-8 are limbs L[0..8] in units of 2^-149, 32 payload bits each plus deferred carries: the cell's
+ * exact sum is the sum of L[j] 2^(32 j) 2^-149.  A value of biased exponent e and 23-bit fraction m (m |= 1 << 23 when e != 0), with
+ * s = max(e, 1) - 1, j = s >> 5, t = s & 31 and v = (uint64_t)m << t, adds v & 0xffffffff to L[j] and v >> 32 to L[j + 1]; at most 2^31
+ * values per cell keep every limb below 2^63.  Word 9 is the count of finite values plus the count of +inf values shifted left by 32.
+ * Every word is an integer sum: parts merge by word-wise addition. */
+#define QD_MEAN_WORDS 10
+
+/* All words 0: `rows` rows of `width` cells.  QD_ERR_INVALID: acc NULL or width == 0. */
+int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows);
+/* The CPU twin of the kernel behind qd_plan_mean, bit for bit: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32 in
+ * `norms`) ACCUMULATE into rows (at + i) / pool of acc, which holds the range's rows from row 0 on.  Parts of a range folded in any
+ * order give the same words.  QD_ERR_INVALID: pool == 0, width == 0, acc NULL, norms NULL with n > 0, or a row whose cells would hold
+ * more than 2^31 values (checked once per row before anything is added, counting every window of the call for the row: acc is then
+ * unchanged). */
+int qd_mean_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n);
+/* dst += src, word-wise.  QD_ERR_INVALID: NULL, width == 0, or a cell's count would pass 2^31 (dst is then unchanged). */
+int qd_mean_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows);
+/* The results of an accumulator, rows * width each; any may be NULL, not all.  QD_ERR_INVALID: acc NULL, width == 0, all outputs NULL. */
+int qd_mean_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *mean_rows, double *sum_rows, uint32_t *count_rows);
+/* The average-trace rows of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and
+ * `stream` as for qd_plan_run (device, host and pinned sources).  mean_rows / sum_rows / count_rows are R W values each of out_mem
+ * memory (host, pinned or device; any may be NULL, not all) and are OVERWRITTEN; the call returns after they are complete.  The windows
+ * go batch by batch through the plan's own kernel into a device carrier of at most max(chunk_bytes, one tile of windows) of norms.  A
+ * row whose windows one workgroup sees in one batch is rounded in the fold kernel; every other row goes through a device limb
+ * accumulator of at most max(2 chunk_bytes, 80 W bytes), whatever R is, and is rounded by a second small kernel.
+ * Codes as qd_plan_pool: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, pool == 0, pool (clamped to n_windows) above
+ * 2^31, all outputs NULL or an unknown memory kind; QD_ERR_SHORT past the sink's loop (the outputs are not touched), and for a
+ * cascade's range past qd_plan_complete_windows (every complete window of the range is folded; rows without one hold count 0, sum 0.0,
+ * mean NaN); QD_ERR_UNSUPPORTED for a plan created with shards (qd_mean_merge per shard's accumulator, or give each device a
+ * contiguous range of ROWS on a plan of its own).  n_windows == 0: QD_OK, nothing is touched. */
+int qd_plan_mean(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                 uint64_t first_window, uint64_t n_windows, uint64_t pool,
+                 float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

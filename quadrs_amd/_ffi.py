@@ -27,8 +27,10 @@ SYMBOLS = [
     "qd_plan_complete_windows", "qd_stages_geometry", "qd_bits_scan", "qd_rows_geometry", "qd_plan_take_fft",
     "qd_summary_init", "qd_summary_fold", "qd_summary_merge", "qd_summary_quantile", "qd_plan_summarize",
     "qd_pool_init", "qd_pool_fold", "qd_plan_pool",
+    "qd_mean_init", "qd_mean_fold", "qd_mean_merge", "qd_mean_finish", "qd_plan_mean",
 ]
 SUMMARY_BUCKETS = 2048
+MEAN_WORDS = 10
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -176,6 +178,11 @@ def lib():
             "qd_pool_init": (i32, [vp, vp, C.c_uint32, u64]),
             "qd_pool_fold": (i32, [vp, vp, C.c_uint32, u64, u64, vp, u64]),
             "qd_plan_pool": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, i32, vp]),
+            "qd_mean_init": (i32, [vp, C.c_uint32, u64]),
+            "qd_mean_fold": (i32, [vp, C.c_uint32, u64, u64, vp, u64]),
+            "qd_mean_merge": (i32, [vp, vp, C.c_uint32, u64]),
+            "qd_mean_finish": (i32, [vp, C.c_uint32, u64, vp, vp, vp]),
+            "qd_plan_mean": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, i32, vp]),
         }
         for name, (res, args) in sig.items():
             try:

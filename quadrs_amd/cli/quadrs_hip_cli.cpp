@@ -96,7 +96,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -249,22 +249,22 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             v = take(m, "stride", &f);
             op.stride = f ? parse_si_u64(v) : op.width;
             ensure_empty(m);
-        } else if (cmd == "peaks") {
+        } else if (cmd == "peaks" || cmd == "means") {
             // not in the reference's grammar: the spectrum analyser's max-hold picture — every window sparkfft would print, each group of
-            // `pool` consecutive windows folded per bin into one row (qd_plan_pool)
+            // `pool` consecutive windows folded per bin into one row (qd_plan_pool) — and its average trace (qd_plan_mean)
             auto m = no_duplicates(raw);
-            op.kind = OP_PEAKS;
+            op.kind = cmd == "peaks" ? OP_PEAKS : OP_MEANS;
             std::string v = take(m, "width", &f);
             op.width = f ? (size_t)parse_si_u64(v) : 128;
             v = take(m, "stride", &f);
             op.stride = f ? parse_si_u64(v) : op.width;
             v = take(m, "pool", &f);
-            if (f) { op.pool = parse_si_u64(v); if (!op.pool) bail("peaks -pool takes a number of windows > 0"); }
+            if (f) { op.pool = parse_si_u64(v); if (!op.pool) bail(cmd + " -pool takes a number of windows > 0"); }
             v = take(m, "count", &f);
             op.has_count = f;
             op.count = f ? (size_t)parse_si_u64(v) : 2048;
-            if (op.has_count && op.pool) bail("peaks takes -pool or -count, not both");
-            if (!op.count) bail("peaks -count takes a number of rows > 0");
+            if (op.has_count && op.pool) bail(cmd + " takes -pool or -count, not both");
+            if (!op.count) bail(cmd + " -count takes a number of rows > 0");
             v = take(m, "range", &f);
             if (f) {
                 size_t c = v.find(':');
@@ -273,10 +273,12 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
                 op.rmin = strtof(v.substr(0, c).c_str(), nullptr);
                 op.rmax = strtof(v.substr(c + 1).c_str(), nullptr);
             }
-            v = take(m, "floor", &f);
-            op.want_floor = f ? parse_bool(v) : false;
+            if (op.kind == OP_PEAKS) {
+                v = take(m, "floor", &f);
+                op.want_floor = f ? parse_bool(v) : false;
+            }
             ensure_empty(m);
-            op.prefix = next("'peaks' requires a prefix argument");
+            op.prefix = next(op.kind == OP_PEAKS ? "'peaks' requires a prefix argument" : "'means' requires a prefix argument");
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
             auto m = no_duplicates(raw);
@@ -919,16 +921,29 @@ void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
 // u8), or with -range lo:hi (v - lo) / (hi - lo) * 256 — the range `levels` tells the user to pass.  A chain the library fuses folds on
 // the device (qd_plan_pool on a norms plan; with -gpus N the ROWS are split into contiguous ranges, one plan each); every other chain
 // pulls its windows through the iterator chain and folds their norms with qd_pool_fold — the same bytes either way.
+//
+// The `means` sink is the same picture of the average trace, PREFIX.sr{rate}.w{W}x{rows}.mean.pgm: row r holds, per bin, the mean of the
+// norms of its windows, from their exact sum, rounded once (qd_plan_mean fused; qd_mean_fold + qd_mean_finish through the iterator).
 struct PeakRows {
     uint64_t windows = 0, pool = 1, rows = 0;
+    bool mean = false;                            // `means`: peak holds the mean rows, acc the iterator path's exact sums
     std::vector<float> peak, floor;
+    std::vector<uint64_t> acc;
     void size_for(const Op &sink, uint64_t n) {
         windows = n;
+        mean = sink.kind == OP_MEANS;
         pool = sink.pool ? sink.pool : std::max<uint64_t>(1, (n + sink.count - 1) / sink.count);
         if (n && pool > n) pool = n;
         rows = n ? (n - 1) / pool + 1 : 0;
-        peak.resize(rows * sink.width); floor.resize(rows * sink.width);
+        peak.resize(rows * sink.width);
+        if (mean) return;
+        floor.resize(rows * sink.width);
         qd_check(qd_pool_init(peak.data(), floor.data(), (uint32_t)sink.width, rows), "pool init");
+    }
+    // windows [w0, w1) of the plan, whose first row is r0, into the rows
+    int run(qd_plan *plan, const void *src, int mem, uint64_t n_samples, uint64_t w0, uint64_t w1, uint64_t r0, size_t width) {
+        if (mean) return qd_plan_mean(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, peak.data() + r0 * width, nullptr, nullptr, QD_MEM_HOST, nullptr);
+        return qd_plan_pool(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, peak.data() + r0 * width, floor.data() + r0 * width, QD_MEM_HOST, nullptr);
     }
 };
 
@@ -987,13 +1002,12 @@ bool peaks_fused(const ChainSpec &cs, const Op &sink, PeakRows *out) {
                 const uint64_t n = d.n_samples - at < piece ? d.n_samples - at : piece;
                 qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, at, (size_t)n, static_cast<qd_c32 *>(gen_src.p) + at, QD_MEM_DEVICE), "gen");
             }
-            rr = qd_plan_pool(plan, gen_src.p, QD_MEM_DEVICE, 0, d.n_samples, w0, w1 - w0, out->pool, out->peak.data(), out->floor.data(), QD_MEM_HOST, nullptr);
+            rr = out->run(plan, gen_src.p, QD_MEM_DEVICE, d.n_samples, w0, w1, 0, sink.width);
         } else if (w1 > w0) {
-            rr = qd_plan_pool(plan, data->p, data->mem, 0, d.n_samples, w0, w1 - w0, out->pool, out->peak.data() + r0 * sink.width,
-                              out->floor.data() + r0 * sink.width, QD_MEM_HOST, nullptr);
+            rr = out->run(plan, data->p, data->mem, d.n_samples, w0, w1, r0, sink.width);
         }
         qd_plan_destroy(plan);
-        qd_check(rr, "pool");
+        qd_check(rr, out->mean ? "mean" : "pool");
     }
     if (parts > 1) qd_check(qd_set_device(0), "set device");
     return true;
@@ -1004,7 +1018,7 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     if (!W || (W & (W - 1))) bail("Radix4 algorithm requires a power-of-two input size");
     if (S == 0) bail("stride 0 never terminates");
     if (W > 0xffffffffull) bail("width too large");
-    if (sink.has_range && !(sink.rmax > sink.rmin)) bail("peaks -range takes lo:hi with lo < hi");
+    if (sink.has_range && !(sink.rmax > sink.rmin)) bail(std::string(sink.kind == OP_MEANS ? "means" : "peaks") + " -range takes lo:hi with lo < hi");
     PeakRows pr;
     bool done = false;
     if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = peaks_fused(*cs, sink, &pr);
@@ -1019,6 +1033,10 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
             try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
         }
         pr.size_for(sink, nwin);
+        if (pr.mean && pr.rows) {
+            pr.acc.resize(pr.rows * W * QD_MEAN_WORDS);
+            qd_check(qd_mean_init(pr.acc.data(), (uint32_t)W, pr.rows), "mean init");
+        }
         // their norms from a side-by-side norms plan, folded on the host
         const uint64_t batch = 4096;
         buf.resize(batch * W);
@@ -1035,8 +1053,10 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
             const int rc = qd_plan_run(plan, buf.data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms.data(), QD_MEM_HOST, nullptr);
             qd_plan_destroy(plan);
             qd_check(rc, "run");
-            qd_check(qd_pool_fold(pr.peak.data(), pr.floor.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
+            if (pr.mean) qd_check(qd_mean_fold(pr.acc.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
+            else qd_check(qd_pool_fold(pr.peak.data(), pr.floor.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
         }
+        if (pr.mean && pr.rows) qd_check(qd_mean_finish(pr.acc.data(), (uint32_t)W, pr.rows, pr.peak.data(), nullptr, nullptr), "mean finish");
     }
     const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "x" + std::to_string(pr.rows);
     const std::string head = "P5\n" + std::to_string(W) + " " + std::to_string(pr.rows) + "\n255\n";
@@ -1044,7 +1064,7 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     std::vector<uint8_t> px(pr.peak.size());
     for (int which = 0; which < (sink.want_floor ? 2 : 1); ++which) {
         const std::vector<float> &rows = which ? pr.floor : pr.peak;
-        const std::string fn = stem + (which ? ".floor.pgm" : ".peak.pgm");
+        const std::string fn = stem + (pr.mean ? ".mean.pgm" : which ? ".floor.pgm" : ".peak.pgm");
         int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
         if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
         for (size_t i = 0; i < rows.size(); ++i) {
@@ -1067,6 +1087,7 @@ void usage() {
             "   marks [-width 128] [-stride =width] [-min 0.08] [-scan SCALE] \\\n"
             "  levels [-width 128] [-stride =width] \\\n"
             "   peaks [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] [-floor no] FILENAME_PREFIX \\\n"
+            "   means [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -1106,6 +1127,10 @@ int main(int argc, char **argv) {
                 case OP_PEAKS:
                     printf("peaks width=%zu stride=%llu %s=%llu range=%s floor=%d\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
                            (unsigned long long)(op.pool ? op.pool : op.count), op.has_range ? "yes" : "no", op.want_floor ? 1 : 0);
+                    break;
+                case OP_MEANS:
+                    printf("means width=%zu stride=%llu %s=%llu range=%s\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
+                           (unsigned long long)(op.pool ? op.pool : op.count), op.has_range ? "yes" : "no");
                     break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 case OP_ROWS:
@@ -1160,6 +1185,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("levels requires an input");
                 cs.cascade = !chain_clean;
                 do_levels(*samples, op, &cs);
+                break;
+            case OP_MEANS:
+                if (!samples) bail("means requires an input");
+                cs.cascade = !chain_clean;
+                do_peaks(*samples, op, &cs);
                 break;
             case OP_PEAKS:
                 if (!samples) bail("peaks requires an input");

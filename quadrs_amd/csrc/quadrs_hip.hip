@@ -32,6 +32,7 @@
 #include "qd_registry.h"
 #include "qd_summary.h"
 #include "qd_pool.h"
+#include "qd_mean.h"
 
 using namespace qd;
 
@@ -3507,6 +3508,224 @@ int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
         if (rc == QD_OK && !out_dev) {
             if (peak_rows) HIPCHK(hipMemcpyAsync(peak_rows, peak_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
             if (floor_rows) HIPCHK(hipMemcpyAsync(floor_rows, floor_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+        }
+        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        if (rc) return rc;
+    }
+    if (is_short)
+        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
+                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
+    return QD_OK;
+}
+
+// ------------------------------------------------------------------ average-trace rows
+
+namespace {
+struct MeanOut { float *mean; double *sum; uint32_t *count; };
+struct MeanAcc { unsigned long long *limbs; uint32_t *flags; uint64_t rows; };      // device: kMeanWords x rows x W limbs (planar), rows flags
+
+// one batch of norms rows (device memory, 16-byte aligned) — windows [g0, g0 + nw) of a range of n_total — into the outputs (whole rows)
+// and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows) of the range, on `st`
+int launch_mean(const qd_plan *p, const MeanParams &geo, uint64_t grid, int V, const float *norms_d, const MeanOut &out, const MeanAcc &acc,
+                bool cuts, uint64_t r_base, hipStream_t st) {
+    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)geo.G.nw);
+    const uint64_t ra = geo.G.g0 / geo.G.pool, rb = (geo.G.g0 + geo.G.nw - 1) / geo.G.pool;
+    if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
+    MeanParams M = geo;
+    M.G.norms = norms_d; M.G.peak = M.G.floor = nullptr;
+    M.mean = out.mean; M.sum = out.sum; M.count = out.count;
+    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
+    hipLaunchKernelGGL(V == 4 ? k_mean<4> : k_mean<1>, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+int mean_acc_clear(const qd_plan *p, const MeanAcc &acc, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(acc.limbs, 0, (size_t)(acc.rows * p->W * kMeanWords * 8 + acc.rows * 4), st));      // the flags lie behind the limbs
+    return QD_OK;
+}
+int launch_mean_finish(const qd_plan *p, const MeanAcc &acc, uint64_t r_base, uint64_t n_rows, const MeanOut &out, hipStream_t st) {
+    const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
+    if (!cells) return QD_OK;
+    hipLaunchKernelGGL(k_mean_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
+                       out.mean, out.sum, out.count);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+uint64_t mean_cell_count(const uint64_t *cell) { return (cell[9] & 0xffffffffull) + (cell[9] >> 32); }
+}  // namespace
+
+int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    memset(acc, 0, (size_t)(rows * width * QD_MEAN_WORDS * 8));
+    return QD_OK;
+}
+
+int qd_mean_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    // once per row, before anything is added: the row's cells take at most its windows of this call on top of what they hold
+    for (uint64_t r = at / pool; r <= (at + n - 1) / pool; ++r) {
+        const uint64_t a = std::max(at, r * pool), b = std::min(at + n, (r + 1) * pool);
+        for (uint32_t c = 0; c < width; ++c)
+            if (mean_cell_count(acc + (r * width + c) * QD_MEAN_WORDS) + (b - a) > kMeanMaxCount)
+                return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)r);
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        uint64_t *cells = acc + (at + i) / pool * width * QD_MEAN_WORDS;
+        for (uint32_t b = 0; b < width; ++b) {
+            uint32_t bits;
+            memcpy(&bits, row + b, 4);
+            mean_add(cells + (uint64_t)b * QD_MEAN_WORDS, bits);
+        }
+    }
+    return QD_OK;
+}
+
+int qd_mean_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
+    if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c)
+        if (mean_cell_count(dst + c * QD_MEAN_WORDS) + mean_cell_count(src + c * QD_MEAN_WORDS) > kMeanMaxCount)
+            return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
+    for (uint64_t i = 0; i < cells * QD_MEAN_WORDS; ++i) dst[i] += src[i];
+    return QD_OK;
+}
+
+int qd_mean_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *mean_rows, double *sum_rows, uint32_t *count_rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!mean_rows && !sum_rows && !count_rows) return fail(QD_ERR_INVALID, "mean_rows, sum_rows and count_rows are all NULL");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c) {
+        uint32_t mb, cnt; double s;
+        mean_finish_cell(acc + c * QD_MEAN_WORDS, &mb, &s, &cnt);
+        if (mean_rows) memcpy(mean_rows + c, &mb, 4);
+        if (sum_rows) sum_rows[c] = s;
+        if (count_rows) count_rows[c] = cnt;
+    }
+    return QD_OK;
+}
+
+int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                 uint64_t pool, float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_mean folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (!mean_rows && !sum_rows && !count_rows) return fail(QD_ERR_INVALID, "mean_rows, sum_rows and count_rows are all NULL");
+    const bool dev = src_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
+    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
+    if (!out_dev && !host_kind(out_mem)) return fail(QD_ERR_INVALID, "unknown out_mem %d", out_mem);
+    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)");
+    if (first_window + n_windows > p->n_windows)
+        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
+                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
+    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    if (n_windows == 0) return QD_OK;
+    if (pool > n_windows) pool = n_windows;                          // one row either way
+    if (pool > kMeanMaxCount) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)pool);
+    const uint32_t W = p->W;
+    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;
+    bool is_short = false;
+    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
+        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
+        is_short = true;
+    }
+    if (n_windows && !src) return fail(QD_ERR_INVALID, "src is NULL");
+    {
+        std::lock_guard<std::mutex> lock(p->mu);
+        DeviceGuard guard(p->device);
+        const hipStream_t st = static_cast<hipStream_t>(stream);
+        WsLease ws(st);
+        if (ws.rc) return ws.rc;
+        int rc = QD_OK;
+        // the outputs: the caller's arrays when they are device memory, else [sum][mean][count] in the workspace, copied down once
+        MeanOut out{mean_rows, sum_rows, count_rows};
+        if (!out_dev) {
+            void *o = nullptr;
+            rc = ws.get(2, (size_t)(words * ((sum_rows ? 8 : 0) + (mean_rows ? 4 : 0) + (count_rows ? 4 : 0))), &o); if (rc) return rc;
+            uint8_t *at = static_cast<uint8_t *>(o);
+            out.sum = sum_rows ? reinterpret_cast<double *>(at) : nullptr; at += sum_rows ? words * 8 : 0;
+            out.mean = mean_rows ? reinterpret_cast<float *>(at) : nullptr; at += mean_rows ? words * 4 : 0;
+            out.count = count_rows ? reinterpret_cast<uint32_t *>(at) : nullptr;
+        }
+        if (is_short) {                                              // rows without a complete window: no values
+            if (out.mean) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out.mean), (int)kMeanNanBits, (size_t)words, st));
+            if (out.sum) HIPCHK(hipMemsetAsync(out.sum, 0, (size_t)(words * 8), st));
+            if (out.count) HIPCHK(hipMemsetAsync(out.count, 0, (size_t)(words * 4), st));
+        }
+        // the limb accumulator (qd_mean.h): at most max(2 chunk_bytes, one row), its flags behind it
+        const uint64_t cw = n_windows ? chunk_windows(p, first_window, n_windows, (uint64_t)W * 4) : 1;
+        const uint64_t row_bytes = (uint64_t)W * kMeanWords * 8;
+        const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
+        MeanAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
+        if (n_windows) {
+            void *a = nullptr;
+            rc = ws.get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
+            acc.limbs = static_cast<unsigned long long *>(a);
+            acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
+        }
+        auto geometry = [&](uint64_t g0, uint64_t nw, MeanParams *M, uint64_t *grid, int *V) { pool_geometry(g0, nw, n_windows, pool, W, p->n_cu, &M->G, grid, V); };
+        if (n_windows && dev) {
+            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
+            void *car = nullptr;
+            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
+            const uint64_t bw = pool <= cw ? cw / pool * pool : cw;                  // seams on row boundaries where a chunk holds a row
+            bool open = false;
+            uint64_t r_base = 0;
+            auto close = [&]() { const int c = open ? launch_mean_finish(p, acc, r_base, std::min(acc.rows, R - r_base), out, st) : QD_OK; open = false; return c; };
+            for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
+                uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
+                MeanParams M{};
+                int V = 1;
+                geometry(g0, nw, &M, &grid, &V);
+                const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
+                const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
+                const bool cuts = M.G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
+                if (cuts) {
+                    if (!open || (!mid && rb >= r_base + acc.rows)) {                // move the accumulator: only between rows
+                        rc = close();
+                        if (rc == QD_OK) rc = mean_acc_clear(p, acc, st);
+                        r_base = ra; open = true;
+                    }
+                    if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
+                        nw = (r_base + acc.rows) * pool - g0;
+                        geometry(g0, nw, &M, &grid, &V);
+                    }
+                }
+                if (rc == QD_OK) rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, first_window + g0, nw, first_window + g0, car, st);
+                if (rc == QD_OK) rc = launch_mean(p, M, grid, V, static_cast<const float *>(car), out, acc, cuts, cuts ? r_base : ra, st);
+                g0 += nw;
+            }
+            if (rc == QD_OK) rc = close();
+        } else if (n_windows) {
+            // host sources: the upload ring cuts its own batches, on two streams; the range goes span by span of the accumulator's rows
+            const uint64_t Rn = (n_windows - 1) / pool + 1;
+            for (uint64_t r_base = 0; r_base < Rn && rc == QD_OK; r_base += acc.rows) {
+                const uint64_t g_a = r_base * pool, g_b = std::min<uint64_t>(n_windows, (r_base + acc.rows) * pool);
+                rc = mean_acc_clear(p, acc, st);
+                if (rc) break;
+                HIPCHK(hipStreamSynchronize(st));         // the slots' streams fold into the outputs and the accumulator too
+                rc = fold_host(p, src, src_mem, src_first, src_count, first_window + g_a, g_b - g_a,
+                               [&](const float *norms_d, uint64_t w, uint64_t nw, hipStream_t s) {
+                                   MeanParams M{};
+                                   uint64_t grid = 0;
+                                   int V = 1;
+                                   geometry(w - first_window, nw, &M, &grid, &V);
+                                   return launch_mean(p, M, grid, V, norms_d, out, acc, true, r_base, s);
+                               });
+                if (rc == QD_OK) rc = launch_mean_finish(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
+            }
+        }
+        if (rc == QD_OK && !out_dev) {
+            if (mean_rows) HIPCHK(hipMemcpyAsync(mean_rows, out.mean, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+            if (sum_rows) HIPCHK(hipMemcpyAsync(sum_rows, out.sum, (size_t)(words * 8), hipMemcpyDeviceToHost, st));
+            if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, out.count, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
         }
         if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
         if (rc) return rc;

@@ -329,6 +329,42 @@ def pool_fold(norms, pool, at=0, into=None):
     return peak, floor
 
 
+def mean_init(width, rows):
+    """qd_mean_init: the exact-sum accumulator of `rows` rows of `width` cells, uint64[rows, width, MEAN_WORDS], all words 0."""
+    acc = np.empty((int(rows), int(width), _ffi.MEAN_WORDS), dtype=np.uint64)
+    check(lib().qd_mean_init(_np_ptr(acc), int(width), int(rows)))
+    return acc
+
+
+def mean_fold(norms, pool, at=0, into=None):
+    """qd_mean_fold: norms rows (n, width) are windows at, at+1, ... of a range and accumulate into rows (at + i) // pool of the
+    accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = mean_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
+    check(lib().qd_mean_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
+    return into
+
+
+def mean_merge(dst, src):
+    """qd_mean_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
+    if dst.shape != src.shape:
+        raise ValueError("accumulators of different shapes do not merge")
+    check(lib().qd_mean_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
+    return dst
+
+
+def mean_finish(acc):
+    """qd_mean_finish: (mean float32, sum float64, count uint32), [rows, width] each, every cell rounded once from its exact sum."""
+    rows, width = acc.shape[0], acc.shape[1]
+    mean = np.empty((rows, width), dtype=np.float32)
+    total = np.empty((rows, width), dtype=np.float64)
+    count = np.empty((rows, width), dtype=np.uint32)
+    check(lib().qd_mean_finish(_np_ptr(acc), width, rows, _np_ptr(mean), _np_ptr(total), _np_ptr(count)))
+    return mean, total, count
+
+
 class Plan:
     """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
@@ -549,6 +585,33 @@ class Plan:
             e.partial = (peak, floor)            # QD_ERR_SHORT of a cascade: the complete windows are folded
             raise
         return peak, floor
+
+    def mean(self, src, pool, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None):
+        """qd_plan_mean of an EPI_NORMS_F32 plan: (mean_rows float32, sum_rows float64, count_rows uint32), [ceil(n_windows / pool), width]
+        each — per bin the exact sum of each group of `pool` consecutive windows of [first_window, +n_windows), rounded once, its mean
+        rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch count_rows is int32: the same bits)."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
+        if _is_torch(src):
+            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
+        else:
+            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+            count = buf.size // _FMT_BYTES[self.desc.format]
+            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
+        if _is_torch(src) if device_out is None else device_out:
+            import torch
+            out = tuple(torch.empty((rows, self.width), dtype=t, device="cuda") for t in (torch.float32, torch.float64, torch.int32))
+            ptrs, out_mem = [C.c_void_p(o.data_ptr()) for o in out], MEM_DEVICE
+        else:
+            out = tuple(np.empty((rows, self.width), dtype=t) for t in (np.float32, np.float64, np.uint32))
+            ptrs, out_mem = [_np_ptr(o) for o in out], MEM_HOST
+        try:
+            check(lib().qd_plan_mean(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), *ptrs, out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = out                      # QD_ERR_SHORT of a cascade: the complete windows are folded
+            raise
+        return out
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))
