@@ -12,6 +12,7 @@
 // falls back to the block iterator, whose read_at() calls the fine-grained entry points exactly where the reference's read_at()
 // computes.
 #include <algorithm>
+#include <functional>
 #include <cerrno>
 #include <cmath>
 #include <cinttypes>
@@ -468,15 +469,17 @@ int g_gpus = 1;      // `-gpus N` in front of the chain: shard the sink's window
 
 // plan for the CLI: the library's defaults, plus window-range shards over g_gpus devices (repeating devices when the
 // machine has fewer: the shards then run as independent streams of one device)
-int create_plan(const qd_chain_desc &d, qd_plan **plan, const std::vector<qd_stage> *stages = nullptr) {
-    if (g_gpus <= 1) return stages ? qd_plan_create_stages(&d, stages->data(), stages->size(), nullptr, plan) : qd_plan_create(&d, plan);
+// (`stages` of a cascade, empty for a one-stage plan; gpus = 1: an unsharded plan on the current device)
+int create_plan(const qd_chain_desc &d, qd_plan **plan, const std::vector<qd_stage> &stages, int gpus = g_gpus) {
+    const bool casc = !stages.empty();
+    if (gpus <= 1) return casc ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, plan) : qd_plan_create(&d, plan);
     qd_plan_options o{};
     o.struct_size = sizeof o;
     int n_dev = 1;
     if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
-    o.n_shards = (uint32_t)(g_gpus > QD_MAX_SHARDS ? QD_MAX_SHARDS : g_gpus);
+    o.n_shards = (uint32_t)(gpus > QD_MAX_SHARDS ? QD_MAX_SHARDS : gpus);
     for (uint32_t g = 0; g < o.n_shards; ++g) o.shard_device[g] = (int32_t)(g % (uint32_t)n_dev);
-    return stages ? qd_plan_create_stages(&d, stages->data(), stages->size(), &o, plan) : qd_plan_create_ex(&d, &o, plan);
+    return casc ? qd_plan_create_stages(&d, stages.data(), stages.size(), &o, plan) : qd_plan_create_ex(&d, &o, plan);
 }
 
 // device buffer that frees itself (the `gen` source of a fused chain lives in HBM)
@@ -484,6 +487,55 @@ struct DeviceBuf {
     void *p = nullptr;
     ~DeviceBuf() { if (p) qd_device_free(p); }
 };
+
+// the first n samples of a `gen` source, produced on the device (src/gen.rs:30-47): they never cross PCIe
+void gen_to_device(const Op &src, uint64_t n, DeviceBuf *buf) {
+    qd_check(qd_device_alloc((size_t)n * 8, &buf->p), "device buffer for gen");
+    const uint64_t piece = 1ull << 28;                                   // Gen::read_at in pieces: bounded kernel launches
+    for (uint64_t a = 0; a < n; a += piece)
+        qd_check(qd_gen(src.cos.data(), src.cos.size(), src.sample_rate, a, (size_t)std::min(n - a, piece), static_cast<qd_c32 *>(buf->p) + a, QD_MEM_DEVICE), "gen");
+}
+
+// The source of a fused plan: the whole file, mapped, or a `gen` stream, which resident() produces on the device when first asked for.
+struct ChainSource {
+    const Op &op;
+    const bool from_gen;
+    std::unique_ptr<MappedFile> data;
+    DeviceBuf gen;
+    uint64_t n_samples;
+    explicit ChainSource(const ChainSpec &cs) : op(*cs.src), from_gen(op.kind == OP_GEN) {
+        if (!from_gen) data.reset(new MappedFile(op.filename));
+        n_samples = from_gen ? (uint64_t)(op.seconds * (double)op.sample_rate)                  // Gen::len, src/gen.rs:32
+                             : data->size / qd_pair_bytes(op.format);
+    }
+    const void *resident(int *mem) {
+        if (!from_gen) { *mem = data->mem; return data->p; }
+        if (!gen.p) gen_to_device(op, n_samples, &gen);
+        *mem = QD_MEM_DEVICE;
+        return gen.p;
+    }
+};
+
+// what a fused plan is made from: the source, the chain's [shift] [lowpass] (or, for a cascade, its stages) and the sink's windows
+void chain_desc(const ChainSpec &cs, const ChainSource &in, size_t width, uint64_t stride, int epilogue, qd_chain_desc *d, std::vector<qd_stage> *stages) {
+    *d = qd_chain_desc{};
+    d->struct_size = sizeof *d;
+    d->format = in.from_gen ? QD_FMT_CF32 : cs.src->format; d->sample_rate = cs.src->sample_rate;
+    d->n_samples = in.n_samples;
+    stages->clear();
+    if (cs.cascade) {
+        for (const Op *op : cs.stages) {
+            qd_stage st{};
+            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
+            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
+            stages->push_back(st);
+        }
+    } else {
+        if (cs.shift) { d->has_shift = 1; d->shift_hz = cs.shift->shift; }
+        if (cs.lowpass) { d->has_lowpass = 1; d->lowpass_hz = cs.lowpass->lp_freq; d->decimate = cs.lowpass->decimate; d->taps = cs.lowpass->size; }
+    }
+    d->width = width; d->stride = stride; d->epilogue = epilogue;
+}
 
 int sink_epilogue(const Op &sink) {
     return sink.kind == OP_BUCKET ? QD_EPI_BUCKET2_U8 : (sink.kind == OP_MARKS ? QD_EPI_MARK_U8 : QD_EPI_GLYPH_U8);
@@ -520,35 +572,16 @@ void print_marks(const uint8_t *marks, uint64_t n, const Op &sink) {
 // error (src/samples.rs:17-27) — sparkfft prints inside its loop (src/fft.rs:28-65), bucket unwraps before printing anything.
 bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
     const uint64_t out_rate = samples.sample_rate();
-    const bool from_gen = cs.src->kind == OP_GEN;
-    std::unique_ptr<MappedFile> data;
-    if (!from_gen) data.reset(new MappedFile(cs.src->filename));
-    qd_chain_desc d{};
-    d.struct_size = sizeof d;
-    d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
-    d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate)          // Gen::len, src/gen.rs:32
-                           : data->size / qd_pair_bytes(cs.src->format);
+    ChainSource in(cs);
+    const bool from_gen = in.from_gen;
+    qd_chain_desc d;
     std::vector<qd_stage> stages;
-    if (cs.cascade) {
-        for (const Op *op : cs.stages) {
-            qd_stage st{};
-            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
-            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
-            stages.push_back(st);
-        }
-    } else {
-        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
-        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
-    }
-    d.width = sink.width; d.stride = sink.stride;
-    d.epilogue = sink_epilogue(sink);
+    chain_desc(cs, in, sink.width, sink.stride, sink_epilogue(sink), &d, &stages);
     d.has_range = sink.has_range; d.range_min = sink.rmin; d.range_max = sink.rmax;
     if (sink.kind == OP_SPARKFFT) printf("sparkfft sample_rate=%" PRIu64 "\n", out_rate);   // printed before any read (src/fft.rs:19)
     qd_plan *plan = nullptr;
     {
-        const int rc = from_gen && !cs.cascade ? qd_plan_create(&d, &plan)
-                     : from_gen ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan)
-                     : create_plan(d, &plan, cs.cascade ? &stages : nullptr);
+        const int rc = create_plan(d, &plan, stages, from_gen ? 1 : g_gpus);
         if (rc == QD_ERR_UNSUPPORTED) return false;
         qd_check(rc, "plan");
     }
@@ -560,21 +593,16 @@ bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
     auto check_run = [&](int rc, const char *what) { if (!(rc == QD_ERR_SHORT && complete < info.n_windows)) qd_check(rc, what); };
     std::vector<uint8_t> out(info.n_windows * info.out_bytes_per_window + 1);
     if (info.n_windows && !from_gen) {
-        if (g_gpus > 1) check_run(qd_plan_run_sharded(plan, data->p, data->mem, out.data(), QD_MEM_HOST), "run (sharded)");
-        else check_run(qd_plan_run(plan, data->p, data->mem, 0, d.n_samples, 0, info.n_windows, out.data(), QD_MEM_HOST, nullptr), "run");
+        if (g_gpus > 1) check_run(qd_plan_run_sharded(plan, in.data->p, in.data->mem, out.data(), QD_MEM_HOST), "run (sharded)");
+        else check_run(qd_plan_run(plan, in.data->p, in.data->mem, 0, d.n_samples, 0, info.n_windows, out.data(), QD_MEM_HOST, nullptr), "run");
     }
     if (info.n_windows && from_gen) {
-        DeviceBuf src, dst;
+        DeviceBuf dst;
         const size_t ob = (size_t)(info.n_windows * info.out_bytes_per_window);
-        qd_check(qd_device_alloc((size_t)d.n_samples * 8, &src.p), "device buffer for gen");
+        int mem = QD_MEM_DEVICE;
+        const void *src = in.resident(&mem);
         qd_check(qd_device_alloc(ob, &dst.p), "device buffer for the sink");
-        const uint64_t piece = 1ull << 28;                                   // Gen::read_at in pieces: bounded kernel launches
-        for (uint64_t a = 0; a < d.n_samples; a += piece) {
-            const uint64_t n = d.n_samples - a < piece ? d.n_samples - a : piece;
-            qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, a, (size_t)n,
-                            static_cast<qd_c32 *>(src.p) + a, QD_MEM_DEVICE), "gen");
-        }
-        check_run(qd_plan_run(plan, src.p, QD_MEM_DEVICE, 0, d.n_samples, 0, info.n_windows, dst.p, QD_MEM_DEVICE, nullptr), "run");
+        check_run(qd_plan_run(plan, src, mem, 0, d.n_samples, 0, info.n_windows, dst.p, QD_MEM_DEVICE, nullptr), "run");
         qd_check(qd_device_copy(out.data(), QD_MEM_HOST, dst.p, QD_MEM_DEVICE, ob), "copy back");   // synchronises with the launch
     }
     qd_plan_destroy(plan);
@@ -683,26 +711,13 @@ void do_write(const Samples &s, bool overwrite, const std::string &prefix, const
     uint64_t off = 0, len;
     try { len = s.len(); } catch (...) { close(fd); throw; }
     if (cs && cs->fusable && cs->src->kind == OP_FROM && cs->lowpass && !getenv("QUADRS_HIP_NO_FUSE")) {
-        MappedFile data(cs->src->filename);
-        qd_chain_desc d{};
-        d.struct_size = sizeof d;
-        d.format = cs->src->format; d.sample_rate = cs->src->sample_rate;
-        d.n_samples = data.size / qd_pair_bytes(cs->src->format);
+        ChainSource in(*cs);
+        const MappedFile &data = *in.data;
+        qd_chain_desc d;
         std::vector<qd_stage> stages;
-        if (cs->cascade) {
-            for (const Op *op : cs->stages) {
-                qd_stage st{};
-                if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
-                else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
-                stages.push_back(st);
-            }
-        } else {
-            if (cs->shift) { d.has_shift = 1; d.shift_hz = cs->shift->shift; }
-            d.has_lowpass = 1; d.lowpass_hz = cs->lowpass->lp_freq; d.decimate = cs->lowpass->decimate; d.taps = cs->lowpass->size;
-        }
-        d.width = 0x1000; d.stride = 0x1000; d.epilogue = QD_EPI_CF32_BLOCKS;
+        chain_desc(*cs, in, 0x1000, 0x1000, QD_EPI_CF32_BLOCKS, &d, &stages);
         qd_plan *plan = nullptr;
-        int rc = create_plan(d, &plan, cs->cascade ? &stages : nullptr);
+        int rc = create_plan(d, &plan, stages);
         if (rc == QD_OK) {
             qd_plan_info info;
             qd_check(qd_plan_get_info(plan, &info), "plan info");
@@ -743,14 +758,11 @@ void do_rows(const Samples &s, const Op &sink, const ChainSpec *cs) {
     try {
         bool done = false;
         if (cs && cs->fusable && !cs->cascade && cs->src->kind == OP_FROM && !getenv("QUADRS_HIP_NO_FUSE")) {
-            MappedFile data(cs->src->filename);
-            qd_chain_desc d{};
-            d.struct_size = sizeof d;
-            d.format = cs->src->format; d.sample_rate = cs->src->sample_rate;
-            d.n_samples = data.size / qd_pair_bytes(cs->src->format);
-            if (cs->shift) { d.has_shift = 1; d.shift_hz = cs->shift->shift; }
-            if (cs->lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs->lowpass->lp_freq; d.decimate = cs->lowpass->decimate; d.taps = cs->lowpass->size; }
-            d.width = W; d.stride = 1; d.epilogue = QD_EPI_ROWS_F32;
+            ChainSource in(*cs);
+            const MappedFile &data = *in.data;
+            qd_chain_desc d;
+            std::vector<qd_stage> stages;                                    // (stays empty: not a cascade)
+            chain_desc(*cs, in, W, 1, QD_EPI_ROWS_F32, &d, &stages);
             qd_rows_desc r{};
             r.struct_size = sizeof r;
             r.has_slice = sink.has_slice ? 1 : 0; r.start = sink.slice_start; r.end = sink.slice_end;
@@ -813,103 +825,101 @@ void print_levels(uint64_t rate, const Op &sink, const qd_summary &sum, const st
     printf("peak_bin %zu %.9g\n", best, peak.empty() ? 0.f : peak[best]);
 }
 
-bool levels_fused(const ChainSpec &cs, const Op &sink, qd_summary *sum, std::vector<float> *peak, std::vector<float> *floor) {
-    const bool from_gen = cs.src->kind == OP_GEN;
-    std::unique_ptr<MappedFile> data;
-    if (!from_gen) data.reset(new MappedFile(cs.src->filename));
-    qd_chain_desc d{};
-    d.struct_size = sizeof d;
-    d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
-    d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate) : data->size / qd_pair_bytes(cs.src->format);
+// The fused half of the norms sinks (levels, peaks, means): one unsharded QD_EPI_NORMS_F32 plan per part (-gpus N; a `gen` source: one), made on
+// that part's device.  part(plan, in, g, parts, complete windows, tile) picks its range of the complete windows and runs it; its status is
+// checked as `what`.  False when the library has no fused plan for the chain: the caller pulls the windows through the iterator chain.
+using NormsPart = std::function<int(qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile)>;
+bool norms_fused(const ChainSpec &cs, const Op &sink, const char *what, const NormsPart &part) {
+    ChainSource in(cs);
+    qd_chain_desc d;
     std::vector<qd_stage> stages;
-    if (cs.cascade) {
-        for (const Op *op : cs.stages) {
-            qd_stage st{};
-            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
-            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
-            stages.push_back(st);
-        }
-    } else {
-        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
-        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
-    }
-    d.width = sink.width; d.stride = sink.stride; d.epilogue = QD_EPI_NORMS_F32;
+    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, &d, &stages);
     int n_dev = 1;
     if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
-    const int parts = from_gen ? 1 : g_gpus;
-    DeviceBuf gen_src;
+    const int parts = in.from_gen ? 1 : g_gpus;
     uint64_t complete = 0;
     for (int g = 0; g < parts; ++g) {
-        // one unsharded plan per window range, made on that range's device
         if (parts > 1) qd_check(qd_set_device(g % n_dev), "set device");
         qd_plan *plan = nullptr;
-        const int rc = cs.cascade ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan) : qd_plan_create(&d, &plan);
+        const int rc = create_plan(d, &plan, stages, 1);
         if (rc == QD_ERR_UNSUPPORTED && g == 0) return false;
         qd_check(rc, "plan");
         if (g == 0) qd_check(qd_plan_complete_windows(plan, &complete), "plan complete windows");
         qd_plan_info info;
         qd_check(qd_plan_get_info(plan, &info), "plan info");
-        const uint64_t tile = info.tile_windows ? info.tile_windows : 1;              // tile-aligned ranges, as the library's own shards
-        const uint64_t per = ((complete + parts - 1) / parts + tile - 1) / tile * tile;
-        const uint64_t w0 = std::min<uint64_t>(complete, per * g), w1 = std::min<uint64_t>(complete, per * (g + 1));
-        qd_summary part;
-        std::vector<float> ppeak(sink.width), pfloor(sink.width);
-        int rr;
-        if (from_gen && w1 > w0) {
-            qd_check(qd_device_alloc((size_t)d.n_samples * 8, &gen_src.p), "device buffer for gen");
-            const uint64_t piece = 1ull << 28;
-            for (uint64_t a = 0; a < d.n_samples; a += piece) {
-                const uint64_t n = d.n_samples - a < piece ? d.n_samples - a : piece;
-                qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, a, (size_t)n, static_cast<qd_c32 *>(gen_src.p) + a, QD_MEM_DEVICE), "gen");
-            }
-            rr = qd_plan_summarize(plan, gen_src.p, QD_MEM_DEVICE, 0, d.n_samples, w0, w1 - w0, &part, ppeak.data(), pfloor.data(), nullptr);
-        } else {
-            rr = qd_plan_summarize(plan, from_gen ? nullptr : data->p, from_gen ? QD_MEM_HOST : data->mem, 0, d.n_samples, w0, w1 - w0, &part, ppeak.data(), pfloor.data(), nullptr);
-        }
+        const int rr = part(plan, in, g, parts, complete, info.tile_windows ? info.tile_windows : 1);
         qd_plan_destroy(plan);
-        qd_check(rr, "summarize");
-        qd_check(qd_summary_merge(sum, peak->data(), floor->data(), &part, ppeak.data(), pfloor.data()), "merge");
+        qd_check(rr, what);
     }
     if (parts > 1) qd_check(qd_set_device(0), "set device");
     return true;
 }
 
-void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
-    const size_t W = sink.width; const uint64_t S = sink.stride;
+bool levels_fused(const ChainSpec &cs, const Op &sink, qd_summary *sum, std::vector<float> *peak, std::vector<float> *floor) {
+    return norms_fused(cs, sink, "summarize", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
+        const uint64_t per = ((complete + parts - 1) / parts + tile - 1) / tile * tile;       // tile-aligned ranges, as the library's own shards
+        const uint64_t w0 = std::min<uint64_t>(complete, per * g), w1 = std::min<uint64_t>(complete, per * (g + 1));
+        qd_summary part;
+        std::vector<float> ppeak(sink.width), pfloor(sink.width);
+        int mem = QD_MEM_HOST;
+        const void *src = w1 > w0 ? in.resident(&mem) : nullptr;
+        const int rc = qd_plan_summarize(plan, src, mem, 0, in.n_samples, w0, w1 - w0, &part, ppeak.data(), pfloor.data(), nullptr);
+        return rc ? rc : qd_summary_merge(sum, peak->data(), floor->data(), &part, ppeak.data(), pfloor.data());
+    });
+}
+
+// The iterator half of the norms sinks: the sink's arguments, the windows of sparkfft's loop (src/fft.rs:28-65) ...
+void check_norms_sink(const Op &sink) {
+    const size_t W = sink.width;
     if (!W || (W & (W - 1))) bail("Radix4 algorithm requires a power-of-two input size");
-    if (S == 0) bail("stride 0 never terminates");
+    if (sink.stride == 0) bail("stride 0 never terminates");
     if (W > 0xffffffffull) bail("width too large");
+}
+uint64_t spark_windows(const Samples &s, size_t W, uint64_t S) {
+    const uint64_t len = s.len();
+    if (len < W) bail("attempt to subtract with overflow");
+    const uint64_t lim = len - W;
+    return lim == 0 ? 0 : (lim - 1) / S + 1;
+}
+// ... and the norms of its windows [w0, w0 + nb), nb <= kIterBatch: each through read_exact_at, then side by side through a throwaway cf32 norms
+// plan.  With stop_short a read that fails ends the batch instead of the program.  Returns the windows whose norms are there.
+const uint64_t kIterBatch = 4096;
+uint64_t iter_norms(const Samples &s, const Op &sink, uint64_t w0, uint64_t nb, bool stop_short, std::vector<qd_c32> *buf, std::vector<float> *norms) {
+    const size_t W = sink.width;
+    buf->resize(kIterBatch * W); norms->resize(kIterBatch * W);
+    for (uint64_t i = 0; i < nb; ++i) {
+        try { s.read_exact_at((w0 + i) * sink.stride, buf->data() + i * W, W); } catch (const Fail &) { if (!stop_short) throw; nb = i; }
+    }
+    if (!nb) return 0;
+    qd_chain_desc d{};
+    d.struct_size = sizeof d;
+    d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
+    d.width = W; d.stride = W; d.epilogue = QD_EPI_NORMS_F32;
+    qd_plan *plan = nullptr;
+    qd_check(qd_plan_create(&d, &plan), "plan");
+    const int rc = qd_plan_run(plan, buf->data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms->data(), QD_MEM_HOST, nullptr);
+    qd_plan_destroy(plan);
+    qd_check(rc, "run");
+    return nb;
+}
+
+void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width;
+    check_norms_sink(sink);
     qd_summary sum;
     std::vector<float> peak(W), floor(W);
     qd_check(qd_summary_init(&sum, peak.data(), floor.data(), (uint32_t)W), "summary");
     bool done = false;
     if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = levels_fused(*cs, sink, &sum, &peak, &floor);
     if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) through read_exact_at, up to the first that fails; their norms from a
-        // side-by-side norms plan, folded on the host
-        uint64_t len = s.len();
-        if (len < W) bail("attempt to subtract with overflow");
-        const uint64_t lim = len - W, nwin = lim == 0 ? 0 : (lim - 1) / S + 1;
-        const uint64_t batch = 4096;
-        std::vector<qd_c32> buf(batch * W);
-        std::vector<float> norms(batch * W);
-        bool short_read = false;
-        for (uint64_t w0 = 0; w0 < nwin && !short_read; w0 += batch) {
-            uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
-            for (uint64_t i = 0; i < nb; ++i) {
-                try { s.read_exact_at((w0 + i) * S, buf.data() + i * W, W); } catch (const Fail &) { nb = i; short_read = true; break; }
-            }
-            if (!nb) break;
-            qd_chain_desc d{};
-            d.struct_size = sizeof d;
-            d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
-            d.width = W; d.stride = W; d.epilogue = QD_EPI_NORMS_F32;
-            qd_plan *plan = nullptr;
-            qd_check(qd_plan_create(&d, &plan), "plan");
-            const int rc = qd_plan_run(plan, buf.data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms.data(), QD_MEM_HOST, nullptr);
-            qd_plan_destroy(plan);
-            qd_check(rc, "run");
+        // up to the first window that fails, folded on the host
+        const uint64_t nwin = spark_windows(s, W, sink.stride);
+        std::vector<qd_c32> buf;
+        std::vector<float> norms;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t want = std::min(nwin - w0, kIterBatch), nb = iter_norms(s, sink, w0, want, true, &buf, &norms);
             qd_check(qd_summary_fold(&sum, peak.data(), floor.data(), norms.data(), nb), "fold");
+            if (nb < want) break;
         }
     }
     print_levels(s.sample_rate(), sink, sum, peak);
@@ -948,86 +958,35 @@ struct PeakRows {
 };
 
 bool peaks_fused(const ChainSpec &cs, const Op &sink, PeakRows *out) {
-    const bool from_gen = cs.src->kind == OP_GEN;
-    std::unique_ptr<MappedFile> data;
-    if (!from_gen) data.reset(new MappedFile(cs.src->filename));
-    qd_chain_desc d{};
-    d.struct_size = sizeof d;
-    d.format = from_gen ? QD_FMT_CF32 : cs.src->format; d.sample_rate = cs.src->sample_rate;
-    d.n_samples = from_gen ? (uint64_t)(cs.src->seconds * (double)cs.src->sample_rate) : data->size / qd_pair_bytes(cs.src->format);
-    std::vector<qd_stage> stages;
-    if (cs.cascade) {
-        for (const Op *op : cs.stages) {
-            qd_stage st{};
-            if (op->kind == OP_SHIFT) { st.kind = QD_STAGE_SHIFT; st.shift_hz = op->shift; }
-            else { st.kind = QD_STAGE_LOWPASS; st.lowpass_hz = op->lp_freq; st.decimate = op->decimate; st.taps = op->size; }
-            stages.push_back(st);
-        }
-    } else {
-        if (cs.shift) { d.has_shift = 1; d.shift_hz = cs.shift->shift; }
-        if (cs.lowpass) { d.has_lowpass = 1; d.lowpass_hz = cs.lowpass->lp_freq; d.decimate = cs.lowpass->decimate; d.taps = cs.lowpass->size; }
-    }
-    d.width = sink.width; d.stride = sink.stride; d.epilogue = QD_EPI_NORMS_F32;
-    int n_dev = 1;
-    if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
-    const int parts = from_gen ? 1 : g_gpus;
-    DeviceBuf gen_src;
     uint64_t rows_per = 0;
-    for (int g = 0; g < parts; ++g) {
-        // one unsharded plan per range of rows, made on that range's device
-        if (parts > 1) qd_check(qd_set_device(g % n_dev), "set device");
-        qd_plan *plan = nullptr;
-        const int rc = cs.cascade ? qd_plan_create_stages(&d, stages.data(), stages.size(), nullptr, &plan) : qd_plan_create(&d, &plan);
-        if (rc == QD_ERR_UNSUPPORTED && g == 0) return false;
-        qd_check(rc, "plan");
+    return norms_fused(cs, sink, sink.kind == OP_MEANS ? "mean" : "pool", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
         if (g == 0) {
-            uint64_t complete = 0;
-            qd_check(qd_plan_complete_windows(plan, &complete), "plan complete windows");
             out->size_for(sink, complete);
-            qd_plan_info info;
-            qd_check(qd_plan_get_info(plan, &info), "plan info");
             // ranges of whole rows that start on a tile of windows where the pool allows it, as the library's own shards do
-            uint64_t tile = info.tile_windows ? info.tile_windows : 1, a = tile, b = out->pool;
+            uint64_t a = tile, b = out->pool;
             while (b) { const uint64_t t = a % b; a = b; b = t; }
             const uint64_t q = tile / a;
             rows_per = ((out->rows + parts - 1) / parts + q - 1) / q * q;
         }
         const uint64_t r0 = std::min<uint64_t>(out->rows, rows_per * g), r1 = std::min<uint64_t>(out->rows, rows_per * (g + 1));
         const uint64_t w0 = r0 * out->pool, w1 = std::min<uint64_t>(out->windows, r1 * out->pool);
-        int rr = QD_OK;
-        if (w1 > w0 && from_gen) {
-            qd_check(qd_device_alloc((size_t)d.n_samples * 8, &gen_src.p), "device buffer for gen");
-            const uint64_t piece = 1ull << 28;
-            for (uint64_t at = 0; at < d.n_samples; at += piece) {
-                const uint64_t n = d.n_samples - at < piece ? d.n_samples - at : piece;
-                qd_check(qd_gen(cs.src->cos.data(), cs.src->cos.size(), cs.src->sample_rate, at, (size_t)n, static_cast<qd_c32 *>(gen_src.p) + at, QD_MEM_DEVICE), "gen");
-            }
-            rr = out->run(plan, gen_src.p, QD_MEM_DEVICE, d.n_samples, w0, w1, 0, sink.width);
-        } else if (w1 > w0) {
-            rr = out->run(plan, data->p, data->mem, d.n_samples, w0, w1, r0, sink.width);
-        }
-        qd_plan_destroy(plan);
-        qd_check(rr, out->mean ? "mean" : "pool");
-    }
-    if (parts > 1) qd_check(qd_set_device(0), "set device");
-    return true;
+        if (w1 <= w0) return (int)QD_OK;
+        int mem = QD_MEM_HOST;
+        const void *src = in.resident(&mem);
+        return out->run(plan, src, mem, in.n_samples, w0, w1, r0, sink.width);
+    });
 }
 
 void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     const size_t W = sink.width; const uint64_t S = sink.stride;
-    if (!W || (W & (W - 1))) bail("Radix4 algorithm requires a power-of-two input size");
-    if (S == 0) bail("stride 0 never terminates");
-    if (W > 0xffffffffull) bail("width too large");
+    check_norms_sink(sink);
     if (sink.has_range && !(sink.rmax > sink.rmin)) bail(std::string(sink.kind == OP_MEANS ? "means" : "peaks") + " -range takes lo:hi with lo < hi");
     PeakRows pr;
     bool done = false;
     if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = peaks_fused(*cs, sink, &pr);
     if (!done) {
         // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t len = s.len();
-        if (len < W) bail("attempt to subtract with overflow");
-        const uint64_t lim = len - W;
-        uint64_t nwin = lim == 0 ? 0 : (lim - 1) / S + 1;
+        uint64_t nwin = spark_windows(s, W, S);
         std::vector<qd_c32> buf(W);
         while (nwin) {
             try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
@@ -1037,22 +996,10 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
             pr.acc.resize(pr.rows * W * QD_MEAN_WORDS);
             qd_check(qd_mean_init(pr.acc.data(), (uint32_t)W, pr.rows), "mean init");
         }
-        // their norms from a side-by-side norms plan, folded on the host
-        const uint64_t batch = 4096;
-        buf.resize(batch * W);
-        std::vector<float> norms(batch * W);
-        for (uint64_t w0 = 0; w0 < nwin; w0 += batch) {
-            const uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
-            for (uint64_t i = 0; i < nb; ++i) s.read_exact_at((w0 + i) * S, buf.data() + i * W, W);
-            qd_chain_desc d{};
-            d.struct_size = sizeof d;
-            d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
-            d.width = W; d.stride = W; d.epilogue = QD_EPI_NORMS_F32;
-            qd_plan *plan = nullptr;
-            qd_check(qd_plan_create(&d, &plan), "plan");
-            const int rc = qd_plan_run(plan, buf.data(), QD_MEM_HOST, 0, nb * W, 0, nb, norms.data(), QD_MEM_HOST, nullptr);
-            qd_plan_destroy(plan);
-            qd_check(rc, "run");
+        // folded on the host
+        std::vector<float> norms;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
             if (pr.mean) qd_check(qd_mean_fold(pr.acc.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
             else qd_check(qd_pool_fold(pr.peak.data(), pr.floor.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
         }

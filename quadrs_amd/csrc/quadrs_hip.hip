@@ -17,6 +17,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <algorithm>
 #include <sys/stat.h>
@@ -2383,76 +2384,99 @@ int ensure_ring(qd_plan *p, size_t in_bytes, size_t ob, bool stage_in, bool stag
     return QD_OK;
 }
 
-// Host-resident stream: chunked, double-buffered H2D / kernel / D2H on two streams (slot = chunk parity).  A pageable
-// buffer (QD_MEM_HOST) is staged through a pinned ring with a multi-threaded memcpy; QD_MEM_HOST_PINNED memory is the
-// DMA source / target itself.  Each slot owns its device buffers AND its launch context (row tables, a two-stage plan's
-// carrier), so nothing a kernel in flight on the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
-int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window,
-             uint64_t n_windows, void *out, int out_mem, uint64_t obw) {
-    const double t_begin = now_ms();
-    p->stats = qd_plan_stats{};
+// Host-resident stream: windows [first_window, +n_windows) in chunks over the plan's two slots (slot = chunk parity, a stream each).  A chunk's
+// slab goes up (a pageable buffer, QD_MEM_HOST, through the slot's pinned staging buffer with a multi-threaded memcpy; QD_MEM_HOST_PINNED
+// memory is the DMA source itself) and through the plan's kernel into dev_out[slot]; `chunk` then enqueues, on the slot's stream, whatever
+// takes the windows from there.  Each slot owns its device buffers AND its launch context (row tables, a two-stage plan's carrier), so nothing
+// a kernel in flight on the other slot reads is ever touched.  Windows are kernel windows (sub-blocks for QD_EPI_CF32_BLOCKS).
+struct RingMode {
+    uint64_t bytes_per_window;      // what chunk_windows divides chunk_bytes by
+    uint64_t obw;                   // bytes per window in dev_out[slot]
+    bool stage_out;                 // pinned staging buffers for the way back too
+    bool sync_always;               // a slot's chunk is through before the slot is used again; else only when staged, or to bound the queue
+    qd_plan_stats *stats;           // bytes_h2d, chunks and the staging time are kept here (may be null)
+};
+using RingChunk = std::function<int(void *out_d, uint64_t w, uint64_t nw, int slot, hipStream_t st)>;
+using RingFreed = std::function<int(int slot)>;        // the slot's stream has been synchronised: finish what its last chunk left
+int walk_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+              const RingMode &m, const RingChunk &chunk, const RingFreed &freed) {
     const int bps = bps_of(p->d.format);
     const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T;
-    const uint64_t cw = chunk_windows(p, first_window, n_windows, step * bps);
-    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps), ob = (size_t)(cw * obw);
-    const bool stage_in = src_mem == QD_MEM_HOST, stage_out = out_mem == QD_MEM_HOST;
-    if (const int rc = ensure_ring(p, in_bytes, ob, stage_in, stage_out)) return rc;
-    double stage_ms = 0;
-    struct Pending { bool live = false; uint64_t w0 = 0, nw = 0; } pend[2];
-    auto drain = [&](int slot) -> int {
-        if (!pend[slot].live) return QD_OK;
-        HIPCHK(hipStreamSynchronize(p->streams[slot]));
-        if (stage_out) {
-            const double t0 = now_ms();
-            par_memcpy(static_cast<uint8_t *>(out) + (pend[slot].w0 - first_window) * obw, p->pin_out[slot], pend[slot].nw * obw, p->opt.copy_threads);
-            stage_ms += now_ms() - t0;
-        }
-        pend[slot].live = false;
-        return QD_OK;
-    };
+    const uint64_t cw = chunk_windows(p, first_window, n_windows, m.bytes_per_window);
+    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps);
+    const bool stage_in = src_mem == QD_MEM_HOST;
+    if (const int rc = ensure_ring(p, in_bytes, (size_t)(cw * m.obw), stage_in, m.stage_out)) return rc;
     // Any error after the first enqueue leaves H2D copies, kernels and D2H copies of earlier chunks in flight — with pinned
     // buffers the D2H target is the CALLER's memory.  Quiesce both slot streams before handing the status back.
     auto quiesce = [&](int status) -> int {
         for (int i = 0; i < 2; ++i) if (p->streams[i]) (void)hipStreamSynchronize(p->streams[i]);
         return status;
     };
+    auto release = [&](int slot) -> int {
+        if (hipError_t e = hipStreamSynchronize(p->streams[slot]); e != hipSuccess) return fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        return freed ? freed(slot) : QD_OK;
+    };
     int slot = 0;
     for (uint64_t w = first_window; w < first_window + n_windows; w += cw, slot ^= 1) {
         // a staged slot's pinned buffers are reused: wait for its previous chunk; a pinned-to-pinned run only needs
         // stream order (same slot = same stream), so the host runs ahead and just bounds the queue depth
-        int rc = (stage_in || stage_out || ((w - first_window) / cw) % 16 >= 14) ? drain(slot) : QD_OK;
+        int rc = (m.sync_always || stage_in || m.stage_out || ((w - first_window) / cw) % 16 >= 14) ? release(slot) : QD_OK;
         if (rc) return quiesce(rc);
-        const uint64_t nw = first_window + n_windows - w < cw ? first_window + n_windows - w : cw;
+        const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
         const uint64_t s0 = w * step, cnt = (nw - 1) * step + rpw;
         // keep vector loads aligned: start the slab on a multiple of 8 samples
         uint64_t s0a = s0 & ~7ull;
         if (s0a < src_first) s0a = src_first;
         const uint64_t cnta = s0 + cnt - s0a;
-        if (s0a < src_first || s0a + cnta > src_first + src_count)
+        if (s0 < src_first || s0a + cnta > src_first + src_count)
             return quiesce(fail(QD_ERR_INVALID, "src slab does not cover the requested windows"));
         const uint8_t *hsrc = static_cast<const uint8_t *>(src) + (s0a - src_first) * bps;
         if (stage_in) {
             const double t0 = now_ms();
             par_memcpy(p->pin_in[slot], hsrc, cnta * bps, p->opt.copy_threads);
-            stage_ms += now_ms() - t0;
+            if (m.stats) m.stats->stage_ms += now_ms() - t0;
             hsrc = static_cast<const uint8_t *>(p->pin_in[slot]);
         }
         if (hipError_t e = hipMemcpyAsync(p->dev_in[slot], hsrc, cnta * bps, hipMemcpyHostToDevice, p->streams[slot]); e != hipSuccess)
             return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(e)));
         rc = launch_windows(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
+        if (rc == QD_OK) rc = chunk(p->dev_out[slot], w, nw, slot, p->streams[slot]);
         if (rc) return quiesce(rc);
-        void *hdst = stage_out ? p->pin_out[slot] : static_cast<void *>(static_cast<uint8_t *>(out) + (w - first_window) * obw);
-        if (hipError_t e = hipMemcpyAsync(hdst, p->dev_out[slot], nw * obw, hipMemcpyDeviceToHost, p->streams[slot]); e != hipSuccess)
-            return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (D2H): %s", hipGetErrorString(e)));
-        pend[slot].live = true; pend[slot].w0 = w; pend[slot].nw = nw;
-        p->stats.bytes_h2d += cnta * bps; p->stats.bytes_d2h += nw * obw; p->stats.chunks += 1;
+        if (m.stats) { m.stats->bytes_h2d += cnta * bps; m.stats->chunks += 1; }
     }
-    int rc = drain(0);
-    if (rc) return quiesce(rc);
-    rc = drain(1);
-    if (rc) return quiesce(rc);
-    p->stats.stage_ms = stage_ms;
-    p->stats.wall_ms = now_ms() - t_begin;
+    for (int i = 0; i < 2; ++i)
+        if (const int rc = release(i)) return quiesce(rc);
+    return QD_OK;
+}
+
+// a run: each chunk's windows come back by a D2H copy on the slot's stream, into the caller's pinned memory or, for pageable memory, into
+// the slot's pinned buffer, which is copied out once the slot's stream is through
+int run_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window,
+             uint64_t n_windows, void *out, int out_mem, uint64_t obw) {
+    const double t_begin = now_ms();
+    p->stats = qd_plan_stats{};
+    const bool stage_out = out_mem == QD_MEM_HOST;
+    struct Pending { bool live = false; uint64_t w0 = 0, nw = 0; } pend[2];
+    const int rc = walk_host(p, src, src_mem, src_first, src_count, first_window, n_windows,
+        RingMode{(uint64_t)p->S * p->D * bps_of(p->d.format), obw, stage_out, false, &p->stats},
+        [&](void *out_d, uint64_t w, uint64_t nw, int slot, hipStream_t st) -> int {
+            void *hdst = stage_out ? p->pin_out[slot] : static_cast<void *>(static_cast<uint8_t *>(out) + (w - first_window) * obw);
+            if (hipError_t e = hipMemcpyAsync(hdst, out_d, nw * obw, hipMemcpyDeviceToHost, st); e != hipSuccess)
+                return fail(QD_ERR_HIP, "hipMemcpyAsync (D2H): %s", hipGetErrorString(e));
+            pend[slot].live = true; pend[slot].w0 = w; pend[slot].nw = nw;
+            p->stats.bytes_d2h += nw * obw;
+            return QD_OK;
+        },
+        [&](int slot) -> int {
+            if (pend[slot].live && stage_out) {
+                const double t0 = now_ms();
+                par_memcpy(static_cast<uint8_t *>(out) + (pend[slot].w0 - first_window) * obw, p->pin_out[slot], pend[slot].nw * obw, p->opt.copy_threads);
+                p->stats.stage_ms += now_ms() - t0;
+            }
+            pend[slot].live = false;
+            return QD_OK;
+        });
+    if (rc == QD_OK) p->stats.wall_ms = now_ms() - t_begin;
     return rc;
 }
 }  // namespace
@@ -3212,47 +3236,90 @@ int launch_summary(const qd_plan *p, const float *norms_d, uint64_t n_rows, SumA
     return QD_OK;
 }
 
-// Host-resident stream: run_host's ring without the way back — each slot's chunk goes up, through the plan's norms kernel into the slot's
-// device buffer and from there, by fold(norms, first window, windows, stream), into the one accumulator (atomics: the two slots' streams
-// may fold at the same time).
-using HostFold = std::function<int(const float *, uint64_t, uint64_t, hipStream_t)>;
-int fold_host(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
-              const HostFold &fold) {
-    const int bps = bps_of(p->d.format);
-    const uint64_t step = (uint64_t)p->S * p->D, rpw = (uint64_t)p->W * p->D + p->T, obw = (uint64_t)p->W * 4;
-    const uint64_t cw = chunk_windows(p, first_window, n_windows, std::max<uint64_t>(step * bps, obw));
-    const size_t in_bytes = (size_t)(((cw - 1) * step + rpw + 8) * bps);
-    const bool stage_in = src_mem == QD_MEM_HOST;
-    if (const int rc = ensure_ring(p, in_bytes, (size_t)(cw * obw), stage_in, false)) return rc;
-    auto quiesce = [&](int status) -> int {
-        for (int i = 0; i < 2; ++i) if (p->streams[i]) (void)hipStreamSynchronize(p->streams[i]);
-        return status;
-    };
-    int slot = 0;
-    for (uint64_t w = first_window; w < first_window + n_windows; w += cw, slot ^= 1) {
-        // the slot's pinned staging buffer and device buffers are reused: its previous chunk must be through
-        if (hipError_t e = hipStreamSynchronize(p->streams[slot]); e != hipSuccess) return quiesce(fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e)));
-        const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
-        const uint64_t s0 = w * step, cnt = (nw - 1) * step + rpw;
-        uint64_t s0a = s0 & ~7ull;                       // keep vector loads aligned, as run_host does
-        if (s0a < src_first) s0a = src_first;
-        const uint64_t cnta = s0 + cnt - s0a;
-        if (s0 < src_first || s0a + cnta > src_first + src_count)
-            return quiesce(fail(QD_ERR_INVALID, "src slab does not cover the requested windows"));
-        const uint8_t *hsrc = static_cast<const uint8_t *>(src) + (s0a - src_first) * bps;
-        if (stage_in) {
-            par_memcpy(p->pin_in[slot], hsrc, cnta * bps, p->opt.copy_threads);
-            hsrc = static_cast<const uint8_t *>(p->pin_in[slot]);
-        }
-        if (hipError_t e = hipMemcpyAsync(p->dev_in[slot], hsrc, cnta * bps, hipMemcpyHostToDevice, p->streams[slot]); e != hipSuccess)
-            return quiesce(fail(QD_ERR_HIP, "hipMemcpyAsync (H2D): %s", hipGetErrorString(e)));
-        int rc = launch_windows(p, &p->tabs_slot[slot], p->dev_in[slot], s0a, cnta, w, nw, w, p->dev_out[slot], p->streams[slot]);
-        if (rc == QD_OK) rc = fold(static_cast<const float *>(p->dev_out[slot]), w, nw, p->streams[slot]);
-        if (rc) return quiesce(rc);
+// The driver of the folds of a norms plan's windows (qd_plan_summarize, qd_plan_pool, qd_plan_mean).  An entry point
+// calls its steps in this order, with its own argument checks where they have always stood:
+//   norms_plan, unsharded, admit    the refusals every fold shares, and the cascade short-read clamp (n_windows is the complete part after it)
+//   open                            plan mutex, device, workspace lease: from here the sink lays out and initialises its accumulators ("begin")
+//   walk (or device / host)         the norms of every window, batch by batch, to the sink's launch ("batch")
+//   close (or sync, short_read)     after the sink has queued its results' way home ("end"): stream sync, status merge, the short read's report
+struct Fold {
+    qd_plan *p; const char *call;
+    const void *src; int src_mem; uint64_t src_first, src_count, first_window, n_windows;
+    hipStream_t st;
+    bool is_short = false;
+    std::unique_lock<std::mutex> lock;
+    std::optional<DeviceGuard> guard;
+    std::optional<WsLease> ws;
+    float *car = nullptr; uint64_t cw = 0;          // device sources: the carrier (workspace slot 0) and its windows
+
+    // one batch of norms rows (device memory, 16-byte aligned), windows [g0, g0 + nw) of the range, to be folded on `st`
+    using Batch = std::function<int(const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t st)>;
+
+    int norms_plan() const {
+        if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "%s folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan", call);
+        return QD_OK;
     }
-    for (int i = 0; i < 2; ++i) HIPCHK(hipStreamSynchronize(p->streams[i]));
-    return QD_OK;
-}
+    int unsharded(const char *advice) const { return p->opt.n_shards > 1 ? fail(QD_ERR_UNSUPPORTED, "%s", advice) : QD_OK; }
+    int admit() {
+        if (first_window + n_windows > p->n_windows)
+            return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
+                        (unsigned long long)n_windows, (unsigned long long)p->n_windows);
+        if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+        if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
+            n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
+            is_short = true;
+        }
+        return known_mem(src_mem, "src_mem");
+    }
+    static int known_mem(int mem, const char *what) { return mem == QD_MEM_DEVICE || host_kind(mem) ? QD_OK : fail(QD_ERR_INVALID, "unknown %s %d", what, mem); }
+    int open() {
+        if (n_windows && !src) return fail(QD_ERR_INVALID, "src is NULL");
+        lock = std::unique_lock<std::mutex>(p->mu);
+        guard.emplace(p->device);
+        ws.emplace(st);
+        return ws->rc;
+    }
+    // device sources: the carrier holds at most max(chunk_bytes, a tile of windows) of norms; windows [g0, g0 + nw), nw <= cw, go through the
+    // plan's own norms kernel into it, then the sink's launch behind it
+    int carrier() {
+        cw = chunk_windows(p, first_window, n_windows, (uint64_t)p->W * 4);
+        void *c = nullptr;
+        const int rc = ws->get(0, (size_t)(cw * p->W * 4), &c);
+        car = static_cast<float *>(c);
+        return rc;
+    }
+    int device(uint64_t g0, uint64_t nw, const Batch &batch) {
+        const int rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, first_window + g0, nw, first_window + g0, car, st);
+        return rc ? rc : batch(car, g0, nw, st);
+    }
+    // host sources: windows [g0, g0 + n) up the plan's ring, which cuts its own batches on its two streams; their launches fold into the
+    // sink's accumulators side by side (atomics), so whatever `st` holds for those is through first.  The run statistics stay the last run's.
+    int host(uint64_t g0, uint64_t n, const Batch &batch) {
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t obw = (uint64_t)p->W * 4;
+        return walk_host(p, src, src_mem, src_first, src_count, first_window + g0, n,
+                         RingMode{std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), obw), obw, false, true, nullptr},
+                         [&](void *norms_d, uint64_t w, uint64_t nw, int, hipStream_t s) { return batch(static_cast<const float *>(norms_d), w - first_window, nw, s); },
+                         nullptr);
+    }
+    int walk(const Batch &batch) {
+        if (n_windows == 0) return QD_OK;
+        if (src_mem != QD_MEM_DEVICE) return host(0, n_windows, batch);
+        int rc = carrier();
+        for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK; g0 += cw) rc = device(g0, std::min<uint64_t>(n_windows - g0, cw), batch);
+        return rc;
+    }
+    int sync(int rc) const {
+        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        return rc;
+    }
+    int short_read() const {
+        if (!is_short) return QD_OK;
+        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
+                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
+    }
+    int close(int rc) const { rc = sync(rc); return rc ? rc : short_read(); }
+};
 }  // namespace
 
 int qd_summary_init(qd_summary *sum, float *peak, float *floor, uint32_t width) {
@@ -3331,59 +3398,30 @@ int qd_summary_quantile(const qd_summary *sum, double q, float *lo, float *hi) {
 int qd_plan_summarize(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
                       qd_summary *sum, float *peak, float *floor, void *stream) {
     if (!p || !sum) return fail(QD_ERR_INVALID, "NULL argument");
-    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_summarize folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
-    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not summarised in one call: summarise each shard's windows on a plan of its own and qd_summary_merge them");
+    Fold f{p, "qd_plan_summarize", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not summarised in one call: summarise each shard's windows on a plan of its own and qd_summary_merge them")) return rc;
     const uint32_t W = p->W;
     (void)qd_summary_init(sum, peak, floor, W);
-    if (first_window + n_windows > p->n_windows)
-        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
-                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
-    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
-    bool is_short = false;
-    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
-        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
-        is_short = true;
-    }
-    const bool dev = src_mem == QD_MEM_DEVICE;
-    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
-    if (n_windows) {
-        if (!src) return fail(QD_ERR_INVALID, "src is NULL");
-        std::lock_guard<std::mutex> lock(p->mu);
-        DeviceGuard guard(p->device);
-        const hipStream_t st = static_cast<hipStream_t>(stream);
-        WsLease ws(st);
-        if (ws.rc) return ws.rc;
+    if (const int rc = f.admit()) return rc;
+    if (f.n_windows) {
+        if (const int rc = f.open()) return rc;
         // the accumulator starts from the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
         const size_t acc_bytes = sum_acc_bytes(W);
         std::vector<uint32_t> image(acc_bytes / 4, 0u);
         uint32_t *ipeak = image.data() + sizeof(SumAcc) / 4, *ifloor = ipeak + W;
         for (uint32_t b = 0; b < W; ++b) ifloor[b] = kSumInfBits;
         void *acc_v = nullptr;
-        int rc = ws.get(1, acc_bytes, &acc_v); if (rc) return rc;
+        if (const int rc = f.ws->get(1, acc_bytes, &acc_v)) return rc;
         SumAcc *acc = static_cast<SumAcc *>(acc_v);
-        HIPCHK(hipMemcpyAsync(acc, image.data(), acc_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));                 // host path: the slots' streams fold into it too
-        if (dev) {
-            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
-            const uint64_t cw = chunk_windows(p, first_window, n_windows, (uint64_t)W * 4);
-            void *car = nullptr;
-            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
-            for (uint64_t w = first_window; w < first_window + n_windows && rc == QD_OK; w += cw) {
-                const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
-                rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, w, nw, w, car, st);
-                if (rc == QD_OK) rc = launch_summary(p, static_cast<const float *>(car), nw, acc, st);
-            }
-        } else {
-            rc = fold_host(p, src, src_mem, src_first, src_count, first_window, n_windows,
-                           [&](const float *norms_d, uint64_t, uint64_t nw, hipStream_t s) { return launch_summary(p, norms_d, nw, acc, s); });
-        }
-        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
+        HIPCHK(hipMemcpyAsync(acc, image.data(), acc_bytes, hipMemcpyHostToDevice, f.st));
+        const int rc = f.sync(f.walk([&](const float *norms_d, uint64_t, uint64_t nw, hipStream_t s) { return launch_summary(p, norms_d, nw, acc, s); }));
         if (rc) return rc;
         HIPCHK(hipMemcpy(image.data(), acc, acc_bytes, hipMemcpyDeviceToHost));
         const SumAcc *h = reinterpret_cast<const SumAcc *>(image.data());
         memcpy(sum->hist, h->hist, sizeof sum->hist);
         sum->n_nan = h->n_nan;
-        sum->n_windows = n_windows;
+        sum->n_windows = f.n_windows;
         uint32_t mx = 0, mn = kSumInfBits;
         for (uint32_t b = 0; b < W; ++b) {
             mx = std::max(mx, ipeak[b]); mn = std::min(mn, ifloor[b]);
@@ -3392,10 +3430,7 @@ int qd_plan_summarize(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
         }
         sum->max = f32_of_bits(mx); sum->min = f32_of_bits(mn);
     }
-    if (is_short)
-        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
-                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
-    return QD_OK;
+    return f.short_read();
 }
 
 // ------------------------------------------------------------------ peak-hold rows
@@ -3449,73 +3484,40 @@ int qd_pool_fold(float *peak_rows, float *floor_rows, uint32_t width, uint64_t p
 int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
                  uint64_t pool, float *peak_rows, float *floor_rows, int out_mem, void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
-    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_pool folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
+    Fold f{p, "qd_plan_pool", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
     if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
     if (!peak_rows && !floor_rows) return fail(QD_ERR_INVALID, "both peak_rows and floor_rows are NULL");
-    const bool dev = src_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
-    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
-    if (!out_dev && !host_kind(out_mem)) return fail(QD_ERR_INVALID, "unknown out_mem %d", out_mem);
-    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not pooled in one call: give each device a contiguous range of rows on a plan of its own");
-    if (first_window + n_windows > p->n_windows)
-        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
-                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
-    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not pooled in one call: give each device a contiguous range of rows on a plan of its own")) return rc;
+    if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
     if (pool > n_windows) pool = n_windows;                          // one row either way
     const uint32_t W = p->W;
-    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;
-    bool is_short = false;
-    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
-        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
-        is_short = true;
+    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;    // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = f.open()) return rc;
+    // the accumulators: the caller's arrays when they are device memory, else [peak][floor] in the workspace
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    const hipStream_t st = f.st;
+    uint32_t *peak_d = reinterpret_cast<uint32_t *>(peak_rows), *floor_d = reinterpret_cast<uint32_t *>(floor_rows);
+    if (!out_dev) {
+        void *acc = nullptr;
+        if (const int rc = f.ws->get(1, (size_t)(words * 4 * ((peak_rows ? 1 : 0) + (floor_rows ? 1 : 0))), &acc)) return rc;
+        peak_d = peak_rows ? static_cast<uint32_t *>(acc) : nullptr;
+        floor_d = floor_rows ? static_cast<uint32_t *>(acc) + (peak_rows ? words : 0) : nullptr;
     }
-    if (n_windows && !src) return fail(QD_ERR_INVALID, "src is NULL");
-    {
-        std::lock_guard<std::mutex> lock(p->mu);
-        DeviceGuard guard(p->device);
-        const hipStream_t st = static_cast<hipStream_t>(stream);
-        WsLease ws(st);
-        if (ws.rc) return ws.rc;
-        // the accumulators: the caller's arrays when they are device memory, else [peak][floor] in the workspace
-        uint32_t *peak_d = reinterpret_cast<uint32_t *>(peak_rows), *floor_d = reinterpret_cast<uint32_t *>(floor_rows);
-        int rc = QD_OK;
-        if (!out_dev) {
-            void *acc = nullptr;
-            rc = ws.get(1, (size_t)(words * 4 * ((peak_rows ? 1 : 0) + (floor_rows ? 1 : 0))), &acc); if (rc) return rc;
-            peak_d = peak_rows ? static_cast<uint32_t *>(acc) : nullptr;
-            floor_d = floor_rows ? static_cast<uint32_t *>(acc) + (peak_rows ? words : 0) : nullptr;
-        }
-        // the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
-        if (peak_d) HIPCHK(hipMemsetAsync(peak_d, 0, (size_t)(words * 4), st));
-        if (floor_d) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(floor_d), (int)kPoolInfBits, (size_t)words, st));
-        if (n_windows && dev) {
-            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
-            const uint64_t cw = chunk_windows(p, first_window, n_windows, (uint64_t)W * 4);
-            void *car = nullptr;
-            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
-            for (uint64_t w = first_window; w < first_window + n_windows && rc == QD_OK; w += cw) {
-                const uint64_t nw = std::min<uint64_t>(first_window + n_windows - w, cw);
-                rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, w, nw, w, car, st);
-                if (rc == QD_OK) rc = launch_pool(p, static_cast<const float *>(car), w - first_window, nw, n_windows, pool, peak_d, floor_d, st);
-            }
-        } else if (n_windows) {
-            HIPCHK(hipStreamSynchronize(st));             // the slots' streams fold into the accumulators too
-            rc = fold_host(p, src, src_mem, src_first, src_count, first_window, n_windows,
-                           [&](const float *norms_d, uint64_t w, uint64_t nw, hipStream_t s) {
-                               return launch_pool(p, norms_d, w - first_window, nw, n_windows, pool, peak_d, floor_d, s);
-                           });
-        }
-        if (rc == QD_OK && !out_dev) {
-            if (peak_rows) HIPCHK(hipMemcpyAsync(peak_rows, peak_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-            if (floor_rows) HIPCHK(hipMemcpyAsync(floor_rows, floor_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-        }
-        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
-        if (rc) return rc;
+    // the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
+    if (peak_d) HIPCHK(hipMemsetAsync(peak_d, 0, (size_t)(words * 4), st));
+    if (floor_d) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(floor_d), (int)kPoolInfBits, (size_t)words, st));
+    const int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+        return launch_pool(p, norms_d, g0, nw, f.n_windows, pool, peak_d, floor_d, s);
+    });
+    if (rc == QD_OK && !out_dev) {
+        if (peak_rows) HIPCHK(hipMemcpyAsync(peak_rows, peak_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+        if (floor_rows) HIPCHK(hipMemcpyAsync(floor_rows, floor_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
     }
-    if (is_short)
-        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
-                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
-    return QD_OK;
+    return f.close(rc);
 }
 
 // ------------------------------------------------------------------ average-trace rows
@@ -3615,125 +3617,106 @@ int qd_mean_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *me
 int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
                  uint64_t pool, float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
-    if (p->rows || p->d.epilogue != QD_EPI_NORMS_F32) return fail(QD_ERR_INVALID, "qd_plan_mean folds the norms sink's rows: it needs a QD_EPI_NORMS_F32 plan");
+    Fold f{p, "qd_plan_mean", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
     if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
     if (!mean_rows && !sum_rows && !count_rows) return fail(QD_ERR_INVALID, "mean_rows, sum_rows and count_rows are all NULL");
-    const bool dev = src_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
-    if (!dev && !host_kind(src_mem)) return fail(QD_ERR_INVALID, "unknown src_mem %d", src_mem);
-    if (!out_dev && !host_kind(out_mem)) return fail(QD_ERR_INVALID, "unknown out_mem %d", out_mem);
-    if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)");
-    if (first_window + n_windows > p->n_windows)
-        return fail(QD_ERR_SHORT, "windows [%llu,+%llu) exceed the sink's loop (%llu windows)", (unsigned long long)first_window,
-                    (unsigned long long)n_windows, (unsigned long long)p->n_windows);
-    if (src_first + src_count > p->d.n_samples) return fail(QD_ERR_INVALID, "src slab exceeds the stream length");
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)")) return rc;
+    if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
     if (pool > n_windows) pool = n_windows;                          // one row either way
     if (pool > kMeanMaxCount) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)pool);
     const uint32_t W = p->W;
-    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;
-    bool is_short = false;
-    if (p->casc && first_window + n_windows > p->c_complete) {       // as qd_plan_run: every complete window of the range, then the short read
-        n_windows = first_window < p->c_complete ? p->c_complete - first_window : 0;
-        is_short = true;
+    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;    // rows of the range as asked ...
+    n_windows = f.n_windows;                                         // ... and from here its complete part
+    if (int rc = f.open()) return rc;
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    const hipStream_t st = f.st;
+    int rc = QD_OK;
+    // the outputs: the caller's arrays when they are device memory, else [sum][mean][count] in the workspace, copied down once
+    MeanOut out{mean_rows, sum_rows, count_rows};
+    if (!out_dev) {
+        void *o = nullptr;
+        rc = f.ws->get(2, (size_t)(words * ((sum_rows ? 8 : 0) + (mean_rows ? 4 : 0) + (count_rows ? 4 : 0))), &o); if (rc) return rc;
+        uint8_t *at = static_cast<uint8_t *>(o);
+        out.sum = sum_rows ? reinterpret_cast<double *>(at) : nullptr; at += sum_rows ? words * 8 : 0;
+        out.mean = mean_rows ? reinterpret_cast<float *>(at) : nullptr; at += mean_rows ? words * 4 : 0;
+        out.count = count_rows ? reinterpret_cast<uint32_t *>(at) : nullptr;
     }
-    if (n_windows && !src) return fail(QD_ERR_INVALID, "src is NULL");
-    {
-        std::lock_guard<std::mutex> lock(p->mu);
-        DeviceGuard guard(p->device);
-        const hipStream_t st = static_cast<hipStream_t>(stream);
-        WsLease ws(st);
-        if (ws.rc) return ws.rc;
-        int rc = QD_OK;
-        // the outputs: the caller's arrays when they are device memory, else [sum][mean][count] in the workspace, copied down once
-        MeanOut out{mean_rows, sum_rows, count_rows};
-        if (!out_dev) {
-            void *o = nullptr;
-            rc = ws.get(2, (size_t)(words * ((sum_rows ? 8 : 0) + (mean_rows ? 4 : 0) + (count_rows ? 4 : 0))), &o); if (rc) return rc;
-            uint8_t *at = static_cast<uint8_t *>(o);
-            out.sum = sum_rows ? reinterpret_cast<double *>(at) : nullptr; at += sum_rows ? words * 8 : 0;
-            out.mean = mean_rows ? reinterpret_cast<float *>(at) : nullptr; at += mean_rows ? words * 4 : 0;
-            out.count = count_rows ? reinterpret_cast<uint32_t *>(at) : nullptr;
+    if (f.is_short) {                                                // rows without a complete window: no values
+        if (out.mean) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out.mean), (int)kMeanNanBits, (size_t)words, st));
+        if (out.sum) HIPCHK(hipMemsetAsync(out.sum, 0, (size_t)(words * 8), st));
+        if (out.count) HIPCHK(hipMemsetAsync(out.count, 0, (size_t)(words * 4), st));
+    }
+    // the limb accumulator (qd_mean.h): at most max(2 chunk_bytes, one row), its flags behind it
+    const uint64_t row_bytes = (uint64_t)W * kMeanWords * 8;
+    const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
+    MeanAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
+    if (n_windows) {
+        void *a = nullptr;
+        rc = f.ws->get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
+        acc.limbs = static_cast<unsigned long long *>(a);
+        acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
+    }
+    auto geometry = [&](uint64_t g0, uint64_t nw, MeanParams *M, uint64_t *grid, int *V) { pool_geometry(g0, nw, n_windows, pool, W, p->n_cu, &M->G, grid, V); };
+    if (n_windows && src_mem == QD_MEM_DEVICE) {
+        // this sink cuts its own batches of the carrier's windows
+        rc = f.carrier();
+        const uint64_t cw = f.cw, bw = pool <= cw ? cw / pool * pool : cw;       // seams on row boundaries where a chunk holds a row
+        bool open = false;
+        uint64_t r_base = 0;
+        auto close = [&]() { const int c = open ? launch_mean_finish(p, acc, r_base, std::min(acc.rows, R - r_base), out, st) : QD_OK; open = false; return c; };
+        for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
+            uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
+            MeanParams M{};
+            int V = 1;
+            geometry(g0, nw, &M, &grid, &V);
+            const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
+            const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
+            const bool cuts = M.G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
+            if (cuts) {
+                if (!open || (!mid && rb >= r_base + acc.rows)) {                // move the accumulator: only between rows
+                    rc = close();
+                    if (rc == QD_OK) rc = mean_acc_clear(p, acc, st);
+                    r_base = ra; open = true;
+                }
+                if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
+                    nw = (r_base + acc.rows) * pool - g0;
+                    geometry(g0, nw, &M, &grid, &V);
+                }
+            }
+            if (rc == QD_OK)
+                rc = f.device(g0, nw, [&](const float *norms_d, uint64_t, uint64_t, hipStream_t s) {
+                    return launch_mean(p, M, grid, V, norms_d, out, acc, cuts, cuts ? r_base : ra, s);
+                });
+            g0 += nw;
         }
-        if (is_short) {                                              // rows without a complete window: no values
-            if (out.mean) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out.mean), (int)kMeanNanBits, (size_t)words, st));
-            if (out.sum) HIPCHK(hipMemsetAsync(out.sum, 0, (size_t)(words * 8), st));
-            if (out.count) HIPCHK(hipMemsetAsync(out.count, 0, (size_t)(words * 4), st));
-        }
-        // the limb accumulator (qd_mean.h): at most max(2 chunk_bytes, one row), its flags behind it
-        const uint64_t cw = n_windows ? chunk_windows(p, first_window, n_windows, (uint64_t)W * 4) : 1;
-        const uint64_t row_bytes = (uint64_t)W * kMeanWords * 8;
-        const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
-        MeanAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
-        if (n_windows) {
-            void *a = nullptr;
-            rc = ws.get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
-            acc.limbs = static_cast<unsigned long long *>(a);
-            acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
-        }
-        auto geometry = [&](uint64_t g0, uint64_t nw, MeanParams *M, uint64_t *grid, int *V) { pool_geometry(g0, nw, n_windows, pool, W, p->n_cu, &M->G, grid, V); };
-        if (n_windows && dev) {
-            // batch by batch through the plan's own norms kernel into the carrier: at most max(chunk_bytes, a tile of windows) of norms
-            void *car = nullptr;
-            rc = ws.get(0, (size_t)(cw * W * 4), &car); if (rc) return rc;
-            const uint64_t bw = pool <= cw ? cw / pool * pool : cw;                  // seams on row boundaries where a chunk holds a row
-            bool open = false;
-            uint64_t r_base = 0;
-            auto close = [&]() { const int c = open ? launch_mean_finish(p, acc, r_base, std::min(acc.rows, R - r_base), out, st) : QD_OK; open = false; return c; };
-            for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
-                uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
+        if (rc == QD_OK) rc = close();
+    } else if (n_windows) {
+        // host sources: the upload ring cuts its own batches, on two streams; the range goes span by span of the accumulator's rows
+        const uint64_t Rn = (n_windows - 1) / pool + 1;
+        for (uint64_t r_base = 0; r_base < Rn && rc == QD_OK; r_base += acc.rows) {
+            const uint64_t g_a = r_base * pool, g_b = std::min<uint64_t>(n_windows, (r_base + acc.rows) * pool);
+            rc = mean_acc_clear(p, acc, st);
+            if (rc) break;
+            rc = f.host(g_a, g_b - g_a, [&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
                 MeanParams M{};
+                uint64_t grid = 0;
                 int V = 1;
                 geometry(g0, nw, &M, &grid, &V);
-                const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
-                const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
-                const bool cuts = M.G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
-                if (cuts) {
-                    if (!open || (!mid && rb >= r_base + acc.rows)) {                // move the accumulator: only between rows
-                        rc = close();
-                        if (rc == QD_OK) rc = mean_acc_clear(p, acc, st);
-                        r_base = ra; open = true;
-                    }
-                    if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
-                        nw = (r_base + acc.rows) * pool - g0;
-                        geometry(g0, nw, &M, &grid, &V);
-                    }
-                }
-                if (rc == QD_OK) rc = launch_windows(p, &p->tabs_dev, src, src_first, src_count, first_window + g0, nw, first_window + g0, car, st);
-                if (rc == QD_OK) rc = launch_mean(p, M, grid, V, static_cast<const float *>(car), out, acc, cuts, cuts ? r_base : ra, st);
-                g0 += nw;
-            }
-            if (rc == QD_OK) rc = close();
-        } else if (n_windows) {
-            // host sources: the upload ring cuts its own batches, on two streams; the range goes span by span of the accumulator's rows
-            const uint64_t Rn = (n_windows - 1) / pool + 1;
-            for (uint64_t r_base = 0; r_base < Rn && rc == QD_OK; r_base += acc.rows) {
-                const uint64_t g_a = r_base * pool, g_b = std::min<uint64_t>(n_windows, (r_base + acc.rows) * pool);
-                rc = mean_acc_clear(p, acc, st);
-                if (rc) break;
-                HIPCHK(hipStreamSynchronize(st));         // the slots' streams fold into the outputs and the accumulator too
-                rc = fold_host(p, src, src_mem, src_first, src_count, first_window + g_a, g_b - g_a,
-                               [&](const float *norms_d, uint64_t w, uint64_t nw, hipStream_t s) {
-                                   MeanParams M{};
-                                   uint64_t grid = 0;
-                                   int V = 1;
-                                   geometry(w - first_window, nw, &M, &grid, &V);
-                                   return launch_mean(p, M, grid, V, norms_d, out, acc, true, r_base, s);
-                               });
-                if (rc == QD_OK) rc = launch_mean_finish(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
-            }
+                return launch_mean(p, M, grid, V, norms_d, out, acc, true, r_base, s);
+            });
+            if (rc == QD_OK) rc = launch_mean_finish(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
         }
-        if (rc == QD_OK && !out_dev) {
-            if (mean_rows) HIPCHK(hipMemcpyAsync(mean_rows, out.mean, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-            if (sum_rows) HIPCHK(hipMemcpyAsync(sum_rows, out.sum, (size_t)(words * 8), hipMemcpyDeviceToHost, st));
-            if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, out.count, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-        }
-        if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess && rc == QD_OK) rc = fail(QD_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
-        if (rc) return rc;
     }
-    if (is_short)
-        return fail(QD_ERR_SHORT, "window %llu: read_exact_at reads fewer samples than asked (%llu complete windows of %llu)",
-                    (unsigned long long)p->c_complete, (unsigned long long)p->c_complete, (unsigned long long)p->n_windows);
-    return QD_OK;
+    if (rc == QD_OK && !out_dev) {
+        if (mean_rows) HIPCHK(hipMemcpyAsync(mean_rows, out.mean, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+        if (sum_rows) HIPCHK(hipMemcpyAsync(sum_rows, out.sum, (size_t)(words * 8), hipMemcpyDeviceToHost, st));
+        if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, out.count, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+    }
+    return f.close(rc);
 }
 
 int qd_device_alloc(size_t bytes, void **ptr) {

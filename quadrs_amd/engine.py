@@ -542,19 +542,41 @@ class Plan:
                                      _np_ptr(rows), MEM_HOST, None))
         return rows
 
+    def _src_args(self, src, pinned):
+        """(ptr, mem, count, stream, keepalive) of a fold's source: bytes / numpy array (host; pinned=True for a PinnedBuffer array) or a
+        torch CUDA tensor (device, torch's current stream)."""
+        if _is_torch(src):
+            return C.c_void_p(src.data_ptr()), MEM_DEVICE, src.numel() * src.element_size() // _FMT_BYTES[self.desc.format], _cur_stream(), src
+        buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+        return _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), buf.size // _FMT_BYTES[self.desc.format], None, buf
+
+    def _fold_rows(self, call, dtypes, src, pool, first_window, n_windows, src_first, pinned, device_out):
+        """one [ceil(n_windows / pool), width] array per dtype, filled by `call` (qd_plan_pool, qd_plan_mean): torch CUDA tensors (the default
+        for a torch src; uint32 as int32, the same bits) or numpy arrays.  A failing call's error carries them as e.partial."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        if _is_torch(src) if device_out is None else device_out:
+            import torch
+            out = tuple(torch.empty((rows, self.width), dtype=getattr(torch, t.replace("uint32", "int32")), device="cuda") for t in dtypes)
+            ptrs, out_mem = [C.c_void_p(o.data_ptr()) for o in out], MEM_DEVICE
+        else:
+            out = tuple(np.empty((rows, self.width), dtype=t) for t in dtypes)
+            ptrs, out_mem = [_np_ptr(o) for o in out], MEM_HOST
+        try:
+            check(call(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), *ptrs, out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = out                      # QD_ERR_SHORT of a cascade: the complete windows are folded
+            raise
+        return out
+
     def summarize(self, src, first_window=0, n_windows=None, src_first=0, pinned=False):
         """qd_plan_summarize of an EPI_NORMS_F32 plan: the Summary (min, max, n_nan, n_windows, hist, peak, floor) of windows
         [first_window, +n_windows) without bringing the norms back.  src: bytes / numpy array (host; pinned=True for a PinnedBuffer
         array) or a torch CUDA tensor (device, torch's current stream) holding source samples [src_first, ...)."""
         n_windows = self.n_windows - first_window if n_windows is None else n_windows
         s = Summary(self.width)
-        if _is_torch(src):
-            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
-        else:
-            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
-            count = buf.size // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
         check(lib().qd_plan_summarize(self._h, ptr, mem, src_first, count, first_window, n_windows, C.byref(s.c), _np_ptr(s.peak),
                                       _np_ptr(s.floor), st))
         return s
@@ -563,55 +585,13 @@ class Plan:
         """qd_plan_pool of an EPI_NORMS_F32 plan: (peak_rows, floor_rows), float32[ceil(n_windows / pool), width] each — per bin the max /
         min over each group of `pool` consecutive windows of [first_window, +n_windows).  src as for summarize.  device_out: the rows as
         torch CUDA tensors (the default for a torch src) instead of numpy arrays."""
-        n_windows = self.n_windows - first_window if n_windows is None else n_windows
-        rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
-        if _is_torch(src):
-            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
-        else:
-            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
-            count = buf.size // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
-        if _is_torch(src) if device_out is None else device_out:
-            import torch
-            peak, floor = (torch.empty((rows, self.width), dtype=torch.float32, device="cuda") for _ in range(2))
-            pp, fp, out_mem = C.c_void_p(peak.data_ptr()), C.c_void_p(floor.data_ptr()), MEM_DEVICE
-        else:
-            peak, floor = (np.empty((rows, self.width), dtype=np.float32) for _ in range(2))
-            pp, fp, out_mem = _np_ptr(peak), _np_ptr(floor), MEM_HOST
-        try:
-            check(lib().qd_plan_pool(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), pp, fp, out_mem, st))
-        except _ffi.QuadrsError as e:
-            e.partial = (peak, floor)            # QD_ERR_SHORT of a cascade: the complete windows are folded
-            raise
-        return peak, floor
+        return self._fold_rows(lib().qd_plan_pool, ("float32", "float32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
 
     def mean(self, src, pool, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None):
         """qd_plan_mean of an EPI_NORMS_F32 plan: (mean_rows float32, sum_rows float64, count_rows uint32), [ceil(n_windows / pool), width]
         each — per bin the exact sum of each group of `pool` consecutive windows of [first_window, +n_windows), rounded once, its mean
         rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch count_rows is int32: the same bits)."""
-        n_windows = self.n_windows - first_window if n_windows is None else n_windows
-        rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
-        if _is_torch(src):
-            count = src.numel() * src.element_size() // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = C.c_void_p(src.data_ptr()), MEM_DEVICE, _cur_stream()
-        else:
-            buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
-            count = buf.size // _FMT_BYTES[self.desc.format]
-            ptr, mem, st = _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), None
-        if _is_torch(src) if device_out is None else device_out:
-            import torch
-            out = tuple(torch.empty((rows, self.width), dtype=t, device="cuda") for t in (torch.float32, torch.float64, torch.int32))
-            ptrs, out_mem = [C.c_void_p(o.data_ptr()) for o in out], MEM_DEVICE
-        else:
-            out = tuple(np.empty((rows, self.width), dtype=t) for t in (np.float32, np.float64, np.uint32))
-            ptrs, out_mem = [_np_ptr(o) for o in out], MEM_HOST
-        try:
-            check(lib().qd_plan_mean(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), *ptrs, out_mem, st))
-        except _ffi.QuadrsError as e:
-            e.partial = out                      # QD_ERR_SHORT of a cascade: the complete windows are folded
-            raise
-        return out
+        return self._fold_rows(lib().qd_plan_mean, ("float32", "float64", "uint32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))

@@ -687,6 +687,23 @@ def test_host_path_many_chunks_equals_device_path(engine, fmt, lp, W, S):
     pin_in.close(); pin_out.close()
 
 
+def test_host_ring_refuses_a_slab_that_starts_late(engine, oracle, fsk):
+    """A slab whose first sample lies behind the first requested window's first sample is refused by the host ring, for a run and for
+    a fold alike, with nothing left in flight: the next, correct call on the same plan gives the reference."""
+    from quadrs_amd import _ffi
+    n, W, S = 40_000, 64, 16
+    data = fsk[:n * 8]
+    plan = engine.Plan(engine.FMT_CF32, 21_000_000, n, width=W, stride=S, chunk_bytes=1 << 16)
+    ref = oracle.Chain.from_bytes(data, oracle.FMT_CF32, 21_000_000).spark_fft(W, S, want_codes=False)[0]
+    assert ref.shape == (plan.n_windows, W) and plan.n_windows * S * 8 >= 3 * (1 << 16)       # at least three chunks
+    for call in (plan.run_host, plan.summarize):
+        with pytest.raises(engine.QuadrsError) as e:
+            call(data[8 * 8:], 0, plan.n_windows, src_first=8)
+        assert e.value.code == _ffi.ERR_INVALID, call
+    assert bits_equal(plan.run_host(data), ref)
+    assert plan.summarize(data).tobytes() == engine.summary_fold(ref).tobytes()
+
+
 @pytest.mark.parametrize("n_shards", [2, 4, 8])
 def test_sharded_runs_equal_single_device_run(engine, n_shards):
     """Multi-GPU behind the C ABI (qd_plan_run_sharded / _sharded_device): G logical shards, all mapped onto device 0 on a

@@ -162,6 +162,21 @@ def test_refusals(engine, fsk, cupboard):
     assert s.tobytes() == engine.summary_init(64).tobytes()
 
 
+def test_folds_leave_the_run_statistics_alone(engine, fsk):
+    """qd_plan_get_stats describes the last qd_plan_run: the folds walk the same host ring and keep no statistics of their own"""
+    n = 40_000
+    data = fsk[:n * 8]
+    plan = engine.Plan(engine.FMT_CF32, 21_000_000, n, width=64, stride=16, chunk_bytes=1 << 16)
+    plan.run_host(data)
+    fields = [f for f, _ in type(plan.stats())._fields_]
+    before = [getattr(plan.stats(), f) for f in fields]
+    assert plan.stats().chunks >= 3 and plan.stats().bytes_h2d > 0 and plan.stats().wall_ms > 0
+    plan.summarize(data)
+    plan.pool(data, 3)
+    plan.mean(data, 3)
+    assert [getattr(plan.stats(), f) for f in fields] == before
+
+
 def test_footprint(engine, world):
     from quadrs_amd import _ffi
     plan, data, dev, ref_of, _ = world("cf32_w64_s16")
