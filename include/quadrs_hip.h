@@ -480,6 +480,64 @@ int qd_plan_mean(qd_plan *plan, const void *src, int src_mem, uint64_t src_first
                  uint64_t first_window, uint64_t n_windows, uint64_t pool,
                  float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ percentile traces and persistence counts of a norms plan
+ *
+ * The trace the average cannot be: a noise floor that one burst, or one +inf, does not drag up — a median, or any percentile, per bin —
+ * and the analyser's persistence display, how often bin b sat at level l.  Over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width
+ * W and R = ceil(n / pool) rows grouped exactly as qd_plan_pool groups them (ragged last row; pool > n acts as pool = n), the values are
+ * counted on the summary's bucket scale, cut to a window of `levels` = L buckets that starts at bucket level0:
+ *   bits  = bits(x) & 0x7fffffff          the sign bit is dropped; bits > 0x7f800000 is a NaN and is ignored
+ *   k     = bits >> 20                    0 ... 2040, 8 buckets per octave, +inf in 2040: qd_summary.hist's scale, so
+ *                                         qd_summary_quantile tells which level0 and L to pass
+ *   level = min(max(k, level0) - level0, L - 1)
+ * Level 0 holds everything at or below the grid's bottom bucket, level L-1 everything at or above its top bucket, +inf included.
+ * 1 <= L <= 256 and level0 + L <= 2041.
+ *   count_rows[(r W + b) L + l]  u32  the number of the row's non-NaN values of fftshifted bin b at level l, of exactly the f32 values the
+ *                                     norms sink writes.  The row's NaN count for a bin is its windows minus the sum over l.
+ * A group holds at most 2^31 windows.  Every cell is an integer count: the result depends on no batch, chunk, memory kind, launch or
+ * arrival order, and parts merge by addition.
+ *
+ * Quantile of a cell (qd_summary_quantile's rule, per cell): N = sum over l of count, r = max(1, ceil(q N)) with the product and the ceil
+ * in f64, j the first level whose cumulative count reaches r.  The r-th smallest non-NaN value lies in [lo_j, hi_j):
+ *   lo_0 = 0.0, lo_j = the f32 of bits (level0 + j) << 20 for j > 0;  hi_j = the f32 of bits (level0 + j + 1) << 20 for j < L-1, hi_{L-1} = +inf
+ * An empty cell (N = 0) gives the quiet NaN 0x7fc00000 for both bounds. */
+
+/* A call's counts workspace (host outputs, or no count_rows) is at most this many bytes; above it qd_plan_density is QD_ERR_UNSUPPORTED. */
+#define QD_DENSITY_MAX_WORKSPACE (1ull << 30)
+
+/* All words 0: `rows` rows of `width` bins of `levels` counts.  QD_ERR_INVALID: counts NULL, width == 0 or levels == 0. */
+int qd_density_init(uint32_t *counts, uint32_t width, uint32_t levels, uint64_t rows);
+/* The CPU twin of the kernel behind qd_plan_density, bit for bit: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32 in
+ * `norms`) ACCUMULATE into rows (at + i) / pool of counts, which holds the range's rows from row 0 on.  Parts of a range folded in any
+ * order give the same words.  QD_ERR_INVALID: NULL arguments (norms with n > 0), width, pool or levels of 0, a grid outside the limits,
+ * or a row whose cells would hold more than 2^31 values (checked once per row before anything is added, counting every window of the
+ * call for the row: counts is then unchanged). */
+int qd_density_fold(uint32_t *counts, uint32_t width, uint32_t level0, uint32_t levels, uint64_t pool, uint64_t at,
+                    const float *norms, uint64_t n);
+/* dst += src, word by word.  QD_ERR_INVALID: NULL, width == 0, levels == 0, or a cell's total would pass 2^31 (dst is then unchanged). */
+int qd_density_merge(uint32_t *dst, const uint32_t *src, uint32_t width, uint32_t levels, uint64_t rows);
+/* Host arithmetic: per cell the bounds of the q-quantile's level and N, rows * width values each; any output may be NULL, not all.
+ * QD_ERR_INVALID: counts NULL, width == 0, a grid outside the limits, all outputs NULL, q outside [0, 1] or NaN. */
+int qd_density_quantile(const uint32_t *counts, uint32_t width, uint32_t level0, uint32_t levels, uint64_t rows, double q,
+                        float *lo_rows, float *hi_rows, uint32_t *n_rows);
+/* The level counts of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan, and the percentile traces read off them; src,
+ * src_mem, src_first, src_count and `stream` as for qd_plan_run (device, host and pinned sources).  count_rows is R W L u32 and may be
+ * NULL.  trace_rows is n_q R W f32, trace i at i R W: the lo bound of the level of the q[i]-quantile of each cell (q = 0.5: the median
+ * trace); n_q <= 8, and trace_rows may be NULL when n_q == 0; not both outputs.  The outputs are of out_mem memory (host, pinned or
+ * device), are OVERWRITTEN, and the call returns after they are complete.  The windows go batch by batch through the plan's own kernel
+ * into a device carrier of at most max(chunk_bytes, one tile of windows) of norms and are counted there into an accumulator of R W L
+ * words: count_rows itself when out_mem is device memory and count_rows is given, else a workspace that is copied down once and may
+ * not exceed QD_DENSITY_MAX_WORKSPACE (1 GiB) — QD_ERR_UNSUPPORTED, and the caller walks the range in spans of rows.
+ * Other codes as qd_plan_pool: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, pool == 0, pool (clamped to n_windows)
+ * above 2^31, a grid outside the limits, n_q > 8, a q outside [0, 1] or NaN, no output or an unknown memory kind; QD_ERR_SHORT past the
+ * sink's loop (the outputs are not touched), and for a cascade's range past qd_plan_complete_windows (every complete window of the
+ * range is counted; rows without one hold counts 0 and a NaN trace); QD_ERR_UNSUPPORTED for a plan created with shards (give each
+ * device a contiguous range of ROWS on a plan of its own, or qd_density_merge per-shard counts).  n_windows == 0: QD_OK, nothing is
+ * touched. */
+int qd_plan_density(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                    uint64_t first_window, uint64_t n_windows, uint64_t pool, uint32_t level0, uint32_t levels,
+                    uint32_t *count_rows, const double *q, uint32_t n_q, float *trace_rows, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_QUANTILES };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -109,6 +109,7 @@ struct Op {
     bool has_scan = false; double scan = 0.0;                           // marks -scan SCALE (bits::scan, src/bits.rs)
     bool overwrite = false; std::string prefix;                         // write
     uint64_t pool = 0; bool has_count = false, want_floor = false;      // peaks (-pool P | -count R, count below)
+    std::vector<double> qs; std::vector<std::string> q_names;         // quantiles -q 0.5[,0.9,...]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
 };
 
@@ -280,6 +281,46 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             }
             ensure_empty(m);
             op.prefix = next(op.kind == OP_PEAKS ? "'peaks' requires a prefix argument" : "'means' requires a prefix argument");
+        } else if (cmd == "quantiles") {
+            // not in the reference's grammar: the percentile traces of the windows sparkfft would print — per bin of each group of `pool`
+            // consecutive windows the level that holds the group's q-quantile (qd_plan_density), one picture per q
+            auto m = no_duplicates(raw);
+            op.kind = OP_QUANTILES;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            v = take(m, "pool", &f);
+            if (f) { op.pool = parse_si_u64(v); if (!op.pool) bail("quantiles -pool takes a number of windows > 0"); }
+            v = take(m, "count", &f);
+            op.has_count = f;
+            op.count = f ? (size_t)parse_si_u64(v) : 2048;
+            if (op.has_count && op.pool) bail("quantiles takes -pool or -count, not both");
+            if (!op.count) bail("quantiles -count takes a number of rows > 0");
+            v = take(m, "q", &f);
+            if (!f) bail("quantiles requires -q");
+            for (size_t a = 0; a <= v.size();) {
+                size_t c = v.find(',', a);
+                if (c == std::string::npos) c = v.size();
+                const std::string tok = v.substr(a, c - a);
+                char *end = nullptr;
+                const double q = strtod(tok.c_str(), &end);
+                if (tok.empty() || *end || !(q >= 0.0 && q <= 1.0)) bail("quantiles -q takes numbers in [0, 1] separated by commas: '" + v + "'");
+                op.qs.push_back(q); op.q_names.push_back(tok);
+                a = c + 1;
+            }
+            if (op.qs.size() > 8) bail("quantiles -q takes at most 8 quantiles");
+            v = take(m, "range", &f);
+            if (!f) bail("quantiles requires -range");
+            {
+                size_t c = v.find(':');
+                if (c == std::string::npos) bail("range argument must contain a ':': '" + v + "'");
+                op.has_range = true;
+                op.rmin = strtof(v.substr(0, c).c_str(), nullptr);
+                op.rmax = strtof(v.substr(c + 1).c_str(), nullptr);
+            }
+            ensure_empty(m);
+            op.prefix = next("'quantiles' requires a prefix argument");
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
             auto m = no_duplicates(raw);
@@ -1023,6 +1064,98 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     }
 }
 
+// The `quantiles` sink: the percentile traces of the windows sparkfft would print (a cascade's complete windows), one picture per -q,
+// PREFIX.sr{rate}.w{W}x{rows}.q{Q}.pgm: row r holds, per bin, the lower bound of the level that holds the q-quantile of the norms of windows
+// [r pool, (r+1) pool) — q 0.5: the median trace.  The level grid comes from the required -range MIN:MAX: it starts at MIN's bucket of the
+// summary's scale (bits >> 20, 8 per octave) and has min(256, MAX's bucket - MIN's bucket + 1) levels; pixels are (v - MIN) / (MAX - MIN) *
+// 256 as u8, as `peaks -range`.  A chain the library fuses counts on the device (qd_plan_density on a norms plan; with -gpus N the ROWS are
+// split into contiguous ranges, one plan each, each range in spans of rows whose counts fit the library's workspace); every other chain
+// pulls its windows through the iterator chain, counts their norms with qd_density_fold and reads them with qd_density_quantile — the
+// same bytes either way.
+uint32_t level_bucket(float x) { uint32_t b; memcpy(&b, &x, 4); return (b & 0x7fffffffu) >> 20; }
+
+void do_quantiles(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    if (!(sink.rmin >= 0.f) || !(sink.rmax > sink.rmin)) bail("quantiles -range takes lo:hi with 0 <= lo < hi");
+    const uint32_t level0 = level_bucket(sink.rmin), L = std::min<uint32_t>(256, level_bucket(sink.rmax) - level0 + 1);
+    const size_t nq = sink.qs.size();
+    uint64_t windows = 0, pool = 1, rows = 0;
+    std::vector<float> traces;                    // nq x rows x W
+    auto size_for = [&](uint64_t n) {
+        windows = n;
+        pool = sink.pool ? sink.pool : std::max<uint64_t>(1, (n + sink.count - 1) / sink.count);
+        if (n && pool > n) pool = n;
+        rows = n ? (n - 1) / pool + 1 : 0;
+        traces.resize(nq * rows * W);
+    };
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+        uint64_t rows_per = 0;
+        done = norms_fused(*cs, sink, "density", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
+            if (g == 0) {
+                size_for(complete);
+                uint64_t a = tile, b = pool;
+                while (b) { const uint64_t t = a % b; a = b; b = t; }
+                const uint64_t q = tile / a;
+                rows_per = ((rows + parts - 1) / parts + q - 1) / q * q;
+            }
+            const uint64_t r0 = std::min<uint64_t>(rows, rows_per * g), r1 = std::min<uint64_t>(rows, rows_per * (g + 1));
+            if (r1 <= r0) return (int)QD_OK;
+            int mem = QD_MEM_HOST;
+            const void *src = in.resident(&mem);
+            const uint64_t span = std::max<uint64_t>(1, QD_DENSITY_MAX_WORKSPACE / 4 / L / W);     // rows whose counts fit the workspace
+            std::vector<float> part;
+            for (uint64_t ra = r0; ra < r1; ra += span) {
+                const uint64_t rb = std::min(r1, ra + span), w0 = ra * pool, w1 = std::min<uint64_t>(windows, rb * pool);
+                part.resize(nq * (rb - ra) * W);
+                const int rc = qd_plan_density(plan, src, mem, 0, in.n_samples, w0, w1 - w0, pool, level0, L, nullptr, sink.qs.data(), (uint32_t)nq,
+                                               part.data(), QD_MEM_HOST, nullptr);
+                if (rc) return rc;
+                for (size_t i = 0; i < nq; ++i)
+                    memcpy(traces.data() + (i * rows + ra) * W, part.data() + i * (rb - ra) * W, (rb - ra) * W * sizeof(float));
+            }
+            return (int)QD_OK;
+        });
+    }
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+        uint64_t nwin = spark_windows(s, W, S);
+        std::vector<qd_c32> buf(W);
+        while (nwin) {
+            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+        }
+        size_for(nwin);
+        if (rows) {
+            std::vector<uint32_t> counts(rows * W * L);
+            qd_check(qd_density_init(counts.data(), (uint32_t)W, L, rows), "density init");
+            std::vector<float> norms;
+            for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+                const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
+                qd_check(qd_density_fold(counts.data(), (uint32_t)W, level0, L, pool, w0, norms.data(), nb), "fold");
+            }
+            for (size_t i = 0; i < nq; ++i)
+                qd_check(qd_density_quantile(counts.data(), (uint32_t)W, level0, L, rows, sink.qs[i], traces.data() + i * rows * W, nullptr, nullptr), "quantile");
+        }
+    }
+    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "x" + std::to_string(rows);
+    const std::string head = "P5\n" + std::to_string(W) + " " + std::to_string(rows) + "\n255\n";
+    const float lo = sink.rmin, span = sink.rmax - sink.rmin;
+    std::vector<uint8_t> px(rows * W);
+    for (size_t i = 0; i < nq; ++i) {
+        const std::string fn = stem + ".q" + sink.q_names[i] + ".pgm";
+        int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
+        const float *t = traces.data() + i * rows * W;
+        for (size_t k = 0; k < px.size(); ++k) {
+            const float v = (t[k] - lo) / span * 256.f;                  // `as u8`: saturating, NaN -> 0
+            px[k] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
+        }
+        if (write(fd, head.data(), head.size()) < 0 || (px.size() && write(fd, px.data(), px.size()) < 0)) { close(fd); bail("write failed"); }
+        close(fd);
+    }
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -1035,6 +1168,7 @@ void usage() {
             "  levels [-width 128] [-stride =width] \\\n"
             "   peaks [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] [-floor no] FILENAME_PREFIX \\\n"
             "   means [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
+            "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -1079,6 +1213,13 @@ int main(int argc, char **argv) {
                     printf("means width=%zu stride=%llu %s=%llu range=%s\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
                            (unsigned long long)(op.pool ? op.pool : op.count), op.has_range ? "yes" : "no");
                     break;
+                case OP_QUANTILES: {
+                    std::string qs;
+                    for (const std::string &q : op.q_names) qs += (qs.empty() ? "" : ",") + q;
+                    printf("quantiles width=%zu stride=%llu %s=%llu q=%s range=%.9g:%.9g\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
+                           (unsigned long long)(op.pool ? op.pool : op.count), qs.c_str(), op.rmin, op.rmax);
+                    break;
+                }
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 case OP_ROWS:
                     printf("rows width=%zu count=%zu slice=%s window=%s\n", op.width, op.count,
@@ -1142,6 +1283,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("peaks requires an input");
                 cs.cascade = !chain_clean;
                 do_peaks(*samples, op, &cs);
+                break;
+            case OP_QUANTILES:
+                if (!samples) bail("quantiles requires an input");
+                cs.cascade = !chain_clean;
+                do_quantiles(*samples, op, &cs);
                 break;
             case OP_ROWS:
                 if (!samples) bail("rows requires an input");

@@ -33,6 +33,7 @@
 #include "qd_registry.h"
 #include "qd_summary.h"
 #include "qd_pool.h"
+#include "qd_density.h"
 #include "qd_mean.h"
 
 using namespace qd;
@@ -3236,7 +3237,7 @@ int launch_summary(const qd_plan *p, const float *norms_d, uint64_t n_rows, SumA
     return QD_OK;
 }
 
-// The driver of the folds of a norms plan's windows (qd_plan_summarize, qd_plan_pool, qd_plan_mean).  An entry point
+// The driver of the folds of a norms plan's windows (qd_plan_summarize, qd_plan_pool, qd_plan_mean, qd_plan_density).  An entry point
 // calls its steps in this order, with its own argument checks where they have always stood:
 //   norms_plan, unsharded, admit    the refusals every fold shares, and the cascade short-read clamp (n_windows is the complete part after it)
 //   open                            plan mutex, device, workspace lease: from here the sink lays out and initialises its accumulators ("begin")
@@ -3715,6 +3716,171 @@ int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
         if (mean_rows) HIPCHK(hipMemcpyAsync(mean_rows, out.mean, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
         if (sum_rows) HIPCHK(hipMemcpyAsync(sum_rows, out.sum, (size_t)(words * 8), hipMemcpyDeviceToHost, st));
         if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, out.count, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+    }
+    return f.close(rc);
+}
+
+// ------------------------------------------------------------------ percentile traces and persistence counts
+
+namespace {
+int density_grid(uint32_t level0, uint32_t levels) {
+    if (levels == 0 || levels > kDensityMaxLevels || level0 > kDensityBuckets || level0 + levels > kDensityBuckets)
+        return fail(QD_ERR_INVALID, "a level grid of %u levels from bucket %u: 1 <= levels <= 256 and level0 + levels <= 2041", levels, level0);
+    return QD_OK;
+}
+int density_q(double q) { return q >= 0.0 && q <= 1.0 ? QD_OK : fail(QD_ERR_INVALID, "quantile %g outside [0, 1]", q); }
+
+// one batch of norms rows (device memory) — windows [g0, g0 + nw) of a range of n_total — into the R x W x L counts, on `st`
+int launch_density(const qd_plan *p, const float *norms_d, uint64_t g0, uint64_t nw, uint64_t n_total, uint64_t pool, uint32_t level0, uint32_t levels,
+                   uint32_t *counts_d, hipStream_t st) {
+    if (nw == 0) return QD_OK;
+    DensityParams D{};
+    uint64_t grid = 0;
+    density_geometry(g0, nw, n_total, pool, p->W, levels, p->n_cu, &D, &grid);
+    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)nw);
+    D.G.norms = norms_d; D.counts = counts_d; D.level0 = level0;
+    hipLaunchKernelGGL(k_density, dim3((uint32_t)grid), dim3(kDensityThreads), 0, st, D);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+}  // namespace
+
+int qd_density_init(uint32_t *counts, uint32_t width, uint32_t levels, uint64_t rows) {
+    if (!counts) return fail(QD_ERR_INVALID, "counts is NULL");
+    if (width == 0 || levels == 0) return fail(QD_ERR_INVALID, "rows of width 0 or of 0 levels hold nothing");
+    memset(counts, 0, (size_t)(rows * width * levels * 4));
+    return QD_OK;
+}
+
+int qd_density_fold(uint32_t *counts, uint32_t width, uint32_t level0, uint32_t levels, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (const int rc = density_grid(level0, levels)) return rc;
+    if (!counts) return fail(QD_ERR_INVALID, "counts is NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    // once per row, before anything is added: the row's cells take at most its windows of this call on top of what they hold
+    for (uint64_t r = at / pool; r <= (at + n - 1) / pool; ++r) {
+        const uint64_t a = std::max(at, r * pool), b = std::min(at + n, (r + 1) * pool);
+        for (uint32_t c = 0; c < width; ++c) {
+            const uint32_t *cell = counts + (r * width + c) * levels;
+            uint64_t N = 0;
+            for (uint32_t l = 0; l < levels; ++l) N += cell[l];
+            if (N + (b - a) > kDensityMaxCount) return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)r);
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        uint32_t *cells = counts + (at + i) / pool * width * levels;
+        for (uint32_t b = 0; b < width; ++b) {
+            uint32_t bits;
+            memcpy(&bits, row + b, 4);
+            const uint32_t lv = density_level(bits, level0, levels);
+            if (lv < levels) cells[(uint64_t)b * levels + lv] += 1;
+        }
+    }
+    return QD_OK;
+}
+
+int qd_density_merge(uint32_t *dst, const uint32_t *src, uint32_t width, uint32_t levels, uint64_t rows) {
+    if (!dst || !src) return fail(QD_ERR_INVALID, "counts is NULL");
+    if (width == 0 || levels == 0) return fail(QD_ERR_INVALID, "rows of width 0 or of 0 levels hold nothing");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c) {
+        uint64_t N = 0;
+        for (uint32_t l = 0; l < levels; ++l) N += (uint64_t)dst[c * levels + l] + src[c * levels + l];
+        if (N > kDensityMaxCount) return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
+    }
+    for (uint64_t i = 0; i < cells * levels; ++i) dst[i] += src[i];
+    return QD_OK;
+}
+
+int qd_density_quantile(const uint32_t *counts, uint32_t width, uint32_t level0, uint32_t levels, uint64_t rows, double q, float *lo_rows,
+                        float *hi_rows, uint32_t *n_rows) {
+    if (!counts) return fail(QD_ERR_INVALID, "counts is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (const int rc = density_grid(level0, levels)) return rc;
+    if (const int rc = density_q(q)) return rc;
+    if (!lo_rows && !hi_rows && !n_rows) return fail(QD_ERR_INVALID, "lo_rows, hi_rows and n_rows are all NULL");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c) {
+        const uint32_t *cell = counts + c * levels;
+        uint64_t N = 0;
+        for (uint32_t l = 0; l < levels; ++l) N += cell[l];
+        uint32_t lo = kDensityNanBits, hi = kDensityNanBits;
+        if (N) {
+            const uint32_t j = density_quantile_level(cell, 1, levels, N, q);
+            lo = density_lo_bits(level0, j); hi = density_hi_bits(level0, levels, j);
+        }
+        if (lo_rows) memcpy(lo_rows + c, &lo, 4);
+        if (hi_rows) memcpy(hi_rows + c, &hi, 4);
+        if (n_rows) n_rows[c] = (uint32_t)N;
+    }
+    return QD_OK;
+}
+
+int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                    uint64_t pool, uint32_t level0, uint32_t levels, uint32_t *count_rows, const double *q, uint32_t n_q, float *trace_rows,
+                    int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_density", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = density_grid(level0, levels)) return rc;
+    if (n_q > (uint32_t)kDensityMaxQ) return fail(QD_ERR_INVALID, "%u quantiles: a call takes at most %d", n_q, kDensityMaxQ);
+    if (n_q && !q) return fail(QD_ERR_INVALID, "q is NULL");
+    DensityQ Q{};
+    for (uint32_t i = 0; i < n_q; ++i) {
+        if (const int rc = density_q(q[i])) return rc;
+        Q.q[i] = q[i];
+    }
+    if (n_q && !trace_rows) return fail(QD_ERR_INVALID, "trace_rows is NULL with %u quantiles asked", n_q);
+    if (!count_rows && !n_q) return fail(QD_ERR_INVALID, "both count_rows and trace_rows are NULL");
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not counted in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard counts (qd_density_merge)")) return rc;
+    if (const int rc = f.admit()) return rc;
+    if (n_windows == 0) return QD_OK;
+    if (pool > n_windows) pool = n_windows;                          // one row either way
+    if (pool > kDensityMaxCount) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)pool);
+    const uint32_t W = p->W;
+    const uint64_t R = (n_windows - 1) / pool + 1, cells = R * W;    // rows of the range as asked; f.n_windows is its complete part
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    const bool own_acc = !(out_dev && count_rows);
+    if (own_acc && (cells > kDensityMaxWorkspace / 4 / levels))
+        return fail(QD_ERR_UNSUPPORTED, "%llu rows x %u bins x %u levels of counts need a workspace of %llu bytes, above the %llu allowed: walk the range in spans of rows",
+                    (unsigned long long)R, W, levels, (unsigned long long)(cells * levels * 4), (unsigned long long)kDensityMaxWorkspace);
+    const uint64_t words = cells * levels;
+    if (const int rc = f.open()) return rc;
+    const hipStream_t st = f.st;
+    // the accumulator: the caller's counts when they are device memory, else a workspace; the traces likewise
+    uint32_t *acc = count_rows;
+    if (own_acc) {
+        void *a = nullptr;
+        if (const int rc = f.ws->get(1, (size_t)(words * 4), &a)) return rc;
+        acc = static_cast<uint32_t *>(a);
+    }
+    uint32_t *trace_d = reinterpret_cast<uint32_t *>(trace_rows);
+    if (n_q && !out_dev) {
+        void *t = nullptr;
+        if (const int rc = f.ws->get(2, (size_t)(cells * n_q * 4), &t)) return rc;
+        trace_d = static_cast<uint32_t *>(t);
+    }
+    HIPCHK(hipMemsetAsync(acc, 0, (size_t)(words * 4), st));
+    int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+        return launch_density(p, norms_d, g0, nw, f.n_windows, pool, level0, levels, acc, s);
+    });
+    if (rc == QD_OK && n_q) {
+        const uint64_t grid = (cells + kDensityThreads - 1) / kDensityThreads;
+        if (grid > 0x7fffffffull) rc = fail(QD_ERR_INVALID, "%llu cells are too many for one launch: walk the range in spans of rows", (unsigned long long)cells);
+        else {
+            hipLaunchKernelGGL(k_density_quantile, dim3((uint32_t)grid), dim3(kDensityThreads), 0, st, acc, cells, level0, levels, Q, n_q, trace_d);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (rc == QD_OK && !out_dev) {
+        if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, acc, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
+        if (n_q) HIPCHK(hipMemcpyAsync(trace_rows, trace_d, (size_t)(cells * n_q * 4), hipMemcpyDeviceToHost, st));
     }
     return f.close(rc);
 }

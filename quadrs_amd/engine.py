@@ -365,6 +365,43 @@ def mean_finish(acc):
     return mean, total, count
 
 
+def density_init(width, levels, rows):
+    """qd_density_init: the level counts of `rows` rows of `width` bins, uint32[rows, width, levels], all words 0."""
+    counts = np.empty((int(rows), int(width), int(levels)), dtype=np.uint32)
+    check(lib().qd_density_init(_np_ptr(counts), int(width), int(levels), int(rows)))
+    return counts
+
+
+def density_fold(norms, pool, level0, levels, at=0, into=None):
+    """qd_density_fold: norms rows (n, width) are windows at, at+1, ... of a range and are counted into rows (at + i) // pool of the
+    counts `into`, or of new ones of ceil((at + n) / pool) rows.  Returns the counts."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = density_init(width, levels, -(-(int(at) + n) // int(pool)) if pool else 0)
+    check(lib().qd_density_fold(_np_ptr(into), width, int(level0), int(levels), int(pool), int(at), _np_ptr(a), n))
+    return into
+
+
+def density_merge(dst, src):
+    """qd_density_merge: dst += src word by word (two count arrays of the same rows, width and levels).  Returns dst."""
+    if dst.shape != src.shape:
+        raise ValueError("counts of different shapes do not merge")
+    check(lib().qd_density_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint32)), dst.shape[1], dst.shape[2], dst.shape[0]))
+    return dst
+
+
+def density_quantile(counts, level0, q):
+    """qd_density_quantile: (lo float32, hi float32, n uint32), [rows, width] each — per cell the bounds of the level that holds the
+    q-quantile of its values, and how many values it holds."""
+    rows, width, levels = counts.shape
+    lo = np.empty((rows, width), dtype=np.float32)
+    hi = np.empty((rows, width), dtype=np.float32)
+    n = np.empty((rows, width), dtype=np.uint32)
+    check(lib().qd_density_quantile(_np_ptr(counts), width, int(level0), levels, rows, float(q), _np_ptr(lo), _np_ptr(hi), _np_ptr(n)))
+    return lo, hi, n
+
+
 class Plan:
     """The fused chain  from -> [shift] -> [lowpass] -> sparkfft|bucket  (Operation::exec, src/lib.rs:83-175); with
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
@@ -550,18 +587,20 @@ class Plan:
         buf = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
         return _np_ptr(buf), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), buf.size // _FMT_BYTES[self.desc.format], None, buf
 
-    def _fold_rows(self, call, dtypes, src, pool, first_window, n_windows, src_first, pinned, device_out):
-        """one [ceil(n_windows / pool), width] array per dtype, filled by `call` (qd_plan_pool, qd_plan_mean): torch CUDA tensors (the default
-        for a torch src; uint32 as int32, the same bits) or numpy arrays.  A failing call's error carries them as e.partial."""
+    def _fold_rows(self, call, dtypes, src, pool, first_window, n_windows, src_first, pinned, device_out, shapes=None):
+        """one [ceil(n_windows / pool), width] array per dtype, filled by `call` (qd_plan_pool, qd_plan_mean, qd_plan_density): torch CUDA
+        tensors (the default for a torch src; uint32 as int32, the same bits) or numpy arrays.  shapes(rows): the arrays' shapes where they
+        are not [rows, width].  A failing call's error carries them as e.partial."""
         n_windows = self.n_windows - first_window if n_windows is None else n_windows
         rows = -(-n_windows // min(int(pool), n_windows)) if pool and n_windows else 0
         ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        shape = shapes(rows) if shapes else [(rows, self.width)] * len(dtypes)
         if _is_torch(src) if device_out is None else device_out:
             import torch
-            out = tuple(torch.empty((rows, self.width), dtype=getattr(torch, t.replace("uint32", "int32")), device="cuda") for t in dtypes)
+            out = tuple(torch.empty(sh, dtype=getattr(torch, t.replace("uint32", "int32")), device="cuda") for t, sh in zip(dtypes, shape))
             ptrs, out_mem = [C.c_void_p(o.data_ptr()) for o in out], MEM_DEVICE
         else:
-            out = tuple(np.empty((rows, self.width), dtype=t) for t in dtypes)
+            out = tuple(np.empty(sh, dtype=t) for t, sh in zip(dtypes, shape))
             ptrs, out_mem = [_np_ptr(o) for o in out], MEM_HOST
         try:
             check(call(self._h, ptr, mem, src_first, count, first_window, n_windows, int(pool), *ptrs, out_mem, st))
@@ -592,6 +631,26 @@ class Plan:
         each — per bin the exact sum of each group of `pool` consecutive windows of [first_window, +n_windows), rounded once, its mean
         rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch count_rows is int32: the same bits)."""
         return self._fold_rows(lib().qd_plan_mean, ("float32", "float64", "uint32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
+
+    def density(self, src, pool, level0, levels, q=(), first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, counts=True):
+        """qd_plan_density of an EPI_NORMS_F32 plan: (count_rows uint32[R, width, levels], trace_rows float32[len(q), R, width]),
+        R = ceil(n_windows / pool) — per bin of each group of `pool` consecutive windows of [first_window, +n_windows) the number of values
+        at each of `levels` buckets of the summary's scale from bucket level0 on, and per q the lower bound of the level that holds the
+        group's q-quantile (q = 0.5: the median trace).  counts=False: only the traces (count_rows is None).  src and device_out as for
+        pool (a torch count_rows is int32: the same bits)."""
+        qs = [float(x) for x in q]
+        qa = (C.c_double * max(len(qs), 1))(*qs)
+        W, L = self.width, int(levels)
+
+        def call(h, ptr, mem, src_first, count, first_window, n_windows, pool, *rest):
+            ptrs, (out_mem, st) = rest[:-2], rest[-2:]
+            cptr, tptr = (ptrs[0], ptrs[1]) if counts else (None, ptrs[0])
+            return lib().qd_plan_density(h, ptr, mem, src_first, count, first_window, n_windows, pool, int(level0), L, cptr, qa, len(qs),
+                                         tptr if qs else None, out_mem, st)
+        shapes = lambda rows: ([(rows, W, L)] if counts else []) + [(len(qs), rows, W)]      # noqa: E731
+        out = self._fold_rows(call, (("uint32",) if counts else ()) + ("float32",), src, pool, first_window, n_windows, src_first, pinned,
+                              device_out, shapes)
+        return out if counts else (None, out[0])
 
     def set_timing(self, on=True):
         check(lib().qd_plan_set_timing(self._h, 1 if on else 0))
