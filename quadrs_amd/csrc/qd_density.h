@@ -17,7 +17,7 @@
 #define QD_DENSITY_HD
 #endif
 
-#include "qd_pool.h"
+#include "qd_pieces.h"
 
 namespace qd {
 
@@ -57,8 +57,7 @@ constexpr uint64_t kDensityMinSeg = 128;         // a row is not split into piec
 constexpr int kDensityGroupsPerCu = 4;           // workgroups per compute unit a launch aims for before it stops splitting rows
 constexpr int kDensityInFlight = 8;              // windows in flight per lane
 
-// Geometry of a launch over one batch, in k_pool's terms (qd_pool.h: PoolParams; pieces, their numbering q = r spr + k and the split of
-// few rows over workgroups are the same question with the same answer), except where L decides:
+// Geometry of a launch over one batch: the pooled folds' pieces (qd_pieces.h), with a column layout that L decides:
 //   columns  a workgroup's histogram is hist[level][column], level-major, ncol columns wide: ncol is the largest power of two with
 //            ncol L <= 16384 words, at most 256 and at least 64 (L = 256: 64; L <= 64: 256).  Column c = slot cols + bin is bin `bin` of
 //            the slab for the workgroup's piece number `slot`: cols = min(W, ncol) bins a slab (n_slabs = W / cols slabs, a workgroup
@@ -72,57 +71,37 @@ constexpr int kDensityInFlight = 8;              // windows in flight per lane
 //   lanes    a lane owns one bin (one 4-byte load a window; the lanes of a wave read 64 consecutive f32).  ncol < 256 (L > 64): the
 //            nsub = 256 / ncol lanes t, t + ncol, ... share a column and take its piece's windows in turn (window wa + sub, step nsub);
 //            they are in different waves, so they meet only in the LDS adder.
-//   split    k_pool's rule with this kernel's figures: seg = pool while the batch's rows give kDensityGroupsPerCu workgroups per compute
-//            unit, else pieces of at least kDensityMinSeg windows — a piece pays up to L words of flush per column, so it is 8 times
-//            k_pool's shortest.
+//   split    piece_split with this kernel's figures: kDensityGroupsPerCu workgroups per compute unit and pieces of at least
+//            kDensityMinSeg windows — a piece pays up to L words of flush per column, so it is 8 times k_pool's shortest.
 //   flush    the lanes of the first piece of a row in the workgroup add up the row's pieces here, level by level (lane sub takes levels
-//            sub, sub + nsub, ...).  Whole row (all windows in this batch, all pieces in this workgroup — k_pool's predicate): the
+//            sub, sub + nsub, ...).  Whole row (all windows in this batch, all pieces in this workgroup: PieceLane::whole): the
 //            non-zero counts are stored; cut row: they are added with u32 atomicAdd.  The accumulator is zero from before the first
 //            batch, so zero counts are never written.
 struct DensityParams {
-    PoolParams G;                                // norms and the geometry; G.peak / G.floor / G.vec_store are not used
+    const float *norms;                          // the batch's windows, nw x W
+    PieceGeometry G;
     uint32_t *counts;                            // R x W x L words
     uint32_t level0, L, ncol, nsub;
 };
 
-// One lane's two halves of k_density, as functions of (workgroup, lane) over a memory policy M, so that a host program can walk every
-// lane of a launch with a policy that checks bounds and counts the reads and the stores.
-struct DensityLane {
-    uint32_t col, sub, slab, slot, bin;
-    bool active;
-    uint64_t wg_q0, r, row_a, row_b, wa, wb, end;
-};
-QD_DENSITY_HD inline DensityLane density_lane(const DensityParams &D, uint32_t block, uint32_t tid) {
-    const PoolParams &P = D.G;
-    DensityLane l;
-    l.col = tid % D.ncol; l.sub = tid / D.ncol;
-    l.slab = block % P.n_slabs;
-    const uint64_t grp0 = (uint64_t)(block / P.n_slabs) * P.pieces_per_group;          // the workgroup's first piece, within the batch
-    l.slot = l.col / P.cols; l.bin = l.col % P.cols;
-    l.active = grp0 + l.slot < P.n_pieces;
-    l.wg_q0 = P.q0 + grp0;
-    const uint64_t q = l.wg_q0 + l.slot;
-    l.r = q / P.spr;
-    const uint64_t k = q - l.r * P.spr;
-    l.row_a = l.r * P.pool; l.row_b = l.row_a + P.pool < P.n_total ? l.row_a + P.pool : P.n_total;
-    l.end = P.g0 + P.nw;
-    uint64_t wa = l.row_a + k * P.seg, wb = wa + P.seg;
-    wa = wa > P.g0 ? wa : P.g0;
-    wb = wb < l.row_b ? wb : l.row_b;
-    wb = wb < l.end ? wb : l.end;
-    if (!l.active) wa = wb = P.g0;
-    l.wa = wa; l.wb = wb;
-    return l;
+// One lane's two halves of k_density, as functions of the lane's piece (PieceLane of its slot) and its own place over a memory policy M,
+// so that a host program can walk every lane of a launch with a policy that checks bounds and counts the reads and the stores.
+struct DensityLane { uint32_t col, sub, slot, bin; };
+QD_DENSITY_HD inline DensityLane density_lane(const DensityParams &D, uint32_t tid) {
+    DensityLane d;
+    d.col = tid % D.ncol; d.sub = tid / D.ncol;
+    d.slot = d.col / D.G.cols; d.bin = d.col % D.G.cols;
+    return d;
 }
 
 template <class M>
-QD_DENSITY_HD inline void density_lane_fold(const DensityParams &D, const DensityLane &l, uint32_t *hist, M &mem) {
-    const PoolParams &P = D.G;
+QD_DENSITY_HD inline void density_lane_fold(const DensityParams &D, const PieceLane &l, const DensityLane &d, uint32_t *hist, M &mem) {
+    const PieceGeometry &P = D.G;
     constexpr int U = kDensityInFlight;
     const uint64_t step = (uint64_t)D.nsub * P.W;
-    const float *ptr = P.norms + (l.wa - P.g0 + l.sub) * P.W + (uint64_t)l.slab * P.cols + l.bin;
-    uint32_t *mine = hist + l.col;
-    for (uint64_t w = l.wa + l.sub; w < l.wb; w += (uint64_t)U * D.nsub, ptr += (uint64_t)U * step) {
+    const float *ptr = D.norms + (l.wa - P.g0 + d.sub) * P.W + (uint64_t)l.slab * P.cols + d.bin;
+    uint32_t *mine = hist + d.col;
+    for (uint64_t w = l.wa + d.sub; w < l.wb; w += (uint64_t)U * D.nsub, ptr += (uint64_t)U * step) {
         uint32_t v[U];
 #if defined(__HIPCC__)
 #pragma unroll
@@ -142,20 +121,14 @@ QD_DENSITY_HD inline void density_lane_fold(const DensityParams &D, const Densit
 }
 
 template <class M>
-QD_DENSITY_HD inline void density_lane_flush(const DensityParams &D, const DensityLane &l, const uint32_t *hist, M &mem) {
-    const PoolParams &P = D.G;
-    const uint64_t row_q0 = l.r * P.spr;
-    const uint32_t lead = row_q0 > l.wg_q0 ? (uint32_t)(row_q0 - l.wg_q0) : 0u;       // <= slot
-    if (!l.active || lead != l.slot) return;
-    // the row's pieces in this workgroup: slots lead ... lead + n_same - 1
-    uint64_t last = row_q0 + P.spr;
-    last = last < l.wg_q0 + P.pieces_per_group ? last : l.wg_q0 + P.pieces_per_group;
-    last = last < P.q0 + P.n_pieces ? last : P.q0 + P.n_pieces;
-    const uint32_t n_same = (uint32_t)(last - (l.wg_q0 + lead));
-    const bool whole = row_q0 >= l.wg_q0 && row_q0 + P.spr <= l.wg_q0 + P.pieces_per_group && l.row_a >= P.g0 && l.row_b <= l.end;
-    uint32_t *out = D.counts + (l.r * P.W + (uint64_t)l.slab * P.cols + l.bin) * D.L;
-    for (uint32_t lv = l.sub; lv < D.L; lv += D.nsub) {
-        const uint32_t *h = hist + lv * D.ncol + l.col;
+QD_DENSITY_HD inline void density_lane_flush(const DensityParams &D, const PieceLane &l, const DensityLane &d, const uint32_t *hist, M &mem) {
+    const PieceGeometry &P = D.G;
+    if (!l.active || l.lead != d.slot) return;
+    uint32_t *out = D.counts + (l.r * P.W + (uint64_t)l.slab * P.cols + d.bin) * D.L;
+    const uint32_t n_same = l.n_same(P);
+    const bool whole = l.whole(P);
+    for (uint32_t lv = d.sub; lv < D.L; lv += D.nsub) {
+        const uint32_t *h = hist + lv * D.ncol + d.col;
         uint32_t c = 0;
         for (uint32_t s = 0; s < n_same; ++s) c += h[s * P.cols];
         if (c == 0) continue;
@@ -165,31 +138,11 @@ QD_DENSITY_HD inline void density_lane_flush(const DensityParams &D, const Densi
 
 // the launch geometry for the batch [g0, g0 + nw) (nw >= 1, 1 <= pool, 1 <= L <= 256) on a device of n_cu compute units; *grid in workgroups
 inline void density_geometry(uint64_t g0, uint64_t nw, uint64_t n_total, uint64_t pool, uint32_t W, uint32_t L, int n_cu, DensityParams *D, uint64_t *grid) {
-    PoolParams *P = &D->G;
     uint32_t ncol = 64;
     while (ncol * 2 * L <= kDensityLdsWords && ncol * 2 <= (uint32_t)kDensityThreads) ncol *= 2;
     D->ncol = ncol; D->nsub = kDensityThreads / ncol; D->L = L;
-    P->g0 = g0; P->nw = nw; P->n_total = n_total; P->pool = pool; P->W = W;
-    P->cols = W < ncol ? W : ncol;
-    P->lanes_per_win = P->cols;
-    P->pieces_per_group = ncol / P->cols;
-    P->n_slabs = W / P->cols;
-    uint64_t want = (uint64_t)n_cu * kDensityGroupsPerCu * P->pieces_per_group / P->n_slabs;
-    if (want < 1) want = 1;
-    const uint64_t rows = nw / pool + 1;
-    uint64_t seg = pool;
-    if (rows < want) {
-        const uint64_t cuts = (want + rows - 1) / rows;
-        seg = (pool + cuts - 1) / cuts;
-        const uint64_t least = pool < kDensityMinSeg ? pool : kDensityMinSeg;
-        if (seg < least) seg = least;
-    }
-    P->seg = seg;
-    P->spr = (pool + seg - 1) / seg;
-    const uint64_t wl = g0 + nw - 1;
-    P->q0 = g0 / pool * P->spr + g0 % pool / seg;
-    P->n_pieces = wl / pool * P->spr + wl % pool / seg - P->q0 + 1;
-    *grid = (P->n_pieces + P->pieces_per_group - 1) / P->pieces_per_group * P->n_slabs;
+    const uint32_t cols = W < ncol ? W : ncol;
+    piece_split(g0, nw, n_total, pool, W, cols, cols, ncol / cols, kDensityMinSeg, kDensityGroupsPerCu, n_cu, &D->G, grid);
 }
 
 }  // namespace qd
@@ -210,10 +163,11 @@ __global__ __launch_bounds__(kDensityThreads) void k_density(const DensityParams
     for (uint32_t i = tid; i < D.ncol * D.L; i += kDensityThreads) s_hist[i] = 0;
     __syncthreads();
     DensityDeviceMem mem;
-    const DensityLane l = density_lane(D, blockIdx.x, tid);
-    density_lane_fold(D, l, s_hist, mem);
+    const DensityLane d = density_lane(D, tid);
+    const PieceLane l = piece_lane(D.G, blockIdx.x, d.slot);
+    density_lane_fold(D, l, d, s_hist, mem);
     __syncthreads();
-    density_lane_flush(D, l, s_hist, mem);
+    density_lane_flush(D, l, d, s_hist, mem);
 }
 
 struct DensityQ { double q[kDensityMaxQ]; };

@@ -140,11 +140,10 @@ QD_MEAN_HD inline void mean_finish_cell(const uint64_t *acc, uint32_t *mean_bits
 
 namespace qd {
 
-// k_mean runs on k_pool's geometry (pool_geometry, qd_pool.h: pieces, lanes, slabs and the split of few rows over workgroups are the
-// same question with the same answer) and reads the carrier once.  A lane owns V bins down a piece and adds each value into its own
-// nine limbs and count word, in registers.  Pieces of a workgroup that share a row meet in LDS, word by word (one u64 per bin: 8 KiB),
+// k_mean runs on k_pool's geometry (pool_geometry, qd_pool.h; the rule is qd_pieces.h) with k_pool's window walker (walk_piece) and reads
+// the carrier once.  A lane owns V bins down a piece and adds each value into its own nine limbs and count word, in registers.  Pieces of a workgroup that share a row meet in LDS, word by word (one u64 per bin: 8 KiB),
 // with u64 LDS adds into the slot of the first of them.  A row then ends in one of two ways:
-//   whole   all of the row's windows lie in this batch and all of its pieces in this workgroup (k_pool's predicate): the leader rounds
+//   whole   all of the row's windows lie in this batch and all of its pieces in this workgroup (PieceLane::whole): the leader rounds
 //           the cells and stores mean / sum / count; no global accumulator is touched.
 //   cut     every other row (cut by a batch seam, or split over workgroups because the rows are few): the leader adds its non-zero
 //           words with 64-bit global atomicAdd — one per word per workgroup — into the limb accumulator and raises the row's flag;
@@ -155,7 +154,8 @@ namespace qd {
 // pool whenever pool <= chunk windows, so rows of small pools are whole and need no accumulator; a batch that can cut rows is clipped to
 // the rows the accumulator holds, and when its rows pass the accumulator's end the span is finished, the accumulator zeroed and moved.
 struct MeanParams {
-    PoolParams G;                                // norms and the geometry; G.peak / G.floor are not used
+    const float *norms;                          // the batch's windows, nw x W
+    PieceGeometry G;
     float *mean; double *sum; uint32_t *count;   // R x W each; any may be nullptr
     unsigned long long *acc;                     // planar limbs, kMeanWords x cells
     uint32_t *flags;                             // acc_rows: the row went through the accumulator
@@ -165,22 +165,11 @@ struct MeanParams {
 template <int V>
 __global__ __launch_bounds__(kPoolThreads) void k_mean(const MeanParams M) {
     __shared__ unsigned long long s_meet[kPoolSlabCols];
-    const PoolParams &P = M.G;
+    const PieceGeometry &P = M.G;
     const uint32_t tid = threadIdx.x;
-    const uint32_t slab = blockIdx.x % P.n_slabs;
-    const uint64_t grp0 = (uint64_t)(blockIdx.x / P.n_slabs) * P.pieces_per_group;     // the workgroup's first piece, within the batch
     const uint32_t grp = tid / P.lanes_per_win;
     const uint32_t lcol = (tid % P.lanes_per_win) * V;                                 // the lane's first bin inside the slab
-    const bool active = grp0 + grp < P.n_pieces;
-    const uint64_t wg_q0 = P.q0 + grp0, q = wg_q0 + grp;
-    const uint64_t r = q / P.spr, k = q - r * P.spr;
-    const uint64_t row_a = r * P.pool, row_b = row_a + P.pool < P.n_total ? row_a + P.pool : P.n_total;
-    const uint64_t end = P.g0 + P.nw;
-    uint64_t wa = row_a + k * P.seg, wb = wa + P.seg;
-    wa = wa > P.g0 ? wa : P.g0;
-    wb = wb < row_b ? wb : row_b;
-    wb = wb < end ? wb : end;
-    if (!active) wa = wb = P.g0;
+    const PieceLane l = piece_lane(P, blockIdx.x, grp);
 
     uint64_t acc[V][kMeanWords];
 #pragma unroll
@@ -188,42 +177,18 @@ __global__ __launch_bounds__(kPoolThreads) void k_mean(const MeanParams M) {
 #pragma unroll
         for (int j = 0; j < kMeanWords; ++j) acc[i][j] = 0;
 
-    constexpr int U = 4;                                                // windows in flight per lane
-    const float *ptr = P.norms + (wa - P.g0) * P.W + (uint64_t)slab * P.cols + lcol;
-    for (uint64_t w = wa; w < wb; w += U, ptr += (uint64_t)U * P.W) {
-        uint32_t v[U][V];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (w + u < wb) {
-                if (V == 4) {
-                    const uint4 f = *reinterpret_cast<const uint4 *>(ptr + (uint64_t)u * P.W);
-                    v[u][0] = f.x; v[u][1 % V] = f.y; v[u][2 % V] = f.z; v[u][3 % V] = f.w;
-                } else {
-                    v[u][0] = __float_as_uint(ptr[(uint64_t)u * P.W]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (w + u < wb) {
-#pragma unroll
-                for (int i = 0; i < V; ++i) mean_add(acc[i], v[u][i]);
-            }
-        }
-    }
+    walk_piece<V>(M.norms + (l.wa - P.g0) * P.W + (uint64_t)l.slab * P.cols + lcol, l.wa, l.wb, P.W, [&](int i, uint32_t bits) { mean_add(acc[i], bits); });
 
     // the pieces of this workgroup that share the row r meet in the LDS slot of the first of them, one word at a time; with one piece
     // a row (spr == 1) or one piece a workgroup every lane group leads its own row and nothing meets
-    const uint64_t row_q0 = r * P.spr;
-    const uint32_t lead = row_q0 > wg_q0 ? (uint32_t)(row_q0 - wg_q0) : 0u;           // <= grp
     if (P.spr > 1 && P.pieces_per_group > 1) {
-        const uint32_t slot = lead * P.lanes_per_win * V + lcol;
+        const uint32_t slot = l.lead * P.lanes_per_win * V + lcol;
 #pragma unroll
         for (int i = 0; i < V; ++i) s_meet[tid * V + i] = 0;
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < kMeanWords; ++j) {
-            if (active) {
+            if (l.active) {
 #pragma unroll
                 for (int i = 0; i < V; ++i)
                     if (acc[i][j]) atomicAdd(&s_meet[slot + i], (unsigned long long)acc[i][j]);
@@ -235,11 +200,10 @@ __global__ __launch_bounds__(kPoolThreads) void k_mean(const MeanParams M) {
             __syncthreads();
         }
     }
-    if (!active || lead != grp) return;
-    const bool whole = row_q0 >= wg_q0 && row_q0 + P.spr <= wg_q0 + P.pieces_per_group && row_a >= P.g0 && row_b <= end;
-    const uint64_t col = (uint64_t)slab * P.cols + lcol;
-    if (whole) {
-        const uint64_t o = r * P.W + col;
+    if (!l.active || l.lead != grp) return;
+    const uint64_t col = (uint64_t)l.slab * P.cols + lcol;
+    if (l.whole(P)) {
+        const uint64_t o = l.r * P.W + col;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             uint32_t mb, cnt; double s;
@@ -249,7 +213,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_mean(const MeanParams M) {
             if (M.count) M.count[o + i] = cnt;
         }
     } else {
-        const uint64_t ra = r - M.r_base, cell = ra * P.W + col;
+        const uint64_t ra = l.r - M.r_base, cell = ra * P.W + col;
         if (ra >= M.acc_rows) return;                                    // never past the accumulator
         if (lcol == 0) M.flags[ra] = 1u;
 #pragma unroll

@@ -17,6 +17,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <optional>
 #include <thread>
 #include <algorithm>
@@ -3321,6 +3322,53 @@ struct Fold {
     }
     int close(int rc) const { rc = sync(rc); return rc ? rc : short_read(); }
 };
+
+// What the pooled sinks (qd_plan_pool, qd_plan_mean, qd_plan_density) and their CPU twins share besides the driver.
+int pool_given(uint64_t pool) { return pool ? QD_OK : fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window"); }
+// the rows R and cells R x W of a range of n_windows >= 1 windows as asked: pool is clamped to one row, and where a cell counts its values
+// (max_count != 0) a row holds at most that many windows
+int pool_rows(uint64_t *pool, uint64_t n_windows, uint32_t W, uint64_t max_count, uint64_t *R, uint64_t *cells) {
+    if (*pool > n_windows) *pool = n_windows;                        // one row either way
+    if (max_count && *pool > max_count) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)*pool);
+    *R = (n_windows - 1) / *pool + 1; *cells = *R * W;
+    return QD_OK;
+}
+// Output planes of a sink: the caller's pointers when out_dev, else back to back in workspace slot `slot` (a plane of 0 bytes is absent
+// and has no address); home queues the copies of the planes the caller asked for.
+struct Planes {
+    struct Plane { void *user; size_t bytes; void *dev; };
+    std::vector<Plane> v;
+    bool out_dev = false;
+    int place(Fold &f, int slot, bool dev, std::initializer_list<Plane> planes) {
+        v = planes; out_dev = dev;
+        size_t total = 0;
+        for (Plane &pl : v) { pl.dev = pl.bytes ? pl.user : nullptr; total += pl.bytes; }
+        if (out_dev || total == 0) return QD_OK;
+        void *base = nullptr;
+        if (const int rc = f.ws->get(slot, total, &base)) return rc;
+        for (Plane &pl : v) { pl.dev = pl.bytes ? base : nullptr; base = static_cast<uint8_t *>(base) + pl.bytes; }
+        return QD_OK;
+    }
+    int home(hipStream_t st) const {
+        for (const Plane &pl : v)
+            if (!out_dev && pl.user && pl.bytes) HIPCHK(hipMemcpyAsync(pl.user, pl.dev, pl.bytes, hipMemcpyDeviceToHost, st));
+        return QD_OK;
+    }
+};
+int launch_grid(uint64_t grid, uint64_t nw) {
+    return grid > 0x7fffffffull ? fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)nw) : QD_OK;
+}
+// the CPU twins' pre-pass over the rows that windows [at, at + n) touch (n >= 1), once per row and before anything is added: a row's
+// cells take at most its windows of this call on top of the held(cell) values they hold
+static_assert(kMeanMaxCount == kDensityMaxCount, "one limit for every counting cell");
+int rows_have_room(uint64_t pool, uint64_t at, uint64_t n, uint32_t width, const std::function<uint64_t(uint64_t cell)> &held) {
+    for (uint64_t r = at / pool; r <= (at + n - 1) / pool; ++r) {
+        const uint64_t a = std::max(at, r * pool), b = std::min(at + n, (r + 1) * pool);
+        for (uint32_t c = 0; c < width; ++c)
+            if (held(r * width + c) + (b - a) > kMeanMaxCount) return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)r);
+    }
+    return QD_OK;
+}
 }  // namespace
 
 int qd_summary_init(qd_summary *sum, float *peak, float *floor, uint32_t width) {
@@ -3444,8 +3492,8 @@ int launch_pool(const qd_plan *p, const float *norms_d, uint64_t g0, uint64_t nw
     PoolParams P{};
     uint64_t grid = 0;
     int V = 1;
-    pool_geometry(g0, nw, n_total, pool, p->W, p->n_cu, &P, &grid, &V);
-    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)nw);
+    pool_geometry(g0, nw, n_total, pool, p->W, p->n_cu, &P.G, &grid, &V);
+    if (const int rc = launch_grid(grid, nw)) return rc;
     P.norms = norms_d; P.peak = peak_d; P.floor = floor_d;
     P.vec_store = (((uintptr_t)peak_d | (uintptr_t)floor_d) & 15) == 0;
     hipLaunchKernelGGL(V == 4 ? k_pool<4> : k_pool<1>, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, P);
@@ -3464,7 +3512,7 @@ int qd_pool_init(float *peak_rows, float *floor_rows, uint32_t width, uint64_t r
 }
 
 int qd_pool_fold(float *peak_rows, float *floor_rows, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     if (!peak_rows && !floor_rows) return fail(QD_ERR_INVALID, "both peak_rows and floor_rows are NULL");
     if (n == 0) return QD_OK;
@@ -3487,37 +3535,27 @@ int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_pool", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
     if (const int rc = f.norms_plan()) return rc;
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (!peak_rows && !floor_rows) return fail(QD_ERR_INVALID, "both peak_rows and floor_rows are NULL");
     if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
     if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
     if (const int rc = f.unsharded("a sharded plan is not pooled in one call: give each device a contiguous range of rows on a plan of its own")) return rc;
     if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
-    if (pool > n_windows) pool = n_windows;                          // one row either way
-    const uint32_t W = p->W;
-    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;    // rows of the range as asked; f.n_windows is its complete part
+    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = pool_rows(&pool, n_windows, p->W, 0, &R, &words)) return rc;
     if (const int rc = f.open()) return rc;
-    // the accumulators: the caller's arrays when they are device memory, else [peak][floor] in the workspace
-    const bool out_dev = out_mem == QD_MEM_DEVICE;
     const hipStream_t st = f.st;
-    uint32_t *peak_d = reinterpret_cast<uint32_t *>(peak_rows), *floor_d = reinterpret_cast<uint32_t *>(floor_rows);
-    if (!out_dev) {
-        void *acc = nullptr;
-        if (const int rc = f.ws->get(1, (size_t)(words * 4 * ((peak_rows ? 1 : 0) + (floor_rows ? 1 : 0))), &acc)) return rc;
-        peak_d = peak_rows ? static_cast<uint32_t *>(acc) : nullptr;
-        floor_d = floor_rows ? static_cast<uint32_t *>(acc) + (peak_rows ? words : 0) : nullptr;
-    }
+    Planes out;                                                      // the accumulators: [peak][floor]
+    if (const int rc = out.place(f, 1, out_mem == QD_MEM_DEVICE, {{peak_rows, peak_rows ? (size_t)(words * 4) : 0}, {floor_rows, floor_rows ? (size_t)(words * 4) : 0}})) return rc;
+    uint32_t *peak_d = static_cast<uint32_t *>(out.v[0].dev), *floor_d = static_cast<uint32_t *>(out.v[1].dev);
     // the fold identities: +0.0 is bit pattern 0, +inf the largest non-NaN
     if (peak_d) HIPCHK(hipMemsetAsync(peak_d, 0, (size_t)(words * 4), st));
     if (floor_d) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(floor_d), (int)kPoolInfBits, (size_t)words, st));
-    const int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+    int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
         return launch_pool(p, norms_d, g0, nw, f.n_windows, pool, peak_d, floor_d, s);
     });
-    if (rc == QD_OK && !out_dev) {
-        if (peak_rows) HIPCHK(hipMemcpyAsync(peak_rows, peak_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-        if (floor_rows) HIPCHK(hipMemcpyAsync(floor_rows, floor_d, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-    }
+    if (rc == QD_OK) rc = out.home(st);
     return f.close(rc);
 }
 
@@ -3531,11 +3569,11 @@ struct MeanAcc { unsigned long long *limbs; uint32_t *flags; uint64_t rows; };  
 // and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows) of the range, on `st`
 int launch_mean(const qd_plan *p, const MeanParams &geo, uint64_t grid, int V, const float *norms_d, const MeanOut &out, const MeanAcc &acc,
                 bool cuts, uint64_t r_base, hipStream_t st) {
-    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)geo.G.nw);
+    if (const int rc = launch_grid(grid, geo.G.nw)) return rc;
     const uint64_t ra = geo.G.g0 / geo.G.pool, rb = (geo.G.g0 + geo.G.nw - 1) / geo.G.pool;
     if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
     MeanParams M = geo;
-    M.G.norms = norms_d; M.G.peak = M.G.floor = nullptr;
+    M.norms = norms_d;
     M.mean = out.mean; M.sum = out.sum; M.count = out.count;
     M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
     hipLaunchKernelGGL(V == 4 ? k_mean<4> : k_mean<1>, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
@@ -3565,18 +3603,12 @@ int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows) {
 }
 
 int qd_mean_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
     if (n == 0) return QD_OK;
     if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
-    // once per row, before anything is added: the row's cells take at most its windows of this call on top of what they hold
-    for (uint64_t r = at / pool; r <= (at + n - 1) / pool; ++r) {
-        const uint64_t a = std::max(at, r * pool), b = std::min(at + n, (r + 1) * pool);
-        for (uint32_t c = 0; c < width; ++c)
-            if (mean_cell_count(acc + (r * width + c) * QD_MEAN_WORDS) + (b - a) > kMeanMaxCount)
-                return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)r);
-    }
+    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return mean_cell_count(acc + cell * QD_MEAN_WORDS); })) return rc;
     for (uint64_t i = 0; i < n; ++i) {
         const float *row = norms + i * width;
         uint64_t *cells = acc + (at + i) / pool * width * QD_MEAN_WORDS;
@@ -3620,32 +3652,24 @@ int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_mean", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
     if (const int rc = f.norms_plan()) return rc;
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (!mean_rows && !sum_rows && !count_rows) return fail(QD_ERR_INVALID, "mean_rows, sum_rows and count_rows are all NULL");
     if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
     if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
     if (const int rc = f.unsharded("a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)")) return rc;
     if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
-    if (pool > n_windows) pool = n_windows;                          // one row either way
-    if (pool > kMeanMaxCount) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)pool);
     const uint32_t W = p->W;
-    const uint64_t R = (n_windows - 1) / pool + 1, words = R * W;    // rows of the range as asked ...
+    uint64_t R, words;                                               // rows of the range as asked ...
+    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
     n_windows = f.n_windows;                                         // ... and from here its complete part
     if (int rc = f.open()) return rc;
-    const bool out_dev = out_mem == QD_MEM_DEVICE;
     const hipStream_t st = f.st;
-    int rc = QD_OK;
-    // the outputs: the caller's arrays when they are device memory, else [sum][mean][count] in the workspace, copied down once
-    MeanOut out{mean_rows, sum_rows, count_rows};
-    if (!out_dev) {
-        void *o = nullptr;
-        rc = f.ws->get(2, (size_t)(words * ((sum_rows ? 8 : 0) + (mean_rows ? 4 : 0) + (count_rows ? 4 : 0))), &o); if (rc) return rc;
-        uint8_t *at = static_cast<uint8_t *>(o);
-        out.sum = sum_rows ? reinterpret_cast<double *>(at) : nullptr; at += sum_rows ? words * 8 : 0;
-        out.mean = mean_rows ? reinterpret_cast<float *>(at) : nullptr; at += mean_rows ? words * 4 : 0;
-        out.count = count_rows ? reinterpret_cast<uint32_t *>(at) : nullptr;
-    }
+    Planes planes;                                                   // the outputs: [sum][mean][count]
+    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {{sum_rows, sum_rows ? (size_t)(words * 8) : 0}, {mean_rows, mean_rows ? (size_t)(words * 4) : 0},
+                                                           {count_rows, count_rows ? (size_t)(words * 4) : 0}});
+    if (rc) return rc;
+    const MeanOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev)};
     if (f.is_short) {                                                // rows without a complete window: no values
         if (out.mean) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out.mean), (int)kMeanNanBits, (size_t)words, st));
         if (out.sum) HIPCHK(hipMemsetAsync(out.sum, 0, (size_t)(words * 8), st));
@@ -3712,11 +3736,7 @@ int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
             if (rc == QD_OK) rc = launch_mean_finish(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
         }
     }
-    if (rc == QD_OK && !out_dev) {
-        if (mean_rows) HIPCHK(hipMemcpyAsync(mean_rows, out.mean, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-        if (sum_rows) HIPCHK(hipMemcpyAsync(sum_rows, out.sum, (size_t)(words * 8), hipMemcpyDeviceToHost, st));
-        if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, out.count, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-    }
+    if (rc == QD_OK) rc = planes.home(st);
     return f.close(rc);
 }
 
@@ -3737,8 +3757,8 @@ int launch_density(const qd_plan *p, const float *norms_d, uint64_t g0, uint64_t
     DensityParams D{};
     uint64_t grid = 0;
     density_geometry(g0, nw, n_total, pool, p->W, levels, p->n_cu, &D, &grid);
-    if (grid > 0x7fffffffull) return fail(QD_ERR_INVALID, "a batch of %llu windows is too large for one launch: lower chunk_bytes", (unsigned long long)nw);
-    D.G.norms = norms_d; D.counts = counts_d; D.level0 = level0;
+    if (const int rc = launch_grid(grid, nw)) return rc;
+    D.norms = norms_d; D.counts = counts_d; D.level0 = level0;
     hipLaunchKernelGGL(k_density, dim3((uint32_t)grid), dim3(kDensityThreads), 0, st, D);
     HIPCHK(hipGetLastError());
     return QD_OK;
@@ -3753,22 +3773,14 @@ int qd_density_init(uint32_t *counts, uint32_t width, uint32_t levels, uint64_t 
 }
 
 int qd_density_fold(uint32_t *counts, uint32_t width, uint32_t level0, uint32_t levels, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     if (const int rc = density_grid(level0, levels)) return rc;
     if (!counts) return fail(QD_ERR_INVALID, "counts is NULL");
     if (n == 0) return QD_OK;
     if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
-    // once per row, before anything is added: the row's cells take at most its windows of this call on top of what they hold
-    for (uint64_t r = at / pool; r <= (at + n - 1) / pool; ++r) {
-        const uint64_t a = std::max(at, r * pool), b = std::min(at + n, (r + 1) * pool);
-        for (uint32_t c = 0; c < width; ++c) {
-            const uint32_t *cell = counts + (r * width + c) * levels;
-            uint64_t N = 0;
-            for (uint32_t l = 0; l < levels; ++l) N += cell[l];
-            if (N + (b - a) > kDensityMaxCount) return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)r);
-        }
-    }
+    auto held = [&](uint64_t cell) { return std::accumulate(counts + cell * levels, counts + (cell + 1) * levels, uint64_t{0}); };
+    if (const int rc = rows_have_room(pool, at, n, width, held)) return rc;
     for (uint64_t i = 0; i < n; ++i) {
         const float *row = norms + i * width;
         uint32_t *cells = counts + (at + i) / pool * width * levels;
@@ -3825,7 +3837,7 @@ int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_density", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
     if (const int rc = f.norms_plan()) return rc;
-    if (pool == 0) return fail(QD_ERR_INVALID, "pool is 0: a row folds at least one window");
+    if (const int rc = pool_given(pool)) return rc;
     if (const int rc = density_grid(level0, levels)) return rc;
     if (n_q > (uint32_t)kDensityMaxQ) return fail(QD_ERR_INVALID, "%u quantiles: a call takes at most %d", n_q, kDensityMaxQ);
     if (n_q && !q) return fail(QD_ERR_INVALID, "q is NULL");
@@ -3841,10 +3853,9 @@ int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     if (const int rc = f.unsharded("a sharded plan is not counted in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard counts (qd_density_merge)")) return rc;
     if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
-    if (pool > n_windows) pool = n_windows;                          // one row either way
-    if (pool > kDensityMaxCount) return fail(QD_ERR_INVALID, "a row of %llu windows: a group holds at most 2^31", (unsigned long long)pool);
     const uint32_t W = p->W;
-    const uint64_t R = (n_windows - 1) / pool + 1, cells = R * W;    // rows of the range as asked; f.n_windows is its complete part
+    uint64_t R, cells;                                               // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = pool_rows(&pool, n_windows, W, kDensityMaxCount, &R, &cells)) return rc;
     const bool out_dev = out_mem == QD_MEM_DEVICE;
     const bool own_acc = !(out_dev && count_rows);
     if (own_acc && (cells > kDensityMaxWorkspace / 4 / levels))
@@ -3853,19 +3864,11 @@ int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     const uint64_t words = cells * levels;
     if (const int rc = f.open()) return rc;
     const hipStream_t st = f.st;
-    // the accumulator: the caller's counts when they are device memory, else a workspace; the traces likewise
-    uint32_t *acc = count_rows;
-    if (own_acc) {
-        void *a = nullptr;
-        if (const int rc = f.ws->get(1, (size_t)(words * 4), &a)) return rc;
-        acc = static_cast<uint32_t *>(a);
-    }
-    uint32_t *trace_d = reinterpret_cast<uint32_t *>(trace_rows);
-    if (n_q && !out_dev) {
-        void *t = nullptr;
-        if (const int rc = f.ws->get(2, (size_t)(cells * n_q * 4), &t)) return rc;
-        trace_d = static_cast<uint32_t *>(t);
-    }
+    // the accumulator: the caller's counts when they are device memory, else a workspace, asked for or not; the traces likewise
+    Planes counts, traces;
+    if (const int rc = counts.place(f, 1, !own_acc, {{count_rows, (size_t)(words * 4)}})) return rc;
+    if (const int rc = traces.place(f, 2, out_dev, {{trace_rows, (size_t)(cells * n_q * 4)}})) return rc;
+    uint32_t *acc = static_cast<uint32_t *>(counts.v[0].dev), *trace_d = static_cast<uint32_t *>(traces.v[0].dev);
     HIPCHK(hipMemsetAsync(acc, 0, (size_t)(words * 4), st));
     int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
         return launch_density(p, norms_d, g0, nw, f.n_windows, pool, level0, levels, acc, s);
@@ -3878,10 +3881,8 @@ int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first
             HIPCHK(hipGetLastError());
         }
     }
-    if (rc == QD_OK && !out_dev) {
-        if (count_rows) HIPCHK(hipMemcpyAsync(count_rows, acc, (size_t)(words * 4), hipMemcpyDeviceToHost, st));
-        if (n_q) HIPCHK(hipMemcpyAsync(trace_rows, trace_d, (size_t)(cells * n_q * 4), hipMemcpyDeviceToHost, st));
-    }
+    if (rc == QD_OK) rc = counts.home(st);
+    if (rc == QD_OK) rc = traces.home(st);
     return f.close(rc);
 }
 

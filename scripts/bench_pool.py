@@ -6,7 +6,7 @@ device-resident 16 GiB cf32 stream in one process: cfg3''s chain (shift -> 200-t
   pool=P      qd_plan_pool into device rows at P = 1, 64, n / 2048 and n
 Expected: a pool leg is no slower than summarize, within summarize's own min-to-max spread; pool = 1 may cost up to the norms sink's
 write on top.
-usage: python scripts/bench_pool.py [log2 samples, default 31]   (writes profiles/r07/pool_sink.log)"""
+usage: python scripts/bench_pool.py [log2 samples, default 31] [log path, default profiles/r07/pool_sink.log]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,8 +18,9 @@ import quadrs_amd as Q
 n = 1 << (int(sys.argv[1]) if len(sys.argv) > 1 else 31)
 dev = torch.device("cuda", 0)
 src = bench.synth_slab(torch, 0, 0, n, 0x5EED0002, dev)
-os.makedirs(os.path.join(ROOT, "profiles", "r07"), exist_ok=True)
-log = open(os.path.join(ROOT, "profiles", "r07", "pool_sink.log"), "w")
+log_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r07", "pool_sink.log")
+os.makedirs(os.path.dirname(os.path.abspath(log_path)), exist_ok=True)
+log = open(log_path, "w")
 
 
 def say(line):

@@ -7,7 +7,7 @@ with HIP events:
   density L=64        qd_plan_density, counts in device rows, pool 512, 64 levels around the median bucket
   density L=256       the hard case: 64 columns a workgroup, four lanes a column
   density L=64 +q     the same with the 0.5 and 0.9 traces (k_density_quantile behind the fold)
-usage: python scripts/density_rate.py [log2 samples, default 31]   (writes profiles/r09/density.log)"""
+usage: python scripts/density_rate.py [log2 samples, default 31] [log path, default profiles/r09/density.log]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,8 +20,9 @@ import quadrs_amd as Q
 n = 1 << (int(sys.argv[1]) if len(sys.argv) > 1 else 31)
 dev = torch.device("cuda", 0)
 src = bench.synth_slab(torch, 0, 0, n, 0x5EED0002, dev)
-os.makedirs(os.path.join(ROOT, "profiles", "r09"), exist_ok=True)
-log = open(os.path.join(ROOT, "profiles", "r09", "density.log"), "w")
+log_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r09", "density.log")
+os.makedirs(os.path.dirname(os.path.abspath(log_path)), exist_ok=True)
+log = open(log_path, "w")
 
 
 def say(line):
