@@ -480,6 +480,55 @@ int qd_plan_mean(qd_plan *plan, const void *src, int src_mem, uint64_t src_first
                  uint64_t first_window, uint64_t n_windows, uint64_t pool,
                  float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ RMS-trace rows of a norms plan
+ *
+ * The power average (the RMS detector; the Bartlett / Welch estimate) next to max hold, min hold and the average of |X|: over windows
+ * [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W and R = ceil(n / pool) rows grouped exactly as qd_plan_pool and qd_plan_mean group
+ * them (ragged last row; pool > n acts as pool = n), per row r and fftshifted bin b over the f32 values v the norms sink writes for the
+ * group (a NaN is ignored, the sign bit is dropped):
+ *   count_rows[r W + b]  u32  the number of non-NaN values, +inf included
+ *   sumsq_rows[r W + b]  f64  the EXACT real sum of v^2 rounded once, to nearest, ties to even; 0.0 with no values; always zero or a
+ *                             normal f64 (2^-298 ... < 2^287)
+ *   rms_rows[r W + b]    f32  the real number sqrt(sum of v^2 / count) rounded once to f32, nearest, ties to even, subnormal results
+ *                             included (it is not (float)sqrt(sumsq / count)); the quiet NaN 0x7fc00000 with no values.  It lies between
+ *                             the group's smallest and largest value, so it never overflows
+ * Any +inf makes sumsq and rms +inf.  The squares are accumulated exactly, in fixed point, and the results depend on no batch, chunk,
+ * memory kind, launch or arrival order.  pool == 1: rms is |norm| bit for bit wherever it is not NaN and sumsq == (double)v * (double)v
+ * exactly.  A group holds at most 2^31 windows.
+ *
+ * The accumulator is public so that parts and shards merge: rows * width * QD_POWER_WORDS caller-owned uint64_t, cell (r, b) at
+ * (r width + b) QD_POWER_WORDS.  Words 0-17 are limbs L[0..17] in units of 2^-298, 32 payload bits each plus deferred carries: the
+ * cell's exact sum of squares is the sum of L[j] 2^(32 j) 2^-298.  A value of biased exponent e and 23-bit fraction m (m |= 1 << 23
+ * when e != 0), with s = max(e, 1) - 1, q = m m (< 2^48), sh = 2 s, j = sh >> 5 (0 ... 15), t = sh & 31 and the 79-bit v = q << t, adds
+ * v & 0xffffffff to L[j], (v >> 32) & 0xffffffff to L[j + 1] and v >> 64 to L[j + 2]; at most 2^31 values per cell keep every limb below
+ * 2^63 and the carried sum below 2^585 (19 limbs of 32 bits).  Word 18 is the count of finite values plus the count of +inf values
+ * shifted left by 32, exactly as QD_MEAN_WORDS' word 9.  Every word is an integer sum: parts merge by word-wise addition. */
+#define QD_POWER_WORDS 19
+
+/* All words 0: `rows` rows of `width` cells.  QD_ERR_INVALID: acc NULL or width == 0. */
+int qd_power_init(uint64_t *acc, uint32_t width, uint64_t rows);
+/* The CPU twin of the kernel behind qd_plan_power, bit for bit: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32 in
+ * `norms`) ACCUMULATE into rows (at + i) / pool of acc, which holds the range's rows from row 0 on.  Parts of a range folded in any
+ * order give the same words.  QD_ERR_INVALID: pool == 0, width == 0, acc NULL, norms NULL with n > 0, or a row whose cells would hold
+ * more than 2^31 values (checked once per row before anything is added: acc is then unchanged). */
+int qd_power_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n);
+/* dst += src, word-wise.  QD_ERR_INVALID: NULL, width == 0, or a cell's count would pass 2^31 (dst is then unchanged). */
+int qd_power_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows);
+/* The results of an accumulator, rows * width each; any may be NULL, not all.  QD_ERR_INVALID: acc NULL, width == 0, all outputs NULL. */
+int qd_power_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *rms_rows, double *sumsq_rows, uint32_t *count_rows);
+/* The RMS-trace rows of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; every argument as qd_plan_mean's, the outputs
+ * OVERWRITTEN, the call returning after they are complete.  A row whose windows one workgroup sees in one batch is rounded in the fold
+ * kernel; every other row goes through a device limb accumulator of at most max(2 chunk_bytes, 152 W bytes), whatever R is, and is
+ * rounded by a second small kernel.
+ * Codes as qd_plan_mean: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, pool == 0, pool (clamped to n_windows) above
+ * 2^31, all outputs NULL or an unknown memory kind; QD_ERR_SHORT past the sink's loop (the outputs are not touched), and for a
+ * cascade's range past qd_plan_complete_windows (every complete window of the range is folded; rows without one hold count 0, sumsq
+ * 0.0, rms NaN); QD_ERR_UNSUPPORTED for a plan created with shards (qd_power_merge per shard's accumulator, or give each device a
+ * contiguous range of ROWS on a plan of its own).  n_windows == 0: QD_OK, nothing is touched. */
+int qd_plan_power(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                  uint64_t first_window, uint64_t n_windows, uint64_t pool,
+                  float *rms_rows, double *sumsq_rows, uint32_t *count_rows, int out_mem, void *stream);
+
 /* ------------------------------------------------------------------ percentile traces and persistence counts of a norms plan
  *
  * The trace the average cannot be: a noise floor that one burst, or one +inf, does not drag up — a median, or any percentile, per bin —

@@ -28,10 +28,12 @@ SYMBOLS = [
     "qd_summary_init", "qd_summary_fold", "qd_summary_merge", "qd_summary_quantile", "qd_plan_summarize",
     "qd_pool_init", "qd_pool_fold", "qd_plan_pool",
     "qd_mean_init", "qd_mean_fold", "qd_mean_merge", "qd_mean_finish", "qd_plan_mean",
+    "qd_power_init", "qd_power_fold", "qd_power_merge", "qd_power_finish", "qd_plan_power",
     "qd_density_init", "qd_density_fold", "qd_density_merge", "qd_density_quantile", "qd_plan_density",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
+POWER_WORDS = 19
 DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
@@ -185,6 +187,11 @@ def lib():
             "qd_mean_merge": (i32, [vp, vp, C.c_uint32, u64]),
             "qd_mean_finish": (i32, [vp, C.c_uint32, u64, vp, vp, vp]),
             "qd_plan_mean": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, i32, vp]),
+            "qd_power_init": (i32, [vp, C.c_uint32, u64]),
+            "qd_power_fold": (i32, [vp, C.c_uint32, u64, u64, vp, u64]),
+            "qd_power_merge": (i32, [vp, vp, C.c_uint32, u64]),
+            "qd_power_finish": (i32, [vp, C.c_uint32, u64, vp, vp, vp]),
+            "qd_plan_power": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, i32, vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -62,9 +62,10 @@ QD_MEAN_HD inline int mean_clz64(uint64_t x) {
 #endif
 }
 
-// The leading 64 bits of the 320-bit integer I[9..0] (I[9] the most significant limb): top has bit 63 set unless I is 0, `bits` is I's
-// bit length and sticky says whether any bit below the 64 is set.  Fixed trip count, no indexed store: it unrolls into registers.
-QD_MEAN_HD inline void mean_leading(const uint32_t *I, uint64_t *top, bool *sticky, int *bits) {
+// The leading 64 bits of the integer I[N-1..0] of N 32-bit limbs (I[N-1] the most significant): top has bit 63 set unless I is 0, `bits`
+// is I's bit length and sticky says whether any bit below the 64 is set.  Fixed trip count, no indexed store: it unrolls into registers.
+template <int N>
+QD_MEAN_HD inline void limbs_leading(const uint32_t *I, uint64_t *top, bool *sticky, int *bits) {
     uint64_t t = 0;
     uint32_t nxt = 0;
     int low = 0;
@@ -72,7 +73,7 @@ QD_MEAN_HD inline void mean_leading(const uint32_t *I, uint64_t *top, bool *stic
 #if defined(__HIPCC__)
 #pragma unroll
 #endif
-    for (int k = kMeanWords - 1; k >= 0; --k) {
+    for (int k = N - 1; k >= 0; --k) {
         if ((t >> 32) == 0) { t = (t << 32) | I[k]; low = k; }
         else if (!have) { nxt = I[k]; have = true; }
         else st = st || I[k] != 0;
@@ -84,6 +85,8 @@ QD_MEAN_HD inline void mean_leading(const uint32_t *I, uint64_t *top, bool *stic
     *sticky = st || (uint32_t)n64 != 0;
     *bits = 64 - lz + 32 * low;
 }
+// the mean's 320-bit integers I[9..0]
+QD_MEAN_HD inline void mean_leading(const uint32_t *I, uint64_t *top, bool *sticky, int *bits) { limbs_leading<kMeanWords>(I, top, sticky, bits); }
 
 // A cell's words into its three results, each rounded once, to nearest, ties to even:
 //   count  finite + inf values;  none: sum 0.0, mean the quiet NaN 0x7fc00000;  any +inf: sum and mean +inf

@@ -36,6 +36,7 @@
 #include "qd_pool.h"
 #include "qd_density.h"
 #include "qd_mean.h"
+#include "qd_power.h"
 
 using namespace qd;
 
@@ -3563,7 +3564,8 @@ int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
 
 namespace {
 struct MeanOut { float *mean; double *sum; uint32_t *count; };
-struct MeanAcc { unsigned long long *limbs; uint32_t *flags; uint64_t rows; };      // device: kMeanWords x rows x W limbs (planar), rows flags
+struct LimbAcc { unsigned long long *limbs; uint32_t *flags; uint64_t rows; };      // device: words x rows x W limbs (planar), rows flags
+using MeanAcc = LimbAcc;                                                            // words = kMeanWords
 
 // one batch of norms rows (device memory, 16-byte aligned) — windows [g0, g0 + nw) of a range of n_total — into the outputs (whole rows)
 // and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows) of the range, on `st`
@@ -3580,10 +3582,6 @@ int launch_mean(const qd_plan *p, const MeanParams &geo, uint64_t grid, int V, c
     HIPCHK(hipGetLastError());
     return QD_OK;
 }
-int mean_acc_clear(const qd_plan *p, const MeanAcc &acc, hipStream_t st) {
-    HIPCHK(hipMemsetAsync(acc.limbs, 0, (size_t)(acc.rows * p->W * kMeanWords * 8 + acc.rows * 4), st));      // the flags lie behind the limbs
-    return QD_OK;
-}
 int launch_mean_finish(const qd_plan *p, const MeanAcc &acc, uint64_t r_base, uint64_t n_rows, const MeanOut &out, hipStream_t st) {
     const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
     if (!cells) return QD_OK;
@@ -3593,6 +3591,94 @@ int launch_mean_finish(const qd_plan *p, const MeanAcc &acc, uint64_t r_base, ui
     return QD_OK;
 }
 uint64_t mean_cell_count(const uint64_t *cell) { return (cell[9] & 0xffffffffull) + (cell[9] >> 32); }
+
+// The walk of the sinks that fold through a limb accumulator (qd_plan_mean, qd_plan_power): a fold kernel that rounds whole rows itself
+// and adds cut rows into `words` planar u64 a cell, and a finish kernel that rounds the flagged rows.  The sink gives its cell size and
+// four steps; the walk owns the accumulator (workspace slot 1: at most max(2 chunk_bytes, one row), its flags behind it) and the batches.
+struct LimbSink {
+    uint32_t words;                              // u64 words per cell
+    // the launch geometry of the batch [g0, g0 + nw) of the range's complete windows
+    std::function<void(uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V)> geometry;
+    // one batch of norms rows into the outputs (whole rows) and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows)
+    std::function<int(const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t st)> fold;
+    // the flagged rows [r_base, r_base + n_rows) of the accumulator into the outputs
+    std::function<int(const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t st)> finish;
+    // every output row as a row without values (a short cascade: rows without a complete window keep this)
+    std::function<int(hipStream_t st)> fill_empty;
+};
+int walk_limbs(Fold &f, uint64_t pool, uint64_t R, const LimbSink &k) {
+    const qd_plan *p = f.p;
+    const uint64_t n_windows = f.n_windows;                          // the complete part of the range; R counts the rows as asked
+    const hipStream_t st = f.st;
+    int rc = f.is_short ? k.fill_empty(st) : QD_OK;
+    if (rc || !n_windows) return rc;
+    const uint64_t row_bytes = (uint64_t)p->W * k.words * 8;
+    const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
+    LimbAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
+    void *a = nullptr;
+    rc = f.ws->get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
+    acc.limbs = static_cast<unsigned long long *>(a);
+    acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
+    auto clear = [&]() { HIPCHK(hipMemsetAsync(acc.limbs, 0, (size_t)(acc.rows * row_bytes + acc.rows * 4), st)); return (int)QD_OK; };
+    if (f.src_mem == QD_MEM_DEVICE) {
+        // this walk cuts its own batches of the carrier's windows
+        rc = f.carrier();
+        const uint64_t cw = f.cw, bw = pool <= cw ? cw / pool * pool : cw;       // seams on row boundaries where a chunk holds a row
+        bool open = false;
+        uint64_t r_base = 0;
+        auto close = [&]() { const int c = open ? k.finish(acc, r_base, std::min(acc.rows, R - r_base), st) : QD_OK; open = false; return c; };
+        for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
+            uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
+            PieceGeometry G{};
+            int V = 1;
+            k.geometry(g0, nw, &G, &grid, &V);
+            const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
+            const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
+            const bool cuts = G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
+            if (cuts) {
+                if (!open || (!mid && rb >= r_base + acc.rows)) {                // move the accumulator: only between rows
+                    rc = close();
+                    if (rc == QD_OK) rc = clear();
+                    r_base = ra; open = true;
+                }
+                if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
+                    nw = (r_base + acc.rows) * pool - g0;
+                    k.geometry(g0, nw, &G, &grid, &V);
+                }
+            }
+            if (rc == QD_OK)
+                rc = f.device(g0, nw, [&](const float *norms_d, uint64_t, uint64_t, hipStream_t s) {
+                    return k.fold(G, grid, V, norms_d, acc, cuts, cuts ? r_base : ra, s);
+                });
+            g0 += nw;
+        }
+        if (rc == QD_OK) rc = close();
+    } else {
+        // host sources: the upload ring cuts its own batches, on two streams; the range goes span by span of the accumulator's rows
+        const uint64_t Rn = (n_windows - 1) / pool + 1;
+        for (uint64_t r_base = 0; r_base < Rn && rc == QD_OK; r_base += acc.rows) {
+            const uint64_t g_a = r_base * pool, g_b = std::min<uint64_t>(n_windows, (r_base + acc.rows) * pool);
+            rc = clear();
+            if (rc) break;
+            rc = f.host(g_a, g_b - g_a, [&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+                PieceGeometry G{};
+                uint64_t grid = 0;
+                int V = 1;
+                k.geometry(g0, nw, &G, &grid, &V);
+                return k.fold(G, grid, V, norms_d, acc, true, r_base, s);
+            });
+            if (rc == QD_OK) rc = k.finish(acc, r_base, std::min(acc.rows, Rn - r_base), st);
+        }
+    }
+    return rc;
+}
+// the empty rows of a sink whose outputs are an f32, an f64 and a u32 plane of `words` cells: the quiet NaN, 0.0, 0
+int fill_no_values(float *f32_d, double *f64_d, uint32_t *u32_d, uint64_t words, hipStream_t st) {
+    if (f32_d) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f32_d), (int)kMeanNanBits, (size_t)words, st));
+    if (f64_d) HIPCHK(hipMemsetAsync(f64_d, 0, (size_t)(words * 8), st));
+    if (u32_d) HIPCHK(hipMemsetAsync(u32_d, 0, (size_t)(words * 4), st));
+    return QD_OK;
+}
 }  // namespace
 
 int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows) {
@@ -3660,83 +3746,156 @@ int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
     if (const int rc = f.admit()) return rc;
     if (n_windows == 0) return QD_OK;
     const uint32_t W = p->W;
-    uint64_t R, words;                                               // rows of the range as asked ...
+    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
     if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
-    n_windows = f.n_windows;                                         // ... and from here its complete part
     if (int rc = f.open()) return rc;
-    const hipStream_t st = f.st;
     Planes planes;                                                   // the outputs: [sum][mean][count]
     int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {{sum_rows, sum_rows ? (size_t)(words * 8) : 0}, {mean_rows, mean_rows ? (size_t)(words * 4) : 0},
                                                            {count_rows, count_rows ? (size_t)(words * 4) : 0}});
     if (rc) return rc;
     const MeanOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev)};
-    if (f.is_short) {                                                // rows without a complete window: no values
-        if (out.mean) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out.mean), (int)kMeanNanBits, (size_t)words, st));
-        if (out.sum) HIPCHK(hipMemsetAsync(out.sum, 0, (size_t)(words * 8), st));
-        if (out.count) HIPCHK(hipMemsetAsync(out.count, 0, (size_t)(words * 4), st));
-    }
-    // the limb accumulator (qd_mean.h): at most max(2 chunk_bytes, one row), its flags behind it
-    const uint64_t row_bytes = (uint64_t)W * kMeanWords * 8;
-    const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
-    MeanAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
-    if (n_windows) {
-        void *a = nullptr;
-        rc = f.ws->get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
-        acc.limbs = static_cast<unsigned long long *>(a);
-        acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
-    }
-    auto geometry = [&](uint64_t g0, uint64_t nw, MeanParams *M, uint64_t *grid, int *V) { pool_geometry(g0, nw, n_windows, pool, W, p->n_cu, &M->G, grid, V); };
-    if (n_windows && src_mem == QD_MEM_DEVICE) {
-        // this sink cuts its own batches of the carrier's windows
-        rc = f.carrier();
-        const uint64_t cw = f.cw, bw = pool <= cw ? cw / pool * pool : cw;       // seams on row boundaries where a chunk holds a row
-        bool open = false;
-        uint64_t r_base = 0;
-        auto close = [&]() { const int c = open ? launch_mean_finish(p, acc, r_base, std::min(acc.rows, R - r_base), out, st) : QD_OK; open = false; return c; };
-        for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
-            uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
-            MeanParams M{};
-            int V = 1;
-            geometry(g0, nw, &M, &grid, &V);
-            const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
-            const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
-            const bool cuts = M.G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
-            if (cuts) {
-                if (!open || (!mid && rb >= r_base + acc.rows)) {                // move the accumulator: only between rows
-                    rc = close();
-                    if (rc == QD_OK) rc = mean_acc_clear(p, acc, st);
-                    r_base = ra; open = true;
-                }
-                if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
-                    nw = (r_base + acc.rows) * pool - g0;
-                    geometry(g0, nw, &M, &grid, &V);
-                }
-            }
-            if (rc == QD_OK)
-                rc = f.device(g0, nw, [&](const float *norms_d, uint64_t, uint64_t, hipStream_t s) {
-                    return launch_mean(p, M, grid, V, norms_d, out, acc, cuts, cuts ? r_base : ra, s);
-                });
-            g0 += nw;
+    // the limb accumulator (qd_mean.h) and the batches: walk_limbs
+    LimbSink k;
+    k.words = kMeanWords;
+    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { pool_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, G, grid, V); };
+    k.fold = [&](const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
+        MeanParams M{};
+        M.G = G;
+        return launch_mean(p, M, grid, V, norms_d, out, acc, cuts, r_base, s);
+    };
+    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_mean_finish(p, acc, r_base, n_rows, out, s); };
+    k.fill_empty = [&](hipStream_t s) { return fill_no_values(out.mean, out.sum, out.count, words, s); };
+    rc = walk_limbs(f, pool, R, k);
+    if (rc == QD_OK) rc = planes.home(f.st);
+    return f.close(rc);
+}
+
+// ------------------------------------------------------------------ RMS-trace rows
+
+namespace {
+struct PowerOut { float *rms; double *sumsq; uint32_t *count; };
+
+// k_power's form (qd_power.h): one bin a lane; a development build also holds four bins a lane, for measuring them side by side
+#ifdef QD_DEVELOP
+int power_form() { const char *e = dev_env("QD_POWER_V"); return e && atoi(e) == 4 ? 4 : 1; }
+#else
+int power_form() { return 1; }
+#endif
+
+// one batch of norms rows (device memory, 16-byte aligned) into the outputs (whole rows) and the accumulator (cut rows), as launch_mean
+int launch_power(const qd_plan *p, const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const PowerOut &out, const LimbAcc &acc,
+                 bool cuts, uint64_t r_base, hipStream_t st) {
+    if (const int rc = launch_grid(grid, G.nw)) return rc;
+    const uint64_t ra = G.g0 / G.pool, rb = (G.g0 + G.nw - 1) / G.pool;
+    if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
+    PowerParams M{};
+    M.G = G;
+    M.norms = norms_d;
+    M.rms = out.rms; M.sumsq = out.sumsq; M.count = out.count;
+    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
+    void (*fn)(PowerParams) = k_power<1>;
+#ifdef QD_DEVELOP
+    if (V == 4) fn = k_power<4>;
+#endif
+    hipLaunchKernelGGL(fn, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+int launch_power_finish(const qd_plan *p, const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, const PowerOut &out, hipStream_t st) {
+    const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
+    if (!cells) return QD_OK;
+    hipLaunchKernelGGL(k_power_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
+                       out.rms, out.sumsq, out.count);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+uint64_t power_cell_count(const uint64_t *cell) { return (cell[18] & 0xffffffffull) + (cell[18] >> 32); }
+}  // namespace
+
+int qd_power_init(uint64_t *acc, uint32_t width, uint64_t rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    memset(acc, 0, (size_t)(rows * width * QD_POWER_WORDS * 8));
+    return QD_OK;
+}
+
+int qd_power_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+    if (const int rc = pool_given(pool)) return rc;
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return power_cell_count(acc + cell * QD_POWER_WORDS); })) return rc;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        uint64_t *cells = acc + (at + i) / pool * width * QD_POWER_WORDS;
+        for (uint32_t b = 0; b < width; ++b) {
+            uint32_t bits;
+            memcpy(&bits, row + b, 4);
+            power_add(cells + (uint64_t)b * QD_POWER_WORDS, bits);
         }
-        if (rc == QD_OK) rc = close();
-    } else if (n_windows) {
-        // host sources: the upload ring cuts its own batches, on two streams; the range goes span by span of the accumulator's rows
-        const uint64_t Rn = (n_windows - 1) / pool + 1;
-        for (uint64_t r_base = 0; r_base < Rn && rc == QD_OK; r_base += acc.rows) {
-            const uint64_t g_a = r_base * pool, g_b = std::min<uint64_t>(n_windows, (r_base + acc.rows) * pool);
-            rc = mean_acc_clear(p, acc, st);
-            if (rc) break;
-            rc = f.host(g_a, g_b - g_a, [&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
-                MeanParams M{};
-                uint64_t grid = 0;
-                int V = 1;
-                geometry(g0, nw, &M, &grid, &V);
-                return launch_mean(p, M, grid, V, norms_d, out, acc, true, r_base, s);
-            });
-            if (rc == QD_OK) rc = launch_mean_finish(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
-        }
     }
-    if (rc == QD_OK) rc = planes.home(st);
+    return QD_OK;
+}
+
+int qd_power_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
+    if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c)
+        if (power_cell_count(dst + c * QD_POWER_WORDS) + power_cell_count(src + c * QD_POWER_WORDS) > kMeanMaxCount)
+            return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
+    for (uint64_t i = 0; i < cells * QD_POWER_WORDS; ++i) dst[i] += src[i];
+    return QD_OK;
+}
+
+int qd_power_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *rms_rows, double *sumsq_rows, uint32_t *count_rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!rms_rows && !sumsq_rows && !count_rows) return fail(QD_ERR_INVALID, "rms_rows, sumsq_rows and count_rows are all NULL");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c) {
+        uint32_t rb, cnt; double s;
+        power_finish_cell(acc + c * QD_POWER_WORDS, &rb, &s, &cnt);
+        if (rms_rows) memcpy(rms_rows + c, &rb, 4);
+        if (sumsq_rows) sumsq_rows[c] = s;
+        if (count_rows) count_rows[c] = cnt;
+    }
+    return QD_OK;
+}
+
+int qd_plan_power(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                  uint64_t pool, float *rms_rows, double *sumsq_rows, uint32_t *count_rows, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_power", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    if (const int rc = pool_given(pool)) return rc;
+    if (!rms_rows && !sumsq_rows && !count_rows) return fail(QD_ERR_INVALID, "rms_rows, sumsq_rows and count_rows are all NULL");
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not power-averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_power_merge)")) return rc;
+    if (const int rc = f.admit()) return rc;
+    if (n_windows == 0) return QD_OK;
+    const uint32_t W = p->W;
+    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
+    if (int rc = f.open()) return rc;
+    Planes planes;                                                   // the outputs: [sumsq][rms][count]
+    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {{sumsq_rows, sumsq_rows ? (size_t)(words * 8) : 0}, {rms_rows, rms_rows ? (size_t)(words * 4) : 0},
+                                                           {count_rows, count_rows ? (size_t)(words * 4) : 0}});
+    if (rc) return rc;
+    const PowerOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev)};
+    // the limb accumulator (qd_power.h) and the batches: walk_limbs
+    LimbSink k;
+    k.words = kPowerWords;
+    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { power_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, power_form(), G, grid, V); };
+    k.fold = [&](const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
+        return launch_power(p, G, grid, V, norms_d, out, acc, cuts, r_base, s);
+    };
+    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_power_finish(p, acc, r_base, n_rows, out, s); };
+    k.fill_empty = [&](hipStream_t s) { return fill_no_values(out.rms, out.sumsq, out.count, words, s); };
+    rc = walk_limbs(f, pool, R, k);
+    if (rc == QD_OK) rc = planes.home(f.st);
     return f.close(rc);
 }
 

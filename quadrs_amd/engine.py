@@ -365,6 +365,43 @@ def mean_finish(acc):
     return mean, total, count
 
 
+def power_init(width, rows):
+    """qd_power_init: the exact sum-of-squares accumulator of `rows` rows of `width` cells, uint64[rows, width, POWER_WORDS], all words 0."""
+    acc = np.empty((int(rows), int(width), _ffi.POWER_WORDS), dtype=np.uint64)
+    check(lib().qd_power_init(_np_ptr(acc), int(width), int(rows)))
+    return acc
+
+
+def power_fold(norms, pool, at=0, into=None):
+    """qd_power_fold: norms rows (n, width) are windows at, at+1, ... of a range and their squares accumulate into rows (at + i) // pool
+    of the accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = power_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
+    check(lib().qd_power_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
+    return into
+
+
+def power_merge(dst, src):
+    """qd_power_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
+    if dst.shape != src.shape:
+        raise ValueError("accumulators of different shapes do not merge")
+    check(lib().qd_power_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
+    return dst
+
+
+def power_finish(acc):
+    """qd_power_finish: (rms float32, sumsq float64, count uint32), [rows, width] each, every cell rounded once from its exact sum of
+    squares."""
+    rows, width = acc.shape[0], acc.shape[1]
+    rms = np.empty((rows, width), dtype=np.float32)
+    total = np.empty((rows, width), dtype=np.float64)
+    count = np.empty((rows, width), dtype=np.uint32)
+    check(lib().qd_power_finish(_np_ptr(acc), width, rows, _np_ptr(rms), _np_ptr(total), _np_ptr(count)))
+    return rms, total, count
+
+
 def density_init(width, levels, rows):
     """qd_density_init: the level counts of `rows` rows of `width` bins, uint32[rows, width, levels], all words 0."""
     counts = np.empty((int(rows), int(width), int(levels)), dtype=np.uint32)
@@ -631,6 +668,13 @@ class Plan:
         each — per bin the exact sum of each group of `pool` consecutive windows of [first_window, +n_windows), rounded once, its mean
         rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch count_rows is int32: the same bits)."""
         return self._fold_rows(lib().qd_plan_mean, ("float32", "float64", "uint32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
+
+    def power(self, src, pool, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None):
+        """qd_plan_power of an EPI_NORMS_F32 plan: (rms_rows float32, sumsq_rows float64, count_rows uint32), [ceil(n_windows / pool), width]
+        each — per bin the root mean square of each group of `pool` consecutive windows of [first_window, +n_windows), rounded once from
+        the exact sum of squares, that sum rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch
+        count_rows is int32: the same bits)."""
+        return self._fold_rows(lib().qd_plan_power, ("float32", "float64", "uint32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
 
     def density(self, src, pool, level0, levels, q=(), first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, counts=True):
         """qd_plan_density of an EPI_NORMS_F32 plan: (count_rows uint32[R, width, levels], trace_rows float32[len(q), R, width]),
