@@ -529,6 +529,65 @@ int qd_plan_power(qd_plan *plan, const void *src, int src_mem, uint64_t src_firs
                   uint64_t first_window, uint64_t n_windows, uint64_t pool,
                   float *rms_rows, double *sumsq_rows, uint32_t *count_rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ deviation-trace rows of a norms plan
+ *
+ * The standard deviation per bin (steady or keyed; the error bar of the average trace; the sigma of a "floor + k sigma" threshold) next
+ * to max hold, min hold, the average of |X| and the power average: over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W and
+ * R = ceil(n / pool) rows grouped exactly as qd_plan_pool, qd_plan_mean and qd_plan_power group them (ragged last row; pool > n acts as
+ * pool = n), per row r and fftshifted bin b over the f32 values v the norms sink writes for the group (a NaN is ignored, the sign bit
+ * is dropped).  With n the count of the non-NaN values, A = sum of v as an integer in units of 2^-149, B = sum of v^2 as an integer in
+ * units of 2^-298 and D = n B - A^2 (never negative, below 2^616):
+ *   count_rows[r W + b]  u32  n, +inf included
+ *   ssd_rows[r W + b]    f64  the sum of squared deviations, sum of (v - mean)^2 = D / n, the EXACT rational rounded once, to nearest,
+ *                             ties to even; 0.0 or a normal f64 (2^-329 ... < 2^287); 0.0 exactly when all values of the cell are equal
+ *                             (n = 1 included).  Divide by n or n - 1 yourself: the library takes no side on Bessel's correction
+ *   std_rows[r W + b]    f32  the population standard deviation sqrt(D) / n, the real number, rounded once to f32, nearest, ties to
+ *                             even, subnormal results included (it is not (float)sqrt(ssd / n)).  It is at most half the group's
+ *                             range, so it never overflows; it may round to +0 with D != 0 (values 0 and one quantum: half a quantum,
+ *                             a tie, rounds to 0)
+ *   mean_rows[r W + b]   f32  bit for bit qd_plan_mean's mean_rows of the same windows and pool
+ *   rms_rows[r W + b]    f32  bit for bit qd_plan_power's rms_rows of the same windows and pool
+ * No values: count 0, ssd 0.0, std / mean / rms the quiet NaN 0x7fc00000.  Any +inf counts, makes mean and rms +inf as in their own
+ * sinks, and makes std 0x7fc00000 and ssd 0x7ff8000000000000: the deviation of a set that holds an infinity is undefined.  pool == 1:
+ * std +0, ssd 0.0, mean and rms |norm| bit for bit wherever the norm is not NaN.  The difference D is taken between two exact
+ * integers, so nothing cancels (sumsq / count - (sum / count)^2 in f64 does, catastrophically), and the results depend on no batch,
+ * chunk, memory kind, launch or arrival order.  A group holds at most 2^31 windows.
+ *
+ * The accumulator is public so that parts and shards merge: rows * width * QD_SPREAD_WORDS caller-owned uint64_t, cell (r, b) at
+ * (r width + b) QD_SPREAD_WORDS.  Words 0-8 are QD_MEAN_WORDS' limbs L[0..8] in units of 2^-149, words 9-26 QD_POWER_WORDS' limbs
+ * L[0..17] in units of 2^-298, each filled by the rule stated there, and word 27 is their count word: the count of finite values plus
+ * the count of +inf values shifted left by 32.  Every word is an integer sum: parts merge by word-wise addition. */
+#define QD_SPREAD_WORDS 28
+/* The result rows of a deviation fold, rows * width values each; any may be NULL, not all. */
+typedef struct qd_spread_rows { float *std_rows; double *ssd_rows; uint32_t *count_rows; float *mean_rows; float *rms_rows; } qd_spread_rows;
+
+/* All words 0: `rows` rows of `width` cells.  QD_ERR_INVALID: acc NULL or width == 0. */
+int qd_spread_init(uint64_t *acc, uint32_t width, uint64_t rows);
+/* The CPU twin of the kernel behind qd_plan_spread, bit for bit: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32 in
+ * `norms`) ACCUMULATE into rows (at + i) / pool of acc, which holds the range's rows from row 0 on.  Parts of a range folded in any
+ * order give the same words.  QD_ERR_INVALID: pool == 0, width == 0, acc NULL, norms NULL with n > 0, or a row whose cells would hold
+ * more than 2^31 values (checked once per row before anything is added: acc is then unchanged). */
+int qd_spread_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n);
+/* dst += src, word-wise.  QD_ERR_INVALID: NULL, width == 0, or a cell's count would pass 2^31 (dst is then unchanged). */
+int qd_spread_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows);
+/* The results of an accumulator into the rows of `out` that are not NULL.  QD_ERR_INVALID: acc NULL, width == 0, out NULL or all of its
+ * rows NULL. */
+int qd_spread_finish(const uint64_t *acc, uint32_t width, uint64_t rows, const qd_spread_rows *out);
+/* The deviation-trace rows of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; every argument as qd_plan_power's, the rows
+ * of `out` (R W values each of out_mem memory; any may be NULL, not all) OVERWRITTEN, the call returning after they are complete.  One
+ * pass over the carrier gives all five; an output whose pointer is NULL is not worked out where that saves work (no root without
+ * std_rows, no division without mean_rows).  A row whose windows one workgroup sees in one batch is rounded in the fold kernel; every
+ * other row goes through a device limb accumulator of at most max(2 chunk_bytes, 224 W bytes), whatever R is, and is rounded by a
+ * second small kernel.
+ * Codes as qd_plan_power: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, pool == 0, pool (clamped to n_windows) above
+ * 2^31, out NULL or all of its rows NULL, or an unknown memory kind; QD_ERR_SHORT past the sink's loop (the outputs are not touched),
+ * and for a cascade's range past qd_plan_complete_windows (every complete window of the range is folded; rows without one hold count
+ * 0, ssd 0.0 and NaNs); QD_ERR_UNSUPPORTED for a plan created with shards (qd_spread_merge per shard's accumulator, or give each
+ * device a contiguous range of ROWS on a plan of its own).  n_windows == 0: QD_OK, nothing is touched. */
+int qd_plan_spread(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                   uint64_t first_window, uint64_t n_windows, uint64_t pool,
+                   const qd_spread_rows *out, int out_mem, void *stream);
+
 /* ------------------------------------------------------------------ percentile traces and persistence counts of a norms plan
  *
  * The trace the average cannot be: a noise floor that one burst, or one +inf, does not drag up — a median, or any percentile, per bin —

@@ -29,11 +29,13 @@ SYMBOLS = [
     "qd_pool_init", "qd_pool_fold", "qd_plan_pool",
     "qd_mean_init", "qd_mean_fold", "qd_mean_merge", "qd_mean_finish", "qd_plan_mean",
     "qd_power_init", "qd_power_fold", "qd_power_merge", "qd_power_finish", "qd_plan_power",
+    "qd_spread_init", "qd_spread_fold", "qd_spread_merge", "qd_spread_finish", "qd_plan_spread",
     "qd_density_init", "qd_density_fold", "qd_density_merge", "qd_density_quantile", "qd_plan_density",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
 POWER_WORDS = 19
+SPREAD_WORDS = 28
 DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
@@ -58,6 +60,11 @@ class PlanInfo(C.Structure):
         ("ratio", C.c_double), ("tile_windows", C.c_uint32), ("threads", C.c_uint32),
         ("lds_bytes", C.c_uint32), ("kernel_kind", C.c_uint32), ("kernel_flags", C.c_uint32), ("_reserved", C.c_uint32),
     ]
+
+
+class SpreadRows(C.Structure):
+    """qd_spread_rows: the five result rows of a deviation fold; a NULL pointer is an output not asked for."""
+    _fields_ = [("std_rows", C.c_void_p), ("ssd_rows", C.c_void_p), ("count_rows", C.c_void_p), ("mean_rows", C.c_void_p), ("rms_rows", C.c_void_p)]
 
 
 class Stage(C.Structure):
@@ -192,6 +199,11 @@ def lib():
             "qd_power_merge": (i32, [vp, vp, C.c_uint32, u64]),
             "qd_power_finish": (i32, [vp, C.c_uint32, u64, vp, vp, vp]),
             "qd_plan_power": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, vp, vp, vp, i32, vp]),
+            "qd_spread_init": (i32, [vp, C.c_uint32, u64]),
+            "qd_spread_fold": (i32, [vp, C.c_uint32, u64, u64, vp, u64]),
+            "qd_spread_merge": (i32, [vp, vp, C.c_uint32, u64]),
+            "qd_spread_finish": (i32, [vp, C.c_uint32, u64, C.POINTER(SpreadRows)]),
+            "qd_plan_spread": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, C.POINTER(SpreadRows), i32, vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_QUANTILES };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -251,11 +251,11 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             v = take(m, "stride", &f);
             op.stride = f ? parse_si_u64(v) : op.width;
             ensure_empty(m);
-        } else if (cmd == "peaks" || cmd == "means" || cmd == "powers") {
+        } else if (cmd == "peaks" || cmd == "means" || cmd == "powers" || cmd == "spreads") {
             // not in the reference's grammar: the spectrum analyser's max-hold picture — every window sparkfft would print, each group of
-            // `pool` consecutive windows folded per bin into one row (qd_plan_pool) — its average trace (qd_plan_mean) and its RMS trace (qd_plan_power)
+            // `pool` consecutive windows folded per bin into one row (qd_plan_pool) — its average trace (qd_plan_mean), its RMS trace (qd_plan_power) and its deviation trace (qd_plan_spread)
             auto m = no_duplicates(raw);
-            op.kind = cmd == "peaks" ? OP_PEAKS : cmd == "means" ? OP_MEANS : OP_POWERS;
+            op.kind = cmd == "peaks" ? OP_PEAKS : cmd == "means" ? OP_MEANS : cmd == "powers" ? OP_POWERS : OP_SPREADS;
             std::string v = take(m, "width", &f);
             op.width = f ? (size_t)parse_si_u64(v) : 128;
             v = take(m, "stride", &f);
@@ -866,7 +866,7 @@ void print_levels(uint64_t rate, const Op &sink, const qd_summary &sum, const st
     printf("peak_bin %zu %.9g\n", best, peak.empty() ? 0.f : peak[best]);
 }
 
-// The fused half of the norms sinks (levels, peaks, means, powers): one unsharded QD_EPI_NORMS_F32 plan per part (-gpus N; a `gen` source: one), made on
+// The fused half of the norms sinks (levels, peaks, means, powers, spreads): one unsharded QD_EPI_NORMS_F32 plan per part (-gpus N; a `gen` source: one), made on
 // that part's device.  part(plan, in, g, parts, complete windows, tile) picks its range of the complete windows and runs it; its status is
 // checked as `what`.  False when the library has no fused plan for the chain: the caller pulls the windows through the iterator chain.
 using NormsPart = std::function<int(qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile)>;
@@ -977,21 +977,27 @@ void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
 // norms of its windows, from their exact sum, rounded once (qd_plan_mean fused; qd_mean_fold + qd_mean_finish through the iterator).
 // The `powers` sink is the picture of the RMS trace, PREFIX.sr{rate}.w{W}x{rows}.rms.pgm: the root of the mean of the squared norms, from
 // their exact sum of squares, rounded once (qd_plan_power fused; qd_power_fold + qd_power_finish through the iterator).
+// The `spreads` sink is the picture of the deviation trace, PREFIX.sr{rate}.w{W}x{rows}.std.pgm: the population standard deviation of the
+// norms of a row's windows, from their exact sum and sum of squares, rounded once (qd_plan_spread fused; qd_spread_fold + qd_spread_finish
+// through the iterator); a NaN norm is ignored, as `means` ignores it.
 struct PeakRows {
     uint64_t windows = 0, pool = 1, rows = 0;
     bool mean = false;                            // `means`: peak holds the mean rows, acc the iterator path's exact sums
     bool power = false;                           // `powers`: peak holds the rms rows, acc the iterator path's exact sums of squares
+    bool spread = false;                          // `spreads`: peak holds the std rows, acc the iterator path's exact sums and sums of squares
+    qd_spread_rows std_at(uint64_t r0, size_t width) { return qd_spread_rows{peak.data() + r0 * width, nullptr, nullptr, nullptr, nullptr}; }
     std::vector<float> peak, floor;
     std::vector<uint64_t> acc;
     void size_for(const Op &sink, uint64_t n) {
         windows = n;
         mean = sink.kind == OP_MEANS;
         power = sink.kind == OP_POWERS;
+        spread = sink.kind == OP_SPREADS;
         pool = sink.pool ? sink.pool : std::max<uint64_t>(1, (n + sink.count - 1) / sink.count);
         if (n && pool > n) pool = n;
         rows = n ? (n - 1) / pool + 1 : 0;
         peak.resize(rows * sink.width);
-        if (mean || power) return;
+        if (mean || power || spread) return;
         floor.resize(rows * sink.width);
         qd_check(qd_pool_init(peak.data(), floor.data(), (uint32_t)sink.width, rows), "pool init");
     }
@@ -999,13 +1005,14 @@ struct PeakRows {
     int run(qd_plan *plan, const void *src, int mem, uint64_t n_samples, uint64_t w0, uint64_t w1, uint64_t r0, size_t width) {
         if (mean) return qd_plan_mean(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, peak.data() + r0 * width, nullptr, nullptr, QD_MEM_HOST, nullptr);
         if (power) return qd_plan_power(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, peak.data() + r0 * width, nullptr, nullptr, QD_MEM_HOST, nullptr);
+        if (spread) { const qd_spread_rows o = std_at(r0, width); return qd_plan_spread(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, &o, QD_MEM_HOST, nullptr); }
         return qd_plan_pool(plan, src, mem, 0, n_samples, w0, w1 - w0, pool, peak.data() + r0 * width, floor.data() + r0 * width, QD_MEM_HOST, nullptr);
     }
 };
 
 bool peaks_fused(const ChainSpec &cs, const Op &sink, PeakRows *out) {
     uint64_t rows_per = 0;
-    return norms_fused(cs, sink, sink.kind == OP_MEANS ? "mean" : sink.kind == OP_POWERS ? "power" : "pool", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
+    return norms_fused(cs, sink, sink.kind == OP_MEANS ? "mean" : sink.kind == OP_POWERS ? "power" : sink.kind == OP_SPREADS ? "spread" : "pool", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
         if (g == 0) {
             out->size_for(sink, complete);
             // ranges of whole rows that start on a tile of windows where the pool allows it, as the library's own shards do
@@ -1026,7 +1033,7 @@ bool peaks_fused(const ChainSpec &cs, const Op &sink, PeakRows *out) {
 void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     const size_t W = sink.width; const uint64_t S = sink.stride;
     check_norms_sink(sink);
-    if (sink.has_range && !(sink.rmax > sink.rmin)) bail(std::string(sink.kind == OP_MEANS ? "means" : sink.kind == OP_POWERS ? "powers" : "peaks") + " -range takes lo:hi with lo < hi");
+    if (sink.has_range && !(sink.rmax > sink.rmin)) bail(std::string(sink.kind == OP_MEANS ? "means" : sink.kind == OP_POWERS ? "powers" : sink.kind == OP_SPREADS ? "spreads" : "peaks") + " -range takes lo:hi with lo < hi");
     PeakRows pr;
     bool done = false;
     if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = peaks_fused(*cs, sink, &pr);
@@ -1046,16 +1053,22 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
             pr.acc.resize(pr.rows * W * QD_POWER_WORDS);
             qd_check(qd_power_init(pr.acc.data(), (uint32_t)W, pr.rows), "power init");
         }
+        if (pr.spread && pr.rows) {
+            pr.acc.resize(pr.rows * W * QD_SPREAD_WORDS);
+            qd_check(qd_spread_init(pr.acc.data(), (uint32_t)W, pr.rows), "spread init");
+        }
         // folded on the host
         std::vector<float> norms;
         for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
             const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
             if (pr.mean) qd_check(qd_mean_fold(pr.acc.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
             else if (pr.power) qd_check(qd_power_fold(pr.acc.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
+            else if (pr.spread) qd_check(qd_spread_fold(pr.acc.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
             else qd_check(qd_pool_fold(pr.peak.data(), pr.floor.data(), (uint32_t)W, pr.pool, w0, norms.data(), nb), "fold");
         }
         if (pr.mean && pr.rows) qd_check(qd_mean_finish(pr.acc.data(), (uint32_t)W, pr.rows, pr.peak.data(), nullptr, nullptr), "mean finish");
         if (pr.power && pr.rows) qd_check(qd_power_finish(pr.acc.data(), (uint32_t)W, pr.rows, pr.peak.data(), nullptr, nullptr), "power finish");
+        if (pr.spread && pr.rows) { const qd_spread_rows o = pr.std_at(0, W); qd_check(qd_spread_finish(pr.acc.data(), (uint32_t)W, pr.rows, &o), "spread finish"); }
     }
     const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "x" + std::to_string(pr.rows);
     const std::string head = "P5\n" + std::to_string(W) + " " + std::to_string(pr.rows) + "\n255\n";
@@ -1063,7 +1076,7 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     std::vector<uint8_t> px(pr.peak.size());
     for (int which = 0; which < (sink.want_floor ? 2 : 1); ++which) {
         const std::vector<float> &rows = which ? pr.floor : pr.peak;
-        const std::string fn = stem + (pr.mean ? ".mean.pgm" : pr.power ? ".rms.pgm" : which ? ".floor.pgm" : ".peak.pgm");
+        const std::string fn = stem + (pr.mean ? ".mean.pgm" : pr.power ? ".rms.pgm" : pr.spread ? ".std.pgm" : which ? ".floor.pgm" : ".peak.pgm");
         int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
         if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
         for (size_t i = 0; i < rows.size(); ++i) {
@@ -1180,6 +1193,7 @@ void usage() {
             "   peaks [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] [-floor no] FILENAME_PREFIX \\\n"
             "   means [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "   powers [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
+            "  spreads [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
@@ -1223,7 +1237,8 @@ int main(int argc, char **argv) {
                     break;
                 case OP_MEANS:
                 case OP_POWERS:
-                    printf("%s width=%zu stride=%llu %s=%llu range=%s\n", op.kind == OP_MEANS ? "means" : "powers", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
+                case OP_SPREADS:
+                    printf("%s width=%zu stride=%llu %s=%llu range=%s\n", op.kind == OP_MEANS ? "means" : op.kind == OP_POWERS ? "powers" : "spreads", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
                            (unsigned long long)(op.pool ? op.pool : op.count), op.has_range ? "yes" : "no");
                     break;
                 case OP_QUANTILES: {
@@ -1287,10 +1302,11 @@ int main(int argc, char **argv) {
                 cs.cascade = !chain_clean;
                 do_levels(*samples, op, &cs);
                 break;
+            case OP_SPREADS:
             case OP_POWERS:
             case OP_MEANS:
             case OP_PEAKS:
-                if (!samples) bail(std::string(op.kind == OP_POWERS ? "powers" : op.kind == OP_MEANS ? "means" : "peaks") + " requires an input");
+                if (!samples) bail(std::string(op.kind == OP_SPREADS ? "spreads" : op.kind == OP_POWERS ? "powers" : op.kind == OP_MEANS ? "means" : "peaks") + " requires an input");
                 cs.cascade = !chain_clean;
                 do_peaks(*samples, op, &cs);
                 break;

@@ -37,6 +37,7 @@
 #include "qd_density.h"
 #include "qd_mean.h"
 #include "qd_power.h"
+#include "qd_spread.h"
 
 using namespace qd;
 
@@ -3592,7 +3593,7 @@ int launch_mean_finish(const qd_plan *p, const MeanAcc &acc, uint64_t r_base, ui
 }
 uint64_t mean_cell_count(const uint64_t *cell) { return (cell[9] & 0xffffffffull) + (cell[9] >> 32); }
 
-// The walk of the sinks that fold through a limb accumulator (qd_plan_mean, qd_plan_power): a fold kernel that rounds whole rows itself
+// The walk of the sinks that fold through a limb accumulator (qd_plan_mean, qd_plan_power, qd_plan_spread): a fold kernel that rounds whole rows itself
 // and adds cut rows into `words` planar u64 a cell, and a finish kernel that rounds the flagged rows.  The sink gives its cell size and
 // four steps; the walk owns the accumulator (workspace slot 1: at most max(2 chunk_bytes, one row), its flags behind it) and the batches.
 struct LimbSink {
@@ -3894,6 +3895,143 @@ int qd_plan_power(qd_plan *p, const void *src, int src_mem, uint64_t src_first, 
     };
     k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_power_finish(p, acc, r_base, n_rows, out, s); };
     k.fill_empty = [&](hipStream_t s) { return fill_no_values(out.rms, out.sumsq, out.count, words, s); };
+    rc = walk_limbs(f, pool, R, k);
+    if (rc == QD_OK) rc = planes.home(f.st);
+    return f.close(rc);
+}
+
+// ------------------------------------------------------------------ deviation-trace rows
+
+namespace {
+struct SpreadOut {
+    float *std; double *ssd; uint32_t *count; float *mean; float *rms;
+    uint32_t want() const { return (std ? kSpreadStd : 0u) | (ssd ? kSpreadSsd : 0u) | (mean ? kSpreadMean : 0u) | (rms ? kSpreadRms : 0u); }
+};
+
+// one batch of norms rows (device memory, 16-byte aligned) into the outputs (whole rows) and the accumulator (cut rows), as launch_mean
+int launch_spread(const qd_plan *p, const PieceGeometry &G, uint64_t grid, const float *norms_d, const SpreadOut &out, const LimbAcc &acc, bool cuts,
+                  uint64_t r_base, hipStream_t st) {
+    if (const int rc = launch_grid(grid, G.nw)) return rc;
+    const uint64_t ra = G.g0 / G.pool, rb = (G.g0 + G.nw - 1) / G.pool;
+    if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
+    SpreadParams M{};
+    M.G = G;
+    M.norms = norms_d;
+    M.std = out.std; M.ssd = out.ssd; M.count = out.count; M.mean = out.mean; M.rms = out.rms; M.want = out.want();
+    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
+    hipLaunchKernelGGL(k_spread, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+int launch_spread_finish(const qd_plan *p, const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, const SpreadOut &out, hipStream_t st) {
+    const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
+    if (!cells) return QD_OK;
+    hipLaunchKernelGGL(k_spread_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
+                       out.want(), out.std, out.ssd, out.count, out.mean, out.rms);
+    HIPCHK(hipGetLastError());
+    return QD_OK;
+}
+uint64_t spread_cell_count(const uint64_t *cell) { return (cell[27] & 0xffffffffull) + (cell[27] >> 32); }
+int spread_rows_given(const qd_spread_rows *out) {
+    if (!out) return fail(QD_ERR_INVALID, "out is NULL");
+    if (!out->std_rows && !out->ssd_rows && !out->count_rows && !out->mean_rows && !out->rms_rows)
+        return fail(QD_ERR_INVALID, "std_rows, ssd_rows, count_rows, mean_rows and rms_rows are all NULL");
+    return QD_OK;
+}
+}  // namespace
+
+int qd_spread_init(uint64_t *acc, uint32_t width, uint64_t rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    memset(acc, 0, (size_t)(rows * width * QD_SPREAD_WORDS * 8));
+    return QD_OK;
+}
+
+int qd_spread_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+    if (const int rc = pool_given(pool)) return rc;
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return spread_cell_count(acc + cell * QD_SPREAD_WORDS); })) return rc;
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        uint64_t *cells = acc + (at + i) / pool * width * QD_SPREAD_WORDS;
+        for (uint32_t b = 0; b < width; ++b) {
+            uint32_t bits;
+            memcpy(&bits, row + b, 4);
+            spread_add(cells + (uint64_t)b * QD_SPREAD_WORDS, bits);
+        }
+    }
+    return QD_OK;
+}
+
+int qd_spread_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
+    if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c)
+        if (spread_cell_count(dst + c * QD_SPREAD_WORDS) + spread_cell_count(src + c * QD_SPREAD_WORDS) > kMeanMaxCount)
+            return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
+    for (uint64_t i = 0; i < cells * QD_SPREAD_WORDS; ++i) dst[i] += src[i];
+    return QD_OK;
+}
+
+int qd_spread_finish(const uint64_t *acc, uint32_t width, uint64_t rows, const qd_spread_rows *out) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (const int rc = spread_rows_given(out)) return rc;
+    const SpreadOut o{out->std_rows, out->ssd_rows, out->count_rows, out->mean_rows, out->rms_rows};
+    const uint32_t want = o.want();
+    const uint64_t cells = rows * width;
+    for (uint64_t c = 0; c < cells; ++c) {
+        SpreadCell r;
+        spread_finish_cell(acc + c * QD_SPREAD_WORDS, want, &r);
+        if (o.std) memcpy(o.std + c, &r.std_bits, 4);
+        if (o.ssd) o.ssd[c] = r.ssd;
+        if (o.count) o.count[c] = r.count;
+        if (o.mean) memcpy(o.mean + c, &r.mean_bits, 4);
+        if (o.rms) memcpy(o.rms + c, &r.rms_bits, 4);
+    }
+    return QD_OK;
+}
+
+int qd_plan_spread(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                   uint64_t pool, const qd_spread_rows *rows, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_spread", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    if (const int rc = pool_given(pool)) return rc;
+    if (const int rc = spread_rows_given(rows)) return rc;
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan's deviation is not taken in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_spread_merge)")) return rc;
+    if (const int rc = f.admit()) return rc;
+    if (n_windows == 0) return QD_OK;
+    const uint32_t W = p->W;
+    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
+    if (int rc = f.open()) return rc;
+    Planes planes;                                                   // the outputs: [ssd][std][count][mean][rms]
+    auto plane = [&](void *u, size_t each) { return Planes::Plane{u, u ? (size_t)(words * each) : 0, nullptr}; };
+    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {plane(rows->ssd_rows, 8), plane(rows->std_rows, 4), plane(rows->count_rows, 4),
+                                                           plane(rows->mean_rows, 4), plane(rows->rms_rows, 4)});
+    if (rc) return rc;
+    const SpreadOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev),
+                        static_cast<float *>(planes.v[3].dev), static_cast<float *>(planes.v[4].dev)};
+    // the limb accumulator (qd_spread.h) and the batches: walk_limbs
+    LimbSink k;
+    k.words = kSpreadWords;
+    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { power_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, 1, G, grid, V); };
+    k.fold = [&](const PieceGeometry &G, uint64_t grid, int, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
+        return launch_spread(p, G, grid, norms_d, out, acc, cuts, r_base, s);
+    };
+    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_spread_finish(p, acc, r_base, n_rows, out, s); };
+    k.fill_empty = [&](hipStream_t s) {
+        if (const int e = fill_no_values(out.std, out.ssd, out.count, words, s)) return e;
+        if (const int e = fill_no_values(out.mean, nullptr, nullptr, words, s)) return e;
+        return fill_no_values(out.rms, nullptr, nullptr, words, s);
+    };
     rc = walk_limbs(f, pool, R, k);
     if (rc == QD_OK) rc = planes.home(f.st);
     return f.close(rc);

@@ -402,6 +402,61 @@ def power_finish(acc):
     return rms, total, count
 
 
+SPREAD_OUTPUTS = ("std", "ssd", "count", "mean", "rms")
+_SPREAD_DTYPES = {"std": "float32", "ssd": "float64", "count": "uint32", "mean": "float32", "rms": "float32"}
+
+
+def _spread_wanted(outputs):
+    want = SPREAD_OUTPUTS if outputs is None else tuple(outputs)
+    if any(o not in SPREAD_OUTPUTS for o in want):
+        raise ValueError("outputs are named from %r" % (SPREAD_OUTPUTS,))
+    return [o for o in SPREAD_OUTPUTS if o in want]
+
+
+def _spread_rows(ptr_of):
+    """a qd_spread_rows whose pointers come from ptr_of (output name -> address or None)"""
+    def addr(p):
+        return p.value if isinstance(p, C.c_void_p) else p
+    return _ffi.SpreadRows(*[addr(ptr_of.get(o)) for o in SPREAD_OUTPUTS])
+
+
+def spread_init(width, rows):
+    """qd_spread_init: the exact sum and sum-of-squares accumulator of `rows` rows of `width` cells, uint64[rows, width, SPREAD_WORDS], all
+    words 0."""
+    acc = np.empty((int(rows), int(width), _ffi.SPREAD_WORDS), dtype=np.uint64)
+    check(lib().qd_spread_init(_np_ptr(acc), int(width), int(rows)))
+    return acc
+
+
+def spread_fold(norms, pool, at=0, into=None):
+    """qd_spread_fold: norms rows (n, width) are windows at, at+1, ... of a range; they and their squares accumulate into rows
+    (at + i) // pool of the accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = spread_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
+    check(lib().qd_spread_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
+    return into
+
+
+def spread_merge(dst, src):
+    """qd_spread_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
+    if dst.shape != src.shape:
+        raise ValueError("accumulators of different shapes do not merge")
+    check(lib().qd_spread_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
+    return dst
+
+
+def spread_finish(acc, outputs=None):
+    """qd_spread_finish: (std float32, ssd float64, count uint32, mean float32, rms float32), [rows, width] each, every cell rounded once
+    from its exact sums.  outputs: the names to work out (SPREAD_OUTPUTS; the default is all); the others are None."""
+    rows, width = acc.shape[0], acc.shape[1]
+    out = {o: np.empty((rows, width), dtype=_SPREAD_DTYPES[o]) for o in _spread_wanted(outputs)}
+    r = _spread_rows({o: _np_ptr(a) for o, a in out.items()})
+    check(lib().qd_spread_finish(_np_ptr(acc), width, rows, C.byref(r)))
+    return tuple(out.get(o) for o in SPREAD_OUTPUTS)
+
+
 def density_init(width, levels, rows):
     """qd_density_init: the level counts of `rows` rows of `width` bins, uint32[rows, width, levels], all words 0."""
     counts = np.empty((int(rows), int(width), int(levels)), dtype=np.uint32)
@@ -675,6 +730,23 @@ class Plan:
         the exact sum of squares, that sum rounded once, and the number of non-NaN values.  src and device_out as for pool (a torch
         count_rows is int32: the same bits)."""
         return self._fold_rows(lib().qd_plan_power, ("float32", "float64", "uint32"), src, pool, first_window, n_windows, src_first, pinned, device_out)
+
+    def spread(self, src, pool, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, outputs=None):
+        """qd_plan_spread of an EPI_NORMS_F32 plan: (std_rows float32, ssd_rows float64, count_rows uint32, mean_rows float32, rms_rows
+        float32), [ceil(n_windows / pool), width] each — per bin of each group of `pool` consecutive windows of [first_window, +n_windows)
+        the population standard deviation rounded once from the exact sum and sum of squares, the sum of squared deviations rounded once,
+        the number of non-NaN values, and Plan.mean's mean and Plan.power's rms bit for bit, from one pass.  src and device_out as for
+        pool (a torch count_rows is int32: the same bits).  outputs: the names to work out (SPREAD_OUTPUTS; the default is all); the
+        others are None and cost nothing."""
+        names = _spread_wanted(outputs)
+
+        def call(h, ptr, mem, src_first, count, first_window, n_windows, pool, *rest):
+            ptrs, (out_mem, st) = rest[:-2], rest[-2:]
+            r = _spread_rows(dict(zip(names, ptrs)))
+            return lib().qd_plan_spread(h, ptr, mem, src_first, count, first_window, n_windows, pool, C.byref(r), out_mem, st)
+        out = dict(zip(names, self._fold_rows(call, tuple(_SPREAD_DTYPES[o] for o in names), src, pool, first_window, n_windows, src_first,
+                                              pinned, device_out)))
+        return tuple(out.get(o) for o in SPREAD_OUTPUTS)
 
     def density(self, src, pool, level0, levels, q=(), first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, counts=True):
         """qd_plan_density of an EPI_NORMS_F32 plan: (count_rows uint32[R, width, levels], trace_rows float32[len(q), R, width]),

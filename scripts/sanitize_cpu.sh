@@ -4,7 +4,9 @@
 #   2. the C++ driver's parser and Samples classes (quadrs_amd/cli/quadrs_hip_cli.cpp) built with g++ -fsanitize=address,undefined,
 #      the CPU half of tests/test_cli.py under it (grammar, filename guessing, errors before any kernel);
 #   3. the host side of the C ABI (quadrs_hip.hip: validation, plan bookkeeping, taps / FFT layout, partitioning) built by hipcc with
-#      host-only instrumentation (-fsanitize=address,undefined -fno-gpu-sanitize), tests/test_abi_cpu.py under it.
+#      host-only instrumentation (-fsanitize=address,undefined -fno-gpu-sanitize), tests/test_abi_cpu.py under it;
+#   4. the deviation cell's arithmetic (quadrs_amd/csrc/qd_spread.h, and qd_mean.h / qd_power.h under it) in a stand-alone program,
+#      scripts/spread_host_check.cpp, built with g++ -fsanitize=address,undefined: planted and random cells against its own big-integer referee.
 # Runs in the GPU-less container; prints one summary line per leg.  usage: scripts/sanitize_cpu.sh [outdir]
 set -u
 cd "$(dirname "$0")/.."
@@ -51,5 +53,11 @@ if [ $ok = 1 ]; then
 else
   echo "   instrumented build of the ABI library failed (see $out/abi_build_*.log): leg skipped"; status=1
 fi
+echo "== 4. qd_spread.h in a stand-alone program under ASan + UBSan"
+g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wextra -o "$out/spread_host_check" \
+    scripts/spread_host_check.cpp || status=1
+timeout 600 "$out/spread_host_check" 4000 > "$out/spread.log" 2>&1
+rc=$?; tail -1 "$out/spread.log"; [ $rc -ne 0 ] && status=1
+grep -c "ERROR: AddressSanitizer\|runtime error:" "$out/spread.log" | sed 's/^/   sanitizer reports: /'
 echo "sanitize_cpu: $([ $status = 0 ] && echo clean || echo FAILED)"
 exit $status
