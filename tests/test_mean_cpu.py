@@ -136,12 +136,12 @@ def f32_bits(x):
     return int(np.asarray(x, dtype=F32).view(np.uint32))
 
 
-def test_planted_rounding_cases(engine):
+def _planted_cases():
     one, eps = 0x3F800000, 1                                    # 1.0 and one unit in its last place (2^-23)
     p100, p47 = f32_bits(2.0 ** 100), f32_bits(2.0 ** 47)
     nan, ninf = NAN_BITS, INF_BITS
     # column -> (values, expected mean bits or None, expected f64 sum or None, expected count)
-    cases = [
+    return [
         ([one, one + eps], one, None, 2),                                           # mean tie -> 1.0 (even)
         ([one + eps, one + 2 * eps], one + 2 * eps, None, 2),                       # mean tie -> 1 + 2^-22 (even)
         ([1, 0], 0, 2.0 ** -149, 2),                                                # 2^-150 -> 0
@@ -155,6 +155,13 @@ def test_planted_rounding_cases(engine):
         ([0x80000000], 0, 0.0, 1),                                                  # -0.0 counts as 0.0
         ([0x80000000 | one, one], one, 2.0, 2),                                     # the sign bit is dropped
     ]
+
+
+PLANTED_CASES = _planted_cases()                # shared with the GPU's planted streams (tests/util.py, planted_cells)
+
+
+def test_planted_rounding_cases(engine):
+    cases, nan = PLANTED_CASES, NAN_BITS
     rows = np.full((3, len(cases)), nan, dtype=np.uint32)
     for c, (vals, *_) in enumerate(cases):
         rows[:len(vals), c] = vals

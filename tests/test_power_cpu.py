@@ -128,9 +128,12 @@ def test_fold_and_finish_match_the_referee(engine, referee, W, pool):
         assert (got[2] == keep).all() and (got[0].view(np.uint32)[~keep] == NAN_BITS).all() and not got[1][~keep].any()
 
 
+VALUE_CLASSES = [0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000, 0x7F7FFFFF, 0xFF7FFFFF,
+                 0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7F800000, 0xFF800000, 0x3F800000, 0x3FC00001]
+
+
 def test_pool_one_identities_over_the_value_classes(engine):
-    vals = [0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000, 0x7F7FFFFF, 0xFF7FFFFF,
-            0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7F800000, 0xFF800000, 0x3F800000, 0x3FC00001]
+    vals = VALUE_CLASSES
     a = np.array([vals], dtype=np.uint32)
     rms, total, count = engine.power_finish(engine.power_fold(a.view(F32), 1))
     for c, b in enumerate(vals):
@@ -167,7 +170,7 @@ def shortcut_rms(vals):
     return int(F32(math.sqrt(s / len(vals))).view(np.uint32))
 
 
-def test_planted_rounding_cases(engine):
+def _planted_cases():
     x1, x3 = (100 << 23) | 1, (100 << 23) | 3
     tie = [x1] * 9 + [0] * 7                                       # root 3 x / 4 exactly: halfway between two f32
     trap = [x3] * 9 + [0] * 6 + [(40 << 23) | 0x123456]            # just above a tie, by less than f64 sees
@@ -177,6 +180,21 @@ def test_planted_rounding_cases(engine):
     cases = [tie, trap, [1, 0, 0, 0], [3, 0, 0, 0], [5, 0, 0, 0], [7, 0, 0, 0], [MAX_BITS] * 3, running, ends, [MAX_BITS, MAX_BITS, 1],
              [NAN_BITS, NAN_BITS | 0x80000000], [0x3F800000, INF_BITS, NAN_BITS], [0x80000000], [0xBF800000, 0x3F800000]]
     want_rms = [0x31C00002, 0x31C00005, 0, 2, 2, 4, MAX_BITS, None, None, None, NAN_BITS, INF_BITS, 0, 0x3F800000]
+    return cases, want_rms
+
+
+# shared with the GPU's planted streams (tests/util.py, planted_cells)
+PLANTED_CASES, PLANTED_WANT_RMS = _planted_cases()
+TRAP, TRAP_SHORTCUT_RMS = PLANTED_CASES[1], 0x31C00004            # what the f64 shortcut gives for the trap
+# an exact f64 tie in the highest limb that only the lowest limb breaks: the sticky bit crosses all of them
+P127, P100 = 254 << 23, 227 << 23                                 # 2^127 and 2^100: squares 2^254 and 2^200, twice the latter half an ulp
+PLANTED_TIES = [[P127, P100, P100], [P127, P100, P100, 1], [P127, P100, P100, P100]]
+PLANTED_TIES_SUMSQ = [2.0 ** 254, 2.0 ** 254 + 2.0 ** 202, 2.0 ** 254 + 2.0 ** 202]
+
+
+def test_planted_rounding_cases(engine):
+    cases, want_rms = PLANTED_CASES, PLANTED_WANT_RMS
+    trap, running = TRAP, PLANTED_CASES[7]
     got, acc = fold_cells(engine, cases)
     for c, vals in enumerate(cases):
         ref = ref_cell(vals)
@@ -184,7 +202,7 @@ def test_planted_rounding_cases(engine):
         assert want_rms[c] is None or got[c][0] == want_rms[c], (c, hex(got[c][0]))
         assert not math.copysign(1.0, got[c][1]) < 0
     # the trap discriminates: the f64 shortcut rounds it the other way (and gets the plain tie's neighbour right)
-    assert shortcut_rms(trap) == 0x31C00004 and got[1][0] == 0x31C00005
+    assert shortcut_rms(trap) == TRAP_SHORTCUT_RMS == 0x31C00004 and got[1][0] == 0x31C00005
     # the top of the range: the sum of squares of three largest values is finite in f64
     assert math.isfinite(got[6][1]) and got[6][1] == 3 * float(np.uint32(MAX_BITS).view(F32)) ** 2
     # a running f64 sum of squares in window order is not the exact one
@@ -195,21 +213,20 @@ def test_planted_rounding_cases(engine):
     assert s != got[7][1] and got[7][1] == math.ldexp(float(exact_sumsq(running)), -298)
     # the first and the last limb of one cell both hold bits, and the lowest one decides the sticky bit of the f64
     assert acc[0, 8, 0] != 0 and acc[0, 8, 17] != 0 and not acc[0, 8, 1:15].any()
-    # an exact f64 tie in the highest limb that only the lowest limb breaks: the sticky bit crosses all of them
-    p127, p100 = 254 << 23, 227 << 23                             # 2^127 and 2^100: squares 2^254 and 2^200, twice the latter half an ulp
-    ties = [[p127, p100, p100], [p127, p100, p100, 1], [p127, p100, p100, p100]]
+    ties = PLANTED_TIES
     tie_sum, acc2 = fold_cells(engine, ties)
     assert tie_sum[0][1] == 2.0 ** 254 and tie_sum[1][1] == 2.0 ** 254 + 2.0 ** 202 and tie_sum[2][1] == 2.0 ** 254 + 2.0 ** 202
+    assert [t[1] for t in tie_sum] == PLANTED_TIES_SUMSQ
     assert acc2[0, 1, 0] == 1 and acc2[0, 1, 17] != 0
     for c, vals in enumerate(ties):
         assert tie_sum[c] == ref_cell(vals)
 
 
-def test_random_cells_match_the_referee(engine):
+def random_cells(n_cells=300, seed=2024):
     """cells of every size class with exponents drawn wide and narrow, so that candidates start at either side of their root"""
-    rng = np.random.default_rng(2024)
+    rng = np.random.default_rng(seed)
     cases = []
-    for i in range(300):
+    for i in range(n_cells):
         n = int(rng.choice([1, 2, 3, 4, 5, 7, 16, 33]))
         e0 = int(rng.integers(0, 255))
         spread = int(rng.choice([0, 1, 3, 30]))
@@ -218,6 +235,13 @@ def test_random_cells_match_the_referee(engine):
         if i % 3 == 0:
             m &= np.uint32(0x7)                                     # short mantissas: exact squares and ties happen
         cases.append([int(x) for x in (e << 23) | m])
+    return cases
+
+
+def test_random_cells_match_the_referee(engine):
+    """random_cells(): 300 cells, seed 2024"""
+    cases = random_cells()
+    assert len(cases) == 300
     got, _ = fold_cells(engine, cases)
     for c, vals in enumerate(cases):
         assert got[c] == ref_cell(vals), (c, [hex(v) for v in vals])

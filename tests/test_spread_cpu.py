@@ -186,7 +186,7 @@ def one_pass_variance(vals):
     return q / len(vals) - (s / len(vals)) ** 2
 
 
-def test_planted_cells(engine):
+def _planted_cells():
     pair24 = [0x4B7FFFFE, 0x4B7FFFFF] * 2048
     pair_sqrt2 = [0x3FB504F3, 0x3FB504F4] * 1500
     pair_max = [0x7F7FFFFE, 0x7F7FFFFF] * 2048
@@ -195,6 +195,17 @@ def test_planted_cells(engine):
     equal = [[b] * k for b in (0, 1, 0x00800000, 0x3F800000, 0x4B7FFFFF, MAX_BITS) for k in (1, 2, 7)]
     others = [[0x3F800000], [0x80000000, 0], [0xBF800000, 0x3F800000, 0xC0000000], [NAN_BITS, 0x3F800000, 0xFFC00001, 0x40000000],
               [0x3F800000, INF_BITS, 0x40000000], [0xFF800000], [NAN_BITS, NAN_BITS | 0x80000000], []]
+    return cases, want, equal, others
+
+
+# shared with the GPU's planted streams (tests/util.py, planted_cells)
+PLANTED_CASES, PLANTED_WANT, PLANTED_EQUAL, PLANTED_OTHERS = _planted_cells()
+PAIR24_SSD = 1024.0                              # the 2^24 pair's sum of squared deviations
+
+
+def test_planted_cells(engine):
+    cases, want, equal, others = PLANTED_CASES, PLANTED_WANT, PLANTED_EQUAL, PLANTED_OTHERS
+    pair24, pair_sqrt2 = cases[5], cases[6]
     got, _ = fold_cells(engine, cases + equal + others)
     for c, vals in enumerate(cases + equal + others):
         assert got[c] == ref_cell(vals), (c, [hex(x) for x in got[c]], [hex(x) for x in ref_cell(vals)])
@@ -203,7 +214,7 @@ def test_planted_cells(engine):
     for c in range(len(cases), len(cases) + len(equal)):
         assert got[c][0] == 0 and got[c][1] == 0                     # all equal: std +0, ssd 0.0
     # the 2^24 pair: sigma is 0.5 exactly, the sum of squared deviations 1024, and the running f64 formula goes negative
-    assert got[5][1] == f64_bits(1024.0) and one_pass_variance(pair24) < 0
+    assert got[5][1] == f64_bits(PAIR24_SSD) == f64_bits(1024.0) and one_pass_variance(pair24) < 0
     # the sqrt(2) pair: the one-pass formula is off by a factor of seven
     v = one_pass_variance(pair_sqrt2)
     assert got[6][0] == 0x33800000 and int(F32(math.sqrt(v)).view(np.uint32)) == 0x34600000
@@ -213,11 +224,11 @@ def test_planted_cells(engine):
     assert tail[6] == (NAN_BITS, 0, 0) and tail[7] == (NAN_BITS, 0, 0)
 
 
-def test_random_cells_match_the_referee(engine):
-    """300 cells of 2, 3, 17 and 100 values whose exponents lie within three binades of a random one"""
-    rng = np.random.default_rng(2025)
+def random_cells(n_cells=300, seed=2025):
+    """cells of 2, 3, 17 and 100 values whose exponents lie within three binades of a random one"""
+    rng = np.random.default_rng(seed)
     cases = []
-    for i in range(300):
+    for i in range(n_cells):
         n = (2, 3, 17, 100)[i % 4]
         e0 = int(rng.integers(0, 255))
         e = np.clip(e0 + rng.integers(0, 4, n), 0, 254).astype(np.uint32)
@@ -225,6 +236,13 @@ def test_random_cells_match_the_referee(engine):
         if i % 5 == 0:
             m &= np.uint32(0x7)                                     # short mantissas: exact roots and ties happen
         cases.append([int(x) for x in (e << 23) | m])
+    return cases
+
+
+def test_random_cells_match_the_referee(engine):
+    """random_cells(): 300 cells, seed 2025"""
+    cases = random_cells()
+    assert len(cases) == 300
     got, _ = fold_cells(engine, cases)
     for c, vals in enumerate(cases):
         assert got[c] == ref_cell(vals), (c, [hex(v) for v in vals])

@@ -1402,3 +1402,135 @@ BUCKET_ORDER_CASES = [
     BucketOrderCase("cascade-w128", _CASC, 128, 128, 100, _fam(part="qd::k_cascade<0>"), sr=2_000_000),
     BucketOrderCase("two-stage-w1024", [_CFG3P], 1024, 1024, 40, _fam(part="two stages:"), seed=20261019),      # (the table's seed: no exact tie in 40 windows)
 ]
+
+
+# ------------------------------------------------------------------ planted-value streams (test_planted_streams_cpu.py, test_gpu_planted.py)
+#
+# A cf32 window whose first sample is (a, 0) and whose other samples are +0 has the norm |a| in every bin, bit for bit (the transform adds
+# and multiplies zeros only).  A stream of such windows lets a test choose the f32 pattern that every bin's cell of a fold receives, window
+# by window; a "cell case" is a run of `depth` consecutive windows folded with pool = depth, so every bin of output row c holds case c.
+
+PLANT_NAN, PLANT_INF, PLANT_MAX = 0x7FC00000, 0x7F800000, 0x7F7FFFFF
+PLANTED_WIDTHS = (1, 4, 128, 256, 2048)          # where pool_geometry / power_geometry change V, lanes per window, pieces per workgroup, slabs
+PLANTED_DEPTHS = (4, 16, 64, 4096)               # pool == depth; 4096 at W <= 4 only
+PLANTED_CAP = 32 << 20                           # bytes a planted stream stays below (its norms are half of it)
+PLANTED_SMALL_CHUNK = 1 << 16                    # chunk_bytes of the second plan
+PLANTED_SR = 21_000_000
+
+
+def impulse_stream(bits, W):
+    """The cf32 bytes of len(bits) + 1 windows of W samples: window i is ((f32 of bits[i]), 0) followed by +0 samples, so that its norms
+    are that pattern in all W bins; the trailing window is zeros (the sink's loop is `while i < len - W`).  A NaN pattern plants a NaN
+    window (every bin NaN).  Signs are not planted: a norm is never negative, so what the folds do with a sign bit (or with a NaN's
+    payload) stays a matter of the CPU twins' tests."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    assert ((bits <= PLANT_INF) | (bits == PLANT_NAN)).all(), "an impulse plants non-negative values, +inf and the quiet NaN only"
+    x = np.zeros((bits.size + 1, int(W), 2), dtype=np.uint32)
+    x[:-1, 0, 0] = bits
+    return x.tobytes()
+
+
+def cases_stream(cases, depth, W):
+    """(bytes, uint32[len(cases), depth]) of the impulse stream whose windows [c depth, (c + 1) depth) hold the values of cases[c] followed
+    by NaN windows (a NaN adds nothing to any fold)"""
+    m = np.full((len(cases), int(depth)), PLANT_NAN, dtype=np.uint32)
+    for c, vals in enumerate(cases):
+        assert len(vals) <= depth
+        m[c, :len(vals)] = vals
+    return impulse_stream(m, W), m
+
+
+def plantable(cell):
+    """whether an impulse stream can hold the cell: no sign bit and no NaN other than the quiet one"""
+    return all(b <= PLANT_INF or b == PLANT_NAN for b in cell)
+
+
+def exponent_sweep():
+    """for every biased exponent e = 0 ... 254 the cells [e<<23 | 1], [e<<23 | 0x7FFFFF] * 3 and a pair one exponent apart — an addend in
+    every limb at every shift s & 31 (2 s & 31 for the squares), pairs that straddle a limb boundary included — and cells that mix the
+    exponents 0 / 1 with 254: bits in the first and in the last limb of one cell"""
+    cells = []
+    for e in range(255):
+        lo, hi = (e << 23) | 1, (e << 23) | 0x7FFFFF
+        cells += [[lo], [hi] * 3, [hi, (min(e + 1, 254) << 23) | 1]]
+    top = 254 << 23
+    cells += [[1, top | 1], [0x7FFFFF, top | 0x7FFFFF, 1], [(1 << 23) | 1, top | 0x7FFFFF], [top | 0x7FFFFF, 1, (1 << 23) | 0x7FFFFF, 3]]
+    return cells
+
+
+def bucket_sweep():
+    """for every bucket k = 0 ... 2040 of the summary's scale (bits >> 20) its two ends k << 20 and (k << 20) | 0xFFFFF; bucket 2040 holds
+    +inf alone.  uint32[4081], ascending"""
+    k = np.arange(2040, dtype=np.uint32) << 20
+    return np.concatenate([np.stack([k, k | np.uint32(0xFFFFF)], axis=1).reshape(-1), np.array([PLANT_INF], np.uint32)])
+
+
+_PLANTED = {}
+
+
+def planted_cells():
+    """(discriminating, rest): the cell cases of the GPU's planted streams.  `discriminating` are the planted rounding cases of the three
+    CPU fold tests, in their order (power's, its ties, the mean's, the spread's); `rest` is exponent_sweep() and the random cells of the
+    CPU generators (2000 of test_power_cpu's, 400 of test_spread_cpu's, their seeds).  Left out, because an impulse cannot plant a sign bit
+    or a NaN payload: the mean's [nan, -nan, nan], [-0.0], [-1.0, 1.0]; the power's [nan, -nan], [-0.0], [-1.0, 1.0]; the spread's
+    [-0.0, 0], [-1, 1, -2], [nan, 1, 0xFFC00001, 2], [-inf], [nan, -nan] (0x80000000, 0xBF800000, 0xC0000000, 0xFF800000, 0xFFC00000,
+    0xFFC00001).  The all-NaN group stays: the spread's empty cell is NaN windows only."""
+    if "cells" not in _PLANTED:
+        import test_mean_cpu as M
+        import test_power_cpu as P
+        import test_spread_cpu as S
+        first = P.PLANTED_CASES + P.PLANTED_TIES + [c[0] for c in M.PLANTED_CASES] + S.PLANTED_CASES + S.PLANTED_EQUAL + S.PLANTED_OTHERS
+        first = [list(c) for c in first if plantable(c)]
+        rest = exponent_sweep() + P.random_cells(2000) + S.random_cells(400)
+        assert all(plantable(c) for c in rest)
+        _PLANTED["cells"] = (first, rest)
+    return _PLANTED["cells"]
+
+
+def planted_depths(W):
+    return [d for d in PLANTED_DEPTHS if d <= 64 or W <= 4]
+
+
+def planted_case_set(W, depth):
+    """The cells of the stream (W, depth), as many as PLANTED_CAP holds: every discriminating cell of at most `depth` values first, then
+    the other cells whose smallest depth this is, then those that a smaller depth holds too; where one of the two groups has to be cut,
+    its members are taken at even distances (the sweep keeps its span of exponents)."""
+    key = (W, depth)
+    if key not in _PLANTED:
+        first, rest = planted_cells()
+        below = max([d for d in PLANTED_DEPTHS if d < depth] + [0])
+        room = (PLANTED_CAP // (8 * W) - 1) // depth
+        cells = [c for c in first if len(c) <= depth][:room]
+        for group in ([c for c in rest if below < len(c) <= depth], [c for c in rest if len(c) <= below]):
+            m = min(len(group), room - len(cells))
+            cells += [group[i * len(group) // m] for i in range(m)]
+        _PLANTED[key] = cells
+    return _PLANTED[key]
+
+
+def planted_small_batch(W):
+    """windows in a batch of a host-source fold of a cf32 plan of width W = stride with chunk_bytes = PLANTED_SMALL_CHUNK: quadrs_hip.hip,
+    Fold::host gives walk_host bytes_per_window = max(S D 8, W 4) = 8 W, and chunk_windows divides chunk_bytes by it (a whole number of
+    the kernel's tiles of `tile_windows`, which the GPU tests check divides it)"""
+    return PLANTED_SMALL_CHUNK // (8 * W)
+
+
+PLANTED_GRIDS = [(0, 256), (1000, 64), (2041 - 256, 256), (1500, 1)]        # (level0, L) of the density tests
+
+
+def bucket_sweep_parts(W):
+    """bucket_sweep() in as few consecutive parts as PLANTED_CAP allows at width W, each but the last of an even number of windows, so
+    that pool = 2 keeps the two ends of a bucket in one row"""
+    b = bucket_sweep()
+    room = (PLANTED_CAP // (8 * W) - 1) // 2 * 2
+    return [b[at:at + room] for at in range(0, b.size, room)]
+
+
+def density_pair_buckets(level0, L, W):
+    """the buckets whose two ends a pool = 2 density test plants at width W on the grid (level0, L): two on either side of both grid
+    edges (so both clamps are hit where the scale has buckets outside the grid) and interior ones at even distances, as many rows as keep
+    the counts [rows, W, L] within 16 MiB (at least 8)"""
+    rows = min(max(8, (16 << 20) // (W * L * 4)), L + 4)
+    edge = [k for k in (level0 - 2, level0 - 1, level0, level0 + 1, level0 + L - 2, level0 + L - 1, level0 + L, level0 + L + 1) if 0 <= k <= 2040]
+    inner = [level0 + 2 + i * max(L - 4, 0) // max(rows - 8, 1) for i in range(max(rows - 8, 0))]
+    return sorted(set(edge) | {k for k in inner if level0 <= k < level0 + L and k <= 2040})
