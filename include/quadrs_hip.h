@@ -646,6 +646,52 @@ int qd_plan_density(qd_plan *plan, const void *src, int src_mem, uint64_t src_fi
                     uint64_t first_window, uint64_t n_windows, uint64_t pool, uint32_t level0, uint32_t levels,
                     uint32_t *count_rows, const double *q, uint32_t n_q, float *trace_rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ band traces of a norms plan
+ *
+ * The folds above reduce over time, per bin.  This one reduces over FREQUENCY, per window: for every window and each of K chosen ranges
+ * of bins it gives the level in the band, the band's peak and where the peak sits, and which band is the loudest — the OOK envelope, an
+ * N-FSK demodulator without re-centring (what `bucket -by freq N` would be), several channels out of one transform, the peak track.
+ * Over windows [w0, w0+n) of a QD_EPI_NORMS_F32 plan of width W and K bands [lo_k, hi_k) of fftshifted bins (0 <= lo < hi <= W; bands may
+ * overlap or repeat), on exactly the f32 values the norms sink writes; window i of the range and band k are at index i K + k:
+ *   count_rows     u32  the band's non-NaN values, +inf included
+ *   sum_rows       f64  the exact sum of the band's values, rounded once;  no values: 0.0;  any +inf: +inf
+ *   level_rows     f32  sum / count, rounded once;  no values: the quiet NaN 0x7fc00000;  any +inf: +inf.  The three are bit for bit
+ *                       qd_mean_finish(qd_mean_fold(...)) of the band's values laid out as hi - lo windows of width 1 with pool = hi - lo.
+ *   peak_rows      f32  the f32::max fold from 0.0 by qd_plan_pool's rule: a NaN is ignored, the sign bit is dropped
+ *   peak_bin_rows  u32  the lowest fftshifted bin of the band whose value equals the peak;  QD_BAND_NONE when count == 0
+ *   pick_rows      u8   at index i: the lowest k with the greatest level_rows among the window's bands with count > 0 (such levels are
+ *                       non-negative or +inf and compare as bit patterns);  255 when no band of the window holds a value.  It is
+ *                       computable from level_rows and count_rows alone.
+ * Every output is an integer sum, an integer max or a function of them: no batch, chunk, memory kind or launch order changes a bit.  A
+ * one-bin band returns the norm itself: level == norm, sum == (double)norm, count == 1, peak == norm, peak_bin == lo. */
+#define QD_BANDS_MAX 255
+#define QD_BAND_NONE 0xffffffffu
+typedef struct qd_band { uint32_t lo, hi; } qd_band;   /* fftshifted bins [lo, hi), 0 <= lo < hi <= W; bands may overlap or repeat */
+/* The result rows of a band fold; a NULL pointer is an output that is not asked for. */
+typedef struct qd_band_rows { float *level_rows; double *sum_rows; uint32_t *count_rows;
+                              float *peak_rows; uint32_t *peak_bin_rows; uint8_t *pick_rows; } qd_band_rows;
+
+/* The CPU twin of the kernels behind qd_plan_bands, bit for bit: n rows of `width` host f32 into the n x n_bands rows of `out`, which are
+ * OVERWRITTEN.  Windows are independent, so the call is stateless: there is no _init / _merge / _finish.  QD_ERR_INVALID: width == 0,
+ * n_bands 0 or above QD_BANDS_MAX, bands NULL, a band with lo >= hi or hi > width, out NULL or all of its rows NULL, norms NULL with
+ * n > 0.  n == 0: QD_OK, nothing is touched. */
+int qd_bands_fold(const float *norms, uint32_t width, uint64_t n, const qd_band *bands, uint32_t n_bands, const qd_band_rows *out);
+/* The band traces of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and `stream` as for
+ * qd_plan_run (device, host and pinned sources).  The rows of `out` are of out_mem memory (host, pinned or device), n_windows x n_bands
+ * each (pick_rows: n_windows), are OVERWRITTEN, and the call returns after they are complete; any may be NULL, not all.  pick_rows needs
+ * neither level_rows nor count_rows.  `bands` is host memory and is read before the call returns.  The windows go batch by batch through
+ * the plan's own kernel into a device carrier of at most max(chunk_bytes, one tile of windows) of norms and are folded there; rows that
+ * are not device memory (and the two pick_rows is read from, when they are not asked for) go through a workspace that is copied down
+ * once and may not exceed 1 GiB — QD_ERR_UNSUPPORTED, and the caller walks the range in spans of windows.
+ * Other codes as qd_plan_pool: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, n_bands 0 or above QD_BANDS_MAX, bands NULL, a
+ * band with lo >= hi or hi > W, out NULL or all of its rows NULL, or an unknown memory kind; QD_ERR_SHORT past the sink's loop (the
+ * outputs are not touched), and for a cascade's range past qd_plan_complete_windows (every complete window of the range is folded; the
+ * rest hold count 0, sum 0.0, level NaN, peak 0.0, QD_BAND_NONE and pick 255); QD_ERR_UNSUPPORTED for a plan created with shards (one plan
+ * per contiguous range of windows: the rows simply concatenate).  n_windows == 0: QD_OK, nothing is touched. */
+int qd_plan_bands(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                  uint64_t first_window, uint64_t n_windows, const qd_band *bands, uint32_t n_bands,
+                  const qd_band_rows *out, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

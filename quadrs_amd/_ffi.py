@@ -31,12 +31,14 @@ SYMBOLS = [
     "qd_power_init", "qd_power_fold", "qd_power_merge", "qd_power_finish", "qd_plan_power",
     "qd_spread_init", "qd_spread_fold", "qd_spread_merge", "qd_spread_finish", "qd_plan_spread",
     "qd_density_init", "qd_density_fold", "qd_density_merge", "qd_density_quantile", "qd_plan_density",
+    "qd_bands_fold", "qd_plan_bands",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
 POWER_WORDS = 19
 SPREAD_WORDS = 28
 DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
+BANDS_MAX, BAND_NONE = 255, 0xffffffff
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -65,6 +67,17 @@ class PlanInfo(C.Structure):
 class SpreadRows(C.Structure):
     """qd_spread_rows: the five result rows of a deviation fold; a NULL pointer is an output not asked for."""
     _fields_ = [("std_rows", C.c_void_p), ("ssd_rows", C.c_void_p), ("count_rows", C.c_void_p), ("mean_rows", C.c_void_p), ("rms_rows", C.c_void_p)]
+
+
+class Band(C.Structure):
+    """qd_band: fftshifted bins [lo, hi)."""
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
+class BandRows(C.Structure):
+    """qd_band_rows: the six result rows of a band fold; a NULL pointer is an output not asked for."""
+    _fields_ = [("level_rows", C.c_void_p), ("sum_rows", C.c_void_p), ("count_rows", C.c_void_p), ("peak_rows", C.c_void_p),
+                ("peak_bin_rows", C.c_void_p), ("pick_rows", C.c_void_p)]
 
 
 class Stage(C.Structure):
@@ -204,6 +217,8 @@ def lib():
             "qd_spread_merge": (i32, [vp, vp, C.c_uint32, u64]),
             "qd_spread_finish": (i32, [vp, C.c_uint32, u64, C.POINTER(SpreadRows)]),
             "qd_plan_spread": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, C.POINTER(SpreadRows), i32, vp]),
+            "qd_bands_fold": (i32, [vp, C.c_uint32, u64, C.POINTER(Band), C.c_uint32, C.POINTER(BandRows)]),
+            "qd_plan_bands": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(Band), C.c_uint32, C.POINTER(BandRows), i32, vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -110,6 +110,7 @@ struct Op {
     bool overwrite = false; std::string prefix;                         // write
     uint64_t pool = 0; bool has_count = false, want_floor = false;      // peaks (-pool P | -count R, count below)
     std::vector<double> qs; std::vector<std::string> q_names;         // quantiles -q 0.5[,0.9,...]
+    std::vector<qd_band> bands; bool pick = false, split = false;      // bands (-bins LO:HI[,LO:HI...] | -split K) [-pick]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
 };
 
@@ -166,11 +167,20 @@ void guess_details(const std::string &filename, const std::string *sr_override, 
     format = fmt;
 }
 
-std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/args.rs:19-45
+std::vector<Op> parse(std::vector<std::string> argv) {                 // src/args.rs:19-45
     std::vector<Op> ops;
     size_t i = 0;
     while (i < argv.size()) {
         std::string cmd = argv[i++];
+        bool pick = false;
+        if (cmd == "bands") {           // -pick is the one flag without a value: it leaves before the "-name value" pairs are read
+            for (size_t j = i; j < argv.size() && !argv[j].empty() && argv[j][0] == '-' && !(argv[j].size() > 2 && isdigit((unsigned char)argv[j][2]));) {
+                if (argv[j] != "-pick") { j += 2; continue; }
+                if (pick) bail("'-pick' specified more than once");
+                pick = true;
+                argv.erase(argv.begin() + j);
+            }
+        }
         ArgMap raw = read_just_args(argv, i);
         Op op{};
         auto next = [&](const char *err) -> std::string { if (i >= argv.size()) bail(err); return argv[i++]; };
@@ -321,6 +331,48 @@ std::vector<Op> parse(const std::vector<std::string> &argv) {          // src/ar
             }
             ensure_empty(m);
             op.prefix = next("'quantiles' requires a prefix argument");
+        } else if (cmd == "bands") {
+            // not in the reference's grammar: the band traces of the windows sparkfft would print — per window and band of fftshifted bins
+            // the level, and the bin of the peak (qd_plan_bands); with -pick the loudest band per window as one line of digits, what
+            // `bucket -by freq K` would print
+            auto m = no_duplicates(raw);
+            op.kind = OP_BANDS; op.pick = pick;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            v = take(m, "bins", &f);
+            const bool has_bins = f;
+            if (f) {
+                for (size_t a = 0; a <= v.size();) {
+                    size_t c = v.find(',', a);
+                    if (c == std::string::npos) c = v.size();
+                    const std::string tok = v.substr(a, c - a);
+                    const size_t colon = tok.find(':');
+                    char *e0 = nullptr, *e1 = nullptr;
+                    const std::string los = tok.substr(0, colon), his = colon == std::string::npos ? "" : tok.substr(colon + 1);
+                    const unsigned long long lo = strtoull(los.c_str(), &e0, 10), hi = strtoull(his.c_str(), &e1, 10);
+                    if (los.empty() || his.empty() || !isdigit((unsigned char)los[0]) || !isdigit((unsigned char)his[0]) || *e0 || *e1 || lo >= hi || hi > op.width)
+                        bail("bands -bins takes LO:HI[,LO:HI...] with 0 <= LO < HI <= width: '" + v + "'");
+                    op.bands.push_back(qd_band{(uint32_t)lo, (uint32_t)hi});
+                    a = c + 1;
+                }
+            }
+            v = take(m, "split", &f);
+            if (f && has_bins) bail("bands takes -bins or -split, not both");
+            if (!f && !has_bins) bail("bands requires -bins or -split");
+            if (f) {
+                const uint64_t K = parse_si_u64(v);
+                if (!K || op.width % K) bail("bands -split takes a number of bands > 0 that divides the width");
+                op.split = true;
+                if (K <= QD_BANDS_MAX)
+                    for (uint64_t k = 0; k < K; ++k) op.bands.push_back(qd_band{(uint32_t)(k * (op.width / K)), (uint32_t)((k + 1) * (op.width / K))});
+                else op.bands.resize(K);
+            }
+            if (op.bands.size() > QD_BANDS_MAX) bail("bands takes at most " + std::to_string(QD_BANDS_MAX) + " bands");
+            if (op.pick && op.bands.size() > 36) bail("bands -pick prints one digit a window: at most 36 bands");
+            ensure_empty(m);
+            op.prefix = next("'bands' requires a prefix argument");
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
             auto m = no_duplicates(raw);
@@ -1180,6 +1232,79 @@ void do_quantiles(const Samples &s, const Op &sink, const ChainSpec *cs) {
     }
 }
 
+// The `bands` sink: the band traces of the windows sparkfft would print (a cascade's complete windows), raw little-endian [windows, K]:
+// PREFIX.sr{rate}.w{W}.k{K}.level.f32, per window and band the mean of the band's norms from their exact sum, rounded once, and
+// PREFIX.sr{rate}.w{W}.k{K}.peak_bin.u32, the lowest fftshifted bin of the band that holds its peak.  One header line on stdout, and with
+// -pick one line of digits, the loudest band of each window (0-9a-z, '.' where no band holds a value): what `bucket -by freq K` would print.
+// A chain the library fuses folds on the device (qd_plan_bands on a norms plan; with -gpus N the WINDOWS are split into contiguous ranges,
+// one plan each, each range in spans of windows whose rows fit the library's workspace); every other chain pulls its windows through the
+// iterator chain and folds their norms with qd_bands_fold — the same bytes either way.
+void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    const uint32_t K = (uint32_t)sink.bands.size();
+    uint64_t windows = 0;
+    std::vector<float> level;
+    std::vector<uint32_t> peak_bin;
+    std::vector<uint8_t> pick;
+    auto size_for = [&](uint64_t n) { windows = n; level.resize(n * K); peak_bin.resize(n * K); if (sink.pick) pick.resize(n); };
+    auto rows_at = [&](uint64_t w) { return qd_band_rows{level.data() + w * K, nullptr, nullptr, nullptr, peak_bin.data() + w * K, sink.pick ? pick.data() + w : nullptr}; };
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+        done = norms_fused(*cs, sink, "bands", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t tile) {
+            if (g == 0) size_for(complete);
+            const uint64_t per = ((complete + parts - 1) / parts + tile - 1) / tile * tile;       // tile-aligned ranges, as the library's own shards
+            const uint64_t w0 = std::min<uint64_t>(complete, per * g), w1 = std::min<uint64_t>(complete, per * (g + 1));
+            if (w1 <= w0) return (int)QD_OK;
+            int mem = QD_MEM_HOST;
+            const void *src = in.resident(&mem);
+            const uint64_t span = std::max<uint64_t>(1, (1ull << 30) / (16ull * K + 1));          // windows whose rows fit the workspace
+            for (uint64_t wa = w0; wa < w1; wa += span) {
+                const qd_band_rows rows = rows_at(wa);
+                const int rc = qd_plan_bands(plan, src, mem, 0, in.n_samples, wa, std::min(w1, wa + span) - wa, sink.bands.data(), K, &rows, QD_MEM_HOST, nullptr);
+                if (rc) return rc;
+            }
+            return (int)QD_OK;
+        });
+    }
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+        uint64_t nwin = spark_windows(s, W, S);
+        std::vector<qd_c32> buf(W);
+        while (nwin) {
+            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+        }
+        size_for(nwin);
+        std::vector<float> norms;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
+            const qd_band_rows rows = rows_at(w0);
+            qd_check(qd_bands_fold(norms.data(), (uint32_t)W, nb, sink.bands.data(), K, &rows), "fold");
+        }
+    }
+    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + ".k" + std::to_string(K);
+    const std::pair<std::string, std::pair<const void *, size_t>> files[] = {{stem + ".level.f32", {level.data(), level.size() * 4}},
+                                                                             {stem + ".peak_bin.u32", {peak_bin.data(), peak_bin.size() * 4}}};
+    for (const auto &file : files) {
+        int fd = open(file.first.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + file.first);
+        const uint8_t *at = static_cast<const uint8_t *>(file.second.first);
+        for (size_t left = file.second.second; left;) {
+            const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
+            if (w <= 0) { close(fd); bail("write failed"); }
+            at += w; left -= (size_t)w;
+        }
+        close(fd);
+    }
+    printf("bands width=%zu stride=%llu k=%u windows=%llu\n", W, (unsigned long long)S, K, (unsigned long long)windows);
+    if (sink.pick) {
+        std::string line(windows, '.');
+        for (uint64_t i = 0; i < windows; ++i)
+            if (pick[i] < 36) line[i] = "0123456789abcdefghijklmnopqrstuvwxyz"[pick[i]];
+        printf("%s\n", line.c_str());
+    }
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -1195,6 +1320,7 @@ void usage() {
             "   powers [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "  spreads [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
+            "   bands [-width 128] [-stride =width] (-bins LO:HI[,LO:HI...] | -split K) [-pick] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -1246,6 +1372,12 @@ int main(int argc, char **argv) {
                     for (const std::string &q : op.q_names) qs += (qs.empty() ? "" : ",") + q;
                     printf("quantiles width=%zu stride=%llu %s=%llu q=%s range=%.9g:%.9g\n", op.width, (unsigned long long)op.stride, op.pool ? "pool" : "count",
                            (unsigned long long)(op.pool ? op.pool : op.count), qs.c_str(), op.rmin, op.rmax);
+                    break;
+                }
+                case OP_BANDS: {
+                    std::string bs;
+                    for (const qd_band &b : op.bands) bs += (bs.empty() ? "" : ",") + std::to_string(b.lo) + ":" + std::to_string(b.hi);
+                    printf("bands width=%zu stride=%llu k=%zu bins=%s pick=%d\n", op.width, (unsigned long long)op.stride, op.bands.size(), bs.c_str(), op.pick ? 1 : 0);
                     break;
                 }
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
@@ -1314,6 +1446,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("quantiles requires an input");
                 cs.cascade = !chain_clean;
                 do_quantiles(*samples, op, &cs);
+                break;
+            case OP_BANDS:
+                if (!samples) bail("bands requires an input");
+                cs.cascade = !chain_clean;
+                do_bands(*samples, op, &cs);
                 break;
             case OP_ROWS:
                 if (!samples) bail("rows requires an input");

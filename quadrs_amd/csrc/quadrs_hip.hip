@@ -38,6 +38,7 @@
 #include "qd_mean.h"
 #include "qd_power.h"
 #include "qd_spread.h"
+#include "qd_bands.h"
 
 using namespace qd;
 
@@ -4180,6 +4181,131 @@ int qd_plan_density(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     }
     if (rc == QD_OK) rc = counts.home(st);
     if (rc == QD_OK) rc = traces.home(st);
+    return f.close(rc);
+}
+
+// ------------------------------------------------------------------ band traces
+
+namespace {
+static_assert(sizeof(Band) == sizeof(qd_band) && kBandsMax == QD_BANDS_MAX && kBandNone == QD_BAND_NONE, "qd_bands.h and the public header agree on a band");
+
+// the checks qd_bands_fold and qd_plan_bands share; *longest is the longest band's bins
+int bands_given(const qd_band *bands, uint32_t n_bands, uint32_t W, const qd_band_rows *out, uint32_t *longest) {
+    if (n_bands == 0 || n_bands > QD_BANDS_MAX) return fail(QD_ERR_INVALID, "%u bands: a call takes 1 ... %d", n_bands, QD_BANDS_MAX);
+    if (!bands) return fail(QD_ERR_INVALID, "bands is NULL");
+    *longest = 0;
+    for (uint32_t k = 0; k < n_bands; ++k) {
+        if (bands[k].lo >= bands[k].hi || bands[k].hi > W) return fail(QD_ERR_INVALID, "band %u is [%u, %u): 0 <= lo < hi <= %u", k, bands[k].lo, bands[k].hi, W);
+        *longest = std::max(*longest, bands[k].hi - bands[k].lo);
+    }
+    if (!out) return fail(QD_ERR_INVALID, "out is NULL");
+    if (!out->level_rows && !out->sum_rows && !out->count_rows && !out->peak_rows && !out->peak_bin_rows && !out->pick_rows)
+        return fail(QD_ERR_INVALID, "every row of out is NULL");
+    return QD_OK;
+}
+}  // namespace
+
+int qd_bands_fold(const float *norms, uint32_t width, uint64_t n, const qd_band *bands, uint32_t n_bands, const qd_band_rows *out) {
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    uint32_t longest = 0;
+    if (const int rc = bands_given(bands, n_bands, width, out, &longest)) return rc;
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    uint32_t level[QD_BANDS_MAX], count[QD_BANDS_MAX];
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        for (uint32_t k = 0; k < n_bands; ++k) {
+            uint64_t acc[kMeanWords] = {}, key = 0;
+            for (uint32_t b = bands[k].lo; b < bands[k].hi; ++b) {
+                uint32_t bits;
+                memcpy(&bits, row + b, 4);
+                mean_add(acc, bits);
+                key = std::max(key, bands_key(bits, b));
+            }
+            double s;
+            mean_finish_cell(acc, &level[k], &s, &count[k]);
+            const uint64_t o = i * n_bands + k;
+            const uint32_t pk = bands_key_peak(key);
+            if (out->level_rows) memcpy(out->level_rows + o, &level[k], 4);
+            if (out->sum_rows) out->sum_rows[o] = s;
+            if (out->count_rows) out->count_rows[o] = count[k];
+            if (out->peak_rows) memcpy(out->peak_rows + o, &pk, 4);
+            if (out->peak_bin_rows) out->peak_bin_rows[o] = bands_key_bin(key);
+        }
+        if (out->pick_rows) out->pick_rows[i] = bands_pick(level, count, n_bands);
+    }
+    return QD_OK;
+}
+
+int qd_plan_bands(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                  const qd_band *bands, uint32_t n_bands, const qd_band_rows *out, int out_mem, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_bands", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    const uint32_t W = p->W, K = n_bands;
+    uint32_t longest = 0;
+    if (const int rc = bands_given(bands, n_bands, W, out, &longest)) return rc;
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan's bands are not traced in one call: give each device a contiguous range of windows on a plan of its own; the rows simply concatenate")) return rc;
+    if (const int rc = f.admit()) return rc;
+    if (n_windows == 0) return QD_OK;
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    const uint64_t items = n_windows * K;                            // of the range as asked; f.n_windows is its complete part
+    // the workspace: the rows that are not device memory, and the level / count rows the pick reads when they are not asked for
+    const bool own_level = out->pick_rows && !out->level_rows, own_count = out->pick_rows && !out->count_rows;
+    uint64_t ws_bytes = (own_level ? items * 4 : 0) + (own_count ? items * 4 : 0);
+    if (!out_dev)
+        ws_bytes += (out->sum_rows ? items * 8 : 0) + (out->level_rows ? items * 4 : 0) + (out->count_rows ? items * 4 : 0) + (out->peak_rows ? items * 4 : 0) +
+                    (out->peak_bin_rows ? items * 4 : 0) + (out->pick_rows ? n_windows : 0);
+    if (ws_bytes > kBandsMaxWorkspace)
+        return fail(QD_ERR_UNSUPPORTED, "%llu windows x %u bands need a workspace of %llu bytes, above the %llu allowed: walk the range in spans of windows",
+                    (unsigned long long)n_windows, K, (unsigned long long)ws_bytes, (unsigned long long)kBandsMaxWorkspace);
+    if (const int rc = f.open()) return rc;
+    const hipStream_t st = f.st;
+    Planes planes;                                                   // the outputs: [sum][level][count][peak][peak_bin][pick]
+    int rc = planes.place(f, 2, out_dev, {{out->sum_rows, out->sum_rows ? (size_t)(items * 8) : 0}, {out->level_rows, out->level_rows ? (size_t)(items * 4) : 0},
+                                          {out->count_rows, out->count_rows ? (size_t)(items * 4) : 0}, {out->peak_rows, out->peak_rows ? (size_t)(items * 4) : 0},
+                                          {out->peak_bin_rows, out->peak_bin_rows ? (size_t)(items * 4) : 0}, {out->pick_rows, out->pick_rows ? (size_t)n_windows : 0}});
+    if (rc) return rc;
+    BandsParams B{};
+    B.sum = static_cast<double *>(planes.v[0].dev); B.level = static_cast<float *>(planes.v[1].dev); B.count = static_cast<uint32_t *>(planes.v[2].dev);
+    B.peak = static_cast<float *>(planes.v[3].dev); B.peak_bin = static_cast<uint32_t *>(planes.v[4].dev);
+    uint8_t *pick_d = static_cast<uint8_t *>(planes.v[5].dev);
+    void *v = nullptr;
+    if (own_level) { rc = f.ws->get(3, (size_t)(items * 4), &v); if (rc) return rc; B.level = static_cast<float *>(v); }
+    if (own_count) { rc = f.ws->get(4, (size_t)(items * 4), &v); if (rc) return rc; B.count = static_cast<uint32_t *>(v); }
+    // the band table: device memory, uploaded once a call
+    rc = f.ws->get(1, (size_t)K * sizeof(Band), &v); if (rc) return rc;
+    B.bands = static_cast<const Band *>(v);
+    HIPCHK(hipMemcpyAsync(v, bands, (size_t)K * sizeof(Band), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                // the table is the caller's array
+    if (f.is_short) {                                                // windows without a complete read keep the rows of a band without values
+        rc = fill_no_values(B.level, B.sum, B.count, items, st); if (rc) return rc;
+        if (B.peak) HIPCHK(hipMemsetAsync(B.peak, 0, (size_t)(items * 4), st));
+        if (B.peak_bin) HIPCHK(hipMemsetAsync(B.peak_bin, 0xff, (size_t)(items * 4), st));
+    }
+    rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+        if (nw == 0) return (int)QD_OK;
+        BandsParams Q = B;
+        uint64_t grid = 0;
+        bands_split(g0, nw, W, K, longest, &Q.G, &grid);
+        if (const int c = launch_grid(grid, nw)) return c;
+        Q.norms = norms_d;
+        hipLaunchKernelGGL(k_bands, dim3((uint32_t)grid), dim3(kBandsThreads), 0, s, Q);
+        HIPCHK(hipGetLastError());
+        return (int)QD_OK;
+    });
+    if (rc == QD_OK && pick_d) {                                     // every batch is through or queued on st (Fold::host returns with its streams drained)
+        const uint32_t lg = bands_pick_log2_lanes(K), per = kBandsThreads >> lg;
+        const uint64_t grid = (n_windows + per - 1) / per;
+        rc = launch_grid(grid, n_windows);
+        if (rc == QD_OK) {
+            hipLaunchKernelGGL(k_bands_pick, dim3((uint32_t)grid), dim3(kBandsThreads), 0, st, B.level, B.count, n_windows, K, lg, pick_d);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (rc == QD_OK) rc = planes.home(st);
     return f.close(rc);
 }
 

@@ -457,6 +457,45 @@ def spread_finish(acc, outputs=None):
     return tuple(out.get(o) for o in SPREAD_OUTPUTS)
 
 
+BAND_OUTPUTS = ("level", "sum", "count", "peak", "peak_bin", "pick")
+_BAND_DTYPES = {"level": "float32", "sum": "float64", "count": "uint32", "peak": "float32", "peak_bin": "uint32", "pick": "uint8"}
+
+
+def _band_wanted(outputs):
+    want = BAND_OUTPUTS if outputs is None else tuple(outputs)
+    if any(o not in BAND_OUTPUTS for o in want):
+        raise ValueError("outputs are named from %r" % (BAND_OUTPUTS,))
+    return [o for o in BAND_OUTPUTS if o in want]
+
+
+def _band_table(bands):
+    """(qd_band array or None, K) of a sequence of (lo, hi) pairs"""
+    pairs = [(int(lo), int(hi)) for lo, hi in bands]
+    if any(not 0 <= x <= 0xffffffff for pair in pairs for x in pair):
+        raise ValueError("a band's bins are unsigned 32-bit numbers")
+    return ((_ffi.Band * len(pairs))(*[_ffi.Band(lo, hi) for lo, hi in pairs]) if pairs else None), len(pairs)
+
+
+def _band_rows(ptr_of):
+    """a qd_band_rows whose pointers come from ptr_of (output name -> address or None)"""
+    def addr(p):
+        return p.value if isinstance(p, C.c_void_p) else p
+    return _ffi.BandRows(*[addr(ptr_of.get(o)) for o in BAND_OUTPUTS])
+
+
+def bands_fold(norms, bands, outputs=None):
+    """qd_bands_fold, the CPU twin of Plan.bands: norms rows (n, width) and K bands (lo, hi) of fftshifted bins into (level float32, sum
+    float64, count uint32, peak float32, peak_bin uint32)[n, K] and pick uint8[n].  outputs: the names to work out (BAND_OUTPUTS; the
+    default is all); the others are None."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    table, K = _band_table(bands)
+    out = {o: np.empty((n,) if o == "pick" else (n, K), dtype=_BAND_DTYPES[o]) for o in _band_wanted(outputs)}
+    r = _band_rows({o: _np_ptr(x) for o, x in out.items()})
+    check(lib().qd_bands_fold(_np_ptr(a), width, n, table, K, C.byref(r)))
+    return tuple(out.get(o) for o in BAND_OUTPUTS)
+
+
 def density_init(width, levels, rows):
     """qd_density_init: the level counts of `rows` rows of `width` bins, uint32[rows, width, levels], all words 0."""
     counts = np.empty((int(rows), int(width), int(levels)), dtype=np.uint32)
@@ -747,6 +786,24 @@ class Plan:
         out = dict(zip(names, self._fold_rows(call, tuple(_SPREAD_DTYPES[o] for o in names), src, pool, first_window, n_windows, src_first,
                                               pinned, device_out)))
         return tuple(out.get(o) for o in SPREAD_OUTPUTS)
+
+    def bands(self, src, bands, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, outputs=None):
+        """qd_plan_bands of an EPI_NORMS_F32 plan: (level_rows float32, sum_rows float64, count_rows uint32, peak_rows float32,
+        peak_bin_rows uint32)[n_windows, K] and pick_rows uint8[n_windows] — per window of [first_window, +n_windows) and band (lo, hi)
+        of fftshifted bins the exact sum rounded once, its mean rounded once, the number of non-NaN values, the peak and the lowest bin
+        that holds it, and per window the loudest band.  src and device_out as for pool (torch uint32 rows are int32: the same bits).
+        outputs: the names to work out (BAND_OUTPUTS; the default is all); the others are None and cost nothing."""
+        names = _band_wanted(outputs)
+        table, K = _band_table(bands)
+
+        def call(h, ptr, mem, src_first, count, first_window, n_windows, _pool, *rest):
+            ptrs, (out_mem, st) = rest[:-2], rest[-2:]
+            r = _band_rows(dict(zip(names, ptrs)))
+            return lib().qd_plan_bands(h, ptr, mem, src_first, count, first_window, n_windows, table, K, C.byref(r), out_mem, st)
+        shapes = lambda rows: [(rows,) if o == "pick" else (rows, K) for o in names]      # noqa: E731
+        out = dict(zip(names, self._fold_rows(call, tuple(_BAND_DTYPES[o] for o in names), src, 1, first_window, n_windows, src_first, pinned,
+                                              device_out, shapes)))
+        return tuple(out.get(o) for o in BAND_OUTPUTS)
 
     def density(self, src, pool, level0, levels, q=(), first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, counts=True):
         """qd_plan_density of an EPI_NORMS_F32 plan: (count_rows uint32[R, width, levels], trace_rows float32[len(q), R, width]),
