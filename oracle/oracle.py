@@ -55,6 +55,7 @@ def lib():
             "qo_shift_apply": (None, [vp, sz, u64, f64]),
             "qo_shift_multipliers_f64": (None, [f64, u64, sz, vp, vp]),
             "qo_shift_override": (i32, [vp, vp, vp, vp, sz]),
+            "qo_gen_terms_f64": (None, [vp, sz, u64, u64, sz, vp, vp]),
             "qo_cutoff": (f32, [u64, u64]),
             "qo_lowpass_taps": (None, [f32, sz, vp]),
             "qo_complex_convolve": (sz, [vp, sz, vp, sz, vp]),
@@ -261,6 +262,17 @@ def shift_multipliers_f64(ratio, n0, count):
     s = np.empty(count, dtype=np.float64)
     if count:
         lib().qo_shift_multipliers_f64(ratio, int(n0), count, _p(c), _p(s))
+    return c, s
+
+
+def gen_terms_f64(cos_hz, sample_rate, first, n):
+    """NOT reference behaviour: the f64 cos(f), sin(f) of every tone of samples first .. first+n-1 before src/gen.rs:41 casts them to
+    f32 (same base and f as src/gen.rs:37,40, same glibc calls).  Returns (c, s), float64[n, n_cos] each."""
+    arr = np.ascontiguousarray(cos_hz, dtype=np.int64)
+    c = np.empty((n, arr.size), dtype=np.float64)
+    s = np.empty((n, arr.size), dtype=np.float64)
+    if n and arr.size:
+        lib().qo_gen_terms_f64(_p(arr), arr.size, int(sample_rate), int(first), n, _p(c), _p(s))
     return c, s
 
 

@@ -170,6 +170,19 @@ void qo_shift_multipliers_f64(double ratio, uint64_t n0, size_t count, double *c
     }
 }
 
+/* NOT reference code: the f64 cos(f), sin(f) of src/gen.rs:41 before the `as f32` casts, for samples first .. first+n-1 and every tone,
+ * sample-major (term [i * n_cos + k]); base and f are the expressions of src/gen.rs:37,40, the calls are the same glibc ones */
+void qo_gen_terms_f64(const int64_t *cos_hz, size_t n_cos, uint64_t sample_rate, uint64_t first, size_t n, double *c, double *s) {
+    for (size_t i = 0; i < n; i++) {
+        double base = (double)(first + (uint64_t)i) * QO_TAU64 / (double)sample_rate;
+        for (size_t k = 0; k < n_cos; k++) {
+            double f = (double)cos_hz[k] * base;
+            c[i * n_cos + k] = cos(f);
+            s[i * n_cos + k] = sin(f);
+        }
+    }
+}
+
 /* src/shift.rs:48-52 */
 void qo_shift_apply(qo_c32 *buf, size_t n, uint64_t abs_off, double ratio) {
     for (size_t i = 0; i < n; i++) {

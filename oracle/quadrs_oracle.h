@@ -74,6 +74,9 @@ void     qo_shift_apply(qo_c32 *buf, size_t n, uint64_t abs_off, double ratio);
 /* NOT reference code, for the NCO rule of the tests: the f64 cos/sin(place) of samples n0 .. n0+count-1 before the f32 casts
  * (same place, same glibc calls as qo_shift_multiplier) */
 void     qo_shift_multipliers_f64(double ratio, uint64_t n0, size_t count, double *c, double *s);
+/* NOT reference code, for the gen tests: the f64 cos(f), sin(f) of src/gen.rs:41 before the f32 casts, samples first .. first+n-1,
+ * sample-major: term [i * n_cos + k] (same base and f as src/gen.rs:37,40, same glibc calls as the gen source's read_at) */
+void     qo_gen_terms_f64(const int64_t *cos_hz, size_t n_cos, uint64_t sample_rate, uint64_t first, size_t n, double *c, double *s);
 /* NOT reference code: shift node `node` uses (c[i], s[i]) as the multiplier of absolute index n[i] of its own stream; k = 0
  * removes every override (and a node without one pays nothing per sample).  0 ok, -1 not a shift node / repeated index / out of memory. */
 int      qo_shift_override(qo_node *node, const uint64_t *n, const float *c, const float *s, size_t k);

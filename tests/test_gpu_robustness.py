@@ -48,7 +48,9 @@ def test_far_offset_slab_uses_second_order_nco(engine, oracle, lp, W, S):
         ref[i] = oracle.norm(y)[np.r_[W // 2:W, 0:W // 2]]
     exact, worst = _norms_close(ref, got)
     from test_gpu_parity import record_observed
-    record_observed(f"deep-stream windows W={W} S={S}", exact_fraction=float(exact), worst_ulp_of_window_max=float(worst))
+    from util import ambiguous_windows
+    record_observed(f"deep-stream windows W={W} S={S}", exact_fraction=float(exact), worst_ulp_of_window_max=float(worst), windows=nwin,
+                    windows_reading_an_ambiguous_component=ambiguous_windows(p, np.arange(w0, w0 + nwin)))
     assert exact >= 0.9999 and worst <= 1.0, (exact, worst)
     from test_gpu_parity import assert_explained
     assert_explained(ref, got, (p, w0), f"deep-stream windows W={W} S={S}")
@@ -99,6 +101,9 @@ def test_cascade_deep_shift_obeys_the_nco_rule(engine, oracle):
     L.qo_fft_free(f)
     ref = oracle.norm(y).reshape(nwin, W)[:, np.r_[W // 2:W, 0:W // 2]]
     assert_explained(ref, got, (p, w0), "cascade deep shift W=4")
+    from test_gpu_parity import record_observed
+    from util import ambiguous_windows
+    record_observed("cascade deep shift W=4 [excusable]", windows=nwin, windows_reading_an_ambiguous_component=ambiguous_windows(p, np.arange(w0, w0 + nwin)))
     p.close()
 
 
@@ -120,7 +125,9 @@ def test_nco_rule_catches_first_order_far_out(engine, oracle):
         bad = explain_check(p, ref, got, w0, detail)
         scale = ulp_of(ref.max(axis=-1, keepdims=True)).astype(np.float64)
         worst = float((np.abs(ref.astype(np.float64) - got.astype(np.float64)) / scale).max())
+        from util import ambiguous_windows
         res[order] = dict(windows=nwin, differing=len(detail), unexplained=len(bad), worst_ulp_of_window_max=worst,
+                          windows_reading_an_ambiguous_component=ambiguous_windows(p, np.arange(w0, w0 + nwin)),
                           old_bound_passes=bool(worst <= 1.0 and (ref.view(np.uint32) == got.view(np.uint32)).mean() >= 0.9999))
         record_observed(f"negative control nco_order={order}", **res[order])
         p.close()

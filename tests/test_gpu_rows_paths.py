@@ -18,7 +18,7 @@ import pytest
 from test_gpu_parity import assert_explained, record_observed
 from test_gpu_rows import CHAINS, LP16, SR, _bluestein_check, _chain, _data, _lens, _plan, _slices
 from test_rows_cpu import DEEP_CASES, DEEP_OUT_LEN, DEEP_SPAN
-from util import FMT_BYTES, bits_equal, real_ties
+from util import FMT_BYTES, ambiguous_windows, bits_equal, real_ties
 
 pytestmark = pytest.mark.gpu
 
@@ -247,5 +247,6 @@ def test_rows_deep_in_a_stream(engine, oracle, case, shift):
         _bluestein_check(ch, ref, got, loc, W, what)
     else:
         differing = _nco_rule_rows(ref, got, offs, _stages(shift, lp), W, what)
-        record_observed(what, rows=DEEP_OUT_LEN, rows_differing=differing)
+        record_observed(what, rows=DEEP_OUT_LEN, rows_differing=differing,
+                        rows_reading_an_ambiguous_component=ambiguous_windows((_stages(shift, lp), W, 1, SR), offs.astype(np.int64)))
     p.close()

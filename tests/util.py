@@ -650,6 +650,21 @@ def ambiguous_components(ratio, lo, hi, eps=NCO_ABS_ERR):
     return out
 
 
+def ambiguous_windows(desc, windows):
+    """how many of the sink windows `windows` (absolute indices, any order) of a Plan or (stages, W, S, sample_rate) read an ambiguous
+    multiplier component of some shift stage: the windows in which the NCO rule would excuse a difference"""
+    w = np.asarray(windows, dtype=np.int64).reshape(-1)
+    hit = np.zeros(w.size, dtype=bool)
+    if w.size == 0:
+        return 0
+    d = desc if isinstance(desc, tuple) else _chain_of(desc)
+    for (lo, hi), ratio in zip(shift_spans(tuple(d), w), shift_ratios(desc)):
+        at = np.array(sorted({n for n, _, _ in ambiguous_components(ratio, int(lo.min()), int(hi.max()))}), dtype=np.int64)
+        # window i reads an ambiguous sample iff one lies in [lo_i, hi_i)
+        hit |= np.searchsorted(at, hi, side="left") > np.searchsorted(at, lo, side="left")
+    return int(hit.sum())
+
+
 REAL_TIE_GAP = 1e-13
 """A multiplier component is a REAL tie where its nco_candidates pair (lo32, hi32) lies further apart than this.  The bound of the
 Bluestein rows (2 ulp_f32 of the reference norm + 1e-12 of the row's l1 norm) holds without any excuse as long as the rows read no
@@ -1349,9 +1364,9 @@ def bucket_order_stream(oracle, case):
     return _BUCKET_STREAMS[key]
 
 
-def _fam(kind=None, kernel=None, flags=0, no_flags=0, eq_flags=None, part=None):
+def _fam(kind=None, kernel=None, flags=0, no_flags=0, eq_flags=None, part=None, threads=None):
     def ok(info, name):
-        return ((kind is None or int(info.kernel_kind) == kind) and (kernel is None or name.startswith(f"qd::{kernel}<"))
+        return ((threads is None or int(info.threads) == threads) and (kind is None or int(info.kernel_kind) == kind) and (kernel is None or name.startswith(f"qd::{kernel}<"))
                 and (int(info.kernel_flags) & flags) == flags and not (int(info.kernel_flags) & no_flags)
                 and (eq_flags is None or int(info.kernel_flags) == eq_flags) and (part is None or part in name))
     return ok
@@ -1534,3 +1549,355 @@ def density_pair_buckets(level0, L, W):
     edge = [k for k in (level0 - 2, level0 - 1, level0, level0 + 1, level0 + L - 2, level0 + L - 1, level0 + L, level0 + L + 1) if 0 <= k <= 2040]
     inner = [level0 + 2 + i * max(L - 4, 0) // max(rows - 8, 1) for i in range(max(rows - 8, 0))]
     return sorted(set(edge) | {k for k in inner if level0 <= k < level0 + L and k <= 2040})
+
+
+# ------------------------------------------------------------------ deep slabs (test_deep_slabs_cpu.py, test_gpu_deep_slabs.py)
+#
+# A run of windows [w0, w0 + n) deep in a long stream reads source samples from base = w0 S D_eff on (D_eff the product of the chain's
+# decimations).  The referee is an oracle chain over the SLAB alone, samples [base, base + count) of the described stream: base is a
+# multiple of every stage's decimation, so the slab's window j is the stream's window w0 + j, every FIR centre falls where it does in the
+# whole stream, and shift stage k (whose input runs at the source rate over the decimations before it) gets the reference's own f32
+# multipliers of the absolute indices base_k + i planted through override_shift, base_k = base / (those decimations).  Everything the
+# oracle makes of a chain is then available deep in the stream: norms, glyph codes, freq_levels digits, marks and read_at blocks.
+# The slabs are chosen (a condition on the inputs, held by test_deep_slabs_cpu.py on the reference alone) so that NO multiplier component
+# of any shift stage is ambiguous in them: the NCO rule then excuses nothing and the comparison is byte for byte.
+
+DEEP_N = (1 << 34) + 12_345                      # the described stream: 2^34 samples and an odd tail
+DEEP_MAX_WINDOWS = 64
+DEEP_SLAB_CAP = 1 << 20
+_DEEP_EPI = {"norms": 0, "glyph": 1, "bucket": 2, "blocks": 3, "mark": 4}
+DEEP_GLYPH_RNG = (0.001, 0.5)
+DEEP_DEPTHS = ("x32", "x33", "end")
+
+
+def deep_run_windows(tile):
+    """windows per run: 3 tiles + 5, or as many whole tiles + 5 as DEEP_MAX_WINDOWS holds (one tile + 5 where the tile itself is that
+    large): a run that starts on a tile ends in a ragged one and can hold a sample strictly inside"""
+    return min(3 * tile + 5, 5 + tile * ((max(DEEP_MAX_WINDOWS, tile + 5) - 5) // tile))
+
+
+class DeepCase:
+    """one chain of the deep-slab tests.  stages: [("shift", hz) | ("lowpass", (hz, D, T)), ...] source to sink; sink: norms / glyph /
+    bucket / mark / blocks (the write sink: W is the block length, S is ignored); policy: "builtin" (QD_KERNEL_NO_PLAN_TIME) / "generic" /
+    "specialise", never auto — a described 2^34-sample stream makes the auto policy compile; family(info, kernel name) says whether the
+    plan is the intended kernel; tile: the plan's tile_windows (the GPU test holds the plan to it), which aligns the runs and sizes
+    them: 3 tiles + 5 windows, a ragged last tile, see deep_run_windows; N: the described length; paths: also through 64 KiB chunks.
+    Every case has three runs (DEEP_DEPTHS): "x32" / "x33" contain source sample 2^32 / 2^33 strictly inside, "end" is the stream's
+    last windows."""
+
+    def __init__(self, name, fmt, stages, W, S, family, sink="norms", policy="builtin", sr=21_000_000, tile=1, tile_hint=None,
+                 N=DEEP_N, paths=False):
+        self.name, self.fmt, self.stages, self.W, self.S, self.family = name, fmt, list(stages), W, (W if sink == "blocks" else S), family
+        self.sink, self.policy, self.sr, self.tile, self.tile_hint, self.N = sink, policy, sr, tile, tile_hint, N
+        self.n, self.paths = deep_run_windows(tile), paths
+
+    def __repr__(self):
+        return self.name
+
+    epilogue = property(lambda self: _DEEP_EPI[self.sink])
+    shifted = property(lambda self: any(k == "shift" for k, _ in self.stages))
+    lowpasses = property(lambda self: [a for k, a in self.stages if k == "lowpass"])
+    chain = property(lambda self: (self.stages, self.W, self.S, self.sr))
+
+    def step(self):
+        """source samples between window starts, S D_eff"""
+        return source_block(self.stages, self.W, self.S, 1)[0]
+
+    def span(self, n):
+        """source samples windows [0, n) read"""
+        return source_block(self.stages, self.W, self.S, 0, n)[1]
+
+    def seed(self):
+        return sum(ord(c) * (i + 1) for i, c in enumerate(self.name)) + 20261019
+
+    def runs(self, total_windows):
+        """[(depth, w0, n), ...] of a stream of total_windows windows (the plan's n_windows): w0 a multiple of the tile"""
+        out = []
+        for depth in DEEP_DEPTHS:
+            if depth == "end":
+                w0 = -(-(total_windows - self.n) // self.tile) * self.tile
+                n = total_windows - w0
+            else:
+                mark = (1 << 32) if depth == "x32" else (1 << 33)
+                w0 = (mark // self.step() - 1 - (self.n - self.tile) // 2) // self.tile * self.tile      # the mark's window is inside the run
+                n = self.n
+            out.append((depth, w0, n if depth != "end" else total_windows - w0))
+        return out
+
+
+def deep_geometry(engine, case):
+    """(n_windows, complete windows, raw_step, raw_per_window) of the case's described stream from host arithmetic alone:
+    qd_stages_geometry, and for the one-stage write sink, which it leaves to the plan, the header's floor((n - T) / (B D)) full blocks"""
+    if case.sink == "blocks" and len(case.lowpasses) == 1:
+        _, D, T = case.lowpasses[0]
+        n = (case.N - T) // (case.W * D)
+        return n, n, case.W * D, case.W * D + T
+    info, done = engine.stages_geometry(case.fmt, case.sr, case.N, case.stages, case.W, case.S, case.epilogue)
+    return int(info.n_windows), int(done), int(info.raw_step), int(info.raw_per_window)
+
+
+def deep_slab_range(case, depth, w0, n):
+    """(base, count): the slab of a run — from the first sample of window w0 to the end of window w0 + n (one window more than the run:
+    the sink's loop is `while i < len - W`; the write sink's blocks need none), or, for the "end" run, to the end of the stream"""
+    base = w0 * case.step()
+    return base, (case.N - base if depth == "end" else case.span(n + (case.sink != "blocks")))
+
+
+def deep_shift_bases(case, base):
+    """[(ratio, base_k, decimation before stage k), ...] of the shift stages, source to sink"""
+    out, dec = [], 1
+    ratios = iter(shift_ratios(case.chain))
+    for kind, arg in case.stages:
+        if kind == "shift":
+            assert base % dec == 0
+            out.append((next(ratios), base // dec, dec))
+        else:
+            dec *= int(arg[1])
+    return out
+
+
+def deep_ambiguous(case, base, count):
+    """the ambiguous multiplier components of every shift stage over the slab [base, base + count), as (stage, n, comp)"""
+    out = []
+    for k, (ratio, bk, dec) in enumerate(deep_shift_bases(case, base)):
+        out += [(k, n, comp) for n, comp, _ in ambiguous_components(ratio, bk, bk + -(-count // dec))]
+    return out
+
+
+_DEEP_REFS = {}
+
+
+def deep_reference(oracle, case, depth, w0, n, index_bits=None):
+    """(slab bytes as a read-only uint8 array, base, the oracle's output of windows [w0, w0 + n) of the case's sink, the glyph / mark
+    range used or None).  Seeded by the case's name and w0; built once per (case, w0, n).  The mark sink's min is the median of the
+    reference's per-window maxima, so that both marks occur.
+    index_bits (the CPU test of the comparison's bite only): plant the multipliers of the absolute indices truncated to that many bits."""
+    key = (case.name, w0, n, index_bits)
+    if key in _DEEP_REFS:
+        return _DEEP_REFS[key]
+    base, count = deep_slab_range(case, depth, w0, n)
+    rng = np.random.default_rng(case.seed() + w0 % 1_000_003)
+    if case.fmt == 0:
+        raw = (rng.standard_normal((count, 2)) * 0.03).astype(np.float32).view(np.uint8).reshape(-1)
+    else:
+        raw = rng.integers(0, 256, count * FMT_BYTES[case.fmt], dtype=np.uint8)
+    ch = oracle.Chain.from_bytes(raw, case.fmt, case.sr)
+    shifts = iter(deep_shift_bases(case, base))
+    k = 0
+    for kind, arg in case.stages:
+        if kind == "shift":
+            ch = ch.shift(arg)
+            ratio, bk, dec = next(shifts)
+            m = -(-count // dec)
+            if index_bits is None:
+                c, s = oracle.shift_multipliers_f64(ratio, bk, m)      # (f64 as f32): the cast of src/shift.rs:49-50
+            else:                                                      # NOT the referee: what an NCO that kept index_bits of the index would use
+                c, s = (np.concatenate(x) for x in zip(*[oracle.shift_multipliers_f64(ratio, (bk + i) & ((1 << index_bits) - 1), 1) for i in range(m)]))
+            ch.override_shift(k, np.arange(m, dtype=np.uint64), c.astype(np.float32), s.astype(np.float32))
+            k += 1
+        else:
+            ch = ch.lowpass(*arg)
+    W, S, used = case.W, case.S, None
+    if case.sink == "blocks":
+        rows = []
+        for b in range(n):
+            got, blk = ch.read_at(b * W, W)
+            assert got == W, (case.name, b, got)
+            rows.append(blk)
+        ref = np.concatenate(rows)
+    elif case.sink == "bucket":
+        ref = ch.freq_levels(W, S, max_windows=n)
+    elif case.sink == "norms":
+        ref = ch.spark_fft(W, S, max_windows=n, want_codes=False)[0]
+    elif case.sink == "glyph":
+        used = DEEP_GLYPH_RNG
+        ref = ch.spark_fft(W, S, rng=used, max_windows=n, want_norms=False)[1]
+    else:
+        norms = ch.spark_fft(W, S, max_windows=n, want_codes=False)[0]
+        used = (float(np.median(norms.max(axis=1))), 1.0)
+        ref = (ch.spark_fft(W, S, rng=used, max_windows=n, want_norms=False)[1] != 0).any(axis=1).astype(np.uint8)
+    assert ref.shape[0] == n * (W if case.sink == "blocks" else 1), (case.name, w0, n, ref.shape)
+    raw.setflags(write=False)
+    ref.setflags(write=False)
+    _DEEP_REFS[key] = (raw, base, ref, used)
+    return _DEEP_REFS[key]
+
+
+_SH = 999_983                                    # no ambiguous component in the slabs below (test_deep_slabs_cpu.py); 280 000 Hz has one every 75 samples
+_SH2 = 1_000_003                                 # the two-stage cases' 295 000-sample slabs: 999 983 Hz has one ambiguous component in two of them
+_SHL = [("shift", _SH)]
+_LP = lambda lp: [("lowpass", lp)]               # noqa: E731
+_GEN_LP = (700_000, 10, 24)
+_HALF = (5_000_000, 8, 384)
+_LONG = (900_000, 16, 256)
+_SLSLS = [("shift", 123_457), ("lowpass", _CASC[0]), ("shift", -61_001), ("lowpass", _CASC[1]), ("shift", 7_919)]
+_K_SPARK = _fam(kind=1, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0)
+_K_CASC, _K_CFG2, _K_P3S = _fam(part="qd::k_cascade<"), _fam(kind=1, kernel="k_chain", eq_flags=65800), _fam(kind=1, kernel="k_chain_pipe3s")
+
+DEEP_CASES = [
+    # built-in FixedGeo k_chain: cfg2's and cfg3''s geometry behind a real shift; cfg4's without one (bit-exact indexing only)
+    DeepCase("builtin-cfg2", 0, _SHL + _LP(_CFG2), 128, 128, _K_CFG2, tile=2, paths=True),
+    DeepCase("builtin-cfg2-glyph", 0, _SHL + _LP(_CFG2), 128, 128, _K_CFG2, sink="glyph", tile=2),
+    DeepCase("builtin-cfg2-bucket", 0, _SHL + _LP(_CFG2), 128, 128, _K_CFG2, sink="bucket", tile=2),
+    DeepCase("builtin-cfg3p", 0, _SHL + _LP(_CFG3P), 128, 128, _fam(kind=1, kernel="k_chain", eq_flags=65868), tile=1),
+    DeepCase("builtin-cfg3p-mark", 0, _SHL + _LP(_CFG3P), 128, 128, _fam(kind=1, kernel="k_chain"), sink="mark", tile=1),
+    DeepCase("builtin-cfg4", 0, _LP(_CFG4), 1024, 1024, _fam(kind=1, kernel="k_chain", eq_flags=8392), sr=100_000_000, tile=1),
+    # built-in streaming three-stage kernel, 64 / 16 behind 400 taps / 32: the cf32 and the cs8 set
+    DeepCase("builtin-pipe3s-cf32", 0, _SHL + _LP(_CFG3), 64, 16, _K_P3S, tile=14, paths=True),
+    DeepCase("builtin-pipe3s-cf32-glyph", 0, _SHL + _LP(_CFG3), 64, 16, _K_P3S, sink="glyph", tile=14),
+    DeepCase("builtin-pipe3s-cf32-bucket", 0, _SHL + _LP(_CFG3), 64, 16, _K_P3S, sink="bucket", tile=14),
+    DeepCase("builtin-pipe3s-cs8", 1, _SHL + _LP(_CFG3), 64, 16, _K_P3S, tile=14),
+    # runtime geometry (DynGeo): every format behind shift + lowpass — their NCO rows are kThreads * (samples per load) long, so the row
+    # index differs per format —, and the chain kernel without a lowpass at S < W
+    DeepCase("generic-cf32", 0, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, policy="generic", tile=32),
+    DeepCase("generic-cs8", 1, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, policy="generic", tile=32),
+    DeepCase("generic-cu8", 2, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, policy="generic", tile=32),
+    DeepCase("generic-cs16", 3, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, policy="generic", tile=32),
+    DeepCase("generic-cf32-glyph", 0, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, sink="glyph", policy="generic", tile=32),
+    DeepCase("generic-cf32-bucket", 0, _SHL + _LP(_GEN_LP), 16, 5, _GENERIC, sink="bucket", policy="generic", tile=32),
+    DeepCase("generic-cu8-nolp", 2, _SHL, 64, 16, _GENERIC, policy="generic", tile=16),
+    DeepCase("generic-cs16-nolp", 3, _SHL, 64, 16, _GENERIC, policy="generic", tile=16),
+    DeepCase("generic-cf32-nolp-mark", 0, [], 64, 16, _GENERIC, sink="mark", policy="generic", tile=16),
+    # plan-time builds of the chain templates, one each: a decimation that is no power of two, half-window tiles, the long-filter policy's
+    # 512-thread tile (T >= 8 D, S = W), and the tile-at-a-time three-stage kernel k_chain_pipe3 (a tile hint: the library's own choice
+    # for 64 / 16 is the streaming form).  The cfg3' recipe's flags run deep as the built-in kernel above.
+    DeepCase("specialise-d12", 0, _SHL + _LP(_D12), 256, 256, _fam(kind=2, kernel="k_chain"), policy="specialise", tile=1),
+    DeepCase("specialise-half-window", 0, _LP(_HALF), 1024, 1024, _fam(kind=2, kernel="k_chain", flags=8192), policy="specialise",
+             sr=100_000_000, tile=1),
+    DeepCase("specialise-long-filter-512", 0, _SHL + _LP(_LONG), 512, 512, _fam(kind=2, kernel="k_chain", threads=512), policy="specialise", tile=1),
+    DeepCase("specialise-pipe3", 1, _SHL + _LP(_CFG3), 64, 16, _fam(kind=2, kernel="k_chain_pipe3", flags=32768, no_flags=131072, threads=1024),
+             policy="specialise", tile=12, tile_hint=[12, 512, 1, 8, 4, 2, 1 | (32800 << 8), 0]),
+    # wave-local, behind a shift: the built-in k_spark with its lane table, k_spark2, the interleaved launches on their phase grids
+    DeepCase("spark-cf32-w8", 0, _SHL, 8, 8, _K_SPARK, tile=64),
+    DeepCase("spark-cf32-w64", 0, _SHL, 64, 64, _K_SPARK, tile=8),
+    DeepCase("spark-cf32-w64-glyph", 0, _SHL, 64, 64, _K_SPARK, sink="glyph", tile=8),
+    DeepCase("spark-cf32-w64-bucket", 0, _SHL, 64, 64, _K_SPARK, sink="bucket", tile=8),
+    DeepCase("spark-cf32-w1024", 0, _SHL, 1024, 1024, _K_SPARK, tile=1),
+    DeepCase("spark-cs8-w128", 1, _SHL, 128, 128, _K_SPARK, tile=4),
+    DeepCase("spark-cs16-w128", 3, _SHL, 128, 128, _K_SPARK, tile=4),
+    DeepCase("spark2-cf32-w128", 0, _SHL, 128, 128, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), policy="specialise", tile=8),
+    DeepCase("spark2-cf32-w128-glyph", 0, _SHL, 128, 128, _fam(kind=2, kernel="k_spark2", flags=_SPARK | _SPARK2), sink="glyph", policy="specialise", tile=8),
+    # the interleaved form: a k_spark built for 64 / 16 whose own tile is 8 windows while the plan's tile_windows is R * (512 / W) = 4 * 8,
+    # the unit of its W / S = 4 launches' NCO row grids — only a plan with spark_R = 4 reports that
+    DeepCase("interleaved-w64-s16", 0, _SHL, 64, 16, _fam(kind=2, kernel="k_spark", flags=_SPARK, no_flags=_SPARK2 | _SPARK0, part="FixedGeo<64, 16, 1, 0, 8,"),
+             policy="specialise", tile=32),
+    # wave-local, no shift: a window per lane (window indices past 2^32: S = 2)
+    DeepCase("spark0-w4-s2", 0, [], 4, 2, _fam(kind=2, kernel="k_spark0", flags=_SPARK | _SPARK0), policy="specialise", tile=64),
+    # k_cascade: lowpass lowpass, and shift lowpass shift lowpass shift (the inner shifts' absolute indices are base / 4 and base / 16)
+    DeepCase("cascade-ll", 0, _LP(_CASC[0]) + _LP(_CASC[1]), 16, 8, _K_CASC, sr=2_000_000, tile=1),
+    DeepCase("cascade-slsls", 0, _SLSLS, 16, 8, _K_CASC, sr=2_000_000, tile=1),
+    DeepCase("cascade-slsls-glyph", 0, _SLSLS, 16, 8, _K_CASC, sink="glyph", sr=2_000_000, tile=1),
+    DeepCase("cascade-slsls-bucket", 0, _SLSLS, 16, 8, _K_CASC, sink="bucket", sr=2_000_000, tile=1),
+    # write sinks: the one-stage QD_EPI_CF32_BLOCKS at two block lengths, the cascade's
+    DeepCase("write-b64", 0, _SHL + _LP(_CFG2), 64, 64, _GENERIC, sink="blocks", tile=4),
+    DeepCase("write-b1024", 1, _SHL + _LP(_CFG2), 1024, 1024, _GENERIC, sink="blocks", tile=1),
+    DeepCase("cascade-write-b1024", 1, _SHL + _LP(_CASC[0]) + _LP(_CASC[1]), 1024, 1024, _fam(part="qd::k_cascade_write<"), sink="blocks", tile=1),
+    # the two-stage plan: a window past the LDS tile, behind a shift
+    DeepCase("two-stage-w1024", 1, [("shift", _SH2)] + _LP(_CFG3P), 1024, 1024, _fam(part="two stages:"), tile=1, paths=True),
+    DeepCase("two-stage-w1024-glyph", 1, [("shift", _SH2)] + _LP(_CFG3P), 1024, 1024, _fam(part="two stages:"), sink="glyph", tile=1),
+    DeepCase("two-stage-w1024-bucket", 1, [("shift", _SH2)] + _LP(_CFG3P), 1024, 1024, _fam(part="two stages:"), sink="bucket", tile=1),
+]
+
+
+# ------------------------------------------------------------------ qd_gen against the oracle (test_gen_cpu.py, test_gpu_gen.py)
+#
+# The rule: a generated sample equals the reference's bytes wherever none of its terms cos(f), sin(f) (src/gen.rs:41, before the f32
+# casts: oracle.gen_terms_f64) is ambiguous under nco_candidates(term, NCO_ABS_ERR) — the bound covers a device sincos (<= 2 ulp of a
+# value <= 1) plus glibc's ulp —, and lies between the f32 sums of the low and of the high candidates where one is (f32 addition is
+# monotone in either addend, and so is the sequential sum).
+
+GEN_BLOCK = 1 << 16
+GEN_SR = 100_000_000
+
+
+def gen_tone_lists(vec_tones):
+    """name -> (tones, sample rate): cfg4's own list; 1, 2, 64 and 255 tones with negative, zero and repeated frequencies; tones of
+    magnitude 2^40 and 2^62 Hz, whose arguments take the huge-argument reduction of a sincos"""
+    rng = np.random.default_rng(20261019)
+    t64 = [int(v) for v in rng.integers(-49_999_999, 50_000_000, 64)]
+    t64[3], t64[10], t64[40], t64[41] = 0, t64[9], -t64[5], 0
+    t255 = [int(v) | 1 for v in rng.integers(-49_999_999, 50_000_000, 255)]
+    return {"cfg4": ([int(v) for v in vec_tones], GEN_SR), "one": ([1_234_567], GEN_SR), "two": ([-999_983, 0], 21_000_000), "t64": (t64, GEN_SR),
+            "t255": (t255, GEN_SR), "huge": ([(1 << 40) + 1, -((1 << 62) + 3), 12_345], GEN_SR)}
+
+
+GEN_FIRSTS = {"0": 0, "2^24-100": (1 << 24) - 100, "2^32-2^15": (1 << 32) - (1 << 15), "2^40": 1 << 40, "2^53-2^15": (1 << 53) - (1 << 15), "2^63": 1 << 63}
+# the short lists, cheap, at every offset; the long ones at one to three of them
+GEN_RUNS = [(name, first) for name in ("one", "two", "huge") for first in GEN_FIRSTS] + \
+           [("cfg4", "0"), ("cfg4", "2^32-2^15"), ("t64", "2^24-100"), ("t64", "2^53-2^15"), ("t64", "2^63"), ("t255", "2^40")]
+
+GEN_TERM_P = 5.8e-7
+"""The chance that one term cos(f) or sin(f) of uniformly distributed phase is ambiguous under NCO_ABS_ERR = 2e-15.  A value in the binade
+[2^-k-1, 2^-k) has f32 rounding boundaries 2^-k-24 apart and is ambiguous within 2e-15 of one: a chance of 4e-15 * 2^(k+24).  |cos| falls
+into binade 0 with probability 2/3 (4.5e-8 in all) and into binade k >= 1 with (2 / pi) 2^-(k+1), which gives (2 / pi) 4e-15 2^23 = 2.1e-8
+for EACH binade until the boundaries lie closer than the bound itself (k = 23): 4.9e-7; below 2^-24 every value is ambiguous: 3.8e-8.
+Measured: 17 samples of 65 536 with 255 tones, 5.1e-7 per term."""
+
+
+def gen_ambiguous_bound(name, tones, n):
+    """how many of n consecutive samples of a tone list may hold an ambiguous term: 3 x the expected count of 2 K n GEN_TERM_P (K the
+    tones that turn: a zero frequency gives exactly (1, 0)) + 5, a margin no Poisson count of that mean reaches; cfg4's own list adds its
+    structure — its tones are odd multiples of 100 MHz / 256, the sines cross zero at every 128th sample and the cosines at the 64th
+    between: n / 64 + 1 samples"""
+    turning = sum(1 for t in tones if t != 0)
+    return int(np.ceil(3 * 2 * turning * n * GEN_TERM_P)) + 5 + (n // 64 + 1 if name == "cfg4" else 0)
+
+
+_GEN_REFS = {}
+
+
+def _maybe_ambiguous(v, f, eps=NCO_ABS_ERR):
+    """a cheap superset of the elements of the f64 array v (f its f32 rounding) within eps of an f32 rounding boundary: the distance to
+    f against half the f32 spacing at f, taken as the quarter where f is a power of two (the spacing below it is half), with a margin
+    of 4 eps.  nco_candidates decides among those."""
+    d = np.abs(v - f.astype(np.float64))
+    u = np.spacing(np.abs(f)).astype(np.float64)
+    mant, _ = np.frexp(f)
+    half = np.where(np.abs(mant) == 0.5, u / 4, u / 2)
+    return half - d <= 4 * eps
+
+
+def gen_reference(oracle, tones, sr, first, n, piece=4096):
+    """(ref float32 (n, 2), ambiguous bool (n), lo float32 (n, 2), hi float32 (n, 2)): the oracle's Gen::read_at(first, n), the samples
+    with an ambiguous term, and the sums of the low / high candidates.  Built once per argument set, read-only."""
+    key = (tuple(tones), sr, first, n)
+    if key not in _GEN_REFS:
+        got, ref = oracle.Chain.gen(tones, sr, 1.0).read_at(first, n)
+        assert got == n
+        amb = np.zeros(n, dtype=bool)
+        lo, hi = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+        for a in range(0, n, piece):
+            m = min(piece, n - a)
+            for comp, v in enumerate(oracle.gen_terms_f64(tones, sr, first + a, m)):
+                l = v.astype(np.float32)
+                h = l.copy()
+                at = _maybe_ambiguous(v, l)
+                # a term that is exactly 0 is sin(+-0): pi is irrational, no other double is a zero of sin, and every sincos returns
+                # its argument there — it has one candidate
+                at &= v != 0.0
+                l[at], h[at] = nco_candidates(v[at])
+                amb[a:a + m] |= (l != h).any(axis=1)
+                lo[a:a + m, comp] = np.cumsum(l, axis=1, dtype=np.float32)[:, -1]
+                hi[a:a + m, comp] = np.cumsum(h, axis=1, dtype=np.float32)[:, -1]
+        for x in (ref, amb, lo, hi):
+            x.setflags(write=False)
+        _GEN_REFS[key] = (ref, amb, lo, hi)
+    return _GEN_REFS[key]
+
+
+def gen_rule_violations(ref, amb, lo, hi, got):
+    """samples of `got` that break the rule: (indices that differ from ref without an ambiguous term, indices outside [lo, hi] with one)"""
+    got = np.asarray(got, dtype=np.float32).reshape(ref.shape)
+    ne = (got.view(np.uint32) != ref.view(np.uint32)).any(axis=1)
+    with np.errstate(invalid="ignore"):
+        outside = ~((got >= lo) & (got <= hi)).all(axis=1)
+    return np.flatnonzero(ne & ~amb), np.flatnonzero(amb & outside)
+
+
+GEN_LONG = dict(tones="t64", first=(1 << 32) - (1 << 23) - 5, n=(1 << 24) + 4097)      # one call past k_gen's 65536 blocks of 256: its grid-stride branch
+
+
+def gen_long_stretches(n, stretch=1 << 14):
+    """offsets of the four stretches of a long call that are held to the oracle: its first and last samples and two inner stretches,
+    the second of them across the end of the grid's first pass (sample 2^24)"""
+    return [0, n // 3, (1 << 24) - stretch + 2048, n - stretch]
