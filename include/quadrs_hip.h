@@ -692,6 +692,87 @@ int qd_plan_bands(qd_plan *plan, const void *src, int src_mem, uint64_t src_firs
                   uint64_t first_window, uint64_t n_windows, const qd_band *bands, uint32_t n_bands,
                   const qd_band_rows *out, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ waterfall pictures of a norms plan
+ *
+ * The picture itself: the `render` loop of the reference's conrod front end (src/ui/mod.rs:294-412) behind the norms sink.  Every
+ * fftshifted |X| goes through an HSV colour map (:345-372) and the windows' columns are laid into wrapped strips of an RGB image with a
+ * `stretch`, a 16-pixel gap and `scan` marker columns (:311-332, :374-391).
+ *
+ * THE DEFINITION.  palette 0.5.0 is named by Cargo.lock:2650; its source is not at hand, so HSV -> RGB is PARITY UNPINNED, like rustfft.
+ * The project pins its own statement instead: the textbook conversion, as palette 0.5 is recalled to write it.  Wherever "the reference's
+ * colours" is claimed, this statement is meant.
+ *
+ * Colour of one norm.  Every operation is one IEEE f32 operation, separately rounded.  Nothing is contracted into an FMA.  Subnormals
+ * are kept.
+ *   scaled = x / scale                     (scale = 2.29 in the reference, :353)
+ *   s1     = 1.0 - scaled
+ *   hue    = (s1 * 0.8) * 360.0
+ *   val    = 1.0 - s1                      (not `scaled`: the reference subtracts twice, :361-366)
+ *   pos    = hue - floor(hue / 360.0) * 360.0
+ *   h      = pos / 60.0
+ *   c      = val * 1.0 ;  m = val - c
+ *   t      = h - 2.0 * floor(h * 0.5)      (h % 2 for finite h >= 0)
+ *   xx     = c * (1.0 - |t - 1.0|)
+ *   (r,g,b) = 0<=h<1:(c,xx,0)  1<=h<2:(xx,c,0)  2<=h<3:(0,c,xx)  3<=h<4:(0,xx,c)  4<=h<5:(xx,0,c)  else:(c,0,xx)
+ *   byte   = Rust's `as u8` of ((chan + m) * 256.0): truncate, saturate to 0..255, NaN -> 0
+ * The `else` branch also takes NaN, because every comparison is false there.  The consequences: NaN and +inf give (0,0,0); 0 and -0
+ * give (0,0,0); x >= scale saturates the red channel (for x up to 1.2 scale; beyond, the negative hue wraps on through the sectors and red is xx in
+ * some of them); 1e-40 gives (0,0,0).  At scale 2.29: 0.25 -> (7,0,27), 1.0 -> (0,111,78),
+ * 2.0 -> (223,135,0), 2.29 -> (255,0,0), 2.75 -> (255,0,255).
+ *
+ * Page.  Pixels are 3 bytes R,G,B, px_width x px_height = w h of them.  Pixel (x, y) lives at byte ((h - 1 - y) w + x) 3, so y = 0 is
+ * the bottom row (MemImage::set, :286-291).  Let row_height = stretch W + 16.  Window p of the range, counted from the range's first
+ * window, is column x = p % w of strip r = p / w, whose origin is oy = r row_height.  The strip exists iff oy <= h: the reference's test
+ * is `>`, so it is not `<` (:330), and a strip at oy == h consumes its windows and shows nothing.  Hence strips = h / row_height + 1, and
+ * at most max_windows = strips w windows are ever looked at; the reference breaks out of its loop there.  Bin o of the window, in the
+ * fftshifted order the norms sink writes, paints pixel rows y = oy + o stretch + off for off < stretch; rows with y >= h are skipped.
+ * A column with scan >= 1 && p % scan == 0 is painted (0,0,0) in place of its colours (:374-376).  scan == 0 means no marker columns:
+ * our one extension — the reference never has 0, and its default of 1 blackens every column.  The gap rows, and every pixel that no
+ * window reaches, are (0,0,0).
+ * Deviation: the reference's ensure!(w > fft_width) ("TODO: window too narrow") is a GUI to-do and not arithmetic; the library does not
+ * carry it. */
+typedef struct qd_picture_desc {
+    uint32_t struct_size;     /* sizeof(qd_picture_desc) */
+    uint32_t px_width;        /* w >= 1 */
+    uint32_t px_height;       /* h >= 1 */
+    uint32_t stretch;         /* >= 1: pixel rows per bin (the reference's Params default: 4, :72-76) */
+    uint32_t scan;            /* 0: no marker columns; N: every N-th window's column is black */
+    float scale;              /* finite, > 0 (the reference: 2.29, :353) */
+} qd_picture_desc;
+/* A call's picture workspace (a picture that is not device memory) is at most this many bytes; above it qd_plan_picture is QD_ERR_UNSUPPORTED. */
+#define QD_PICTURE_MAX_WORKSPACE (1ull << 30)
+
+/* The page for windows of `width` bins (:311-332): *strips = h / row_height + 1, *max_windows = strips w, *bytes = 3 w h; any of the
+ * three may be NULL.  QD_ERR_INVALID (the outputs are not touched): desc NULL or of an unknown struct_size, width == 0, px_width,
+ * px_height or stretch of 0, or a scale that is not a finite positive f32.  Every call below refuses a desc by the same rule. */
+int qd_picture_geometry(const qd_picture_desc *desc, uint32_t width, uint64_t *strips, uint64_t *max_windows, uint64_t *bytes);
+/* The colour map alone, on the host (:345-372): n host f32 into 3 n bytes R,G,B.  QD_ERR_INVALID: a scale that is not finite and
+ * positive, or a NULL array with n > 0. */
+int qd_picture_color(const float *norms, size_t n, float scale, uint8_t *rgb);
+/* Writes black: 3 w h zero bytes of host memory. */
+int qd_picture_init(uint8_t *pixels, const qd_picture_desc *desc);
+/* The CPU twin of the kernel behind qd_plan_picture, byte for byte: windows at, at+1, ... at+n-1 of a range (n rows of `width` host f32
+ * in `norms`) paint their columns into the host picture `pixels`, which holds the whole page.  A window writes only its own column, so
+ * parts of a range folded in any order give the whole.  Windows at or beyond max_windows are ignored.  QD_ERR_INVALID: a refused desc,
+ * pixels NULL, or norms NULL with n > 0. */
+int qd_picture_fold(uint8_t *pixels, const qd_picture_desc *desc, uint32_t width, uint64_t at, const float *norms, uint64_t n);
+/* The picture of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan (`render`, :294-412; one transform per window as fft_at,
+ * :414-430); src, src_mem, src_first, src_count and `stream` as for qd_plan_run (device, host and pinned sources).  `pixels` is 3 w h
+ * bytes of out_mem memory (host, pinned or device, of any alignment) and is OVERWRITTEN: black first, then the columns; the call returns
+ * after it is complete.  *painted (may be NULL) is the number of windows transformed: min(n_windows, max_windows), or fewer for a short
+ * cascade.  Windows beyond that are not even run through the chain.  The windows go batch by batch through the plan's own kernel into a
+ * device carrier of at most max(chunk_bytes, one tile of windows) of norms and are painted from there into the picture itself when
+ * out_mem is device memory, else into a workspace that is copied down once.  Each byte of a column is stored once, by one lane, without
+ * atomics: no batch, chunk, memory kind or launch order changes a byte.  A fold leaves qd_plan_get_stats alone.
+ * Codes as qd_plan_pool: QD_ERR_INVALID for any epilogue other than QD_EPI_NORMS_F32, a refused desc, pixels NULL or an unknown memory
+ * kind; QD_ERR_SHORT past the sink's loop (the outputs are not touched), and for a cascade when a window that is looked at is past
+ * qd_plan_complete_windows (every complete window of the range is painted and *painted counts them); QD_ERR_UNSUPPORTED for a plan
+ * created with shards (one plan per contiguous range of columns, composed on the host the way qd_picture_fold composes parts), and for
+ * a picture workspace above QD_PICTURE_MAX_WORKSPACE.  n_windows == 0: QD_OK and a black picture. */
+int qd_plan_picture(qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                    uint64_t first_window, uint64_t n_windows, const qd_picture_desc *desc,
+                    uint8_t *pixels, int out_mem, uint64_t *painted, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

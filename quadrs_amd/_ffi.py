@@ -32,6 +32,7 @@ SYMBOLS = [
     "qd_spread_init", "qd_spread_fold", "qd_spread_merge", "qd_spread_finish", "qd_plan_spread",
     "qd_density_init", "qd_density_fold", "qd_density_merge", "qd_density_quantile", "qd_plan_density",
     "qd_bands_fold", "qd_plan_bands",
+    "qd_picture_geometry", "qd_picture_color", "qd_picture_init", "qd_picture_fold", "qd_plan_picture",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
@@ -39,6 +40,7 @@ POWER_WORDS = 19
 SPREAD_WORDS = 28
 DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
 BANDS_MAX, BAND_NONE = 255, 0xffffffff
+PICTURE_MAX_WORKSPACE = 1 << 30
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -78,6 +80,12 @@ class BandRows(C.Structure):
     """qd_band_rows: the six result rows of a band fold; a NULL pointer is an output not asked for."""
     _fields_ = [("level_rows", C.c_void_p), ("sum_rows", C.c_void_p), ("count_rows", C.c_void_p), ("peak_rows", C.c_void_p),
                 ("peak_bin_rows", C.c_void_p), ("pick_rows", C.c_void_p)]
+
+
+class PictureDesc(C.Structure):
+    """qd_picture_desc: the page of a waterfall picture."""
+    _fields_ = [("struct_size", C.c_uint32), ("px_width", C.c_uint32), ("px_height", C.c_uint32), ("stretch", C.c_uint32), ("scan", C.c_uint32),
+                ("scale", C.c_float)]
 
 
 class Stage(C.Structure):
@@ -219,6 +227,11 @@ def lib():
             "qd_plan_spread": (i32, [vp, vp, i32, u64, u64, u64, u64, u64, C.POINTER(SpreadRows), i32, vp]),
             "qd_bands_fold": (i32, [vp, C.c_uint32, u64, C.POINTER(Band), C.c_uint32, C.POINTER(BandRows)]),
             "qd_plan_bands": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(Band), C.c_uint32, C.POINTER(BandRows), i32, vp]),
+            "qd_picture_geometry": (i32, [C.POINTER(PictureDesc), C.c_uint32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+            "qd_picture_color": (i32, [vp, sz, f32, vp]),
+            "qd_picture_init": (i32, [vp, C.POINTER(PictureDesc)]),
+            "qd_picture_fold": (i32, [vp, C.POINTER(PictureDesc), C.c_uint32, u64, vp, u64]),
+            "qd_plan_picture": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(PictureDesc), vp, i32, C.POINTER(u64), vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -111,6 +111,7 @@ struct Op {
     uint64_t pool = 0; bool has_count = false, want_floor = false;      // peaks (-pool P | -count R, count below)
     std::vector<double> qs; std::vector<std::string> q_names;         // quantiles -q 0.5[,0.9,...]
     std::vector<qd_band> bands; bool pick = false, split = false;      // bands (-bins LO:HI[,LO:HI...] | -split K) [-pick]
+    uint32_t px_w = 0, px_h = 0, stretch = 4, marker = 0; float scale = 2.29f;   // picture -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
 };
 
@@ -373,6 +374,37 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             if (op.pick && op.bands.size() > 36) bail("bands -pick prints one digit a window: at most 36 bands");
             ensure_empty(m);
             op.prefix = next("'bands' requires a prefix argument");
+        } else if (cmd == "picture") {
+            // not in the reference's grammar: the waterfall its conrod front end renders (src/ui/mod.rs:294-412) as a binary PPM.  -width 8,
+            // -stride 1 and -stretch 4 are its Params (:72-76) and 2.29 its scale (:353); -scan 0, no marker columns, is not: its default of 1
+            // blackens every column
+            auto m = no_duplicates(raw);
+            op.kind = OP_PICTURE;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 8;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : 1;
+            v = take(m, "size", &f);
+            if (!f) bail("picture requires -size PXWxPXH");
+            {
+                const size_t x = v.find('x');
+                char *e0 = nullptr, *e1 = nullptr;
+                const std::string ws = v.substr(0, x), hs = x == std::string::npos ? "" : v.substr(x + 1);
+                const unsigned long long pw = strtoull(ws.c_str(), &e0, 10), ph = strtoull(hs.c_str(), &e1, 10);
+                if (ws.empty() || hs.empty() || !isdigit((unsigned char)ws[0]) || !isdigit((unsigned char)hs[0]) || *e0 || *e1 || !pw || !ph || pw > 0xffffffffull || ph > 0xffffffffull)
+                    bail("picture -size takes PXWxPXH, both > 0: '" + v + "'");
+                op.px_w = (uint32_t)pw; op.px_h = (uint32_t)ph;
+            }
+            v = take(m, "stretch", &f);
+            if (f) { const uint64_t k = parse_si_u64(v); if (!k || k > 0xffffffffull) bail("picture -stretch takes a number of pixel rows > 0"); op.stretch = (uint32_t)k; }
+            v = take(m, "scan", &f);
+            if (f) { const uint64_t k = parse_si_u64(v); if (k > 0xffffffffull) bail("picture -scan takes 0 or a number of windows"); op.marker = (uint32_t)k; }
+            v = take(m, "scale", &f);
+            if (f) { char *e = nullptr; op.scale = strtof(v.c_str(), &e); if (*e || !(op.scale > 0.f) || std::isinf(op.scale)) bail("picture -scale takes a finite number > 0: '" + v + "'"); }
+            v = take(m, "overwrite", &f);
+            op.overwrite = f ? parse_bool(v) : false;
+            ensure_empty(m);
+            op.prefix = next("'picture' requires a prefix argument");
         } else if (cmd == "rows") {
             // not in the reference's grammar: the rows of its spectrogram view (take_fft, src/ffts.rs:18-85) as a greyscale picture
             auto m = no_duplicates(raw);
@@ -1305,6 +1337,83 @@ void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
     }
 }
 
+// The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
+// it out (src/ui/mod.rs:294-412; the colour map is the project's own statement of palette 0.5's HSV -> RGB, include/quadrs_hip.h), written
+// as PREFIX.sr{rate}.w{W}.{pxw}x{pxh}.ppm: binary P6, maxval 255, top row first — the buffer as it lies.  A chain the library fuses paints
+// on the device (qd_plan_picture on a norms plan).  With -gpus N every device gets a contiguous range of whole strips: the picture of a
+// range that starts at strip r0 is the top px_height - r0 row_height rows of the page, so each part paints straight into its rows of
+// the one host buffer; marker columns count from the first window of the whole range, so there the parts paint without them and the
+// host blackens them.  Every other chain pulls its windows through the iterator chain into qd_picture_fold.  The same bytes either way.
+void do_picture(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    qd_picture_desc desc{};
+    desc.struct_size = sizeof desc;
+    desc.px_width = sink.px_w; desc.px_height = sink.px_h; desc.stretch = sink.stretch; desc.scan = sink.marker; desc.scale = sink.scale;
+    uint64_t strips = 0, max_windows = 0, bytes = 0;
+    qd_check(qd_picture_geometry(&desc, (uint32_t)W, &strips, &max_windows, &bytes), "picture");
+    const uint64_t row_height = (uint64_t)sink.stretch * W + 16;
+    const std::string fn = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + "." + std::to_string(sink.px_w) + "x" +
+                           std::to_string(sink.px_h) + ".ppm";
+    int fd = open(fn.c_str(), O_WRONLY | (sink.overwrite ? O_CREAT | O_TRUNC : O_CREAT | O_EXCL), 0644);
+    if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
+    std::vector<uint8_t> pixels;
+    uint64_t painted = 0;
+    try {
+        pixels.assign((size_t)bytes, 0);
+        bool done = false;
+        if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+            done = norms_fused(*cs, sink, "picture", [&](qd_plan *plan, ChainSource &in, int g, int parts, uint64_t complete, uint64_t) {
+                const uint64_t n = std::min(complete, max_windows);
+                int mem = QD_MEM_HOST;
+                if (parts == 1) {
+                    const void *src = n ? in.resident(&mem) : nullptr;
+                    return qd_plan_picture(plan, src, mem, 0, in.n_samples, 0, n, &desc, pixels.data(), QD_MEM_HOST, &painted, nullptr);
+                }
+                painted = n;
+                const uint64_t used = (n + sink.px_w - 1) / sink.px_w, per = (used + parts - 1) / parts;      // strips that hold a window; a part's share
+                const uint64_t r0 = per * g, w0 = r0 * sink.px_w, w1 = std::min(n, (r0 + per) * sink.px_w);
+                if (w1 <= w0 || r0 * row_height >= sink.px_h) return (int)QD_OK;                      // no windows, or the strip at oy == h
+                qd_picture_desc part = desc;
+                part.px_height = (uint32_t)(sink.px_h - r0 * row_height);
+                part.scan = 0;
+                return qd_plan_picture(plan, in.resident(&mem), mem, 0, in.n_samples, w0, w1 - w0, &part, pixels.data(), QD_MEM_HOST, nullptr, nullptr);
+            });
+            if (done && g_gpus > 1 && sink.marker) {
+                for (uint64_t p = 0; p < painted; p += sink.marker) {
+                    const uint64_t x = p % sink.px_w, oy = p / sink.px_w * row_height;
+                    for (uint64_t y = oy; y < oy + (uint64_t)sink.stretch * W && y < sink.px_h; ++y) memset(pixels.data() + ((sink.px_h - 1 - y) * sink.px_w + x) * 3, 0, 3);
+                }
+            }
+        }
+        if (!done) {
+            // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+            uint64_t nwin = spark_windows(s, W, S);
+            std::vector<qd_c32> buf(W);
+            while (nwin) {
+                try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+            }
+            painted = std::min(nwin, max_windows);
+            std::vector<float> norms;
+            for (uint64_t w0 = 0; w0 < painted; w0 += kIterBatch) {
+                const uint64_t nb = iter_norms(s, sink, w0, std::min(painted - w0, kIterBatch), false, &buf, &norms);
+                qd_check(qd_picture_fold(pixels.data(), &desc, (uint32_t)W, w0, norms.data(), nb), "fold");
+            }
+        }
+        const std::string head = "P6\n" + std::to_string(sink.px_w) + " " + std::to_string(sink.px_h) + "\n255\n";
+        if (write(fd, head.data(), head.size()) < 0) bail("write failed");
+        const uint8_t *at = pixels.data();
+        for (size_t left = pixels.size(); left;) {
+            const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
+            if (w <= 0) bail("write failed");
+            at += w; left -= (size_t)w;
+        }
+    } catch (...) { close(fd); unlink(fn.c_str()); throw; }
+    close(fd);
+    printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g strips=%llu max_windows=%llu painted=%llu\n", W, (unsigned long long)S,
+           sink.px_w, sink.px_h, sink.stretch, sink.marker, sink.scale, (unsigned long long)strips, (unsigned long long)max_windows, (unsigned long long)painted);
+}
+
 void usage() {
     fprintf(stderr,
             "usage: quadrs-hip [-gpus N] \\\n"
@@ -1321,6 +1430,7 @@ void usage() {
             "  spreads [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
             "   bands [-width 128] [-stride =width] (-bins LO:HI[,LO:HI...] | -split K) [-pick] FILENAME_PREFIX \\\n"
+            " picture [-width 8] [-stride 1] -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29] [-overwrite no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
@@ -1380,6 +1490,10 @@ int main(int argc, char **argv) {
                     printf("bands width=%zu stride=%llu k=%zu bins=%s pick=%d\n", op.width, (unsigned long long)op.stride, op.bands.size(), bs.c_str(), op.pick ? 1 : 0);
                     break;
                 }
+                case OP_PICTURE:
+                    printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g overwrite=%d\n", op.width, (unsigned long long)op.stride, op.px_w, op.px_h,
+                           op.stretch, op.marker, op.scale, op.overwrite ? 1 : 0);
+                    break;
                 case OP_WRITE: printf("write prefix=%s overwrite=%d\n", op.prefix.c_str(), op.overwrite ? 1 : 0); break;
                 case OP_ROWS:
                     printf("rows width=%zu count=%zu slice=%s window=%s\n", op.width, op.count,
@@ -1451,6 +1565,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("bands requires an input");
                 cs.cascade = !chain_clean;
                 do_bands(*samples, op, &cs);
+                break;
+            case OP_PICTURE:
+                if (!samples) bail("picture requires an input");
+                cs.cascade = !chain_clean;
+                do_picture(*samples, op, &cs);
                 break;
             case OP_ROWS:
                 if (!samples) bail("rows requires an input");

@@ -39,6 +39,7 @@
 #include "qd_power.h"
 #include "qd_spread.h"
 #include "qd_bands.h"
+#include "qd_paint.h"
 
 using namespace qd;
 
@@ -4307,6 +4308,127 @@ int qd_plan_bands(qd_plan *p, const void *src, int src_mem, uint64_t src_first, 
     }
     if (rc == QD_OK) rc = planes.home(st);
     return f.close(rc);
+}
+
+// ------------------------------------------------------------------ waterfall pictures
+
+namespace {
+static_assert(kPaintMaxWorkspace == QD_PICTURE_MAX_WORKSPACE, "qd_paint.h and the public header agree on the workspace cap");
+
+int picture_scale(float scale) {
+    return std::isfinite(scale) && scale > 0.0f ? QD_OK : fail(QD_ERR_INVALID, "scale %g: the colour map divides by a finite positive f32", (double)scale);
+}
+// the checks every picture call shares
+int picture_page(const qd_picture_desc *d, uint32_t W, PaintPage *G) {
+    if (!d) return fail(QD_ERR_INVALID, "desc is NULL");
+    if (d->struct_size != sizeof(qd_picture_desc)) return fail(QD_ERR_INVALID, "qd_picture_desc size mismatch");
+    if (W == 0) return fail(QD_ERR_INVALID, "windows of width 0 paint nothing");
+    if (d->px_width == 0 || d->px_height == 0) return fail(QD_ERR_INVALID, "a picture of %u x %u pixels", d->px_width, d->px_height);
+    if (d->stretch == 0) return fail(QD_ERR_INVALID, "stretch is 0: a bin paints at least one pixel row");
+    if (const int rc = picture_scale(d->scale)) return rc;
+    paint_page(W, d->px_width, d->px_height, d->stretch, d->scan, d->scale, G);
+    return QD_OK;
+}
+}  // namespace
+
+int qd_picture_geometry(const qd_picture_desc *desc, uint32_t width, uint64_t *strips, uint64_t *max_windows, uint64_t *bytes) {
+    PaintPage G;
+    if (const int rc = picture_page(desc, width, &G)) return rc;
+    if (strips) *strips = G.strips;
+    if (max_windows) *max_windows = G.max_windows;
+    if (bytes) *bytes = G.bytes;
+    return QD_OK;
+}
+
+int qd_picture_color(const float *norms, size_t n, float scale, uint8_t *rgb) {
+    if (const int rc = picture_scale(scale)) return rc;
+    if (n == 0) return QD_OK;
+    if (!norms || !rgb) return fail(QD_ERR_INVALID, "NULL argument");
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t px = paint_color(norms[i], scale);
+        rgb[3 * i] = (uint8_t)px; rgb[3 * i + 1] = (uint8_t)(px >> 8); rgb[3 * i + 2] = (uint8_t)(px >> 16);
+    }
+    return QD_OK;
+}
+
+int qd_picture_init(uint8_t *pixels, const qd_picture_desc *desc) {
+    PaintPage G;
+    if (const int rc = picture_page(desc, 1, &G)) return rc;
+    if (!pixels) return fail(QD_ERR_INVALID, "pixels is NULL");
+    memset(pixels, 0, (size_t)G.bytes);
+    return QD_OK;
+}
+
+int qd_picture_fold(uint8_t *pixels, const qd_picture_desc *desc, uint32_t width, uint64_t at, const float *norms, uint64_t n) {
+    PaintPage G;
+    if (const int rc = picture_page(desc, width, &G)) return rc;
+    if (!pixels) return fail(QD_ERR_INVALID, "pixels is NULL");
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    for (uint64_t i = 0; i < n && at + i < G.max_windows; ++i) {         // the reference breaks out of its loop at the first strip past the page (:330)
+        const uint64_t p = at + i, x = p % G.w, oy = p / G.w * G.row_height;
+        const bool marker = paint_marker(p, G.scan);
+        const float *row = norms + i * width;
+        for (uint32_t o = 0; o < width; ++o) {
+            const uint64_t ya = oy + (uint64_t)o * G.stretch;
+            if (ya >= G.h) break;
+            const uint32_t px = marker ? 0u : paint_color(row[o], G.scale);
+            for (uint64_t y = ya; y < ya + G.stretch && y < G.h; ++y) {
+                uint8_t *d = pixels + ((G.h - 1 - y) * G.w + x) * 3;
+                d[0] = (uint8_t)px; d[1] = (uint8_t)(px >> 8); d[2] = (uint8_t)(px >> 16);
+            }
+        }
+    }
+    return QD_OK;
+}
+
+int qd_plan_picture(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                    const qd_picture_desc *desc, uint8_t *pixels, int out_mem, uint64_t *painted, void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_picture", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    PaintPage G;
+    if (const int rc = picture_page(desc, p->W, &G)) return rc;
+    if (!pixels) return fail(QD_ERR_INVALID, "pixels is NULL");
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan is not painted in one call: give each device a contiguous range of columns on a plan of its own and compose the "
+                                   "parts on the host, the way qd_picture_fold composes the parts of a range")) return rc;
+    if (const int rc = f.admit()) return rc;
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    if (!out_dev && G.bytes > kPaintMaxWorkspace)
+        return fail(QD_ERR_UNSUPPORTED, "a picture of %u x %u pixels needs a workspace of %llu bytes, above the %llu allowed: paint into device memory, or page by page",
+                    G.w, G.h, (unsigned long long)G.bytes, (unsigned long long)kPaintMaxWorkspace);
+    // the windows that are looked at: the surplus past the page is not run through the chain, and cannot make the read short
+    const uint64_t look = std::min(n_windows, G.max_windows);
+    if (f.is_short && first_window + look <= p->c_complete) f.is_short = false;
+    f.n_windows = std::min(f.n_windows, look);
+    if (const int rc = f.open()) return rc;
+    const hipStream_t st = f.st;
+    Planes out;                                                      // the accumulator is the picture
+    if (const int rc = out.place(f, 1, out_dev, {{pixels, (size_t)G.bytes}})) return rc;
+    uint8_t *pix_d = static_cast<uint8_t *>(out.v[0].dev);
+    HIPCHK(hipMemsetAsync(pix_d, 0, (size_t)G.bytes, st));           // black first
+    const uint32_t tps = paint_tiles_per_strip(G.w), bin_tiles = (G.W + kPaintBins - 1) / kPaintBins;
+    int rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+        if (nw == 0) return (int)QD_OK;
+        PaintParams Q{};
+        Q.norms = norms_d; Q.pixels = pix_d; Q.g0 = g0; Q.nw = nw;
+        Q.tile0 = paint_tile_of(g0, G.w);
+        Q.row_height = G.row_height;
+        Q.W = G.W; Q.w = G.w; Q.h = G.h; Q.stretch = G.stretch; Q.scan = G.scan; Q.tiles_per_strip = tps; Q.bin_tiles = bin_tiles;
+        Q.scale = G.scale;
+        const uint64_t grid = (paint_tile_of(g0 + nw - 1, G.w) - Q.tile0 + 1) * bin_tiles;
+        if (const int c = launch_grid(grid, nw)) return c;
+        hipLaunchKernelGGL(k_paint, dim3((uint32_t)grid), dim3(kPaintThreads), 0, s, Q);
+        HIPCHK(hipGetLastError());
+        return (int)QD_OK;
+    });
+    if (rc == QD_OK) rc = out.home(st);
+    rc = f.sync(rc);
+    if (rc) return rc;
+    if (painted) *painted = f.n_windows;
+    return f.short_read();
 }
 
 int qd_device_alloc(size_t bytes, void **ptr) {

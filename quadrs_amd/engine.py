@@ -496,6 +496,46 @@ def bands_fold(norms, bands, outputs=None):
     return tuple(out.get(o) for o in BAND_OUTPUTS)
 
 
+def picture_desc(px_width, px_height, stretch=4, scan=0, scale=2.29):
+    """a qd_picture_desc: the page of a waterfall picture.  stretch 4 and scale 2.29 are the reference's; scan 0 (no marker columns) is
+    not: its default of 1 blackens every column."""
+    return _ffi.PictureDesc(C.sizeof(_ffi.PictureDesc), int(px_width), int(px_height), int(stretch), int(scan), float(scale))
+
+
+def picture_geometry(desc, width):
+    """qd_picture_geometry: (strips, max_windows, bytes) of the page for windows of `width` bins."""
+    s, m, b = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().qd_picture_geometry(C.byref(desc), int(width), C.byref(s), C.byref(m), C.byref(b)))
+    return s.value, m.value, b.value
+
+
+def picture_color(norms, scale=2.29):
+    """qd_picture_color, the colour map alone on the host: float32 norms of any shape into uint8 R,G,B of that shape + (3,)."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    rgb = np.empty(a.shape + (3,), dtype=np.uint8)
+    check(lib().qd_picture_color(_np_ptr(a), a.size, float(scale), _np_ptr(rgb)))
+    return rgb
+
+
+def picture_init(desc):
+    """qd_picture_init: a black picture, uint8[px_height, px_width, 3], top row first."""
+    pixels = np.empty((desc.px_height, desc.px_width, 3), dtype=np.uint8)
+    check(lib().qd_picture_init(_np_ptr(pixels), C.byref(desc)))
+    return pixels
+
+
+def picture_fold(norms, desc, at=0, into=None):
+    """qd_picture_fold, the CPU twin of Plan.picture: norms rows (n, width) are windows at, at+1, ... of a range and paint their columns
+    into the picture `into`, or into a new black one.  Returns the picture, uint8[px_height, px_width, 3]."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        picture_geometry(desc, width)            # a refused desc has no picture to start from
+        into = picture_init(desc)
+    check(lib().qd_picture_fold(_np_ptr(into), C.byref(desc), width, int(at), _np_ptr(a), n))
+    return into
+
+
 def density_init(width, levels, rows):
     """qd_density_init: the level counts of `rows` rows of `width` bins, uint32[rows, width, levels], all words 0."""
     counts = np.empty((int(rows), int(width), int(levels)), dtype=np.uint32)
@@ -804,6 +844,34 @@ class Plan:
         out = dict(zip(names, self._fold_rows(call, tuple(_BAND_DTYPES[o] for o in names), src, 1, first_window, n_windows, src_first, pinned,
                                               device_out, shapes)))
         return tuple(out.get(o) for o in BAND_OUTPUTS)
+
+    def picture(self, src, desc, first_window=0, n_windows=None, src_first=0, pinned=False, out=None, device_out=None):
+        """qd_plan_picture of an EPI_NORMS_F32 plan: (pixels uint8[px_height, px_width, 3], painted) — the waterfall picture of windows
+        [first_window, +n_windows) on the page `desc` (picture_desc), top row first, and the number of windows transformed.  src as for
+        pool.  out: a uint8 numpy array or torch CUDA tensor of 3 w h bytes to paint into (it is overwritten); without it the picture is
+        a torch CUDA tensor when device_out (the default for a torch src), else a numpy array.  A failing call's error carries
+        (pixels, painted or None) as e.partial."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        shape = (desc.px_height, desc.px_width, 3)
+        if out is None:
+            if _is_torch(src) if device_out is None else device_out:
+                import torch
+                out = torch.empty(shape, dtype=torch.uint8, device="cuda")
+            else:
+                out = np.empty(shape, dtype=np.uint8)
+        if _is_torch(out):
+            optr, out_mem = C.c_void_p(out.data_ptr()), MEM_DEVICE
+        else:
+            optr, out_mem = _np_ptr(out), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST)
+        painted = C.c_uint64(0xffffffffffffffff)
+        try:
+            check(lib().qd_plan_picture(self._h, ptr, mem, src_first, count, first_window, n_windows, C.byref(desc), optr, out_mem,
+                                        C.byref(painted), st))
+        except _ffi.QuadrsError as e:
+            e.partial = (out, None if painted.value == 0xffffffffffffffff else painted.value)
+            raise
+        return out, painted.value
 
     def density(self, src, pool, level0, levels, q=(), first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None, counts=True):
         """qd_plan_density of an EPI_NORMS_F32 plan: (count_rows uint32[R, width, levels], trace_rows float32[len(q), R, width]),
