@@ -353,6 +353,14 @@ int qd_rows_geometry(const qd_chain_desc *desc, const qd_rows_desc *rows, uint64
 int qd_plan_take_fft(qd_plan *plan, const qd_rows_desc *rows_desc, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
                      float *rows, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ the folds of a norms plan
+ *
+ * The eight sections from here to the waterfall pictures fold the windows of a QD_EPI_NORMS_F32 plan on the device: qd_plan_summarize,
+ * _pool, _mean, _power, _spread, _density, _bands and _picture.  THE FOOTPRINT they share: of `src` only qd_plan_src_range of the
+ * windows the call transforms is read (all of [first_window, +n_windows); for a picture those its page looks at); only the outputs asked
+ * for are written, each over exactly its stated size; all device work is ordered on `stream`; and the results are complete on return,
+ * for device outputs too.  tests/test_gpu_fold_footprint.py and tests/test_gpu_fold_streams.py hold every fold to it. */
+
 /* ------------------------------------------------------------------ level summary of a norms plan
  *
  * What `-range` to pass and where in the band the signal sits, without bringing the norms back: FftResult::max / min

@@ -906,10 +906,10 @@ def framed(kind, fmt, which, front_bytes, slab, back_bytes, engine=None):
     return Framed(kind, poison(fmt, front_bytes, which), slab, poison(fmt, back_bytes, which), engine)
 
 
-def framed_out(kind, guard_bytes, payload_bytes, engine=None):
-    """an output of payload_bytes between two guards, all three filled with GUARD_BYTE"""
-    g = np.full(guard_bytes, GUARD_BYTE, dtype=np.uint8)
-    return Framed(kind, g, np.full(payload_bytes, GUARD_BYTE, dtype=np.uint8), g, engine)
+def framed_out(kind, guard_bytes, payload_bytes, engine=None, fill=GUARD_BYTE):
+    """an output of payload_bytes between two guards, all three filled with `fill` (GUARD_BYTE)"""
+    g = np.full(guard_bytes, fill, dtype=np.uint8)
+    return Framed(kind, g, np.full(payload_bytes, fill, dtype=np.uint8), g, engine)
 
 
 class FootprintRun:
@@ -1024,6 +1024,104 @@ def footprint_reference(oracle_chain, stages, sr, W, S, epi, rng, n_total):
         exact = not shifted and epi in (0, 3)
         return ref, (None if exact else rule), (1 if epi in (1, 2) else 4)
     return expect
+
+
+# ------------------------------------------------------------------ the fold sinks' footprint (tests/test_gpu_fold_footprint.py)
+#
+# A fold (qd_plan_summarize, _pool, _mean, _power, _spread, _density, _bands, _picture) leaves SEVERAL output planes.  Each sits in a
+# framed_out allocation of its own, and everything is byte for byte: the planes' expected bytes are the CPU twins' over the plan's norms.
+# The payload pre-fill is the run's own: 0xA5 in the first run and 0x5A in the second.  As f32 / f64 the 0xA5 pattern is negative and as
+# u32 above the 2^31 count limit, so no fold ever writes it; in a u8 plane (pick_rows, pixels, the summary struct's bytes) either byte
+# is a value a fold may write, and an unwritten element shows in the run whose pre-fill the expected byte is not.
+
+FOLD_FILLS = (GUARD_BYTE, 0x5A)                # the output pre-fill of run 0 / run 1
+
+
+def fold_guard_bytes(row_bytes):
+    """the least size of a fold plane's guard: max(64 KiB, four output rows), a multiple of 4 KiB.  A condition, not a measurement."""
+    return _round_up(max(64 << 10, 4 * int(row_bytes)), 4096)
+
+
+def fold_plane(kind, row_bytes, payload_bytes, fill=GUARD_BYTE, skew=0, engine=None):
+    """one output plane of a fold between guards of fold_guard_bytes(row_bytes) + skew bytes: skew (a multiple of the element size that
+    is no multiple of 16) moves the payload off the allocation's own alignment"""
+    return framed_out(kind, fold_guard_bytes(row_bytes) + int(skew), int(payload_bytes), engine, fill)
+
+
+class FoldRun:
+    """what one framed fold run left behind: per plane name its FootprintRun (guards and payload) and the bytes of an output row, the
+    run's pre-fill byte, and the source buffer's bytes where a kernel could write it (device, pinned)"""
+
+    def __init__(self, planes, row_bytes, fill=GUARD_BYTE, src=None):
+        self.fill = int(fill)
+        self.row_bytes = {name: int(b) for name, b in row_bytes.items()}
+        self.planes = {name: FootprintRun(out) for name, out in planes.items()}
+        self.src_uploaded = self.src_now = None
+        if src is not None and src.kind != "host":
+            self.src_uploaded, self.src_now = src.uploaded, src.snapshot()
+
+
+def fold_footprint_violations(runs, refs):
+    """The footprint checker of the fold sinks.  runs: the FoldRun of each poison pattern (two; run k pre-filled with FOLD_FILLS[k]),
+    same windows, same true slab.  refs: plane name -> the expected bytes (an array laid out like the payload; its dtype gives the
+    element size).  Byte for byte.  Returns the violated conditions, each naming its plane; every wrong payload byte falls into exactly
+    one of the first three classes:
+      1. "unwritten": an output element still holds its run's pre-fill where the expected value is something else;
+      2. "poison": the runs' payloads differ elsewhere (memory outside the slab, or a stale workspace, reached an output byte);
+      3. "oracle": a byte on which the runs agree is not the expected one;
+      4. "guard": a byte of a plane's guard changed, or a guard is smaller than fold_guard_bytes (64 KiB, four output rows);
+      5. "source": a byte of the source buffer (frames or slab) changed."""
+    bad = []
+    if len(runs) != len(POISON_WORDS):
+        bad.append(f"poison: {len(runs)} runs, one per pattern is {len(POISON_WORDS)}")
+    for name, ref in refs.items():
+        ref = np.ascontiguousarray(ref)
+        unit = ref.dtype.itemsize
+        ref_b = ref.view(np.uint8).reshape(-1)
+        rs = [r.planes.get(name) for r in runs]
+        if any(r is None for r in rs):
+            bad.append(f"oracle: plane {name}: a run left no such plane")
+            continue
+        if unit == 1 and len({r.fill for r in runs}) < 2:
+            bad.append(f"unwritten: plane {name}: a u8 plane needs a run with each pre-fill of {FOLD_FILLS}")
+        sizes = [r.payload.size for r in rs]
+        if any(s != ref_b.size for s in sizes):
+            bad.append(f"oracle: plane {name}: payloads of {sizes} bytes, the expected plane has {ref_b.size}")
+            continue
+        stale = np.zeros(ref_b.size // unit, dtype=bool)
+        for run, r in zip(runs, rs):
+            fill = np.full(unit, run.fill, dtype=np.uint8)
+            held = (r.payload.reshape(-1, unit) == fill).all(axis=1)
+            stale |= held & ~(ref_b.reshape(-1, unit) == fill).all(axis=1)
+        if stale.any():
+            bad.append(f"unwritten: plane {name}: {int(stale.sum())} output elements still hold the pre-fill, first element {int(np.flatnonzero(stale)[0])}")
+        live = ~np.repeat(stale, unit)
+        apart = np.zeros(ref_b.size, dtype=bool)
+        for r in rs[1:]:
+            apart |= r.payload != rs[0].payload
+        apart &= live
+        if apart.any():
+            bad.append(f"poison: plane {name}: payloads of the two fills differ in {int(apart.sum())} bytes, first at byte {int(np.flatnonzero(apart)[0])}")
+        off = np.zeros(ref_b.size, dtype=bool)
+        for r in rs:
+            off |= r.payload != ref_b
+        off &= live & ~apart
+        if off.any():
+            bad.append(f"oracle: plane {name}: {int(off.sum())} bytes differ from the expected plane, first at byte {int(np.flatnonzero(off)[0])}")
+        for k, (run, r) in enumerate(zip(runs, rs)):
+            need = fold_guard_bytes(run.row_bytes.get(name, 0))
+            if min(r.front.size, r.back.size) < need:
+                bad.append(f"guard: plane {name}: fill {k}: guards of {r.front.size} / {r.back.size} bytes, the condition is {need}")
+            for side, g in (("front", r.front), ("back", r.back)):
+                d = np.flatnonzero(g != run.fill)
+                if d.size:
+                    where = int(d[0]) if side == "back" else int(d[-1]) - g.size
+                    bad.append(f"guard: plane {name}: fill {k}: {d.size} bytes of the {side} guard were written, nearest at {where:+d} bytes from the payload")
+    for k, run in enumerate(runs):
+        if run.src_now is not None and not np.array_equal(run.src_now, run.src_uploaded):
+            d = np.flatnonzero(run.src_now != run.src_uploaded)
+            bad.append(f"source: fill {k}: {d.size} bytes of the source buffer changed, first at byte {int(d[0])}")
+    return bad
 
 
 # ------------------------------------------------------------------ value-domain streams (tests/test_gpu_values.py)
