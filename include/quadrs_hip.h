@@ -104,6 +104,11 @@ int qd_shift(qd_c32 *buf, size_t n, uint64_t abs_off, double ratio, int mem);
  * Host arithmetic with the platform libm, exactly as the reference does it (O(size), once). */
 int qd_lowpass_design(uint64_t frequency, uint64_t sample_rate, size_t size, float *taps);
 
+/* The W-float table of a window (qd_chain_desc.windowing, qd_rows_desc.windowing, qd_take_fft): 1 is
+ * generate_blackman_harris_window, src/ffts.rs:110-119, in f32 with the platform cosf like the reference; 0 is ones.
+ * Host arithmetic only.  Any other windowing: QD_ERR_INVALID. */
+int qd_window_design(int windowing, size_t W, float *w);
+
 /* bits::scan, src/bits.rs:3-55 (host arithmetic, f64): run-length decode n marks (0 / non-0, e.g. a QD_EPI_MARK_U8 output) at
  * `scale` marks per bit.  half = round(scale / 2) (halves away from zero); a run of the expected value (0 first, flipping after every
  * accepted run) ends where the first stretch of more than `half` wrong values began; an accepted run (longer than half) emits
@@ -161,7 +166,12 @@ typedef struct {
     int32_t  has_range;       /* sparkfft -range min:max; else 0.08 / 1.0 (src/fft.rs:22-23) */
     float    range_min, range_max;
     int32_t  mode;            /* qd_mode: QD_MODE_EXACT (0, the default: the reference's products, order and roundings) or QD_MODE_FAST */
-    int32_t  _pad2;
+    int32_t  windowing;       /* the window of the FFT sinks (NORMS_F32, GLYPH_U8, BUCKET2_U8, MARK_U8): 0 rectangular (none), 1 Blackman-Harris —
+                                 sink sample k of every window is multiplied by qd_window_design(1, width)[k] as Complex<f32> * f32 (two
+                                 separately rounded products, src/ffts.rs:64-68) behind the lowpass (truncated tail outputs included) and any
+                                 shift, in front of the forward FFT; nothing else of the chain changes.  Any other value: QD_ERR_INVALID;
+                                 non-zero with QD_EPI_CF32_BLOCKS (no transform): QD_ERR_INVALID; ignored by QD_EPI_ROWS_F32 (qd_rows_desc's
+                                 window).  No geometry (qd_plan_info, qd_plan_src_range, qd_stages_geometry, qd_rows_geometry) depends on it. */
 } qd_chain_desc;
 
 /* QD_MODE_FAST is a PERMISSION, never the default and never what bench.py's `value` is measured in: the FIR may fuse each
@@ -188,7 +198,8 @@ typedef struct {
     uint32_t kernel_flags;    /* variant bits of the main kernel (0 for the generic kernels): 4 packed lane-per-output FIR, 8 row-aligned
                                  phase 1, 32 straight-line shared FIR, 64 deferred FFT, 128 packed two-output FIR, 256 non-temporal stream loads (65536: only rows no other tile reads), 8192 half-window tiles, 16384 fused FIR (QD_MODE_FAST),
                                  32768 three-stage kernel (producer / FIR / FFT waves on consecutive tiles), 131072 its streaming form (runs of tiles, state carried in LDS), 262144 the streaming kernel as the write sink (QD_EPI_CF32_BLOCKS: producers + FIR waves, no FFT stage),
-                                 524288 the wave-local kernel of chains WITHOUT a lowpass (stride == width: one wave per tile, no workgroup barriers), 1048576 its form with the base butterflies out of the row registers (W = 128 ... 1024; plan-time builds), 2097152 overlapping windows of 2 ... 8 points, a window per lane (plan-time builds);
+                                 524288 the wave-local kernel of chains WITHOUT a lowpass (stride == width: one wave per tile, no workgroup barriers), 1048576 its form with the base butterflies out of the row registers (W = 128 ... 1024; plan-time builds), 2097152 overlapping windows of 2 ... 8 points, a window per lane (plan-time builds),
+                                 4194304 applies the plan's window (qd_chain_desc.windowing; plan-time builds of k_chain);
                                  chosen from the chain's geometry at plan time (built-in kernels: the same predicates, fixed at build time) */
     uint32_t _reserved;
 } qd_plan_info;

@@ -17,7 +17,7 @@ EPI_NORMS_F32, EPI_GLYPH_U8, EPI_BUCKET2_U8, EPI_CF32_BLOCKS, EPI_MARK_U8, EPI_R
 # every symbol include/quadrs_hip.h declares
 SYMBOLS = [
     "qd_last_error", "qd_version", "qd_device_count", "qd_set_device", "qd_pair_bytes", "qd_unpack",
-    "qd_shift_ratio", "qd_shift", "qd_lowpass_design", "qd_lowpass_block", "qd_fft_norm_batch",
+    "qd_shift_ratio", "qd_shift", "qd_lowpass_design", "qd_window_design", "qd_lowpass_block", "qd_fft_norm_batch",
     "qd_plan_create", "qd_plan_destroy", "qd_plan_get_info", "qd_plan_get_taps", "qd_plan_src_range",
     "qd_plan_run", "qd_plan_set_timing", "qd_plan_last_kernel_ms", "qd_gen", "qd_take_fft",
     "qd_device_alloc", "qd_device_free", "qd_device_copy",
@@ -53,7 +53,7 @@ class ChainDesc(C.Structure):
         ("lowpass_hz", C.c_uint64), ("decimate", C.c_uint64), ("taps", C.c_uint64),
         ("width", C.c_uint64), ("stride", C.c_uint64), ("epilogue", C.c_int32),
         ("has_range", C.c_int32), ("range_min", C.c_float), ("range_max", C.c_float),
-        ("mode", C.c_int32), ("_pad2", C.c_int32),
+        ("mode", C.c_int32), ("windowing", C.c_int32),
     ]
 
 
@@ -168,6 +168,7 @@ def lib():
             "qd_shift_ratio": (f64, [i64, u64]),
             "qd_shift": (i32, [vp, sz, u64, f64, i32]),
             "qd_lowpass_design": (i32, [u64, u64, sz, vp]),
+            "qd_window_design": (i32, [i32, sz, vp]),
             "qd_lowpass_block": (i32, [vp, sz, u64, vp, sz, vp, sz, C.POINTER(sz), i32]),
             "qd_fft_norm_batch": (i32, [vp, sz, sz, sz, vp, i32]),
             "qd_plan_create": (i32, [C.POINTER(ChainDesc), C.POINTER(vp)]),

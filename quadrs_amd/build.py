@@ -64,7 +64,7 @@ def build_cli(force=False, verbose=False):
     if not force and os.path.exists(CLI_OUT) and os.path.getmtime(CLI_OUT) >= max(
             os.path.getmtime(CLI_SRC), os.path.getmtime(OUT), os.path.getmtime(DEPS[-1])):
         return CLI_OUT
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", CLI_OUT, CLI_SRC,
+    cmd = ["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", CLI_OUT, CLI_SRC,
            "-L", HERE, "-lquadrs_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + "/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

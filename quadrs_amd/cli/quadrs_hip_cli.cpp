@@ -113,6 +113,7 @@ struct Op {
     std::vector<qd_band> bands; bool pick = false, split = false;      // bands (-bins LO:HI[,LO:HI...] | -split K) [-pick]
     uint32_t px_w = 0, px_h = 0, stretch = 4, marker = 0; float scale = 2.29f;   // picture -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
+    int sink_window = 0;                                                // -window bh|rect of the window-plan verbs (qd_chain_desc.windowing)
 };
 
 typedef std::map<std::string, std::vector<std::string>> ArgMap;
@@ -184,6 +185,17 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
         }
         ArgMap raw = read_just_args(argv, i);
         Op op{};
+        // -window bh|rect (default rect) of every verb that builds a window plan through chain_desc: parsed here, once, with `rows -window`'s words
+        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture"};
+        if (std::find_if(std::begin(kWindowVerbs), std::end(kWindowVerbs), [&](const char *v) { return cmd == v; }) != std::end(kWindowVerbs)) {
+            auto it = raw.find("window");
+            if (it != raw.end()) {
+                if (it->second.size() != 1) bail("'-window' specified more than once");
+                if (it->second[0] != "bh" && it->second[0] != "rect") bail(cmd + " -window takes bh or rect");
+                op.sink_window = it->second[0] == "bh" ? 1 : 0;
+                raw.erase(it);
+            }
+        }
         auto next = [&](const char *err) -> std::string { if (i >= argv.size()) bail(err); return argv[i++]; };
         bool f;
         if (cmd == "from") {
@@ -642,7 +654,7 @@ struct ChainSource {
 };
 
 // what a fused plan is made from: the source, the chain's [shift] [lowpass] (or, for a cascade, its stages) and the sink's windows
-void chain_desc(const ChainSpec &cs, const ChainSource &in, size_t width, uint64_t stride, int epilogue, qd_chain_desc *d, std::vector<qd_stage> *stages) {
+void chain_desc(const ChainSpec &cs, const ChainSource &in, size_t width, uint64_t stride, int epilogue, qd_chain_desc *d, std::vector<qd_stage> *stages, int windowing = 0) {
     *d = qd_chain_desc{};
     d->struct_size = sizeof *d;
     d->format = in.from_gen ? QD_FMT_CF32 : cs.src->format; d->sample_rate = cs.src->sample_rate;
@@ -660,6 +672,7 @@ void chain_desc(const ChainSpec &cs, const ChainSource &in, size_t width, uint64
         if (cs.lowpass) { d->has_lowpass = 1; d->lowpass_hz = cs.lowpass->lp_freq; d->decimate = cs.lowpass->decimate; d->taps = cs.lowpass->size; }
     }
     d->width = width; d->stride = stride; d->epilogue = epilogue;
+    d->windowing = windowing;
 }
 
 int sink_epilogue(const Op &sink) {
@@ -701,7 +714,7 @@ bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
     const bool from_gen = in.from_gen;
     qd_chain_desc d;
     std::vector<qd_stage> stages;
-    chain_desc(cs, in, sink.width, sink.stride, sink_epilogue(sink), &d, &stages);
+    chain_desc(cs, in, sink.width, sink.stride, sink_epilogue(sink), &d, &stages, sink.sink_window);
     d.has_range = sink.has_range; d.range_min = sink.rmin; d.range_max = sink.rmax;
     if (sink.kind == OP_SPARKFFT) printf("sparkfft sample_rate=%" PRIu64 "\n", out_rate);   // printed before any read (src/fft.rs:19)
     qd_plan *plan = nullptr;
@@ -760,6 +773,16 @@ bool run_fused(const ChainSpec &cs, const Op &sink, const Samples &samples) {
     return true;
 }
 
+// -window on the iterator path: sample k of each gathered window times qd_window_design's w[k], as Complex<f32> * f32 — the two separately
+// rounded products the fused plans form (a product alone has nothing to contract with; the build passes -ffp-contract=off all the same)
+void window_gathered(qd_c32 *buf, uint64_t nb, size_t W, const Op &sink) {
+    if (!sink.sink_window) return;
+    std::vector<float> w(W);
+    qd_check(qd_window_design(sink.sink_window, W, w.data()), "window");
+    for (uint64_t i = 0; i < nb; ++i)
+        for (size_t k = 0; k < W; ++k) { qd_c32 &v = buf[i * W + k]; v.re = v.re * w[k]; v.im = v.im * w[k]; }
+}
+
 // FFT + epilogue of nb gathered windows (contiguous, stride W) on the GPU: a no-shift/no-lowpass plan
 std::vector<uint8_t> sink_batch(const qd_c32 *buf, uint64_t nb, size_t W, const Op &sink) {
     qd_chain_desc d{};
@@ -799,6 +822,7 @@ void run_iter_sink(const Samples &s, const Op &sink, bool header_printed = false
     for (uint64_t w0 = 0; w0 < nwin; w0 += batch) {
         uint64_t nb = nwin - w0 < batch ? nwin - w0 : batch;
         for (uint64_t i = 0; i < nb; ++i) s.read_exact_at((w0 + i) * S, buf.data() + i * W, W);
+        window_gathered(buf.data(), nb, W, sink);
         std::vector<uint8_t> out = sink_batch(buf.data(), nb, W, sink);
         if (sink.kind == OP_SPARKFFT) {
             std::string line;
@@ -958,7 +982,7 @@ bool norms_fused(const ChainSpec &cs, const Op &sink, const char *what, const No
     ChainSource in(cs);
     qd_chain_desc d;
     std::vector<qd_stage> stages;
-    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, &d, &stages);
+    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, &d, &stages, sink.sink_window);
     int n_dev = 1;
     if (qd_device_count(&n_dev) != QD_OK || n_dev < 1) n_dev = 1;
     const int parts = in.from_gen ? 1 : g_gpus;
@@ -1016,6 +1040,7 @@ uint64_t iter_norms(const Samples &s, const Op &sink, uint64_t w0, uint64_t nb, 
         try { s.read_exact_at((w0 + i) * sink.stride, buf->data() + i * W, W); } catch (const Fail &) { if (!stop_short) throw; nb = i; }
     }
     if (!nb) return 0;
+    window_gathered(buf->data(), nb, W, sink);
     qd_chain_desc d{};
     d.struct_size = sizeof d;
     d.format = QD_FMT_CF32; d.sample_rate = 1; d.n_samples = nb * W + 1;
@@ -1434,6 +1459,8 @@ void usage() {
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
+            "\nsparkfft, bucket, marks, levels, peaks, means, powers, spreads, quantiles, bands and picture also take [-window bh|rect] (default rect):\n"
+            "a Blackman-Harris window on every window's samples in front of the transform\n"
             "\n\nFormat for FREQUENCY, SAMPLE_RATE, and other suffixes: 123, 123k, 123M, 123G\n");
 }
 
@@ -1500,6 +1527,7 @@ int main(int argc, char **argv) {
                            op.has_slice ? (std::to_string(op.slice_start) + ":" + std::to_string(op.slice_end)).c_str() : "all", op.windowing ? "bh" : "rect");
                     break;
                 }
+                if (op.sink_window) printf("window=bh\n");      // the verb above was given -window bh
             }
             return 0;
         }

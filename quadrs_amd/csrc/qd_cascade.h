@@ -193,6 +193,7 @@ __global__ __launch_bounds__(kCascadeThreads) void k_cascade(const CascadeParams
             } else {
                 v = inter[k];
             }
+            if (C.window) { const float wv = C.window[k]; v.x = v.x * wv; v.y = v.y * wv; }   // the plan's window (qd_chain_desc.windowing): Complex<f32> * f32
             const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
             fb[yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
         }

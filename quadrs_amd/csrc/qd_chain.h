@@ -128,6 +128,22 @@ __device__ __forceinline__ uint8_t glyph_of(const ChainParams &P, float nm) {
     else return glyph_code_ieee(nm, P.rmin, P.rmax, P.gstep);
 }
 
+// The plan's window (qd_chain_desc.windowing: take_fft's product, src/ffts.rs:64-68) on sink sample k of a window, applied where phase 2
+// stores the sample into the FFT buffer — behind the lowpass (truncated tails included) and the shift, in front of the transform:
+// Complex<f32> * f32, two separately rounded products.  Only a geometry with kWindow contains any of it: a plan-time build carries the
+// variant bit kGeoWindow, the runtime-geometry kernels behind a lowpass have instantiations of their own (WinGeo) — the DynGeo ones sit at
+// their scalar-register budget (test_builtin_kernels_do_not_spill) and stay as they are.  Without a lowpass DynGeo tests the pointer.
+template <class GeoT>
+__device__ __forceinline__ float2 win_mul(const ChainParams &P, uint32_t k, float2 v) {
+    if constexpr (GeoT::kWindow) { const float wv = P.window[k]; v.x = v.x * wv; v.y = v.y * wv; }
+    return v;
+}
+template <class GeoT>
+__device__ __forceinline__ float win_mul(const ChainParams &P, uint32_t k, float v) {      // one component (the component-split FIR)
+    if constexpr (GeoT::kWindow) v = v * P.window[k];
+    return v;
+}
+
 // ---------------------------------------------------------------- geometry policies
 
 // (the rules themselves — flag bits, derived constants, predicates, LDS layouts — are qd_geometry.h's; FixedGeo is a view of fixed_rules())
@@ -140,6 +156,7 @@ struct FixedGeo {
     static constexpr bool kRows = false;
     static constexpr FixedRules R = fixed_rules(W_, S_, D_, T_, G_, FIRB_, FIRR_, PAD_, BATCH_, FLAGS_);
     static constexpr uint32_t kFlags = FLAGS_;
+    static constexpr bool kWindow = (FLAGS_ & kGeoWindow) != 0;      // applies ChainParams::window (win_mul)
     // Planar raw tile: the shifted samples are parked as two f32 planes (re / im) instead of interleaved pairs, rows of D floats
     // at a 16-byte aligned pitch DpP with DpP/4 odd.  The component-split FIR then reads FOUR taps of its component with one
     // conflict-free ds_read_b128 (256 B/clk) instead of two with a ds_read2_b32 (128 B/clk): half the LDS-array cycles and
@@ -210,6 +227,7 @@ struct FixedGeo {
 struct DynGeo {
     static constexpr bool kFixed = false;
     static constexpr bool kRows = false;
+    static constexpr bool kWindow = false;
     static constexpr uint32_t kBatch = 1;
     static constexpr uint32_t kFlags = 0, G_ct = 1, W_ct = 1;
     static constexpr bool kPlanar = false, kBakedTaps = false, kPairFir = false, kUnrolledShared = false, kPackedTile = false, kHalfTile = false;
@@ -233,6 +251,12 @@ struct DynGeo {
 // the row's true length: the FFT sink has blk_len == W; the cf32 sink (the read_at blocks a Bluestein width is transformed from) may
 // have a shorter one, truncates against it and stores rows of blk_len samples.  ChainParams::window scales sample k behind the FIR too.
 // Only the kernels instantiated with this policy contain any of it.
+// DynGeo for a windowed plan behind a lowpass (qd_chain_desc.windowing): phase 2 multiplies by ChainParams::window, which is never null here
+struct WinGeo : DynGeo {
+    static constexpr bool kWindow = true;
+    __device__ __forceinline__ explicit WinGeo(const ChainParams &P) : DynGeo(P) {}
+};
+
 struct RowGeo : DynGeo {
     static constexpr bool kRows = true;
     __device__ __forceinline__ explicit RowGeo(const ChainParams &P) : DynGeo(P) {}
@@ -1419,6 +1443,10 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     constexpr bool kFastP1 = fast_p1_ok<FMT, NT, GeoT>(RCH, WHOLE, ALIGNED);
     constexpr bool kHalf = GeoT::kHalfTile;                 // two passes per window (FixedGeo::kHalfTile); `half` = the pass this iteration runs
     static_assert(!kHalf || (kFastP1 && defer_fft_ok<GeoT, HAS_FIR>((uint32_t)NT)), "half-window tiles: row-aligned phase 1 and the deferred FFT");
+    // kGeoWindow: every store of phase 2 into the FFT buffer below goes through win_mul (the deferred forms' two, the shared gather, the
+    // component-split, helper-lane, register-tiled, packed lane-per-output and span FIRs, the plain gather); the flags word must mean this kernel
+    static_assert((GeoT::kFlags & kGeoWindow) == 0 || (GeoT::kFixed && family_of(GeoT::kFlags) == kFamChain), "kGeoWindow: a plan-time build of k_chain");
+    static_assert(!GeoT::kWindow || HAS_FIR || GeoT::kFixed, "WinGeo: behind a lowpass only (without one DynGeo tests the pointer)");
     uint32_t half = 0;
     LaneRot lr[SPL];
     auto load_lane_rot = [&](uint32_t first) {
@@ -1447,6 +1475,16 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     __syncthreads();
 
     const uint64_t n_tiles = (P.n_windows + geo.G - 1) / geo.G;
+    // kGeoWindow on the packed lane-per-output FIR with one output a lane (G W <= NT): the lane's output is sample tid mod W of its window in
+    // every tile, so its table entry is read ONCE, here.  Read where phase 2 stores instead, the load sits behind the FIR in front of an
+    // s_waitcnt vmcnt(0) that also drains the next tile's prefetch (loads retire in order): 4.7 % on the 192-tap / W = 128 recipe.
+    constexpr bool kWinLane = GeoT::kFixed && GeoT::kWindow && GeoT::kPairFir && !kHalf && GeoT::G_ct * GeoT::W_ct <= (uint32_t)NT;
+    float win_lane = 1.f;
+    if constexpr (kWinLane) win_lane = P.window[tid & (W - 1)];
+    auto win_pair = [&](uint32_t k, float2 v) -> float2 {      // the packed lane-per-output FIR's two stores
+        if constexpr (kWinLane) { v.x = v.x * win_lane; v.y = v.y * win_lane; return v; }
+        else return win_mul<GeoT>(P, k, v);
+    };
 
     // Register prefetch pipeline.  Slots whose row does not exist in the tile re-load its last
     // row (an L2 hit) so that every load stays unconditional.
@@ -1780,7 +1818,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                         for (int r = 0; r < 2; ++r) {
                             const uint32_t k = k0 + r;
                             const uint32_t xx = k & ((1u << log_width_d) - 1), yy = k >> log_width_d;
-                            fb_cur[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = jm[r] < T ? snp[r] : full[r];
+                            fb_cur[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_mul<GeoT>(P, k, jm[r] < T ? snp[r] : full[r]);
                         }
                     }
                 } else if (tid < n_out_d) {                    // one lane per complex output
@@ -1790,7 +1828,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     const float2 *rp = raw + (size_t)((kHalf ? tid : g * S + k) + geo.a0) * Dp;
                     const float2 v = QD_DBG(P, 2) ? rp[0] : fir_pair<GeoT>(rp, jmax, tapl);      // dbg: timing-only ablation
                     const uint32_t xx = k & ((1u << log_width_d) - 1), yy = k >> log_width_d;
-                    fb_cur[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
+                    fb_cur[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_pair(k, v);
                 }
             } else if (kHalf && half != 0) {                   // the previous window was transformed beside this window's first pass
             } else if (kQuadFft && !one_wave_sink(P.epi)) {   // one long window: four spare waves share its FFT + epilogue
@@ -1914,7 +1952,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                 const uint32_t g = o >> logW, k = o & (W - 1);
                 const uint32_t qi = g * S + k;
                 const bool tr = (W - k) * D + T / 2 < T;
-                const float2 v = tr ? trc[qi] : dec[qi];
+                const float2 v = win_mul<GeoT>(P, k, tr ? trc[qi] : dec[qi]);
                 const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
                 fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
             }
@@ -1940,7 +1978,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     v = QD_DBG(P, 2) ? xp[0] : fir_comp<GeoT>(xp, jmax, tapl);     // dbg: timing-only ablation
                 }
                 const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-                reinterpret_cast<float *>(fb + (g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base))[part] = v;
+                reinterpret_cast<float *>(fb + (g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base))[part] = win_mul<GeoT>(P, k, v);
             }
         } else
         if constexpr (GeoT::kFixed && !GeoT::kShared && GeoT::kFirTile > 1 && HAS_FIR && GeoT::helper_ok((uint32_t)NT) && !GeoT::kPackedTile) {
@@ -1961,7 +1999,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                         const uint32_t k = k0 + r;
                         if (k + NTR < W) {                               // the truncated ones belong to the helper lanes
                             const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-                            fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = full[r];
+                            fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_mul<GeoT>(P, k, full[r]);
                         }
                     }
                 }
@@ -1975,7 +2013,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     const uint32_t jmax = (W - k) * D + T / 2;           // < T for these k
                     const float2 v = fir_prefix<GeoT>(raw, (g * S + k) * D + GeoT::c, jmax, tapl);
                     const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-                    fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
+                    fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_mul<GeoT>(P, k, v);
                 }
             }
         } else
@@ -1996,7 +2034,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                 for (int r = 0; r < R; ++r) {
                     const uint32_t k = k0 + r;
                     const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-                    fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = jm[r] < T ? snp[r] : full[r];
+                    fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_mul<GeoT>(P, k, jm[r] < T ? snp[r] : full[r]);
                 }
             }
         } else
@@ -2008,7 +2046,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                 const float2 *rp = raw + (size_t)(g * S + k + geo.a0) * Dp;
                 const float2 v = QD_DBG(P, 2) ? rp[0] : fir_pair<GeoT>(rp, jmax, tapl);      // dbg: timing-only ablation
                 const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-                fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
+                fb[(g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base)] = win_pair(k, v);
             }
         } else
         if constexpr (!GeoT::kFixed || !GeoT::kShared) if (!shared)
@@ -2047,7 +2085,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             // bitreversed_transpose::<4>(base_len, ..): out[y + rev(x)*base] = in[x + y*width]
             const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
             const uint32_t pos = cf32_out ? k : yy + (rev4(xx, geo.layers) << geo.log_base);   // write sink: natural order
-            fb[(g << logW) + pos] = make_float2(accr, acci);
+            fb[(g << logW) + pos] = win_mul<GeoT>(P, k, make_float2(accr, acci));
         }
         QD_STAMP_AT(2);
         // Park this tile's window(s): remember where their output goes, advance to the next tile.  The FFT + epilogue run
@@ -2266,6 +2304,7 @@ constexpr bool pipe_geometry_ok(int rch) {
 
 template <int FMT, int NCO, class GeoT, int RCH, int LB, int NT = kPipeThreads>
 __global__ __launch_bounds__(NT, LB) void k_chain_pipe(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     static_assert(NT == 320 || NT == 384, "four producer waves + the FIR wave (+ an FFT wave)");
     constexpr bool kFftWave = NT == 384;          // a sixth wave transforms the PREVIOUS window while the FIR wave filters this one (two FFT slots)
     using FT = FmtTraits<FMT>;
@@ -2554,6 +2593,7 @@ template <class GeoT> constexpr uint32_t pipe3_q_pad() { return (uint32_t)GeoT::
 
 template <int FMT, int NCO, class GeoT, int RCH, int LB>
 __global__ __launch_bounds__(kPipe3Threads, LB) void k_chain_pipe3(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     using FT = FmtTraits<FMT>;
     using Vec = typename FT::Vec;
     constexpr int SPL = FT::SPL;
@@ -2947,6 +2987,7 @@ struct Pipe3S {
 
 template <int FMT, int NCO, class GeoT, int RN_, int LB, int PT_ = kPipe3Prod>
 __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512), LB) void k_chain_pipe3s(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     using FT = FmtTraits<FMT>;
     using Vec = typename FT::Vec;
     using K = Pipe3S<FMT, GeoT, PT_>;
@@ -3296,6 +3337,7 @@ template <int FMT> struct SparkTraits {
 
 template <int FMT, int NCO, class GeoT, int NCH, int LB, int EPI = -1 /* plan-time builds: the plan's sink, compile-time (norms 0 / glyph 1: the lean epilogue below); -1: P.epi at run time */>
 __global__ __launch_bounds__(kThreads, LB) void k_spark(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     using FT = FmtTraits<FMT>;
     using Vec = typename FT::Vec;
     using ST = SparkTraits<FMT>;
@@ -3591,6 +3633,7 @@ template <class GeoT> struct Spark2 {
 
 template <int FMT, int NCO, class GeoT, int LB, int EPI /* the plan's qd_epilogue, compile-time: the tile loop carries no sink dispatch */>
 __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     using K = Spark2<GeoT>;
     using FT = FmtTraits<FMT>;
     static_assert(K::ok, "k_spark2: W = base * 16 or base * 64");
@@ -3859,6 +3902,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
 
 template <int FMT, class GeoT, int LB, int EPI /* the plan's qd_epilogue */>
 __global__ __launch_bounds__(kThreads, LB) void k_spark0(const ChainParams P) {
+    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
     using FT = FmtTraits<FMT>;
     constexpr uint32_t W = GeoT::W, S = GeoT::S, BPS = FT::BPS, ND = W * BPS / 4;       // dwords per window
     static_assert(GeoT::kFixed && GeoT::R.spark0_ok(BPS),

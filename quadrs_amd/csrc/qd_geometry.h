@@ -38,6 +38,7 @@ constexpr uint32_t kGeoWriteSink = 262144;      // bit 18: the streaming kernel 
 constexpr uint32_t kGeoSpark = 524288;          // bit 19: the wave-local kernels of chains without a lowpass (k_spark)
 constexpr uint32_t kGeoSparkReg = 1048576;      // bit 20: ... with the first FFT pass out of registers (k_spark2)
 constexpr uint32_t kGeoSparkDirect = 2097152;   // bit 21: ... a window of 2 ... 8 points per lane, no LDS (k_spark0)
+constexpr uint32_t kGeoWindow = 1u << 22;       // bit 22: applies the plan's window (ChainParams::window) where phase 2 stores into the FFT buffer; k_chain only
 
 // cache policy (buffer-load aux operand) of the phase-1 stream loads: nt / sc0 / sc1
 constexpr int ct_load_aux(uint32_t flags) { return ((flags & kGeoNtLoads) ? 2 : 0) | ((flags & kGeoLoadSc0) ? 1 : 0) | ((flags & kGeoLoadSc1) ? 16 : 0); }

@@ -323,13 +323,21 @@ FftLayout fft_layout(uint64_t W) {
 // past 2^28 rad of phase, which get a plan-time build anyway) are budgeted for three.  Budgeting ALL shifted kernels for three waves
 // removed the scratch too but cost 6-18 % on 256 MiB streams (profiles/r04/generic_rate.log).  tests/test_abi_cpu.py audits every kernel.
 constexpr int dyn_lb(int nco) { return nco == 2 ? 3 : 4; }
-template <int F, int NCO, bool FI>
+template <int F, int NCO, bool FI, class G = DynGeo>
 chain_fn pick_dyn(bool aligned) {
-    return aligned ? k_chain<F, NCO, DynGeo, FI, 4, false, true, dyn_lb(NCO)> : k_chain<F, NCO, DynGeo, FI, 4, false, false, dyn_lb(NCO)>;
+    return aligned ? k_chain<F, NCO, G, FI, 4, false, true, dyn_lb(NCO)> : k_chain<F, NCO, G, FI, 4, false, false, dyn_lb(NCO)>;
 }
 
+// (windowed plans behind a lowpass: the WinGeo instantiations; without a lowpass the DynGeo kernels test ChainParams::window themselves)
 template <int F>
-chain_fn pick_fmt(int nco, bool fir, bool aligned) {
+chain_fn pick_fmt(int nco, bool fir, bool aligned, bool windowed) {
+    if (windowed && fir) {
+        switch (nco) {
+        case 0: return pick_dyn<F, 0, true, WinGeo>(aligned);
+        case 1: return pick_dyn<F, 1, true, WinGeo>(aligned);
+        default: return pick_dyn<F, 2, true, WinGeo>(aligned);
+        }
+    }
     switch (nco) {
     case 0: return fir ? pick_dyn<F, 0, true>(aligned) : pick_dyn<F, 0, false>(aligned);
     case 1: return fir ? pick_dyn<F, 1, true>(aligned) : pick_dyn<F, 1, false>(aligned);
@@ -337,8 +345,8 @@ chain_fn pick_fmt(int nco, bool fir, bool aligned) {
     }
 }
 
-chain_fn pick_generic(int fmt, int nco, bool fir, bool aligned) {
-#define QD_X(F) pick_fmt<F>(nco, fir, aligned)
+chain_fn pick_generic(int fmt, int nco, bool fir, bool aligned, bool windowed = false) {
+#define QD_X(F) pick_fmt<F>(nco, fir, aligned, windowed)
     switch (fmt) { QD_FMT_CASES(QD_X) }
 #undef QD_X
     return nullptr;
@@ -739,6 +747,7 @@ struct qd_plan {
     // take_fft mode (generic kernels): per-window start offsets and an f32 window, both on the device
     const uint64_t *row_offsets_d = nullptr;
     const float *window_d = nullptr;
+    float *win_own_d = nullptr;               // qd_chain_desc.windowing == 1: the plan's own copy of blackman_harris(width); window_d points at it
     // QD_EPI_ROWS_F32 (qd_plan_take_fft): blk_len is the row width W (any), W / S the row-mode kernel's power-of-two width and LDS pitch
     bool rows = false, rows_blue = false;     // rows_blue: W is not a power of two (k_bluestein; behind a lowpass over the rows' read_at blocks)
     RowTab rows_tab512;                       // k_bluestein's loader behind a shift: NCO rows of 512 samples
@@ -1381,7 +1390,7 @@ bool geometry_recipe(const qd_plan *p, uint32_t T_lds, Candidate *r) {
 }
 
 // The candidates of a chain plan without a tile hint, best first; every list ends in a kernel that is always to be had.
-std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
+std::vector<Candidate> chain_candidates_of(const qd_plan *p, uint32_t T_lds, bool windowed) {
     const qd_chain_desc &d = p->d;
     const int policy = p->opt.kernel_policy, spl = spl_of(d.format), bps = bps_of(d.format);
     const uint32_t W = p->W, S = p->S;
@@ -1393,7 +1402,7 @@ std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
     Candidate generic = plain;
     generic.wg_regs = dyn_lb(p->nco);
     // shape-specialised built-in kernels (kFixed): exact arithmetic; QD_MODE_FAST prefers a fused build of the shape's recipe
-    const FixedEntry *fixed = (p->has_fir && !write_sink && policy != QD_KERNEL_GENERIC) ? find_fixed(d.format, p->nco, W, S, p->D, p->T) : nullptr;
+    const FixedEntry *fixed = (p->has_fir && !write_sink && policy != QD_KERNEL_GENERIC && !windowed) ? find_fixed(d.format, p->nco, W, S, p->D, p->T) : nullptr;
     const bool fast = d.mode == QD_MODE_FAST && p->has_fir && jit_ok && !write_sink;
     Candidate recipe;
     const bool has_recipe = jit_ok && p->has_fir && (!fixed || fast) && geometry_recipe(p, T_lds, &recipe);
@@ -1454,7 +1463,7 @@ std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
         c.spark_R = R; c.spark_jt_lds = p->has_shift;
         return spark_build(c, p->nco, W, (int)(c.spark_ts / (64u * (uint32_t)spl)));
     };
-    const bool spark_ok = !p->has_fir && W <= kSparkMaxW && !write_sink && policy != QD_KERNEL_GENERIC;
+    const bool spark_ok = !p->has_fir && W <= kSparkMaxW && !write_sink && policy != QD_KERNEL_GENERIC && !windowed;
     if (spark_ok && S == W) {
         const uint32_t ts = spark_tile(W, p->nco);
         if (!jit_ok) return {spark(ts, 0, spark_lb(ts, p->nco))};
@@ -1489,6 +1498,22 @@ std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
     return {generic};
 }
 
+// A windowed plan (qd_chain_desc.windowing): the unwindowed list without the table and wave-local kernels, filtered down to the plan-time
+// builds of k_chain — which get the variant bit kGeoWindow — and the generic kernel, which tests ChainParams::window.
+std::vector<Candidate> chain_candidates(const qd_plan *p, uint32_t T_lds) {
+    const bool windowed = p->d.windowing != 0 && p->d.epilogue != QD_EPI_CF32_BLOCKS;
+    std::vector<Candidate> list = chain_candidates_of(p, T_lds, windowed);
+    if (!windowed) return list;
+    std::vector<Candidate> out;
+    for (Candidate c : list) {
+        if (c.src == Candidate::kGeneric) { out.push_back(c); continue; }
+        if (c.src != Candidate::kBuild || family_of(c.flags) != kFamChain) continue;
+        c.flags |= kGeoWindow; c.key.flags |= kGeoWindow;
+        out.push_back(c);
+    }
+    return out;
+}
+
 // Commits the chosen candidate to the plan: tiling, LDS sizes, kernels (jit_fn: the plan-time build, when it is one).
 int commit_candidate(qd_plan *p, const Candidate &c, hipFunction_t jit_fn, uint32_t T_lds) {
     const int fmt = p->d.format;
@@ -1512,8 +1537,9 @@ int commit_candidate(qd_plan *p, const Candidate &c, hipFunction_t jit_fn, uint3
     p->geo.Dp = p->D + ((p->D % 2 == 0) ? 1 : 0);
     if ((uint64_t)raw_elems * p->D >= (1ull << 32)) return fail(QD_ERR_UNSUPPORTED, "tile too large");
     // (a k_spark2 plan's built-in kernel is the runtime-width k_spark of its tile: take_fft's row-offset launches run it)
-    p->fn = c.fixed ? c.fixed->fn : (p->spark ? pick_spark(fmt, p->nco, c.spark_ts) : pick_generic(fmt, p->nco, p->has_fir, true));
-    p->fn_unaligned = pick_generic(fmt, p->nco, p->has_fir, false);
+    const bool windowed = p->d.windowing != 0 && p->d.epilogue != QD_EPI_CF32_BLOCKS;
+    p->fn = c.fixed ? c.fixed->fn : (p->spark ? pick_spark(fmt, p->nco, c.spark_ts) : pick_generic(fmt, p->nco, p->has_fir, true, windowed));
+    p->fn_unaligned = pick_generic(fmt, p->nco, p->has_fir, false, windowed);
     if (!p->fn || !p->fn_unaligned) return fail(QD_ERR_UNSUPPORTED, "no kernel built for this format (QD_DEV_FAST build?)");
     return QD_OK;
 }
@@ -1552,6 +1578,16 @@ double qd_shift_ratio(int64_t frequency, uint64_t sample_rate) {
 int qd_lowpass_design(uint64_t frequency, uint64_t sample_rate, size_t size, float *taps) {
     if (!taps) return fail(QD_ERR_INVALID, "taps is NULL");
     design_taps(frequency, sample_rate, size, taps);
+    return QD_OK;
+}
+
+int qd_window_design(int windowing, size_t W, float *w) {
+    if (!w) return fail(QD_ERR_INVALID, "w is NULL");
+    if (windowing != 0 && windowing != 1) return fail(QD_ERR_INVALID, "unknown windowing %d", windowing);
+    if (windowing == 0) { for (size_t i = 0; i < W; ++i) w[i] = 1.0f; return QD_OK; }
+    std::vector<float> win;
+    blackman_harris(W, &win);
+    if (W) memcpy(w, win.data(), W * sizeof(float));
     return QD_OK;
 }
 
@@ -1664,6 +1700,10 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
     const uint64_t in_bytes = (uint64_t)d.n_samples * bps_of(d.format);
     const bool may_compile = policy == QD_KERNEL_SPECIALISE || hinted || in_bytes >= (1ull << 30) || d.mode == QD_MODE_FAST;
     if (p->has_fir) { p->taps_h.resize(p->T); design_taps(d.lowpass_hz, d.sample_rate, p->T, p->taps_h.data()); }
+    if (hinted && d.windowing) {
+        if (family_of(hint.flags) != kFamChain) return fail(QD_ERR_UNSUPPORTED, "tile_hint: only k_chain builds apply the plan's window");
+        hint.flags |= kGeoWindow;
+    }
     const std::vector<Candidate> cands = hinted ? std::vector<Candidate>{chain_build(p, hint, true)} : chain_candidates(p, T_lds);
     const Candidate *won = nullptr;
     std::string why;
@@ -2057,6 +2097,16 @@ int rows_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t rate) {
     return QD_OK;
 }
 
+// qd_chain_desc.windowing == 1: the device copy of blackman_harris(width) that every launch of the plan hands its kernel (plan_params)
+int window_init(qd_plan *p) {
+    std::vector<float> win;
+    blackman_harris(p->d.width, &win);
+    HIPCHK(hipMalloc(&p->win_own_d, win.size() * sizeof(float)));
+    HIPCHK(hipMemcpy(p->win_own_d, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->window_d = p->win_own_d;
+    return QD_OK;
+}
+
 // a window larger than the LDS tile, windows side by side (plan_init's kNeedComposite): two plans behind the parent's handle
 int composite_init(qd_plan *p, uint64_t rate) {
     if (p->opt.n_shards > 1) return fail(QD_ERR_UNSUPPORTED, "a window larger than the LDS tile runs as a two-stage plan, which is not sharded inside one process");
@@ -2066,6 +2116,7 @@ int composite_init(qd_plan *p, uint64_t rate) {
     memset(copt.tile_hint, 0, sizeof copt.tile_hint);
     qd_chain_desc a = d;                         // stage A: the same source chain into read_at blocks of W decimated samples
     a.stride = d.width; a.epilogue = QD_EPI_CF32_BLOCKS; a.has_range = 0;
+    a.windowing = 0;                             // (the write sink has no transform: the window is stage B's)
     int rc = qd_plan_create_ex(&a, &copt, &p->cmp_a);
     if (rc) return rc;
     qd_chain_desc b{};                           // stage B: W-point windows side by side over the decimated stream
@@ -2074,6 +2125,7 @@ int composite_init(qd_plan *p, uint64_t rate) {
     b.n_samples = d.epilogue == QD_EPI_BUCKET2_U8 ? (p->n_windows + 1) * d.width : p->n_windows * d.width + 1;      // exactly n_windows windows (src/fft.rs:28,65 / :86)
     b.width = d.width; b.stride = d.width; b.epilogue = d.epilogue; b.mode = d.mode;
     b.has_range = d.has_range; b.range_min = d.range_min; b.range_max = d.range_max;
+    b.windowing = d.windowing;
     rc = qd_plan_create_ex(&b, &copt, &p->cmp_b);
     if (rc) return rc;
     p->geo.G = 1;
@@ -2121,6 +2173,10 @@ int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stag
     rc = check_options(options, &opt);
     if (rc) return rc;
     qd_chain_desc d = *desc;
+    if (d.epilogue != QD_EPI_ROWS_F32) {       // (that sink's window is qd_rows_desc's: the field is ignored like stride and range_*)
+        if (d.windowing != 0 && d.windowing != 1) return fail(QD_ERR_INVALID, "unknown windowing %d", d.windowing);
+        if (d.windowing && d.epilogue == QD_EPI_CF32_BLOCKS) return fail(QD_ERR_INVALID, "QD_EPI_CF32_BLOCKS has no transform to window: windowing must be 0");
+    }
     if (g.routed) {                  // the one-stage description holds it: the same plan, kernels and bytes whichever entry point
         if (g.s0 >= 0) { d.has_shift = 1; d.shift_hz = stages[g.s0].shift_hz; }
         if (g.l1 >= 0) { d.has_lowpass = 1; d.lowpass_hz = stages[g.l1].lowpass_hz; d.decimate = stages[g.l1].decimate; d.taps = stages[g.l1].taps; }
@@ -2143,6 +2199,7 @@ int create_plan(const qd_chain_desc *desc, const qd_stage *stages, size_t n_stag
     if (d.epilogue == QD_EPI_ROWS_F32) rc = rows_init(p, d, g.len, g.rate);      // (stages_geo has refused a cascade)
     else if (!g.routed) rc = cascade_init(p, g, stages);
     else if ((rc = plan_init(p, d, g.len, g.rate)) == kNeedComposite) rc = composite_init(p, g.rate);
+    if (rc == QD_OK && !p->rows && !p->cmp_a && d.windowing == 1) rc = window_init(p);      // (a two-stage plan's window is stage B's)
     if (rc == QD_OK && !p->rows) rc = make_shards(p, desc, stages, n_stages, list);
     if (rc) { qd_plan_destroy(p); return rc; }
     *out = p;
@@ -2202,6 +2259,7 @@ int qd_plan_destroy(qd_plan *p) {
     free_streaming(p);
     for (void *q : {(void *)p->c_h1, (void *)p->c_h2, (void *)p->c_jtab}) if (q) (void)hipFree(q);
     if (p->taps_d) (void)hipFree(p->taps_d);
+    if (p->win_own_d) (void)hipFree(p->win_own_d);
     if (p->tw_d) (void)hipFree(p->tw_d);
     if (p->jtab_d) (void)hipFree(p->jtab_d);
     if (p->jtab256_d) (void)hipFree(p->jtab256_d);
@@ -2272,7 +2330,7 @@ int qd_plan_kernel_name(const qd_plan *p, char *buf, size_t cap) {
     char geo[160];
     if (p->jit_fn || p->fixed)
         snprintf(geo, sizeof geo, "FixedGeo<%u, %u, %u, %u, %u, ..., %u>", p->W, p->S, p->D, p->T, p->geo.G, p->kflags);
-    else snprintf(geo, sizeof geo, "DynGeo");
+    else snprintf(geo, sizeof geo, (p->d.windowing && p->has_fir) ? "DynGeo with the plan's window (WinGeo)" : "DynGeo");
     snprintf(buf, cap, "%s<fmt %d, nco %d, %s>, %d threads, %s", kFamilies[plan_family(p)].name, fmt, p->nco, geo, p->launch_nt,
              p->jit_fn ? "plan-time build" : (p->fixed || p->spark ? "built-in" : "generic"));
     return QD_OK;

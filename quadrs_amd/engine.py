@@ -39,6 +39,16 @@ def lowpass_design(frequency, sample_rate, size):
     return out
 
 
+WINDOW_RECT, WINDOW_BH = 0, 1      # qd_chain_desc.windowing / qd_rows_desc.windowing
+
+
+def window_design(windowing, W):
+    """qd_window_design: the W-float table of a window — ones (WINDOW_RECT) or generate_blackman_harris_window (WINDOW_BH, src/ffts.rs:110-119)."""
+    out = np.zeros(int(W), dtype=np.float32)
+    check(lib().qd_window_design(int(windowing), int(W), _np_ptr(out)))
+    return out
+
+
 def unpack(fmt, data):
     """FileFormat::to_cf32 over a block (src/lib.rs:231-255) on the GPU; returns float32 (n,2)."""
     data = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
@@ -578,7 +588,7 @@ class Plan:
     stages=[("shift", f), ("lowpass", (frequency, decimate, size)), ...] any stage list the CLI folds (qd_plan_create_stages)."""
 
     def __init__(self, fmt, sample_rate, n_samples, shift_hz=None, lowpass=None, width=128, stride=None,
-                 epilogue=_ffi.EPI_NORMS_F32, rng=None, options=None, mode=_ffi.MODE_EXACT, stages=None, **option_kw):
+                 epilogue=_ffi.EPI_NORMS_F32, rng=None, options=None, mode=_ffi.MODE_EXACT, stages=None, windowing=0, **option_kw):
         if stages is not None and (shift_hz is not None or lowpass is not None):
             raise ValueError("stages= describes the whole chain: it does not combine with shift_hz= / lowpass=")
         self.stages = list(stages) if stages is not None else None
@@ -596,6 +606,7 @@ class Plan:
         d.stride = width if stride is None else stride
         d.epilogue = epilogue
         d.mode = mode            # MODE_FAST: permission to fuse the FIR's multiply-adds (never the default)
+        d.windowing = int(windowing)     # WINDOW_BH: sink sample k of every window times window_design(1, width)[k], in front of the FFT
         if rng is not None:
             d.has_range, d.range_min, d.range_max = 1, rng[0], rng[1]
         self.desc = d
