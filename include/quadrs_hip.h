@@ -792,6 +792,64 @@ int qd_plan_picture(qd_plan *plan, const void *src, int src_mem, uint64_t src_fi
                     uint64_t first_window, uint64_t n_windows, const qd_picture_desc *desc,
                     uint8_t *pixels, int out_mem, uint64_t *painted, void *stream);
 
+/* ------------------------------------------------------------------ burst list of a norms plan
+ * What happened when: a threshold per bin, applied to windows [w0, w0 + n) of a QD_EPI_NORMS_F32 plan of width W (exactly the f32 values
+ * the norms sink writes), and the list of on/off runs per bin.  `thresholds` is a host array of W f32 in fftshifted bin order.  This is
+ * the project's own definition; the reference has no counterpart.
+ *
+ * Admissible thresholds.  Write a(v) = bits(v) & 0x7fffffff and t_b = bits(thresholds[b]).  A threshold is admissible if its sign bit is
+ * clear and it is not a NaN (t_b <= 0x7f800000: +0.0 and +inf are allowed); a NaN of either sign is admissible too and MASKS the bin.
+ * Anything else (negative numbers, -0.0, -inf) is QD_ERR_INVALID.
+ * On cells.  Cell (i, b) is on when the bin is not masked, a(v) <= 0x7f800000 (a NaN value is never on) and a(v) >= t_b: the sign of a
+ * value is dropped, by qd_plan_pool's rule, and the comparison is one of bit patterns, which for these operands is the f32 comparison.
+ * A threshold of 0 turns on every non-NaN cell, one of +inf only +inf.
+ * Bursts.  A burst is a maximal run of on cells in one bin: windows [first, first + length) of the range, counted from the range's first
+ * window, all on, with window first - 1 and window first + length off or outside the range (a run is cut at the range's edges).
+ * Peak.  `peak` is the greatest a(v) of the run as an f32 (+inf is possible), `peak_at` the first window of the run, range-relative,
+ * that attains it.
+ * Which are kept.  A burst is kept iff length >= min_len; min_len >= 1, and 0 is QD_ERR_INVALID.
+ * Order.  Ascending (first + length - 1, bin): the last window of the burst, then the bin.  No two bursts share that key.  It is the
+ * order of an event log: a burst is reported when it ends.
+ * Counts.  *found is the number of kept bursts, always the full count; the list receives the first min(found, cap) of them in that
+ * order, and its bytes past that are not touched.  on_counts[b] (optional) is the number of on cells of bin b over the range, the
+ * bin's occupancy at this threshold, not filtered by min_len.
+ * Determinism.  Every output is an integer count, an integer max or an index: no batch, chunk, piece, memory kind, cap or launch order
+ * changes a byte. */
+typedef struct qd_burst { uint64_t first, length, peak_at; uint32_t bin; float peak; } qd_burst;   /* 32 bytes, little-endian as it lies */
+#define QD_BURSTS_WORDS 3          /* u64 of state per bin: first window of the open run or ~0, its peak_at, its peak bits */
+/* A call's list workspace (a list that is not device memory, cap x 32 bytes) is at most this; above it qd_plan_bursts is QD_ERR_UNSUPPORTED. */
+#define QD_BURSTS_MAX_WORKSPACE (1ull << 30)
+
+/* The CPU twin, byte for byte.  It is stateful because a run crosses parts: `state` is QD_BURSTS_WORDS*width + 1 u64 of host memory,
+ * the last word being the next window expected.  _init: no run open, next window 0, on_counts (may be NULL) zeroed.
+ * _fold takes windows at ... at+n-1 of the range (n rows of `width` host f32); `at` must equal the state's next window, else
+ * QD_ERR_INVALID.  A burst is detected at the first off window after it: row i emits the runs that ended at i-1, by bin ascending, so
+ * the order of emission is the order of the list.  *found is in/out and keeps counting past cap; record number *found goes to
+ * list[*found] while that is below cap.  on_counts (may be NULL) is in/out.
+ * _finish closes the runs still open, with last window next-1, by bin ascending, and leaves the state as _init does.
+ * Any partition of a range into folds followed by _finish gives exactly the list of the definition; n == 0 folds are fine.
+ * QD_ERR_INVALID: width 0, NULL state, thresholds or found, an inadmissible threshold, min_len == 0, list == NULL with cap > 0, norms
+ * NULL with n > 0. */
+int qd_bursts_init  (uint64_t *state, uint64_t *on_counts /* may be NULL */, uint32_t width);
+int qd_bursts_fold  (uint64_t *state, uint32_t width, const float *thresholds, uint64_t min_len, uint64_t at,
+                     const float *norms, uint64_t n, qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts);
+int qd_bursts_finish(uint64_t *state, uint32_t width, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found);
+/* The burst list of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and `stream` as
+ * for qd_plan_bands (device, host and pinned sources), and so are the refusals and a cascade's short read.  `list` (cap records) and
+ * on_counts (W u64, may be NULL) are of out_mem memory (host, pinned or device); `found` and `thresholds` are host memory, and the call
+ * returns after everything is complete.  A list that is not device memory goes through a workspace of cap x 32 bytes that is copied
+ * down once (min(found, cap) records of it).  cap == 0 with list == NULL counts only.  The windows go batch by batch through the plan's
+ * own kernel into a device carrier and are walked from there; runs are carried from batch to batch on the device.  A fold leaves
+ * qd_plan_get_stats alone.
+ * QD_ERR_INVALID: any epilogue other than QD_EPI_NORMS_F32, thresholds or found NULL, an inadmissible threshold, min_len == 0, list NULL
+ * with cap > 0, an unknown memory kind.  QD_ERR_UNSUPPORTED: a plan created with shards (run one range on one device; joining lists
+ * across a seam is the caller's job), a list workspace above QD_BURSTS_MAX_WORKSPACE, a width above 131072.  QD_ERR_SHORT: a range past
+ * the sink's loop (the outputs are not touched), and for a cascade a range past qd_plan_complete_windows: the complete part is folded,
+ * and the open runs close at the last complete window.  n_windows == 0: QD_OK with *found = 0, on_counts zeroed and the list untouched. */
+int qd_plan_bursts  (qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                     uint64_t first_window, uint64_t n_windows, const float *thresholds, uint64_t min_len,
+                     qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

@@ -33,6 +33,7 @@ SYMBOLS = [
     "qd_density_init", "qd_density_fold", "qd_density_merge", "qd_density_quantile", "qd_plan_density",
     "qd_bands_fold", "qd_plan_bands",
     "qd_picture_geometry", "qd_picture_color", "qd_picture_init", "qd_picture_fold", "qd_plan_picture",
+    "qd_bursts_init", "qd_bursts_fold", "qd_bursts_finish", "qd_plan_bursts",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
@@ -41,6 +42,7 @@ SPREAD_WORDS = 28
 DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
 BANDS_MAX, BAND_NONE = 255, 0xffffffff
 PICTURE_MAX_WORKSPACE = 1 << 30
+BURSTS_WORDS, BURSTS_MAX_WORKSPACE = 3, 1 << 30
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -233,6 +235,10 @@ def lib():
             "qd_picture_init": (i32, [vp, C.POINTER(PictureDesc)]),
             "qd_picture_fold": (i32, [vp, C.POINTER(PictureDesc), C.c_uint32, u64, vp, u64]),
             "qd_plan_picture": (i32, [vp, vp, i32, u64, u64, u64, u64, C.POINTER(PictureDesc), vp, i32, C.POINTER(u64), vp]),
+            "qd_bursts_init": (i32, [vp, vp, C.c_uint32]),
+            "qd_bursts_fold": (i32, [vp, C.c_uint32, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), vp]),
+            "qd_bursts_finish": (i32, [vp, C.c_uint32, u64, vp, u64, C.POINTER(u64)]),
+            "qd_plan_bursts": (i32, [vp, vp, i32, u64, u64, u64, u64, vp, u64, vp, u64, C.POINTER(u64), vp, i32, vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -112,6 +112,8 @@ struct Op {
     std::vector<double> qs; std::vector<std::string> q_names;         // quantiles -q 0.5[,0.9,...]
     std::vector<qd_band> bands; bool pick = false, split = false;      // bands (-bins LO:HI[,LO:HI...] | -split K) [-pick]
     uint32_t px_w = 0, px_h = 0, stretch = 4, marker = 0; float scale = 2.29f;   // picture -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29]
+    bool has_level = false, has_times = false; float level = 0, times = 1; std::string levels_file;   // bursts (-level X | -levels FILE) [-times K]
+    uint64_t min_len = 1, cap = 1048576, print_n = 0;                   // bursts [-min 1] [-cap 1048576] [-print 0]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
     int sink_window = 0;                                                // -window bh|rect of the window-plan verbs (qd_chain_desc.windowing)
 };
@@ -186,7 +188,7 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
         ArgMap raw = read_just_args(argv, i);
         Op op{};
         // -window bh|rect (default rect) of every verb that builds a window plan through chain_desc: parsed here, once, with `rows -window`'s words
-        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture"};
+        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture", "bursts"};
         if (std::find_if(std::begin(kWindowVerbs), std::end(kWindowVerbs), [&](const char *v) { return cmd == v; }) != std::end(kWindowVerbs)) {
             auto it = raw.find("window");
             if (it != raw.end()) {
@@ -386,6 +388,39 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             if (op.pick && op.bands.size() > 36) bail("bands -pick prints one digit a window: at most 36 bands");
             ensure_empty(m);
             op.prefix = next("'bands' requires a prefix argument");
+        } else if (cmd == "bursts") {
+            // not in the reference's grammar: a threshold per fftshifted bin applied to the windows sparkfft would print, and the list of
+            // on/off runs per bin (qd_plan_bursts): what happened when
+            auto m = no_duplicates(raw);
+            op.kind = OP_BURSTS;
+            std::string v = take(m, "width", &f);
+            op.width = f ? (size_t)parse_si_u64(v) : 128;
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            auto number = [&](const std::string &t, const char *flag) {
+                char *e = nullptr;
+                const float x = strtof(t.c_str(), &e);
+                if (t.empty() || *e) bail(std::string("bursts ") + flag + " takes a number: '" + t + "'");
+                return x;
+            };
+            v = take(m, "level", &f);
+            op.has_level = f;
+            if (f) op.level = number(v, "-level");
+            v = take(m, "levels", &f);
+            if (f && op.has_level) bail("bursts takes -level or -levels, not both");
+            if (!f && !op.has_level) bail("bursts requires -level or -levels");
+            if (f) op.levels_file = v;
+            v = take(m, "times", &f);
+            op.has_times = f;
+            if (f) op.times = number(v, "-times");
+            v = take(m, "min", &f);
+            if (f) { op.min_len = parse_si_u64(v); if (!op.min_len) bail("bursts -min takes a number of windows > 0"); }
+            v = take(m, "cap", &f);
+            if (f) { op.cap = parse_si_u64(v); if (op.cap > QD_BURSTS_MAX_WORKSPACE / sizeof(qd_burst)) bail("bursts -cap takes at most 33554432 records"); }
+            v = take(m, "print", &f);
+            if (f) op.print_n = parse_si_u64(v);
+            ensure_empty(m);
+            op.prefix = next("'bursts' requires a prefix argument");
         } else if (cmd == "picture") {
             // not in the reference's grammar: the waterfall its conrod front end renders (src/ui/mod.rs:294-412) as a binary PPM.  -width 8,
             // -stride 1 and -stretch 4 are its Params (:72-76) and 2.29 its scale (:353); -scan 0, no marker columns, is not: its default of 1
@@ -1362,6 +1397,82 @@ void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
     }
 }
 
+// The `bursts` sink: a threshold per fftshifted bin (-level X for every bin, or -levels FILE: W raw little-endian f32, one row of what
+// means, quantiles or peaks write; -times K multiplies each by K in one f32 multiply) applied to the windows sparkfft would print (a
+// cascade's complete windows), and the list of the runs of cells at or above it, at least -min windows long, in the order they end:
+// PREFIX.sr{rate}.w{W}.bursts holds the first -cap records raw (qd_burst, 32 bytes each), PREFIX.sr{rate}.w{W}.on.u64 the on cells of
+// every bin.  One header line on stdout, then with -print N the first N records as `first length bin peak_at peak`.  A chain the library
+// fuses lists on the device (qd_plan_bursts on a norms plan); every other chain pulls its windows through the iterator chain into
+// qd_bursts_fold and qd_bursts_finish — the same bytes either way.  A run crosses the seam between two devices' ranges, so -gpus N is refused.
+void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    if (g_gpus > 1) bail("bursts lists one range of windows on one device: a run crosses the seam between two devices' ranges (run it without -gpus)");
+    std::vector<float> thr(W, sink.level);
+    if (!sink.has_level) {
+        FILE *fp = fopen(sink.levels_file.c_str(), "rb");
+        if (!fp) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + sink.levels_file);
+        uint8_t extra;
+        const bool ok = fread(thr.data(), 4, W, fp) == W && fread(&extra, 1, 1, fp) == 0;
+        fclose(fp);
+        if (!ok) bail("bursts -levels takes a file of exactly " + std::to_string(W) + " f32 values (" + std::to_string(W * 4) + " bytes): " + sink.levels_file);
+    }
+    if (sink.has_times)
+        for (float &t : thr) t = t * sink.times;
+    std::vector<qd_burst> list(sink.cap);
+    std::vector<uint64_t> on(W, 0);
+    uint64_t found = 0, windows = 0;
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+        done = norms_fused(*cs, sink, "bursts", [&](qd_plan *plan, ChainSource &in, int, int, uint64_t complete, uint64_t) {
+            windows = complete;
+            int mem = QD_MEM_HOST;
+            const void *src = in.resident(&mem);
+            return qd_plan_bursts(plan, src, mem, 0, in.n_samples, 0, complete, thr.data(), sink.min_len, sink.cap ? list.data() : nullptr, sink.cap, &found,
+                                  on.data(), QD_MEM_HOST, nullptr);
+        });
+    }
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+        uint64_t nwin = spark_windows(s, W, S);
+        std::vector<qd_c32> buf(W);
+        while (nwin) {
+            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+        }
+        windows = nwin;
+        std::vector<uint64_t> state((size_t)QD_BURSTS_WORDS * W + 1);
+        qd_check(qd_bursts_init(state.data(), on.data(), (uint32_t)W), "init");
+        std::vector<float> norms;
+        qd_burst *lp = sink.cap ? list.data() : nullptr;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
+            qd_check(qd_bursts_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, w0, norms.data(), nb, lp, sink.cap, &found, on.data()), "fold");
+        }
+        if (nwin == 0) qd_check(qd_bursts_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, 0, nullptr, 0, lp, sink.cap, &found, on.data()), "fold");
+        qd_check(qd_bursts_finish(state.data(), (uint32_t)W, sink.min_len, lp, sink.cap, &found), "finish");
+    }
+    const uint64_t written = std::min(found, sink.cap);
+    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W);
+    const std::pair<std::string, std::pair<const void *, size_t>> files[] = {{stem + ".bursts", {list.data(), (size_t)written * sizeof(qd_burst)}},
+                                                                             {stem + ".on.u64", {on.data(), on.size() * 8}}};
+    for (const auto &file : files) {
+        int fd = open(file.first.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + file.first);
+        const uint8_t *at = static_cast<const uint8_t *>(file.second.first);
+        for (size_t left = file.second.second; left;) {
+            const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
+            if (w <= 0) { close(fd); bail("write failed"); }
+            at += w; left -= (size_t)w;
+        }
+        close(fd);
+    }
+    printf("bursts width=%zu stride=%llu min=%llu windows=%llu found=%llu written=%llu\n", W, (unsigned long long)S, (unsigned long long)sink.min_len,
+           (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
+    for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i)
+        printf("%llu %llu %u %llu %.9g\n", (unsigned long long)list[i].first, (unsigned long long)list[i].length, list[i].bin, (unsigned long long)list[i].peak_at,
+               (double)list[i].peak);
+}
+
 // The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
 // it out (src/ui/mod.rs:294-412; the colour map is the project's own statement of palette 0.5's HSV -> RGB, include/quadrs_hip.h), written
 // as PREFIX.sr{rate}.w{W}.{pxw}x{pxh}.ppm: binary P6, maxval 255, top row first — the buffer as it lies.  A chain the library fuses paints
@@ -1455,11 +1566,12 @@ void usage() {
             "  spreads [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) [-range MIN:MAX] FILENAME_PREFIX \\\n"
             "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
             "   bands [-width 128] [-stride =width] (-bins LO:HI[,LO:HI...] | -split K) [-pick] FILENAME_PREFIX \\\n"
+            "  bursts [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
             " picture [-width 8] [-stride 1] -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29] [-overwrite no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
-            "\nsparkfft, bucket, marks, levels, peaks, means, powers, spreads, quantiles, bands and picture also take [-window bh|rect] (default rect):\n"
+            "\nsparkfft, bucket, marks, levels, peaks, means, powers, spreads, quantiles, bands, bursts and picture also take [-window bh|rect] (default rect):\n"
             "a Blackman-Harris window on every window's samples in front of the transform\n"
             "\n\nFormat for FREQUENCY, SAMPLE_RATE, and other suffixes: 123, 123k, 123M, 123G\n");
 }
@@ -1517,6 +1629,11 @@ int main(int argc, char **argv) {
                     printf("bands width=%zu stride=%llu k=%zu bins=%s pick=%d\n", op.width, (unsigned long long)op.stride, op.bands.size(), bs.c_str(), op.pick ? 1 : 0);
                     break;
                 }
+                case OP_BURSTS:
+                    if (op.has_level) printf("bursts width=%zu stride=%llu level=%.9g", op.width, (unsigned long long)op.stride, op.level);
+                    else printf("bursts width=%zu stride=%llu levels=%s", op.width, (unsigned long long)op.stride, op.levels_file.c_str());
+                    printf(" times=%.9g min=%llu cap=%llu print=%llu\n", op.times, (unsigned long long)op.min_len, (unsigned long long)op.cap, (unsigned long long)op.print_n);
+                    break;
                 case OP_PICTURE:
                     printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g overwrite=%d\n", op.width, (unsigned long long)op.stride, op.px_w, op.px_h,
                            op.stretch, op.marker, op.scale, op.overwrite ? 1 : 0);
@@ -1593,6 +1710,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("bands requires an input");
                 cs.cascade = !chain_clean;
                 do_bands(*samples, op, &cs);
+                break;
+            case OP_BURSTS:
+                if (!samples) bail("bursts requires an input");
+                cs.cascade = !chain_clean;
+                do_bursts(*samples, op, &cs);
                 break;
             case OP_PICTURE:
                 if (!samples) bail("picture requires an input");

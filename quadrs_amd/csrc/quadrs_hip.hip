@@ -39,6 +39,7 @@
 #include "qd_power.h"
 #include "qd_spread.h"
 #include "qd_bands.h"
+#include "qd_bursts.h"
 #include "qd_paint.h"
 
 using namespace qd;
@@ -4486,6 +4487,185 @@ int qd_plan_picture(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     rc = f.sync(rc);
     if (rc) return rc;
     if (painted) *painted = f.n_windows;
+    return f.short_read();
+}
+
+// ------------------------------------------------------------------ burst list
+
+namespace {
+static_assert(sizeof(Burst) == sizeof(qd_burst) && sizeof(qd_burst) == 32 && kBurstsWords == QD_BURSTS_WORDS && kBurstsMaxWorkspace == QD_BURSTS_MAX_WORKSPACE,
+              "qd_bursts.h and the public header agree on a record");
+
+// the checks the twin and qd_plan_bursts share; words (may be NULL) receives the W threshold words
+int bursts_given(uint32_t W, const float *thresholds, uint64_t min_len, const qd_burst *list, uint64_t cap, const uint64_t *found, uint32_t *words) {
+    if (W == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!thresholds) return fail(QD_ERR_INVALID, "thresholds is NULL");
+    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
+    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: a burst holds at least one window");
+    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    for (uint32_t b = 0; b < W; ++b) {
+        uint32_t w;
+        if (!bursts_threshold(bits_of_f32(thresholds[b]), &w))
+            return fail(QD_ERR_INVALID, "threshold %u is %g: a threshold is +0 ... +inf, or a NaN that masks the bin", b, (double)thresholds[b]);
+        if (words) words[b] = w;
+    }
+    return QD_OK;
+}
+void bursts_emit(const BurstsRun &r, uint64_t end, uint32_t bin, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found) {
+    if (end - r.first < min_len) return;
+    if (*found < cap) {
+        qd_burst &d = list[*found];
+        d.first = r.first; d.length = end - r.first; d.peak_at = r.peak_at; d.bin = bin; d.peak = f32_of_bits(r.peak);
+    }
+    *found += 1;
+}
+}  // namespace
+
+int qd_bursts_init(uint64_t *state, uint64_t *on_counts, uint32_t width) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    for (uint32_t b = 0; b < width; ++b) {
+        state[(size_t)b * kBurstsWords] = kBurstsNone; state[(size_t)b * kBurstsWords + 1] = 0; state[(size_t)b * kBurstsWords + 2] = 0;
+        if (on_counts) on_counts[b] = 0;
+    }
+    state[(size_t)width * kBurstsWords] = 0;
+    return QD_OK;
+}
+
+int qd_bursts_fold(uint64_t *state, uint32_t width, const float *thresholds, uint64_t min_len, uint64_t at, const float *norms, uint64_t n,
+                   qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    std::vector<uint32_t> thr(width);
+    if (const int rc = bursts_given(width, thresholds, min_len, list, cap, found, thr.data())) return rc;
+    uint64_t &next = state[(size_t)width * kBurstsWords];
+    if (at != next) return fail(QD_ERR_INVALID, "the fold starts at window %llu, the state expects %llu", (unsigned long long)at, (unsigned long long)next);
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    for (uint64_t i = 0; i < n; ++i) {
+        const float *row = norms + i * width;
+        const uint64_t w = at + i;
+        for (uint32_t b = 0; b < width; ++b) {
+            uint64_t *s = state + (size_t)b * kBurstsWords;
+            BurstsRun r{s[0], s[1], (uint32_t)s[2]}, e;
+            const uint32_t a = bursts_mag(bits_of_f32(row[b]));
+            const bool on = bursts_on(a, thr[b]);
+            if (bursts_step(r, w, a, on, &e)) bursts_emit(e, w, b, min_len, list, cap, found);
+            if (on && on_counts) on_counts[b] += 1;
+            s[0] = r.first; s[1] = r.peak_at; s[2] = r.peak;
+        }
+    }
+    next = at + n;
+    return QD_OK;
+}
+
+int qd_bursts_finish(uint64_t *state, uint32_t width, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
+    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: a burst holds at least one window");
+    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    const uint64_t next = state[(size_t)width * kBurstsWords];
+    for (uint32_t b = 0; b < width; ++b) {
+        const uint64_t *s = state + (size_t)b * kBurstsWords;
+        if (s[0] != kBurstsNone) bursts_emit(BurstsRun{s[0], s[1], (uint32_t)s[2]}, next, b, min_len, list, cap, found);
+    }
+    return qd_bursts_init(state, nullptr, width);
+}
+
+int qd_plan_bursts(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                   const float *thresholds, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts, int out_mem,
+                   void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_bursts", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    const uint32_t W = p->W;
+    std::vector<uint32_t> thr(W);
+    if (const int rc = bursts_given(W, thresholds, min_len, list, cap, found, thr.data())) return rc;
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan's bursts are not listed in one call: run one range on one device on a plan of its own; joining the lists across a "
+                                   "seam, where a run may cross, is the caller's job")) return rc;
+    if (bursts_seg_max(W) == 0) return fail(QD_ERR_UNSUPPORTED, "windows of %u bins are too wide for the burst walker (at most 131072)", W);
+    if (const int rc = f.admit()) return rc;
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    if (!out_dev && cap > kBurstsMaxWorkspace / sizeof(Burst))
+        return fail(QD_ERR_UNSUPPORTED, "a list of %llu records needs a workspace of %llu bytes, above the %llu allowed: list into device memory, or lower cap",
+                    (unsigned long long)cap, (unsigned long long)cap * 32ull, (unsigned long long)kBurstsMaxWorkspace);
+    if (const int rc = f.open()) return rc;
+    const hipStream_t st = f.st;
+    // slot 1: [state: 3 W][found][on_counts: W][threshold words: W u32], written from one host image
+    const size_t head_words = (size_t)kBurstsWords * W + 1 + W;
+    std::vector<uint64_t> image(head_words + (W + 1) / 2, 0);
+    for (uint32_t b = 0; b < W; ++b) image[b] = kBurstsNone;
+    memcpy(image.data() + head_words, thr.data(), (size_t)W * 4);
+    void *v = nullptr;
+    int rc = f.ws->get(1, image.size() * 8, &v); if (rc) return rc;
+    unsigned long long *head = static_cast<unsigned long long *>(v);
+    HIPCHK(hipMemcpyAsync(head, image.data(), image.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                // the image is this call's array
+    BurstsParams B{};
+    B.state = head; B.found = head + (size_t)kBurstsWords * W; B.thr = reinterpret_cast<const uint32_t *>(head + head_words);
+    unsigned long long *counts_ws = head + (size_t)kBurstsWords * W + 1;
+    B.on_counts = !on_counts ? nullptr : out_dev ? reinterpret_cast<unsigned long long *>(on_counts) : counts_ws;
+    if (on_counts && out_dev) HIPCHK(hipMemsetAsync(on_counts, 0, (size_t)W * 8, st));
+    B.min_len = min_len; B.cap = cap;
+    if (cap && !out_dev) { rc = f.ws->get(5, (size_t)(cap * sizeof(Burst)), &v); if (rc) return rc; B.list = static_cast<Burst *>(v); }
+    else B.list = reinterpret_cast<Burst *>(list);
+    B.vec_store = ((uintptr_t)B.list & 15) == 0;
+    if (f.n_windows) {
+        // the per-piece words: sized by the longest batch either walk cuts
+        const uint64_t nw_max = std::max(chunk_windows(p, first_window, f.n_windows, (uint64_t)W * 4),
+                                         chunk_windows(p, first_window, f.n_windows, std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), (uint64_t)W * 4)));
+        const uint64_t bound = bursts_pieces_bound(nw_max, W, p->n_cu);
+        const size_t piece_bytes = (size_t)(bound * kBurstsWords * W * 8);
+        rc = f.ws->get(2, piece_bytes, &v); if (rc) return rc; B.edge = static_cast<unsigned long long *>(v);
+        rc = f.ws->get(3, piece_bytes, &v); if (rc) return rc; B.inc = static_cast<unsigned long long *>(v);
+        rc = f.ws->get(4, (size_t)(bound * 16), &v); if (rc) return rc;
+        B.totals = static_cast<unsigned long long *>(v); B.bases = B.totals + bound;
+        // a run crosses batches, so a batch's walk starts behind the previous batch's: the host ring's two streams meet through an event
+        struct Seam {                                                // destroyed on every way out of the call
+            hipEvent_t e[2] = {nullptr, nullptr};
+            ~Seam() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+        } seam;
+        const bool ring = src_mem != QD_MEM_DEVICE;
+        if (ring) for (hipEvent_t &e : seam.e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        uint64_t k = 0;
+        rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+            if (nw == 0) return (int)QD_OK;
+            BurstsParams Q = B;
+            uint64_t grid = 0;
+            bursts_split(g0, nw, W, p->n_cu, &Q.G, &grid);
+            if (Q.G.n_pieces > bound) return fail(QD_ERR_INVALID, "a batch of %llu windows is cut into more pieces than the workspace holds", (unsigned long long)nw);
+            if (const int c = launch_grid(grid, nw)) return c;
+            Q.norms = norms_d;
+            if (ring && k) HIPCHK(hipStreamWaitEvent(s, seam.e[(k - 1) & 1], 0));
+            hipLaunchKernelGGL(k_bursts_edge, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
+            hipLaunchKernelGGL(k_bursts_stitch, dim3((W + kBurstsStitchBins - 1) / kBurstsStitchBins), dim3(kBurstsThreads), 0, s, Q);
+            hipLaunchKernelGGL(k_bursts_emit<kBurstsCount>, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
+            hipLaunchKernelGGL(k_bursts_scan, dim3(1), dim3(kBurstsThreads), 0, s, Q);
+            if (cap) hipLaunchKernelGGL(k_bursts_emit<kBurstsEmit>, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
+            HIPCHK(hipGetLastError());
+            if (ring) HIPCHK(hipEventRecord(seam.e[k & 1], s));
+            ++k;
+            return (int)QD_OK;
+        });
+        if (rc == QD_OK) {
+            BurstsParams Q = B;
+            Q.G.W = W;
+            hipLaunchKernelGGL(k_bursts_close, dim3(1), dim3(kBurstsThreads), 0, st, Q, f.n_windows);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    uint64_t total = 0;
+    if (rc == QD_OK) {
+        HIPCHK(hipMemcpyAsync(&total, B.found, 8, hipMemcpyDeviceToHost, st));
+        if (on_counts && !out_dev) HIPCHK(hipMemcpyAsync(on_counts, counts_ws, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    }
+    rc = f.sync(rc);
+    if (rc) return rc;
+    const uint64_t written = std::min(total, cap);
+    if (written && !out_dev) HIPCHK(hipMemcpy(list, B.list, (size_t)(written * sizeof(Burst)), hipMemcpyDeviceToHost));
+    *found = total;
     return f.short_read();
 }
 

@@ -506,6 +506,72 @@ def bands_fold(norms, bands, outputs=None):
     return tuple(out.get(o) for o in BAND_OUTPUTS)
 
 
+BURST_DTYPE = np.dtype([("first", "<u8"), ("length", "<u8"), ("peak_at", "<u8"), ("bin", "<u4"), ("peak", "<f4")])      # qd_burst, 32 bytes
+BURSTS_DEFAULT_CAP = 1 << 20
+
+
+def _burst_thresholds(thresholds, width):
+    """float32[width] of a scalar (one level for every bin) or of `width` values"""
+    t = np.asarray(thresholds, dtype=np.float32)
+    if t.ndim == 0:
+        t = np.full(width, t, dtype=np.float32)
+    t = np.ascontiguousarray(t.reshape(-1))
+    if t.size != width:
+        raise ValueError("thresholds holds %d values for %d bins" % (t.size, width))
+    return t
+
+
+def _burst_cap(cap, n, width):
+    """cap as given, else what cannot overflow (a bin holds at most ceil(n / 2) bursts), at most BURSTS_DEFAULT_CAP"""
+    return min(-(-int(n) // 2) * int(width), BURSTS_DEFAULT_CAP) if cap is None else int(cap)
+
+
+def _burst_list(into):
+    """(list pointer or None, cap) of a BURST_DTYPE array or None"""
+    return (None, 0) if into is None or into.size == 0 else (_np_ptr(into), into.size)
+
+
+def bursts_init(width):
+    """qd_bursts_init: (state uint64[3 width + 1], on_counts uint64[width]) with no run open."""
+    state = np.empty(_ffi.BURSTS_WORDS * int(width) + 1, dtype=np.uint64)
+    on_counts = np.empty(int(width), dtype=np.uint64)
+    check(lib().qd_bursts_init(_np_ptr(state), _np_ptr(on_counts), int(width)))
+    return state, on_counts
+
+
+def bursts_fold(state, norms, thresholds, min_len=1, at=0, into=None, found=0, on_counts=None):
+    """qd_bursts_fold: norms rows (n, width) are windows at, at+1, ... of a range.  The bursts that end in them go to the BURST_DTYPE array
+    `into` (its length is cap; None: count only) from record `found` on.  Returns the new found."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    t = _burst_thresholds(thresholds, width)
+    f = C.c_uint64(int(found))
+    check(lib().qd_bursts_fold(_np_ptr(state), width, _np_ptr(t), int(min_len), int(at), _np_ptr(a) if n else None, n,
+                               *_burst_list(into), C.byref(f),
+                               None if on_counts is None else _np_ptr(on_counts)))
+    return f.value
+
+
+def bursts_finish(state, min_len=1, into=None, found=0):
+    """qd_bursts_finish: closes the open runs at the last window folded; the state is left as bursts_init leaves it.  Returns found."""
+    f = C.c_uint64(int(found))
+    width = (state.size - 1) // _ffi.BURSTS_WORDS
+    check(lib().qd_bursts_finish(_np_ptr(state), width, int(min_len), *_burst_list(into),
+                                 C.byref(f)))
+    return f.value
+
+
+def bursts_of(norms, thresholds, min_len=1, cap=None):
+    """The CPU twin of Plan.bursts on norms rows (n, width): (list BURST_DTYPE[min(found, cap)], found, on_counts uint64[width])."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    state, on_counts = bursts_init(width)
+    into = np.zeros(_burst_cap(cap, n, width), dtype=BURST_DTYPE)
+    found = bursts_fold(state, a, thresholds, min_len, 0, into, 0, on_counts)
+    found = bursts_finish(state, min_len, into, found)
+    return into[:min(found, into.size)], found, on_counts
+
+
 def picture_desc(px_width, px_height, stretch=4, scan=0, scale=2.29):
     """a qd_picture_desc: the page of a waterfall picture.  stretch 4 and scale 2.29 are the reference's; scan 0 (no marker columns) is
     not: its default of 1 blackens every column."""
@@ -855,6 +921,51 @@ class Plan:
         out = dict(zip(names, self._fold_rows(call, tuple(_BAND_DTYPES[o] for o in names), src, 1, first_window, n_windows, src_first, pinned,
                                               device_out, shapes)))
         return tuple(out.get(o) for o in BAND_OUTPUTS)
+
+    def bursts(self, src, thresholds, min_len=1, cap=None, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None,
+               out=None, counts_out=None):
+        """qd_plan_bursts of an EPI_NORMS_F32 plan: (list, found, on_counts) — the runs of cells at or above the bin's threshold
+        (a scalar, or `width` float32 in fftshifted order; NaN masks a bin) in windows [first_window, +n_windows), at least min_len long,
+        in the order they end; found counts all of them, the list holds the first min(found, cap) (cap None: what cannot overflow, at
+        most BURSTS_DEFAULT_CAP).  src and device_out as for bands: the list is a BURST_DTYPE numpy array, or a torch uint8 CUDA tensor
+        [records, 32] with on_counts int64 (the same bits).  out / counts_out: a BURST_DTYPE array or uint8 tensor, and width uint64 words,
+        to write into instead; cap then defaults to the records `out` holds and may not exceed them.  A failing call's error carries
+        (list, found, on_counts) as e.partial."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        W = self.width
+        t = _burst_thresholds(thresholds, W)
+        dev = (_is_torch(src) if device_out is None else device_out) if out is None else _is_torch(out)
+        if out is None:
+            cap = _burst_cap(cap, n_windows, W)
+        else:                                    # the list given holds what it holds: cap defaults to it and may not exceed it
+            room = (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) // BURST_DTYPE.itemsize
+            cap = room if cap is None else int(cap)
+            if cap > room:
+                raise ValueError("cap %d above the %d records that out holds" % (cap, room))
+        if counts_out is not None and (counts_out.numel() * counts_out.element_size() if _is_torch(counts_out) else counts_out.nbytes) < 8 * W:
+            raise ValueError("counts_out holds fewer than %d uint64 words" % W)
+        if dev:
+            import torch
+            lst = torch.empty((cap, 32), dtype=torch.uint8, device="cuda") if out is None else out
+            cnt = torch.empty(W, dtype=torch.int64, device="cuda") if counts_out is None else counts_out
+            lptr, cptr, out_mem = C.c_void_p(lst.data_ptr()) if cap else None, C.c_void_p(cnt.data_ptr()), MEM_DEVICE
+        else:
+            lst = np.zeros(cap, dtype=BURST_DTYPE) if out is None else out
+            cnt = np.empty(W, dtype=np.uint64) if counts_out is None else counts_out
+            lptr, cptr, out_mem = _np_ptr(lst) if cap else None, _np_ptr(cnt), (_ffi.MEM_HOST_PINNED if pinned and out is not None else MEM_HOST)
+        found = C.c_uint64(0)
+
+        def result():
+            k = min(found.value, cap)
+            return (lst.reshape(-1, 32)[:k] if dev else lst[:k]), found.value, cnt
+        try:
+            check(lib().qd_plan_bursts(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), int(min_len), lptr, cap,
+                                       C.byref(found), cptr, out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = result()
+            raise
+        return result()
 
     def picture(self, src, desc, first_window=0, n_windows=None, src_first=0, pinned=False, out=None, device_out=None):
         """qd_plan_picture of an EPI_NORMS_F32 plan: (pixels uint8[px_height, px_width, 3], painted) — the waterfall picture of windows
