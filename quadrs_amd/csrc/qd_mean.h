@@ -136,112 +136,36 @@ QD_MEAN_HD inline void mean_finish_cell(const uint64_t *acc, uint32_t *mean_bits
     }
 }
 
+// the mean's cell for the limb fold (qd_limbs.h)
+struct MeanCell {
+    static constexpr int kWords = kMeanWords;
+    struct Out { float *mean; double *sum; uint32_t *count; };                          // R x W each; any may be nullptr
+    QD_MEAN_HD static void add(uint64_t *acc, uint32_t bits) { mean_add(acc, bits); }
+#if defined(__HIPCC__)
+    __device__ static void round_to(const uint64_t *acc, const Out &out, uint64_t at) {
+        uint32_t mb, cnt; double s;
+        mean_finish_cell(acc, &mb, &s, &cnt);
+        if (out.mean) out.mean[at] = __uint_as_float(mb);
+        if (out.sum) out.sum[at] = s;
+        if (out.count) out.count[at] = cnt;
+    }
+#endif
+};
+
 }  // namespace qd
 
 #if defined(__HIPCC__)
-#include "qd_pool.h"
+#include "qd_limbs.h"
 
 namespace qd {
 
-// k_mean runs on k_pool's geometry (pool_geometry, qd_pool.h; the rule is qd_pieces.h) with k_pool's window walker (walk_piece) and reads
-// the carrier once.  A lane owns V bins down a piece and adds each value into its own nine limbs and count word, in registers.  Pieces of a workgroup that share a row meet in LDS, word by word (one u64 per bin: 8 KiB),
-// with u64 LDS adds into the slot of the first of them.  A row then ends in one of two ways:
-//   whole   all of the row's windows lie in this batch and all of its pieces in this workgroup (PieceLane::whole): the leader rounds
-//           the cells and stores mean / sum / count; no global accumulator is touched.
-//   cut     every other row (cut by a batch seam, or split over workgroups because the rows are few): the leader adds its non-zero
-//           words with 64-bit global atomicAdd — one per word per workgroup — into the limb accumulator and raises the row's flag;
-//           k_mean_finish, one lane per cell, rounds the flagged rows once all of their batches are through.
-// The limb accumulator is planar (word k of cell c at k cells + c, cells = acc_rows W, so the lanes of a wave touch consecutive words)
-// and holds rows [r_base, r_base + acc_rows) of the range.
-// Workspace rule (qd_plan_mean): the accumulator is at most max(2 chunk_bytes, 80 W bytes), whatever R is.  Batches end on multiples of
-// pool whenever pool <= chunk windows, so rows of small pools are whole and need no accumulator; a batch that can cut rows is clipped to
-// the rows the accumulator holds, and when its rows pass the accumulator's end the span is finished, the accumulator zeroed and moved.
-struct MeanParams {
-    const float *norms;                          // the batch's windows, nw x W
-    PieceGeometry G;
-    float *mean; double *sum; uint32_t *count;   // R x W each; any may be nullptr
-    unsigned long long *acc;                     // planar limbs, kMeanWords x cells
-    uint32_t *flags;                             // acc_rows: the row went through the accumulator
-    uint64_t r_base, acc_rows, cells;           // acc_rows 0: the host found that this launch cuts no row
-};
-
+// k_mean is the limb fold (qd_limbs.h) with ten words a cell on pool_geometry: V = 4 bins a lane (one 16-byte load a window), V = 1 below W = 4.
 template <int V>
-__global__ __launch_bounds__(kPoolThreads) void k_mean(const MeanParams M) {
-    __shared__ unsigned long long s_meet[kPoolSlabCols];
-    const PieceGeometry &P = M.G;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t grp = tid / P.lanes_per_win;
-    const uint32_t lcol = (tid % P.lanes_per_win) * V;                                 // the lane's first bin inside the slab
-    const PieceLane l = piece_lane(P, blockIdx.x, grp);
+__global__ __launch_bounds__(kPoolThreads) void k_mean(const LimbParams<MeanCell> M) { limb_fold<MeanCell, V, kPoolThreads * V>(M); }
 
-    uint64_t acc[V][kMeanWords];
-#pragma unroll
-    for (int i = 0; i < V; ++i)
-#pragma unroll
-        for (int j = 0; j < kMeanWords; ++j) acc[i][j] = 0;
-
-    walk_piece<V>(M.norms + (l.wa - P.g0) * P.W + (uint64_t)l.slab * P.cols + lcol, l.wa, l.wb, P.W, [&](int i, uint32_t bits) { mean_add(acc[i], bits); });
-
-    // the pieces of this workgroup that share the row r meet in the LDS slot of the first of them, one word at a time; with one piece
-    // a row (spr == 1) or one piece a workgroup every lane group leads its own row and nothing meets
-    if (P.spr > 1 && P.pieces_per_group > 1) {
-        const uint32_t slot = l.lead * P.lanes_per_win * V + lcol;
-#pragma unroll
-        for (int i = 0; i < V; ++i) s_meet[tid * V + i] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < kMeanWords; ++j) {
-            if (l.active) {
-#pragma unroll
-                for (int i = 0; i < V; ++i)
-                    if (acc[i][j]) atomicAdd(&s_meet[slot + i], (unsigned long long)acc[i][j]);
-            }
-            __syncthreads();
-            // slot tid V + i is read and cleared by lane tid alone
-#pragma unroll
-            for (int i = 0; i < V; ++i) { acc[i][j] = s_meet[tid * V + i]; s_meet[tid * V + i] = 0; }
-            __syncthreads();
-        }
-    }
-    if (!l.active || l.lead != grp) return;
-    const uint64_t col = (uint64_t)l.slab * P.cols + lcol;
-    if (l.whole(P)) {
-        const uint64_t o = l.r * P.W + col;
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            uint32_t mb, cnt; double s;
-            mean_finish_cell(acc[i], &mb, &s, &cnt);
-            if (M.mean) M.mean[o + i] = __uint_as_float(mb);
-            if (M.sum) M.sum[o + i] = s;
-            if (M.count) M.count[o + i] = cnt;
-        }
-    } else {
-        const uint64_t ra = l.r - M.r_base, cell = ra * P.W + col;
-        if (ra >= M.acc_rows) return;                                    // never past the accumulator
-        if (lcol == 0) M.flags[ra] = 1u;
-#pragma unroll
-        for (int i = 0; i < V; ++i)
-#pragma unroll
-            for (int j = 0; j < kMeanWords; ++j)
-                if (acc[i][j]) atomicAdd(&M.acc[(uint64_t)j * M.cells + cell + i], (unsigned long long)acc[i][j]);
-    }
-}
-
-// the flagged rows of the accumulator, rows [r_base, r_base + n_rows) of the range, into the outputs: one lane per cell
 __global__ __launch_bounds__(kPoolThreads) void k_mean_finish(const unsigned long long *accg, const uint32_t *flags, uint64_t cells, uint64_t r_base,
-                                                              uint64_t n_rows, uint32_t W, float *mean, double *sum, uint32_t *count) {
-    const uint64_t c = (uint64_t)blockIdx.x * kPoolThreads + threadIdx.x;
-    if (c >= n_rows * W) return;
-    if (!flags[c / W]) return;
-    uint64_t acc[kMeanWords];
-#pragma unroll
-    for (int j = 0; j < kMeanWords; ++j) acc[j] = accg[(uint64_t)j * cells + c];
-    uint32_t mb, cnt; double s;
-    mean_finish_cell(acc, &mb, &s, &cnt);
-    const uint64_t o = r_base * W + c;
-    if (mean) mean[o] = __uint_as_float(mb);
-    if (sum) sum[o] = s;
-    if (count) count[o] = cnt;
+                                                              uint64_t n_rows, uint32_t W, const MeanCell::Out out) {
+    limb_finish<MeanCell>(accg, flags, cells, r_base, n_rows, W, out);
 }
 
 }  // namespace qd

@@ -154,101 +154,36 @@ QD_MEAN_HD inline void power_finish_cell(const uint64_t *acc, uint32_t *rms_bits
     *rms_bits = p + ((half > 0 || (half == 0 && (p & 1))) ? 1u : 0u);
 }
 
+// the power's cell for the limb fold (qd_limbs.h)
+struct PowerCell {
+    static constexpr int kWords = kPowerWords;
+    struct Out { float *rms; double *sumsq; uint32_t *count; };                         // R x W each; any may be nullptr
+    QD_MEAN_HD static void add(uint64_t *acc, uint32_t bits) { power_add(acc, bits); }
+#if defined(__HIPCC__)
+    __device__ static void round_to(const uint64_t *acc, const Out &out, uint64_t at) {
+        uint32_t rb, cnt; double s;
+        power_finish_cell(acc, &rb, &s, &cnt);
+        if (out.rms) out.rms[at] = __uint_as_float(rb);
+        if (out.sumsq) out.sumsq[at] = s;
+        if (out.count) out.count[at] = cnt;
+    }
+#endif
+};
+
 }  // namespace qd
 
 #if defined(__HIPCC__)
 namespace qd {
 
-// k_power is k_mean (qd_mean.h) with nineteen words a cell: pool_geometry's pieces, walk_piece reading the carrier once, the LDS meeting
-// of pieces that share a row word by word, and the same two row endings — a whole row is rounded here and touches no global accumulator,
-// a cut row adds its non-zero words with 64-bit global atomicAdd into the planar limb accumulator (word k of cell c at k cells + c) and
-// raises its flag for k_power_finish.  Nineteen u64 a bin are 38 VGPRs a bin, so two forms are built: V = 4 bins a lane (one 16-byte
-// load a window, pool_geometry as it stands) and V = 1 (4-byte loads, 256 bins a workgroup); power_geometry lays out either.
-struct PowerParams {
-    const float *norms;                          // the batch's windows, nw x W
-    PieceGeometry G;
-    float *rms; double *sumsq; uint32_t *count;  // R x W each; any may be nullptr
-    unsigned long long *acc;                     // planar limbs, kPowerWords x cells
-    uint32_t *flags;                             // acc_rows: the row went through the accumulator
-    uint64_t r_base, acc_rows, cells;            // acc_rows 0: the host found that this launch cuts no row
-};
-
+// k_power is the limb fold (qd_limbs.h) with nineteen words a cell.  Nineteen u64 a bin are 38 VGPRs a bin, so two forms are built:
+// V = 4 bins a lane (one 16-byte load a window, pool_geometry as it stands) and V = 1 (4-byte loads, 256 bins a workgroup);
+// power_geometry lays out either.
 template <int V>
-__global__ __launch_bounds__(kPoolThreads) void k_power(const PowerParams M) {
-    __shared__ unsigned long long s_meet[kPoolThreads * V];
-    const PieceGeometry &P = M.G;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t grp = tid / P.lanes_per_win;
-    const uint32_t lcol = (tid % P.lanes_per_win) * V;                                 // the lane's first bin inside the slab
-    const PieceLane l = piece_lane(P, blockIdx.x, grp);
+__global__ __launch_bounds__(kPoolThreads) void k_power(const LimbParams<PowerCell> M) { limb_fold<PowerCell, V, kPoolThreads * V>(M); }
 
-    uint64_t acc[V][kPowerWords];
-#pragma unroll
-    for (int i = 0; i < V; ++i)
-#pragma unroll
-        for (int j = 0; j < kPowerWords; ++j) acc[i][j] = 0;
-
-    walk_piece<V>(M.norms + (l.wa - P.g0) * P.W + (uint64_t)l.slab * P.cols + lcol, l.wa, l.wb, P.W, [&](int i, uint32_t bits) { power_add(acc[i], bits); });
-
-    // the pieces of this workgroup that share the row r meet in the LDS slot of the first of them, one word at a time
-    if (P.spr > 1 && P.pieces_per_group > 1) {
-        const uint32_t slot = l.lead * P.lanes_per_win * V + lcol;
-#pragma unroll
-        for (int i = 0; i < V; ++i) s_meet[tid * V + i] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < kPowerWords; ++j) {
-            if (l.active) {
-#pragma unroll
-                for (int i = 0; i < V; ++i)
-                    if (acc[i][j]) atomicAdd(&s_meet[slot + i], (unsigned long long)acc[i][j]);
-            }
-            __syncthreads();
-            // slot tid V + i is read and cleared by lane tid alone
-#pragma unroll
-            for (int i = 0; i < V; ++i) { acc[i][j] = s_meet[tid * V + i]; s_meet[tid * V + i] = 0; }
-            __syncthreads();
-        }
-    }
-    if (!l.active || l.lead != grp) return;
-    const uint64_t col = (uint64_t)l.slab * P.cols + lcol;
-    if (l.whole(P)) {
-        const uint64_t o = l.r * P.W + col;
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            uint32_t rb, cnt; double s;
-            power_finish_cell(acc[i], &rb, &s, &cnt);
-            if (M.rms) M.rms[o + i] = __uint_as_float(rb);
-            if (M.sumsq) M.sumsq[o + i] = s;
-            if (M.count) M.count[o + i] = cnt;
-        }
-    } else {
-        const uint64_t ra = l.r - M.r_base, cell = ra * P.W + col;
-        if (ra >= M.acc_rows) return;                                    // never past the accumulator
-        if (lcol == 0) M.flags[ra] = 1u;
-#pragma unroll
-        for (int i = 0; i < V; ++i)
-#pragma unroll
-            for (int j = 0; j < kPowerWords; ++j)
-                if (acc[i][j]) atomicAdd(&M.acc[(uint64_t)j * M.cells + cell + i], (unsigned long long)acc[i][j]);
-    }
-}
-
-// the flagged rows of the accumulator, rows [r_base, r_base + n_rows) of the range, into the outputs: one lane per cell
 __global__ __launch_bounds__(kPoolThreads) void k_power_finish(const unsigned long long *accg, const uint32_t *flags, uint64_t cells, uint64_t r_base,
-                                                               uint64_t n_rows, uint32_t W, float *rms, double *sumsq, uint32_t *count) {
-    const uint64_t c = (uint64_t)blockIdx.x * kPoolThreads + threadIdx.x;
-    if (c >= n_rows * W) return;
-    if (!flags[c / W]) return;
-    uint64_t acc[kPowerWords];
-#pragma unroll
-    for (int j = 0; j < kPowerWords; ++j) acc[j] = accg[(uint64_t)j * cells + c];
-    uint32_t rb, cnt; double s;
-    power_finish_cell(acc, &rb, &s, &cnt);
-    const uint64_t o = r_base * W + c;
-    if (rms) rms[o] = __uint_as_float(rb);
-    if (sumsq) sumsq[o] = s;
-    if (count) count[o] = cnt;
+                                                               uint64_t n_rows, uint32_t W, const PowerCell::Out out) {
+    limb_finish<PowerCell>(accg, flags, cells, r_base, n_rows, W, out);
 }
 
 // The launch geometry for the batch [g0, g0 + nw) in the form `form`: pool_geometry for V = 4 (W < 4 is always V = 1); V = 1 has its own

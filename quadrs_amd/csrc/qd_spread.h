@@ -21,7 +21,7 @@ constexpr uint64_t kSpreadNanBits64 = 0x7ff8000000000000ull;
 
 // which results spread_finish_cell works out (count always)
 enum : uint32_t { kSpreadStd = 1u, kSpreadSsd = 2u, kSpreadMean = 4u, kSpreadRms = 8u, kSpreadAll = 15u };
-struct SpreadCell { uint32_t std_bits, mean_bits, rms_bits, count; double ssd; };
+struct SpreadRounded { uint32_t std_bits, mean_bits, rms_bits, count; double ssd; };
 
 // acc[0..27] += one value: mean_term's two addends and power_term's three.  The limb indices are data dependent: unrolled selects over
 // the nine and the eighteen limbs keep the cell in registers.
@@ -209,7 +209,7 @@ QD_MEAN_HD inline void spread_deviation(const uint64_t *acc, uint32_t n, uint32_
 //   mean   mean_finish_cell on words 0-8 and the count word;  rms  power_finish_cell on words 9-26 and the count word
 //   std, ssd   none: std the quiet NaN 0x7fc00000, ssd 0.0;  any +inf: both the quiet NaN (the deviation of a set that holds an infinity
 //          is undefined);  one value: +0 and 0.0;  else spread_deviation
-QD_MEAN_HD inline void spread_finish_cell(const uint64_t *acc, uint32_t want, SpreadCell *out) {
+QD_MEAN_HD inline void spread_finish_cell(const uint64_t *acc, uint32_t want, SpreadRounded *out) {
     const uint64_t n_inf = acc[27] >> 32, c64 = (acc[27] & 0xffffffffull) + n_inf;
     const uint32_t c = (uint32_t)c64;
     out->count = c;
@@ -242,16 +242,26 @@ QD_MEAN_HD inline void spread_finish_cell(const uint64_t *acc, uint32_t want, Sp
     spread_deviation(acc, c, want, &out->std_bits, &out->ssd);
 }
 
+// the spread's cell for the host path the three sinks share (quadrs_hip.hip); k_spread has its own parameters below
+struct SpreadCell {
+    static constexpr int kWords = kSpreadWords;
+    struct Out {
+        float *std; double *ssd; uint32_t *count; float *mean; float *rms;              // R x W each; any may be nullptr
+        uint32_t want;                                                                  // kSpread* of the outputs that are not nullptr
+    };
+    QD_MEAN_HD static void add(uint64_t *acc, uint32_t bits) { spread_add(acc, bits); }
+};
+
 }  // namespace qd
 
 #if defined(__HIPCC__)
 namespace qd {
 
-// k_spread is k_power<1> (qd_power.h) with twenty-eight words a cell: power_geometry's V = 1 column layout, walk_piece reading the carrier
-// once, the LDS meeting of pieces that share a row word by word, and the same two row endings — a whole row is rounded here and touches
-// no global accumulator, a cut row adds its non-zero words with 64-bit global atomicAdd into the planar limb accumulator (word k of
-// cell c at k cells + c) and raises its flag for k_spread_finish.  Twenty-eight u64 a bin are 56 VGPRs a bin: one bin a lane is the only
-// form (four would be 224 VGPRs of accumulator alone).
+// k_spread folds as limb_fold (qd_limbs.h) does, with twenty-eight words a cell on power_geometry's V = 1 column layout, and keeps its
+// own text: entered through the shared body its legs at one row of everything measured 0.4-0.8 % above this text's (one MI355X,
+// ROCm 7.2, October 2026) and the cause was not found.  A change to limb_fold's meeting or row endings has to
+// be made here too.
+// Twenty-eight u64 a bin are 56 VGPRs a bin: one bin a lane is the only form (four would be 224 VGPRs of accumulator alone).
 struct SpreadParams {
     const float *norms;                          // the batch's windows, nw x W
     PieceGeometry G;
@@ -262,7 +272,7 @@ struct SpreadParams {
     uint32_t want;                               // kSpread* of the outputs that are not nullptr
 };
 
-__device__ inline void spread_store(const SpreadCell &c, uint64_t o, float *std, double *ssd, uint32_t *count, float *mean, float *rms) {
+__device__ inline void spread_store(const SpreadRounded &c, uint64_t o, float *std, double *ssd, uint32_t *count, float *mean, float *rms) {
     if (std) std[o] = __uint_as_float(c.std_bits);
     if (ssd) ssd[o] = c.ssd;
     if (count) count[o] = c.count;
@@ -301,7 +311,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_spread(const SpreadParams M) {
     if (!l.active || l.lead != grp) return;
     const uint64_t col = (uint64_t)l.slab * P.cols + lcol;
     if (l.whole(P)) {
-        SpreadCell c;
+        SpreadRounded c;
         spread_finish_cell(acc, M.want, &c);
         spread_store(c, l.r * P.W + col, M.std, M.ssd, M.count, M.mean, M.rms);
     } else {
@@ -324,7 +334,7 @@ __global__ __launch_bounds__(kPoolThreads) void k_spread_finish(const unsigned l
     uint64_t acc[kSpreadWords];
 #pragma unroll
     for (int j = 0; j < kSpreadWords; ++j) acc[j] = accg[(uint64_t)j * cells + c];
-    SpreadCell r;
+    SpreadRounded r;
     spread_finish_cell(acc, want, &r);
     spread_store(r, r_base * W + c, std, ssd, count, mean, rms);
 }

@@ -3622,63 +3622,88 @@ int qd_plan_pool(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
     return f.close(rc);
 }
 
-// ------------------------------------------------------------------ average-trace rows
+// ------------------------------------------------------------------ exact-sum rows: average, RMS and deviation traces (DESIGN.md sections 3.13, 3.17, 3.18; the one path is 3.24)
 
+extern "C++" {                                                       // templates
 namespace {
-struct MeanOut { float *mean; double *sum; uint32_t *count; };
 struct LimbAcc { unsigned long long *limbs; uint32_t *flags; uint64_t rows; };      // device: words x rows x W limbs (planar), rows flags
-using MeanAcc = LimbAcc;                                                            // words = kMeanWords
 
-// one batch of norms rows (device memory, 16-byte aligned) — windows [g0, g0 + nw) of a range of n_total — into the outputs (whole rows)
-// and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows) of the range, on `st`
-int launch_mean(const qd_plan *p, const MeanParams &geo, uint64_t grid, int V, const float *norms_d, const MeanOut &out, const MeanAcc &acc,
-                bool cuts, uint64_t r_base, hipStream_t st) {
-    if (const int rc = launch_grid(grid, geo.G.nw)) return rc;
-    const uint64_t ra = geo.G.g0 / geo.G.pool, rb = (geo.G.g0 + geo.G.nw - 1) / geo.G.pool;
+// k_power's form (qd_power.h): one bin a lane; a development build also holds four bins a lane, for measuring them side by side
+#ifdef QD_DEVELOP
+int power_form() { const char *e = dev_env("QD_POWER_V"); return e && atoi(e) == 4 ? 4 : 1; }
+#else
+int power_form() { return 1; }
+#endif
+
+// a cell's kernels on `grid` workgroups of `st` (qd_mean.h, qd_power.h; k_spread takes the same parameters in its own struct, qd_spread.h)
+void enqueue_fold(const LimbParams<MeanCell> &M, int V, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(V == 4 ? k_mean<4> : k_mean<1>, dim3(grid), dim3(kPoolThreads), 0, st, M);
+}
+void enqueue_fold(const LimbParams<PowerCell> &M, int V, uint32_t grid, hipStream_t st) {
+    void (*fn)(LimbParams<PowerCell>) = k_power<1>;
+#ifdef QD_DEVELOP
+    if (V == 4) fn = k_power<4>;
+#endif
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kPoolThreads), 0, st, M);
+}
+void enqueue_fold(const LimbParams<SpreadCell> &M, int, uint32_t grid, hipStream_t st) {
+    const SpreadCell::Out &o = M.out;
+    const SpreadParams S{M.norms, M.G, o.std, o.ssd, o.count, o.mean, o.rms, M.acc, M.flags, M.r_base, M.acc_rows, M.cells, o.want};
+    hipLaunchKernelGGL(k_spread, dim3(grid), dim3(kPoolThreads), 0, st, S);
+}
+// the finish kernel over the accumulator's flagged rows [r_base, r_base + n_rows)
+void enqueue_finish(const MeanCell::Out &o, const LimbAcc &acc, uint64_t cells, uint64_t r_base, uint64_t n_rows, uint32_t W, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_mean_finish, dim3(grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, cells, r_base, n_rows, W, o);
+}
+void enqueue_finish(const PowerCell::Out &o, const LimbAcc &acc, uint64_t cells, uint64_t r_base, uint64_t n_rows, uint32_t W, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_power_finish, dim3(grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, cells, r_base, n_rows, W, o);
+}
+void enqueue_finish(const SpreadCell::Out &o, const LimbAcc &acc, uint64_t cells, uint64_t r_base, uint64_t n_rows, uint32_t W, uint32_t grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_spread_finish, dim3(grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, cells, r_base, n_rows, W, o.want, o.std, o.ssd, o.count, o.mean, o.rms);
+}
+
+// one batch of norms rows (device memory, 16-byte aligned) — the windows of G — into the outputs (whole rows) and the accumulator (cut
+// rows), which holds rows [r_base, r_base + acc.rows) of the range, on `st`
+template <class Cell>
+int launch_limbs(const qd_plan *p, const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const typename Cell::Out &out, const LimbAcc &acc,
+                 bool cuts, uint64_t r_base, hipStream_t st) {
+    if (const int rc = launch_grid(grid, G.nw)) return rc;
+    const uint64_t ra = G.g0 / G.pool, rb = (G.g0 + G.nw - 1) / G.pool;
     if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
-    MeanParams M = geo;
-    M.norms = norms_d;
-    M.mean = out.mean; M.sum = out.sum; M.count = out.count;
-    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
-    hipLaunchKernelGGL(V == 4 ? k_mean<4> : k_mean<1>, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
+    enqueue_fold(LimbParams<Cell>{norms_d, G, out, acc.limbs, acc.flags, r_base, cuts ? acc.rows : 0, acc.rows * p->W}, V, (uint32_t)grid, st);
     HIPCHK(hipGetLastError());
     return QD_OK;
 }
-int launch_mean_finish(const qd_plan *p, const MeanAcc &acc, uint64_t r_base, uint64_t n_rows, const MeanOut &out, hipStream_t st) {
+// the flagged rows [r_base, r_base + n_rows) of the accumulator into the outputs
+template <class Cell>
+int launch_limbs_finish(const qd_plan *p, const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, const typename Cell::Out &out, hipStream_t st) {
     const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
     if (!cells) return QD_OK;
-    hipLaunchKernelGGL(k_mean_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
-                       out.mean, out.sum, out.count);
+    enqueue_finish(out, acc, acc.rows * p->W, r_base, n_rows, p->W, (uint32_t)grid, st);
     HIPCHK(hipGetLastError());
     return QD_OK;
 }
-uint64_t mean_cell_count(const uint64_t *cell) { return (cell[9] & 0xffffffffull) + (cell[9] >> 32); }
 
-// The walk of the sinks that fold through a limb accumulator (qd_plan_mean, qd_plan_power, qd_plan_spread): a fold kernel that rounds whole rows itself
-// and adds cut rows into `words` planar u64 a cell, and a finish kernel that rounds the flagged rows.  The sink gives its cell size and
-// four steps; the walk owns the accumulator (workspace slot 1: at most max(2 chunk_bytes, one row), its flags behind it) and the batches.
-struct LimbSink {
-    uint32_t words;                              // u64 words per cell
-    // the launch geometry of the batch [g0, g0 + nw) of the range's complete windows
-    std::function<void(uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V)> geometry;
-    // one batch of norms rows into the outputs (whole rows) and the accumulator (cut rows), which holds rows [r_base, r_base + acc.rows)
-    std::function<int(const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t st)> fold;
-    // the flagged rows [r_base, r_base + n_rows) of the accumulator into the outputs
-    std::function<int(const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t st)> finish;
-    // every output row as a row without values (a short cascade: rows without a complete window keep this)
-    std::function<int(hipStream_t st)> fill_empty;
-};
-int walk_limbs(Fold &f, uint64_t pool, uint64_t R, const LimbSink &k) {
+// The walk of the sinks that fold through a limb accumulator (qd_plan_mean, qd_plan_power, qd_plan_spread): the fold kernel rounds whole
+// rows itself and adds cut rows into Cell::kWords planar u64 a cell, the finish kernel rounds the flagged rows.  The walk owns the
+// accumulator (workspace slot 1: at most max(2 chunk_bytes, one row), its flags behind it) and the batches.  form: 0 lays a batch out with
+// pool_geometry (k_mean), 1 or 4 with power_geometry in that form.
+template <class Cell>
+int walk_limbs(Fold &f, uint64_t pool, uint64_t R, int form, const typename Cell::Out &out) {
     const qd_plan *p = f.p;
     const uint64_t n_windows = f.n_windows;                          // the complete part of the range; R counts the rows as asked
     const hipStream_t st = f.st;
-    int rc = f.is_short ? k.fill_empty(st) : QD_OK;
-    if (rc || !n_windows) return rc;
-    const uint64_t row_bytes = (uint64_t)p->W * k.words * 8;
+    if (!n_windows) return QD_OK;
+    // the launch geometry of the batch [g0, g0 + nw) of the range's complete windows
+    auto geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) {
+        if (form) power_geometry(g0, nw, n_windows, pool, p->W, p->n_cu, form, G, grid, V);
+        else pool_geometry(g0, nw, n_windows, pool, p->W, p->n_cu, G, grid, V);
+    };
+    const uint64_t row_bytes = (uint64_t)p->W * Cell::kWords * 8;
     const uint64_t target = 2 * (p->opt.chunk_bytes ? p->opt.chunk_bytes : (64ull << 20));
     LimbAcc acc{nullptr, nullptr, std::max<uint64_t>(1, std::min<uint64_t>(target / row_bytes, R))};
     void *a = nullptr;
-    rc = f.ws->get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
+    int rc = f.ws->get(1, (size_t)(acc.rows * row_bytes + acc.rows * 4), &a); if (rc) return rc;
     acc.limbs = static_cast<unsigned long long *>(a);
     acc.flags = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(a) + acc.rows * row_bytes);
     auto clear = [&]() { HIPCHK(hipMemsetAsync(acc.limbs, 0, (size_t)(acc.rows * row_bytes + acc.rows * 4), st)); return (int)QD_OK; };
@@ -3688,12 +3713,12 @@ int walk_limbs(Fold &f, uint64_t pool, uint64_t R, const LimbSink &k) {
         const uint64_t cw = f.cw, bw = pool <= cw ? cw / pool * pool : cw;       // seams on row boundaries where a chunk holds a row
         bool open = false;
         uint64_t r_base = 0;
-        auto close = [&]() { const int c = open ? k.finish(acc, r_base, std::min(acc.rows, R - r_base), st) : QD_OK; open = false; return c; };
+        auto close = [&]() { const int c = open ? launch_limbs_finish<Cell>(p, acc, r_base, std::min(acc.rows, R - r_base), out, st) : QD_OK; open = false; return c; };
         for (uint64_t g0 = 0; g0 < n_windows && rc == QD_OK;) {
             uint64_t nw = std::min<uint64_t>(n_windows - g0, bw), grid = 0;
             PieceGeometry G{};
             int V = 1;
-            k.geometry(g0, nw, &G, &grid, &V);
+            geometry(g0, nw, &G, &grid, &V);
             const uint64_t ra = g0 / pool, rb = (g0 + nw - 1) / pool;
             const bool mid = g0 % pool != 0;                                     // row ra has windows in the open span already
             const bool cuts = G.spr > 1 || mid || ((g0 + nw) % pool && g0 + nw != n_windows);
@@ -3705,12 +3730,12 @@ int walk_limbs(Fold &f, uint64_t pool, uint64_t R, const LimbSink &k) {
                 }
                 if (rb >= r_base + acc.rows) {                                   // clip the batch to the rows the accumulator holds
                     nw = (r_base + acc.rows) * pool - g0;
-                    k.geometry(g0, nw, &G, &grid, &V);
+                    geometry(g0, nw, &G, &grid, &V);
                 }
             }
             if (rc == QD_OK)
                 rc = f.device(g0, nw, [&](const float *norms_d, uint64_t, uint64_t, hipStream_t s) {
-                    return k.fold(G, grid, V, norms_d, acc, cuts, cuts ? r_base : ra, s);
+                    return launch_limbs<Cell>(p, G, grid, V, norms_d, out, acc, cuts, cuts ? r_base : ra, s);
                 });
             g0 += nw;
         }
@@ -3726,10 +3751,10 @@ int walk_limbs(Fold &f, uint64_t pool, uint64_t R, const LimbSink &k) {
                 PieceGeometry G{};
                 uint64_t grid = 0;
                 int V = 1;
-                k.geometry(g0, nw, &G, &grid, &V);
-                return k.fold(G, grid, V, norms_d, acc, true, r_base, s);
+                geometry(g0, nw, &G, &grid, &V);
+                return launch_limbs<Cell>(p, G, grid, V, norms_d, out, acc, true, r_base, s);
             });
-            if (rc == QD_OK) rc = k.finish(acc, r_base, std::min(acc.rows, Rn - r_base), st);
+            if (rc == QD_OK) rc = launch_limbs_finish<Cell>(p, acc, r_base, std::min(acc.rows, Rn - r_base), out, st);
         }
     }
     return rc;
@@ -3741,44 +3766,135 @@ int fill_no_values(float *f32_d, double *f64_d, uint32_t *u32_d, uint64_t words,
     if (u32_d) HIPCHK(hipMemsetAsync(u32_d, 0, (size_t)(words * 4), st));
     return QD_OK;
 }
-}  // namespace
 
-int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows) {
-    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    memset(acc, 0, (size_t)(rows * width * QD_MEAN_WORDS * 8));
-    return QD_OK;
+SpreadCell::Out spread_out(float *std, double *ssd, uint32_t *count, float *mean, float *rms) {
+    return {std, ssd, count, mean, rms, (std ? kSpreadStd : 0u) | (ssd ? kSpreadSsd : 0u) | (mean ? kSpreadMean : 0u) | (rms ? kSpreadRms : 0u)};
+}
+// why a qd_spread_rows is refused, or nullptr
+const char *spread_rows_refusal(const qd_spread_rows *out) {
+    if (!out) return "out is NULL";
+    if (!out->std_rows && !out->ssd_rows && !out->count_rows && !out->mean_rows && !out->rms_rows) return "std_rows, ssd_rows, count_rows, mean_rows and rms_rows are all NULL";
+    return nullptr;
 }
 
-int qd_mean_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
+// What a plan call's outputs give plan_limbs, in one place per shape of outputs:
+//   refusal()                     why they are refused (all NULL), or nullptr
+//   place(planes, f, dev, words)  the caller's planes of `words` cells into workspace slot 2 or as they are, the f64 plane first
+//   out(planes)                   the placed planes as the cell's Out;  fill_empty(out, words, st)  every row as a row without values
+// the mean's and the power's: an f32, an f64 and a u32 plane
+template <class C>
+struct TraceRows {
+    using Cell = C;
+    float *f32; double *f64; uint32_t *u32;
+    const char *all_null;
+    const char *refusal() const { return !f32 && !f64 && !u32 ? all_null : nullptr; }
+    int place(Planes &o, Fold &f, bool dev, uint64_t words) const {
+        return o.place(f, 2, dev, {{f64, f64 ? (size_t)(words * 8) : 0}, {f32, f32 ? (size_t)(words * 4) : 0}, {u32, u32 ? (size_t)(words * 4) : 0}});
+    }
+    static typename C::Out out(const Planes &o) { return {static_cast<float *>(o.v[1].dev), static_cast<double *>(o.v[0].dev), static_cast<uint32_t *>(o.v[2].dev)}; }
+    static int fill_empty(const typename C::Out &d, uint64_t words, hipStream_t st) {
+        const auto &[f, g, u] = d;
+        return fill_no_values(f, g, u, words, st);
+    }
+};
+// the spread's: a qd_spread_rows, which may itself be NULL until refusal() has been asked
+struct SpreadRows {
+    using Cell = SpreadCell;
+    const qd_spread_rows *rows;
+    const char *refusal() const { return spread_rows_refusal(rows); }
+    int place(Planes &o, Fold &f, bool dev, uint64_t words) const {                       // [ssd][std][count][mean][rms]
+        auto plane = [&](void *u, size_t each) { return Planes::Plane{u, u ? (size_t)(words * each) : 0, nullptr}; };
+        return o.place(f, 2, dev, {plane(rows->ssd_rows, 8), plane(rows->std_rows, 4), plane(rows->count_rows, 4), plane(rows->mean_rows, 4), plane(rows->rms_rows, 4)});
+    }
+    static SpreadCell::Out out(const Planes &o) {
+        return spread_out(static_cast<float *>(o.v[1].dev), static_cast<double *>(o.v[0].dev), static_cast<uint32_t *>(o.v[2].dev),
+                          static_cast<float *>(o.v[3].dev), static_cast<float *>(o.v[4].dev));
+    }
+    static int fill_empty(const SpreadCell::Out &d, uint64_t words, hipStream_t st) {
+        if (const int e = fill_no_values(d.std, d.ssd, d.count, words, st)) return e;
+        if (const int e = fill_no_values(d.mean, nullptr, nullptr, words, st)) return e;
+        return fill_no_values(d.rms, nullptr, nullptr, words, st);
+    }
+};
+
+// The body of qd_plan_mean, qd_plan_power and qd_plan_spread behind their own NULL check and Fold: the shared refusals in their order,
+// the outputs' own (`rows`, above) in its place among them, `advice` to a sharded plan, `form` for walk_limbs.
+template <class Rows>
+int plan_limbs(Fold &f, uint64_t pool, int out_mem, const Rows &rows, const char *advice, int form) {
+    using Cell = typename Rows::Cell;
+    const uint64_t n_windows = f.n_windows;                          // as asked: admit clamps f.n_windows to the complete part
+    if (const int rc = f.norms_plan()) return rc;
+    if (const int rc = pool_given(pool)) return rc;
+    if (const char *why = rows.refusal()) return fail(QD_ERR_INVALID, "%s", why);
+    if (const int rc = Fold::known_mem(f.src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded(advice)) return rc;
+    if (const int rc = f.admit()) return rc;
+    if (n_windows == 0) return QD_OK;
+    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
+    if (const int rc = pool_rows(&pool, n_windows, f.p->W, kMeanMaxCount, &R, &words)) return rc;
+    if (int rc = f.open()) return rc;
+    Planes planes;
+    int rc = rows.place(planes, f, out_mem == QD_MEM_DEVICE, words);
+    if (rc) return rc;
+    const typename Cell::Out out = Rows::out(planes);
+    if (f.is_short) rc = Rows::fill_empty(out, words, f.st);         // a short cascade: rows without a complete window keep this
+    if (rc == QD_OK) rc = walk_limbs<Cell>(f, pool, R, form, out);
+    if (rc == QD_OK) rc = planes.home(f.st);
+    return f.close(rc);
+}
+
+// The CPU twins of the three sinks: cells of Cell::kWords words, interleaved (word k of cell c at c kWords + k); the count word is the last
+template <class Cell>
+uint64_t cell_count(const uint64_t *cell) { return (cell[Cell::kWords - 1] & 0xffffffffull) + (cell[Cell::kWords - 1] >> 32); }
+
+template <class Cell>
+int limb_init(uint64_t *acc, uint32_t width, uint64_t rows) {
+    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    memset(acc, 0, (size_t)(rows * width * Cell::kWords * 8));
+    return QD_OK;
+}
+template <class Cell>
+int limb_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
     if (const int rc = pool_given(pool)) return rc;
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
     if (n == 0) return QD_OK;
     if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
-    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return mean_cell_count(acc + cell * QD_MEAN_WORDS); })) return rc;
+    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return cell_count<Cell>(acc + cell * Cell::kWords); })) return rc;
     for (uint64_t i = 0; i < n; ++i) {
         const float *row = norms + i * width;
-        uint64_t *cells = acc + (at + i) / pool * width * QD_MEAN_WORDS;
+        uint64_t *cells = acc + (at + i) / pool * width * Cell::kWords;
         for (uint32_t b = 0; b < width; ++b) {
             uint32_t bits;
             memcpy(&bits, row + b, 4);
-            mean_add(cells + (uint64_t)b * QD_MEAN_WORDS, bits);
+            Cell::add(cells + (uint64_t)b * Cell::kWords, bits);
         }
     }
     return QD_OK;
 }
-
-int qd_mean_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
+template <class Cell>
+int limb_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
     if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     const uint64_t cells = rows * width;
     for (uint64_t c = 0; c < cells; ++c)
-        if (mean_cell_count(dst + c * QD_MEAN_WORDS) + mean_cell_count(src + c * QD_MEAN_WORDS) > kMeanMaxCount)
+        if (cell_count<Cell>(dst + c * Cell::kWords) + cell_count<Cell>(src + c * Cell::kWords) > kMeanMaxCount)
             return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
-    for (uint64_t i = 0; i < cells * QD_MEAN_WORDS; ++i) dst[i] += src[i];
+    for (uint64_t i = 0; i < cells * Cell::kWords; ++i) dst[i] += src[i];
     return QD_OK;
 }
+
+static_assert(MeanCell::kWords == QD_MEAN_WORDS && PowerCell::kWords == QD_POWER_WORDS && SpreadCell::kWords == QD_SPREAD_WORDS, "the header's cell sizes");
+}  // namespace
+}  // extern "C++"
+
+// ---- average-trace rows
+
+int qd_mean_init(uint64_t *acc, uint32_t width, uint64_t rows) { return limb_init<MeanCell>(acc, width, rows); }
+int qd_mean_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) { return limb_fold<MeanCell>(acc, width, pool, at, norms, n); }
+int qd_mean_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) { return limb_merge<MeanCell>(dst, src, width, rows); }
 
 int qd_mean_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *mean_rows, double *sum_rows, uint32_t *count_rows) {
     if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
@@ -3799,117 +3915,15 @@ int qd_plan_mean(qd_plan *p, const void *src, int src_mem, uint64_t src_first, u
                  uint64_t pool, float *mean_rows, double *sum_rows, uint32_t *count_rows, int out_mem, void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_mean", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
-    if (const int rc = f.norms_plan()) return rc;
-    if (const int rc = pool_given(pool)) return rc;
-    if (!mean_rows && !sum_rows && !count_rows) return fail(QD_ERR_INVALID, "mean_rows, sum_rows and count_rows are all NULL");
-    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
-    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
-    if (const int rc = f.unsharded("a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)")) return rc;
-    if (const int rc = f.admit()) return rc;
-    if (n_windows == 0) return QD_OK;
-    const uint32_t W = p->W;
-    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
-    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
-    if (int rc = f.open()) return rc;
-    Planes planes;                                                   // the outputs: [sum][mean][count]
-    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {{sum_rows, sum_rows ? (size_t)(words * 8) : 0}, {mean_rows, mean_rows ? (size_t)(words * 4) : 0},
-                                                           {count_rows, count_rows ? (size_t)(words * 4) : 0}});
-    if (rc) return rc;
-    const MeanOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev)};
-    // the limb accumulator (qd_mean.h) and the batches: walk_limbs
-    LimbSink k;
-    k.words = kMeanWords;
-    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { pool_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, G, grid, V); };
-    k.fold = [&](const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
-        MeanParams M{};
-        M.G = G;
-        return launch_mean(p, M, grid, V, norms_d, out, acc, cuts, r_base, s);
-    };
-    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_mean_finish(p, acc, r_base, n_rows, out, s); };
-    k.fill_empty = [&](hipStream_t s) { return fill_no_values(out.mean, out.sum, out.count, words, s); };
-    rc = walk_limbs(f, pool, R, k);
-    if (rc == QD_OK) rc = planes.home(f.st);
-    return f.close(rc);
+    return plan_limbs(f, pool, out_mem, TraceRows<MeanCell>{mean_rows, sum_rows, count_rows, "mean_rows, sum_rows and count_rows are all NULL"},
+        "a sharded plan is not averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_mean_merge)", 0);
 }
 
-// ------------------------------------------------------------------ RMS-trace rows
+// ---- RMS-trace rows
 
-namespace {
-struct PowerOut { float *rms; double *sumsq; uint32_t *count; };
-
-// k_power's form (qd_power.h): one bin a lane; a development build also holds four bins a lane, for measuring them side by side
-#ifdef QD_DEVELOP
-int power_form() { const char *e = dev_env("QD_POWER_V"); return e && atoi(e) == 4 ? 4 : 1; }
-#else
-int power_form() { return 1; }
-#endif
-
-// one batch of norms rows (device memory, 16-byte aligned) into the outputs (whole rows) and the accumulator (cut rows), as launch_mean
-int launch_power(const qd_plan *p, const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const PowerOut &out, const LimbAcc &acc,
-                 bool cuts, uint64_t r_base, hipStream_t st) {
-    if (const int rc = launch_grid(grid, G.nw)) return rc;
-    const uint64_t ra = G.g0 / G.pool, rb = (G.g0 + G.nw - 1) / G.pool;
-    if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
-    PowerParams M{};
-    M.G = G;
-    M.norms = norms_d;
-    M.rms = out.rms; M.sumsq = out.sumsq; M.count = out.count;
-    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
-    void (*fn)(PowerParams) = k_power<1>;
-#ifdef QD_DEVELOP
-    if (V == 4) fn = k_power<4>;
-#endif
-    hipLaunchKernelGGL(fn, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
-    HIPCHK(hipGetLastError());
-    return QD_OK;
-}
-int launch_power_finish(const qd_plan *p, const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, const PowerOut &out, hipStream_t st) {
-    const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
-    if (!cells) return QD_OK;
-    hipLaunchKernelGGL(k_power_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
-                       out.rms, out.sumsq, out.count);
-    HIPCHK(hipGetLastError());
-    return QD_OK;
-}
-uint64_t power_cell_count(const uint64_t *cell) { return (cell[18] & 0xffffffffull) + (cell[18] >> 32); }
-}  // namespace
-
-int qd_power_init(uint64_t *acc, uint32_t width, uint64_t rows) {
-    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    memset(acc, 0, (size_t)(rows * width * QD_POWER_WORDS * 8));
-    return QD_OK;
-}
-
-int qd_power_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
-    if (const int rc = pool_given(pool)) return rc;
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (n == 0) return QD_OK;
-    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
-    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return power_cell_count(acc + cell * QD_POWER_WORDS); })) return rc;
-    for (uint64_t i = 0; i < n; ++i) {
-        const float *row = norms + i * width;
-        uint64_t *cells = acc + (at + i) / pool * width * QD_POWER_WORDS;
-        for (uint32_t b = 0; b < width; ++b) {
-            uint32_t bits;
-            memcpy(&bits, row + b, 4);
-            power_add(cells + (uint64_t)b * QD_POWER_WORDS, bits);
-        }
-    }
-    return QD_OK;
-}
-
-int qd_power_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
-    if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    const uint64_t cells = rows * width;
-    for (uint64_t c = 0; c < cells; ++c)
-        if (power_cell_count(dst + c * QD_POWER_WORDS) + power_cell_count(src + c * QD_POWER_WORDS) > kMeanMaxCount)
-            return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
-    for (uint64_t i = 0; i < cells * QD_POWER_WORDS; ++i) dst[i] += src[i];
-    return QD_OK;
-}
+int qd_power_init(uint64_t *acc, uint32_t width, uint64_t rows) { return limb_init<PowerCell>(acc, width, rows); }
+int qd_power_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) { return limb_fold<PowerCell>(acc, width, pool, at, norms, n); }
+int qd_power_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) { return limb_merge<PowerCell>(dst, src, width, rows); }
 
 int qd_power_finish(const uint64_t *acc, uint32_t width, uint64_t rows, float *rms_rows, double *sumsq_rows, uint32_t *count_rows) {
     if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
@@ -3930,124 +3944,26 @@ int qd_plan_power(qd_plan *p, const void *src, int src_mem, uint64_t src_first, 
                   uint64_t pool, float *rms_rows, double *sumsq_rows, uint32_t *count_rows, int out_mem, void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_power", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
-    if (const int rc = f.norms_plan()) return rc;
-    if (const int rc = pool_given(pool)) return rc;
-    if (!rms_rows && !sumsq_rows && !count_rows) return fail(QD_ERR_INVALID, "rms_rows, sumsq_rows and count_rows are all NULL");
-    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
-    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
-    if (const int rc = f.unsharded("a sharded plan is not power-averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_power_merge)")) return rc;
-    if (const int rc = f.admit()) return rc;
-    if (n_windows == 0) return QD_OK;
-    const uint32_t W = p->W;
-    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
-    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
-    if (int rc = f.open()) return rc;
-    Planes planes;                                                   // the outputs: [sumsq][rms][count]
-    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {{sumsq_rows, sumsq_rows ? (size_t)(words * 8) : 0}, {rms_rows, rms_rows ? (size_t)(words * 4) : 0},
-                                                           {count_rows, count_rows ? (size_t)(words * 4) : 0}});
-    if (rc) return rc;
-    const PowerOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev)};
-    // the limb accumulator (qd_power.h) and the batches: walk_limbs
-    LimbSink k;
-    k.words = kPowerWords;
-    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { power_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, power_form(), G, grid, V); };
-    k.fold = [&](const PieceGeometry &G, uint64_t grid, int V, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
-        return launch_power(p, G, grid, V, norms_d, out, acc, cuts, r_base, s);
-    };
-    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_power_finish(p, acc, r_base, n_rows, out, s); };
-    k.fill_empty = [&](hipStream_t s) { return fill_no_values(out.rms, out.sumsq, out.count, words, s); };
-    rc = walk_limbs(f, pool, R, k);
-    if (rc == QD_OK) rc = planes.home(f.st);
-    return f.close(rc);
+    return plan_limbs(f, pool, out_mem, TraceRows<PowerCell>{rms_rows, sumsq_rows, count_rows, "rms_rows, sumsq_rows and count_rows are all NULL"},
+        "a sharded plan is not power-averaged in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_power_merge)",
+        power_form());
 }
 
-// ------------------------------------------------------------------ deviation-trace rows
+// ---- deviation-trace rows
 
-namespace {
-struct SpreadOut {
-    float *std; double *ssd; uint32_t *count; float *mean; float *rms;
-    uint32_t want() const { return (std ? kSpreadStd : 0u) | (ssd ? kSpreadSsd : 0u) | (mean ? kSpreadMean : 0u) | (rms ? kSpreadRms : 0u); }
-};
-
-// one batch of norms rows (device memory, 16-byte aligned) into the outputs (whole rows) and the accumulator (cut rows), as launch_mean
-int launch_spread(const qd_plan *p, const PieceGeometry &G, uint64_t grid, const float *norms_d, const SpreadOut &out, const LimbAcc &acc, bool cuts,
-                  uint64_t r_base, hipStream_t st) {
-    if (const int rc = launch_grid(grid, G.nw)) return rc;
-    const uint64_t ra = G.g0 / G.pool, rb = (G.g0 + G.nw - 1) / G.pool;
-    if (cuts && (ra < r_base || rb >= r_base + acc.rows)) return fail(QD_ERR_INVALID, "internal: rows [%llu,%llu] outside the accumulator", (unsigned long long)ra, (unsigned long long)rb);
-    SpreadParams M{};
-    M.G = G;
-    M.norms = norms_d;
-    M.std = out.std; M.ssd = out.ssd; M.count = out.count; M.mean = out.mean; M.rms = out.rms; M.want = out.want();
-    M.acc = acc.limbs; M.flags = acc.flags; M.r_base = r_base; M.acc_rows = cuts ? acc.rows : 0; M.cells = acc.rows * p->W;
-    hipLaunchKernelGGL(k_spread, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, M);
-    HIPCHK(hipGetLastError());
-    return QD_OK;
-}
-int launch_spread_finish(const qd_plan *p, const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, const SpreadOut &out, hipStream_t st) {
-    const uint64_t cells = n_rows * p->W, grid = (cells + kPoolThreads - 1) / kPoolThreads;
-    if (!cells) return QD_OK;
-    hipLaunchKernelGGL(k_spread_finish, dim3((uint32_t)grid), dim3(kPoolThreads), 0, st, acc.limbs, acc.flags, acc.rows * p->W, r_base, n_rows, p->W,
-                       out.want(), out.std, out.ssd, out.count, out.mean, out.rms);
-    HIPCHK(hipGetLastError());
-    return QD_OK;
-}
-uint64_t spread_cell_count(const uint64_t *cell) { return (cell[27] & 0xffffffffull) + (cell[27] >> 32); }
-int spread_rows_given(const qd_spread_rows *out) {
-    if (!out) return fail(QD_ERR_INVALID, "out is NULL");
-    if (!out->std_rows && !out->ssd_rows && !out->count_rows && !out->mean_rows && !out->rms_rows)
-        return fail(QD_ERR_INVALID, "std_rows, ssd_rows, count_rows, mean_rows and rms_rows are all NULL");
-    return QD_OK;
-}
-}  // namespace
-
-int qd_spread_init(uint64_t *acc, uint32_t width, uint64_t rows) {
-    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    memset(acc, 0, (size_t)(rows * width * QD_SPREAD_WORDS * 8));
-    return QD_OK;
-}
-
-int qd_spread_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) {
-    if (const int rc = pool_given(pool)) return rc;
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (n == 0) return QD_OK;
-    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
-    if (const int rc = rows_have_room(pool, at, n, width, [&](uint64_t cell) { return spread_cell_count(acc + cell * QD_SPREAD_WORDS); })) return rc;
-    for (uint64_t i = 0; i < n; ++i) {
-        const float *row = norms + i * width;
-        uint64_t *cells = acc + (at + i) / pool * width * QD_SPREAD_WORDS;
-        for (uint32_t b = 0; b < width; ++b) {
-            uint32_t bits;
-            memcpy(&bits, row + b, 4);
-            spread_add(cells + (uint64_t)b * QD_SPREAD_WORDS, bits);
-        }
-    }
-    return QD_OK;
-}
-
-int qd_spread_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) {
-    if (!dst || !src) return fail(QD_ERR_INVALID, "acc is NULL");
-    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    const uint64_t cells = rows * width;
-    for (uint64_t c = 0; c < cells; ++c)
-        if (spread_cell_count(dst + c * QD_SPREAD_WORDS) + spread_cell_count(src + c * QD_SPREAD_WORDS) > kMeanMaxCount)
-            return fail(QD_ERR_INVALID, "row %llu would hold more than 2^31 windows", (unsigned long long)(c / width));
-    for (uint64_t i = 0; i < cells * QD_SPREAD_WORDS; ++i) dst[i] += src[i];
-    return QD_OK;
-}
+int qd_spread_init(uint64_t *acc, uint32_t width, uint64_t rows) { return limb_init<SpreadCell>(acc, width, rows); }
+int qd_spread_fold(uint64_t *acc, uint32_t width, uint64_t pool, uint64_t at, const float *norms, uint64_t n) { return limb_fold<SpreadCell>(acc, width, pool, at, norms, n); }
+int qd_spread_merge(uint64_t *dst, const uint64_t *src, uint32_t width, uint64_t rows) { return limb_merge<SpreadCell>(dst, src, width, rows); }
 
 int qd_spread_finish(const uint64_t *acc, uint32_t width, uint64_t rows, const qd_spread_rows *out) {
     if (!acc) return fail(QD_ERR_INVALID, "acc is NULL");
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    if (const int rc = spread_rows_given(out)) return rc;
-    const SpreadOut o{out->std_rows, out->ssd_rows, out->count_rows, out->mean_rows, out->rms_rows};
-    const uint32_t want = o.want();
+    if (const char *why = spread_rows_refusal(out)) return fail(QD_ERR_INVALID, "%s", why);
+    const SpreadCell::Out o = spread_out(out->std_rows, out->ssd_rows, out->count_rows, out->mean_rows, out->rms_rows);
     const uint64_t cells = rows * width;
     for (uint64_t c = 0; c < cells; ++c) {
-        SpreadCell r;
-        spread_finish_cell(acc + c * QD_SPREAD_WORDS, want, &r);
+        SpreadRounded r;
+        spread_finish_cell(acc + c * QD_SPREAD_WORDS, o.want, &r);
         if (o.std) memcpy(o.std + c, &r.std_bits, 4);
         if (o.ssd) o.ssd[c] = r.ssd;
         if (o.count) o.count[c] = r.count;
@@ -4061,41 +3977,8 @@ int qd_plan_spread(qd_plan *p, const void *src, int src_mem, uint64_t src_first,
                    uint64_t pool, const qd_spread_rows *rows, int out_mem, void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
     Fold f{p, "qd_plan_spread", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
-    if (const int rc = f.norms_plan()) return rc;
-    if (const int rc = pool_given(pool)) return rc;
-    if (const int rc = spread_rows_given(rows)) return rc;
-    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
-    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
-    if (const int rc = f.unsharded("a sharded plan's deviation is not taken in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_spread_merge)")) return rc;
-    if (const int rc = f.admit()) return rc;
-    if (n_windows == 0) return QD_OK;
-    const uint32_t W = p->W;
-    uint64_t R, words;                                               // rows of the range as asked; f.n_windows is its complete part
-    if (const int rc = pool_rows(&pool, n_windows, W, kMeanMaxCount, &R, &words)) return rc;
-    if (int rc = f.open()) return rc;
-    Planes planes;                                                   // the outputs: [ssd][std][count][mean][rms]
-    auto plane = [&](void *u, size_t each) { return Planes::Plane{u, u ? (size_t)(words * each) : 0, nullptr}; };
-    int rc = planes.place(f, 2, out_mem == QD_MEM_DEVICE, {plane(rows->ssd_rows, 8), plane(rows->std_rows, 4), plane(rows->count_rows, 4),
-                                                           plane(rows->mean_rows, 4), plane(rows->rms_rows, 4)});
-    if (rc) return rc;
-    const SpreadOut out{static_cast<float *>(planes.v[1].dev), static_cast<double *>(planes.v[0].dev), static_cast<uint32_t *>(planes.v[2].dev),
-                        static_cast<float *>(planes.v[3].dev), static_cast<float *>(planes.v[4].dev)};
-    // the limb accumulator (qd_spread.h) and the batches: walk_limbs
-    LimbSink k;
-    k.words = kSpreadWords;
-    k.geometry = [&](uint64_t g0, uint64_t nw, PieceGeometry *G, uint64_t *grid, int *V) { power_geometry(g0, nw, f.n_windows, pool, W, p->n_cu, 1, G, grid, V); };
-    k.fold = [&](const PieceGeometry &G, uint64_t grid, int, const float *norms_d, const LimbAcc &acc, bool cuts, uint64_t r_base, hipStream_t s) {
-        return launch_spread(p, G, grid, norms_d, out, acc, cuts, r_base, s);
-    };
-    k.finish = [&](const LimbAcc &acc, uint64_t r_base, uint64_t n_rows, hipStream_t s) { return launch_spread_finish(p, acc, r_base, n_rows, out, s); };
-    k.fill_empty = [&](hipStream_t s) {
-        if (const int e = fill_no_values(out.std, out.ssd, out.count, words, s)) return e;
-        if (const int e = fill_no_values(out.mean, nullptr, nullptr, words, s)) return e;
-        return fill_no_values(out.rms, nullptr, nullptr, words, s);
-    };
-    rc = walk_limbs(f, pool, R, k);
-    if (rc == QD_OK) rc = planes.home(f.st);
-    return f.close(rc);
+    return plan_limbs(f, pool, out_mem, SpreadRows{rows},
+        "a sharded plan's deviation is not taken in one call: give each device a contiguous range of rows on a plan of its own, or merge per-shard accumulators (qd_spread_merge)", 1);
 }
 
 // ------------------------------------------------------------------ percentile traces and persistence counts

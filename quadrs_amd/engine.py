@@ -339,30 +339,45 @@ def pool_fold(norms, pool, at=0, into=None):
     return peak, floor
 
 
+def _limb_init(name, words, width, rows):
+    """qd_<name>_init over a new uint64[rows, width, words]"""
+    acc = np.empty((int(rows), int(width), words), dtype=np.uint64)
+    check(getattr(lib(), "qd_%s_init" % name)(_np_ptr(acc), int(width), int(rows)))
+    return acc
+
+
+def _limb_fold(name, words, norms, pool, at, into):
+    """qd_<name>_fold of norms rows (n, width) into `into`, or into a new accumulator of ceil((at + n) / pool) rows"""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    if into is None:
+        into = _limb_init(name, words, width, -(-(int(at) + n) // int(pool)) if pool else 0)
+    check(getattr(lib(), "qd_%s_fold" % name)(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
+    return into
+
+
+def _limb_merge(name, dst, src):
+    """qd_<name>_merge: dst += src"""
+    if dst.shape != src.shape:
+        raise ValueError("accumulators of different shapes do not merge")
+    check(getattr(lib(), "qd_%s_merge" % name)(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
+    return dst
+
+
 def mean_init(width, rows):
     """qd_mean_init: the exact-sum accumulator of `rows` rows of `width` cells, uint64[rows, width, MEAN_WORDS], all words 0."""
-    acc = np.empty((int(rows), int(width), _ffi.MEAN_WORDS), dtype=np.uint64)
-    check(lib().qd_mean_init(_np_ptr(acc), int(width), int(rows)))
-    return acc
+    return _limb_init("mean", _ffi.MEAN_WORDS, width, rows)
 
 
 def mean_fold(norms, pool, at=0, into=None):
     """qd_mean_fold: norms rows (n, width) are windows at, at+1, ... of a range and accumulate into rows (at + i) // pool of the
     accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
-    a = np.ascontiguousarray(norms, dtype=np.float32)
-    n, width = a.shape
-    if into is None:
-        into = mean_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
-    check(lib().qd_mean_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
-    return into
+    return _limb_fold("mean", _ffi.MEAN_WORDS, norms, pool, at, into)
 
 
 def mean_merge(dst, src):
     """qd_mean_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
-    if dst.shape != src.shape:
-        raise ValueError("accumulators of different shapes do not merge")
-    check(lib().qd_mean_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
-    return dst
+    return _limb_merge("mean", dst, src)
 
 
 def mean_finish(acc):
@@ -377,28 +392,18 @@ def mean_finish(acc):
 
 def power_init(width, rows):
     """qd_power_init: the exact sum-of-squares accumulator of `rows` rows of `width` cells, uint64[rows, width, POWER_WORDS], all words 0."""
-    acc = np.empty((int(rows), int(width), _ffi.POWER_WORDS), dtype=np.uint64)
-    check(lib().qd_power_init(_np_ptr(acc), int(width), int(rows)))
-    return acc
+    return _limb_init("power", _ffi.POWER_WORDS, width, rows)
 
 
 def power_fold(norms, pool, at=0, into=None):
     """qd_power_fold: norms rows (n, width) are windows at, at+1, ... of a range and their squares accumulate into rows (at + i) // pool
     of the accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
-    a = np.ascontiguousarray(norms, dtype=np.float32)
-    n, width = a.shape
-    if into is None:
-        into = power_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
-    check(lib().qd_power_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
-    return into
+    return _limb_fold("power", _ffi.POWER_WORDS, norms, pool, at, into)
 
 
 def power_merge(dst, src):
     """qd_power_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
-    if dst.shape != src.shape:
-        raise ValueError("accumulators of different shapes do not merge")
-    check(lib().qd_power_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
-    return dst
+    return _limb_merge("power", dst, src)
 
 
 def power_finish(acc):
@@ -433,28 +438,18 @@ def _spread_rows(ptr_of):
 def spread_init(width, rows):
     """qd_spread_init: the exact sum and sum-of-squares accumulator of `rows` rows of `width` cells, uint64[rows, width, SPREAD_WORDS], all
     words 0."""
-    acc = np.empty((int(rows), int(width), _ffi.SPREAD_WORDS), dtype=np.uint64)
-    check(lib().qd_spread_init(_np_ptr(acc), int(width), int(rows)))
-    return acc
+    return _limb_init("spread", _ffi.SPREAD_WORDS, width, rows)
 
 
 def spread_fold(norms, pool, at=0, into=None):
     """qd_spread_fold: norms rows (n, width) are windows at, at+1, ... of a range; they and their squares accumulate into rows
     (at + i) // pool of the accumulator `into`, or of a new one of ceil((at + n) / pool) rows.  Returns the accumulator."""
-    a = np.ascontiguousarray(norms, dtype=np.float32)
-    n, width = a.shape
-    if into is None:
-        into = spread_init(width, -(-(int(at) + n) // int(pool)) if pool else 0)
-    check(lib().qd_spread_fold(_np_ptr(into), width, int(pool), int(at), _np_ptr(a), n))
-    return into
+    return _limb_fold("spread", _ffi.SPREAD_WORDS, norms, pool, at, into)
 
 
 def spread_merge(dst, src):
     """qd_spread_merge: dst += src word by word (two accumulators of the same rows and width).  Returns dst."""
-    if dst.shape != src.shape:
-        raise ValueError("accumulators of different shapes do not merge")
-    check(lib().qd_spread_merge(_np_ptr(dst), _np_ptr(np.ascontiguousarray(src, dtype=np.uint64)), dst.shape[1], dst.shape[0]))
-    return dst
+    return _limb_merge("spread", dst, src)
 
 
 def spread_finish(acc, outputs=None):

@@ -114,7 +114,7 @@ uint32_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_
 void check(const std::vector<uint32_t> &vals, const char *what, long want_std = -1) {
     uint64_t acc[qd::kSpreadWords] = {0}, ma[qd::kMeanWords] = {0}, pa[qd::kPowerWords] = {0};
     for (uint32_t b : vals) { qd::spread_add(acc, b); qd::mean_add(ma, b); qd::power_add(pa, b); }
-    qd::SpreadCell c;
+    qd::SpreadRounded c;
     qd::spread_finish_cell(acc, qd::kSpreadAll, &c);
     uint32_t mb, rb, cnt; double s;
     qd::mean_finish_cell(ma, &mb, &s, &cnt);
@@ -127,7 +127,7 @@ void check(const std::vector<uint32_t> &vals, const char *what, long want_std = 
     else ok = ok && c.std_bits == r.std_bits && ssd_right(c.ssd, r);
     if (want_std >= 0 && c.std_bits != (uint32_t)want_std) ok = false;
     // each half alone gives the same bits
-    qd::SpreadCell d;
+    qd::SpreadRounded d;
     qd::spread_finish_cell(acc, qd::kSpreadSsd, &d);
     uint64_t db; memcpy(&db, &d.ssd, 8);
     ok = ok && db == sb;
