@@ -850,6 +850,74 @@ int qd_plan_bursts  (qd_plan *plan, const void *src, int src_mem, uint64_t src_f
                      uint64_t first_window, uint64_t n_windows, const float *thresholds, uint64_t min_len,
                      qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ emission list of a norms plan
+ * What happened when, per signal and not per bin: the thresholds of the burst list applied to windows [w0, w0 + n) of a
+ * QD_EPI_NORMS_F32 plan of width W, and one record per connected region of on cells in the (window, bin) plane.  This is the
+ * project's own definition; the reference has no counterpart.
+ *
+ * Thresholds, on cells.  Exactly the burst list's rules: a(v) = bits(v) & 0x7fffffff; a threshold is +0 ... +inf, or a NaN of either
+ * sign, which masks its bin; negative numbers, -0.0 and -inf are QD_ERR_INVALID; a NaN value is never on.
+ * Emission.  A maximal 4-connected set of on cells of the range: cells (i, b) and (i', b') are neighbours iff |i - i'| + |b - b'| = 1.
+ * Bins 0 and W - 1 are not neighbours (the fftshifted row does not wrap), and an emission is cut at the range's edges.
+ * Record.  first, last: the first and last window, range-relative and inclusive.  cells: the number of on cells.  lo, hi: the lowest
+ * and highest bin, inclusive.  end_bin: the lowest bin that is on in window `last`.  peak: the greatest a(v) as an f32 (+inf is
+ * possible); (peak_at, peak_bin) is the lexicographically smallest (window, bin) that attains it.  flags: bit 0 is set when the emission
+ * touches the range's first window, bit 1 when it touches the range's last window (both mean it was cut); all other bits are 0.
+ * Which are kept.  An emission is kept iff last - first + 1 >= min_len and cells >= min_cells; both are >= 1, and 0 is QD_ERR_INVALID.
+ * Order.  Ascending (last, end_bin).  Cell (last, end_bin) belongs to exactly one emission, so no two emissions share the key.  It is
+ * the order of an event log: an emission is reported when it ends.
+ * Counts.  *found is the number of kept emissions, always the full count; the list receives the first min(found, cap) of them in that
+ * order, and its bytes past them are not touched.  cap == 0 with list == NULL counts only.
+ * Determinism.  Every output is an integer count, an integer extreme or an index: no batch, chunk, span, tile, memory kind, cap or launch
+ * order changes a byte. */
+typedef struct qd_emission {
+    uint64_t first, last, cells, peak_at;
+    uint32_t lo, hi, end_bin, peak_bin;
+    float    peak;
+    uint32_t flags;
+} qd_emission;                     /* 56 bytes, little-endian as it lies */
+#define QD_EMISSION_CUT_FIRST 1u
+#define QD_EMISSION_CUT_LAST  2u
+#define QD_EMISSIONS_WORDS 8       /* u64 of state per bin: the bin's open slot or ~0, and the 7 words of one record of the open table */
+/* A call's list workspace (a list that is not device memory, cap x 56 bytes) is at most this; above it qd_plan_emissions is
+ * QD_ERR_UNSUPPORTED.  The labelling's own workspace stays below it whatever chunk_bytes is. */
+#define QD_EMISSIONS_MAX_WORKSPACE (1ull << 30)
+#define QD_EMISSIONS_MAX_WIDTH 4096u
+
+/* The CPU twin, byte for byte.  It is stateful because an emission crosses parts: `state` is QD_EMISSIONS_WORDS*width + 2 u64 of host
+ * memory: per bin the slot of the emission that is open there in the previous row, or ~0; a table of at most `width` open partial
+ * records (a row has at most ceil(width / 2) open emissions); the next window expected; the number of open records.
+ * _init: nothing open, next window 0.  _fold takes windows at ... at+n-1 of the range (n rows of `width` host f32), one row at a time;
+ * `at` must equal the state's next window, else QD_ERR_INVALID.  A row joins its runs of on cells with the open emissions above them
+ * (a union-find over the open slots) and emits the open emissions that found no on neighbour, by end_bin ascending, so the order of
+ * emission is the order of the list.  *found is in/out and keeps counting past cap; record number *found goes to list[*found] while
+ * that is below cap.  _finish closes what is open at the last window folded, in the same order, with bit 1 of flags set, and leaves
+ * the state as _init does.  Any partition of a range into folds followed by _finish gives exactly the list of the definition; n == 0
+ * folds are fine.
+ * QD_ERR_INVALID: width 0, NULL state, thresholds or found, an inadmissible threshold, min_len == 0, min_cells == 0, list == NULL with
+ * cap > 0, norms NULL with n > 0. */
+int qd_emissions_init  (uint64_t *state, uint32_t width);
+int qd_emissions_fold  (uint64_t *state, uint32_t width, const float *thresholds, uint64_t min_len, uint64_t min_cells, uint64_t at,
+                        const float *norms, uint64_t n, qd_emission *list, uint64_t cap, uint64_t *found);
+int qd_emissions_finish(uint64_t *state, uint32_t width, uint64_t min_len, uint64_t min_cells, qd_emission *list, uint64_t cap,
+                        uint64_t *found);
+/* The emission list of windows [first_window, +n_windows) of a QD_EPI_NORMS_F32 plan; src, src_mem, src_first, src_count and `stream`
+ * as for qd_plan_bursts (device, host and pinned sources), and so are the refusals and a cascade's short read.  `list` (cap records,
+ * 8-byte aligned) is of out_mem memory (host, pinned or device); `found` and `thresholds` are host memory, and the call returns after
+ * everything is complete.  A list that is not device memory goes through a workspace of cap x 56 bytes that is copied down once
+ * (min(found, cap) records of it).  The windows go batch by batch through the plan's own kernel into a device carrier; a batch is
+ * labelled in spans of at most 2^20 / W windows, and the open emissions are carried from span to span and from batch to batch on the
+ * device.  A fold leaves qd_plan_get_stats alone.
+ * QD_ERR_INVALID: any epilogue other than QD_EPI_NORMS_F32, thresholds or found NULL, an inadmissible threshold, min_len == 0,
+ * min_cells == 0, list NULL with cap > 0, an unknown memory kind.  QD_ERR_UNSUPPORTED: a plan created with shards (run one range on one
+ * device; an emission crosses the seam), a list workspace above QD_EMISSIONS_MAX_WORKSPACE, a width above QD_EMISSIONS_MAX_WIDTH.
+ * QD_ERR_SHORT: a range past the sink's loop (the outputs are not touched), and for a cascade a range past qd_plan_complete_windows:
+ * the complete part is listed, and the open emissions close at the last complete window.  n_windows == 0: QD_OK with *found = 0 and
+ * the list untouched. */
+int qd_plan_emissions  (qd_plan *plan, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                        uint64_t first_window, uint64_t n_windows, const float *thresholds, uint64_t min_len, uint64_t min_cells,
+                        qd_emission *list, uint64_t cap, uint64_t *found, int out_mem, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

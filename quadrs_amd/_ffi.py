@@ -34,6 +34,7 @@ SYMBOLS = [
     "qd_bands_fold", "qd_plan_bands",
     "qd_picture_geometry", "qd_picture_color", "qd_picture_init", "qd_picture_fold", "qd_plan_picture",
     "qd_bursts_init", "qd_bursts_fold", "qd_bursts_finish", "qd_plan_bursts",
+    "qd_emissions_init", "qd_emissions_fold", "qd_emissions_finish", "qd_plan_emissions",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
@@ -43,6 +44,7 @@ DENSITY_MAX_LEVELS, DENSITY_BUCKETS, DENSITY_MAX_Q = 256, 2041, 8
 BANDS_MAX, BAND_NONE = 255, 0xffffffff
 PICTURE_MAX_WORKSPACE = 1 << 30
 BURSTS_WORDS, BURSTS_MAX_WORKSPACE = 3, 1 << 30
+EMISSIONS_WORDS, EMISSIONS_MAX_WORKSPACE, EMISSIONS_MAX_WIDTH = 8, 1 << 30, 4096
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -239,6 +241,10 @@ def lib():
             "qd_bursts_fold": (i32, [vp, C.c_uint32, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), vp]),
             "qd_bursts_finish": (i32, [vp, C.c_uint32, u64, vp, u64, C.POINTER(u64)]),
             "qd_plan_bursts": (i32, [vp, vp, i32, u64, u64, u64, u64, vp, u64, vp, u64, C.POINTER(u64), vp, i32, vp]),
+            "qd_emissions_init": (i32, [vp, C.c_uint32]),
+            "qd_emissions_fold": (i32, [vp, C.c_uint32, vp, u64, u64, u64, vp, u64, vp, u64, C.POINTER(u64)]),
+            "qd_emissions_finish": (i32, [vp, C.c_uint32, u64, u64, vp, u64, C.POINTER(u64)]),
+            "qd_plan_emissions": (i32, [vp, vp, i32, u64, u64, u64, u64, vp, u64, u64, vp, u64, C.POINTER(u64), i32, vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

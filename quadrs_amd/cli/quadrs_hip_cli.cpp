@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS, OP_EMISSIONS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -114,6 +114,7 @@ struct Op {
     uint32_t px_w = 0, px_h = 0, stretch = 4, marker = 0; float scale = 2.29f;   // picture -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29]
     bool has_level = false, has_times = false; float level = 0, times = 1; std::string levels_file;   // bursts (-level X | -levels FILE) [-times K]
     uint64_t min_len = 1, cap = 1048576, print_n = 0;                   // bursts [-min 1] [-cap 1048576] [-print 0]
+    uint64_t min_cells = 1;                                             // emissions [-cells 1]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
     int sink_window = 0;                                                // -window bh|rect of the window-plan verbs (qd_chain_desc.windowing)
 };
@@ -188,7 +189,7 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
         ArgMap raw = read_just_args(argv, i);
         Op op{};
         // -window bh|rect (default rect) of every verb that builds a window plan through chain_desc: parsed here, once, with `rows -window`'s words
-        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture", "bursts"};
+        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture", "bursts", "emissions"};
         if (std::find_if(std::begin(kWindowVerbs), std::end(kWindowVerbs), [&](const char *v) { return cmd == v; }) != std::end(kWindowVerbs)) {
             auto it = raw.find("window");
             if (it != raw.end()) {
@@ -388,11 +389,12 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             if (op.pick && op.bands.size() > 36) bail("bands -pick prints one digit a window: at most 36 bands");
             ensure_empty(m);
             op.prefix = next("'bands' requires a prefix argument");
-        } else if (cmd == "bursts") {
+        } else if (cmd == "bursts" || cmd == "emissions") {
             // not in the reference's grammar: a threshold per fftshifted bin applied to the windows sparkfft would print, and the list of
-            // on/off runs per bin (qd_plan_bursts): what happened when
+            // on/off runs per bin (qd_plan_bursts), or of the connected regions of on cells (qd_plan_emissions): what happened when
+            const bool em = cmd == "emissions";
             auto m = no_duplicates(raw);
-            op.kind = OP_BURSTS;
+            op.kind = em ? OP_EMISSIONS : OP_BURSTS;
             std::string v = take(m, "width", &f);
             op.width = f ? (size_t)parse_si_u64(v) : 128;
             v = take(m, "stride", &f);
@@ -400,27 +402,35 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             auto number = [&](const std::string &t, const char *flag) {
                 char *e = nullptr;
                 const float x = strtof(t.c_str(), &e);
-                if (t.empty() || *e) bail(std::string("bursts ") + flag + " takes a number: '" + t + "'");
+                if (t.empty() || *e) bail(cmd + " " + flag + " takes a number: '" + t + "'");
                 return x;
             };
             v = take(m, "level", &f);
             op.has_level = f;
             if (f) op.level = number(v, "-level");
             v = take(m, "levels", &f);
-            if (f && op.has_level) bail("bursts takes -level or -levels, not both");
-            if (!f && !op.has_level) bail("bursts requires -level or -levels");
+            if (f && op.has_level) bail(cmd + " takes -level or -levels, not both");
+            if (!f && !op.has_level) bail(cmd + " requires -level or -levels");
             if (f) op.levels_file = v;
             v = take(m, "times", &f);
             op.has_times = f;
             if (f) op.times = number(v, "-times");
             v = take(m, "min", &f);
-            if (f) { op.min_len = parse_si_u64(v); if (!op.min_len) bail("bursts -min takes a number of windows > 0"); }
+            if (f) { op.min_len = parse_si_u64(v); if (!op.min_len) bail(cmd + " -min takes a number of windows > 0"); }
             v = take(m, "cap", &f);
-            if (f) { op.cap = parse_si_u64(v); if (op.cap > QD_BURSTS_MAX_WORKSPACE / sizeof(qd_burst)) bail("bursts -cap takes at most 33554432 records"); }
+            if (f) {
+                op.cap = parse_si_u64(v);
+                if (!em && op.cap > QD_BURSTS_MAX_WORKSPACE / sizeof(qd_burst)) bail("bursts -cap takes at most 33554432 records");
+                if (em && op.cap > QD_EMISSIONS_MAX_WORKSPACE / sizeof(qd_emission)) bail("emissions -cap takes at most 19173961 records");
+            }
+            if (em) {
+                v = take(m, "cells", &f);
+                if (f) { op.min_cells = parse_si_u64(v); if (!op.min_cells) bail("emissions -cells takes a number of cells > 0"); }
+            }
             v = take(m, "print", &f);
             if (f) op.print_n = parse_si_u64(v);
             ensure_empty(m);
-            op.prefix = next("'bursts' requires a prefix argument");
+            op.prefix = next(em ? "'emissions' requires a prefix argument" : "'bursts' requires a prefix argument");
         } else if (cmd == "picture") {
             // not in the reference's grammar: the waterfall its conrod front end renders (src/ui/mod.rs:294-412) as a binary PPM.  -width 8,
             // -stride 1 and -stretch 4 are its Params (:72-76) and 2.29 its scale (:353); -scan 0, no marker columns, is not: its default of 1
@@ -1397,6 +1407,24 @@ void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
     }
 }
 
+// the thresholds of the bursts and emissions sinks: -level X for every bin, or -levels FILE (W raw little-endian f32); -times K multiplies
+// each by K in one f32 multiply
+std::vector<float> sink_thresholds(const Op &sink, const char *verb) {
+    const size_t W = sink.width;
+    std::vector<float> thr(W, sink.level);
+    if (!sink.has_level) {
+        FILE *fp = fopen(sink.levels_file.c_str(), "rb");
+        if (!fp) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + sink.levels_file);
+        uint8_t extra;
+        const bool ok = fread(thr.data(), 4, W, fp) == W && fread(&extra, 1, 1, fp) == 0;
+        fclose(fp);
+        if (!ok) bail(std::string(verb) + " -levels takes a file of exactly " + std::to_string(W) + " f32 values (" + std::to_string(W * 4) + " bytes): " + sink.levels_file);
+    }
+    if (sink.has_times)
+        for (float &t : thr) t = t * sink.times;
+    return thr;
+}
+
 // The `bursts` sink: a threshold per fftshifted bin (-level X for every bin, or -levels FILE: W raw little-endian f32, one row of what
 // means, quantiles or peaks write; -times K multiplies each by K in one f32 multiply) applied to the windows sparkfft would print (a
 // cascade's complete windows), and the list of the runs of cells at or above it, at least -min windows long, in the order they end:
@@ -1408,17 +1436,7 @@ void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) {
     const size_t W = sink.width; const uint64_t S = sink.stride;
     check_norms_sink(sink);
     if (g_gpus > 1) bail("bursts lists one range of windows on one device: a run crosses the seam between two devices' ranges (run it without -gpus)");
-    std::vector<float> thr(W, sink.level);
-    if (!sink.has_level) {
-        FILE *fp = fopen(sink.levels_file.c_str(), "rb");
-        if (!fp) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + sink.levels_file);
-        uint8_t extra;
-        const bool ok = fread(thr.data(), 4, W, fp) == W && fread(&extra, 1, 1, fp) == 0;
-        fclose(fp);
-        if (!ok) bail("bursts -levels takes a file of exactly " + std::to_string(W) + " f32 values (" + std::to_string(W * 4) + " bytes): " + sink.levels_file);
-    }
-    if (sink.has_times)
-        for (float &t : thr) t = t * sink.times;
+    std::vector<float> thr = sink_thresholds(sink, "bursts");
     std::vector<qd_burst> list(sink.cap);
     std::vector<uint64_t> on(W, 0);
     uint64_t found = 0, windows = 0;
@@ -1471,6 +1489,74 @@ void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) {
     for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i)
         printf("%llu %llu %u %llu %.9g\n", (unsigned long long)list[i].first, (unsigned long long)list[i].length, list[i].bin, (unsigned long long)list[i].peak_at,
                (double)list[i].peak);
+}
+
+// The `emissions` sink: the thresholds of `bursts`, and the list of the 4-connected regions of cells at or above them, at least -min
+// windows long and -cells cells large, in the order they end: PREFIX.sr{rate}.w{W}.emissions holds the first -cap records raw
+// (qd_emission, 56 bytes each).  One header line on stdout, then with -print N the first N records as `first last lo hi cells peak_at
+// peak_bin peak flags`, each followed by a line for the reader: start and end in seconds and the low and high edge in Hz relative to the
+// chain's centre, (lo - W/2) rate / W and (hi + 1 - W/2) rate / W at the sink's (decimated) rate: what a later `shift` and `lowpass`
+// take.  A chain the library fuses lists on the device (qd_plan_emissions on a norms plan); every other chain pulls its windows through
+// the iterator chain into qd_emissions_fold and qd_emissions_finish: the same bytes either way.  An emission crosses the seam between
+// two devices' ranges, so -gpus N is refused.
+void do_emissions(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    if (g_gpus > 1) bail("emissions lists one range of windows on one device: an emission crosses the seam between two devices' ranges (run it without -gpus)");
+    const std::vector<float> thr = sink_thresholds(sink, "emissions");
+    std::vector<qd_emission> list(sink.cap);
+    uint64_t found = 0, windows = 0;
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+        done = norms_fused(*cs, sink, "emissions", [&](qd_plan *plan, ChainSource &in, int, int, uint64_t complete, uint64_t) {
+            windows = complete;
+            int mem = QD_MEM_HOST;
+            const void *src = in.resident(&mem);
+            return qd_plan_emissions(plan, src, mem, 0, in.n_samples, 0, complete, thr.data(), sink.min_len, sink.min_cells, sink.cap ? list.data() : nullptr,
+                                     sink.cap, &found, QD_MEM_HOST, nullptr);
+        });
+    }
+    if (!done) {
+        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+        uint64_t nwin = spark_windows(s, W, S);
+        std::vector<qd_c32> buf(W);
+        while (nwin) {
+            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
+        }
+        windows = nwin;
+        std::vector<uint64_t> state((size_t)QD_EMISSIONS_WORDS * W + 2);
+        qd_check(qd_emissions_init(state.data(), (uint32_t)W), "init");
+        std::vector<float> norms;
+        qd_emission *lp = sink.cap ? list.data() : nullptr;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
+            qd_check(qd_emissions_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, sink.min_cells, w0, norms.data(), nb, lp, sink.cap, &found), "fold");
+        }
+        if (nwin == 0) qd_check(qd_emissions_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, sink.min_cells, 0, nullptr, 0, lp, sink.cap, &found), "fold");
+        qd_check(qd_emissions_finish(state.data(), (uint32_t)W, sink.min_len, sink.min_cells, lp, sink.cap, &found), "finish");
+    }
+    const uint64_t written = std::min(found, sink.cap);
+    const std::string fn = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + ".emissions";
+    int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+    if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
+    const uint8_t *at = reinterpret_cast<const uint8_t *>(list.data());
+    for (size_t left = (size_t)written * sizeof(qd_emission); left;) {
+        const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
+        if (w <= 0) { close(fd); bail("write failed"); }
+        at += w; left -= (size_t)w;
+    }
+    close(fd);
+    printf("emissions width=%zu stride=%llu min=%llu cells=%llu windows=%llu found=%llu written=%llu\n", W, (unsigned long long)S, (unsigned long long)sink.min_len,
+           (unsigned long long)sink.min_cells, (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
+    const double rate = (double)s.sample_rate();
+    for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i) {
+        const qd_emission &e = list[i];
+        printf("%llu %llu %u %u %llu %llu %u %.9g %u\n", (unsigned long long)e.first, (unsigned long long)e.last, e.lo, e.hi, (unsigned long long)e.cells,
+               (unsigned long long)e.peak_at, e.peak_bin, (double)e.peak, e.flags);
+        // a window starts every S samples and holds W of them
+        printf("  %.9g s ... %.9g s, %.9g Hz ... %.9g Hz\n", (double)(e.first * S) / rate, (double)(e.last * S + W) / rate,
+               ((double)e.lo - (double)W / 2) * rate / (double)W, ((double)e.hi + 1 - (double)W / 2) * rate / (double)W);
+    }
 }
 
 // The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
@@ -1567,11 +1653,12 @@ void usage() {
             "quantiles [-width 128] [-stride =width] (-pool WINDOWS | -count 2048) -q 0.5[,0.9,...] -range MIN:MAX FILENAME_PREFIX \\\n"
             "   bands [-width 128] [-stride =width] (-bins LO:HI[,LO:HI...] | -split K) [-pick] FILENAME_PREFIX \\\n"
             "  bursts [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
+            "emissions [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cells 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
             " picture [-width 8] [-stride 1] -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29] [-overwrite no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
             "     gen [-cos FREQUENCY]* [-len 1 (second)] SAMPLE_RATE \\\n"
-            "\nsparkfft, bucket, marks, levels, peaks, means, powers, spreads, quantiles, bands, bursts and picture also take [-window bh|rect] (default rect):\n"
+            "\nsparkfft, bucket, marks, levels, peaks, means, powers, spreads, quantiles, emissions, bands, bursts and picture also take [-window bh|rect] (default rect):\n"
             "a Blackman-Harris window on every window's samples in front of the transform\n"
             "\n\nFormat for FREQUENCY, SAMPLE_RATE, and other suffixes: 123, 123k, 123M, 123G\n");
 }
@@ -1633,6 +1720,12 @@ int main(int argc, char **argv) {
                     if (op.has_level) printf("bursts width=%zu stride=%llu level=%.9g", op.width, (unsigned long long)op.stride, op.level);
                     else printf("bursts width=%zu stride=%llu levels=%s", op.width, (unsigned long long)op.stride, op.levels_file.c_str());
                     printf(" times=%.9g min=%llu cap=%llu print=%llu\n", op.times, (unsigned long long)op.min_len, (unsigned long long)op.cap, (unsigned long long)op.print_n);
+                    break;
+                case OP_EMISSIONS:
+                    if (op.has_level) printf("emissions width=%zu stride=%llu level=%.9g", op.width, (unsigned long long)op.stride, op.level);
+                    else printf("emissions width=%zu stride=%llu levels=%s", op.width, (unsigned long long)op.stride, op.levels_file.c_str());
+                    printf(" times=%.9g min=%llu cells=%llu cap=%llu print=%llu\n", op.times, (unsigned long long)op.min_len, (unsigned long long)op.min_cells,
+                           (unsigned long long)op.cap, (unsigned long long)op.print_n);
                     break;
                 case OP_PICTURE:
                     printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g overwrite=%d\n", op.width, (unsigned long long)op.stride, op.px_w, op.px_h,
@@ -1715,6 +1808,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("bursts requires an input");
                 cs.cascade = !chain_clean;
                 do_bursts(*samples, op, &cs);
+                break;
+            case OP_EMISSIONS:
+                if (!samples) bail("emissions requires an input");
+                cs.cascade = !chain_clean;
+                do_emissions(*samples, op, &cs);
                 break;
             case OP_PICTURE:
                 if (!samples) bail("picture requires an input");

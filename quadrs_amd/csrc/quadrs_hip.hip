@@ -40,6 +40,7 @@
 #include "qd_spread.h"
 #include "qd_bands.h"
 #include "qd_bursts.h"
+#include "qd_emissions.h"
 #include "qd_paint.h"
 
 using namespace qd;
@@ -4548,6 +4549,157 @@ int qd_plan_bursts(qd_plan *p, const void *src, int src_mem, uint64_t src_first,
     if (rc) return rc;
     const uint64_t written = std::min(total, cap);
     if (written && !out_dev) HIPCHK(hipMemcpy(list, B.list, (size_t)(written * sizeof(Burst)), hipMemcpyDeviceToHost));
+    *found = total;
+    return f.short_read();
+}
+
+// ------------------------------------------------------------------ emission list
+
+namespace {
+static_assert(sizeof(Emission) == sizeof(qd_emission) && sizeof(qd_emission) == 56 && kEmissionsWords == QD_EMISSIONS_WORDS &&
+              kEmissionsMaxWorkspace == QD_EMISSIONS_MAX_WORKSPACE && kEmissionsMaxWidth == QD_EMISSIONS_MAX_WIDTH &&
+              kEmissionsCutFirst == QD_EMISSION_CUT_FIRST && kEmissionsCutLast == QD_EMISSION_CUT_LAST,
+              "qd_emissions.h and the public header agree on a record");
+static_assert(kEmissionsLdsWords * 4 <= 64 * 1024, "k_emissions_tile's LDS");
+
+// the checks the twin and qd_plan_emissions share, on top of the burst list's
+int emissions_given(uint32_t W, const float *thresholds, uint64_t min_len, uint64_t min_cells, const qd_emission *list, uint64_t cap, const uint64_t *found,
+                    uint32_t *words) {
+    if (const int rc = bursts_given(W, thresholds, min_len ? min_len : 1, nullptr, 0, found, words)) return rc;
+    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: an emission holds at least one window");
+    if (min_cells == 0) return fail(QD_ERR_INVALID, "min_cells is 0: an emission holds at least one cell");
+    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    return QD_OK;
+}
+}  // namespace
+
+int qd_emissions_init(uint64_t *state, uint32_t width) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    emissions_twin_init(state, width);
+    return QD_OK;
+}
+
+int qd_emissions_fold(uint64_t *state, uint32_t width, const float *thresholds, uint64_t min_len, uint64_t min_cells, uint64_t at, const float *norms,
+                      uint64_t n, qd_emission *list, uint64_t cap, uint64_t *found) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    std::vector<uint32_t> thr(width);
+    if (const int rc = emissions_given(width, thresholds, min_len, min_cells, list, cap, found, thr.data())) return rc;
+    uint64_t &next = state[(size_t)width * kEmissionsWords];
+    if (at != next) return fail(QD_ERR_INVALID, "the fold starts at window %llu, the state expects %llu", (unsigned long long)at, (unsigned long long)next);
+    if (n == 0) return QD_OK;
+    if (!norms) return fail(QD_ERR_INVALID, "norms is NULL");
+    const EmissionsSink sink{reinterpret_cast<Emission *>(list), cap, found, min_len, min_cells};
+    for (uint64_t i = 0; i < n; ++i) emissions_twin_row(state, width, thr.data(), at + i, reinterpret_cast<const uint32_t *>(norms + i * width), sink);
+    next = at + n;
+    return QD_OK;
+}
+
+int qd_emissions_finish(uint64_t *state, uint32_t width, uint64_t min_len, uint64_t min_cells, qd_emission *list, uint64_t cap, uint64_t *found) {
+    if (!state) return fail(QD_ERR_INVALID, "state is NULL");
+    if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
+    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
+    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: an emission holds at least one window");
+    if (min_cells == 0) return fail(QD_ERR_INVALID, "min_cells is 0: an emission holds at least one cell");
+    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    emissions_twin_finish(state, width, EmissionsSink{reinterpret_cast<Emission *>(list), cap, found, min_len, min_cells});
+    return QD_OK;
+}
+
+int qd_plan_emissions(qd_plan *p, const void *src, int src_mem, uint64_t src_first, uint64_t src_count, uint64_t first_window, uint64_t n_windows,
+                      const float *thresholds, uint64_t min_len, uint64_t min_cells, qd_emission *list, uint64_t cap, uint64_t *found, int out_mem,
+                      void *stream) {
+    if (!p) return fail(QD_ERR_INVALID, "NULL argument");
+    Fold f{p, "qd_plan_emissions", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    if (const int rc = f.norms_plan()) return rc;
+    const uint32_t W = p->W;
+    std::vector<uint32_t> thr(W);
+    if (const int rc = emissions_given(W, thresholds, min_len, min_cells, list, cap, found, thr.data())) return rc;
+    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
+    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+    if (const int rc = f.unsharded("a sharded plan's emissions are not listed in one call: run one range on one device on a plan of its own; an emission crosses "
+                                   "the seam, and joining the lists there is the caller's job")) return rc;
+    if (W > kEmissionsMaxWidth) return fail(QD_ERR_UNSUPPORTED, "windows of %u bins are too wide for the emission tiles (at most %u)", W, kEmissionsMaxWidth);
+    if (const int rc = f.admit()) return rc;
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    if (!out_dev && cap > kEmissionsMaxWorkspace / sizeof(Emission))
+        return fail(QD_ERR_UNSUPPORTED, "a list of %llu records needs a workspace of %llu bytes, above the %llu allowed: list into device memory, or lower cap",
+                    (unsigned long long)cap, (unsigned long long)cap * 56ull, (unsigned long long)kEmissionsMaxWorkspace);
+    if (const int rc = f.open()) return rc;
+    const hipStream_t st = f.st;
+    // slot 1: [found][threshold words: W u32], written from one host image
+    std::vector<uint64_t> image(1 + (W + 1) / 2, 0);
+    memcpy(image.data() + 1, thr.data(), (size_t)W * 4);
+    void *v = nullptr;
+    int rc = f.ws->get(1, image.size() * 8, &v); if (rc) return rc;
+    unsigned long long *head = static_cast<unsigned long long *>(v);
+    HIPCHK(hipMemcpyAsync(head, image.data(), image.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                // the image is this call's array
+    EmissionsParams E{};
+    E.found = head; E.thr = reinterpret_cast<const uint32_t *>(head + 1);
+    E.min_len = min_len; E.min_cells = min_cells; E.cap = cap;
+    if (cap && !out_dev) { rc = f.ws->get(5, (size_t)(cap * sizeof(Emission)), &v); if (rc) return rc; E.list = static_cast<Emission *>(v); }
+    else E.list = reinterpret_cast<Emission *>(list);
+    if (f.n_windows) {
+        // the span's workspace: sized by the longest batch either walk cuts, and by the span rule whatever chunk_bytes is
+        const uint64_t nw_max = std::max(chunk_windows(p, first_window, f.n_windows, (uint64_t)W * 4),
+                                         chunk_windows(p, first_window, f.n_windows, std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), (uint64_t)W * 4)));
+        const uint64_t span_max = emissions_span_max(W, nw_max), ns = emissions_slots(W, span_max), pieces = emissions_pieces_bound(W, span_max);
+        rc = f.ws->get(2, (size_t)emissions_plane_bytes(W, span_max), &v); if (rc) return rc; E.plane = static_cast<uint32_t *>(v);
+        rc = f.ws->get(3, (size_t)(ns * kEmissionsRecWords * 8), &v); if (rc) return rc; E.rec = static_cast<unsigned long long *>(v);
+        rc = f.ws->get(4, (size_t)(pieces * 16), &v); if (rc) return rc;
+        E.totals = static_cast<unsigned long long *>(v); E.bases = E.totals + pieces;
+        // nothing is open before the first window: an off virtual row without records
+        HIPCHK(hipMemsetAsync(E.plane, 0xff, (size_t)W * 4, st));
+        HIPCHK(hipMemsetAsync(E.rec + (uint64_t)kEmOwn * ns, 0xff, (size_t)emissions_half(W) * 8, st));
+        // an emission crosses batches, so a batch's walk starts behind the previous batch's: the host ring's two streams meet through an event
+        struct Seam {                                                // destroyed on every way out of the call
+            hipEvent_t e[2] = {nullptr, nullptr};
+            ~Seam() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+        } seam;
+        const bool ring = src_mem != QD_MEM_DEVICE;
+        if (ring) for (hipEvent_t &e : seam.e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (ring) HIPCHK(hipStreamSynchronize(st));                  // the virtual row is laid before a ring stream reads it
+        uint64_t k = 0;
+        EmissionsGeometry last{};
+        rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
+            if (nw == 0) return (int)QD_OK;
+            if (ring && k) HIPCHK(hipStreamWaitEvent(s, seam.e[(k - 1) & 1], 0));
+            for (uint64_t a = 0; a < nw; a += span_max) {
+                EmissionsParams Q = E;
+                const uint64_t S = std::min<uint64_t>(nw - a, span_max);
+                emissions_split(g0 + a, S, W, span_max, &Q.G);
+                Q.norms = norms_d + a * W;
+                const uint64_t slots = (S + 1) * Q.G.H;
+                const dim3 t(kEmissionsThreads), g_slots((uint32_t)((slots + kEmissionsThreads - 1) / kEmissionsThreads));
+                hipLaunchKernelGGL(k_emissions_tile, dim3(Q.G.n_trows * Q.G.n_tcols), t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_link, dim3((uint32_t)((emissions_link_lanes(Q.G) + kEmissionsThreads - 1) / kEmissionsThreads)), t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_fold, g_slots, t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_peak, g_slots, t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_emit<kEmissionsCount>, dim3(Q.G.n_pieces), t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_scan, dim3(1), t, 0, s, Q);
+                if (cap) hipLaunchKernelGGL(k_emissions_emit<kEmissionsEmit>, dim3(Q.G.n_pieces), t, 0, s, Q);
+                hipLaunchKernelGGL(k_emissions_carry, dim3((W + kEmissionsThreads - 1) / kEmissionsThreads), t, 0, s, Q);
+                last = Q.G;
+            }
+            HIPCHK(hipGetLastError());
+            if (ring) HIPCHK(hipEventRecord(seam.e[k & 1], s));
+            ++k;
+            return (int)QD_OK;
+        });
+        if (rc == QD_OK) {
+            EmissionsParams Q = E;
+            Q.G = last;
+            hipLaunchKernelGGL(k_emissions_close, dim3(1), dim3(kEmissionsThreads), 0, st, Q);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    uint64_t total = 0;
+    if (rc == QD_OK) HIPCHK(hipMemcpyAsync(&total, E.found, 8, hipMemcpyDeviceToHost, st));
+    rc = f.sync(rc);
+    if (rc) return rc;
+    const uint64_t written = std::min(total, cap);
+    if (written && !out_dev) HIPCHK(hipMemcpy(list, E.list, (size_t)(written * sizeof(Emission)), hipMemcpyDeviceToHost));
     *found = total;
     return f.short_read();
 }

@@ -567,6 +567,54 @@ def bursts_of(norms, thresholds, min_len=1, cap=None):
     return into[:min(found, into.size)], found, on_counts
 
 
+EMISSION_DTYPE = np.dtype([("first", "<u8"), ("last", "<u8"), ("cells", "<u8"), ("peak_at", "<u8"), ("lo", "<u4"), ("hi", "<u4"), ("end_bin", "<u4"),
+                           ("peak_bin", "<u4"), ("peak", "<f4"), ("flags", "<u4")])      # qd_emission, 56 bytes
+EMISSIONS_DEFAULT_CAP = 1 << 20
+
+
+def _emission_cap(cap, n, width):
+    """cap as given, else what cannot overflow (no two neighbouring cells belong to two emissions), at most EMISSIONS_DEFAULT_CAP"""
+    return min(-(-int(n) * int(width) // 2), EMISSIONS_DEFAULT_CAP) if cap is None else int(cap)
+
+
+def emissions_init(width):
+    """qd_emissions_init: state uint64[8 width + 2] with nothing open."""
+    state = np.empty(_ffi.EMISSIONS_WORDS * int(width) + 2, dtype=np.uint64)
+    check(lib().qd_emissions_init(_np_ptr(state), int(width)))
+    return state
+
+
+def emissions_fold(state, norms, thresholds, min_len=1, min_cells=1, at=0, into=None, found=0):
+    """qd_emissions_fold: norms rows (n, width) are windows at, at+1, ... of a range.  The emissions that end above them go to the
+    EMISSION_DTYPE array `into` (its length is cap; None: count only) from record `found` on.  Returns the new found."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    t = _burst_thresholds(thresholds, width)
+    f = C.c_uint64(int(found))
+    check(lib().qd_emissions_fold(_np_ptr(state), width, _np_ptr(t), int(min_len), int(min_cells), int(at), _np_ptr(a) if n else None, n,
+                                  *_burst_list(into), C.byref(f)))
+    return f.value
+
+
+def emissions_finish(state, min_len=1, min_cells=1, into=None, found=0):
+    """qd_emissions_finish: closes what is open at the last window folded; the state is left as emissions_init leaves it.  Returns found."""
+    f = C.c_uint64(int(found))
+    width = (state.size - 2) // _ffi.EMISSIONS_WORDS
+    check(lib().qd_emissions_finish(_np_ptr(state), width, int(min_len), int(min_cells), *_burst_list(into), C.byref(f)))
+    return f.value
+
+
+def emissions_of(norms, thresholds, min_len=1, min_cells=1, cap=None):
+    """The CPU twin of Plan.emissions on norms rows (n, width): (list EMISSION_DTYPE[min(found, cap)], found)."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    state = emissions_init(width)
+    into = np.zeros(_emission_cap(cap, n, width), dtype=EMISSION_DTYPE)
+    found = emissions_fold(state, a, thresholds, min_len, min_cells, 0, into, 0)
+    found = emissions_finish(state, min_len, min_cells, into, found)
+    return into[:min(found, into.size)], found
+
+
 def picture_desc(px_width, px_height, stretch=4, scan=0, scale=2.29):
     """a qd_picture_desc: the page of a waterfall picture.  stretch 4 and scale 2.29 are the reference's; scan 0 (no marker columns) is
     not: its default of 1 blackens every column."""
@@ -957,6 +1005,47 @@ class Plan:
         try:
             check(lib().qd_plan_bursts(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), int(min_len), lptr, cap,
                                        C.byref(found), cptr, out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = result()
+            raise
+        return result()
+
+    def emissions(self, src, thresholds, min_len=1, min_cells=1, cap=None, first_window=0, n_windows=None, src_first=0, pinned=False,
+                  device_out=None, out=None):
+        """qd_plan_emissions of an EPI_NORMS_F32 plan: (list, found) — the 4-connected regions of cells at or above the bin's threshold
+        (as for bursts) in windows [first_window, +n_windows), at least min_len windows long and min_cells cells large, in the order they
+        end; found counts all of them, the list holds the first min(found, cap) (cap None: what cannot overflow, at most
+        EMISSIONS_DEFAULT_CAP).  src and device_out as for bursts: the list is an EMISSION_DTYPE numpy array, or a torch uint8 CUDA tensor
+        [records, 56].  out: an EMISSION_DTYPE array or uint8 tensor to write into instead; cap then defaults to the records `out` holds
+        and may not exceed them.  A failing call's error carries (list, found) as e.partial."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        W = self.width
+        t = _burst_thresholds(thresholds, W)
+        dev = (_is_torch(src) if device_out is None else device_out) if out is None else _is_torch(out)
+        size = EMISSION_DTYPE.itemsize
+        if out is None:
+            cap = _emission_cap(cap, n_windows, W)
+        else:                                    # the list given holds what it holds: cap defaults to it and may not exceed it
+            room = (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) // size
+            cap = room if cap is None else int(cap)
+            if cap > room:
+                raise ValueError("cap %d above the %d records that out holds" % (cap, room))
+        if dev:
+            import torch
+            lst = torch.empty((cap, size), dtype=torch.uint8, device="cuda") if out is None else out
+            lptr, out_mem = C.c_void_p(lst.data_ptr()) if cap else None, MEM_DEVICE
+        else:
+            lst = np.zeros(cap, dtype=EMISSION_DTYPE) if out is None else out
+            lptr, out_mem = _np_ptr(lst) if cap else None, (_ffi.MEM_HOST_PINNED if pinned and out is not None else MEM_HOST)
+        found = C.c_uint64(0)
+
+        def result():
+            k = min(found.value, cap)
+            return (lst.reshape(-1, size)[:k] if dev else lst[:k]), found.value
+        try:
+            check(lib().qd_plan_emissions(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), int(min_len), int(min_cells),
+                                          lptr, cap, C.byref(found), out_mem, st))
         except _ffi.QuadrsError as e:
             e.partial = result()
             raise

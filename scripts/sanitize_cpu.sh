@@ -7,6 +7,8 @@
 #      host-only instrumentation (-fsanitize=address,undefined -fno-gpu-sanitize), tests/test_abi_cpu.py under it;
 #   4. the deviation cell's arithmetic (quadrs_amd/csrc/qd_spread.h, and qd_mean.h / qd_power.h under it) in a stand-alone program,
 #      scripts/spread_host_check.cpp, built with g++ -fsanitize=address,undefined: planted and random cells against its own big-integer referee.
+#   5. the emission list's CPU twin (quadrs_amd/csrc/qd_emissions.h, what qd_emissions_fold / _finish run) in a stand-alone program,
+#      scripts/emissions_host_check.cpp, built the same way: random matrices, lists with and without room, against its own flood fill.
 # Runs in the GPU-less container; prints one summary line per leg.  usage: scripts/sanitize_cpu.sh [outdir]
 set -u
 cd "$(dirname "$0")/.."
@@ -59,5 +61,11 @@ g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-re
 timeout 600 "$out/spread_host_check" 4000 > "$out/spread.log" 2>&1
 rc=$?; tail -1 "$out/spread.log"; [ $rc -ne 0 ] && status=1
 grep -c "ERROR: AddressSanitizer\|runtime error:" "$out/spread.log" | sed 's/^/   sanitizer reports: /'
+echo "== 5. qd_emissions.h's twin in a stand-alone program under ASan + UBSan"
+g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wextra -o "$out/emissions_host_check" \
+    scripts/emissions_host_check.cpp || status=1
+timeout 600 "$out/emissions_host_check" 400 > "$out/emissions.log" 2>&1
+rc=$?; tail -1 "$out/emissions.log"; [ $rc -ne 0 ] && status=1
+grep -c "ERROR: AddressSanitizer\|runtime error:" "$out/emissions.log" | sed 's/^/   sanitizer reports: /'
 echo "sanitize_cpu: $([ $status = 0 ] && echo clean || echo FAILED)"
 exit $status
