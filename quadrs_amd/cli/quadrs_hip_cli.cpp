@@ -1097,6 +1097,28 @@ uint64_t iter_norms(const Samples &s, const Op &sink, uint64_t w0, uint64_t nb, 
     qd_check(rc, "run");
     return nb;
 }
+// the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
+uint64_t readable_windows(const Samples &s, size_t W, uint64_t S, std::vector<qd_c32> *buf) {
+    uint64_t nwin = spark_windows(s, W, S);
+    buf->resize(W);
+    while (nwin) {
+        try { s.read_exact_at((nwin - 1) * S, buf->data(), W); break; } catch (const Fail &) { --nwin; }
+    }
+    return nwin;
+}
+// a file that must not exist yet: `head`, then `bytes` of data in pieces of 1 GiB
+void write_new_file(const std::string &path, const void *data, size_t bytes, const std::string &head = "") {
+    int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
+    if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + path);
+    if (!head.empty() && write(fd, head.data(), head.size()) < 0) { close(fd); bail("write failed"); }
+    const uint8_t *at = static_cast<const uint8_t *>(data);
+    for (size_t left = bytes; left;) {
+        const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
+        if (w <= 0) { close(fd); bail("write failed"); }
+        at += w; left -= (size_t)w;
+    }
+    close(fd);
+}
 
 void do_levels(const Samples &s, const Op &sink, const ChainSpec *cs) {
     const size_t W = sink.width;
@@ -1192,12 +1214,8 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     bool done = false;
     if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) done = peaks_fused(*cs, sink, &pr);
     if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t nwin = spark_windows(s, W, S);
-        std::vector<qd_c32> buf(W);
-        while (nwin) {
-            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-        }
+        std::vector<qd_c32> buf;
+        const uint64_t nwin = readable_windows(s, W, S, &buf);
         pr.size_for(sink, nwin);
         if (pr.mean && pr.rows) {
             pr.acc.resize(pr.rows * W * QD_MEAN_WORDS);
@@ -1231,14 +1249,11 @@ void do_peaks(const Samples &s, const Op &sink, const ChainSpec *cs) {
     for (int which = 0; which < (sink.want_floor ? 2 : 1); ++which) {
         const std::vector<float> &rows = which ? pr.floor : pr.peak;
         const std::string fn = stem + (pr.mean ? ".mean.pgm" : pr.power ? ".rms.pgm" : pr.spread ? ".std.pgm" : which ? ".floor.pgm" : ".peak.pgm");
-        int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
-        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
         for (size_t i = 0; i < rows.size(); ++i) {
             const float v = (sink.has_range ? rows[i] - lo : rows[i]) / span * 256.f;      // `as u8`: saturating, NaN -> 0
             px[i] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
         }
-        if (write(fd, head.data(), head.size()) < 0 || (px.size() && write(fd, px.data(), px.size()) < 0)) { close(fd); bail("write failed"); }
-        close(fd);
+        write_new_file(fn, px.data(), px.size(), head);
     }
 }
 
@@ -1297,12 +1312,8 @@ void do_quantiles(const Samples &s, const Op &sink, const ChainSpec *cs) {
         });
     }
     if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t nwin = spark_windows(s, W, S);
-        std::vector<qd_c32> buf(W);
-        while (nwin) {
-            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-        }
+        std::vector<qd_c32> buf;
+        const uint64_t nwin = readable_windows(s, W, S, &buf);
         size_for(nwin);
         if (rows) {
             std::vector<uint32_t> counts(rows * W * L);
@@ -1322,15 +1333,12 @@ void do_quantiles(const Samples &s, const Op &sink, const ChainSpec *cs) {
     std::vector<uint8_t> px(rows * W);
     for (size_t i = 0; i < nq; ++i) {
         const std::string fn = stem + ".q" + sink.q_names[i] + ".pgm";
-        int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
-        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
         const float *t = traces.data() + i * rows * W;
         for (size_t k = 0; k < px.size(); ++k) {
             const float v = (t[k] - lo) / span * 256.f;                  // `as u8`: saturating, NaN -> 0
             px[k] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)v);
         }
-        if (write(fd, head.data(), head.size()) < 0 || (px.size() && write(fd, px.data(), px.size()) < 0)) { close(fd); bail("write failed"); }
-        close(fd);
+        write_new_file(fn, px.data(), px.size(), head);
     }
 }
 
@@ -1370,12 +1378,8 @@ void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
         });
     }
     if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t nwin = spark_windows(s, W, S);
-        std::vector<qd_c32> buf(W);
-        while (nwin) {
-            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-        }
+        std::vector<qd_c32> buf;
+        const uint64_t nwin = readable_windows(s, W, S, &buf);
         size_for(nwin);
         std::vector<float> norms;
         for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
@@ -1385,19 +1389,8 @@ void do_bands(const Samples &s, const Op &sink, const ChainSpec *cs) {
         }
     }
     const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + ".k" + std::to_string(K);
-    const std::pair<std::string, std::pair<const void *, size_t>> files[] = {{stem + ".level.f32", {level.data(), level.size() * 4}},
-                                                                             {stem + ".peak_bin.u32", {peak_bin.data(), peak_bin.size() * 4}}};
-    for (const auto &file : files) {
-        int fd = open(file.first.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
-        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + file.first);
-        const uint8_t *at = static_cast<const uint8_t *>(file.second.first);
-        for (size_t left = file.second.second; left;) {
-            const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
-            if (w <= 0) { close(fd); bail("write failed"); }
-            at += w; left -= (size_t)w;
-        }
-        close(fd);
-    }
+    write_new_file(stem + ".level.f32", level.data(), level.size() * 4);
+    write_new_file(stem + ".peak_bin.u32", peak_bin.data(), peak_bin.size() * 4);
     printf("bands width=%zu stride=%llu k=%u windows=%llu\n", W, (unsigned long long)S, K, (unsigned long long)windows);
     if (sink.pick) {
         std::string line(windows, '.');
@@ -1432,64 +1425,30 @@ std::vector<float> sink_thresholds(const Op &sink, const char *verb) {
 // every bin.  One header line on stdout, then with -print N the first N records as `first length bin peak_at peak`.  A chain the library
 // fuses lists on the device (qd_plan_bursts on a norms plan); every other chain pulls its windows through the iterator chain into
 // qd_bursts_fold and qd_bursts_finish — the same bytes either way.  A run crosses the seam between two devices' ranges, so -gpus N is refused.
-void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) {
-    const size_t W = sink.width; const uint64_t S = sink.stride;
-    check_norms_sink(sink);
-    if (g_gpus > 1) bail("bursts lists one range of windows on one device: a run crosses the seam between two devices' ranges (run it without -gpus)");
-    std::vector<float> thr = sink_thresholds(sink, "bursts");
-    std::vector<qd_burst> list(sink.cap);
-    std::vector<uint64_t> on(W, 0);
-    uint64_t found = 0, windows = 0;
-    bool done = false;
-    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
-        done = norms_fused(*cs, sink, "bursts", [&](qd_plan *plan, ChainSource &in, int, int, uint64_t complete, uint64_t) {
-            windows = complete;
-            int mem = QD_MEM_HOST;
-            const void *src = in.resident(&mem);
-            return qd_plan_bursts(plan, src, mem, 0, in.n_samples, 0, complete, thr.data(), sink.min_len, sink.cap ? list.data() : nullptr, sink.cap, &found,
-                                  on.data(), QD_MEM_HOST, nullptr);
-        });
+struct BurstsVerb {
+    using Record = qd_burst;
+    static constexpr const char *name = "bursts", *ext = ".bursts";
+    static constexpr const char *one_device = "bursts lists one range of windows on one device: a run crosses the seam between two devices' ranges (run it without -gpus)";
+    static constexpr size_t words = QD_BURSTS_WORDS, tail = 1;                  // the twin's state: words per bin, and behind them
+    std::vector<uint64_t> on;                                                  // the on cells of every bin
+    explicit BurstsVerb(const Op &sink) : on(sink.width, 0) {}
+    int plan(qd_plan *p, const void *src, int mem, uint64_t n_samples, uint64_t n, const float *thr, const Op &k, Record *list, uint64_t *found) {
+        return qd_plan_bursts(p, src, mem, 0, n_samples, 0, n, thr, k.min_len, list, k.cap, found, on.data(), QD_MEM_HOST, nullptr);
     }
-    if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t nwin = spark_windows(s, W, S);
-        std::vector<qd_c32> buf(W);
-        while (nwin) {
-            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-        }
-        windows = nwin;
-        std::vector<uint64_t> state((size_t)QD_BURSTS_WORDS * W + 1);
-        qd_check(qd_bursts_init(state.data(), on.data(), (uint32_t)W), "init");
-        std::vector<float> norms;
-        qd_burst *lp = sink.cap ? list.data() : nullptr;
-        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
-            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
-            qd_check(qd_bursts_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, w0, norms.data(), nb, lp, sink.cap, &found, on.data()), "fold");
-        }
-        if (nwin == 0) qd_check(qd_bursts_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, 0, nullptr, 0, lp, sink.cap, &found, on.data()), "fold");
-        qd_check(qd_bursts_finish(state.data(), (uint32_t)W, sink.min_len, lp, sink.cap, &found), "finish");
+    int init(uint64_t *state, uint32_t W) { return qd_bursts_init(state, on.data(), W); }
+    int fold(uint64_t *state, uint32_t W, const float *thr, const Op &k, uint64_t at, const float *norms, uint64_t n, Record *list, uint64_t *found) {
+        return qd_bursts_fold(state, W, thr, k.min_len, at, norms, n, list, k.cap, found, on.data());
     }
-    const uint64_t written = std::min(found, sink.cap);
-    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W);
-    const std::pair<std::string, std::pair<const void *, size_t>> files[] = {{stem + ".bursts", {list.data(), (size_t)written * sizeof(qd_burst)}},
-                                                                             {stem + ".on.u64", {on.data(), on.size() * 8}}};
-    for (const auto &file : files) {
-        int fd = open(file.first.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
-        if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + file.first);
-        const uint8_t *at = static_cast<const uint8_t *>(file.second.first);
-        for (size_t left = file.second.second; left;) {
-            const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
-            if (w <= 0) { close(fd); bail("write failed"); }
-            at += w; left -= (size_t)w;
-        }
-        close(fd);
+    int finish(uint64_t *state, uint32_t W, const Op &k, Record *list, uint64_t *found) { return qd_bursts_finish(state, W, k.min_len, list, k.cap, found); }
+    void more_files(const std::string &stem) const { write_new_file(stem + ".on.u64", on.data(), on.size() * 8); }
+    static void header(const Op &k, uint64_t windows, uint64_t found, uint64_t written) {
+        printf("bursts width=%zu stride=%llu min=%llu windows=%llu found=%llu written=%llu\n", (size_t)k.width, (unsigned long long)k.stride,
+               (unsigned long long)k.min_len, (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
     }
-    printf("bursts width=%zu stride=%llu min=%llu windows=%llu found=%llu written=%llu\n", W, (unsigned long long)S, (unsigned long long)sink.min_len,
-           (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
-    for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i)
-        printf("%llu %llu %u %llu %.9g\n", (unsigned long long)list[i].first, (unsigned long long)list[i].length, list[i].bin, (unsigned long long)list[i].peak_at,
-               (double)list[i].peak);
-}
+    static void print(const Record &b, const Samples &, const Op &) {
+        printf("%llu %llu %u %llu %.9g\n", (unsigned long long)b.first, (unsigned long long)b.length, b.bin, (unsigned long long)b.peak_at, (double)b.peak);
+    }
+};
 
 // The `emissions` sink: the thresholds of `bursts`, and the list of the 4-connected regions of cells at or above them, at least -min
 // windows long and -cells cells large, in the order they end: PREFIX.sr{rate}.w{W}.emissions holds the first -cap records raw
@@ -1499,65 +1458,81 @@ void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) {
 // take.  A chain the library fuses lists on the device (qd_plan_emissions on a norms plan); every other chain pulls its windows through
 // the iterator chain into qd_emissions_fold and qd_emissions_finish: the same bytes either way.  An emission crosses the seam between
 // two devices' ranges, so -gpus N is refused.
-void do_emissions(const Samples &s, const Op &sink, const ChainSpec *cs) {
-    const size_t W = sink.width; const uint64_t S = sink.stride;
-    check_norms_sink(sink);
-    if (g_gpus > 1) bail("emissions lists one range of windows on one device: an emission crosses the seam between two devices' ranges (run it without -gpus)");
-    const std::vector<float> thr = sink_thresholds(sink, "emissions");
-    std::vector<qd_emission> list(sink.cap);
-    uint64_t found = 0, windows = 0;
-    bool done = false;
-    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
-        done = norms_fused(*cs, sink, "emissions", [&](qd_plan *plan, ChainSource &in, int, int, uint64_t complete, uint64_t) {
-            windows = complete;
-            int mem = QD_MEM_HOST;
-            const void *src = in.resident(&mem);
-            return qd_plan_emissions(plan, src, mem, 0, in.n_samples, 0, complete, thr.data(), sink.min_len, sink.min_cells, sink.cap ? list.data() : nullptr,
-                                     sink.cap, &found, QD_MEM_HOST, nullptr);
-        });
+struct EmissionsVerb {
+    using Record = qd_emission;
+    static constexpr const char *name = "emissions", *ext = ".emissions";
+    static constexpr const char *one_device = "emissions lists one range of windows on one device: an emission crosses the seam between two devices' ranges (run it without -gpus)";
+    static constexpr size_t words = QD_EMISSIONS_WORDS, tail = 2;
+    explicit EmissionsVerb(const Op &) {}
+    int plan(qd_plan *p, const void *src, int mem, uint64_t n_samples, uint64_t n, const float *thr, const Op &k, Record *list, uint64_t *found) {
+        return qd_plan_emissions(p, src, mem, 0, n_samples, 0, n, thr, k.min_len, k.min_cells, list, k.cap, found, QD_MEM_HOST, nullptr);
     }
-    if (!done) {
-        // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-        uint64_t nwin = spark_windows(s, W, S);
-        std::vector<qd_c32> buf(W);
-        while (nwin) {
-            try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-        }
-        windows = nwin;
-        std::vector<uint64_t> state((size_t)QD_EMISSIONS_WORDS * W + 2);
-        qd_check(qd_emissions_init(state.data(), (uint32_t)W), "init");
-        std::vector<float> norms;
-        qd_emission *lp = sink.cap ? list.data() : nullptr;
-        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
-            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
-            qd_check(qd_emissions_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, sink.min_cells, w0, norms.data(), nb, lp, sink.cap, &found), "fold");
-        }
-        if (nwin == 0) qd_check(qd_emissions_fold(state.data(), (uint32_t)W, thr.data(), sink.min_len, sink.min_cells, 0, nullptr, 0, lp, sink.cap, &found), "fold");
-        qd_check(qd_emissions_finish(state.data(), (uint32_t)W, sink.min_len, sink.min_cells, lp, sink.cap, &found), "finish");
+    int init(uint64_t *state, uint32_t W) { return qd_emissions_init(state, W); }
+    int fold(uint64_t *state, uint32_t W, const float *thr, const Op &k, uint64_t at, const float *norms, uint64_t n, Record *list, uint64_t *found) {
+        return qd_emissions_fold(state, W, thr, k.min_len, k.min_cells, at, norms, n, list, k.cap, found);
     }
-    const uint64_t written = std::min(found, sink.cap);
-    const std::string fn = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W) + ".emissions";
-    int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_EXCL, 0644);
-    if (fd < 0) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + fn);
-    const uint8_t *at = reinterpret_cast<const uint8_t *>(list.data());
-    for (size_t left = (size_t)written * sizeof(qd_emission); left;) {
-        const ssize_t w = write(fd, at, std::min<size_t>(left, 1u << 30));
-        if (w <= 0) { close(fd); bail("write failed"); }
-        at += w; left -= (size_t)w;
+    int finish(uint64_t *state, uint32_t W, const Op &k, Record *list, uint64_t *found) {
+        return qd_emissions_finish(state, W, k.min_len, k.min_cells, list, k.cap, found);
     }
-    close(fd);
-    printf("emissions width=%zu stride=%llu min=%llu cells=%llu windows=%llu found=%llu written=%llu\n", W, (unsigned long long)S, (unsigned long long)sink.min_len,
-           (unsigned long long)sink.min_cells, (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
-    const double rate = (double)s.sample_rate();
-    for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i) {
-        const qd_emission &e = list[i];
+    void more_files(const std::string &) const {}
+    static void header(const Op &k, uint64_t windows, uint64_t found, uint64_t written) {
+        printf("emissions width=%zu stride=%llu min=%llu cells=%llu windows=%llu found=%llu written=%llu\n", (size_t)k.width, (unsigned long long)k.stride,
+               (unsigned long long)k.min_len, (unsigned long long)k.min_cells, (unsigned long long)windows, (unsigned long long)found, (unsigned long long)written);
+    }
+    static void print(const Record &e, const Samples &s, const Op &k) {
+        const double rate = (double)s.sample_rate(), W = (double)k.width;
         printf("%llu %llu %u %u %llu %llu %u %.9g %u\n", (unsigned long long)e.first, (unsigned long long)e.last, e.lo, e.hi, (unsigned long long)e.cells,
                (unsigned long long)e.peak_at, e.peak_bin, (double)e.peak, e.flags);
         // a window starts every S samples and holds W of them
-        printf("  %.9g s ... %.9g s, %.9g Hz ... %.9g Hz\n", (double)(e.first * S) / rate, (double)(e.last * S + W) / rate,
-               ((double)e.lo - (double)W / 2) * rate / (double)W, ((double)e.hi + 1 - (double)W / 2) * rate / (double)W);
+        printf("  %.9g s ... %.9g s, %.9g Hz ... %.9g Hz\n", (double)(e.first * k.stride) / rate, (double)(e.last * k.stride + k.width) / rate,
+               ((double)e.lo - W / 2) * rate / W, ((double)e.hi + 1 - W / 2) * rate / W);
     }
+};
+
+// The body of the list sinks, `bursts` and `emissions`: the fused attempt, else the iterator chain into the twin; the list's file, the
+// verb's other files, the header line and the -print records.
+template <typename Verb>
+void do_list(const Samples &s, const Op &sink, const ChainSpec *cs) {
+    using Record = typename Verb::Record;
+    const size_t W = sink.width; const uint64_t S = sink.stride;
+    check_norms_sink(sink);
+    if (g_gpus > 1) bail(Verb::one_device);
+    const std::vector<float> thr = sink_thresholds(sink, Verb::name);
+    Verb verb(sink);
+    std::vector<Record> list(sink.cap);
+    Record *lp = sink.cap ? list.data() : nullptr;
+    uint64_t found = 0, windows = 0;
+    bool done = false;
+    if (cs && cs->fusable && !getenv("QUADRS_HIP_NO_FUSE")) {
+        done = norms_fused(*cs, sink, Verb::name, [&](qd_plan *plan, ChainSource &in, int, int, uint64_t complete, uint64_t) {
+            windows = complete;
+            int mem = QD_MEM_HOST;
+            const void *src = in.resident(&mem);
+            return verb.plan(plan, src, mem, in.n_samples, complete, thr.data(), sink, lp, &found);
+        });
+    }
+    if (!done) {
+        std::vector<qd_c32> buf;
+        const uint64_t nwin = windows = readable_windows(s, W, S, &buf);
+        std::vector<uint64_t> state(Verb::words * W + Verb::tail);
+        qd_check(verb.init(state.data(), (uint32_t)W), "init");
+        std::vector<float> norms;
+        for (uint64_t w0 = 0; w0 < nwin; w0 += kIterBatch) {
+            const uint64_t nb = iter_norms(s, sink, w0, std::min(nwin - w0, kIterBatch), false, &buf, &norms);
+            qd_check(verb.fold(state.data(), (uint32_t)W, thr.data(), sink, w0, norms.data(), nb, lp, &found), "fold");
+        }
+        if (nwin == 0) qd_check(verb.fold(state.data(), (uint32_t)W, thr.data(), sink, 0, nullptr, 0, lp, &found), "fold");
+        qd_check(verb.finish(state.data(), (uint32_t)W, sink, lp, &found), "finish");
+    }
+    const uint64_t written = std::min(found, sink.cap);
+    const std::string stem = sink.prefix + ".sr" + std::to_string(s.sample_rate()) + ".w" + std::to_string(W);
+    write_new_file(stem + Verb::ext, list.data(), (size_t)written * sizeof(Record));
+    verb.more_files(stem);
+    Verb::header(sink, windows, found, written);
+    for (uint64_t i = 0; i < std::min(written, sink.print_n); ++i) Verb::print(list[i], s, sink);
 }
+void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) { do_list<BurstsVerb>(s, sink, cs); }
+void do_emissions(const Samples &s, const Op &sink, const ChainSpec *cs) { do_list<EmissionsVerb>(s, sink, cs); }
 
 // The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
 // it out (src/ui/mod.rs:294-412; the colour map is the project's own statement of palette 0.5's HSV -> RGB, include/quadrs_hip.h), written
@@ -1609,13 +1584,8 @@ void do_picture(const Samples &s, const Op &sink, const ChainSpec *cs) {
             }
         }
         if (!done) {
-            // the windows of sparkfft's loop (src/fft.rs:28-65) whose read_exact_at succeeds: a chain's over-reported len fails at the tail
-            uint64_t nwin = spark_windows(s, W, S);
-            std::vector<qd_c32> buf(W);
-            while (nwin) {
-                try { s.read_exact_at((nwin - 1) * S, buf.data(), W); break; } catch (const Fail &) { --nwin; }
-            }
-            painted = std::min(nwin, max_windows);
+            std::vector<qd_c32> buf;
+            painted = std::min(readable_windows(s, W, S, &buf), max_windows);
             std::vector<float> norms;
             for (uint64_t w0 = 0; w0 < painted; w0 += kIterBatch) {
                 const uint64_t nb = iter_norms(s, sink, w0, std::min(painted - w0, kIterBatch), false, &buf, &norms);

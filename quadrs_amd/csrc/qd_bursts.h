@@ -12,6 +12,8 @@
 
 #include <stdint.h>
 
+#include "qd_lists.h"
+
 #if defined(__HIPCC__)
 #define QD_BURSTS_HD __host__ __device__
 #else
@@ -22,6 +24,7 @@ namespace qd {
 
 constexpr uint32_t kBurstsThreads = 256;
 constexpr uint32_t kBurstsWaves = kBurstsThreads / 64;
+static_assert(kBurstsThreads == kListThreads, "k_bursts_scan and k_bursts_close are rounds of qd_lists.h");
 constexpr uint32_t kBurstsWords = 3;                     // QD_BURSTS_WORDS: first window of the open run or kBurstsNone, its peak_at, its peak bits
 constexpr uint64_t kBurstsNone = ~0ull;
 constexpr uint32_t kBurstsMasked = 0xffffffffu;          // the threshold word of a masked bin: above every |value|, so never on
@@ -176,19 +179,17 @@ struct BurstsParams {
     const float *norms;                      // the batch's windows, nw x W
     const uint32_t *thr;                     // W threshold words (bursts_threshold)
     BurstsGeometry G;
-    uint64_t min_len, cap;
+    uint64_t min_len;
     unsigned long long *state;               // kBurstsWords planes of W: the open runs after the last batch
     unsigned long long *edge;                // per piece: the run that touches the piece's end, and bit 32 of word 2: every window is on
     unsigned long long *inc;                 // per piece: the open run that comes in
-    unsigned long long *totals, *bases;      // per piece: the bursts that end in it, and the rank of the first of them
-    unsigned long long *found;               // the running count
+    ListCursor<Burst> L;                     // per piece: the bursts that end in it; the running count; the list (qd_lists.h)
     unsigned long long *on_counts;           // W words, or nullptr
-    Burst *list;
     int vec_store;                           // the list is 16-byte aligned
 };
 
 __device__ inline void bursts_store(const BurstsParams &B, uint64_t rank, const BurstsRun &r, uint64_t end, uint32_t bin) {
-    Burst *d = B.list + rank;
+    Burst *d = B.L.list + rank;
     const uint64_t len = end - r.first;
     if (B.vec_store) {
         uint4 *q = reinterpret_cast<uint4 *>(d);
@@ -304,10 +305,7 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_emit(const BurstsPara
     if (MODE == kBurstsEmit) {
         if (tid == 0) s_any = 0;
         __syncthreads();
-        if (work) {
-            base = B.bases[l.piece];
-            work = B.totals[l.piece] != 0 && base < B.cap;
-        }
+        if (work) work = list_piece_stores(B.L, l.piece, &base);
         if (work) s_any = 1;
         __syncthreads();
         if (!s_any) return;                                                 // workgroup-uniform
@@ -348,7 +346,7 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_emit(const BurstsPara
     if (MODE == kBurstsCount) {
         if (cnt) atomicAdd(&s_tot[l.slot], cnt);
         __syncthreads();
-        if (tid < G.ppg && (uint64_t)blockIdx.x * G.ppg + tid < G.n_pieces) B.totals[(uint64_t)blockIdx.x * G.ppg + tid] = s_tot[tid];
+        if (tid < G.ppg && (uint64_t)blockIdx.x * G.ppg + tid < G.n_pieces) B.L.totals[(uint64_t)blockIdx.x * G.ppg + tid] = s_tot[tid];
         return;
     }
     __syncthreads();
@@ -366,7 +364,7 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_emit(const BurstsPara
                     (uint32_t)B.inc[bursts_slot_word(G.W, l.piece, 2, col)]}, e;
         const float *p = B.norms + (l.wa - G.g0) * G.W + col;
         uint64_t rank0 = base;                                              // of the first end of row j
-        for (uint32_t j = 0; l.wa + j < l.wb && rank0 < B.cap; ++j, p += G.W) {
+        for (uint32_t j = 0; l.wa + j < l.wb && rank0 < B.L.cap; ++j, p += G.W) {
             const uint64_t w = l.wa + j;
             const uint32_t a = bursts_mag(__float_as_uint(*p));
             if (bursts_step(r, w, a, bursts_on(a, t), &e) && w - e.first >= B.min_len) {
@@ -375,7 +373,7 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_emit(const BurstsPara
                     for (uint32_t v = 0; v < pwn; ++v) rank += __popcll(s_bal[bursts_word(G, j, s2, pw0 + v)] & pmask);
                 for (uint32_t v = pw0; v < wave; ++v) rank += __popcll(s_bal[bursts_word(G, j, s, v)] & pmask);
                 rank += __popcll(s_bal[bursts_word(G, j, s, wave)] & pmask & below_me);
-                if (rank < B.cap) bursts_store(B, rank, e, w, col);
+                if (rank < B.L.cap) bursts_store(B, rank, e, w, col);
             }
             for (uint32_t s2 = 0; s2 < G.n_slabs; ++s2)
                 for (uint32_t v = 0; v < pwn; ++v) rank0 += __popcll(s_bal[bursts_word(G, j, s2, pw0 + v)] & pmask);
@@ -383,30 +381,15 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_emit(const BurstsPara
     }
 }
 
-// between COUNT and EMIT: one workgroup turns the pieces' totals into their bases, exclusive, from the running count, and adds the
-// batch's bursts to it
-__global__ __launch_bounds__(kBurstsThreads) void k_bursts_scan(const BurstsParams B) {
-    __shared__ unsigned long long s_sum[kBurstsThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n = B.G.n_pieces, per = (n + kBurstsThreads - 1) / kBurstsThreads;
-    const uint64_t a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
-    unsigned long long mine = 0;
-    for (uint64_t q = a; q < b; ++q) mine += B.totals[q];
-    s_sum[tid] = mine;
-    __syncthreads();
-    unsigned long long before = *B.found;
-    for (uint32_t i = 0; i < tid; ++i) before += s_sum[i];
-    for (uint64_t q = a; q < b; ++q) { B.bases[q] = before; before += B.totals[q]; }
-    __syncthreads();
-    if (tid == kBurstsThreads - 1) *B.found = before;
-}
+// between COUNT and EMIT: the pieces' totals into their bases, and the batch's bursts onto the running count (list_scan, qd_lists.h)
+__global__ __launch_bounds__(kBurstsThreads) void k_bursts_scan(const BurstsParams B) { list_scan(B.L, B.G.n_pieces); }
 
 // Phase 4, after the last batch: the runs still open close at the range's last folded window, by bin; `end` is the number of windows
 // folded.  One workgroup walks the bins in slabs of 256; the state is left as before the first batch.
 __global__ __launch_bounds__(kBurstsThreads) void k_bursts_close(const BurstsParams B, uint64_t end) {
     __shared__ unsigned long long s_bal[kBurstsWaves];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, W = B.G.W;
-    uint64_t rank0 = *B.found;
+    const uint32_t tid = threadIdx.x, W = B.G.W;
+    uint64_t rank0 = *B.L.found;
     __syncthreads();                                                        // everybody has read the count before anybody replaces it
     for (uint32_t c0 = 0; c0 < W; c0 += kBurstsThreads) {
         const uint32_t col = c0 + tid;
@@ -416,17 +399,11 @@ __global__ __launch_bounds__(kBurstsThreads) void k_bursts_close(const BurstsPar
             B.state[col] = kBurstsNone; B.state[W + col] = 0; B.state[2ull * W + col] = 0;
         }
         const bool keep = r.first != kBurstsNone && end - r.first >= B.min_len;
-        const unsigned long long bal = __ballot(keep);
-        if ((tid & 63u) == 0) s_bal[wave] = bal;
-        __syncthreads();
-        uint64_t rank = rank0;
-        for (uint32_t v = 0; v < wave; ++v) rank += __popcll(s_bal[v]);
-        rank += __popcll(bal & ((1ull << (tid & 63u)) - 1ull));
-        if (keep && rank < B.cap) bursts_store(B, rank, r, end, col);
-        for (uint32_t v = 0; v < kBurstsWaves; ++v) rank0 += __popcll(s_bal[v]);
-        __syncthreads();
+        const uint64_t rank = list_round_rank(keep, s_bal, rank0);
+        if (keep && rank < B.L.cap) bursts_store(B, rank, r, end, col);
+        __syncthreads();                                                    // the next round replaces the words
     }
-    if (tid == 0) *B.found = rank0;
+    if (tid == 0) *B.L.found = rank0;
 }
 
 }  // namespace qd

@@ -29,6 +29,7 @@ namespace qd {
 
 constexpr uint32_t kEmissionsThreads = 256;
 constexpr uint32_t kEmissionsWaves = kEmissionsThreads / 64;
+static_assert(kEmissionsThreads == kListThreads, "k_emissions_scan, _emit and _close are rounds of qd_lists.h");
 constexpr uint32_t kEmissionsWords = 8;                      // QD_EMISSIONS_WORDS: per bin one slot word and one 7-word record of the open table
 constexpr uint64_t kEmissionsNone = ~0ull;
 constexpr uint32_t kEmissionsOff = 0xffffffffu;              // the label of an off cell
@@ -257,12 +258,10 @@ struct EmissionsParams {
     const float *norms;                      // the span's windows, S x W
     const uint32_t *thr;                     // W threshold words (bursts_threshold)
     EmissionsGeometry G;
-    uint64_t min_len, min_cells, cap;
+    uint64_t min_len, min_cells;
     uint32_t *plane;                         // (span_max + 1) W labels
     unsigned long long *rec;                 // kEmissionsRecWords planes of G.ns
-    unsigned long long *totals, *bases;      // per piece: the emissions that end in it, and the rank of the first of them
-    unsigned long long *found;               // the running count
-    Emission *list;
+    ListCursor<Emission> L;                  // per piece: the emissions that end in it; the running count; the list (qd_lists.h)
 };
 enum { kEmFirst = 0, kEmLast, kEmCells, kEmLoHi, kEmPeakFlags, kEmPos, kEmOwn, kEmOwnPos };
 
@@ -422,7 +421,7 @@ __global__ __launch_bounds__(kEmissionsThreads) void k_emissions_peak(const Emis
 }
 
 __device__ inline void emissions_store(const EmissionsParams &E, uint64_t rank, uint64_t slot, uint32_t end_bin, uint32_t more_flags) {
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(E.list + rank);
+    unsigned long long *d = reinterpret_cast<unsigned long long *>(E.L.list + rank);
     const unsigned long long lohi = *emissions_rec(E, kEmLoHi, slot), pf = *emissions_rec(E, kEmPeakFlags, slot), pos = *emissions_rec(E, kEmPos, slot);
     d[0] = *emissions_rec(E, kEmFirst, slot);
     d[1] = *emissions_rec(E, kEmLast, slot);
@@ -444,16 +443,16 @@ __global__ __launch_bounds__(kEmissionsThreads) void k_emissions_emit(const Emis
     __shared__ unsigned long long s_bal[2][kEmissionsWaves];
     __shared__ uint32_t s_tot;
     const EmissionsGeometry &G = E.G;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, q = blockIdx.x;
+    const uint32_t tid = threadIdx.x, q = blockIdx.x;
     uint64_t rank0 = 0;
     if (MODE == kEmissionsEmit) {
-        rank0 = E.bases[q];
-        if (E.totals[q] == 0 || rank0 >= E.cap) return;                     // workgroup-uniform
+        if (!list_piece_stores(E.L, q, &rank0)) return;                     // workgroup-uniform
     } else {
         if (tid == 0) s_tot = 0;
         __syncthreads();
     }
     uint32_t cnt = 0;
+#pragma unroll(MODE == kEmissionsEmit ? kEmissionsPieceCells / kEmissionsThreads : 2)      // the forms the compiler chose for the parent's text (section 3.26)
     for (uint32_t it = 0; it < kEmissionsPieceCells / kEmissionsThreads; ++it) {
         uint32_t r = 0, b = 0;
         bool keep = false;
@@ -463,39 +462,18 @@ __global__ __launch_bounds__(kEmissionsThreads) void k_emissions_emit(const Emis
             if (E.plane[c] == c) { slot = emissions_slot(G, r, b); keep = emissions_slot_kept(E, slot); }
         }
         if (MODE == kEmissionsCount) { cnt += keep; continue; }
-        const unsigned long long bal = __ballot(keep);
-        if ((tid & 63u) == 0) s_bal[it & 1][wave] = bal;
-        __syncthreads();                                                    // two sets of words: the next round writes the other one
-        uint64_t rank = rank0;
-        for (uint32_t v = 0; v < wave; ++v) rank += __popcll(s_bal[it & 1][v]);
-        rank += __popcll(bal & ((1ull << (tid & 63u)) - 1ull));
-        if (keep && rank < E.cap) emissions_store(E, rank, slot, b, 0);
-        for (uint32_t v = 0; v < kEmissionsWaves; ++v) rank0 += __popcll(s_bal[it & 1][v]);
+        const uint64_t rank = list_round_rank(keep, s_bal[it & 1], rank0);  // two sets of words: the next round writes the other one
+        if (keep && rank < E.L.cap) emissions_store(E, rank, slot, b, 0);
     }
     if (MODE == kEmissionsCount) {
         if (cnt) atomicAdd(&s_tot, cnt);
         __syncthreads();
-        if (tid == 0) E.totals[q] = s_tot;
+        if (tid == 0) E.L.totals[q] = s_tot;
     }
 }
 
-// between COUNT and EMIT: one workgroup turns the pieces' totals into their bases, exclusive, from the running count, and adds the
-// span's emissions to it
-__global__ __launch_bounds__(kEmissionsThreads) void k_emissions_scan(const EmissionsParams E) {
-    __shared__ unsigned long long s_sum[kEmissionsThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n = E.G.n_pieces, per = (n + kEmissionsThreads - 1) / kEmissionsThreads;
-    const uint64_t a = tid * per < n ? tid * per : n, b = a + per < n ? a + per : n;
-    unsigned long long mine = 0;
-    for (uint64_t q = a; q < b; ++q) mine += E.totals[q];
-    s_sum[tid] = mine;
-    __syncthreads();
-    unsigned long long before = *E.found;
-    for (uint32_t i = 0; i < tid; ++i) before += s_sum[i];
-    for (uint64_t q = a; q < b; ++q) { E.bases[q] = before; before += E.totals[q]; }
-    __syncthreads();
-    if (tid == kEmissionsThreads - 1) *E.found = before;
-}
+// between COUNT and EMIT: the pieces' totals into their bases, and the span's emissions onto the running count (list_scan, qd_lists.h)
+__global__ __launch_bounds__(kEmissionsThreads) void k_emissions_scan(const EmissionsParams E) { list_scan(E.L, E.G.n_pieces); }
 
 // The seam, of spans and of batches alike: the span's last row becomes the next span's virtual row.  A cell of the last row has its
 // root there; a root's record moves to row 0 with its emission's peak as its own.
@@ -524,28 +502,22 @@ __global__ __launch_bounds__(kEmissionsThreads) void k_emissions_carry(const Emi
 __global__ __launch_bounds__(kEmissionsThreads) void k_emissions_close(const EmissionsParams E) {
     __shared__ unsigned long long s_bal[kEmissionsWaves];
     const EmissionsGeometry &G = E.G;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6;
-    uint64_t rank0 = *E.found;
+    const uint32_t tid = threadIdx.x;
+    uint64_t rank0 = *E.L.found;
     __syncthreads();                                                        // everybody has read the count before anybody replaces it
     for (uint32_t c0 = 0; c0 < G.W; c0 += kEmissionsThreads) {
         const uint32_t b = c0 + tid;
         bool keep = false;
         if (b < G.W && E.plane[emissions_index(G, 0, b)] == emissions_index(G, 0, b)) keep = emissions_slot_kept(E, emissions_slot(G, 0, b));
-        const unsigned long long bal = __ballot(keep);
-        if ((tid & 63u) == 0) s_bal[wave] = bal;
-        __syncthreads();
-        uint64_t rank = rank0;
-        for (uint32_t v = 0; v < wave; ++v) rank += __popcll(s_bal[v]);
-        rank += __popcll(bal & ((1ull << (tid & 63u)) - 1ull));
-        if (keep && rank < E.cap) {
+        const uint64_t rank = list_round_rank(keep, s_bal, rank0);
+        if (keep && rank < E.L.cap) {
             // the carried record holds its emission's peak as its own: nothing has joined it since
             *emissions_rec(E, kEmPos, emissions_slot(G, 0, b)) = *emissions_rec(E, kEmOwnPos, emissions_slot(G, 0, b));
             emissions_store(E, rank, emissions_slot(G, 0, b), b, kEmissionsCutLast);
         }
-        for (uint32_t v = 0; v < kEmissionsWaves; ++v) rank0 += __popcll(s_bal[v]);
-        __syncthreads();
+        __syncthreads();                                                    // the next round replaces the words
     }
-    if (tid == 0) *E.found = rank0;
+    if (tid == 0) *E.L.found = rank0;
 }
 
 }  // namespace qd

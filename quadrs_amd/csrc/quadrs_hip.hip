@@ -4374,6 +4374,98 @@ int qd_plan_picture(qd_plan *p, const void *src, int src_mem, uint64_t src_first
     return f.short_read();
 }
 
+// ------------------------------------------------------------------ event lists
+
+namespace {
+// the refusals of a list's arguments, in the order every caller has had them: found, the sink's minima in the sink's noun, the list
+struct ListMin { uint64_t value; const char *name, *unit; };
+int list_given(const void *list, uint64_t cap, const uint64_t *found, const char *noun, std::initializer_list<ListMin> mins) {
+    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
+    for (const ListMin &m : mins)
+        if (m.value == 0) return fail(QD_ERR_INVALID, "%s is 0: %s holds at least one %s", m.name, noun, m.unit);
+    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    return QD_OK;
+}
+
+// the longest batch either walk of a fold cuts (the device carrier's, the host ring's): what a per-batch workspace is sized by
+uint64_t longest_batch(const Fold &f) {
+    const qd_plan *p = f.p;
+    const uint64_t obw = (uint64_t)p->W * 4;
+    return std::max(chunk_windows(p, f.first_window, f.n_windows, obw),
+                    chunk_windows(p, f.first_window, f.n_windows, std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), obw)));
+}
+
+// A record crosses batches, so a batch's walk starts behind the previous batch's: the host ring's two streams meet through an event.
+// wait(s) stands in front of a batch's launches on its stream and record(s) behind them; a device source has one stream and needs neither.
+struct Seam {
+    hipEvent_t e[2] = {nullptr, nullptr}; bool ring = false; uint64_t k = 0;
+    ~Seam() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }       // destroyed on every way out of the call
+    int open(int src_mem) {
+        ring = src_mem != QD_MEM_DEVICE;
+        if (ring) for (hipEvent_t &x : e) HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+        return QD_OK;
+    }
+    int wait(hipStream_t s) const { if (ring && k) HIPCHK(hipStreamWaitEvent(s, e[(k - 1) & 1], 0)); return QD_OK; }
+    int record(hipStream_t s) { if (ring) HIPCHK(hipEventRecord(e[k & 1], s)); ++k; return QD_OK; }
+};
+
+// The driver of the sinks that list records (qd_plan_bursts, qd_plan_emissions), on top of Fold.  An entry point calls its steps in this
+// order, with its own checks, workspace (slots 2 ... 4), batch launches and close launch between them:
+//   whole, admit      the refusals the list sinks share around the sink's too-wide refusal; admit ends with Fold::open
+//   lay               workspace slot 1 from one host image, and the list (slot 5 unless it is device memory): the cursor L but for its pieces
+//   pieces            totals and bases of at most n pieces (slot 4)
+//   home              found and the list come home: stream sync, status merge, *found, the short read's report
+extern "C++" template <typename Record>
+struct ListCall {
+    Fold f;
+    Record *list; uint64_t cap; uint64_t *found; int out_mem;
+    uint64_t max_workspace;                                          // of the list when it is not device memory
+    ListCursor<Record> L{}; unsigned long long *head = nullptr; bool out_dev = false;       // head: slot 1
+    template <typename T> int slot(int i, size_t bytes, T **at) { void *v = nullptr; const int rc = f.ws->get(i, bytes, &v); *at = static_cast<T *>(v); return rc; }
+    int whole(const char *sharded_advice) const {
+        if (const int rc = Fold::known_mem(f.src_mem, "src_mem")) return rc;
+        if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
+        return f.unsharded(sharded_advice);
+    }
+    int admit() {
+        if (const int rc = f.admit()) return rc;
+        out_dev = out_mem == QD_MEM_DEVICE;
+        if (!out_dev && cap > max_workspace / sizeof(Record))
+            return fail(QD_ERR_UNSUPPORTED, "a list of %llu records needs a workspace of %llu bytes, above the %llu allowed: list into device memory, or lower cap",
+                        (unsigned long long)cap, (unsigned long long)cap * sizeof(Record), (unsigned long long)max_workspace);
+        return f.open();
+    }
+    // slot 1: [front: the sink's own u64 words][found = 0][behind: u64 words, zero][threshold words: W u32]; *thr_d receives the last
+    int lay(const std::vector<uint64_t> &front, size_t behind, const std::vector<uint32_t> &thr, const uint32_t **thr_d) {
+        const size_t head_words = front.size() + 1 + behind;
+        std::vector<uint64_t> image(head_words + (thr.size() + 1) / 2, 0);
+        std::copy(front.begin(), front.end(), image.begin());
+        memcpy(image.data() + head_words, thr.data(), thr.size() * 4);
+        if (const int rc = slot(1, image.size() * 8, &head)) return rc;
+        HIPCHK(hipMemcpyAsync(head, image.data(), image.size() * 8, hipMemcpyHostToDevice, f.st));
+        HIPCHK(hipStreamSynchronize(f.st));                          // the image is this call's array
+        L.found = head + front.size(); L.cap = cap; L.list = list;
+        *thr_d = reinterpret_cast<const uint32_t *>(head + head_words);
+        return cap && !out_dev ? slot(5, (size_t)(cap * sizeof(Record)), &L.list) : QD_OK;
+    }
+    int pieces(uint64_t n) { const int rc = slot(4, (size_t)(n * 16), &L.totals); L.bases = L.totals + n; return rc; }
+    // `also` comes home behind found: a plane of the sink's in the workspace (bytes 0: none)
+    int home(int rc, void *also_user = nullptr, const void *also_dev = nullptr, size_t also_bytes = 0) {
+        uint64_t total = 0;
+        if (rc == QD_OK) {
+            HIPCHK(hipMemcpyAsync(&total, L.found, 8, hipMemcpyDeviceToHost, f.st));
+            if (also_bytes) HIPCHK(hipMemcpyAsync(also_user, also_dev, also_bytes, hipMemcpyDeviceToHost, f.st));
+        }
+        rc = f.sync(rc);
+        if (rc) return rc;
+        const uint64_t written = std::min(total, cap);
+        if (written && !out_dev) HIPCHK(hipMemcpy(list, L.list, (size_t)(written * sizeof(Record)), hipMemcpyDeviceToHost));
+        *found = total;
+        return f.short_read();
+    }
+};
+}  // namespace
+
 // ------------------------------------------------------------------ burst list
 
 namespace {
@@ -4384,9 +4476,7 @@ static_assert(sizeof(Burst) == sizeof(qd_burst) && sizeof(qd_burst) == 32 && kBu
 int bursts_given(uint32_t W, const float *thresholds, uint64_t min_len, const qd_burst *list, uint64_t cap, const uint64_t *found, uint32_t *words) {
     if (W == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
     if (!thresholds) return fail(QD_ERR_INVALID, "thresholds is NULL");
-    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
-    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: a burst holds at least one window");
-    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    if (const int rc = list_given(list, cap, found, "a burst", {{min_len, "min_len", "window"}})) return rc;
     for (uint32_t b = 0; b < W; ++b) {
         uint32_t w;
         if (!bursts_threshold(bits_of_f32(thresholds[b]), &w))
@@ -4445,9 +4535,7 @@ int qd_bursts_fold(uint64_t *state, uint32_t width, const float *thresholds, uin
 int qd_bursts_finish(uint64_t *state, uint32_t width, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found) {
     if (!state) return fail(QD_ERR_INVALID, "state is NULL");
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
-    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: a burst holds at least one window");
-    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    if (const int rc = list_given(list, cap, found, "a burst", {{min_len, "min_len", "window"}})) return rc;
     const uint64_t next = state[(size_t)width * kBurstsWords];
     for (uint32_t b = 0; b < width; ++b) {
         const uint64_t *s = state + (size_t)b * kBurstsWords;
@@ -4460,78 +4548,54 @@ int qd_plan_bursts(qd_plan *p, const void *src, int src_mem, uint64_t src_first,
                    const float *thresholds, uint64_t min_len, qd_burst *list, uint64_t cap, uint64_t *found, uint64_t *on_counts, int out_mem,
                    void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
-    Fold f{p, "qd_plan_bursts", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    ListCall<Burst> c{{p, "qd_plan_bursts", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)},
+                      reinterpret_cast<Burst *>(list), cap, found, out_mem, kBurstsMaxWorkspace};
+    Fold &f = c.f;
     if (const int rc = f.norms_plan()) return rc;
     const uint32_t W = p->W;
     std::vector<uint32_t> thr(W);
     if (const int rc = bursts_given(W, thresholds, min_len, list, cap, found, thr.data())) return rc;
-    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
-    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
-    if (const int rc = f.unsharded("a sharded plan's bursts are not listed in one call: run one range on one device on a plan of its own; joining the lists across a "
-                                   "seam, where a run may cross, is the caller's job")) return rc;
+    if (const int rc = c.whole("a sharded plan's bursts are not listed in one call: run one range on one device on a plan of its own; joining the lists across a "
+                               "seam, where a run may cross, is the caller's job")) return rc;
     if (bursts_seg_max(W) == 0) return fail(QD_ERR_UNSUPPORTED, "windows of %u bins are too wide for the burst walker (at most 131072)", W);
-    if (const int rc = f.admit()) return rc;
-    const bool out_dev = out_mem == QD_MEM_DEVICE;
-    if (!out_dev && cap > kBurstsMaxWorkspace / sizeof(Burst))
-        return fail(QD_ERR_UNSUPPORTED, "a list of %llu records needs a workspace of %llu bytes, above the %llu allowed: list into device memory, or lower cap",
-                    (unsigned long long)cap, (unsigned long long)cap * 32ull, (unsigned long long)kBurstsMaxWorkspace);
-    if (const int rc = f.open()) return rc;
+    if (const int rc = c.admit()) return rc;
     const hipStream_t st = f.st;
-    // slot 1: [state: 3 W][found][on_counts: W][threshold words: W u32], written from one host image
-    const size_t head_words = (size_t)kBurstsWords * W + 1 + W;
-    std::vector<uint64_t> image(head_words + (W + 1) / 2, 0);
-    for (uint32_t b = 0; b < W; ++b) image[b] = kBurstsNone;
-    memcpy(image.data() + head_words, thr.data(), (size_t)W * 4);
-    void *v = nullptr;
-    int rc = f.ws->get(1, image.size() * 8, &v); if (rc) return rc;
-    unsigned long long *head = static_cast<unsigned long long *>(v);
-    HIPCHK(hipMemcpyAsync(head, image.data(), image.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));                                // the image is this call's array
+    // slot 1: [state: 3 W][found][on_counts: W][threshold words: W u32]
+    std::vector<uint64_t> state((size_t)kBurstsWords * W, 0);
+    std::fill(state.begin(), state.begin() + W, kBurstsNone);
     BurstsParams B{};
-    B.state = head; B.found = head + (size_t)kBurstsWords * W; B.thr = reinterpret_cast<const uint32_t *>(head + head_words);
-    unsigned long long *counts_ws = head + (size_t)kBurstsWords * W + 1;
-    B.on_counts = !on_counts ? nullptr : out_dev ? reinterpret_cast<unsigned long long *>(on_counts) : counts_ws;
-    if (on_counts && out_dev) HIPCHK(hipMemsetAsync(on_counts, 0, (size_t)W * 8, st));
-    B.min_len = min_len; B.cap = cap;
-    if (cap && !out_dev) { rc = f.ws->get(5, (size_t)(cap * sizeof(Burst)), &v); if (rc) return rc; B.list = static_cast<Burst *>(v); }
-    else B.list = reinterpret_cast<Burst *>(list);
-    B.vec_store = ((uintptr_t)B.list & 15) == 0;
+    if (const int rc = c.lay(state, W, thr, &B.thr)) return rc;
+    B.state = c.head;
+    unsigned long long *counts_ws = c.L.found + 1;
+    B.on_counts = !on_counts ? nullptr : c.out_dev ? reinterpret_cast<unsigned long long *>(on_counts) : counts_ws;
+    if (on_counts && c.out_dev) HIPCHK(hipMemsetAsync(on_counts, 0, (size_t)W * 8, st));
+    B.min_len = min_len;
+    B.vec_store = ((uintptr_t)c.L.list & 15) == 0;
+    int rc = QD_OK;
     if (f.n_windows) {
         // the per-piece words: sized by the longest batch either walk cuts
-        const uint64_t nw_max = std::max(chunk_windows(p, first_window, f.n_windows, (uint64_t)W * 4),
-                                         chunk_windows(p, first_window, f.n_windows, std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), (uint64_t)W * 4)));
-        const uint64_t bound = bursts_pieces_bound(nw_max, W, p->n_cu);
+        const uint64_t bound = bursts_pieces_bound(longest_batch(f), W, p->n_cu);
         const size_t piece_bytes = (size_t)(bound * kBurstsWords * W * 8);
-        rc = f.ws->get(2, piece_bytes, &v); if (rc) return rc; B.edge = static_cast<unsigned long long *>(v);
-        rc = f.ws->get(3, piece_bytes, &v); if (rc) return rc; B.inc = static_cast<unsigned long long *>(v);
-        rc = f.ws->get(4, (size_t)(bound * 16), &v); if (rc) return rc;
-        B.totals = static_cast<unsigned long long *>(v); B.bases = B.totals + bound;
-        // a run crosses batches, so a batch's walk starts behind the previous batch's: the host ring's two streams meet through an event
-        struct Seam {                                                // destroyed on every way out of the call
-            hipEvent_t e[2] = {nullptr, nullptr};
-            ~Seam() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-        } seam;
-        const bool ring = src_mem != QD_MEM_DEVICE;
-        if (ring) for (hipEvent_t &e : seam.e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        uint64_t k = 0;
+        if ((rc = c.slot(2, piece_bytes, &B.edge)) || (rc = c.slot(3, piece_bytes, &B.inc)) || (rc = c.pieces(bound))) return rc;
+        B.L = c.L;
+        Seam seam;
+        if ((rc = seam.open(src_mem))) return rc;
         rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
             if (nw == 0) return (int)QD_OK;
             BurstsParams Q = B;
             uint64_t grid = 0;
             bursts_split(g0, nw, W, p->n_cu, &Q.G, &grid);
             if (Q.G.n_pieces > bound) return fail(QD_ERR_INVALID, "a batch of %llu windows is cut into more pieces than the workspace holds", (unsigned long long)nw);
-            if (const int c = launch_grid(grid, nw)) return c;
+            if (const int r = launch_grid(grid, nw)) return r;
             Q.norms = norms_d;
-            if (ring && k) HIPCHK(hipStreamWaitEvent(s, seam.e[(k - 1) & 1], 0));
+            if (const int r = seam.wait(s)) return r;
             hipLaunchKernelGGL(k_bursts_edge, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
             hipLaunchKernelGGL(k_bursts_stitch, dim3((W + kBurstsStitchBins - 1) / kBurstsStitchBins), dim3(kBurstsThreads), 0, s, Q);
             hipLaunchKernelGGL(k_bursts_emit<kBurstsCount>, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
             hipLaunchKernelGGL(k_bursts_scan, dim3(1), dim3(kBurstsThreads), 0, s, Q);
             if (cap) hipLaunchKernelGGL(k_bursts_emit<kBurstsEmit>, dim3((uint32_t)grid), dim3(kBurstsThreads), 0, s, Q);
             HIPCHK(hipGetLastError());
-            if (ring) HIPCHK(hipEventRecord(seam.e[k & 1], s));
-            ++k;
-            return (int)QD_OK;
+            return seam.record(s);
         });
         if (rc == QD_OK) {
             BurstsParams Q = B;
@@ -4540,17 +4604,7 @@ int qd_plan_bursts(qd_plan *p, const void *src, int src_mem, uint64_t src_first,
             HIPCHK(hipGetLastError());
         }
     }
-    uint64_t total = 0;
-    if (rc == QD_OK) {
-        HIPCHK(hipMemcpyAsync(&total, B.found, 8, hipMemcpyDeviceToHost, st));
-        if (on_counts && !out_dev) HIPCHK(hipMemcpyAsync(on_counts, counts_ws, (size_t)W * 8, hipMemcpyDeviceToHost, st));
-    }
-    rc = f.sync(rc);
-    if (rc) return rc;
-    const uint64_t written = std::min(total, cap);
-    if (written && !out_dev) HIPCHK(hipMemcpy(list, B.list, (size_t)(written * sizeof(Burst)), hipMemcpyDeviceToHost));
-    *found = total;
-    return f.short_read();
+    return c.home(rc, on_counts, counts_ws, on_counts && !c.out_dev ? (size_t)W * 8 : 0);
 }
 
 // ------------------------------------------------------------------ emission list
@@ -4562,14 +4616,11 @@ static_assert(sizeof(Emission) == sizeof(qd_emission) && sizeof(qd_emission) == 
               "qd_emissions.h and the public header agree on a record");
 static_assert(kEmissionsLdsWords * 4 <= 64 * 1024, "k_emissions_tile's LDS");
 
-// the checks the twin and qd_plan_emissions share, on top of the burst list's
+// the checks the twin and qd_plan_emissions share: the burst list's of the width, the thresholds and found, then the list's own
 int emissions_given(uint32_t W, const float *thresholds, uint64_t min_len, uint64_t min_cells, const qd_emission *list, uint64_t cap, const uint64_t *found,
                     uint32_t *words) {
-    if (const int rc = bursts_given(W, thresholds, min_len ? min_len : 1, nullptr, 0, found, words)) return rc;
-    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: an emission holds at least one window");
-    if (min_cells == 0) return fail(QD_ERR_INVALID, "min_cells is 0: an emission holds at least one cell");
-    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
-    return QD_OK;
+    if (const int rc = bursts_given(W, thresholds, 1, nullptr, 0, found, words)) return rc;
+    return list_given(list, cap, found, "an emission", {{min_len, "min_len", "window"}, {min_cells, "min_cells", "cell"}});
 }
 }  // namespace
 
@@ -4598,10 +4649,7 @@ int qd_emissions_fold(uint64_t *state, uint32_t width, const float *thresholds, 
 int qd_emissions_finish(uint64_t *state, uint32_t width, uint64_t min_len, uint64_t min_cells, qd_emission *list, uint64_t cap, uint64_t *found) {
     if (!state) return fail(QD_ERR_INVALID, "state is NULL");
     if (width == 0) return fail(QD_ERR_INVALID, "rows of width 0 hold nothing");
-    if (!found) return fail(QD_ERR_INVALID, "found is NULL");
-    if (min_len == 0) return fail(QD_ERR_INVALID, "min_len is 0: an emission holds at least one window");
-    if (min_cells == 0) return fail(QD_ERR_INVALID, "min_cells is 0: an emission holds at least one cell");
-    if (!list && cap) return fail(QD_ERR_INVALID, "list is NULL with cap %llu", (unsigned long long)cap);
+    if (const int rc = list_given(list, cap, found, "an emission", {{min_len, "min_len", "window"}, {min_cells, "min_cells", "cell"}})) return rc;
     emissions_twin_finish(state, width, EmissionsSink{reinterpret_cast<Emission *>(list), cap, found, min_len, min_cells});
     return QD_OK;
 }
@@ -4610,61 +4658,39 @@ int qd_plan_emissions(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
                       const float *thresholds, uint64_t min_len, uint64_t min_cells, qd_emission *list, uint64_t cap, uint64_t *found, int out_mem,
                       void *stream) {
     if (!p) return fail(QD_ERR_INVALID, "NULL argument");
-    Fold f{p, "qd_plan_emissions", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)};
+    ListCall<Emission> c{{p, "qd_plan_emissions", src, src_mem, src_first, src_count, first_window, n_windows, static_cast<hipStream_t>(stream)},
+                         reinterpret_cast<Emission *>(list), cap, found, out_mem, kEmissionsMaxWorkspace};
+    Fold &f = c.f;
     if (const int rc = f.norms_plan()) return rc;
     const uint32_t W = p->W;
     std::vector<uint32_t> thr(W);
     if (const int rc = emissions_given(W, thresholds, min_len, min_cells, list, cap, found, thr.data())) return rc;
-    if (const int rc = Fold::known_mem(src_mem, "src_mem")) return rc;
-    if (const int rc = Fold::known_mem(out_mem, "out_mem")) return rc;
-    if (const int rc = f.unsharded("a sharded plan's emissions are not listed in one call: run one range on one device on a plan of its own; an emission crosses "
-                                   "the seam, and joining the lists there is the caller's job")) return rc;
+    if (const int rc = c.whole("a sharded plan's emissions are not listed in one call: run one range on one device on a plan of its own; an emission crosses "
+                               "the seam, and joining the lists there is the caller's job")) return rc;
     if (W > kEmissionsMaxWidth) return fail(QD_ERR_UNSUPPORTED, "windows of %u bins are too wide for the emission tiles (at most %u)", W, kEmissionsMaxWidth);
-    if (const int rc = f.admit()) return rc;
-    const bool out_dev = out_mem == QD_MEM_DEVICE;
-    if (!out_dev && cap > kEmissionsMaxWorkspace / sizeof(Emission))
-        return fail(QD_ERR_UNSUPPORTED, "a list of %llu records needs a workspace of %llu bytes, above the %llu allowed: list into device memory, or lower cap",
-                    (unsigned long long)cap, (unsigned long long)cap * 56ull, (unsigned long long)kEmissionsMaxWorkspace);
-    if (const int rc = f.open()) return rc;
+    if (const int rc = c.admit()) return rc;
     const hipStream_t st = f.st;
-    // slot 1: [found][threshold words: W u32], written from one host image
-    std::vector<uint64_t> image(1 + (W + 1) / 2, 0);
-    memcpy(image.data() + 1, thr.data(), (size_t)W * 4);
-    void *v = nullptr;
-    int rc = f.ws->get(1, image.size() * 8, &v); if (rc) return rc;
-    unsigned long long *head = static_cast<unsigned long long *>(v);
-    HIPCHK(hipMemcpyAsync(head, image.data(), image.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));                                // the image is this call's array
+    // slot 1: [found][threshold words: W u32]
     EmissionsParams E{};
-    E.found = head; E.thr = reinterpret_cast<const uint32_t *>(head + 1);
-    E.min_len = min_len; E.min_cells = min_cells; E.cap = cap;
-    if (cap && !out_dev) { rc = f.ws->get(5, (size_t)(cap * sizeof(Emission)), &v); if (rc) return rc; E.list = static_cast<Emission *>(v); }
-    else E.list = reinterpret_cast<Emission *>(list);
+    if (const int rc = c.lay({}, 0, thr, &E.thr)) return rc;
+    E.min_len = min_len; E.min_cells = min_cells;
+    int rc = QD_OK;
     if (f.n_windows) {
         // the span's workspace: sized by the longest batch either walk cuts, and by the span rule whatever chunk_bytes is
-        const uint64_t nw_max = std::max(chunk_windows(p, first_window, f.n_windows, (uint64_t)W * 4),
-                                         chunk_windows(p, first_window, f.n_windows, std::max<uint64_t>((uint64_t)p->S * p->D * bps_of(p->d.format), (uint64_t)W * 4)));
-        const uint64_t span_max = emissions_span_max(W, nw_max), ns = emissions_slots(W, span_max), pieces = emissions_pieces_bound(W, span_max);
-        rc = f.ws->get(2, (size_t)emissions_plane_bytes(W, span_max), &v); if (rc) return rc; E.plane = static_cast<uint32_t *>(v);
-        rc = f.ws->get(3, (size_t)(ns * kEmissionsRecWords * 8), &v); if (rc) return rc; E.rec = static_cast<unsigned long long *>(v);
-        rc = f.ws->get(4, (size_t)(pieces * 16), &v); if (rc) return rc;
-        E.totals = static_cast<unsigned long long *>(v); E.bases = E.totals + pieces;
+        const uint64_t span_max = emissions_span_max(W, longest_batch(f)), ns = emissions_slots(W, span_max);
+        if ((rc = c.slot(2, (size_t)emissions_plane_bytes(W, span_max), &E.plane)) || (rc = c.slot(3, (size_t)(ns * kEmissionsRecWords * 8), &E.rec)) ||
+            (rc = c.pieces(emissions_pieces_bound(W, span_max)))) return rc;
+        E.L = c.L;
         // nothing is open before the first window: an off virtual row without records
         HIPCHK(hipMemsetAsync(E.plane, 0xff, (size_t)W * 4, st));
         HIPCHK(hipMemsetAsync(E.rec + (uint64_t)kEmOwn * ns, 0xff, (size_t)emissions_half(W) * 8, st));
-        // an emission crosses batches, so a batch's walk starts behind the previous batch's: the host ring's two streams meet through an event
-        struct Seam {                                                // destroyed on every way out of the call
-            hipEvent_t e[2] = {nullptr, nullptr};
-            ~Seam() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-        } seam;
-        const bool ring = src_mem != QD_MEM_DEVICE;
-        if (ring) for (hipEvent_t &e : seam.e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (ring) HIPCHK(hipStreamSynchronize(st));                  // the virtual row is laid before a ring stream reads it
-        uint64_t k = 0;
+        Seam seam;
+        if ((rc = seam.open(src_mem))) return rc;
+        if (seam.ring) HIPCHK(hipStreamSynchronize(st));             // the virtual row is laid before a ring stream reads it
         EmissionsGeometry last{};
         rc = f.walk([&](const float *norms_d, uint64_t g0, uint64_t nw, hipStream_t s) {
             if (nw == 0) return (int)QD_OK;
-            if (ring && k) HIPCHK(hipStreamWaitEvent(s, seam.e[(k - 1) & 1], 0));
+            if (const int r = seam.wait(s)) return r;
             for (uint64_t a = 0; a < nw; a += span_max) {
                 EmissionsParams Q = E;
                 const uint64_t S = std::min<uint64_t>(nw - a, span_max);
@@ -4683,9 +4709,7 @@ int qd_plan_emissions(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
                 last = Q.G;
             }
             HIPCHK(hipGetLastError());
-            if (ring) HIPCHK(hipEventRecord(seam.e[k & 1], s));
-            ++k;
-            return (int)QD_OK;
+            return seam.record(s);
         });
         if (rc == QD_OK) {
             EmissionsParams Q = E;
@@ -4694,14 +4718,7 @@ int qd_plan_emissions(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
             HIPCHK(hipGetLastError());
         }
     }
-    uint64_t total = 0;
-    if (rc == QD_OK) HIPCHK(hipMemcpyAsync(&total, E.found, 8, hipMemcpyDeviceToHost, st));
-    rc = f.sync(rc);
-    if (rc) return rc;
-    const uint64_t written = std::min(total, cap);
-    if (written && !out_dev) HIPCHK(hipMemcpy(list, E.list, (size_t)(written * sizeof(Emission)), hipMemcpyDeviceToHost));
-    *found = total;
-    return f.short_read();
+    return c.home(rc);
 }
 
 int qd_device_alloc(size_t bytes, void **ptr) {

@@ -526,6 +526,24 @@ def _burst_list(into):
     return (None, 0) if into is None or into.size == 0 else (_np_ptr(into), into.size)
 
 
+def _list_fold(call, state, norms, thresholds, mins, at, into, found, *more):
+    """qd_<sink>_fold of norms rows (n, width), windows at, at+1, ..., behind record `found` of `into`; `mins` are the sink's minima and
+    `more` what its call takes behind found.  Returns the new found."""
+    a = np.ascontiguousarray(norms, dtype=np.float32)
+    n, width = a.shape
+    t = _burst_thresholds(thresholds, width)
+    f = C.c_uint64(int(found))
+    check(call(_np_ptr(state), width, _np_ptr(t), *mins, int(at), _np_ptr(a) if n else None, n, *_burst_list(into), C.byref(f), *more))
+    return f.value
+
+
+def _list_finish(call, state, width, mins, into, found):
+    """qd_<sink>_finish of a state of `width` bins behind record `found` of `into`.  Returns found."""
+    f = C.c_uint64(int(found))
+    check(call(_np_ptr(state), width, *mins, *_burst_list(into), C.byref(f)))
+    return f.value
+
+
 def bursts_init(width):
     """qd_bursts_init: (state uint64[3 width + 1], on_counts uint64[width]) with no run open."""
     state = np.empty(_ffi.BURSTS_WORDS * int(width) + 1, dtype=np.uint64)
@@ -537,23 +555,12 @@ def bursts_init(width):
 def bursts_fold(state, norms, thresholds, min_len=1, at=0, into=None, found=0, on_counts=None):
     """qd_bursts_fold: norms rows (n, width) are windows at, at+1, ... of a range.  The bursts that end in them go to the BURST_DTYPE array
     `into` (its length is cap; None: count only) from record `found` on.  Returns the new found."""
-    a = np.ascontiguousarray(norms, dtype=np.float32)
-    n, width = a.shape
-    t = _burst_thresholds(thresholds, width)
-    f = C.c_uint64(int(found))
-    check(lib().qd_bursts_fold(_np_ptr(state), width, _np_ptr(t), int(min_len), int(at), _np_ptr(a) if n else None, n,
-                               *_burst_list(into), C.byref(f),
-                               None if on_counts is None else _np_ptr(on_counts)))
-    return f.value
+    return _list_fold(lib().qd_bursts_fold, state, norms, thresholds, (int(min_len),), at, into, found, None if on_counts is None else _np_ptr(on_counts))
 
 
 def bursts_finish(state, min_len=1, into=None, found=0):
     """qd_bursts_finish: closes the open runs at the last window folded; the state is left as bursts_init leaves it.  Returns found."""
-    f = C.c_uint64(int(found))
-    width = (state.size - 1) // _ffi.BURSTS_WORDS
-    check(lib().qd_bursts_finish(_np_ptr(state), width, int(min_len), *_burst_list(into),
-                                 C.byref(f)))
-    return f.value
+    return _list_finish(lib().qd_bursts_finish, state, (state.size - 1) // _ffi.BURSTS_WORDS, (int(min_len),), into, found)
 
 
 def bursts_of(norms, thresholds, min_len=1, cap=None):
@@ -587,21 +594,12 @@ def emissions_init(width):
 def emissions_fold(state, norms, thresholds, min_len=1, min_cells=1, at=0, into=None, found=0):
     """qd_emissions_fold: norms rows (n, width) are windows at, at+1, ... of a range.  The emissions that end above them go to the
     EMISSION_DTYPE array `into` (its length is cap; None: count only) from record `found` on.  Returns the new found."""
-    a = np.ascontiguousarray(norms, dtype=np.float32)
-    n, width = a.shape
-    t = _burst_thresholds(thresholds, width)
-    f = C.c_uint64(int(found))
-    check(lib().qd_emissions_fold(_np_ptr(state), width, _np_ptr(t), int(min_len), int(min_cells), int(at), _np_ptr(a) if n else None, n,
-                                  *_burst_list(into), C.byref(f)))
-    return f.value
+    return _list_fold(lib().qd_emissions_fold, state, norms, thresholds, (int(min_len), int(min_cells)), at, into, found)
 
 
 def emissions_finish(state, min_len=1, min_cells=1, into=None, found=0):
     """qd_emissions_finish: closes what is open at the last window folded; the state is left as emissions_init leaves it.  Returns found."""
-    f = C.c_uint64(int(found))
-    width = (state.size - 2) // _ffi.EMISSIONS_WORDS
-    check(lib().qd_emissions_finish(_np_ptr(state), width, int(min_len), int(min_cells), *_burst_list(into), C.byref(f)))
-    return f.value
+    return _list_finish(lib().qd_emissions_finish, state, (state.size - 2) // _ffi.EMISSIONS_WORDS, (int(min_len), int(min_cells)), into, found)
 
 
 def emissions_of(norms, thresholds, min_len=1, min_cells=1, cap=None):
@@ -965,6 +963,50 @@ class Plan:
                                               device_out, shapes)))
         return tuple(out.get(o) for o in BAND_OUTPUTS)
 
+    def _list_call(self, call, dtype, cap_rule, mins, src, thresholds, cap, first_window, n_windows, src_first, pinned, device_out, out, counts=None):
+        """(list, found) of a list sink's `call` (qd_plan_bursts, qd_plan_emissions) whose records are `dtype`: cap from `out`, else from
+        cap_rule; `mins` are the sink's minima.  counts: (counts_out,) where the call also fills a plane of width uint64 words, which
+        then comes third.  A failing call's error carries the result as e.partial."""
+        n_windows = self.n_windows - first_window if n_windows is None else n_windows
+        ptr, mem, count, st, _keep = self._src_args(src, pinned)
+        W, size = self.width, dtype.itemsize
+        t = _burst_thresholds(thresholds, W)
+        dev = (_is_torch(src) if device_out is None else device_out) if out is None else _is_torch(out)
+        if out is None:
+            cap = cap_rule(cap, n_windows, W)
+        else:                                    # the list given holds what it holds: cap defaults to it and may not exceed it
+            room = (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) // size
+            cap = room if cap is None else int(cap)
+            if cap > room:
+                raise ValueError("cap %d above the %d records that out holds" % (cap, room))
+        cnt = counts[0] if counts else None
+        if cnt is not None and (cnt.numel() * cnt.element_size() if _is_torch(cnt) else cnt.nbytes) < 8 * W:
+            raise ValueError("counts_out holds fewer than %d uint64 words" % W)
+        if dev:
+            import torch
+            lst = torch.empty((cap, size), dtype=torch.uint8, device="cuda") if out is None else out
+            lptr, out_mem = C.c_void_p(lst.data_ptr()) if cap else None, MEM_DEVICE
+            if counts:
+                cnt = torch.empty(W, dtype=torch.int64, device="cuda") if cnt is None else cnt
+                counts = (C.c_void_p(cnt.data_ptr()),)
+        else:
+            lst = np.zeros(cap, dtype=dtype) if out is None else out
+            lptr, out_mem = _np_ptr(lst) if cap else None, (_ffi.MEM_HOST_PINNED if pinned and out is not None else MEM_HOST)
+            if counts:
+                cnt = np.empty(W, dtype=np.uint64) if cnt is None else cnt
+                counts = (_np_ptr(cnt),)
+        found = C.c_uint64(0)
+
+        def result():
+            k = min(found.value, cap)
+            return ((lst.reshape(-1, size)[:k] if dev else lst[:k]), found.value) + ((cnt,) if counts else ())
+        try:
+            check(call(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), *mins, lptr, cap, C.byref(found), *(counts or ()), out_mem, st))
+        except _ffi.QuadrsError as e:
+            e.partial = result()
+            raise
+        return result()
+
     def bursts(self, src, thresholds, min_len=1, cap=None, first_window=0, n_windows=None, src_first=0, pinned=False, device_out=None,
                out=None, counts_out=None):
         """qd_plan_bursts of an EPI_NORMS_F32 plan: (list, found, on_counts) — the runs of cells at or above the bin's threshold
@@ -974,41 +1016,8 @@ class Plan:
         [records, 32] with on_counts int64 (the same bits).  out / counts_out: a BURST_DTYPE array or uint8 tensor, and width uint64 words,
         to write into instead; cap then defaults to the records `out` holds and may not exceed them.  A failing call's error carries
         (list, found, on_counts) as e.partial."""
-        n_windows = self.n_windows - first_window if n_windows is None else n_windows
-        ptr, mem, count, st, _keep = self._src_args(src, pinned)
-        W = self.width
-        t = _burst_thresholds(thresholds, W)
-        dev = (_is_torch(src) if device_out is None else device_out) if out is None else _is_torch(out)
-        if out is None:
-            cap = _burst_cap(cap, n_windows, W)
-        else:                                    # the list given holds what it holds: cap defaults to it and may not exceed it
-            room = (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) // BURST_DTYPE.itemsize
-            cap = room if cap is None else int(cap)
-            if cap > room:
-                raise ValueError("cap %d above the %d records that out holds" % (cap, room))
-        if counts_out is not None and (counts_out.numel() * counts_out.element_size() if _is_torch(counts_out) else counts_out.nbytes) < 8 * W:
-            raise ValueError("counts_out holds fewer than %d uint64 words" % W)
-        if dev:
-            import torch
-            lst = torch.empty((cap, 32), dtype=torch.uint8, device="cuda") if out is None else out
-            cnt = torch.empty(W, dtype=torch.int64, device="cuda") if counts_out is None else counts_out
-            lptr, cptr, out_mem = C.c_void_p(lst.data_ptr()) if cap else None, C.c_void_p(cnt.data_ptr()), MEM_DEVICE
-        else:
-            lst = np.zeros(cap, dtype=BURST_DTYPE) if out is None else out
-            cnt = np.empty(W, dtype=np.uint64) if counts_out is None else counts_out
-            lptr, cptr, out_mem = _np_ptr(lst) if cap else None, _np_ptr(cnt), (_ffi.MEM_HOST_PINNED if pinned and out is not None else MEM_HOST)
-        found = C.c_uint64(0)
-
-        def result():
-            k = min(found.value, cap)
-            return (lst.reshape(-1, 32)[:k] if dev else lst[:k]), found.value, cnt
-        try:
-            check(lib().qd_plan_bursts(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), int(min_len), lptr, cap,
-                                       C.byref(found), cptr, out_mem, st))
-        except _ffi.QuadrsError as e:
-            e.partial = result()
-            raise
-        return result()
+        return self._list_call(lib().qd_plan_bursts, BURST_DTYPE, _burst_cap, (int(min_len),), src, thresholds, cap, first_window, n_windows, src_first,
+                               pinned, device_out, out, (counts_out,))
 
     def emissions(self, src, thresholds, min_len=1, min_cells=1, cap=None, first_window=0, n_windows=None, src_first=0, pinned=False,
                   device_out=None, out=None):
@@ -1018,38 +1027,8 @@ class Plan:
         EMISSIONS_DEFAULT_CAP).  src and device_out as for bursts: the list is an EMISSION_DTYPE numpy array, or a torch uint8 CUDA tensor
         [records, 56].  out: an EMISSION_DTYPE array or uint8 tensor to write into instead; cap then defaults to the records `out` holds
         and may not exceed them.  A failing call's error carries (list, found) as e.partial."""
-        n_windows = self.n_windows - first_window if n_windows is None else n_windows
-        ptr, mem, count, st, _keep = self._src_args(src, pinned)
-        W = self.width
-        t = _burst_thresholds(thresholds, W)
-        dev = (_is_torch(src) if device_out is None else device_out) if out is None else _is_torch(out)
-        size = EMISSION_DTYPE.itemsize
-        if out is None:
-            cap = _emission_cap(cap, n_windows, W)
-        else:                                    # the list given holds what it holds: cap defaults to it and may not exceed it
-            room = (out.numel() * out.element_size() if _is_torch(out) else out.nbytes) // size
-            cap = room if cap is None else int(cap)
-            if cap > room:
-                raise ValueError("cap %d above the %d records that out holds" % (cap, room))
-        if dev:
-            import torch
-            lst = torch.empty((cap, size), dtype=torch.uint8, device="cuda") if out is None else out
-            lptr, out_mem = C.c_void_p(lst.data_ptr()) if cap else None, MEM_DEVICE
-        else:
-            lst = np.zeros(cap, dtype=EMISSION_DTYPE) if out is None else out
-            lptr, out_mem = _np_ptr(lst) if cap else None, (_ffi.MEM_HOST_PINNED if pinned and out is not None else MEM_HOST)
-        found = C.c_uint64(0)
-
-        def result():
-            k = min(found.value, cap)
-            return (lst.reshape(-1, size)[:k] if dev else lst[:k]), found.value
-        try:
-            check(lib().qd_plan_emissions(self._h, ptr, mem, src_first, count, first_window, n_windows, _np_ptr(t), int(min_len), int(min_cells),
-                                          lptr, cap, C.byref(found), out_mem, st))
-        except _ffi.QuadrsError as e:
-            e.partial = result()
-            raise
-        return result()
+        return self._list_call(lib().qd_plan_emissions, EMISSION_DTYPE, _emission_cap, (int(min_len), int(min_cells)), src, thresholds, cap, first_window,
+                               n_windows, src_first, pinned, device_out, out)
 
     def picture(self, src, desc, first_window=0, n_windows=None, src_first=0, pinned=False, out=None, device_out=None):
         """qd_plan_picture of an EPI_NORMS_F32 plan: (pixels uint8[px_height, px_width, 3], painted) — the waterfall picture of windows

@@ -228,6 +228,31 @@ def test_overflow_keeps_the_prefix_and_the_guards(engine, world):
             assert hc[1:W + 1].tobytes() == counts.tobytes() and hc[0] == hc[W + 1] == 0x5A5A5A5A5A5A5A5A
 
 
+@pytest.mark.parametrize("name", ["cf32_w4", "cf32_w128"])
+def test_cap_ladder(engine, world, name):
+    """cap at the wave, round and off-by-one boundaries of the ballot rank (63 ... 65, 255 ... 257), at found and past it; at W = 4
+    several pieces share a wave.  The list is the twin's first min(found, cap) records byte for byte, found is the twin's, and the guard
+    bytes in front of and behind the list are intact.  A host source into a host list and a device source into a device list, where
+    the kernels store."""
+    import torch
+    plan, data, dev, norms, n, spec = world(name)
+    W = spec[3]["width"]
+    thr = threshold_sets(norms)["median"]
+    full, found, _ = engine.bursts_of(norms, thr, 1, cap=n * W)
+    assert found > 257 and full.size == found                              # every cap of the ladder cuts the list
+    for cap in (63, 64, 65, 255, 256, 257, found, found + 1):
+        k = min(cap, found)
+        buf = np.full((cap + 2) * 32, util.GUARD_BYTE, dtype=np.uint8)
+        got = plan.bursts(data, thr, 1, cap=cap, n_windows=n, out=buf[32:32 + cap * 32].view(BURST))
+        t = torch.full(((cap + 2) * 32,), util.GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        got_d = plan.bursts(dev, thr, 1, cap=cap, n_windows=n, out=t[32:32 + cap * 32])
+        torch.cuda.synchronize()
+        for g, h in ((got, buf), (got_d, t.cpu().numpy())):
+            assert g[1] == found and g[0].shape[0] == k, cap
+            assert h[32:32 + k * 32].tobytes() == full[:k].tobytes(), cap
+            assert (h[:32] == util.GUARD_BYTE).all() and (h[32 + k * 32:] == util.GUARD_BYTE).all(), cap
+
+
 def test_covered_windows_are_the_mark_sinks(engine, cupboard):
     """nofir_w4_s2 on the OOK file, which has no NaN: with every threshold 0.001 and min_len 1 a window is covered by a burst iff one of
     its norms is >= 0.001, which is when the mark sink under -range 0.001:0.01 writes 1"""

@@ -283,6 +283,30 @@ def test_overflow_keeps_the_prefix_and_the_guards(engine, world):
             assert (hbuf[:lead] == util.GUARD_BYTE).all() and (hbuf[lead + k * 56:] == util.GUARD_BYTE).all()
 
 
+@pytest.mark.parametrize("name", ["cf32_w4", "cf32_w128"])
+def test_cap_ladder(engine, world, name):
+    """cap at the wave, round and off-by-one boundaries of the ballot rank every record passes through (63 ... 65, 255 ... 257), at found
+    and past it: the list is the twin's first min(found, cap) records byte for byte, found is the twin's, and the guard bytes in front of
+    and behind the list are intact.  A host source into a host list and a device source into a device list, where the kernels store."""
+    import torch
+    plan, data, dev, norms, n, spec = world(name)
+    W = spec[3]["width"]
+    thr = threshold_sets(norms)["median"]
+    full, found = engine.emissions_of(norms, thr, cap=n * W)
+    assert found > 257 and full.size == found                              # every cap of the ladder cuts the list
+    for cap in (63, 64, 65, 255, 256, 257, found, found + 1):
+        k = min(cap, found)
+        buf = np.full((cap + 2) * 56, util.GUARD_BYTE, dtype=np.uint8)
+        got = plan.emissions(data, thr, cap=cap, n_windows=n, out=buf[56:56 + cap * 56].view(EMISSION))
+        t = torch.full(((cap + 2) * 56,), util.GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        got_d = plan.emissions(dev, thr, cap=cap, n_windows=n, out=t[56:56 + cap * 56])
+        torch.cuda.synchronize()
+        for g, h in ((got, buf), (got_d, t.cpu().numpy())):
+            assert g[1] == found and g[0].shape[0] == k, cap
+            assert h[56:56 + k * 56].tobytes() == full[:k].tobytes(), cap
+            assert (h[:56] == util.GUARD_BYTE).all() and (h[56 + k * 56:] == util.GUARD_BYTE).all(), cap
+
+
 def test_relation_to_the_burst_list(engine, world):
     """min_len = min_cells = 1: every on cell lies in exactly one emission, so the cells of the list sum to the burst list's on_counts;
     at W = 1 an emission is a burst, field for field"""
