@@ -1999,3 +1999,136 @@ def gen_long_stretches(n, stretch=1 << 14):
     """offsets of the four stretches of a long call that are held to the oracle: its first and last samples and two inner stretches,
     the second of them across the end of the grid's first pass (sample 2^24)"""
     return [0, n // 3, (1 << 24) - stretch + 2048, n - stretch]
+
+
+# ------------------------------------------------------------------ designed on/off shapes (test_emission_shapes_cpu.py, test_gpu_emission_shapes.py)
+#
+# Boolean masks [n windows, W bins] on which a tiled connected-component labelling goes wrong, and the cf32 stream that plants one:
+# a window that is the inverse DFT of a row of levels has exactly those levels as its norms, up to the transform's rounding.
+
+EMISSIONS_TILE_COLS = 256                        # kEmissionsTileCols: a tile of the emission kernels is at most this many bins wide
+
+
+def emissions_tile_rows(W):
+    """emissions_tile_rows of qd_emissions.h: 8 rows at W >= 256, 16 at 128, 512 at 4, 1024 at 2 and 1"""
+    return 2048 // (2 * ((min(int(W), EMISSIONS_TILE_COLS) + 1) // 2))
+
+
+def serpentine(n, W, phase=0):
+    """Every other window is fully on; the window between two of them holds one cell, at bin 0 and bin W - 1 in turn: one emission that
+    sweeps every row in both directions.  phase 0: the odd windows are the full ones, so a full row is the last row above every
+    tile-row border (window k tr - 1, tr even); phase 1: the even ones, so a single connector cell is."""
+    m = np.zeros((n, W), dtype=bool)
+    m[(1 - phase) % 2::2] = True
+    for k, i in enumerate(range(phase % 2, n, 2)):
+        m[i, 0 if k % 2 == 0 else W - 1] = True
+    return m
+
+
+def spiral(n, W, gap=1):
+    """A single-armed rectangular spiral from (0, 0) inwards, clockwise, one cell thick, `gap` off cells between two turns: one
+    emission; with gap 1 the off cells are one 4-connected region too"""
+    m = np.zeros((n, W), dtype=bool)
+    step = gap + 1
+    t, b, l, r = 0, n - 1, 0, W - 1              # the rows and bins that keep `gap` cells away from what is drawn, the arm's own line apart
+    i = j = d = 0
+    m[0, 0] = True
+    while t <= b and l <= r:
+        if d == 0:
+            if r <= j:
+                break
+            m[i, j:r + 1] = True
+            j, t = r, i + step
+        elif d == 1:
+            if b <= i:
+                break
+            m[i:b + 1, j] = True
+            i, r = b, j - step
+        elif d == 2:
+            if l >= j:
+                break
+            m[i, l:j + 1] = True
+            j, b = l, i - step
+        else:
+            if t >= i:
+                break
+            m[t:i + 1, j] = True
+            i, l = t, j + step
+        d = (d + 1) % 4
+    return m
+
+
+def rings(n, W):
+    """The cells whose distance to the border is even: nested closed rings, none touching another, each around the next.  Ring d (d even)
+    spans windows d ... n - 1 - d and bins d ... W - 1 - d, so the innermost ends first."""
+    i, b = np.arange(n)[:, None], np.arange(W)[None, :]
+    return np.minimum(np.minimum(i, n - 1 - i), np.minimum(b, W - 1 - b)) % 2 == 0
+
+
+def comb_lengths(n, W, seed):
+    """the tooth lengths of comb(n, W, seed), one per even bin: seeded, 1 ... n - 3, the greatest exactly once and not at bin 0"""
+    rng = np.random.default_rng(seed)
+    ln = rng.integers(1, n - 3, (W + 1) // 2)    # 1 ... n - 4
+    ln[int(rng.integers(1, ln.size))] = n - 3
+    return ln
+
+
+def comb(n, W, seed):
+    """Window 0 is off, window 1 a full spine, and from every even bin a tooth of comb_lengths hangs down from window 2: one emission,
+    which stays open through a seam as many cells of one root that are no neighbours of each other, and which ends where its longest
+    tooth ends, in window n - 2 at that tooth's bin"""
+    m = np.zeros((n, W), dtype=bool)
+    m[1] = True
+    for k, ln in enumerate(comb_lengths(n, W, seed)):
+        m[2:2 + int(ln), 2 * k] = True
+    return m
+
+
+def corner_figures(n, W, tr):
+    """[(window k tr, bin 256 j, figure, mirrored)] of corners(n, W, tr): the interior tile corners in reading order, the figures
+    0, 1, 2 in rotation, mirrored on every second round"""
+    out = []
+    for k in range(1, (n - 1) // tr + 1):
+        for j in range(1, (W - 1) // EMISSIONS_TILE_COLS + 1):
+            out.append((k * tr, j * EMISSIONS_TILE_COLS, len(out) % 3, (len(out) // 3) % 2))
+    return out
+
+
+def corners(n, W, tr):
+    """At every interior tile corner (between windows k tr - 1 and k tr, bins 256 j - 1 and 256 j) one of three figures: 0, two cells
+    that meet only diagonally across the corner (two emissions of one cell); 1, an L through three of the four tiles; 2, a block of
+    2 x 2 cells, one in each tile.  Mirrored figures use the other diagonal."""
+    m = np.zeros((n, W), dtype=bool)
+    for i, b, fig, mirrored in corner_figures(n, W, tr):
+        left, right = (b, b - 1) if mirrored else (b - 1, b)
+        if fig == 2:
+            m[i - 1:i + 1, b - 1:b + 1] = True
+        else:
+            m[i - 1, left] = m[i, right] = True
+            if fig == 1:
+                m[i, left] = True
+    return m
+
+
+def checker(n, W):
+    """(window + bin) even: every on cell is an emission of its own, and every slot (pair of bins) of every row holds a root"""
+    return (np.arange(n)[:, None] + np.arange(W)[None, :]) % 2 == 0
+
+
+def shape_levels(mask, seed):
+    """f32 levels of a mask: seeded integers 1 ... 3 where it is on, 0 where it is off"""
+    rng = np.random.default_rng(seed)
+    return np.where(mask, rng.integers(1, 4, mask.shape), 0).astype(np.float32)
+
+
+def tone_stream(mask_levels):
+    """The cf32 bytes of n + 1 windows of W samples for f32 levels [n, W] (0: off): window i is the inverse DFT, normalised by 1 / W, of
+    row i laid in the norms sink's fftshifted order (column o is frequency o ^ W/2), so that the norm of cell (i, o) is its level and
+    an off cell's is the transform's rounding alone; the trailing window is zeros, as impulse_stream's.  W is a power of two."""
+    lv = np.ascontiguousarray(mask_levels, dtype=np.float32)
+    n, W = lv.shape
+    assert W >= 2 and W & (W - 1) == 0
+    x = np.fft.ifft(lv.astype(np.float64)[:, np.arange(W) ^ (W // 2)], axis=1)
+    out = np.zeros((n + 1, W, 2), dtype=np.float32)
+    out[:-1, :, 0], out[:-1, :, 1] = x.real, x.imag
+    return out.tobytes()
