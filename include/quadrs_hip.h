@@ -918,6 +918,68 @@ int qd_plan_emissions  (qd_plan *plan, const void *src, int src_mem, uint64_t sr
                         uint64_t first_window, uint64_t n_windows, const float *thresholds, uint64_t min_len, uint64_t min_cells,
                         qd_emission *list, uint64_t cap, uint64_t *found, int out_mem, void *stream);
 
+/* ------------------------------------------------------------------ cut list: shift, lowpass and decimate many stream ranges in one call
+ * The step behind the emission list: the IQ of each thing in the capture, moved to DC, filtered and decimated, all cuts in one call.
+ * Cut.  With D = decimate, T = taps, c = T - T/2 and valid = count D + T, the bytes of a cut are what the reference writes into
+ * buf[..count] on read_at(first, buf) of the chain  from F -> [shift shift_hz] -> lowpass -decimate D (size T) lowpass_hz  over the whole
+ * described stream (n_samples samples at sample_rate):
+ *   out[i] = sum_{j < jmax(i)} x[first D + i D + c + j] taps[j],  jmax(i) = min(T, valid - (i D + c)),
+ * ascending j, two separately rounded products and two adds per term, no FMA (qd_lowpass_block's arithmetic); x is the unpacked source
+ * sample times the reference's NCO multiplier of its ABSOLUTE index (qd_shift's arithmetic; no multiply at all with shift_hz == 0); taps
+ * is qd_lowpass_design(lowpass_hz, sample_rate, T).  The block's own tail truncation is part of the definition: the last ceil(c / D)
+ * outputs of a cut see a shortened filter, as the last outputs of a `write` block do; a caller who wants clean samples asks for that
+ * many more and drops them (qd_cut_of_emission adds them).  The SOURCE SPAN of a cut is samples [first D, first D + valid).
+ * NCO.  The exact product is split on the absolute row grid of 512 samples, as qd_shift splits it, and the second-order form is used for
+ * a cut iff fabs(ratio) * (double)(first D + valid) > 268435456.0: qd_shift's rule for a call over exactly that span.  So a cut's bytes
+ * depend on its six fields and the stream and on nothing else - not on its place in the list, its neighbours, tiles, batches,
+ * chunk_bytes or memory kinds - and equal qd_unpack -> qd_shift(abs_off = first D) -> qd_lowpass_block(valid) byte for byte.
+ * QD_MODE_FAST does not exist for cuts. */
+typedef struct qd_cut {
+    int64_t  shift_hz;        /* 0: no Shift stage at all (bit-exact path) */
+    uint64_t lowpass_hz, decimate, taps;
+    uint64_t first, count;    /* output samples [first, first + count) of the chain's stream */
+} qd_cut;                     /* 48 bytes */
+#define QD_CUT_MAX_DECIMATE 1024u
+#define QD_CUT_MAX_TAPS     4096u
+
+/* Validation, the same in both calls below and all of it ahead of any device call.  Cuts are checked in list order and the first
+ * offender is named in qd_last_error by its index; for one cut the order is: decimate 0, taps < 2, |shift_hz| >= sample_rate / 2 in
+ * integer division as Shift::new asserts (QD_ERR_PANIC, the plan's codes); decimate > QD_CUT_MAX_DECIMATE, taps > QD_CUT_MAX_TAPS,
+ * count > 2^31 (QD_ERR_UNSUPPORTED); first D + valid > n_samples - a cut is one FULL block - (QD_ERR_SHORT; no output byte is touched
+ * by the call); a span outside [src_first, src_first + src_count) (QD_ERR_INVALID, qd_cuts_run only).  A cut with count == 0 has no
+ * span: only its fields are checked, and it writes nothing.  n_cuts == 0 is fine. */
+
+/* host arithmetic only: offsets[k] = sum of count over cuts before k (offsets[n] = total; may be NULL); the union's hull of the
+ * source spans in *src_first / *src_count (0 / 0 without a span); validates as qd_cuts_run does */
+int qd_cuts_geometry(uint64_t sample_rate, uint64_t n_samples, const qd_cut *cuts, size_t n_cuts,
+                     uint64_t *offsets, uint64_t *src_first, uint64_t *src_count);
+/* src: raw bytes of source samples [src_first, +src_count) in `fmt`, as for qd_plan_run (device, host, pinned).  out: total qd_c32
+ * of out_mem memory, cut k at element offsets[k], packed.  options: chunk_bytes only (NULL: defaults).  Returns after
+ * everything is complete.  Device sources are read in place; of a host or pinned source only the union of the cuts' spans is copied
+ * up, in batches of at most chunk_bytes of source (0: 64 MiB; a batch holds at least one tile), a longer cut split at tile
+ * boundaries; host outputs come back batch by batch.  QD_ERR_INVALID also for an unknown format or memory kind and for a NULL
+ * cuts, src or out that would be read or written. */
+int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem,
+                uint64_t src_first, uint64_t src_count, const qd_cut *cuts, size_t n_cuts,
+                qd_c32 *out, int out_mem, const qd_plan_options *options, void *stream);
+
+/* Emission -> cut: host arithmetic in integers.  desc is the one-stage QD_EPI_NORMS_F32 desc the list was made from, first_window the
+ * first_window of that qd_plan_emissions call.  With sr = sample_rate, D0 = decimate with a lowpass else 1, T0 = taps with a lowpass
+ * else 0, R = sr / D0, W = width, S = stride, f0 = shift_hz with a shift else 0, fdiv / cdiv floor / ceiling division of signed integers:
+ *   nu = fdiv((lo + hi - W) R + W, 2 W)            the centre of bins lo ... hi at the sink's rate, halves rounded up
+ *   s = (f0 - nu) mod sr in [0, sr); hs = sr / 2; s >= hs: s -= sr; then s <= -hs: s = 1 - hs;  shift_hz = s (the emission lands on DC)
+ *   lowpass_hz = max(1, cdiv((hi - lo + 1 + 2 guard_bins) R, 2 W))
+ *   decimate = clamp(sr / (2 oversample lowpass_hz), 1, max_decimate)     (max_decimate 0: QD_CUT_MAX_DECIMATE)
+ *   taps = rule.taps, or with rule.taps == 0 min(QD_CUT_MAX_TAPS, max(40, 8 decimate))
+ *   a = (first_window + e.first) S D0;  b = min(n_samples, (first_window + e.last) S D0 + W D0 + T0)
+ *   first = max(0, fdiv(a - T, D) - pad);  end = cdiv(max(b - T, 0), D) + pad + cdiv(T - T/2, D)
+ *   count = max(0, min(end, fdiv(n_samples - T, D)) - first)
+ * QD_ERR_INVALID: NULL, a wrong struct_size of desc or rule, oversample == 0, a non-zero rule.taps < 2, lo > hi or hi >= W, a desc
+ * with sample_rate 0, stride 0 or (with a lowpass) decimate 0.  QD_ERR_UNSUPPORTED: sr >= 2^48, or a window index, stride or width
+ * that puts b (before the min) at or past 2^62.  Cascade plans have no single (f0, D0) and are out of scope. */
+typedef struct qd_cut_rule { uint32_t struct_size, guard_bins, oversample, pad; uint64_t taps, max_decimate; } qd_cut_rule;
+int qd_cut_of_emission(const qd_chain_desc *desc, uint64_t first_window, const qd_emission *e, const qd_cut_rule *rule, qd_cut *cut);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

@@ -35,6 +35,7 @@ SYMBOLS = [
     "qd_picture_geometry", "qd_picture_color", "qd_picture_init", "qd_picture_fold", "qd_plan_picture",
     "qd_bursts_init", "qd_bursts_fold", "qd_bursts_finish", "qd_plan_bursts",
     "qd_emissions_init", "qd_emissions_fold", "qd_emissions_finish", "qd_plan_emissions",
+    "qd_cuts_geometry", "qd_cuts_run", "qd_cut_of_emission",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
@@ -45,6 +46,7 @@ BANDS_MAX, BAND_NONE = 255, 0xffffffff
 PICTURE_MAX_WORKSPACE = 1 << 30
 BURSTS_WORDS, BURSTS_MAX_WORKSPACE = 3, 1 << 30
 EMISSIONS_WORDS, EMISSIONS_MAX_WORKSPACE, EMISSIONS_MAX_WIDTH = 8, 1 << 30, 4096
+CUT_MAX_DECIMATE, CUT_MAX_TAPS = 1024, 4096
 STAGE_SHIFT, STAGE_LOWPASS = 1, 2
 MAX_STAGES = 8
 
@@ -90,6 +92,24 @@ class PictureDesc(C.Structure):
     """qd_picture_desc: the page of a waterfall picture."""
     _fields_ = [("struct_size", C.c_uint32), ("px_width", C.c_uint32), ("px_height", C.c_uint32), ("stretch", C.c_uint32), ("scan", C.c_uint32),
                 ("scale", C.c_float)]
+
+
+class Cut(C.Structure):
+    """qd_cut: shift, lowpass, decimation and output range [first, first + count) of one cut, 48 bytes."""
+    _fields_ = [("shift_hz", C.c_int64), ("lowpass_hz", C.c_uint64), ("decimate", C.c_uint64), ("taps", C.c_uint64),
+                ("first", C.c_uint64), ("count", C.c_uint64)]
+
+
+class CutRule(C.Structure):
+    """qd_cut_rule: how qd_cut_of_emission sizes a cut."""
+    _fields_ = [("struct_size", C.c_uint32), ("guard_bins", C.c_uint32), ("oversample", C.c_uint32), ("pad", C.c_uint32),
+                ("taps", C.c_uint64), ("max_decimate", C.c_uint64)]
+
+
+class Emission(C.Structure):
+    """qd_emission, 56 bytes (engine.EMISSION_DTYPE is the same layout)."""
+    _fields_ = [("first", C.c_uint64), ("last", C.c_uint64), ("cells", C.c_uint64), ("peak_at", C.c_uint64), ("lo", C.c_uint32), ("hi", C.c_uint32),
+                ("end_bin", C.c_uint32), ("peak_bin", C.c_uint32), ("peak", C.c_float), ("flags", C.c_uint32)]
 
 
 class Stage(C.Structure):
@@ -245,6 +265,9 @@ def lib():
             "qd_emissions_fold": (i32, [vp, C.c_uint32, vp, u64, u64, u64, vp, u64, vp, u64, C.POINTER(u64)]),
             "qd_emissions_finish": (i32, [vp, C.c_uint32, u64, u64, vp, u64, C.POINTER(u64)]),
             "qd_plan_emissions": (i32, [vp, vp, i32, u64, u64, u64, u64, vp, u64, u64, vp, u64, C.POINTER(u64), i32, vp]),
+            "qd_cuts_geometry": (i32, [u64, u64, vp, sz, vp, C.POINTER(u64), C.POINTER(u64)]),
+            "qd_cuts_run": (i32, [i32, u64, u64, vp, i32, u64, u64, vp, sz, vp, i32, C.POINTER(PlanOptions), vp]),
+            "qd_cut_of_emission": (i32, [C.POINTER(ChainDesc), u64, C.POINTER(Emission), C.POINTER(CutRule), C.POINTER(Cut)]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

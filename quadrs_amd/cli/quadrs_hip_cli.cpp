@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS, OP_EMISSIONS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS, OP_EMISSIONS, OP_CUTS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -115,6 +115,7 @@ struct Op {
     bool has_level = false, has_times = false; float level = 0, times = 1; std::string levels_file;   // bursts (-level X | -levels FILE) [-times K]
     uint64_t min_len = 1, cap = 1048576, print_n = 0;                   // bursts [-min 1] [-cap 1048576] [-print 0]
     uint64_t min_cells = 1;                                             // emissions [-cells 1]
+    std::string list_file; uint64_t first_window = 0, guard = 1, oversample = 2, cut_taps = 0, cut_pad = 1;   // cuts -list FILE [-first-window 0] [-guard 1] [-oversample 2] [-taps 0] [-pad 1]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
     int sink_window = 0;                                                // -window bh|rect of the window-plan verbs (qd_chain_desc.windowing)
 };
@@ -431,6 +432,37 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             if (f) op.print_n = parse_si_u64(v);
             ensure_empty(m);
             op.prefix = next(em ? "'emissions' requires a prefix argument" : "'bursts' requires a prefix argument");
+        } else if (cmd == "cuts") {
+            // not in the reference's grammar: the IQ of every record of an `emissions` list, cut out of the source in one call (qd_cuts_run).
+            // The chain words in front describe the plan the list came from, -width and -stride its windows
+            auto m = no_duplicates(raw);
+            op.kind = OP_CUTS;
+            std::string v = take(m, "width", &f);
+            if (!f) bail("cuts requires -width, the width of the plan the list came from");
+            op.width = (size_t)parse_si_u64(v);
+            v = take(m, "stride", &f);
+            op.stride = f ? parse_si_u64(v) : op.width;
+            v = take(m, "list", &f);
+            if (!f) bail("cuts requires -list FILE.emissions");
+            op.list_file = v;
+            auto u32 = [&](const char *flag, uint64_t deflt, uint64_t least) {
+                const std::string t = take(m, flag, &f);
+                if (!f) return deflt;
+                const uint64_t k = parse_si_u64(t);
+                if (k < least || k > 0xffffffffull) bail(std::string("cuts -") + flag + " takes a number from " + std::to_string(least) + " to 4294967295");
+                return k;
+            };
+            v = take(m, "first-window", &f);
+            if (f) op.first_window = parse_si_u64(v);
+            op.guard = u32("guard", 1, 0);
+            op.oversample = u32("oversample", 2, 1);
+            op.cut_pad = u32("pad", 1, 0);
+            v = take(m, "taps", &f);
+            if (f) { op.cut_taps = parse_si_u64(v); if (op.cut_taps == 1 || op.cut_taps > QD_CUT_MAX_TAPS) bail("cuts -taps takes 0 (from the decimation) or 2 ... 4096"); }
+            v = take(m, "print", &f);
+            if (f) op.print_n = parse_si_u64(v);
+            ensure_empty(m);
+            op.prefix = next("'cuts' requires a prefix argument");
         } else if (cmd == "picture") {
             // not in the reference's grammar: the waterfall its conrod front end renders (src/ui/mod.rs:294-412) as a binary PPM.  -width 8,
             // -stride 1 and -stretch 4 are its Params (:72-76) and 2.29 its scale (:353); -scan 0, no marker columns, is not: its default of 1
@@ -1534,6 +1566,78 @@ void do_list(const Samples &s, const Op &sink, const ChainSpec *cs) {
 void do_bursts(const Samples &s, const Op &sink, const ChainSpec *cs) { do_list<BurstsVerb>(s, sink, cs); }
 void do_emissions(const Samples &s, const Op &sink, const ChainSpec *cs) { do_list<EmissionsVerb>(s, sink, cs); }
 
+// The `cuts` sink: the IQ of every record of an emission list (-list FILE.emissions, what `emissions` wrote for the same chain words, -width
+// and -stride; -first-window N when the list was made from window N on).  Each record becomes a cut by qd_cut_of_emission (-guard bins on
+// either side, an output rate of -oversample x twice the lowpass, -taps, -pad extra outputs on either side): shifted so that the emission
+// lands on DC, lowpassed to its width and decimated, always out of the SOURCE samples.  One file PREFIX.NNNNNN.sr{rate / decimate}.cf32
+// per record with outputs (NNNNNN the record's place in the list), one header line, and with -print K the first K cuts as
+// `shift_hz lowpass_hz decimate taps first count`.  All cuts run in one qd_cuts_run; with QUADRS_HIP_NO_FUSE=1 one by one through
+// qd_unpack, qd_shift and qd_lowpass_block: the same bytes.  A cascade has no single shift and decimation to work the cut out from.
+void do_cuts(const Op &sink, const ChainSpec &cs) {
+    if (cs.cascade) bail("cuts takes the chain the list came from as from [shift] [lowpass]: a cascade has no single shift and decimation to place an emission by");
+    if (g_gpus > 1) bail("cuts run on one device: every cut reads the one source (run it without -gpus)");
+    FILE *fp = fopen(sink.list_file.c_str(), "rb");
+    if (!fp) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + sink.list_file);
+    std::vector<qd_emission> list;
+    {
+        qd_emission e;
+        size_t got;
+        while ((got = fread(&e, 1, sizeof e, fp)) == sizeof e) list.push_back(e);
+        fclose(fp);
+        if (got) bail("cuts -list takes a file of whole qd_emission records (56 bytes each): " + sink.list_file);
+    }
+    ChainSource in(cs);
+    qd_chain_desc d;
+    std::vector<qd_stage> stages;
+    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, &d, &stages);
+    qd_cut_rule rule{};
+    rule.struct_size = sizeof rule;
+    rule.guard_bins = (uint32_t)sink.guard; rule.oversample = (uint32_t)sink.oversample; rule.pad = (uint32_t)sink.cut_pad; rule.taps = sink.cut_taps;
+    std::vector<qd_cut> cuts(list.size());
+    for (size_t k = 0; k < list.size(); ++k) qd_check(qd_cut_of_emission(&d, sink.first_window, &list[k], &rule, &cuts[k]), ("record " + std::to_string(k)).c_str());
+    std::vector<uint64_t> offs(cuts.size() + 1);
+    uint64_t lo = 0, n = 0;
+    qd_check(qd_cuts_geometry(d.sample_rate, d.n_samples, cuts.data(), cuts.size(), offs.data(), &lo, &n), "cuts");
+    std::vector<qd_c32> out((size_t)offs[cuts.size()]);
+    uint64_t made = 0;
+    if (!getenv("QUADRS_HIP_NO_FUSE")) {
+        int mem = QD_MEM_HOST;
+        const void *src = out.empty() ? nullptr : in.resident(&mem);
+        qd_check(qd_cuts_run(d.format, d.sample_rate, d.n_samples, src, mem, 0, d.n_samples, cuts.data(), cuts.size(), out.data(), QD_MEM_HOST, nullptr, nullptr), "cuts");
+    } else {
+        std::vector<qd_c32> raw;
+        std::vector<float> taps;
+        const uint64_t pb = qd_pair_bytes(d.format);
+        for (size_t k = 0; k < cuts.size(); ++k) {
+            const qd_cut &c = cuts[k];
+            if (!c.count) continue;
+            const uint64_t a = c.first * c.decimate, valid = c.count * c.decimate + c.taps;
+            raw.resize((size_t)valid);
+            if (in.from_gen) qd_check(qd_gen(in.op.cos.data(), in.op.cos.size(), in.op.sample_rate, a, (size_t)valid, raw.data(), QD_MEM_HOST), "gen");
+            else qd_check(qd_unpack(d.format, in.data->p + a * pb, (size_t)valid, raw.data(), QD_MEM_HOST), "unpack");
+            if (c.shift_hz) qd_check(qd_shift(raw.data(), (size_t)valid, a, qd_shift_ratio(c.shift_hz, d.sample_rate), QD_MEM_HOST), "shift");
+            taps.resize((size_t)c.taps);
+            qd_check(qd_lowpass_design(c.lowpass_hz, d.sample_rate, (size_t)c.taps, taps.data()), "lowpass_design");
+            size_t produced = 0;
+            qd_check(qd_lowpass_block(taps.data(), (size_t)c.taps, c.decimate, raw.data(), (size_t)valid, out.data() + offs[k], (size_t)c.count, &produced, QD_MEM_HOST), "lowpass");
+            if (produced != c.count) bail("cut " + std::to_string(k) + ": " + std::to_string(produced) + " outputs, not " + std::to_string(c.count));
+        }
+    }
+    for (size_t k = 0; k < cuts.size(); ++k) {
+        if (!cuts[k].count) continue;
+        char num[32];
+        snprintf(num, sizeof num, ".%06zu", k);
+        write_new_file(sink.prefix + num + ".sr" + std::to_string(d.sample_rate / cuts[k].decimate) + ".cf32", out.data() + offs[k], (size_t)cuts[k].count * sizeof(qd_c32));
+        ++made;
+    }
+    printf("cuts width=%zu stride=%llu first_window=%llu guard=%llu oversample=%llu taps=%llu pad=%llu records=%zu files=%llu samples=%llu\n", (size_t)sink.width,
+           (unsigned long long)sink.stride, (unsigned long long)sink.first_window, (unsigned long long)sink.guard, (unsigned long long)sink.oversample,
+           (unsigned long long)sink.cut_taps, (unsigned long long)sink.cut_pad, cuts.size(), (unsigned long long)made, (unsigned long long)offs[cuts.size()]);
+    for (size_t k = 0; k < std::min<uint64_t>(cuts.size(), sink.print_n); ++k)
+        printf("%lld %llu %llu %llu %llu %llu\n", (long long)cuts[k].shift_hz, (unsigned long long)cuts[k].lowpass_hz, (unsigned long long)cuts[k].decimate,
+               (unsigned long long)cuts[k].taps, (unsigned long long)cuts[k].first, (unsigned long long)cuts[k].count);
+}
+
 // The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
 // it out (src/ui/mod.rs:294-412; the colour map is the project's own statement of palette 0.5's HSV -> RGB, include/quadrs_hip.h), written
 // as PREFIX.sr{rate}.w{W}.{pxw}x{pxh}.ppm: binary P6, maxval 255, top row first — the buffer as it lies.  A chain the library fuses paints
@@ -1624,6 +1728,7 @@ void usage() {
             "   bands [-width 128] [-stride =width] (-bins LO:HI[,LO:HI...] | -split K) [-pick] FILENAME_PREFIX \\\n"
             "  bursts [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
             "emissions [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cells 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
+            "    cuts -width W [-stride =width] -list FILE.emissions [-first-window 0] [-guard 1] [-oversample 2] [-taps 0] [-pad 1] [-print 0] FILENAME_PREFIX \\\n"
             " picture [-width 8] [-stride 1] -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29] [-overwrite no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
@@ -1696,6 +1801,11 @@ int main(int argc, char **argv) {
                     else printf("emissions width=%zu stride=%llu levels=%s", op.width, (unsigned long long)op.stride, op.levels_file.c_str());
                     printf(" times=%.9g min=%llu cells=%llu cap=%llu print=%llu\n", op.times, (unsigned long long)op.min_len, (unsigned long long)op.min_cells,
                            (unsigned long long)op.cap, (unsigned long long)op.print_n);
+                    break;
+                case OP_CUTS:
+                    printf("cuts width=%zu stride=%llu list=%s first_window=%llu guard=%llu oversample=%llu taps=%llu pad=%llu print=%llu\n", op.width, (unsigned long long)op.stride,
+                           op.list_file.c_str(), (unsigned long long)op.first_window, (unsigned long long)op.guard, (unsigned long long)op.oversample,
+                           (unsigned long long)op.cut_taps, (unsigned long long)op.cut_pad, (unsigned long long)op.print_n);
                     break;
                 case OP_PICTURE:
                     printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g overwrite=%d\n", op.width, (unsigned long long)op.stride, op.px_w, op.px_h,
@@ -1783,6 +1893,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("emissions requires an input");
                 cs.cascade = !chain_clean;
                 do_emissions(*samples, op, &cs);
+                break;
+            case OP_CUTS:
+                if (!samples) bail("cuts requires an input");
+                cs.cascade = !chain_clean;
+                do_cuts(op, cs);
                 break;
             case OP_PICTURE:
                 if (!samples) bail("picture requires an input");

@@ -41,6 +41,7 @@
 #include "qd_bands.h"
 #include "qd_bursts.h"
 #include "qd_emissions.h"
+#include "qd_cuts.h"
 #include "qd_paint.h"
 
 using namespace qd;
@@ -4719,6 +4720,148 @@ int qd_plan_emissions(qd_plan *p, const void *src, int src_mem, uint64_t src_fir
         }
     }
     return c.home(rc);
+}
+
+// ------------------------------------------------------------------ cut list (include/quadrs_hip.h, "cut list"; qd_cuts.h, qd_cuts_plan.h)
+
+int qd_cuts_geometry(uint64_t sample_rate, uint64_t n_samples, const qd_cut *cuts, size_t n_cuts, uint64_t *offsets, uint64_t *src_first, uint64_t *src_count) {
+    std::string err;
+    if (const int rc = cuts_check(sample_rate, n_samples, cuts, n_cuts, false, 0, 0, offsets, src_first, src_count, &err)) return fail(rc, "%s", err.c_str());
+    return QD_OK;
+}
+
+int qd_cut_of_emission(const qd_chain_desc *desc, uint64_t first_window, const qd_emission *e, const qd_cut_rule *rule, qd_cut *cut) {
+    std::string err;
+    if (const int rc = cut_of_emission(desc, first_window, e, rule, cut, &err)) return fail(rc, "%s", err.c_str());
+    return QD_OK;
+}
+
+int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                const qd_cut *cuts, size_t n_cuts, qd_c32 *out, int out_mem, const qd_plan_options *options, void *stream) {
+    if (fmt < 0 || fmt > 3) return fail(QD_ERR_INVALID, "unknown format %d", fmt);
+    if (src_mem < QD_MEM_HOST || src_mem > QD_MEM_HOST_PINNED || out_mem < QD_MEM_HOST || out_mem > QD_MEM_HOST_PINNED) return fail(QD_ERR_INVALID, "unknown memory kind");
+    qd_plan_options opt;
+    if (const int rc = check_options(options, &opt)) return rc;
+    const uint64_t bps = (uint64_t)bps_of(fmt);
+    if (src_count > (~0ull - src_first) || src_count > (1ull << 60)) return fail(QD_ERR_INVALID, "the slab [%llu, +%llu) is no range of samples", (unsigned long long)src_first, (unsigned long long)src_count);
+    std::vector<uint64_t> offs(n_cuts + 1);
+    std::string err;
+    if (const int rc = cuts_check(sample_rate, n_samples, cuts, n_cuts, true, src_first, src_count, offs.data(), nullptr, nullptr, &err)) return fail(rc, "%s", err.c_str());
+    if (offs[n_cuts] == 0) return QD_OK;
+    if (!src || !out) return fail(QD_ERR_INVALID, "NULL buffer");
+
+    // the job table: one entry per cut; taps designed once per (lowpass_hz, taps), a lane table per distinct shift
+    std::vector<CutJob> jobs(n_cuts);
+    std::vector<float> taps_h;
+    std::vector<double> lane_ratio;
+    std::map<std::pair<uint64_t, uint64_t>, uint64_t> taps_of;
+    std::map<int64_t, uint64_t> lane_of;
+    for (size_t k = 0; k < n_cuts; ++k) {
+        const qd_cut &c = cuts[k];
+        CutJob &j = jobs[k];
+        j = CutJob{};
+        j.D = (uint32_t)c.decimate; j.T = (uint32_t)c.taps;
+        j.span0 = c.first * c.decimate; j.valid = c.count * c.decimate + c.taps;
+        if (c.count == 0) continue;
+        auto t = taps_of.find({c.lowpass_hz, c.taps});
+        if (t == taps_of.end()) {
+            t = taps_of.insert({{c.lowpass_hz, c.taps}, (uint64_t)taps_h.size()}).first;
+            taps_h.resize(taps_h.size() + c.taps);
+            design_taps(c.lowpass_hz, sample_rate, c.taps, taps_h.data() + t->second);
+        }
+        j.taps_at = t->second;
+        if (c.shift_hz != 0) {
+            j.ratio = qd_shift_ratio(c.shift_hz, sample_rate);
+            auto l = lane_of.find(c.shift_hz);
+            if (l == lane_of.end()) { l = lane_of.insert({c.shift_hz, (uint64_t)lane_ratio.size()}).first; lane_ratio.push_back(j.ratio); }
+            j.lane_at = l->second * kCutsNcoRow;
+            j.flags = kCutShift | ((std::fabs(j.ratio) * (double)(j.span0 + j.valid) > 268435456.0) ? kCutSecondOrder : 0u);      // qd_shift's rule over the span
+        }
+    }
+    std::vector<CutBatch> batches;
+    cuts_batches(cuts, n_cuts, std::max<uint64_t>(1, (opt.chunk_bytes ? opt.chunk_bytes : kCutsDefaultChunk) / bps), &batches);
+
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const void *anchor = src_mem == QD_MEM_DEVICE ? src : (out_mem == QD_MEM_DEVICE ? (const void *)out : nullptr);
+    if (anchor) {                                        // run where the caller's device buffer lives
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, anchor) == hipSuccess) dev = at.device;
+        else (void)hipGetLastError();
+    }
+    DeviceGuard guard(dev);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    WsLease ws(st);
+    if (ws.rc) return ws.rc;
+    const bool src_dev = src_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
+    const size_t n_lane = lane_ratio.size();
+    const size_t jobs_b = (jobs.size() * sizeof(CutJob) + 15) & ~(size_t)15, taps_b = (taps_h.size() * 4 + 15) & ~(size_t)15, ratio_b = (n_lane * 8 + 15) & ~(size_t)15;
+    void *tab_d = nullptr, *lane_d = nullptr;
+    int rc = ws.get(2, jobs_b + taps_b + ratio_b, &tab_d); if (rc) return rc;
+    rc = ws.get(3, std::max<size_t>(n_lane, 1) * kCutsNcoRow * sizeof(double2), &lane_d); if (rc) return rc;
+    char *const tab = static_cast<char *>(tab_d);
+    HIPCHK(hipMemcpyAsync(tab, jobs.data(), jobs.size() * sizeof(CutJob), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(tab + jobs_b, taps_h.data(), taps_h.size() * 4, hipMemcpyHostToDevice, st));
+    if (n_lane) HIPCHK(hipMemcpyAsync(tab + jobs_b + taps_b, lane_ratio.data(), n_lane * 8, hipMemcpyHostToDevice, st));
+    const CutJob *jobs_d = reinterpret_cast<const CutJob *>(tab);
+    const float *taps_d = reinterpret_cast<const float *>(tab + jobs_b);
+    const double *ratio_d = reinterpret_cast<const double *>(tab + jobs_b + taps_b);
+
+    const void *fn = fmt == 0 ? reinterpret_cast<const void *>(k_cuts<0>) : fmt == 1 ? reinterpret_cast<const void *>(k_cuts<1>)
+                   : fmt == 2 ? reinterpret_cast<const void *>(k_cuts<2>) : reinterpret_cast<const void *>(k_cuts<3>);
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCutsLdsBytes));
+
+    std::vector<std::vector<CutTile>> kept;              // the tile tables stay alive until their copies are done
+    kept.reserve(batches.size());
+    std::vector<qd_c32> down;
+    bool first_batch = true;
+    for (const CutBatch &b : batches) {
+        kept.emplace_back();
+        std::vector<CutTile> &tiles = kept.back();
+        cuts_tiles(cuts, b, out_dev, offs.data(), src_dev, src_first, &tiles);
+        const uint32_t n_tiles = (uint32_t)tiles.size();
+        const size_t tiles_b = ((size_t)n_tiles * sizeof(CutTile) + 31) & ~(size_t)31;
+        void *batch_d = nullptr, *in_d = nullptr, *out_d = nullptr;
+        rc = ws.get(4, tiles_b + (size_t)n_tiles * kCutsTileRows * sizeof(RowBase), &batch_d); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(batch_d, tiles.data(), (size_t)n_tiles * sizeof(CutTile), hipMemcpyHostToDevice, st));
+        const CutTile *tiles_d = static_cast<const CutTile *>(batch_d);
+        RowBase *rows_d = reinterpret_cast<RowBase *>(static_cast<char *>(batch_d) + tiles_b);
+        const uint8_t *in = static_cast<const uint8_t *>(src);
+        if (!src_dev) {                                  // only the union of the batch's reads goes up
+            rc = ws.get(0, b.src_samples * bps + 16, &in_d); if (rc) return rc;
+            for (const CutSpan &sp : b.spans)
+                HIPCHK(hipMemcpyAsync(static_cast<char *>(in_d) + sp.at * bps, static_cast<const char *>(src) + (sp.first - src_first) * bps, sp.count * bps,
+                                      hipMemcpyHostToDevice, st));
+            in = static_cast<const uint8_t *>(in_d);
+        }
+        float2 *o = reinterpret_cast<float2 *>(out);
+        if (!out_dev) {
+            rc = ws.get(1, b.out_samples * 8, &out_d); if (rc) return rc;
+            o = static_cast<float2 *>(out_d);
+        }
+        const uint32_t lanes = first_batch ? (uint32_t)n_lane : 0u;
+        const uint64_t table_threads = (uint64_t)n_tiles * kCutsTileRows + (uint64_t)lanes * kCutsNcoRow;
+        hipLaunchKernelGGL(k_cuts_tables, dim3((uint32_t)((table_threads + 255) / 256)), dim3(256), 0, st, jobs_d, tiles_d, n_tiles, rows_d, ratio_d, lanes,
+                           static_cast<double2 *>(lane_d));
+        const RowBase *rows_c = rows_d;
+        const double2 *lane_c = static_cast<const double2 *>(lane_d);
+        switch (fmt) {
+        case 0: hipLaunchKernelGGL(k_cuts<0>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;
+        case 1: hipLaunchKernelGGL(k_cuts<1>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;
+        case 2: hipLaunchKernelGGL(k_cuts<2>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;
+        default: hipLaunchKernelGGL(k_cuts<3>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;
+        }
+        HIPCHK(hipGetLastError());
+        first_batch = false;
+        if (!out_dev) {                                  // the batch's outputs come down in one piece and are put in place here
+            down.resize(b.out_samples);
+            HIPCHK(hipMemcpyAsync(down.data(), out_d, b.out_samples * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (const CutPiece &p : b.pieces) memcpy(out + offs[p.cut] + p.first, down.data() + p.out_at, (size_t)p.count * 8);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return QD_OK;
 }
 
 int qd_device_alloc(size_t bytes, void **ptr) {

@@ -613,6 +613,74 @@ def emissions_of(norms, thresholds, min_len=1, min_cells=1, cap=None):
     return into[:min(found, into.size)], found
 
 
+CUT_DTYPE = np.dtype([("shift_hz", "<i8"), ("lowpass_hz", "<u8"), ("decimate", "<u8"), ("taps", "<u8"), ("first", "<u8"), ("count", "<u8")])      # qd_cut, 48 bytes
+
+
+def cut_rule(guard_bins=1, oversample=2, pad=1, taps=0, max_decimate=0):
+    """a qd_cut_rule: guard bins on either side of the emission's bins, output rate over twice the lowpass, extra outputs on either side,
+    the filter size (0: from the decimation) and the largest decimation (0: QD_CUT_MAX_DECIMATE)."""
+    return _ffi.CutRule(C.sizeof(_ffi.CutRule), int(guard_bins), int(oversample), int(pad), int(taps), int(max_decimate))
+
+
+def cut_of_emission(desc, first_window, emission, rule=None):
+    """qd_cut_of_emission (host arithmetic): the cut of one EMISSION_DTYPE record of a list made by a plan with ChainDesc `desc` (Plan.desc)
+    from window first_window on.  Returns a CUT_DTYPE scalar."""
+    rule = cut_rule() if rule is None else rule
+    e = _ffi.Emission.from_buffer_copy(np.asarray(emission, dtype=EMISSION_DTYPE).reshape(1).tobytes())
+    cut = _ffi.Cut()
+    check(lib().qd_cut_of_emission(C.byref(desc), int(first_window), C.byref(e), C.byref(rule), C.byref(cut)))
+    return np.frombuffer(bytes(cut), dtype=CUT_DTYPE)[0]
+
+
+def _cut_table(cuts):
+    a = np.ascontiguousarray(cuts, dtype=CUT_DTYPE).reshape(-1)
+    return a if a.size else np.zeros(1, dtype=CUT_DTYPE)[:0], int(np.asarray(cuts).reshape(-1).size)
+
+
+def cuts_geometry(sample_rate, n_samples, cuts):
+    """qd_cuts_geometry (host arithmetic): (offsets uint64[n + 1], src_first, src_count) of a CUT_DTYPE list."""
+    a, n = _cut_table(cuts)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    lo, cnt = C.c_uint64(), C.c_uint64()
+    check(lib().qd_cuts_geometry(int(sample_rate), int(n_samples), _np_ptr(a) if n else None, n, _np_ptr(offs), C.byref(lo), C.byref(cnt)))
+    return offs, lo.value, cnt.value
+
+
+def cuts_run(fmt, sample_rate, n_samples, src, cuts, src_first=0, src_count=None, pinned=False, out=None, chunk_bytes=0, stream=None):
+    """qd_cuts_run: every cut of a CUT_DTYPE list in one call.  src holds the raw bytes of source samples [src_first, +src_count): bytes /
+    a numpy array (host; pinned=True for a PinnedBuffer array) or a torch CUDA tensor (device).  out: None (host results), a PinnedBuffer
+    array (with pinned=True) or a torch CUDA tensor of at least total x 8 bytes (device results).  Returns one float32 (count, 2) array per
+    cut: numpy views of one host buffer, or views of `out` for a torch tensor."""
+    a, n = _cut_table(cuts)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    lo, cnt = C.c_uint64(), C.c_uint64()
+    check(lib().qd_cuts_geometry(int(sample_rate), int(n_samples), _np_ptr(a) if n else None, n, _np_ptr(offs), C.byref(lo), C.byref(cnt)))
+    total = int(offs[n])
+    if _is_torch(src):
+        ptr, mem, have, keep = C.c_void_p(src.data_ptr()), MEM_DEVICE, src.numel() * src.element_size() // _FMT_BYTES.get(fmt, 1), src
+        st = _cur_stream() if stream is None else C.c_void_p(stream)
+    else:
+        keep = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+        ptr, mem, have = _np_ptr(keep), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), keep.size // _FMT_BYTES.get(fmt, 1)      # (an unknown format is the library's to refuse)
+        st = None if stream is None else C.c_void_p(stream)
+    src_count = have if src_count is None else int(src_count)
+    if out is not None and _is_torch(out):
+        import torch
+        flat, out_ptr, out_mem = out.view(-1).view(torch.float32), C.c_void_p(out.data_ptr()), MEM_DEVICE
+        assert flat.numel() >= 2 * total, "out is smaller than the cuts' total"
+        views = [flat[2 * int(offs[k]):2 * int(offs[k + 1])].view(-1, 2) for k in range(n)]
+    else:
+        flat = np.zeros(2 * max(total, 1), dtype=np.float32) if out is None else out.view(np.float32).reshape(-1)
+        assert flat.size >= 2 * total, "out is smaller than the cuts' total"
+        out_ptr, out_mem = _np_ptr(flat), (_ffi.MEM_HOST_PINNED if (pinned and out is not None) else MEM_HOST)
+        views = [flat[2 * int(offs[k]):2 * int(offs[k + 1])].reshape(-1, 2) for k in range(n)]
+    opts = plan_options(chunk_bytes=int(chunk_bytes))
+    check(lib().qd_cuts_run(int(fmt), int(sample_rate), int(n_samples), ptr, mem, int(src_first), src_count, _np_ptr(a) if n else None, n,
+                            out_ptr, out_mem, C.byref(opts), st))
+    del keep
+    return views
+
+
 def picture_desc(px_width, px_height, stretch=4, scan=0, scale=2.29):
     """a qd_picture_desc: the page of a waterfall picture.  stretch 4 and scale 2.29 are the reference's; scan 0 (no marker columns) is
     not: its default of 1 blackens every column."""
