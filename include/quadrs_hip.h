@@ -980,6 +980,53 @@ int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *s
 typedef struct qd_cut_rule { uint32_t struct_size, guard_bins, oversample, pad; uint64_t taps, max_decimate; } qd_cut_rule;
 int qd_cut_of_emission(const qd_chain_desc *desc, uint64_t first_window, const qd_emission *e, const qd_cut_rule *rule, qd_cut *cut);
 
+/* ------------------------------------------------------------------ symbol list: bucket digits and marks of many short streams in one call
+ * The step behind the cut list: every cut's digit string (`bucket -by freq 2`) or blank / non-blank rows (sparkfft, the input of
+ * qd_bits_scan), all cuts in one call.  A SEGMENT is elements [first, first + count) of a cf32 buffer, viewed as a stream of len = count.
+ * With width W (a power of two) and stride S >= 1, segment k yields one byte per FFT window:
+ *   QD_EPI_BUCKET2_U8  n_k = (count - W) / S windows (src/fft.rs:86).  Window r is Radix4 forward over samples [r S, r S + W); first is
+ *                      the sequential f32 sum of |X[j]|, ascending j < W/2 in un-shifted bin order, second that for j >= W/2; the byte is
+ *                      first < second ? 0 : 1 (a NaN compares false: 1).  The arithmetic of a QD_EPI_BUCKET2_U8 plan.
+ *   QD_EPI_MARK_U8     n_k = the trip count of `while i < len - W { ...; i += S }` (src/fft.rs:28,65) = ceil((count - W) / S).  The byte is 0
+ *                      when every |X| of the window is < min in f32 (min = range_min with has_range, else 0.08f), else 1; a NaN marks.
+ *   windowing == 1     sample j of every window is multiplied by qd_window_design(1, W)[j] as Complex<f32> x f32 ahead of the transform,
+ *                      exactly as qd_chain_desc.windowing does.
+ * SHORT SEGMENTS: a segment with count <= W has 0 windows and writes nothing.  This is the one departure from the reference, which
+ * underflows a u64 there (qd_plan_create answers QD_ERR_PANIC for such a stream): in a list of emissions a short cut is routine and
+ * must not fail the whole call.
+ * Outputs are packed: segment k's bytes sit at offsets[k], offsets[n] is the total.  A segment's bytes depend on its samples, W, S, the
+ * epilogue, min and the window, and on nothing else - not on its place in the list, its neighbours, tiles, batches or memory kinds.
+ * Segments may overlap, repeat and leave gaps.
+ * Validation, all of it ahead of any device call, in this order: NULL desc or a wrong struct_size, an epilogue other than the two,
+ * stride == 0, windowing outside {0, 1} (QD_ERR_INVALID); a width that is not a power of two (QD_ERR_PANIC, qd_plan_create's code and
+ * message), a width above 4096 (QD_ERR_UNSUPPORTED); a NULL segment list with n > 0 (QD_ERR_INVALID); then the segments in list order,
+ * the first offender named in qd_last_error by its index: count > 2^31 (QD_ERR_UNSUPPORTED), first + count > n_in (QD_ERR_SHORT,
+ * qd_symbols_run only; no output byte is touched); last a NULL in / out that would be read / written (QD_ERR_INVALID).  n == 0 is fine. */
+typedef struct qd_segment { uint64_t first, count; } qd_segment;
+typedef struct qd_symbols_desc {
+    uint32_t struct_size; int32_t epilogue;      /* QD_EPI_BUCKET2_U8 or QD_EPI_MARK_U8 */
+    uint64_t width, stride;
+    int32_t  has_range; float range_min;         /* MARK only */
+    int32_t  windowing; int32_t _pad;
+    uint64_t iq_bytes;                           /* qd_cuts_symbols only: device workspace for the cuts' IQ; 0: 1 GiB */
+} qd_symbols_desc;
+#define QD_SYMBOLS_MAX_WIDTH 4096u
+/* host arithmetic only: offsets[k] = windows of the segments before k, offsets[n] the total (offsets may be NULL: validation alone) */
+int qd_symbols_geometry(const qd_symbols_desc *desc, const qd_segment *segments, size_t n, uint64_t *offsets /* n + 1, may be NULL */);
+/* in: n_in qd_c32 of in_mem memory (device, host, pinned); out: offsets[n] bytes of out_mem memory.  Device buffers are read and written
+ * in place; of a host buffer the hull of the segments goes up and the bytes come down once.  Returns after everything is complete.
+ * QD_ERR_INVALID also for an unknown memory kind. */
+int qd_symbols_run(const qd_symbols_desc *desc, const qd_c32 *in, int in_mem, uint64_t n_in,
+                   const qd_segment *segments, size_t n, uint8_t *out, int out_mem, void *stream);
+/* qd_cuts_run and qd_symbols_run in one call: cut k is segment k, its bytes go at the offsets qd_symbols_geometry gives for the cuts'
+ * counts, and they equal qd_cuts_run into a buffer followed by qd_symbols_run over it byte for byte.  The IQ never leaves the device: it
+ * goes into a device workspace of at most iq_bytes, the cuts taken in list order in groups of whole cuts that fit; a single cut above
+ * the cap is QD_ERR_UNSUPPORTED (lower its count or raise iq_bytes).  qd_cuts_run's validation runs unchanged and first, then the
+ * desc's; options is chunk_bytes only, as there.  A host out comes down once per group. */
+int qd_cuts_symbols(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem,
+                    uint64_t src_first, uint64_t src_count, const qd_cut *cuts, size_t n_cuts,
+                    const qd_symbols_desc *desc, uint8_t *out, int out_mem, const qd_plan_options *options, void *stream);
+
 /* Host-side figures of the most recent host-resident run of the plan (qd_plan_run with host buffers, or one shard of
  * qd_plan_run_sharded): the survey's qd_plan_stats. */
 typedef struct {

@@ -17,6 +17,7 @@ from .engine import (PinnedBuffer, Plan, options_from_env, stages_geometry, rows
                      bursts_init, bursts_fold, bursts_finish, bursts_of, BURST_DTYPE, BURSTS_DEFAULT_CAP,
                      emissions_init, emissions_fold, emissions_finish, emissions_of, EMISSION_DTYPE, EMISSIONS_DEFAULT_CAP,
                      cut_of_emission, cut_rule, cuts_geometry, cuts_run, CUT_DTYPE,
+                     symbols_desc, symbols_geometry, symbols_run, cuts_symbols, SEGMENT_DTYPE,
                      window_design, WINDOW_RECT, WINDOW_BH)
 from ._ffi import (MODE_EXACT, MODE_FAST, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_NO_PLAN_TIME, KERNEL_SPECIALISE, MEM_DEVICE, MEM_HOST, MEM_HOST_PINNED,  # noqa: F401
                    EPI_BUCKET2_U8, EPI_CF32_BLOCKS, EPI_GLYPH_U8, EPI_MARK_U8, EPI_NORMS_F32, EPI_ROWS_F32, RowsDesc, FMT_CF32, FMT_CS16, FMT_CS8, FMT_CU8,  # noqa: F401

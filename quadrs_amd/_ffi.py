@@ -36,6 +36,7 @@ SYMBOLS = [
     "qd_bursts_init", "qd_bursts_fold", "qd_bursts_finish", "qd_plan_bursts",
     "qd_emissions_init", "qd_emissions_fold", "qd_emissions_finish", "qd_plan_emissions",
     "qd_cuts_geometry", "qd_cuts_run", "qd_cut_of_emission",
+    "qd_symbols_geometry", "qd_symbols_run", "qd_cuts_symbols",
 ]
 SUMMARY_BUCKETS = 2048
 MEAN_WORDS = 10
@@ -104,6 +105,12 @@ class CutRule(C.Structure):
     """qd_cut_rule: how qd_cut_of_emission sizes a cut."""
     _fields_ = [("struct_size", C.c_uint32), ("guard_bins", C.c_uint32), ("oversample", C.c_uint32), ("pad", C.c_uint32),
                 ("taps", C.c_uint64), ("max_decimate", C.c_uint64)]
+
+
+class SymbolsDesc(C.Structure):
+    """qd_symbols_desc: the sink of a symbol list, 48 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("epilogue", C.c_int32), ("width", C.c_uint64), ("stride", C.c_uint64),
+                ("has_range", C.c_int32), ("range_min", C.c_float), ("windowing", C.c_int32), ("_pad", C.c_int32), ("iq_bytes", C.c_uint64)]
 
 
 class Emission(C.Structure):
@@ -268,6 +275,9 @@ def lib():
             "qd_cuts_geometry": (i32, [u64, u64, vp, sz, vp, C.POINTER(u64), C.POINTER(u64)]),
             "qd_cuts_run": (i32, [i32, u64, u64, vp, i32, u64, u64, vp, sz, vp, i32, C.POINTER(PlanOptions), vp]),
             "qd_cut_of_emission": (i32, [C.POINTER(ChainDesc), u64, C.POINTER(Emission), C.POINTER(CutRule), C.POINTER(Cut)]),
+            "qd_symbols_geometry": (i32, [C.POINTER(SymbolsDesc), vp, sz, vp]),
+            "qd_symbols_run": (i32, [C.POINTER(SymbolsDesc), vp, i32, u64, vp, sz, vp, i32, vp]),
+            "qd_cuts_symbols": (i32, [i32, u64, u64, vp, i32, u64, u64, vp, sz, C.POINTER(SymbolsDesc), vp, i32, C.POINTER(PlanOptions), vp]),
             "qd_density_init": (i32, [vp, C.c_uint32, C.c_uint32, u64]),
             "qd_density_fold": (i32, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64, u64, vp, u64]),
             "qd_density_merge": (i32, [vp, vp, C.c_uint32, C.c_uint32, u64]),

@@ -97,7 +97,7 @@ int format_from_ext(const std::string &ext) {
     return -1;
 }
 
-enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS, OP_EMISSIONS, OP_CUTS };
+enum OpKind { OP_FROM, OP_GEN, OP_SHIFT, OP_LOWPASS, OP_SPARKFFT, OP_BUCKET, OP_WRITE, OP_MARKS, OP_ROWS, OP_LEVELS, OP_PEAKS, OP_MEANS, OP_POWERS, OP_SPREADS, OP_QUANTILES, OP_BANDS, OP_PICTURE, OP_BURSTS, OP_EMISSIONS, OP_CUTS, OP_SYMBOLS };
 struct Op {
     OpKind kind;
     std::string filename; int format = 0; uint64_t sample_rate = 0;     // from
@@ -116,6 +116,7 @@ struct Op {
     uint64_t min_len = 1, cap = 1048576, print_n = 0;                   // bursts [-min 1] [-cap 1048576] [-print 0]
     uint64_t min_cells = 1;                                             // emissions [-cells 1]
     std::string list_file; uint64_t first_window = 0, guard = 1, oversample = 2, cut_taps = 0, cut_pad = 1;   // cuts -list FILE [-first-window 0] [-guard 1] [-oversample 2] [-taps 0] [-pad 1]
+    size_t fft = 0; uint64_t step = 0; bool by_level = false;            // symbols -fft w [-step =w] -by freq|level [-range min] [-scan SCALE]
     size_t count = 2048; bool has_slice = false; uint64_t slice_start = 0, slice_end = 0; int windowing = 1;   // rows
     int sink_window = 0;                                                // -window bh|rect of the window-plan verbs (qd_chain_desc.windowing)
 };
@@ -190,7 +191,7 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
         ArgMap raw = read_just_args(argv, i);
         Op op{};
         // -window bh|rect (default rect) of every verb that builds a window plan through chain_desc: parsed here, once, with `rows -window`'s words
-        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture", "bursts", "emissions"};
+        static const char *const kWindowVerbs[] = {"sparkfft", "bucket", "marks", "levels", "peaks", "means", "powers", "spreads", "quantiles", "bands", "picture", "bursts", "emissions", "symbols"};
         if (std::find_if(std::begin(kWindowVerbs), std::end(kWindowVerbs), [&](const char *v) { return cmd == v; }) != std::end(kWindowVerbs)) {
             auto it = raw.find("window");
             if (it != raw.end()) {
@@ -432,24 +433,26 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             if (f) op.print_n = parse_si_u64(v);
             ensure_empty(m);
             op.prefix = next(em ? "'emissions' requires a prefix argument" : "'bursts' requires a prefix argument");
-        } else if (cmd == "cuts") {
-            // not in the reference's grammar: the IQ of every record of an `emissions` list, cut out of the source in one call (qd_cuts_run).
-            // The chain words in front describe the plan the list came from, -width and -stride its windows
+        } else if (cmd == "cuts" || cmd == "symbols") {
+            // not in the reference's grammar: the IQ of every record of an `emissions` list, cut out of the source in one call (qd_cuts_run) -
+            // and, as `symbols`, the digits (`bucket -by freq 2`) or blank / non-blank rows (sparkfft) of every cut, the IQ staying on the
+            // device (qd_cuts_symbols).  The chain words in front describe the plan the list came from, -width and -stride its windows
             auto m = no_duplicates(raw);
-            op.kind = OP_CUTS;
+            const bool sym = cmd == "symbols";
+            op.kind = sym ? OP_SYMBOLS : OP_CUTS;
             std::string v = take(m, "width", &f);
-            if (!f) bail("cuts requires -width, the width of the plan the list came from");
+            if (!f) bail(cmd + " requires -width, the width of the plan the list came from");
             op.width = (size_t)parse_si_u64(v);
             v = take(m, "stride", &f);
             op.stride = f ? parse_si_u64(v) : op.width;
             v = take(m, "list", &f);
-            if (!f) bail("cuts requires -list FILE.emissions");
+            if (!f) bail(cmd + " requires -list FILE.emissions");
             op.list_file = v;
             auto u32 = [&](const char *flag, uint64_t deflt, uint64_t least) {
                 const std::string t = take(m, flag, &f);
                 if (!f) return deflt;
                 const uint64_t k = parse_si_u64(t);
-                if (k < least || k > 0xffffffffull) bail(std::string("cuts -") + flag + " takes a number from " + std::to_string(least) + " to 4294967295");
+                if (k < least || k > 0xffffffffull) bail(cmd + " -" + flag + " takes a number from " + std::to_string(least) + " to 4294967295");
                 return k;
             };
             v = take(m, "first-window", &f);
@@ -458,11 +461,31 @@ std::vector<Op> parse(std::vector<std::string> argv) {                 // src/ar
             op.oversample = u32("oversample", 2, 1);
             op.cut_pad = u32("pad", 1, 0);
             v = take(m, "taps", &f);
-            if (f) { op.cut_taps = parse_si_u64(v); if (op.cut_taps == 1 || op.cut_taps > QD_CUT_MAX_TAPS) bail("cuts -taps takes 0 (from the decimation) or 2 ... 4096"); }
+            if (f) { op.cut_taps = parse_si_u64(v); if (op.cut_taps == 1 || op.cut_taps > QD_CUT_MAX_TAPS) bail(cmd + " -taps takes 0 (from the decimation) or 2 ... 4096"); }
             v = take(m, "print", &f);
             if (f) op.print_n = parse_si_u64(v);
+            if (sym) {
+                v = take(m, "fft", &f);
+                if (!f) bail("symbols requires -fft, the width of the windows over each cut");
+                op.fft = (size_t)parse_si_u64(v);
+                v = take(m, "step", &f);
+                op.step = f ? parse_si_u64(v) : op.fft;
+                v = take(m, "by", &f);
+                if (!f || (v != "freq" && v != "level")) bail("symbols -by takes freq (the bucket sink's digits) or level (the mark sink's blank / non-blank rows)");
+                op.by_level = v == "level";
+                v = take(m, "range", &f);
+                if (f) {
+                    if (!op.by_level) bail("symbols -range is the mark sink's minimum: it goes with -by level");
+                    op.has_range = true; op.rmin = strtof(v.c_str(), nullptr); op.rmax = 1.0f;
+                }
+                v = take(m, "scan", &f);
+                if (f) {
+                    op.has_scan = true; op.scan = strtod(v.c_str(), nullptr);
+                    if (!std::isfinite(op.scan) || !(op.scan > 0.0)) bail("symbols -scan takes a scale > 0");
+                }
+            }
             ensure_empty(m);
-            op.prefix = next("'cuts' requires a prefix argument");
+            op.prefix = next(sym ? "'symbols' requires a prefix argument" : "'cuts' requires a prefix argument");
         } else if (cmd == "picture") {
             // not in the reference's grammar: the waterfall its conrod front end renders (src/ui/mod.rs:294-412) as a binary PPM.  -width 8,
             // -stride 1 and -stretch 4 are its Params (:72-76) and 2.29 its scale (:353); -scan 0, no marker columns, is not: its default of 1
@@ -1573,9 +1596,8 @@ void do_emissions(const Samples &s, const Op &sink, const ChainSpec *cs) { do_li
 // per record with outputs (NNNNNN the record's place in the list), one header line, and with -print K the first K cuts as
 // `shift_hz lowpass_hz decimate taps first count`.  All cuts run in one qd_cuts_run; with QUADRS_HIP_NO_FUSE=1 one by one through
 // qd_unpack, qd_shift and qd_lowpass_block: the same bytes.  A cascade has no single shift and decimation to work the cut out from.
-void do_cuts(const Op &sink, const ChainSpec &cs) {
-    if (cs.cascade) bail("cuts takes the chain the list came from as from [shift] [lowpass]: a cascade has no single shift and decimation to place an emission by");
-    if (g_gpus > 1) bail("cuts run on one device: every cut reads the one source (run it without -gpus)");
+// the cuts of a -list file's records (`cuts` and `symbols`): d is the desc of the plan the list came from
+void cuts_of_list(const char *verb, const Op &sink, const ChainSpec &cs, const ChainSource &in, qd_chain_desc *d, std::vector<qd_cut> *cuts) {
     FILE *fp = fopen(sink.list_file.c_str(), "rb");
     if (!fp) bail(std::string(strerror(errno)) + " (os error " + std::to_string(errno) + "): " + sink.list_file);
     std::vector<qd_emission> list;
@@ -1584,17 +1606,41 @@ void do_cuts(const Op &sink, const ChainSpec &cs) {
         size_t got;
         while ((got = fread(&e, 1, sizeof e, fp)) == sizeof e) list.push_back(e);
         fclose(fp);
-        if (got) bail("cuts -list takes a file of whole qd_emission records (56 bytes each): " + sink.list_file);
+        if (got) bail(std::string(verb) + " -list takes a file of whole qd_emission records (56 bytes each): " + sink.list_file);
     }
-    ChainSource in(cs);
-    qd_chain_desc d;
     std::vector<qd_stage> stages;
-    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, &d, &stages);
+    chain_desc(cs, in, sink.width, sink.stride, QD_EPI_NORMS_F32, d, &stages);
     qd_cut_rule rule{};
     rule.struct_size = sizeof rule;
     rule.guard_bins = (uint32_t)sink.guard; rule.oversample = (uint32_t)sink.oversample; rule.pad = (uint32_t)sink.cut_pad; rule.taps = sink.cut_taps;
-    std::vector<qd_cut> cuts(list.size());
-    for (size_t k = 0; k < list.size(); ++k) qd_check(qd_cut_of_emission(&d, sink.first_window, &list[k], &rule, &cuts[k]), ("record " + std::to_string(k)).c_str());
+    cuts->resize(list.size());
+    for (size_t k = 0; k < list.size(); ++k) qd_check(qd_cut_of_emission(d, sink.first_window, &list[k], &rule, &(*cuts)[k]), ("record " + std::to_string(k)).c_str());
+}
+
+// cut k of a list through the fine-grained calls (QUADRS_HIP_NO_FUSE=1): qd_unpack | qd_gen, qd_shift, qd_lowpass_block into out[0, count)
+void cut_fine(const ChainSource &in, const qd_chain_desc &d, const qd_cut &c, size_t k, qd_c32 *out) {
+    static std::vector<qd_c32> raw;
+    static std::vector<float> taps;
+    const uint64_t pb = qd_pair_bytes(d.format);
+    const uint64_t a = c.first * c.decimate, valid = c.count * c.decimate + c.taps;
+    raw.resize((size_t)valid);
+    if (in.from_gen) qd_check(qd_gen(in.op.cos.data(), in.op.cos.size(), in.op.sample_rate, a, (size_t)valid, raw.data(), QD_MEM_HOST), "gen");
+    else qd_check(qd_unpack(d.format, in.data->p + a * pb, (size_t)valid, raw.data(), QD_MEM_HOST), "unpack");
+    if (c.shift_hz) qd_check(qd_shift(raw.data(), (size_t)valid, a, qd_shift_ratio(c.shift_hz, d.sample_rate), QD_MEM_HOST), "shift");
+    taps.resize((size_t)c.taps);
+    qd_check(qd_lowpass_design(c.lowpass_hz, d.sample_rate, (size_t)c.taps, taps.data()), "lowpass_design");
+    size_t produced = 0;
+    qd_check(qd_lowpass_block(taps.data(), (size_t)c.taps, c.decimate, raw.data(), (size_t)valid, out, (size_t)c.count, &produced, QD_MEM_HOST), "lowpass");
+    if (produced != c.count) bail("cut " + std::to_string(k) + ": " + std::to_string(produced) + " outputs, not " + std::to_string(c.count));
+}
+
+void do_cuts(const Op &sink, const ChainSpec &cs) {
+    if (cs.cascade) bail("cuts takes the chain the list came from as from [shift] [lowpass]: a cascade has no single shift and decimation to place an emission by");
+    if (g_gpus > 1) bail("cuts run on one device: every cut reads the one source (run it without -gpus)");
+    ChainSource in(cs);
+    qd_chain_desc d;
+    std::vector<qd_cut> cuts;
+    cuts_of_list("cuts", sink, cs, in, &d, &cuts);
     std::vector<uint64_t> offs(cuts.size() + 1);
     uint64_t lo = 0, n = 0;
     qd_check(qd_cuts_geometry(d.sample_rate, d.n_samples, cuts.data(), cuts.size(), offs.data(), &lo, &n), "cuts");
@@ -1605,23 +1651,8 @@ void do_cuts(const Op &sink, const ChainSpec &cs) {
         const void *src = out.empty() ? nullptr : in.resident(&mem);
         qd_check(qd_cuts_run(d.format, d.sample_rate, d.n_samples, src, mem, 0, d.n_samples, cuts.data(), cuts.size(), out.data(), QD_MEM_HOST, nullptr, nullptr), "cuts");
     } else {
-        std::vector<qd_c32> raw;
-        std::vector<float> taps;
-        const uint64_t pb = qd_pair_bytes(d.format);
-        for (size_t k = 0; k < cuts.size(); ++k) {
-            const qd_cut &c = cuts[k];
-            if (!c.count) continue;
-            const uint64_t a = c.first * c.decimate, valid = c.count * c.decimate + c.taps;
-            raw.resize((size_t)valid);
-            if (in.from_gen) qd_check(qd_gen(in.op.cos.data(), in.op.cos.size(), in.op.sample_rate, a, (size_t)valid, raw.data(), QD_MEM_HOST), "gen");
-            else qd_check(qd_unpack(d.format, in.data->p + a * pb, (size_t)valid, raw.data(), QD_MEM_HOST), "unpack");
-            if (c.shift_hz) qd_check(qd_shift(raw.data(), (size_t)valid, a, qd_shift_ratio(c.shift_hz, d.sample_rate), QD_MEM_HOST), "shift");
-            taps.resize((size_t)c.taps);
-            qd_check(qd_lowpass_design(c.lowpass_hz, d.sample_rate, (size_t)c.taps, taps.data()), "lowpass_design");
-            size_t produced = 0;
-            qd_check(qd_lowpass_block(taps.data(), (size_t)c.taps, c.decimate, raw.data(), (size_t)valid, out.data() + offs[k], (size_t)c.count, &produced, QD_MEM_HOST), "lowpass");
-            if (produced != c.count) bail("cut " + std::to_string(k) + ": " + std::to_string(produced) + " outputs, not " + std::to_string(c.count));
-        }
+        for (size_t k = 0; k < cuts.size(); ++k)
+            if (cuts[k].count) cut_fine(in, d, cuts[k], k, out.data() + offs[k]);
     }
     for (size_t k = 0; k < cuts.size(); ++k) {
         if (!cuts[k].count) continue;
@@ -1636,6 +1667,106 @@ void do_cuts(const Op &sink, const ChainSpec &cs) {
     for (size_t k = 0; k < std::min<uint64_t>(cuts.size(), sink.print_n); ++k)
         printf("%lld %llu %llu %llu %llu %llu\n", (long long)cuts[k].shift_hz, (unsigned long long)cuts[k].lowpass_hz, (unsigned long long)cuts[k].decimate,
                (unsigned long long)cuts[k].taps, (unsigned long long)cuts[k].first, (unsigned long long)cuts[k].count);
+}
+
+// The `symbols` sink: the digit string (-by freq: `bucket -by freq 2`) or the blank / non-blank rows (-by level: sparkfft's rows, the input of
+// bits::scan) of every cut of an emission list - `cuts`' words say which cuts, -fft and -step the windows over each cut (at the cut's own
+// rate), -range the mark sink's minimum, -window bh a Blackman-Harris window.  PREFIX.symbols holds one line a record,
+// `NNNNNN rate windows digits` (digits `-` where the cut has no window), and with -scan SCALE a second one, `NNNNNN bits error`, from
+// qd_bits_scan; where bits::scan never returns (QD_ERR_PANIC) that line carries the bits found so far, the error so far and the word
+// `loops`: one stuck record does not cost the others.  All of it is ONE qd_cuts_symbols call - the IQ never leaves the device -; with
+// QUADRS_HIP_NO_FUSE=1 cut by cut through qd_cuts_run to the host and a plan per cut: the same file.
+void do_symbols(const Op &sink, const ChainSpec &cs) {
+    if (cs.cascade) bail("symbols takes the chain the list came from as from [shift] [lowpass]: a cascade has no single shift and decimation to place an emission by");
+    if (g_gpus > 1) bail("symbols run on one device: every cut reads the one source (run it without -gpus)");
+    ChainSource in(cs);
+    qd_chain_desc d;
+    std::vector<qd_cut> cuts;
+    cuts_of_list("symbols", sink, cs, in, &d, &cuts);
+    qd_symbols_desc sd{};
+    sd.struct_size = sizeof sd;
+    sd.epilogue = sink.by_level ? QD_EPI_MARK_U8 : QD_EPI_BUCKET2_U8;
+    sd.width = sink.fft; sd.stride = sink.step;
+    sd.has_range = sink.has_range ? 1 : 0; sd.range_min = sink.rmin;
+    sd.windowing = sink.sink_window;
+    std::vector<qd_segment> segs(cuts.size());
+    for (size_t k = 0; k < cuts.size(); ++k) segs[k] = qd_segment{0, cuts[k].count};
+    std::vector<uint64_t> offs(cuts.size() + 1);
+    qd_check(qd_cuts_geometry(d.sample_rate, d.n_samples, cuts.data(), cuts.size(), nullptr, nullptr, nullptr), "symbols");
+    qd_check(qd_symbols_geometry(&sd, segs.data(), segs.size(), offs.data()), "symbols");
+    std::vector<uint8_t> out((size_t)offs[cuts.size()]);
+    if (!getenv("QUADRS_HIP_NO_FUSE")) {
+        int mem = QD_MEM_HOST;
+        const void *src = out.empty() ? nullptr : in.resident(&mem);
+        qd_check(qd_cuts_symbols(d.format, d.sample_rate, d.n_samples, src, mem, 0, d.n_samples, cuts.data(), cuts.size(), &sd, out.data(), QD_MEM_HOST, nullptr, nullptr), "symbols");
+    } else {
+        std::vector<qd_c32> iq;
+        int mem = QD_MEM_HOST;
+        const void *src = out.empty() ? nullptr : in.resident(&mem);
+        for (size_t k = 0; k < cuts.size(); ++k) {
+            const uint64_t nw = offs[k + 1] - offs[k];
+            if (!nw) continue;
+            iq.resize((size_t)cuts[k].count);
+            qd_check(qd_cuts_run(d.format, d.sample_rate, d.n_samples, src, mem, 0, d.n_samples, &cuts[k], 1, iq.data(), QD_MEM_HOST, nullptr, nullptr), "cuts");
+            qd_chain_desc w{};
+            w.struct_size = sizeof w;
+            w.format = QD_FMT_CF32; w.sample_rate = d.sample_rate / cuts[k].decimate; w.n_samples = cuts[k].count;
+            w.width = sd.width; w.stride = sd.stride; w.epilogue = sd.epilogue;
+            w.has_range = sd.has_range; w.range_min = sd.range_min; w.range_max = 1.0f;
+            w.windowing = sd.windowing;
+            qd_plan *plan = nullptr;
+            qd_check(qd_plan_create(&w, &plan), "plan");
+            qd_plan_info info;
+            qd_check(qd_plan_get_info(plan, &info), "plan");
+            if (info.n_windows != nw) bail("cut " + std::to_string(k) + ": the plan has " + std::to_string(info.n_windows) + " windows, not " + std::to_string(nw));
+            qd_check(qd_plan_run(plan, iq.data(), QD_MEM_HOST, 0, cuts[k].count, 0, nw, out.data() + offs[k], QD_MEM_HOST, nullptr), "run");
+            qd_plan_destroy(plan);
+        }
+    }
+    std::string text;
+    std::vector<uint8_t> bits;
+    uint64_t stuck = 0;
+    for (size_t k = 0; k < cuts.size(); ++k) {
+        const uint64_t nw = offs[k + 1] - offs[k];
+        char head[64];
+        snprintf(head, sizeof head, "%06zu %llu %llu ", k, (unsigned long long)(d.sample_rate / cuts[k].decimate), (unsigned long long)nw);
+        text += head;
+        if (!nw) text += '-';
+        for (uint64_t w = 0; w < nw; ++w) text.push_back((char)('0' + (out[offs[k] + w] ? 1 : 0)));
+        text += '\n';
+        if (!sink.has_scan) continue;
+        bits.resize((size_t)nw + 1);
+        size_t produced = 0;
+        double error = 0.0;
+        int rc = qd_bits_scan(out.data() + offs[k], (size_t)nw, sink.scan, bits.data(), bits.size(), &produced, &error);
+        if (rc == QD_ERR_INVALID && produced > bits.size()) {                // (a scale below 1 emits more bits than marks)
+            bits.resize(produced);
+            rc = qd_bits_scan(out.data() + offs[k], (size_t)nw, sink.scan, bits.data(), bits.size(), &produced, &error);
+        }
+        if (rc != QD_ERR_PANIC) qd_check(rc, "scan");                        // the reference's endless loop: what it had found by then
+        else ++stuck;
+        snprintf(head, sizeof head, "%06zu ", k);
+        text += head;
+        if (!produced) text += '-';
+        for (size_t b = 0; b < produced; ++b) text.push_back((char)('0' + bits[b]));
+        snprintf(head, sizeof head, " %.17g", error);
+        text += head;
+        if (rc == QD_ERR_PANIC) text += " loops";
+        text += '\n';
+    }
+    write_new_file(sink.prefix + ".symbols", text.data(), text.size());
+    printf("symbols width=%zu stride=%llu first_window=%llu guard=%llu oversample=%llu taps=%llu pad=%llu fft=%zu step=%llu by=%s window=%s records=%zu windows=%llu",
+           (size_t)sink.width, (unsigned long long)sink.stride, (unsigned long long)sink.first_window, (unsigned long long)sink.guard, (unsigned long long)sink.oversample,
+           (unsigned long long)sink.cut_taps, (unsigned long long)sink.cut_pad, (size_t)sink.fft, (unsigned long long)sink.step, sink.by_level ? "level" : "freq",
+           sink.sink_window ? "bh" : "rect", cuts.size(), (unsigned long long)offs[cuts.size()]);
+    if (sink.has_scan) printf(" scan=%.9g stuck=%llu", sink.scan, (unsigned long long)stuck);
+    printf("\n");
+    size_t at = 0;
+    for (uint64_t k = 0; k < sink.print_n && at < text.size(); ++k) {        // -print K: the file's first K lines
+        const size_t nl = text.find('\n', at);
+        printf("%s\n", text.substr(at, nl - at).c_str());
+        at = nl + 1;
+    }
 }
 
 // The `picture` sink: the waterfall of the windows sparkfft would print (a cascade's complete windows) as the reference's `render` lays
@@ -1729,6 +1860,8 @@ void usage() {
             "  bursts [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
             "emissions [-width 128] [-stride =width] (-level X | -levels FILE) [-times K] [-min 1] [-cells 1] [-cap 1048576] [-print 0] FILENAME_PREFIX \\\n"
             "    cuts -width W [-stride =width] -list FILE.emissions [-first-window 0] [-guard 1] [-oversample 2] [-taps 0] [-pad 1] [-print 0] FILENAME_PREFIX \\\n"
+            " symbols -width W [-stride =width] -list FILE.emissions [cuts' flags] -fft w [-step =w] -by freq|level [-range min] [-window bh|rect] \\\n"
+            "         [-scan SCALE] [-print 0] FILENAME_PREFIX \\\n"
             " picture [-width 8] [-stride 1] -size PXWxPXH [-stretch 4] [-scan 0] [-scale 2.29] [-overwrite no] FILENAME_PREFIX \\\n"
             "    rows [-width 512] [-count 2048] [-slice START:END] [-window bh|rect] FILENAME_PREFIX \\\n"
             "   write [-overwrite no] FILENAME_PREFIX \\\n"
@@ -1806,6 +1939,15 @@ int main(int argc, char **argv) {
                     printf("cuts width=%zu stride=%llu list=%s first_window=%llu guard=%llu oversample=%llu taps=%llu pad=%llu print=%llu\n", op.width, (unsigned long long)op.stride,
                            op.list_file.c_str(), (unsigned long long)op.first_window, (unsigned long long)op.guard, (unsigned long long)op.oversample,
                            (unsigned long long)op.cut_taps, (unsigned long long)op.cut_pad, (unsigned long long)op.print_n);
+                    break;
+                case OP_SYMBOLS:
+                    printf("symbols width=%zu stride=%llu list=%s first_window=%llu guard=%llu oversample=%llu taps=%llu pad=%llu fft=%zu step=%llu by=%s", op.width,
+                           (unsigned long long)op.stride, op.list_file.c_str(), (unsigned long long)op.first_window, (unsigned long long)op.guard,
+                           (unsigned long long)op.oversample, (unsigned long long)op.cut_taps, (unsigned long long)op.cut_pad, op.fft, (unsigned long long)op.step,
+                           op.by_level ? "level" : "freq");
+                    if (op.has_range) printf(" range=%.9g", op.rmin);
+                    if (op.has_scan) printf(" scan=%.9g", op.scan);
+                    printf(" print=%llu\n", (unsigned long long)op.print_n);
                     break;
                 case OP_PICTURE:
                     printf("picture width=%zu stride=%llu size=%ux%u stretch=%u scan=%u scale=%.9g overwrite=%d\n", op.width, (unsigned long long)op.stride, op.px_w, op.px_h,
@@ -1898,6 +2040,11 @@ int main(int argc, char **argv) {
                 if (!samples) bail("cuts requires an input");
                 cs.cascade = !chain_clean;
                 do_cuts(op, cs);
+                break;
+            case OP_SYMBOLS:
+                if (!samples) bail("symbols requires an input");
+                cs.cascade = !chain_clean;
+                do_symbols(op, cs);
                 break;
             case OP_PICTURE:
                 if (!samples) bail("picture requires an input");

@@ -42,6 +42,7 @@
 #include "qd_bursts.h"
 #include "qd_emissions.h"
 #include "qd_cuts.h"
+#include "qd_symbols.h"
 #include "qd_paint.h"
 
 using namespace qd;
@@ -4736,8 +4737,9 @@ int qd_cut_of_emission(const qd_chain_desc *desc, uint64_t first_window, const q
     return QD_OK;
 }
 
-int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
-                const qd_cut *cuts, size_t n_cuts, qd_c32 *out, int out_mem, const qd_plan_options *options, void *stream) {
+// qd_cuts_run's body, shared with qd_cuts_symbols.  check_only: the validation alone, up to where the first buffer would be looked at.
+static int cuts_run_impl(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                         const qd_cut *cuts, size_t n_cuts, qd_c32 *out, int out_mem, const qd_plan_options *options, void *stream, bool check_only) {
     if (fmt < 0 || fmt > 3) return fail(QD_ERR_INVALID, "unknown format %d", fmt);
     if (src_mem < QD_MEM_HOST || src_mem > QD_MEM_HOST_PINNED || out_mem < QD_MEM_HOST || out_mem > QD_MEM_HOST_PINNED) return fail(QD_ERR_INVALID, "unknown memory kind");
     qd_plan_options opt;
@@ -4747,7 +4749,7 @@ int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *s
     std::vector<uint64_t> offs(n_cuts + 1);
     std::string err;
     if (const int rc = cuts_check(sample_rate, n_samples, cuts, n_cuts, true, src_first, src_count, offs.data(), nullptr, nullptr, &err)) return fail(rc, "%s", err.c_str());
-    if (offs[n_cuts] == 0) return QD_OK;
+    if (offs[n_cuts] == 0 || check_only) return QD_OK;
     if (!src || !out) return fail(QD_ERR_INVALID, "NULL buffer");
 
     // the job table: one entry per cut; taps designed once per (lowpass_hz, taps), a lane table per distinct shift
@@ -4861,6 +4863,163 @@ int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *s
         }
     }
     HIPCHK(hipStreamSynchronize(st));
+    return QD_OK;
+}
+
+int qd_cuts_run(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                const qd_cut *cuts, size_t n_cuts, qd_c32 *out, int out_mem, const qd_plan_options *options, void *stream) {
+    return cuts_run_impl(fmt, sample_rate, n_samples, src, src_mem, src_first, src_count, cuts, n_cuts, out, out_mem, options, stream, false);
+}
+
+// ------------------------------------------------------------------ symbol list (include/quadrs_hip.h, "symbol list"; qd_symbols.h, qd_symbols_plan.h)
+
+int qd_symbols_geometry(const qd_symbols_desc *desc, const qd_segment *segments, size_t n, uint64_t *offsets) {
+    std::string err;
+    if (const int rc = symbols_check(desc, segments, n, false, 0, offsets, nullptr, nullptr, &err)) return fail(rc, "%s", err.c_str());
+    return QD_OK;
+}
+
+// the device a call runs on: where the caller's device buffer lives
+static int symbols_device_of(const void *a, bool a_dev, const void *b, bool b_dev) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const void *anchor = a_dev ? a : (b_dev ? b : nullptr);
+    if (anchor) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, anchor) == hipSuccess) dev = at.device;
+        else (void)hipGetLastError();
+    }
+    return dev;
+}
+
+// Validated segments of a device buffer (its element 0 is element `base` of the segments' indices) -> bytes at out_d + offs[k], all of it
+// complete on return.  Workspace slots 2 (twiddles, window) and 4 (tile table).
+static int symbols_on_device(const qd_symbols_desc &d, const float2 *in_d, uint64_t base, const qd_segment *segs, size_t n, const uint64_t *offs,
+                             uint8_t *out_d, WsLease &ws, hipStream_t st) {
+    const FftLayout L = fft_layout(d.width);
+    std::vector<float> win;
+    if (d.windowing) blackman_harris(d.width, &win);
+    const size_t tw_b = (L.tw.size() * sizeof(float2) + 15) & ~(size_t)15;
+    void *tab_d = nullptr;
+    int rc = ws.get(2, tw_b + win.size() * 4 + 16, &tab_d); if (rc) return rc;
+    if (!L.tw.empty()) HIPCHK(hipMemcpyAsync(tab_d, L.tw.data(), L.tw.size() * sizeof(float2), hipMemcpyHostToDevice, st));
+    if (!win.empty()) HIPCHK(hipMemcpyAsync(static_cast<char *>(tab_d) + tw_b, win.data(), win.size() * 4, hipMemcpyHostToDevice, st));
+    ChainParams P{};
+    P.W = (uint32_t)d.width; P.logW = ilog2(d.width);
+    P.S = (uint32_t)std::min<uint64_t>(d.stride, kSymMaxCount);
+    P.base_len = L.base_len; P.log_base = L.log_base; P.layers = L.layers;
+    P.epi = (uint32_t)d.epilogue;
+    P.rmin = d.has_range ? d.range_min : 0.08f;          // src/fft.rs:22-23
+    P.root2 = (float)std::sqrt(0.5);
+    P.tw16_1 = compute_twiddle(1, 16); P.tw16_2 = compute_twiddle(2, 16); P.tw16_3 = compute_twiddle(3, 16);
+    P.tw = static_cast<const float2 *>(tab_d);
+    P.window = win.empty() ? nullptr : reinterpret_cast<const float *>(static_cast<char *>(tab_d) + tw_b);
+    P.out = out_d; P.out_window0 = 0;
+    const bool bucket = d.epilogue == QD_EPI_BUCKET2_U8;
+    const void *fn = bucket ? reinterpret_cast<const void *>(k_symbols<QD_EPI_BUCKET2_U8>) : reinterpret_cast<const void *>(k_symbols<QD_EPI_MARK_U8>);
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSymLdsBytes));
+    const uint32_t waves = symbols_waves(d.width);
+    std::vector<std::vector<SymTile>> kept;              // the tile tables stay alive until their copies are done
+    SymCursor cur;
+    for (bool more = true; more;) {
+        kept.emplace_back();
+        std::vector<SymTile> &tiles = kept.back();
+        more = symbols_tiles(&d, segs, n, offs, base, &cur, kSymBatchTiles, &tiles);
+        if (tiles.empty()) break;
+        const uint32_t n_tiles = (uint32_t)tiles.size();
+        void *tiles_d = nullptr;
+        rc = ws.get(4, (size_t)kSymBatchTiles * sizeof(SymTile), &tiles_d); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(tiles_d, tiles.data(), (size_t)n_tiles * sizeof(SymTile), hipMemcpyHostToDevice, st));
+        const dim3 grid((n_tiles + waves - 1) / waves), block(kSymThreads);
+        if (bucket) hipLaunchKernelGGL(k_symbols<QD_EPI_BUCKET2_U8>, grid, block, kSymLdsBytes, st, P, in_d, static_cast<const SymTile *>(tiles_d), n_tiles);
+        else hipLaunchKernelGGL(k_symbols<QD_EPI_MARK_U8>, grid, block, kSymLdsBytes, st, P, in_d, static_cast<const SymTile *>(tiles_d), n_tiles);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return QD_OK;
+}
+
+int qd_symbols_run(const qd_symbols_desc *desc, const qd_c32 *in, int in_mem, uint64_t n_in, const qd_segment *segments, size_t n,
+                   uint8_t *out, int out_mem, void *stream) {
+    if (in_mem < QD_MEM_HOST || in_mem > QD_MEM_HOST_PINNED || out_mem < QD_MEM_HOST || out_mem > QD_MEM_HOST_PINNED) return fail(QD_ERR_INVALID, "unknown memory kind");
+    std::vector<uint64_t> offs(n + 1);
+    uint64_t hull_first = 0, hull_count = 0;
+    std::string err;
+    if (const int rc = symbols_check(desc, segments, n, true, n_in, offs.data(), &hull_first, &hull_count, &err)) return fail(rc, "%s", err.c_str());
+    const uint64_t total = offs[n];
+    if (total == 0) return QD_OK;
+    if (!in || !out) return fail(QD_ERR_INVALID, "NULL buffer");
+    const bool in_dev = in_mem == QD_MEM_DEVICE, out_dev = out_mem == QD_MEM_DEVICE;
+    DeviceGuard guard(symbols_device_of(in, in_dev, out, out_dev));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    WsLease ws(st);
+    if (ws.rc) return ws.rc;
+    const float2 *in_d = reinterpret_cast<const float2 *>(in);
+    uint64_t base = 0;
+    if (!in_dev) {                                       // the hull of the segments that have a window goes up
+        void *up = nullptr;
+        if (const int rc = ws.get(0, hull_count * 8 + 16, &up)) return rc;
+        HIPCHK(hipMemcpyAsync(up, in + hull_first, hull_count * 8, hipMemcpyHostToDevice, st));
+        in_d = static_cast<const float2 *>(up);
+        base = hull_first;
+    }
+    uint8_t *out_d = out;
+    if (!out_dev) {
+        void *o = nullptr;
+        if (const int rc = ws.get(1, total, &o)) return rc;
+        out_d = static_cast<uint8_t *>(o);
+    }
+    if (const int rc = symbols_on_device(*desc, in_d, base, segments, n, offs.data(), out_d, ws, st)) return rc;
+    if (!out_dev) {
+        HIPCHK(hipMemcpyAsync(out, out_d, total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return QD_OK;
+}
+
+int qd_cuts_symbols(int fmt, uint64_t sample_rate, uint64_t n_samples, const void *src, int src_mem, uint64_t src_first, uint64_t src_count,
+                    const qd_cut *cuts, size_t n_cuts, const qd_symbols_desc *desc, uint8_t *out, int out_mem, const qd_plan_options *options, void *stream) {
+    if (const int rc = cuts_run_impl(fmt, sample_rate, n_samples, src, src_mem, src_first, src_count, cuts, n_cuts, nullptr, out_mem, options, stream, true)) return rc;
+    std::vector<qd_segment> segs(n_cuts);
+    for (size_t k = 0; k < n_cuts; ++k) segs[k] = qd_segment{0, cuts[k].count};
+    std::vector<uint64_t> offs(n_cuts + 1);
+    std::string err;
+    if (const int rc = symbols_check(desc, segs.data(), n_cuts, false, 0, offs.data(), nullptr, nullptr, &err)) return fail(rc, "%s", err.c_str());
+    std::vector<std::pair<size_t, size_t>> groups;
+    if (const int rc = symbols_groups(cuts, n_cuts, desc->iq_bytes, &groups, &err)) return fail(rc, "%s", err.c_str());
+    if (offs[n_cuts] == 0) return QD_OK;
+    if (!src || !out) return fail(QD_ERR_INVALID, "NULL buffer");
+    const bool out_dev = out_mem == QD_MEM_DEVICE;
+    DeviceGuard guard(symbols_device_of(src, src_mem == QD_MEM_DEVICE, out, out_dev));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    WsLease ws(st);
+    if (ws.rc) return ws.rc;
+    std::vector<uint64_t> goffs;
+    for (const auto &g : groups) {
+        const size_t k0 = g.first, ng = g.second - g.first;
+        const uint64_t bytes = offs[g.second] - offs[k0];
+        if (bytes == 0) continue;                        // (no cut of the group has a window: its IQ is not needed)
+        uint64_t iq = 0;
+        for (size_t k = 0; k < ng; ++k) { segs[k0 + k].first = iq; iq += cuts[k0 + k].count; }
+        void *iq_d = nullptr;
+        if (const int rc = ws.get(0, iq * 8, &iq_d)) return rc;
+        if (const int rc = cuts_run_impl(fmt, sample_rate, n_samples, src, src_mem, src_first, src_count, cuts + k0, ng, static_cast<qd_c32 *>(iq_d), QD_MEM_DEVICE,
+                                         options, stream, false))
+            return rc;
+        goffs.assign(offs.begin() + k0, offs.begin() + g.second + 1);
+        uint8_t *out_d = out;                            // a device out is written in place, at the list's own offsets
+        if (!out_dev) {
+            void *o = nullptr;
+            if (const int rc = ws.get(1, bytes, &o)) return rc;
+            out_d = static_cast<uint8_t *>(o);
+            for (uint64_t &v : goffs) v -= offs[k0];
+        }
+        if (const int rc = symbols_on_device(*desc, static_cast<const float2 *>(iq_d), 0, segs.data() + k0, ng, goffs.data(), out_d, ws, st)) return rc;
+        if (!out_dev) {
+            HIPCHK(hipMemcpyAsync(out + offs[k0], out_d, bytes, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
     return QD_OK;
 }
 

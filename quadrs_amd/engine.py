@@ -681,6 +681,88 @@ def cuts_run(fmt, sample_rate, n_samples, src, cuts, src_first=0, src_count=None
     return views
 
 
+SEGMENT_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8")])      # qd_segment, 16 bytes
+
+
+def symbols_desc(epilogue, width, stride=None, rng=None, windowing=0, iq_bytes=0):
+    """a qd_symbols_desc: EPI_BUCKET2_U8 or EPI_MARK_U8 over windows of `width` samples every `stride` (None: width); rng = (min, ...) is
+    the mark sink's range; iq_bytes caps cuts_symbols' device workspace (0: 1 GiB)."""
+    return _ffi.SymbolsDesc(C.sizeof(_ffi.SymbolsDesc), int(epilogue), int(width), int(width if stride is None else stride),
+                            0 if rng is None else 1, 0.0 if rng is None else float(rng[0]), int(windowing), 0, int(iq_bytes))
+
+
+def _segment_table(segments):
+    a = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE).reshape(-1)
+    return a, int(a.size)
+
+
+def symbols_geometry(desc, segments):
+    """qd_symbols_geometry (host arithmetic): offsets uint64[n + 1] of a SEGMENT_DTYPE list, offsets[n] the total of bytes."""
+    a, n = _segment_table(segments)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    check(lib().qd_symbols_geometry(C.byref(desc), _np_ptr(a) if n else None, n, _np_ptr(offs)))
+    return offs
+
+
+def _symbols_out(out, total, offs, n, pinned):
+    """(keep, pointer, memory kind, per-segment views) of a symbol call's output: None (a new host buffer), a numpy uint8 array (pinned=True
+    for a PinnedBuffer array) or a torch CUDA uint8 tensor."""
+    if out is not None and _is_torch(out):
+        flat = out.view(-1)
+        assert flat.element_size() == 1 and flat.numel() >= total, "out is smaller than the symbols' total"
+        return flat, C.c_void_p(flat.data_ptr()), MEM_DEVICE, [flat[int(offs[k]):int(offs[k + 1])] for k in range(n)]
+    flat = np.zeros(max(total, 1), dtype=np.uint8) if out is None else out.view(np.uint8).reshape(-1)
+    assert flat.size >= total, "out is smaller than the symbols' total"
+    return flat, _np_ptr(flat), (_ffi.MEM_HOST_PINNED if (pinned and out is not None) else MEM_HOST), [flat[int(offs[k]):int(offs[k + 1])] for k in range(n)]
+
+
+def symbols_run(desc, iq, segments, pinned=False, out=None, stream=None):
+    """qd_symbols_run: one byte per FFT window of every segment of a SEGMENT_DTYPE list over the cf32 buffer iq: a numpy array (host;
+    pinned=True for a PinnedBuffer array) or a torch CUDA tensor (device).  out as for cuts_run, in bytes.  Returns one uint8 array per
+    segment: numpy views of one host buffer, or views of `out` for a torch tensor."""
+    a, n = _segment_table(segments)
+    offs = symbols_geometry(desc, a)
+    if _is_torch(iq):
+        keep, ptr, mem, n_in = iq, C.c_void_p(iq.data_ptr()), MEM_DEVICE, iq.numel() * iq.element_size() // 8
+        st = _cur_stream() if stream is None else C.c_void_p(stream)
+    else:
+        keep = np.ascontiguousarray(iq).view(np.uint8).reshape(-1)
+        ptr, mem, n_in = _np_ptr(keep), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), keep.size // 8
+        st = None if stream is None else C.c_void_p(stream)
+    flat, out_ptr, out_mem, views = _symbols_out(out, int(offs[n]), offs, n, pinned)
+    check(lib().qd_symbols_run(C.byref(desc), ptr, mem, n_in, _np_ptr(a) if n else None, n, out_ptr, out_mem, st))
+    del keep
+    return views
+
+
+def cuts_symbols(fmt, sample_rate, n_samples, src, cuts, desc, src_first=0, src_count=None, pinned=False, out=None, chunk_bytes=0, stream=None):
+    """qd_cuts_symbols: cuts_run and symbols_run in one call, the IQ staying on the device; cut k is segment k.  src as for cuts_run, out as
+    for symbols_run.  Returns one uint8 array per cut."""
+    a, n = _cut_table(cuts)
+    segs = np.zeros(n, dtype=SEGMENT_DTYPE)
+    segs["count"] = a["count"]
+    try:
+        offs = symbols_geometry(desc, segs)
+    except _ffi.QuadrsError:                             # the call below names the first offender in ITS order: the cuts' checks come first
+        check(lib().qd_cuts_symbols(int(fmt), int(sample_rate), int(n_samples), None, MEM_HOST, int(src_first), 0 if src_count is None else int(src_count),
+                                    _np_ptr(a) if n else None, n, C.byref(desc), None, MEM_HOST, None, None))
+        raise
+    if _is_torch(src):
+        ptr, mem, have, keep = C.c_void_p(src.data_ptr()), MEM_DEVICE, src.numel() * src.element_size() // _FMT_BYTES.get(fmt, 1), src
+        st = _cur_stream() if stream is None else C.c_void_p(stream)
+    else:
+        keep = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if not isinstance(src, np.ndarray) else src.view(np.uint8).reshape(-1))
+        ptr, mem, have = _np_ptr(keep), (_ffi.MEM_HOST_PINNED if pinned else MEM_HOST), keep.size // _FMT_BYTES.get(fmt, 1)
+        st = None if stream is None else C.c_void_p(stream)
+    src_count = have if src_count is None else int(src_count)
+    flat, out_ptr, out_mem, views = _symbols_out(out, int(offs[n]), offs, n, pinned)
+    opts = plan_options(chunk_bytes=int(chunk_bytes))
+    check(lib().qd_cuts_symbols(int(fmt), int(sample_rate), int(n_samples), ptr, mem, int(src_first), src_count, _np_ptr(a) if n else None, n,
+                                C.byref(desc), out_ptr, out_mem, C.byref(opts), st))
+    del keep
+    return views
+
+
 def picture_desc(px_width, px_height, stretch=4, scan=0, scale=2.29):
     """a qd_picture_desc: the page of a waterfall picture.  stretch 4 and scale 2.29 are the reference's; scan 0 (no marker columns) is
     not: its default of 1 blackens every column."""
