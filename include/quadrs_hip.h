@@ -226,10 +226,13 @@ typedef struct {
     uint32_t tile_hint[8];       /* tuning: force a plan-time build with this tiling — windows per tile, threads (256 /
                                     512 / 1024), FIR outputs per lane, FIR block taps, waves per SIMD the build is register-
                                     budgeted for, LDS pad elements per row (1 / 2), FFT slots (tiles per FFT batch; 2 with the
-                                    deferred FFT) in bits 0-7 of slot 6 and the kernel variant bits in bits 8-15 (1 planar LDS
-                                    tile, 2 taps baked into the code, 4 packed lane-per-output FIR, 8 row-aligned phase 1, 16
-                                    packed span FIR, 32 straight-line shared FIR, 64 deferred FFT, 128 packed two-output tile FIR;
-                                    a bit a shape cannot take is ignored), workgroups per CU; all 0: the library's own choice.
+                                    deferred FFT) in bits 0-7 of slot 6 and the kernel variant bits above them (4 packed
+                                    lane-per-output FIR, 8 row-aligned phase 1, 32 straight-line shared FIR, 64 deferred FFT, 128
+                                    packed two-output tile FIR, 256 non-temporal stream loads, 8192 half-window tiles, 16384 fused
+                                    multiply-add, 32768 three-stage kernel, 65536 shared rows at the default cache policy, 131072
+                                    its streaming form, 262144 the write sink's; a bit a shape cannot take is ignored; bits 1, 2,
+                                    16, 512, 1024, 2048 and 4096 are reserved and a hint that carries one is refused with
+                                    QD_ERR_INVALID), workgroups per CU; all 0: the library's own choice.
                                     Every variant of one workgroup size computes the same bytes; with a shift stage, tilings of different workgroup
                                     size may round ~1e-8 of the NCO multipliers the other way (DESIGN.md sections 3.1, 4) */
 } qd_plan_options;

@@ -44,14 +44,6 @@ namespace qd {
 #define QD_STAMP_ROW(k)
 #endif
 
-// Plan-time builds may bake the plan's filter into the code (FixedGeo FLAGS_ bit 1): the host puts
-// `#define QD_BAKED_TAPS_LIST 0x1.8p-7f, ...` (the designed taps, exact hex floats) in front of this header.
-#ifdef QD_BAKED_TAPS_LIST
-constexpr float kBakedTapTable[] = {QD_BAKED_TAPS_LIST};
-#else
-constexpr float kBakedTapTable[1] = {0.f};
-#endif
-
 // Timing-only ablation bits (ChainParams::dbg) exist in development builds (-DQD_DEVELOP: libquadrs_hip_dev.so, the
 // probe scripts) only; in the shipped library the tests compile to nothing.
 #ifdef QD_DEVELOP
@@ -157,16 +149,6 @@ struct FixedGeo {
     static constexpr FixedRules R = fixed_rules(W_, S_, D_, T_, G_, FIRB_, FIRR_, PAD_, BATCH_, FLAGS_);
     static constexpr uint32_t kFlags = FLAGS_;
     static constexpr bool kWindow = (FLAGS_ & kGeoWindow) != 0;      // applies ChainParams::window (win_mul)
-    // Planar raw tile: the shifted samples are parked as two f32 planes (re / im) instead of interleaved pairs, rows of D floats
-    // at a 16-byte aligned pitch DpP with DpP/4 odd.  The component-split FIR then reads FOUR taps of its component with one
-    // conflict-free ds_read_b128 (256 B/clk) instead of two with a ds_read2_b32 (128 B/clk): half the LDS-array cycles and
-    // half the LDS instructions of the dominant loop.
-    static constexpr uint32_t DpP = R.DpP;
-    static constexpr uint32_t plane_floats = R.plane_floats;
-    static constexpr bool planar_geometry = R.planar_geometry;
-    // Baked taps (plan-time builds only): the filter is a compile-time table, so every tap is an immediate operand of its
-    // multiply — no LDS reads, no registers, no lgkmcnt traffic for the taps at all.
-    static constexpr bool baked_request = R.baked_request;
     // FFT batching: the decimated windows of BATCH_ consecutive tiles of a workgroup are parked in LDS and transformed
     // together.  The FFT + epilogue of ONE 128-point window keeps 16-32 of 256 lanes busy between three barriers and is
     // pure latency; B windows at once cost the same latency for B times the work.
@@ -210,7 +192,6 @@ struct FixedGeo {
     static constexpr bool kHalfTile = R.kHalfTile;
     static constexpr uint32_t kHalfOut = R.kHalfOut;
     static constexpr uint32_t kHalfRaw = R.kHalfRaw;
-    static constexpr uint32_t lds_raw_elems_std = R.lds_raw_elems_std;
     static constexpr uint32_t kNtrunc = R.kNtrunc;
     static constexpr bool kShared = R.kShared;     // shared-FIR mode (see phase 2)
     static constexpr bool split_ok(uint32_t nt) { return R.split_ok(nt); }
@@ -219,8 +200,6 @@ struct FixedGeo {
     static constexpr bool kPairFir = R.kPairFir;
     static constexpr bool kUnrolledShared = R.kUnrolledShared;
     static constexpr bool kPackedTile = R.kPackedTile;
-    static constexpr bool kPlanar = R.kPlanar;
-    static constexpr bool kBakedTaps = R.kBakedTaps;
     static constexpr uint32_t lds_raw_elems = R.lds_raw_elems;      // float2 elements
 };
 
@@ -230,9 +209,8 @@ struct DynGeo {
     static constexpr bool kWindow = false;
     static constexpr uint32_t kBatch = 1;
     static constexpr uint32_t kFlags = 0, G_ct = 1, W_ct = 1;
-    static constexpr bool kPlanar = false, kBakedTaps = false, kPairFir = false, kUnrolledShared = false, kPackedTile = false, kHalfTile = false;
+    static constexpr bool kPairFir = false, kUnrolledShared = false, kPackedTile = false, kHalfTile = false;
     static constexpr uint32_t kHalfOut = 0, kHalfRaw = 0;
-    static constexpr uint32_t DpP = 0, plane_floats = 0;
     static constexpr bool kShared = false;
     static constexpr uint32_t kFirTile = 1;
     static constexpr bool split_ok(uint32_t) { return false; }
@@ -466,27 +444,6 @@ __device__ __forceinline__ void process_row(const ChainParams &P, const GeoT &ge
             for (int u = 0; u < SPL; ++u) x[u] = cmul_pk(x[u], m[u]);   // buf[i] *= mul (src/shift.rs:51)
         }
     }
-    if constexpr (GeoT::kPlanar && NT == 256) {
-        // planar tile: re plane, then im plane; sample m sits at float m + (DpP - D) * (m / D) of its plane.  rel is a
-        // multiple of D (tile starts and rows both are) and SPL divides D, so a lane's SPL samples are contiguous.
-        constexpr uint32_t LOGD = ct_log2(GeoT::D), PADP = GeoT::DpP - GeoT::D;
-        float *pre = reinterpret_cast<float *>(raw), *pim = pre + GeoT::plane_floats;
-        const int32_t off = m0 + (int32_t)PADP * (m0 >> LOGD);            // arithmetic shift: floor for the (never stored) negatives
-        if constexpr (INTERIOR) {
-            if constexpr (SPL == 2) {
-                *reinterpret_cast<float2 *>(pre + off) = make_float2(x[0].x, x[1].x);
-                *reinterpret_cast<float2 *>(pim + off) = make_float2(x[0].y, x[1].y);
-            } else {
-                *reinterpret_cast<float4 *>(pre + off) = make_float4(x[0].x, x[1].x, x[2].x, x[3].x);
-                *reinterpret_cast<float4 *>(pim + off) = make_float4(x[0].y, x[1].y, x[2].y, x[3].y);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < SPL; ++u)
-                if (m0 + u >= 0 && m0 + u < (int32_t)g.tile_raw) { pre[off + u] = x[u].x; pim[off + u] = x[u].y; }
-        }
-        return;
-    }
     // Additive addressing: rel is a multiple of PD (n_start and ROW both are) and SPL divides PD, so
     // pad(rel + t) = pad_s(rel) + pad(t) and a lane's SPL samples are contiguous in LDS.
     const bool additive = geo.pshift != 0xffffffffu && geo.PD >= (uint32_t)SPL && geo.PD <= ROW;
@@ -588,17 +545,6 @@ __device__ __forceinline__ void fir_span(const GeoT &geo, const float2 *rowp, ui
                 const uint32_t jj = j0 + blk * 8;
                 if (SNAP && jj >= geo.T / 2 + D && jj < geo.T && ((jj - geo.T / 2) % D) == 0) {   // wave-uniform
                     if (jmax == jj) { snapr = accr; snapi = acci; }
-                }
-                if constexpr ((GeoT::kFlags & kGeoPackedSpan) != 0) {
-                    // both chains of the output as one float pair: v_pk_mul_f32 + v_pk_add_f32 per tap (same two roundings per
-                    // component; half the VALU instructions — the kernel is bound by issue slots, see fir_pair)
-                    typedef float v2f_t __attribute__((ext_vector_type(2)));
-                    v2f_t a2 = {accr, acci};
-                    const float hv[8] = {hh[0].x, hh[0].y, hh[0].z, hh[0].w, hh[1].x, hh[1].y, hh[1].z, hh[1].w};
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { const v2f_t xv = {x[i].x, x[i].y}; const v2f_t hs = {hv[i], hv[i]}; a2 = a2 + xv * hs; }
-                    accr = a2.x; acci = a2.y;
-                    return;
                 }
                 accr = accr + x[0].x * hh[0].x; acci = acci + x[0].y * hh[0].x;
                 accr = accr + x[1].x * hh[0].y; acci = acci + x[1].y * hh[0].y;
@@ -917,55 +863,13 @@ __device__ __forceinline__ float fir_comp(const float *xp, uint32_t jmax, const 
     return jmax < T ? snap : acc;
 }
 
-// Component-split FIR over the PLANAR tile (FixedGeo::kPlanar): a lane carries one accumulate chain — acc.re += x.re*h or
-// acc.im += x.im*h, the reference's two f32 chains (src/filter.rs:119), ascending taps, separately rounded multiply and add —
-// and reads FOUR consecutive taps' worth of its component with one ds_read_b128 (the plane's rows are 16-byte aligned at a
-// pitch whose quarter is odd: conflict-free in every 16-lane group).  xp = this lane's plane + the first float of the output's
-// first LDS row.  PF blocks are kept in flight.  With baked taps (plan-time builds) the taps are immediates; otherwise they are
-// broadcast ds_read_b128 from LDS.  A truncated output (jmax < T) is the accumulator snapshot at tap jmax, as in fir_span.
-template <class GeoT>
-__device__ __forceinline__ float fir_comp_planar(const float *xp, uint32_t jmax, const float *h) {
-    constexpr uint32_t D = GeoT::D, DpP = GeoT::DpP, T = GeoT::T, b = GeoT::b0, NB = T / 4;
-    constexpr int PF = GeoT::kFirBlock >= 4 ? (int)(GeoT::kFirBlock / 2) : 2;     // blocks of 4 taps in flight (FIRB 8 -> 4 blocks = 16 taps ahead)
-    static_assert(T % 4 == 0 && b % 4 == 0 && D % 4 == 0 && NB > (uint32_t)PF, "planar FIR geometry");
-    float acc = 0.f, snap = 0.f;
-    auto cand = [&](uint32_t jj) -> bool { return jj >= T / 2 + D && jj < T && ((jj - T / 2) % D) == 0; };
-    auto xoff = [&](uint32_t t) -> uint32_t { return (t / D) * DpP + (t % D); };
-    float4 x[PF], hh[PF];
-    auto load = [&](uint32_t k, int slot) {
-        x[slot] = *reinterpret_cast<const float4 *>(xp + xoff(b + 4 * k));
-        if constexpr (!GeoT::kBakedTaps) hh[slot] = *reinterpret_cast<const float4 *>(h + 4 * k);
-    };
-    auto tap = [&](uint32_t jj, int slot, int i) -> float {
-        if constexpr (GeoT::kBakedTaps) return kBakedTapTable[jj < sizeof(kBakedTapTable) / sizeof(float) ? jj : 0];
-        else return i == 0 ? hh[slot].x : (i == 1 ? hh[slot].y : (i == 2 ? hh[slot].z : hh[slot].w));
-    };
-#pragma unroll
-    for (int k = 0; k < PF; ++k) load(k, k);
-#pragma unroll
-    for (uint32_t k = 0; k < NB; ++k) {
-        const int slot = (int)(k % PF);
-        const float xs[4] = {x[slot].x, x[slot].y, x[slot].z, x[slot].w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t jj = 4 * k + i;
-            if (cand(jj)) { if (jmax == jj) snap = acc; }
-            acc = acc + xs[i] * tap(jj, slot, i);
-        }
-        asm volatile("" : "+v"(acc));                 // pin the add chain inside its block (see fir_comp)
-        if (k + PF < NB) load(k + PF, slot);           // refill the slot just consumed
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return jmax < T ? snap : acc;
-}
-
 // Packed lane-per-output FIR (FixedGeo FLAGS_ bit 2, interleaved tile with 16-byte aligned rows, PAD 2): a lane carries BOTH
 // accumulate chains of one output as a float pair and advances them with one v_pk_mul_f32 + one v_pk_add_f32 per tap —
 // the same two separately rounded operations per component as the scalar form (src/filter.rs:119), half the VALU
 // instructions.  On gfx950 a packed op occupies the pipe as long as two scalar ones, but the chain kernel is bound by
 // issue slots, not by pipe time: the component-split FIR issues 4 VALU instructions per tap and output, this one 2.  Only
 // G*W lanes take part (half the workgroup at G*W = 128).  Two taps (re, im, re, im) come with each ds_read_b128.
-template <class GeoT, bool PACKED = true>
+template <class GeoT>
 __device__ __forceinline__ float2 fir_pair(const float2 *rowp /* first LDS row of the output */, uint32_t jmax, const float *h, float2 *snap_out = nullptr) {
     constexpr uint32_t D = GeoT::D, Dp = GeoT::Dp, T = GeoT::T, b = GeoT::b0, NB = T / 4;     // blocks of 4 taps = two b128 sample reads
     constexpr int PF = 3;
@@ -975,7 +879,6 @@ __device__ __forceinline__ float2 fir_pair(const float2 *rowp /* first LDS row o
     return rowp[0];
 #endif
     v2f acc = {0.f, 0.f}, snap = {0.f, 0.f};
-    float ar = 0.f, ai = 0.f, sr = 0.f, si = 0.f;          // the scalar form keeps plain floats (a vector type would be re-packed)
     auto cand = [&](uint32_t jj) -> bool { return jj >= T / 2 + D && jj < T && ((jj - T / 2) % D) == 0; };
     auto xoff = [&](uint32_t t) -> uint32_t { return (t / D) * Dp + (t % D); };      // float2 elements
     float4 xa[PF], xb[PF], hh[PF];
@@ -983,79 +886,46 @@ __device__ __forceinline__ float2 fir_pair(const float2 *rowp /* first LDS row o
         const uint32_t t0 = b + 4 * k;                      // taps 4k..4k+3: sample pairs (4k, 4k+1) and (4k+2, 4k+3) never straddle a row (D % 4 == 0, b even)
         xa[slot] = *reinterpret_cast<const float4 *>(rowp + xoff(t0));
         xb[slot] = *reinterpret_cast<const float4 *>(rowp + xoff(t0 + 2));
-        if constexpr (!GeoT::baked_request) hh[slot] = *reinterpret_cast<const float4 *>(h + 4 * k);
-    };
-    auto tap = [&](uint32_t jj, int slot, int i) -> float {
-        if constexpr (GeoT::baked_request) return kBakedTapTable[jj < sizeof(kBakedTapTable) / sizeof(float) ? jj : 0];
-        else return i == 0 ? hh[slot].x : (i == 1 ? hh[slot].y : (i == 2 ? hh[slot].z : hh[slot].w));
+        hh[slot] = *reinterpret_cast<const float4 *>(h + 4 * k);
     };
 #pragma unroll
     for (int k = 0; k < PF; ++k) load(k, k);
-    if constexpr (PACKED && !GeoT::baked_request) {
-        // Taps from LDS, four per ds_read_b128, used straight out of the register pair they arrive in: op_sel picks the pair's
-        // low or high word for BOTH halves of the packed multiply, so no tap is ever splat into a register pair of its own
-        // (hipcc emits a v_mov per tap for that, or an s_mov per tap for immediates).  One asm statement per block of four taps:
-        // 4 v_pk_mul_f32 + 4 v_pk_add_f32 in chain order — the statement is also what keeps the adds next to their products.
-        // 11 instructions per four taps (3 LDS reads + 8 VALU) against 18 with the taps as immediates.
-#pragma unroll
-        for (uint32_t k = 0; k < NB; ++k) {
-            const int slot = (int)(k % PF);
-            if (cand(4 * k)) { if (jmax == 4 * k) snap = acc; }                 // candidates are multiples of four (D % 4 == 0, T/2 % 4 == 0)
-            static_assert((T / 2) % 4 == 0, "snapshot taps sit on block boundaries");
-            const v2f x0 = {xa[slot].x, xa[slot].y}, x1 = {xa[slot].z, xa[slot].w}, x2 = {xb[slot].x, xb[slot].y}, x3 = {xb[slot].z, xb[slot].w};
-            const v2f h01 = {hh[slot].x, hh[slot].y}, h23 = {hh[slot].z, hh[slot].w};
-            v2f p0, p1;
-            if constexpr ((GeoT::kFlags & kGeoFastFma) != 0) {
-                // QD_MODE_FAST: acc = fma(x, h, acc) — the same ascending-tap chain with ONE rounding per tap; not the reference's bits
-                asm volatile("v_pk_fma_f32 %0, %1, %5, %0 op_sel_hi:[1,0,1]\n\t"
-                             "v_pk_fma_f32 %0, %2, %5, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-                             "v_pk_fma_f32 %0, %3, %6, %0 op_sel_hi:[1,0,1]\n\t"
-                             "v_pk_fma_f32 %0, %4, %6, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
-                             : "+v"(acc)
-                             : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(h01), "v"(h23));
-            } else
-            asm volatile("v_pk_mul_f32 %1, %3, %7 op_sel_hi:[1,0]\n\t"
-                         "v_pk_mul_f32 %2, %4, %7 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-                         "v_pk_add_f32 %0, %0, %1\n\t"
-                         "v_pk_mul_f32 %1, %5, %8 op_sel_hi:[1,0]\n\t"
-                         "v_pk_add_f32 %0, %0, %2\n\t"
-                         "v_pk_mul_f32 %2, %6, %8 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-                         "v_pk_add_f32 %0, %0, %1\n\t"
-                         "v_pk_add_f32 %0, %0, %2"
-                         : "+v"(acc), "=&v"(p0), "=&v"(p1)
-                         : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(h01), "v"(h23));
-            if (k + PF < NB) load(k + PF, slot);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (snap_out) { *snap_out = make_float2(snap.x, snap.y); return make_float2(acc.x, acc.y); }
-        const v2f r = jmax < T ? snap : acc;
-        return make_float2(r.x, r.y);
-    }
+    // Taps from LDS, four per ds_read_b128, used straight out of the register pair they arrive in: op_sel picks the pair's
+    // low or high word for BOTH halves of the packed multiply, so no tap is ever splat into a register pair of its own
+    // (hipcc emits a v_mov per tap for that, or an s_mov per tap for immediates).  One asm statement per block of four taps:
+    // 4 v_pk_mul_f32 + 4 v_pk_add_f32 in chain order — the statement is also what keeps the adds next to their products.
+    // 11 instructions per four taps (3 LDS reads + 8 VALU) against 18 with the taps as immediates.
 #pragma unroll
     for (uint32_t k = 0; k < NB; ++k) {
         const int slot = (int)(k % PF);
-        const float xr[4] = {xa[slot].x, xa[slot].z, xb[slot].x, xb[slot].z}, xi[4] = {xa[slot].y, xa[slot].w, xb[slot].y, xb[slot].w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t jj = 4 * k + i;
-            const float hv = tap(jj, slot, i);
-            if constexpr (PACKED) {
-                if (cand(jj)) { if (jmax == jj) snap = acc; }
-                const v2f xs = {xr[i], xi[i]}, hs = {hv, hv};
-                acc = acc + xs * hs;                       // (re, im) * h, then +=: one v_pk_mul_f32, one v_pk_add_f32
-            } else {                                       // two scalar chains (FIR-dominated shapes: shorter dependent latency per tap)
-                if (cand(jj)) { if (jmax == jj) { sr = ar; si = ai; } }
-                ar = ar + xr[i] * hv;
-                ai = ai + xi[i] * hv;
-            }
-        }
-        if constexpr (PACKED) asm volatile("" : "+v"(acc));      // pin the add chain(s) inside their block (see fir_comp)
-        else asm volatile("" : "+v"(ar), "+v"(ai));
+        if (cand(4 * k)) { if (jmax == 4 * k) snap = acc; }                 // candidates are multiples of four (D % 4 == 0, T/2 % 4 == 0)
+        static_assert((T / 2) % 4 == 0, "snapshot taps sit on block boundaries");
+        const v2f x0 = {xa[slot].x, xa[slot].y}, x1 = {xa[slot].z, xa[slot].w}, x2 = {xb[slot].x, xb[slot].y}, x3 = {xb[slot].z, xb[slot].w};
+        const v2f h01 = {hh[slot].x, hh[slot].y}, h23 = {hh[slot].z, hh[slot].w};
+        v2f p0, p1;
+        if constexpr ((GeoT::kFlags & kGeoFastFma) != 0) {
+            // QD_MODE_FAST: acc = fma(x, h, acc) — the same ascending-tap chain with ONE rounding per tap; not the reference's bits
+            asm volatile("v_pk_fma_f32 %0, %1, %5, %0 op_sel_hi:[1,0,1]\n\t"
+                         "v_pk_fma_f32 %0, %2, %5, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+                         "v_pk_fma_f32 %0, %3, %6, %0 op_sel_hi:[1,0,1]\n\t"
+                         "v_pk_fma_f32 %0, %4, %6, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+                         : "+v"(acc)
+                         : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(h01), "v"(h23));
+        } else
+        asm volatile("v_pk_mul_f32 %1, %3, %7 op_sel_hi:[1,0]\n\t"
+                     "v_pk_mul_f32 %2, %4, %7 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+                     "v_pk_add_f32 %0, %0, %1\n\t"
+                     "v_pk_mul_f32 %1, %5, %8 op_sel_hi:[1,0]\n\t"
+                     "v_pk_add_f32 %0, %0, %2\n\t"
+                     "v_pk_mul_f32 %2, %6, %8 op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+                     "v_pk_add_f32 %0, %0, %1\n\t"
+                     "v_pk_add_f32 %0, %0, %2"
+                     : "+v"(acc), "=&v"(p0), "=&v"(p1)
+                     : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(h01), "v"(h23));
         if (k + PF < NB) load(k + PF, slot);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (!PACKED) { acc.x = ar; acc.y = ai; snap.x = sr; snap.y = si; }
-    if (snap_out) { *snap_out = make_float2(snap.x, snap.y); return make_float2(acc.x, acc.y); }      // shared-FIR mode keeps both
+    if (snap_out) { *snap_out = make_float2(snap.x, snap.y); return make_float2(acc.x, acc.y); }
     const v2f r = jmax < T ? snap : acc;
     return make_float2(r.x, r.y);
 }
@@ -1422,7 +1292,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     float2 *fb0 = raw + geo.lds_raw_elems;                    // kBatch slots of G*W decimated samples (FFT buffers)
     float2 *twl = fb0 + (size_t)kSlots * geo.G * geo.W;       // radix-4 layer twiddles (< W entries), staged once
     float *tapl = reinterpret_cast<float *>(twl + geo.W);     // FIR taps (T floats, padded to a multiple of 4)
-    float *lut = tapl + ((GeoT::kBakedTaps && NT == 256) ? 0u : ((geo.T + 3) & ~3u));   // 8-bit unpack table (8-bit formats only); baked taps take no LDS
+    float *lut = tapl + ((geo.T + 3) & ~3u);                  // 8-bit unpack table (8-bit formats only)
     // shared-FIR mode (overlapping windows): every decimated output of the tile once + its truncated variant
     float2 *dec = reinterpret_cast<float2 *>(lut + kLutElems);
     float2 *trc = dec + ((geo.G - 1) * geo.S + geo.W);
@@ -1470,7 +1340,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
         // ... and the taps: the FIR loop then contains LDS reads only, so its waits are counted
         // lgkmcnt(N) instead of a full drain per batch (scalar loads share that counter and return
         // out of order, which forces lgkmcnt(0)).
-        if constexpr (!(GeoT::kBakedTaps && NT == 256)) { for (uint32_t i = tid; i < T; i += NT) tapl[i] = P.taps[i]; }
+        for (uint32_t i = tid; i < T; i += NT) tapl[i] = P.taps[i];
     }
     __syncthreads();
 
@@ -1929,8 +1799,8 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                 float accr = 0.f, acci = 0.f;
                 float2 snap = make_float2(0.f, 0.f);
                 if constexpr (GeoT::kUnrolledShared) {
-                    // straight-line, pinned tap loop (taps may be immediates: FLAGS_ bit 1), two scalar chains per lane
-                    const float2 full = fir_pair<GeoT, !GeoT::baked_request>(rowp, jmax, tapl, &snap);
+                    // straight-line, pinned tap loop
+                    const float2 full = fir_pair<GeoT>(rowp, jmax, tapl, &snap);
                     accr = full.x; acci = full.y;
                 } else if constexpr (GeoT::kFixed) {
                     fir_span<false, GeoT, true>(geo, rowp, geo.b0, 0, T, jmax, tapl, accr, acci, &snap);
@@ -1959,24 +1829,15 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
         }
         constexpr bool kSplit = HAS_FIR && GeoT::split_ok((uint32_t)NT);
         if constexpr (kSplit) {
-            constexpr bool kPlanarK = GeoT::kPlanar && NT == 256;
-            const uint32_t t_end = kPlanarK ? 2u * geo.G * geo.W : 2u * n_out;
+            const uint32_t t_end = 2u * n_out;
             for (uint32_t t = tid; t < t_end; t += NT) {
-                // interleaved tile: lanes alternate re / im of one output; planar tile: the first G*W lanes take the re chains,
-                // the next G*W the im chains, so a wave reads ONE plane at a lane stride of DpP floats (conflict-free b128)
-                uint32_t o = t >> 1, part = t & 1u;
-                if constexpr (GeoT::kPlanar && NT == 256) { o = t & (GeoT::G * GeoT::W - 1); part = t / (GeoT::G * GeoT::W); if (o >= n_out) continue; }
+                // lanes alternate re / im of one output
+                const uint32_t o = t >> 1, part = t & 1u;
                 const uint32_t g = o >> logW, k = o & (W - 1);
                 uint32_t jmax = (W - k) * D + T / 2;
                 if (jmax > T) jmax = T;
-                float v;
-                if constexpr (GeoT::kPlanar && NT == 256) {
-                    const float *xp = reinterpret_cast<const float *>(raw) + part * GeoT::plane_floats + (size_t)(g * S + k + geo.a0) * GeoT::DpP;
-                    v = QD_DBG(P, 2) ? xp[0] : fir_comp_planar<GeoT>(xp, jmax, tapl);
-                } else {
-                    const float *xp = reinterpret_cast<const float *>(raw + (size_t)(g * S + k + geo.a0) * Dp) + part;
-                    v = QD_DBG(P, 2) ? xp[0] : fir_comp<GeoT>(xp, jmax, tapl);     // dbg: timing-only ablation
-                }
+                const float *xp = reinterpret_cast<const float *>(raw + (size_t)(g * S + k + geo.a0) * Dp) + part;
+                const float v = QD_DBG(P, 2) ? xp[0] : fir_comp<GeoT>(xp, jmax, tapl);     // dbg: timing-only ablation
                 const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
                 reinterpret_cast<float *>(fb + (g << logW) + yy + (rev4(xx, geo.layers) << geo.log_base))[part] = win_mul<GeoT>(P, k, v);
             }
@@ -2277,306 +2138,13 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     if (P.dbg == 0xdeadbeefu) reinterpret_cast<double *>(P.out)[tid] = rt_touch;   // never true: keeps rt_touch live
 }
 
-// ---------------------------------------------------------------- the role-split kernel (FixedGeo FLAGS_ bit 9)
-//
-// k_chain keeps a tile's phases in sequence on ALL waves of the workgroup: phase 1 (4 waves), barrier, FIR (2 waves), barrier,
-// with the FFT of the previous tile on a third wave — a chain of ~11 000 cycles per 128-point window on the north_star shape,
-// during which the vector units are 76 % busy (profiles/r02/cfg3p_summary.json).  The chain, not HBM, sets the rate there: the
-// same launch shape streams 17 % faster with the arithmetic ablated.
-//
-// Here the roles are split across waves and run CONCURRENTLY on one tile buffer: four producer waves (unpack -> NCO -> LDS,
-// with the next tile's rows prefetched in registers, exactly k_chain's row-aligned phase 1) and one consumer wave (FIR of the
-// window's two halves, then FFT + |X| + store), 320 threads per workgroup, five waves per SIMD.  A window's outputs split in
-// two halves of W/2; half 0 reads tile rows [0, RA], half 1 rows [RB, RCH) (RB <= RA + 1), so one step of the consumer always
-// leaves a set of rows nobody reads, and the producers refill exactly those:
-//     step 1   consumer: FIR of half 0 (rows 0 .. RA)         producers: rows RA+1 .. RCH-1 of THIS window
-//     step 2   consumer: FIR of half 1 (rows RB .. RCH-1)     producers: rows 0 .. RB-1 of the NEXT window
-//     step 3   consumer: FFT + epilogue (no raw rows)         producers: rows RB .. RA of the next window
-// One s_barrier ends each step (every wave executes the same number of barriers: no flags, no polling, nothing to deadlock).
-// The products, their order and every rounding are k_chain's: the same process_row, fir_pair and wave_fft_epilogue_fn.
-template <int V> struct IntC { static constexpr int value = V; };
-
-template <int FMT, class GeoT>
-constexpr bool pipe_geometry_ok(int rch) {
-    if constexpr (!GeoT::kFixed) return false;
-    else return GeoT::R.pipe_geometry_ok(FmtTraits<FMT>::SPL, (uint64_t)rch);
-}
-
-template <int FMT, int NCO, class GeoT, int RCH, int LB, int NT = kPipeThreads>
-__global__ __launch_bounds__(NT, LB) void k_chain_pipe(const ChainParams P) {
-    static_assert((GeoT::kFlags & kGeoWindow) == 0, "kGeoWindow: only k_chain applies the plan's window; this kernel would ignore it");
-    static_assert(NT == 320 || NT == 384, "four producer waves + the FIR wave (+ an FFT wave)");
-    constexpr bool kFftWave = NT == 384;          // a sixth wave transforms the PREVIOUS window while the FIR wave filters this one (two FFT slots)
-    using FT = FmtTraits<FMT>;
-    using Vec = typename FT::Vec;
-    constexpr int SPL = FT::SPL;
-    constexpr bool HAS_SHIFT = NCO != 0;
-    static_assert(pipe_geometry_ok<FMT, GeoT>(RCH), "role-split kernel: non-overlapping 128-point windows on a row-aligned, 16-byte-row tile");
-    constexpr uint32_t PT = 256;                                                   // producer threads
-    constexpr uint32_t W = GeoT::W, D = GeoT::D, T = GeoT::T, Dp = GeoT::Dp, HO = W / 2;
-    constexpr uint32_t ROW = PT * SPL, ROWB = ROW * FT::BPS, VECB = SPL * FT::BPS;
-    constexpr uint32_t kTileRaw = W * D + T, kRem = kTileRaw - (RCH - 1) * ROW;
-    constexpr int RA = (int)((GeoT::c + (HO - 1) * D + T - 1) / ROW);              // last row half 0 reads
-    constexpr int RB = (int)((HO * D + GeoT::c) / ROW);                            // first row half 1 reads
-    static_assert(RB <= RA + 1 && RA < RCH && RB >= 1, "half split");
-    const GeoT geo(P);
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2 *raw = reinterpret_cast<float2 *>(smem);                                // same layout as k_chain (chain_lds_bytes)
-    float2 *fb0 = raw + geo.lds_raw_elems;
-    float2 *twl = fb0 + (size_t)GeoT::kBatch * W;
-    float *tapl = reinterpret_cast<float *>(twl + W);
-    float *lut = tapl + ((T + 3) & ~3u);
-    constexpr uint32_t kLutElems = (FMT == 1 || FMT == 2) ? 256u : 0u;
-    uint32_t *wq = reinterpret_cast<uint32_t *>(lut + kLutElems) + 4 * GeoT::kBatch;
-
-    const uint32_t tid = threadIdx.x;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool producer = wave < 4;
-    {
-        const uint32_t n_tw = W - geo.base_len;
-        for (uint32_t i = tid; i < n_tw; i += NT) twl[i] = P.tw[i];
-        for (uint32_t i = tid; i < T; i += NT) tapl[i] = P.taps[i];
-    }
-    __syncthreads();
-
-    const uint64_t n_tiles = P.n_windows;
-    // tile walk and dynamic tile queue: as in k_chain
-    uint64_t walk_base = 0, walk_local = blockIdx.x, walk_step = gridDim.x, walk_limit = n_tiles;
-    const bool xcd_walk = (gridDim.x & 7u) == 0 && n_tiles >= 8;
-    const uint64_t n8 = (n_tiles + 7) / 8;
-    auto xcd_limit = [&](uint32_t x) -> uint64_t { const uint64_t b = (uint64_t)x * n8; return b >= n_tiles ? 0 : (n_tiles - b < n8 ? n_tiles - b : n8); };
-    if (xcd_walk) {
-        walk_base = (uint64_t)(blockIdx.x & 7u) * n8;
-        walk_local = blockIdx.x >> 3;
-        walk_step = gridDim.x >> 3;
-        walk_limit = xcd_limit(blockIdx.x & 7u);
-    }
-    auto walk_tile = [&](uint64_t local) -> uint64_t { return local < walk_limit ? walk_base + local : n_tiles; };
-    const bool dyn = P.work != nullptr && xcd_walk;
-    const uint32_t my_x = blockIdx.x & 7u;
-    auto claim_resolve = [&](unsigned long long got) -> uint64_t {
-        uint32_t mx = my_x;
-        asm volatile("" : "+s"(mx));
-        const uint64_t dyn_base = 2 * walk_step;
-        if (got + dyn_base < xcd_limit(mx)) return (uint64_t)mx * n8 + dyn_base + got;
-#pragma unroll 1
-        for (uint32_t k = 1; k < 8; ++k) {                                // own eighth exhausted: help the others
-            const uint32_t xx = (mx + k) & 7u;
-            const uint64_t lim = xcd_limit(xx);
-            if (lim <= dyn_base) continue;
-            const unsigned long long i = atomicAdd(&P.work[16 * xx], 1ull);
-            if (i + dyn_base < lim) return (uint64_t)xx * n8 + dyn_base + i;
-        }
-        return n_tiles;
-    };
-    uint64_t tile, tile_n;
-    tile = walk_tile(walk_local);                                         // static for the first two rounds, dynamic or static after
-    tile_n = walk_tile(walk_local + walk_step);
-
-    // ---- producer state
-    LaneRot lr[SPL];
-    if (HAS_SHIFT && producer) {
-#pragma unroll
-        for (int u = 0; u < SPL; ++u) {
-            const uint32_t j = tid * SPL + u;
-            const double2 cs = P.jtab[j];
-            lr[u].jf = (double)j; lr[u].c = cs.x; lr[u].s = cs.y;
-        }
-    }
-    const uint32_t lane_pad = pad_index(geo, tid * SPL);
-    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-    typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
-    auto n_start_of = [&](uint64_t t) -> uint64_t { return (P.first_window + t) * ((uint64_t)GeoT::S * D); };
-    auto rsrc_of = [&](uint64_t t) {
-        const uint64_t ns = n_start_of(t);
-        // t < n_tiles: ns is a window start of this launch, inside the slab launch_chain checked (see k_chain's row-aligned phase 1)
-        const uint64_t left = (P.src_first + P.src_count - ns) * FT::BPS;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(P.src) + (ns - P.src_first) * FT::BPS, 0,
-                                                 left > 0xffffffffull ? 0xffffffffu : (uint32_t)left, 0x00020000);
-    };
-    Vec pf[RCH];
-    auto load_row = [&](const decltype(rsrc_of(0)) &rsrc, int i) {
-        constexpr uint32_t kLastVec = ((kRem * FT::BPS - 1) / VECB) * VECB;
-        uint32_t voff = tid * VECB;
-        if (i + 1 == RCH && kRem != ROW) voff = voff < kLastVec ? voff : kLastVec;
-        constexpr int aux = ct_load_aux(GeoT::kFlags);
-        if constexpr (sizeof(Vec) == 16) {
-            const v4u_t w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)(i * ROWB), aux);
-            pf[i].x = w.x; pf[i].y = w.y; pf[i].z = w.z; pf[i].w = w.w;
-        } else {
-            const v2u_t w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, (int)(i * ROWB), aux);
-            pf[i].x = w.x; pf[i].y = w.y;
-        }
-    };
-    double rt_touch = 0.0;
-    // rows [I0, I1) of tile t_cur: consume the prefetched row, park it, refill the slot with the same row of t_refill
-    auto produce = [&](auto i0c, auto i1c, uint64_t t_cur, uint64_t t_refill) {
-        constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;
-        if constexpr (I0 < I1) {
-            const uint64_t ns = n_start_of(t_cur);
-            const uint64_t t_pf = t_refill < n_tiles ? t_refill : t_cur;           // last tile of this workgroup: harmless re-loads
-            const auto rsrc = rsrc_of(t_pf);
-            const_f64_p rows = (const_f64_p)(uintptr_t)(P.rowtab + (ns / ROW - P.rowtab_row0));
-            if constexpr (HAS_SHIFT && I0 == 0) {                                   // L2 touch of the NEXT tile's row bases (see prefetch_rowtab)
-                uint32_t r = tid < (uint32_t)RCH ? tid : (uint32_t)RCH - 1;
-                asm volatile("" : "+v"(r));
-                rt_touch += P.rowtab[n_start_of(t_pf) / ROW - P.rowtab_row0 + r].c;
-            }
-            TileGeo gl{};
-            gl.tile_raw = kTileRaw;
-            RowBase rb_next{};
-            if constexpr (HAS_SHIFT) rb_next = load_rowbase_at(rows, I0);
-#pragma unroll
-            for (int i = I0; i < I1; ++i) {
-                const Vec v = pf[i];
-                const RowBase rb = rb_next;
-                if constexpr (HAS_SHIFT) { if (i + 1 < I1) rb_next = load_rowbase_at(rows, i + 1); }
-                if (i + 1 < RCH || kRem == ROW) {
-                    process_row<FMT, PT, NCO, true>(P, geo, gl, i * (int)ROW, tid, v, rb, lr, lane_pad, lut, raw);
-                } else {
-                    if (tid * SPL < kRem) process_row<FMT, PT, NCO, (kRem % SPL) == 0>(P, geo, gl, i * (int)ROW, tid, v, rb, lr, lane_pad, lut, raw);
-                }
-                __builtin_amdgcn_sched_barrier(0);       // refill slot i only after row i is consumed (see k_chain)
-                load_row(rsrc, i);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
-    // ---- consumer: one half of the window's FIR outputs (k = half * HO + lane), scattered for the FFT
-    auto fir_half = [&](uint32_t half, float2 *fb) {
-        uint32_t lane = tid & 63u;
-        asm volatile("" : "+v"(lane));                   // per-lane LDS addresses are rebuilt per step, not hoisted and spilled
-        const uint32_t k = half * HO + lane;
-        uint32_t jmax = (W - k) * D + T / 2;
-        if (jmax > T) jmax = T;
-        const float2 *rp = raw + (size_t)(k + geo.a0) * Dp;
-        const float2 v = fir_pair<GeoT>(rp, jmax, tapl);
-        constexpr uint32_t log_width = 2 * GeoT::layers;
-        const uint32_t xx = k & ((1u << log_width) - 1), yy = k >> log_width;
-        fb[yy + (rev4(xx, geo.layers) << geo.log_base)] = v;
-    };
-
-    // Each role runs its OWN loop (same trip count, three barriers per trip): in one shared loop the producers' prefetch and
-    // lane registers would be live across the consumer's FIR as well and the kernel would need the SUM of the two register
-    // sets instead of the larger one (114 VGPRs against the 96 that five waves per SIMD allow).
-    bool cur_valid = tile < n_tiles;
-    QD_STAMP_DECL
-    auto next_after = [&]() -> uint64_t {                                        // the tile after `tile_n`, read behind step 1's barrier
-        if (dyn) return ((uint64_t)__builtin_amdgcn_readfirstlane(wq[1]) << 32) | __builtin_amdgcn_readfirstlane(wq[0]);
-        walk_local += walk_step;
-        return walk_tile(walk_local + walk_step);
-    };
-    if (producer) {
-        __builtin_amdgcn_s_setprio(0);
-        if (cur_valid) {
-            const auto rsrc = rsrc_of(tile);
-#pragma unroll
-            for (int i = 0; i < RCH; ++i) load_row(rsrc, i);
-            produce(IntC<0>{}, IntC<RB>{}, tile, tile_n);
-            produce(IntC<RB>{}, IntC<RA + 1>{}, tile, tile_n);
-        }
-        // The claim for the tile after next is one atomic whose reply takes ~1-2 us under load: it is issued a whole step
-        // before its reply is read (behind step 1's barrier it is already needed by every wave).
-        unsigned long long claim = 0;
-        if (dyn && tid == 0) claim = atomicAdd(&P.work[16 * my_x], 1ull);
-        __syncthreads();
-        QD_STAMP_START();
-        while (cur_valid) {
-            produce(IntC<RA + 1>{}, IntC<RCH>{}, tile, tile_n);                    // step 1
-            if (dyn && tid == 0) {
-                const uint64_t t2 = claim_resolve(claim);
-                wq[0] = (uint32_t)t2; wq[1] = (uint32_t)(t2 >> 32);
-            }
-            QD_STAMP_AT(0);
-            __syncthreads();
-            QD_STAMP_AT(1);
-            const uint64_t tile_nn = next_after();
-            const bool next_valid = tile_n < n_tiles;
-            if (dyn && tid == 0 && next_valid) claim = atomicAdd(&P.work[16 * my_x], 1ull);     // read at the end of the next step 1
-            if (next_valid) produce(IntC<0>{}, IntC<RB>{}, tile_n, tile_nn);       // step 2
-            QD_STAMP_AT(2);
-            __syncthreads();
-            QD_STAMP_AT(3);
-            // step 3: the row(s) both halves read.  With the FFT on its own wave nothing else runs meanwhile, so go first.
-            if constexpr (kFftWave) __builtin_amdgcn_s_setprio(3);
-            if (next_valid) produce(IntC<RB>{}, IntC<RA + 1>{}, tile_n, tile_nn);
-            if constexpr (kFftWave) __builtin_amdgcn_s_setprio(0);
-            QD_STAMP_AT(4);
-            __syncthreads();
-            QD_STAMP_AT(5);
-            QD_STAMP_TILE();
-            tile = tile_n; tile_n = tile_nn; cur_valid = next_valid;
-        }
-    } else if (wave == 4) {
-        __builtin_amdgcn_s_setprio(2);
-        uint32_t par = 0;
-        __syncthreads();
-        QD_STAMP_START();
-        while (cur_valid) {
-            float2 *fb = fb0 + (kFftWave ? par * W : 0u);
-            fir_half(0, fb);                                                       // step 1
-            QD_STAMP_AT(0);
-            __syncthreads();
-            QD_STAMP_AT(1);
-            const uint64_t tile_nn = next_after();
-            const bool next_valid = tile_n < n_tiles;
-            fir_half(1, fb);                                                       // step 2
-            QD_STAMP_AT(2);
-            __syncthreads();
-            QD_STAMP_AT(3);
-            if constexpr (!kFftWave) {                                             // step 3
-                __builtin_amdgcn_s_setprio(3);
-                wave_fft_epilogue_fn<GeoT>(P, geo, twl, fb, P.first_window + tile, 1u, tid);
-                __builtin_amdgcn_s_setprio(2);
-            }
-            QD_STAMP_AT(4);
-            __syncthreads();
-            QD_STAMP_AT(5);
-            par ^= 1u;
-            tile = tile_n; tile_n = tile_nn; cur_valid = next_valid;
-        }
-    } else {
-        // the FFT wave: window i-1 (parked in the other slot) during step 1 of window i
-        __builtin_amdgcn_s_setprio(1);
-        uint32_t par = 0;
-        uint64_t prev = n_tiles;
-        __syncthreads();
-        QD_STAMP_START();
-        while (cur_valid) {
-            if (prev < n_tiles) wave_fft_epilogue_fn<GeoT>(P, geo, twl, fb0 + (par ^ 1u) * W, P.first_window + prev, 1u, tid);
-            QD_STAMP_AT(0);
-            __syncthreads();
-            QD_STAMP_AT(1);
-            const uint64_t tile_nn = next_after();
-            const bool next_valid = tile_n < n_tiles;
-            __syncthreads();
-            QD_STAMP_AT(3);
-            __syncthreads();
-            QD_STAMP_AT(5);
-            par ^= 1u;
-            prev = tile;
-            tile = tile_n; tile_n = tile_nn; cur_valid = next_valid;
-        }
-        if (prev < n_tiles) wave_fft_epilogue_fn<GeoT>(P, geo, twl, fb0 + (par ^ 1u) * W, P.first_window + prev, 1u, tid);
-    }
-    QD_STAMP_FLUSH();
-    if (dyn && tid == 0) {       // the last workgroup to leave re-arms the queue for the next launch
-        if (atomicAdd(&P.work[16 * 8], 1ull) == (unsigned long long)gridDim.x - 1) {
-#pragma unroll
-            for (int x = 0; x <= 8; ++x) P.work[16 * x] = 0;
-        }
-    }
-    if (P.dbg == 0xdeadbeefu) reinterpret_cast<double *>(P.out)[tid] = rt_touch;   // never true: keeps rt_touch live
-}
-
 // ---------------------------------------------------------------- the three-stage kernel for overlapping windows (FixedGeo FLAGS_ bit 15)
 //
 // Overlapping-window chains with long filters (cfg3, the README's FSK chain: 400 taps, W = 64, S = 16) run k_chain with ONE
 // ~156 KiB tile of 27 windows per CU, so a tile's phases — unpack + NCO, the shared FIR, gather + FFT, |X| — run strictly one
 // after the other and add up (13 k + 12.4 k + 6.4 k stamped cycles): the vector units idle while the FIR
-// waits on LDS, the LDS idles while the NCO computes.  Unlike the 128-point shapes (k_chain_pipe), here a tile's FIR is ONE pass
-// over all of the tile's outputs, and two half-size tiles fit in LDS: so the three stages run CONCURRENTLY on consecutive tiles,
+// waits on LDS, the LDS idles while the NCO computes.  Here a tile's FIR is ONE pass over all of the
+// tile's outputs, and two half-size tiles fit in LDS: so the three stages run CONCURRENTLY on consecutive tiles,
 //     waves 0-7   (512 threads)  phase 1 of tile i+1 into raw[(i+1)&1]   (next tile's rows prefetched in registers)
 //     waves 8-11  (256 lanes)    shared FIR of tile i from raw[i&1] into dec / trc[i&1]   (fir_pair, packed, taps from LDS)
 //     waves 12-15 (4 waves)      tile i-1: gather from dec / trc[(i-1)&1], FFT, |X|, store — each wave its own windows, wave-local
@@ -2773,7 +2341,7 @@ __global__ __launch_bounds__(kPipe3Threads, LB) void k_chain_pipe3(const ChainPa
                     }
                     const float2 *rowp = raw0 + (size_t)par * geo.lds_raw_elems + (size_t)(qi + geo.a0) * Dp;
                     float2 snap = make_float2(0.f, 0.f);
-                    const float2 full = fir_pair<GeoT, true>(rowp, jmax, tapl, &snap);
+                    const float2 full = fir_pair<GeoT>(rowp, jmax, tapl, &snap);
                     float2 *dec = dec0 + (size_t)par * 2 * QP, *trc = dec + QP;
                     dec[qi] = full;
                     if (jmax < T) trc[qi] = snap;
@@ -3150,7 +2718,7 @@ __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512),
                     uint32_t taps_off = (uint32_t)(uintptr_t)(lds_f32_p)tapl;            // the LDS byte offset, in a VGPR the compiler cannot see through
                     asm volatile("" : "+v"(taps_off));
                     const float *taps_v = (const float *)(lds_f32_p)(uintptr_t)taps_off;
-                    const float2 full = fir_pair<GeoT, true>(rowp, jmax, taps_v, &snap);
+                    const float2 full = fir_pair<GeoT>(rowp, jmax, taps_v, &snap);
                     const uint32_t pos = q % DR;
                     if constexpr (kWrite) {
                         // do_write / LowPass::read_at output (src/lib.rs:206-209): the decimated cf32 samples themselves, in stream order

@@ -16,19 +16,14 @@ typedef unsigned int uint32_t; typedef int int32_t; typedef unsigned long long u
 namespace qd {
 
 // ---------------------------------------------------------------- FixedGeo FLAGS_ bits (qd_plan_info.kernel_flags, tile_hint[6] >> 8)
-constexpr uint32_t kGeoPlanar = 1;              // bit 0: the raw tile as two f32 planes (component-split FIR reads four taps per ds_read_b128)
-constexpr uint32_t kGeoBakedTaps = 2;           // bit 1: the plan's filter as immediates (plan-time builds of the planar FIR)
+// Bits 0, 1, 4 and 9-12 selected experiments that lost and were removed; they stay reserved, so every other
+// bit keeps its number, and plan creation refuses a tile hint that carries one (kHintGeoBits).
 constexpr uint32_t kGeoNoSplit = 4;             // bit 2: no component-split FIR; on a 16-byte-row tile the packed lane-per-output FIR (fir_pair)
 constexpr uint32_t kGeoFastP1 = 8;              // bit 3: row-aligned phase 1 (tiles start on row boundaries, a compile-time number of rows)
-constexpr uint32_t kGeoPackedSpan = 16;         // bit 4: packed span FIR
 constexpr uint32_t kGeoUnrolledFir = 32;        // bit 5: the shared FIR of overlapping windows as straight-line code
 constexpr uint32_t kGeoDeferFft = 64;           // bit 6: the previous tile's FFT + epilogue on a wave the FIR leaves idle (two FFT slots)
 constexpr uint32_t kGeoPackedTile = 128;        // bit 7: two outputs per lane as straight-line packed code (fir_tiled2_pk)
 constexpr uint32_t kGeoNtLoads = 256;           // bit 8: phase-1 stream loads non-temporal
-constexpr uint32_t kGeoPipe = 512;              // bit 9: the role-split kernel (k_chain_pipe)
-constexpr uint32_t kGeoPipeFftWave = 1024;      // bit 10: ... with a sixth wave for the FFT + epilogue (384 threads, two FFT slots)
-constexpr uint32_t kGeoLoadSc0 = 2048;          // bit 11: development: sc0 on the phase-1 stream loads (with kGeoNtLoads)
-constexpr uint32_t kGeoLoadSc1 = 4096;          // bit 12: development: sc1 on the phase-1 stream loads
 constexpr uint32_t kGeoHalfTile = 8192;         // bit 13: the tile buffer holds HALF a window's FIR input, two passes per window
 constexpr uint32_t kGeoFastFma = 16384;         // bit 14: QD_MODE_FAST — the packed FIRs fuse multiply and add, one rounding per tap
 constexpr uint32_t kGeoPipe3 = 32768;           // bit 15: the three-stage kernel for overlapping windows (k_chain_pipe3)
@@ -40,40 +35,41 @@ constexpr uint32_t kGeoSparkReg = 1048576;      // bit 20: ... with the first FF
 constexpr uint32_t kGeoSparkDirect = 2097152;   // bit 21: ... a window of 2 ... 8 points per lane, no LDS (k_spark0)
 constexpr uint32_t kGeoWindow = 1u << 22;       // bit 22: applies the plan's window (ChainParams::window) where phase 2 stores into the FFT buffer; k_chain only
 
-// cache policy (buffer-load aux operand) of the phase-1 stream loads: nt / sc0 / sc1
-constexpr int ct_load_aux(uint32_t flags) { return ((flags & kGeoNtLoads) ? 2 : 0) | ((flags & kGeoLoadSc0) ? 1 : 0) | ((flags & kGeoLoadSc1) ? 16 : 0); }
+// the variant bits a tile hint may carry: the ones above below bit 19 (the wave-local kernels are not hinted)
+constexpr uint32_t kHintGeoBits = kGeoNoSplit | kGeoFastP1 | kGeoUnrolledFir | kGeoDeferFft | kGeoPackedTile | kGeoNtLoads | kGeoHalfTile | kGeoFastFma |
+                                  kGeoPipe3 | kGeoNtInner | kGeoStream | kGeoWriteSink;
+
+// cache policy (buffer-load aux operand) of the phase-1 stream loads: nt
+constexpr int ct_load_aux(uint32_t flags) { return (flags & kGeoNtLoads) ? 2 : 0; }
 
 // ---------------------------------------------------------------- which kernel a flags word means
 constexpr int kThreads = 256;
-constexpr int kPipeThreads = 320;
 constexpr int kPipe3Threads = 1024, kPipe3Prod = 512;
 constexpr uint32_t kSparkRow = 512;          // samples per NCO row of the wave-local kernels, every format
 constexpr uint32_t kSparkMaxW = 1024;
 
-enum Family { kFamChain, kFamPipe, kFamPipe3, kFamPipe3s, kFamSpark, kFamSpark2, kFamSpark0 };
+enum Family { kFamChain, kFamPipe3, kFamPipe3s, kFamSpark, kFamSpark2, kFamSpark0 };
 
 constexpr Family family_of(uint32_t flags) {
     return (flags & kGeoSpark) ? ((flags & kGeoSparkDirect) ? kFamSpark0 : (flags & kGeoSparkReg) ? kFamSpark2 : kFamSpark)
-         : (flags & kGeoPipe3) ? ((flags & kGeoStream) ? kFamPipe3s : kFamPipe3)
-         : (flags & kGeoPipe) ? kFamPipe : kFamChain;
+         : (flags & kGeoPipe3) ? ((flags & kGeoStream) ? kFamPipe3s : kFamPipe3) : kFamChain;
 }
 
 struct FamilyRow {
     const char *name;
-    bool on_rows;       // its tiles always start on row boundaries (k_chain / k_chain_pipe: only with kGeoFastP1)
+    bool on_rows;       // its tiles always start on row boundaries (k_chain: only with kGeoFastP1)
 };
 constexpr FamilyRow kFamilies[] = {
-    {"qd::k_chain", false}, {"qd::k_chain_pipe", false}, {"qd::k_chain_pipe3", true}, {"qd::k_chain_pipe3s", true},
+    {"qd::k_chain", false}, {"qd::k_chain_pipe3", true}, {"qd::k_chain_pipe3s", true},
     {"qd::k_spark", true},  {"qd::k_spark2", true},      {"qd::k_spark0", true},
 };
 constexpr const char *family_name(uint32_t flags) { return kFamilies[family_of(flags)].name; }
 // row-aligned kernels: a launch whose first window is off the row grid goes to the per-sample kernel
 constexpr bool row_aligned(uint32_t flags) { return kFamilies[family_of(flags)].on_rows || (flags & kGeoFastP1) != 0; }
-// workgroup size: nt row-loading threads plus the consumer waves of the role-split and three-stage kernels; the wave-local kernels
+// workgroup size: nt row-loading threads plus the consumer waves of the three-stage kernels; the wave-local kernels
 // run four waves per workgroup whatever their row geometry (their nt = 512 / SPL only lays out the NCO tables)
 constexpr int family_threads(int nt, uint32_t flags) {
     switch (family_of(flags)) {
-    case kFamPipe: return nt + ((flags & kGeoPipeFftWave) ? 128 : 64);
     case kFamPipe3: return nt + 512;
     case kFamPipe3s: return nt + ((flags & kGeoWriteSink) ? 256 : 512);
     case kFamChain: return nt;
@@ -100,26 +96,20 @@ constexpr uint64_t ct_tile_raw(uint64_t W, uint64_t S, uint64_t D, uint64_t T, u
 constexpr uint64_t ct_raw_elems(uint64_t W, uint64_t S, uint64_t D, uint64_t T, uint64_t G, uint64_t pad_per_row = 1) {
     return ct_tile_elems(ct_tile_raw(W, S, D, T, G), D, G * W, pad_per_row);
 }
-// planar raw tile (kGeoPlanar): floats per plane, rows of D floats at a 16-byte aligned pitch with pitch / 4 odd
-constexpr uint64_t ct_planar_pitch(uint64_t D) { return ((D / 4) % 2 == 1) ? D : D + 4; }
-constexpr uint64_t ct_plane_floats(uint64_t W, uint64_t S, uint64_t D, uint64_t T, uint64_t G) {
-    return ((ct_tile_raw(W, S, D, T, G) / D + 1) * ct_planar_pitch(D) + 7) & ~7ull;
-}
 
 // ---------------------------------------------------------------- FixedGeo<W, S, D, T, G, FIRB, FIRR, PAD, BATCH, FLAGS>
 // (what each constant means is said where the kernels use it: FixedGeo in qd_chain.h)
 struct FixedRules {
     uint64_t W, S, D, T, G;
     uint32_t flags, kBatch, kFirBlock;
-    uint64_t DpP, plane_floats;
-    bool planar_geometry, baked_request, kFirTile4;
+    bool kFirTile4;
     uint32_t kFirTile, pshift, logW, kPad, dshift, dmagic, log_base, base_len, layers;
     uint64_t PD, Dp, c, a0, b0, T_fast, a1, b1;
     bool kHalfTile;
-    uint64_t kHalfOut, kHalfRaw, tile_raw, pass_raw, lds_raw_elems_std, kNtrunc, Q;
-    bool kShared, kPairFir, kUnrolledShared, kPackedTile, kPlanar, kBakedTaps;
+    uint64_t kHalfOut, kHalfRaw, tile_raw, pass_raw, kNtrunc, Q;
+    bool kShared, kPairFir, kUnrolledShared, kPackedTile;
     uint64_t lds_raw_elems;        // float2 elements of the raw tile as the kernel lays it out
-    uint64_t lds_raw_alloc;        // ... as the host sizes it: rows padded as ASKED (PAD), never less than the planes a planar request needs
+    uint64_t lds_raw_alloc;        // ... as the host sizes it: rows padded as ASKED (PAD)
     // component-split FIR (fir_comp): mid-length filters whose tile leaves at least half the lanes without an output
     constexpr bool split_ok(uint64_t nt) const {
         return !(flags & kGeoNoSplit) && !kShared && kFirTile == 1 && kPad != 2 && D % 8 == 0 && T >= 64 && 2 * G * W <= nt;
@@ -150,10 +140,6 @@ struct FixedRules {
         return whole && aligned && ((kHalfTile ? kHalfOut : S) * D) % (nt * spl) == 0 && (G * S * D) % (nt * spl) == 0 && rch == rows(nt, spl) &&
                D % spl == 0 && (flags & kGeoFastP1);
     }
-    // k_chain_pipe: non-overlapping 128-point windows on a row-aligned, 16-byte-row tile (256 producer threads)
-    constexpr bool pipe_geometry_ok(uint64_t spl, uint64_t rch) const {
-        return G == 1 && S == W && kPairFir && W == 128 && (S * D) % (256 * spl) == 0 && rch == ct_rows(W * D + T, 256 * spl) && D % spl == 0 && T > D;
-    }
     // k_chain_pipe3: overlapping windows, straight-line shared FIR, <= 256 outputs per tile, row-aligned tiles (512 producer threads)
     constexpr bool pipe3_geometry_ok(uint64_t spl, uint64_t rch) const {
         return kShared && kUnrolledShared && Q <= 256 && (G * S * D) % (kPipe3Prod * spl) == 0 && rch == ct_rows(tile_raw, kPipe3Prod * spl) &&
@@ -179,10 +165,6 @@ constexpr FixedRules fixed_rules(uint64_t W, uint64_t S, uint64_t D, uint64_t T,
     r.c = T - T / 2;
     r.tile_raw = ct_tile_raw(W, S, D, T, G);
     r.Q = (G - 1) * S + W;
-    r.DpP = ct_planar_pitch(D);
-    r.plane_floats = ct_plane_floats(W, S, D, T, G);
-    r.planar_geometry = (flags & kGeoPlanar) && ct_pow2(D) && D % 8 == 0 && T % 4 == 0 && (r.c % D) % 4 == 0 && T >= 64 && ct_pow2(G * W);
-    r.baked_request = (flags & kGeoBakedTaps) != 0;
     // outputs per lane in the FIR (register tiling).  The straight-line packed two-output form walks 4-sample blocks and needs
     // 4-aligned geometry only; the register-tiled form needs 8-aligned geometry and at least three interior 4-sample blocks
     r.kFirTile4 = firr == 2 && (flags & kGeoPackedTile) && pad == 2 && D % 4 == 0 && r.c % 4 == 0 && T % 4 == 0 && (T / 2) % 4 == 0 && W % 2 == 0 && S % 2 == 0 &&
@@ -207,17 +189,14 @@ constexpr FixedRules fixed_rules(uint64_t W, uint64_t S, uint64_t D, uint64_t T,
     r.kHalfOut = W / 2;
     r.kHalfRaw = r.c + (r.kHalfOut - 1) * D + T;
     r.pass_raw = r.kHalfTile ? r.kHalfRaw : r.tile_raw;      // raw samples of one pass
-    r.lds_raw_elems_std = ct_tile_elems(r.pass_raw, D, G * W, r.kPad ? r.kPad : 1);
+    r.lds_raw_elems = ct_tile_elems(r.pass_raw, D, G * W, r.kPad ? r.kPad : 1);
     r.kNtrunc = r.c ? (r.c + D - 1) / D - 1 : 0;
     r.kShared = T > 0 && S < W && r.kNtrunc <= S;     // shared-FIR mode
     const bool pair_geo = r.kFirTile == 1 && r.kPad == 2 && T % 4 == 0 && r.b0 % 2 == 0 && D % 4 == 0 && T >= 32;
     r.kPairFir = (flags & kGeoNoSplit) && !r.kShared && pair_geo;             // packed lane-per-output FIR (fir_pair) on a 16-byte-row tile
     r.kUnrolledShared = (flags & kGeoUnrolledFir) && r.kShared && pair_geo;
     r.kPackedTile = (flags & kGeoPackedTile) && !r.kShared && r.kFirTile == 2 && r.kPad == 2 && (T / 2) % 4 == 0 && D / 4 <= 8;
-    r.kPlanar = r.planar_geometry && r.split_ok(256);       // the planar layout serves the component-split FIR of 256-thread tiles
-    r.kBakedTaps = r.baked_request && r.kPlanar;            // only the planar FIR takes its taps as immediates
-    r.lds_raw_elems = r.kPlanar ? r.plane_floats : r.lds_raw_elems_std;
-    r.lds_raw_alloc = ct_max(ct_tile_elems(r.pass_raw, D, G * W, pad), ((flags & kGeoPlanar) && r.pass_raw < (1u << 24)) ? r.plane_floats : 0);
+    r.lds_raw_alloc = ct_tile_elems(r.pass_raw, D, G * W, pad);
     return r;
 }
 
@@ -262,11 +241,10 @@ constexpr Pipe3sRules pipe3s_rules(uint64_t spl, uint64_t pt, const FixedRules &
 }
 
 // ---------------------------------------------------------------- dynamic LDS of every family's layout, in bytes
-// k_chain / k_chain_pipe: raw tile | batch x G*W FFT buffers | twiddles | taps | 8-bit LUT | shared-FIR dec + trc | batch bookkeeping |
+// k_chain: raw tile | batch x G*W FFT buffers | twiddles | taps | 8-bit LUT | shared-FIR dec + trc | batch bookkeeping |
 // tile-queue hand-over
 constexpr uint64_t chain_lds_bytes(const FixedRules &g, bool lut8) {
-    const bool baked = g.baked_request && (g.flags & kGeoPlanar) && g.pass_raw < (1u << 24);
-    return g.lds_raw_alloc * 8 + g.kBatch * g.G * g.W * 8 + g.W * 8 + (baked ? 0 : ct_taps_bytes(g.T)) + (lut8 ? 256 * 4 : 0) +
+    return g.lds_raw_alloc * 8 + g.kBatch * g.G * g.W * 8 + g.W * 8 + ct_taps_bytes(g.T) + (lut8 ? 256 * 4 : 0) +
            ((g.T && g.S < g.W) ? 2 * g.Q * 8 : 0) + g.kBatch * 16 + 16;
 }
 // the runtime-geometry kernels (interleaved tile, pad 1, batch 1, taps in LDS, always the full tile) run inside the same allocation

@@ -14,7 +14,7 @@ struct FixedEntry {
     int nt;              // workgroup size
     int pad;             // LDS pad elements per row (FixedGeo::kPad request: 1 or 2)
     int batch;           // tiles per FFT batch (FixedGeo::kBatch)
-    int flags;           // FixedGeo FLAGS_ (kGeoPlanar | kGeoNoSplit | kGeoFastP1 | ...)
+    int flags;           // FixedGeo FLAGS_ (kGeoNoSplit | kGeoFastP1 | ...)
     chain_fn fn;
     const char *name;
 };

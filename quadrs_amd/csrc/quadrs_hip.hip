@@ -473,11 +473,10 @@ const FixedEntry *find_fixed(int fmt, int nco, uint32_t W, uint32_t S, uint32_t 
 // streams of 1 GiB and more, for tile hints and for QD_MODE_FAST (QD_KERNEL_SPECIALISE: always).
 struct JitKey {
     int fmt, nco, fir, rch, whole, lb, nt; uint32_t W, S, D, T, G; uint32_t firb = 8, firr = 1; int noslp = 0; uint32_t pad = 1, batch = 1, flags = 0;
-    uint64_t taps_hash = 0;        // baked-taps builds: FNV-1a of the filter (the code depends on it)
     int epi = 0;                   // kernels that take the sink as a template argument (k_spark2)
     bool operator<(const JitKey &o) const {
-        return std::tie(fmt, nco, fir, rch, whole, lb, nt, W, S, D, T, G, firb, firr, noslp, pad, batch, flags, taps_hash, epi) <
-               std::tie(o.fmt, o.nco, o.fir, o.rch, o.whole, o.lb, o.nt, o.W, o.S, o.D, o.T, o.G, o.firb, o.firr, o.noslp, o.pad, o.batch, o.flags, o.taps_hash, o.epi);
+        return std::tie(fmt, nco, fir, rch, whole, lb, nt, W, S, D, T, G, firb, firr, noslp, pad, batch, flags, epi) <
+               std::tie(o.fmt, o.nco, o.fir, o.rch, o.whole, o.lb, o.nt, o.W, o.S, o.D, o.T, o.G, o.firb, o.firr, o.noslp, o.pad, o.batch, o.flags, o.epi);
     }
 };
 std::mutex g_jit_mu;
@@ -529,7 +528,7 @@ std::string jit_cache_dir() {
 
 // returns nullptr (and leaves a message in *why) when specialisation is not possible; with may_compile false only the
 // in-process and on-disk caches are consulted
-hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compile = true, const std::vector<float> *taps = nullptr) {
+hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compile = true) {
     std::lock_guard<std::mutex> lock(g_jit_mu);
     int jit_dev = 0;
     (void)hipGetDevice(&jit_dev);
@@ -554,19 +553,11 @@ hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compi
     case kFamSpark: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, k.epi); break;                          // rch = chunks per tile
     case kFamPipe3s: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, k.nt); break;                          // rch = rows per step, nt = producer threads
     case kFamPipe3: snprintf(tail, sizeof tail, "%d, %d", k.rch, k.lb); break;
-    case kFamPipe: snprintf(tail, sizeof tail, "%d, %d, %d", k.rch, k.lb, family_threads(256, k.flags)); break;
     default: snprintf(tail, sizeof tail, "%s, %d, %s, true, %d, %d", k.fir ? "true" : "false", k.rch, k.whole ? "true" : "false", k.lb, k.nt); break;
     }
     if (fam == kFamSpark0) snprintf(name, sizeof name, "%s<%d, %s, %s>", family_name(k.flags), k.fmt, geo, tail);      // (no shift: no NCO argument)
     else snprintf(name, sizeof name, "%s<%d, %d, %s, %s>", family_name(k.flags), k.fmt, k.nco, geo, tail);
-    std::string src;
-    if ((k.flags & kGeoBakedTaps) && taps && !taps->empty()) {       // the plan's filter as exact hex-float literals
-        src += "#define QD_BAKED_TAPS_LIST ";
-        char lit[48];
-        for (size_t i = 0; i < taps->size(); ++i) { snprintf(lit, sizeof lit, "%s%af", i ? ", " : "", (double)(*taps)[i]); src += lit; }
-        src += "\n";
-    }
-    src += std::string("#include \"qd_chain.h\"\ntemplate __global__ void ") + name + "(const qd::ChainParams);\n";
+    const std::string src = std::string("#include \"qd_chain.h\"\ntemplate __global__ void ") + name + "(const qd::ChainParams);\n";
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), "qd_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) { *why = "hiprtcCreateProgram failed"; return nullptr; }
     hiprtcAddNameExpression(prog, name);
@@ -597,7 +588,7 @@ hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compi
     std::string cache_file;
     {
         uint64_t h = fnv1a(name, strlen(name));
-        h = fnv1a(src.data(), src.size(), h);                  // includes the baked filter, if any
+        h = fnv1a(src.data(), src.size(), h);
         int rtc_major = 0, rtc_minor = 0;                      // a code object does not outlive the compiler that made it
         (void)hiprtcVersion(&rtc_major, &rtc_minor);
         h = fnv1a(&rtc_major, sizeof rtc_major, h);
@@ -676,8 +667,8 @@ size_t lds_for(uint32_t G, uint64_t W, uint64_t S, uint64_t D, uint64_t T, uint3
     // *raw_elems is what the runtime-geometry kernels read (ChainParams::lds_raw_elems): THEIR raw tile, whatever the main kernel's
     if (raw_elems) *raw_elems = (uint32_t)generic_raw_elems(g);
     uint64_t main_b = 0;
-    // (the role-split kernel's layout is k_chain's; a wave-local plan sizes the generic chain kernels here, its own LDS is spark_lds_bytes)
-    switch (family_of(flags & ~(kGeoSpark | kGeoPipe))) {
+    // (a wave-local plan sizes the generic chain kernels here, its own LDS is spark_lds_bytes)
+    switch (family_of(flags & ~kGeoSpark)) {
     case kFamPipe3s: {
         const Pipe3sRules k = pipe3s_rules((uint64_t)stream_spl, (uint64_t)stream_nt, g);
         main_b = k.kLdsBytes + (k.kWrite ? kStreamWriteLdsSlack : kStreamLdsSlack - k.FBX_ALIGN * 8);
@@ -742,7 +733,7 @@ struct qd_plan {
     uint32_t phase_unit = 1;             // ... window ranges that start on multiples of it start on a load vector
     hipFunction_t jit_fn = nullptr;      // plan-time specialised kernel (hiprtc), replaces fn for aligned launches
     int wg_per_cu = 1, n_cu = 256, prefetch_mode = 2, nco = 0, nt = kThreads;      // nt: threads that share a row of phase 1 (row = nt * SPL samples)
-    int launch_nt = kThreads;            // workgroup size of the main kernel: nt, plus the consumer wave of the role-split kernel
+    int launch_nt = kThreads;            // workgroup size of the main kernel: nt, plus the consumer waves of the three-stage kernels
     uint32_t kflags = 0;                 // FixedGeo FLAGS_ of the main kernel
     uint32_t dbg = 0;                    // development builds: ablation bits, read once at plan creation
     // NCO tables: lane tables per plan, row tables per launch context (device path; one per slot of the host ring)
@@ -788,7 +779,7 @@ struct qd_plan {
     std::mutex mu;
 };
 // the kernel a committed chain plan launches: its flags' family where a shape-specialised kernel won, the runtime-geometry k_chain otherwise
-// (the flag bits of k_chain_pipe, k_spark2 and k_spark0 — 9, 20, 21 — only ever come from plan-time builds: no table entry carries them)
+// (the flag bits of k_spark2 and k_spark0 — 20, 21 — only ever come from plan-time builds: no table entry carries them)
 static Family plan_family(const qd_plan *p) { return (p->jit_fn || p->fixed || p->spark) ? family_of(p->kflags) : kFamChain; }
 // ... and whether that kernel wants its launches on the row grid
 static bool plan_on_rows(const qd_plan *p) { return (p->jit_fn || p->fixed || p->spark) && row_aligned(p->kflags); }
@@ -1272,7 +1263,7 @@ uint32_t plain_tiles(const qd_plan *p, uint32_t T_lds) {
     return G;
 }
 
-// the plan-time build of a chain kernel (k_chain and its role-split / three-stage forms) with this tiling; `capped`: its register budget
+// the plan-time build of a chain kernel (k_chain and its three-stage forms) with this tiling; `capped`: its register budget
 // bounds the workgroups per CU (lb waves per SIMD)
 Candidate chain_build(const qd_plan *p, Candidate c, bool capped) {
     const uint64_t spl = spl_of(p->d.format), ROW = (uint64_t)c.nt * spl, step = (uint64_t)p->S * p->D;
@@ -1286,8 +1277,7 @@ Candidate chain_build(const qd_plan *p, Candidate c, bool capped) {
     const int noslp = c.noslp || ((c.flags & kGeoUnrolledFir) && fam != kFamPipe3 && fam != kFamPipe3s);
     c.src = Candidate::kBuild;
     c.key = JitKey{p->d.format, p->nco, p->has_fir ? 1 : 0, rows <= kWholeRows ? (int)rows : 4, rows <= kWholeRows ? 1 : 0, c.lb, c.nt,
-                   p->W, p->S, p->D, p->T, c.G, c.firb, c.firr, noslp, c.pad, c.batch, c.flags,
-                   (c.flags & kGeoBakedTaps) ? fnv1a(p->taps_h.data(), p->taps_h.size() * sizeof(float)) : 0ull};
+                   p->W, p->S, p->D, p->T, c.G, c.firb, c.firr, noslp, c.pad, c.batch, c.flags};
     c.wg_regs = capped ? std::max(1, c.lb * 4 * 64 / family_threads(c.nt, c.flags)) : 0;
     return c;
 }
@@ -1446,7 +1436,7 @@ std::vector<Candidate> chain_candidates_of(const qd_plan *p, uint32_t T_lds, boo
     };
     auto spark_build = [&](Candidate c, int nco, uint32_t key_S, int rch) {      // (their keys are not chain_build's)
         c.src = Candidate::kBuild;
-        c.key = JitKey{d.format, nco, 0, rch, 1, c.lb, kThreads, W, key_S, 1, 0, c.G, 8, 1, 0, 1, 1, c.flags, 0ull, d.epilogue};
+        c.key = JitKey{d.format, nco, 0, rch, 1, c.lb, kThreads, W, key_S, 1, 0, c.G, 8, 1, 0, 1, 1, c.flags, d.epilogue};
         return c;
     };
     const bool pow2_spark2 = W == 128 || W == 256 || W == 512 || W == 1024;
@@ -1694,7 +1684,7 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
         hint.required = true;
         if (!(p->has_fir && d.epilogue != QD_EPI_CF32_BLOCKS && hint.lb >= 1 && hint.lb <= 8 && hint.G >= 1 &&
               (hint.nt == 256 || hint.nt == 512 || hint.nt == 1024) && (hint.pad == 1 || hint.pad == 2) && hint.batch <= 64 && h[7] <= 8 &&
-              hint.flags <= 524287 &&
+              (hint.flags & ~kHintGeoBits) == 0 &&      // a removed (reserved) variant bit is refused here, before any build
               lds_for(hint.G, p->W, p->S, p->D, T_lds, nullptr, hint.pad, hint.batch, lut8_of(d.format), hint.flags, nullptr, spl_of(d.format), hint.nt) <= kLdsMax))
             return fail(QD_ERR_INVALID, "tile_hint {%u,%u,%u,%u,%u,%u,%u,%u} does not fit this chain", hint.G, (uint32_t)hint.nt, hint.firr, hint.firb,
                         (uint32_t)hint.lb, hint.pad, hint.batch, h[7]);
@@ -1713,7 +1703,7 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
     std::string why;
     for (const Candidate &c : cands) {
         hipFunction_t fn = nullptr;
-        if (c.src == Candidate::kBuild && !(fn = jit_chain_kernel(c.key, &why, may_compile, &p->taps_h))) {
+        if (c.src == Candidate::kBuild && !(fn = jit_chain_kernel(c.key, &why, may_compile))) {
             if (c.required) return fail(QD_ERR_UNSUPPORTED, "tile_hint build failed: %s", why.c_str());
             continue;
         }

@@ -21,7 +21,7 @@ for f in sorted(os.listdir(src)):
         d = json.load(open(os.path.join(src, f)))
         wl = d["workload"]
         # the traffic figure may only describe the kernel bench.py times for this workload: the bench line of the same box
-        # (config.kernel_flags, baked-taps bit excluded: it does not change the memory traffic) against the profiled kernel's name
+        # (config.kernel_flags, bit 1 excluded: a reserved bit, once the baked-taps variant, which old bench lines may carry) against the profiled kernel's name
         bline = os.path.join(src, f"{rnd}_bench_{'default' if wl == 'cfg3p' else wl}.json")
         ident = d.get("kernel_identity")
         if os.path.exists(bline) and ident is not None:

@@ -162,6 +162,8 @@ def test_geometry_rules_live_in_one_host_clean_header(tmp_path):
     for path in product:
         for name in re.findall(r"\b(kGeo[A-Z]\w*) =", open(path, encoding="utf-8").read()):
             defs.setdefault(name, []).append(os.path.relpath(path, ROOT))
-    assert len(defs) >= 22, sorted(defs)
+    assert sorted(defs) == sorted("kGeo" + n for n in (
+        "NoSplit", "FastP1", "UnrolledFir", "DeferFft", "PackedTile", "NtLoads", "HalfTile", "FastFma", "Pipe3", "NtInner", "Stream", "WriteSink",
+        "Spark", "SparkReg", "SparkDirect", "Window")), sorted(defs)
     assert all(where == [os.path.join("quadrs_amd", "csrc", "qd_geometry.h")] for where in defs.values()), defs
     assert "restate" not in open(os.path.join(csrc, "quadrs_hip.hip"), encoding="utf-8").read()

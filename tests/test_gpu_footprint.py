@@ -104,13 +104,12 @@ L1, L2 = ("lowpass", (200_000, 4, 40)), ("lowpass", (30_000, 4, 64))
 CASC = {"LL": [L1, L2], "LS": [L1, ("shift", 30_000)],
         "SLSLS": [("shift", 300_000), L1, ("shift", 15_000), L2, ("shift", 3_000)]}
 
-# row 1: the built-in kernels of cfg2, cfg3', cfg4; k_chain_pipe and half-window tiles through a tile hint
+# row 1: the built-in kernels of cfg2, cfg3', cfg4; two-window and half-window tiles through a tile hint
 ROW1 = [
     Case("cfg2", 0, 300_000, family=builtin("k_chain"), follows_env=True, **CFG2),
     Case("cfg3p", 0, 400_000, family=builtin("k_chain"), follows_env=True, **CFG3P),
     Case("cfg4", 0, 150_000, family=builtin("k_chain"), follows_env=True, **CFG4),
     Case("cfg2-two-window-tiles", 0, 300_000, family=plan_time("k_chain", 264), follows_env=True, tile_hint=[2, 256, 1, 8, 4, 1, 1 | (264 << 8), 0], **CFG2),
-    Case("cfg3p-k_chain_pipe", 0, 400_000, family=plan_time("k_chain_pipe", 512), follows_env=True, tile_hint=[1, 256, 1, 8, 5, 2, 1 | (516 << 8), 0], **CFG3P),
     Case("cfg4-half-window-tiles", 0, 150_000, family=plan_time("k_chain", 8192), follows_env=True, tile_hint=[1, 512, 2, 4, 4, 2, 2 | (8392 << 8), 0], **CFG4),
 ]
 # row 2: the three-stage kernel and its streaming form; long streams give every workgroup a run of many steps and switch the

@@ -401,7 +401,14 @@ def test_plan_time_specialisation_matches_generic(engine, oracle, monkeypatch, f
     assert_norms_close(ref, b[:ref.shape[0]], "jit")
 
 
-@pytest.mark.parametrize("fmt,lp,W,S,shift,hint", [
+def _variant_rows(rows):
+    """Ids as pytest numbers them, with the numbering the rows had before the four role-split rows (13-16) left: every surviving case
+    keeps its id, so its results stay comparable across that removal."""
+    ids = [i if i < 13 else i + 4 for i in range(len(rows))]
+    return [pytest.param(*r, id=f"{r[0]}-lp{j}-{r[2]}-{r[3]}-{r[4]}-hint{j}") for r, j in zip(rows, ids)]
+
+
+@pytest.mark.parametrize("fmt,lp,W,S,shift,hint", _variant_rows([
     # the built-in cfg3' kernel's variant set on a short stream: packed pair FIR + row-aligned phase 1 + deferred FFT (two slots)
     (0, (200_000, 32, 200), 128, 128, 280_000, (1, 256, 1, 8, 4, 2, 2 | (76 << 8), 0)),
     (0, (200_000, 32, 200), 128, 128, 280_000, (1, 256, 1, 8, 4, 2, 1 | (12 << 8), 0)),
@@ -419,11 +426,6 @@ def test_plan_time_specialisation_matches_generic(engine, oracle, monkeypatch, f
     (0, (200_000, 32, 200), 128, 128, 280_000, (1, 256, 2, 8, 4, 2, 2 | (200 << 8), 0)),
     (0, (200_000, 32, 200), 128, 128, None, (1, 256, 2, 8, 4, 2, 1 | (128 << 8), 0)),
     (3, (700_000, 16, 72), 128, 128, 90_000, (1, 256, 2, 8, 4, 2, 2 | (192 << 8), 0)),      # cs16, D = 16 (lag 4: taps held), T/2 = 36
-    # the role-split kernel (k_chain_pipe): four producer waves + the FIR wave (320 threads), and + an FFT wave (384 threads)
-    (0, (200_000, 32, 200), 128, 128, 280_000, (1, 256, 1, 8, 5, 2, 1 | (516 << 8), 0)),
-    (0, (200_000, 32, 200), 128, 128, 280_000, (1, 256, 1, 8, 6, 2, 2 | (1540 << 8), 0)),
-    (0, (2_000_000, 16, 40), 128, 128, 280_000, (1, 256, 1, 8, 6, 2, 2 | (1796 << 8), 0)),    # cfg2's shape: rows 0-1 / 2 / 3-4, nt loads
-    (1, (2_000_000, 16, 40), 128, 128, None, (1, 256, 1, 8, 5, 2, 1 | (516 << 8), 0)),        # cs8 rows of 1024 samples, no shift
     # the built-in cfg2 set (row-aligned phase 1 + nt loads, two windows per tile): 39 windows = a SHORT last tile through the fast path
     (0, (2_000_000, 16, 40), 128, 128, 280_000, (2, 256, 1, 8, 4, 1, 1 | (264 << 8), 0)),
     (0, (2_000_000, 16, 40), 128, 128, 280_000, (2, 256, 1, 8, 4, 1, 1 | (65800 << 8), 0)),   # + shared rows at the default policy (bit 16)
@@ -445,7 +447,7 @@ def test_plan_time_specialisation_matches_generic(engine, oracle, monkeypatch, f
     (3, (300_000, 16, 128), 64, 32, None, (4, 512, 1, 8, 4, 2, 1 | (163872 << 8), 0)),        # cs16, no shift
     (1, (200_000, 32, 400), 64, 16, 280_000, (14, 256, 1, 8, 4, 2, 1 | (164128 << 8), 0)),    # the built-in cs8 set: four producer waves (768 threads), 14-window steps
     (0, (200_000, 32, 200), 128, 128, 280_000, (2, 512, 1, 8, 4, 2, 1 | (164100 << 8), 0)),   # windows side by side (S == W): cfg3's chain through the streaming kernel, no trc ring
-])
+]))
 @pytest.mark.parametrize("epi", [0, 1, 2])
 def test_kernel_variant_flags_equal_generic(engine, oracle, fmt, lp, W, S, shift, hint, epi):
     """Every FixedGeo FLAGS_ variant the built-in kernels use (and neighbours of them on other shapes), forced through
@@ -465,7 +467,7 @@ def test_kernel_variant_flags_equal_generic(engine, oracle, fmt, lp, W, S, shift
     var_plan = engine.Plan(fmt, 21_000_000, N, tile_hint=list(hint), **kw)
     assert ref_plan.info.kernel_kind == 0 and var_plan.info.kernel_kind == 2
     flags = hint[6] >> 8
-    threads = hint[1] + (512 if flags & 32768 else (0 if not flags & 512 else (128 if flags & 1024 else 64)))       # the role-split kernels add their consumer waves
+    threads = hint[1] + (512 if flags & 32768 else 0)       # the three-stage kernels add their consumer waves
     assert var_plan.info.tile_windows == hint[0] and var_plan.info.threads == threads
     a, b = ref_plan.run_host(data), var_plan.run_host(data)
     assert a.shape == b.shape and a.shape[0] in (38, 39)         # bucket: lim / stride windows (src/fft.rs:86), one fewer than sparkfft counts here
@@ -476,6 +478,25 @@ def test_kernel_variant_flags_equal_generic(engine, oracle, fmt, lp, W, S, shift
     if epi == 0 and shift is None:
         ref, _ = oracle.Chain.from_bytes(data, fmt, 21_000_000).lowpass(*lp).spark_fft(W, S, max_windows=40)
         assert bits_equal(ref, b[:ref.shape[0]])
+
+
+def test_removed_variant_bits_are_refused(engine):
+    """The variant bits whose kernels were removed (0 planar tile, 1 baked taps, 4 packed span FIR, 9 / 10 role-split kernel, 11 / 12
+    cache-policy experiments) are reserved: a tile hint that carries one, alone or on top of the built-in cfg3' set, is refused at plan
+    creation as invalid; the built-in set alone still builds k_chain."""
+    if os.environ.get("QD_NO_FIXED"):
+        pytest.skip("QD_NO_FIXED=1 runs the generic kernels only")
+    from quadrs_amd import _ffi
+    lp, W, BUILTIN = (200_000, 32, 200), 128, 65868
+    N = (38 * W + W) * lp[1] + lp[2] + 3
+    kw = dict(shift_hz=280_000, lowpass=lp, width=W, stride=W)
+    for bit in (1, 2, 16, 512, 1024, 2048, 4096):
+        for flags in (bit, BUILTIN | bit):
+            with pytest.raises(engine.QuadrsError) as e:
+                engine.Plan(0, 21_000_000, N, tile_hint=[1, 256, 1, 8, 4, 2, 1 | (flags << 8), 0], **kw)
+            assert e.value.code == 1 == _ffi.ERR_INVALID, flags
+    plan = engine.Plan(0, 21_000_000, N, tile_hint=[1, 256, 1, 8, 4, 2, 1 | (BUILTIN << 8), 0], **kw)
+    assert plan.info.kernel_kind == 2 and plan.info.kernel_flags == BUILTIN and plan.kernel_name().startswith("qd::k_chain<"), plan.kernel_name()
 
 
 def test_random_shapes_specialised_equals_generic(engine, oracle):
