@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 # (source, extra flags)
 SRC = [(os.path.join(HERE, "csrc", "quadrs_hip.hip"), [])]
-DEPS = [s for s, _ in SRC] + [os.path.join(HERE, "csrc", f) for f in ("qd_chain.h", "qd_cascade.h", "qd_device.h", "qd_geometry.h", "qd_registry.h", "qd_summary.h", "qd_pieces.h", "qd_pool.h", "qd_limbs.h", "qd_mean.h", "qd_power.h", "qd_spread.h", "qd_density.h", "qd_bands.h", "qd_paint.h", "qd_lists.h", "qd_bursts.h", "qd_emissions.h", "qd_cuts.h", "qd_cuts_plan.h", "qd_symbols.h", "qd_symbols_plan.h")] + [
+DEPS = [s for s, _ in SRC] + [os.path.join(HERE, "csrc", f) for f in ("qd_chain.h", "qd_cascade.h", "qd_device.h", "qd_nco.h", "qd_geometry.h", "qd_registry.h", "qd_summary.h", "qd_pieces.h", "qd_pool.h", "qd_limbs.h", "qd_mean.h", "qd_power.h", "qd_spread.h", "qd_density.h", "qd_bands.h", "qd_paint.h", "qd_lists.h", "qd_bursts.h", "qd_emissions.h", "qd_cuts.h", "qd_cuts_plan.h", "qd_symbols.h", "qd_symbols_plan.h")] + [
     os.path.join(ROOT, "include", "quadrs_hip.h")]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 OUT = os.path.join(HERE, "libquadrs_hip.so")

@@ -44,7 +44,7 @@ constexpr uint32_t kCascS0 = 1, kCascS1 = 2, kCascL2 = 4, kCascS2 = 8;       // 
 struct CascadeParams {
     ChainParams c;              // src / src_first / src_count, first_window / n_windows / out_window0 / out, FFT layout, epilogue
     const float *h1, *h2;       // taps of the two lowpass stages (global, read as scalar loads)
-    const double2 *jtab;        // 3 x 512 lane entries (cos, sin)(exact j * ratio_k), one block per NCO
+    const LaneEntry *jtab;      // 3 x 512 lane entries (qd_nco.h) of the exact products j * ratio_k, one block per NCO
     const RowBase *rows[3];     // row bases of each NCO (k_rowtab, 512-sample rows of its own stage's index) over the launch's range ...
     uint64_t row0[3];           // ... starting at this absolute row
     double ratio0, ratio1, ratio2;
@@ -128,12 +128,9 @@ __device__ __forceinline__ float2 casc_load(const uint8_t *src, uint64_t i) {
 }
 
 // multiplier of absolute sample n of one NCO's stream (rb: its row table, whose first row is row0)
-__device__ __forceinline__ float2 casc_nco(const RowBase *rb, uint64_t row0, uint64_t n, const double2 *jt, double ratio) {
+__device__ __forceinline__ float2 casc_nco(const RowBase *rb, uint64_t row0, uint64_t n, const LaneEntry *jt, double ratio) {
     const uint32_t j = (uint32_t)(n % kCascadeRow);
-    const double2 cs = jt[j];
-    LaneRot lr;
-    lr.jf = (double)j; lr.c = cs.x; lr.s = cs.y;
-    return nco_mul<true>(rb[n / kCascadeRow - row0], lr, ratio);
+    return nco_mul<true>(rb[n / kCascadeRow - row0], nco_lane_rot((double)j, jt[j]), ratio);
 }
 
 template <int FMT>

@@ -75,7 +75,7 @@ struct ChainParams {
     void *out;
     const RowBase *rowtab;     // indexed by absolute row - rowtab_row0
     uint64_t rowtab_row0;
-    const double2 *jtab;       // ROW entries (cos, sin)(fl(j*ratio))
+    const LaneEntry *jtab;     // ROW lane entries (qd_nco.h) of the exact products j*ratio
     const float *taps;
     const float2 *tw;          // radix-4 layer twiddles, bottom layer first
     double ratio;
@@ -373,18 +373,29 @@ __device__ __forceinline__ double prefetch_rowtab(const ChainParams &P, const Ti
     return v;
 }
 
-// scalar (wave-uniform) load of one row base
+// scalar (wave-uniform) load of one row base: 32 contiguous bytes, one s_load_dwordx8.
+// LOAD_CS false (the runtime-geometry kernels): three values are loaded and with_cs forms the fourth where the row is processed — the
+// same f64 add of the same two values as nco_row_entry's, so the same bits.  Those kernels keep ~50 geometry values uniform and spill
+// scalar registers already; a fourth pair per row base in flight took the worst of them from 159 to 179 spilled SGPRs.  One f64 add per
+// lane and row there.
+template <bool LOAD_CS>
 __device__ __forceinline__ RowBase load_rowbase(const ChainParams &P, uint64_t r) {
     const_f64_p rp = (const_f64_p)(uintptr_t)(P.rowtab + (r - P.rowtab_row0));
     RowBase rb;
-    rb.c = rp[0]; rb.s = rp[1]; rb.nf = rp[2]; rb.pad_ = 0.0;
+    rb.c = rp[0]; rb.s = rp[1]; rb.nf = rp[2]; rb.cs = 0.0;
+    if constexpr (LOAD_CS) rb.cs = rp[3];
+    return rb;
+}
+template <bool LOAD_CS>
+__device__ __forceinline__ RowBase with_cs(RowBase rb) {
+    if constexpr (!LOAD_CS) rb.cs = rb.c + rb.s;
     return rb;
 }
 
 // row-aligned tiles (fast phase 1): base pointer of the tile's first row + a compile-time row offset -> s_load with an immediate
 __device__ __forceinline__ RowBase load_rowbase_at(const_f64_p tile_rows, uint32_t i) {
     RowBase rb;
-    rb.c = tile_rows[4 * i + 0]; rb.s = tile_rows[4 * i + 1]; rb.nf = tile_rows[4 * i + 2]; rb.pad_ = 0.0;
+    rb.c = tile_rows[4 * i + 0]; rb.s = tile_rows[4 * i + 1]; rb.nf = tile_rows[4 * i + 2]; rb.cs = tile_rows[4 * i + 3];
     return rb;
 }
 
@@ -1304,7 +1315,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
     const uint32_t W = geo.W, logW = geo.logW, S = geo.S, D = geo.D, T = geo.T, Dp = geo.Dp;
 
 
-    // Per-lane NCO constants: 3 doubles per sample slot.  Kernels whose FIR is register-hungry (register-tiled
+    // Per-lane NCO constants: 4 doubles per sample slot (LaneRot).  Kernels whose FIR is register-hungry (register-tiled
     // long filters) re-derive them at the top of every tile instead of keeping 8*SPL VGPRs live across the FIR
     // (the table is L2-resident; a tile of such a shape costs tens of thousands of cycles).
     // ... and so do the runtime-geometry kernels (round 4): with the five base-butterfly paths and the generic FIR loops they sit at the
@@ -1323,10 +1334,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
 #pragma unroll
         for (int u = 0; u < SPL; ++u) {
             uint32_t j = first + u;
-            double2 cs = P.jtab[j];
-            lr[u].jf = (double)j;
-            lr[u].c = cs.x;
-            lr[u].s = cs.y;
+            lr[u] = nco_lane_rot((double)j, P.jtab[j]);
         }
     };
     if constexpr (HAS_SHIFT && !kReloadLane) load_lane_rot(tid * SPL);
@@ -1533,8 +1541,8 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                 for (uint32_t r = 0; r < wg.n_rows; ++r) {
                     const Vec v = fetch_row<FMT, NT, false>(P, wg, r, tid);
                     RowBase rb{};
-                    if constexpr (HAS_SHIFT) rb = load_rowbase(P, wg.r0 + r);
-                    process_row_any<FMT, NT, NCO>(P, geo, wg, r, tid, v, rb, lr, lane_pad, lut, rawg);
+                    if constexpr (HAS_SHIFT) rb = load_rowbase<GeoT::kFixed>(P, wg.r0 + r);
+                    process_row_any<FMT, NT, NCO>(P, geo, wg, r, tid, v, with_cs<GeoT::kFixed>(rb), lr, lane_pad, lut, rawg);
                 }
             }
         } else
@@ -1608,7 +1616,7 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
             if (!ng.valid) ng = tg;                  // last tile of this workgroup: harmless re-loads
             rt_pf = prefetch_rowtab<HAS_SHIFT>(P, ng, tid);
             RowBase rb_next{};
-            if constexpr (HAS_SHIFT) rb_next = load_rowbase(P, tg.r0);
+            if constexpr (HAS_SHIFT) rb_next = load_rowbase<GeoT::kFixed>(P, tg.r0);
 #pragma unroll
             for (int i = 0; i < RCH; ++i) {
                 const Vec v = pf[i];
@@ -1623,9 +1631,9 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
                     QD_STAMP_ROW(2);
 #endif
                     if constexpr (HAS_SHIFT) {           // scalar load for the next row while this one computes
-                        if ((uint32_t)i + 1 < tg.n_rows) rb_next = load_rowbase(P, tg.r0 + i + 1);
+                        if ((uint32_t)i + 1 < tg.n_rows) rb_next = load_rowbase<GeoT::kFixed>(P, tg.r0 + i + 1);
                     }
-                    process_row_any<FMT, NT, NCO>(P, geo, tg, i, tid, v, rb, lr, lane_pad, lut, raw);
+                    process_row_any<FMT, NT, NCO>(P, geo, tg, i, tid, v, with_cs<GeoT::kFixed>(rb), lr, lane_pad, lut, raw);
                     QD_STAMP_ROW(3);
                 }
                 // Refill slot i only now, into the registers row i just vacated.  Issued before the row is consumed
@@ -1655,11 +1663,11 @@ __global__ __launch_bounds__(NT, LB) void k_chain(const ChainParams P) {
 #pragma unroll
                 for (int i = 0; i < RCH; ++i) {
                     rb[i] = RowBase{};
-                    if constexpr (HAS_SHIFT) { if (r + i < tg.n_rows) rb[i] = load_rowbase(P, tg.r0 + r + i); }
+                    if constexpr (HAS_SHIFT) { if (r + i < tg.n_rows) rb[i] = load_rowbase<GeoT::kFixed>(P, tg.r0 + r + i); }
                 }
 #pragma unroll
                 for (int i = 0; i < RCH; ++i)
-                    if (r + i < tg.n_rows) process_row_any<FMT, NT, NCO>(P, geo, tg, r + i, tid, cur[i], rb[i], lr, lane_pad, lut, raw);
+                    if (r + i < tg.n_rows) process_row_any<FMT, NT, NCO>(P, geo, tg, r + i, tid, cur[i], with_cs<GeoT::kFixed>(rb[i]), lr, lane_pad, lut, raw);
             }
         }
         QD_STAMP_AT(0);
@@ -2241,8 +2249,7 @@ __global__ __launch_bounds__(kPipe3Threads, LB) void k_chain_pipe3(const ChainPa
 #pragma unroll
             for (int u = 0; u < SPL; ++u) {
                 const uint32_t j = tid * SPL + u;
-                const double2 cs = P.jtab[j];
-                lr[u].jf = (double)j; lr[u].c = cs.x; lr[u].s = cs.y;
+                lr[u] = nco_lane_rot((double)j, P.jtab[j]);
             }
         }
         const uint32_t lane_pad = pad_index(geo, tid * SPL);
@@ -2606,8 +2613,7 @@ __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512),
 #pragma unroll
             for (int u = 0; u < SPL; ++u) {
                 const uint32_t j = tid * SPL + u;
-                const double2 cs = P.jtab[j];
-                lr[u].jf = (double)j; lr[u].c = cs.x; lr[u].s = cs.y;
+                lr[u] = nco_lane_rot((double)j, P.jtab[j]);
             }
         }
         const uint32_t lane_pad = pad_index(geo, tid * SPL);
@@ -2873,7 +2879,7 @@ __global__ __launch_bounds__(PT_ + ((GeoT::kFlags & kGeoWriteSink) ? 256 : 512),
 // is bit-identical to the generic kernel's (tests/test_gpu_robustness.py::test_wave_local_kernel_equals_generic) and to the oracle.
 // NCO row geometry: rows of 512 samples for every format (ChainParams::rowtab, jtab with 512 entries); a tile is two rows, a chunk
 // the quarter (cf32) or half (8-bit, cs16) of a row, so the lane constants of chunk c are those of quarter c % RQ: RQ * SPL = 8
-// (cos, sin) pairs per lane, kept in registers.
+// lane entries per lane, kept in registers.
 
 // Which tiles a wave takes.  Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8), each XCD with an L2 of its own whose
 // channels interleave the address space in 4 KiB steps.  A chip-wide grid-stride walk hands XCD x the 32 KiB chunks x, x + 8, x + 16 ...
@@ -2898,6 +2904,8 @@ struct SparkWalk {
 
 template <class GeoT, bool F = GeoT::kFixed> struct W_CT_GE8 { static constexpr bool value = false; };      // a compile-time width of at least 8
 template <class GeoT> struct W_CT_GE8<GeoT, true> { static constexpr bool value = GeoT::W >= 8; };
+static_assert(sizeof(LaneEntry) == kLaneEntryBytes, "the lane table's entry as qd_geometry.h sizes it");
+constexpr uint32_t kSparkLaneLds = kSparkRow * kLaneEntryBytes / 8;      // the LDS copy of the lane table, in float2 elements (a multiple of 256 bytes)
 template <int FMT> struct SparkTraits {
     using FT = FmtTraits<FMT>;
     static constexpr uint32_t SPL = FT::SPL, CH = 64u * SPL, RQ = kSparkRow / CH;       // chunk: one wave-wide load; RQ chunks per NCO row
@@ -2921,11 +2929,11 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark(const ChainParams P) {
     float2 *twl = reinterpret_cast<float2 *>(smem);                        // radix-4 layer twiddles (< W entries), shared by the four waves
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Plan-time builds with a shift read the lane constants out of an LDS copy of the lane table (one ds_read_b128 per sample) instead of
-    // holding RQ * SPL (cos, sin) pairs — 32 registers — across the tile loop: that is what kept them at three waves per SIMD.
+    // Plan-time builds with a shift read the lane constants out of an LDS copy of the lane table (24 bytes per sample) instead of
+    // holding RQ * SPL lane entries — 48 registers — across the tile loop: that is what kept them at three waves per SIMD.
     constexpr bool kLdsLane = HAS_SHIFT && GeoT::kFixed;
-    double2 *jt = reinterpret_cast<double2 *>(twl + (W < 32u ? 32u : W));      // (twiddle area of at least 256 bytes: the transform buffers start on 256-byte boundaries)
-    float2 *fbw = twl + (W < 32u ? 32u : W) + (kLdsLane ? 2u * kSparkRow : 0u) + (size_t)wave * TS;           // this wave's transform buffer: TS complex samples
+    LaneEntry *jt = reinterpret_cast<LaneEntry *>(twl + (W < 32u ? 32u : W));      // (twiddle area of at least 256 bytes: the transform buffers start on 256-byte boundaries)
+    float2 *fbw = twl + (W < 32u ? 32u : W) + (kLdsLane ? kSparkLaneLds : 0u) + (size_t)wave * TS;           // this wave's transform buffer: TS complex samples
     {
         const uint32_t n_tw = W - geo.base_len;
         for (uint32_t i = tid; i < n_tw; i += kThreads) twl[i] = P.tw[i];
@@ -2958,9 +2966,9 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark(const ChainParams P) {
             for (int i = 0; i < NCH * SPL; ++i) pos[i] ^= SZ::delta(pos[i]);
         }
     }
-    // (cos, sin)(j * ratio) of the lane's sample slots in each row quarter; the slot index itself is kept for quarter 0 only — the
+    // lane entries (qd_nco.h) of the lane's sample slots in each row quarter; the slot index itself is kept for quarter 0 only — the
     // quarter's offset q * CH goes into the row's sample count instead (integers below 2^53: the same double whichever way they add up)
-    double2 lcs[HAS_SHIFT && !kLdsLane ? RQ * SPL : 1];
+    LaneEntry lcs[HAS_SHIFT && !kLdsLane ? RQ * SPL : 1];
     double ljf[HAS_SHIFT ? SPL : 1];
     if constexpr (HAS_SHIFT) {
         if constexpr (!kLdsLane) {
@@ -3059,8 +3067,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark(const ChainParams P) {
                 LaneRot lr[SPL];
 #pragma unroll
                 for (int u = 0; u < SPL; ++u) {
-                    const double2 cs = kLdsLane ? jt[(uint32_t)q * CH + lane * SPL + (uint32_t)u] : lcs[kLdsLane ? 0 : q * SPL + u];
-                    lr[u].jf = ljf[u]; lr[u].c = cs.x; lr[u].s = cs.y;
+                    lr[u] = nco_lane_rot(ljf[u], kLdsLane ? jt[(uint32_t)q * CH + lane * SPL + (uint32_t)u] : lcs[kLdsLane ? 0 : q * SPL + u]);
                 }
                 RowBase rbq = rb;
                 rbq.nf = rb.nf + (double)(q * (int)CH);
@@ -3214,10 +3221,10 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *twl = reinterpret_cast<float2 *>(smem);                        // layer twiddles (W - base entries)
-    double2 *jt = reinterpret_cast<double2 *>(twl + W);                    // NCO lane table (512 entries), chains with a shift only
+    LaneEntry *jt = reinterpret_cast<LaneEntry *>(twl + W);                // NCO lane table (512 entries), chains with a shift only
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float2 *fbw = twl + W + (HAS_SHIFT ? 2u * kSparkRow : 0u) + (size_t)wave * TS;
+    float2 *fbw = twl + W + (HAS_SHIFT ? kSparkLaneLds : 0u) + (size_t)wave * TS;
     for (uint32_t i = tid; i < W - base; i += kThreads) twl[i] = P.tw[i];
     if constexpr (HAS_SHIFT) { for (uint32_t i = tid; i < kSparkRow; i += kThreads) jt[i] = P.jtab[i]; }
     __syncthreads();                                                       // the only workgroup barrier
@@ -3322,8 +3329,7 @@ __global__ __launch_bounds__(kThreads, LB) void k_spark2(const ChainParams P) {
                 if constexpr (HAS_SHIFT) {
                     const uint32_t jrow = (W >= kSparkRow ? 0u : (g * W) % kSparkRow) + (y * width) % kSparkRow;      // sample's place in its NCO row (before the column)
                     const uint32_t j = jrow + 2 * xp + (uint32_t)u;
-                    const double2 cs = jt[j];
-                    LaneRot lr; lr.jf = (double)j; lr.c = cs.x; lr.s = cs.y;
+                    const LaneRot lr = nco_lane_rot((double)j, jt[j]);
                     const RowBase &rb = rbl[W > kSparkRow ? (y * width) / kSparkRow : 0];
                     x = cmul_pk(x, nco_mul<NCO == 2>(rb, lr, P.ratio));     // buf[i] *= mul (src/shift.rs:51)
                 }

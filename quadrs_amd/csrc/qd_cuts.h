@@ -38,7 +38,7 @@ __device__ __forceinline__ void cut_tile_reads(const CutJob &jb, const CutTile &
 }
 
 __global__ __launch_bounds__(256) void k_cuts_tables(const CutJob *__restrict__ jobs, const CutTile *__restrict__ tiles, uint32_t n_tiles, RowBase *__restrict__ rowtab,
-                                                    const double *__restrict__ lane_ratio, uint32_t n_lane, double2 *__restrict__ lanetab) {
+                                                    const double *__restrict__ lane_ratio, uint32_t n_lane, LaneEntry *__restrict__ lanetab) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t n_row = (uint64_t)n_tiles * kCutsTileRows;
     if (i < n_row) {
@@ -50,16 +50,10 @@ __global__ __launch_bounds__(256) void k_cuts_tables(const CutJob *__restrict__ 
         cut_tile_reads(jb, tl, &lo, &hi);
         const uint64_t row = (jb.span0 + lo) / kCutsNcoRow + r;
         if (row * kCutsNcoRow >= jb.span0 + hi) return;
-        RowBase rb;
-        rb.nf = (double)(row * kCutsNcoRow);
-        rb.pad_ = 0.0;
-        nco_table_entry(rb.nf, jb.ratio, &rb.c, &rb.s);
-        rowtab[i] = rb;
+        rowtab[i] = nco_row_entry((double)(row * kCutsNcoRow), jb.ratio);
     } else if (i - n_row < (uint64_t)n_lane * kCutsNcoRow) {
         const uint64_t u = (i - n_row) / kCutsNcoRow, j = (i - n_row) % kCutsNcoRow;
-        double c, s;
-        nco_table_entry((double)j, lane_ratio[u], &c, &s);
-        lanetab[u * kCutsNcoRow + j] = make_double2(c, s);
+        lanetab[u * kCutsNcoRow + j] = nco_lane_entry((double)j, lane_ratio[u]);
     }
 }
 
@@ -102,7 +96,7 @@ __device__ __forceinline__ void cuts_load_vec(const uint8_t *p, float2 *s) {
 template <int FMT>
 __global__ __launch_bounds__(kCutsThreads) void k_cuts(const uint8_t *__restrict__ src, const CutJob *__restrict__ jobs, const CutTile *__restrict__ tiles,
                                                        const float *__restrict__ taps, const RowBase *__restrict__ rowtab,
-                                                       const double2 *__restrict__ lanetab, float2 *__restrict__ out) {
+                                                       const LaneEntry *__restrict__ lanetab, float2 *__restrict__ out) {
     extern __shared__ __attribute__((aligned(32))) char smem_cuts[];
     RowBase *rows = reinterpret_cast<RowBase *>(smem_cuts);                                  // kCutsTileRows entries
     float2 *xs = reinterpret_cast<float2 *>(smem_cuts + kCutsTileRows * sizeof(RowBase));    // kCutsLdsSamples elements
@@ -125,9 +119,7 @@ __global__ __launch_bounds__(kCutsThreads) void k_cuts(const uint8_t *__restrict
             const uint64_t n = abs0 + k;
             const uint32_t j = (uint32_t)(n % kCutsNcoRow);
             const RowBase rb = rows[(uint32_t)(n / kCutsNcoRow - row0)];
-            const double2 cs = lanetab[jb.lane_at + j];
-            LaneRot lr;
-            lr.jf = (double)j; lr.c = cs.x; lr.s = cs.y;
+            const LaneRot lr = nco_lane_rot((double)j, lanetab[jb.lane_at + j]);
             const float2 m = second ? nco_mul<true>(rb, lr, jb.ratio) : nco_mul<false>(rb, lr, jb.ratio);
             v = cmul(v, m);
         }

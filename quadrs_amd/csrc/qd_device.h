@@ -220,84 +220,19 @@ __device__ __forceinline__ uint32_t rev4(uint32_t x, uint32_t digits) {
 
 // ---------------------------------------------------------------- NCO (src/shift.rs:49-50)
 //
-// Reference: place = fl((n as f64) * ratio); mul = (cos(place) as f32, sin(place) as f32).
-// A libm-grade f64 sincos per sample costs more f64 issue slots than the chip has at HBM rate, and f64 work also
-// lowers the clock the chip holds.  Scheme: the EXACT product X = n*ratio splits as n_r*ratio + j*ratio (n = n_r + j,
-// n_r the first sample of a row of ROW samples).  Tables hold cos/sin of those two exact products (each the libm
-// sincos of the rounded product, corrected to first order by the product's exactly known rounding residual), so one
-// rotation gives cos/sin(X).  The reference's argument is place = fl(X) = X - r with r = fma(n, ratio, -place) the exact
-// residual of ITS multiplication (|r| <= ulp(place)/2), so cos(place) = cos(X - r) = C + r*S, sin(place) = S - r*C to
-// first order (the dropped r^2/2 is <= 1.1e-16 for |place| < 2^28 rad; beyond that the second-order form is used).
-// 9 f64 operations per sample (12 second-order) + two f64->f32 converts; absolute error ~4e-16, so the f32 rounding
-// equals glibc's except when the f64 value lies within ~1e-8 f32-ulp of a rounding boundary.
-
-// Row-base entry: everything that is uniform over one row of ROW consecutive samples.
-struct __attribute__((aligned(32))) RowBase {
-    double c, s;     // cos/sin of the exact product (row*ROW) * ratio
-    double nf;       // (double)(row*ROW)
-    double pad_;
-};
-
-// Per-lane constants for one sample slot j inside a row: cos/sin of the exact product j * ratio.
-struct LaneRot { double jf, c, s; };
-
-// table entry: cos/sin of the exact product k * ratio, from the platform sincos of the rounded product
-__device__ __forceinline__ void nco_table_entry(double kf, double ratio, double *c, double *s) {
-    const double th = kf * ratio;
-    const double lo = __builtin_fma(kf, ratio, -th);     // exact: k*ratio = th + lo
-    double s0, c0;
-    sincos(th, &s0, &c0);
-    // cos / sin(th + lo), |lo| <= ulp(th)/2 (up to ~4e-6 at the far end of a 2^34-sample stream): third order in lo, the
-    // small terms gathered first so that each entry takes one final rounding
-    const double q = 0.5 * lo * lo, sl = __builtin_fma(-lo * lo * lo, 1.0 / 6.0, lo);     // 1 - cos lo, sin lo
-    *c = c0 + __builtin_fma(-q, c0, -sl * s0);
-    *s = s0 + __builtin_fma(-q, s0, sl * c0);
-}
+// The arithmetic — RowBase, LaneEntry, LaneRot, nco_table_entry, nco_row_entry, nco_lane_entry, nco_mul, nco_mul_n — is qd_nco.h's,
+// which also compiles as host C++ (scripts/nco_host_check.cpp holds it to __float128): the rotation of the row entry by the lane
+// entry in three multiplications, 8 f64 operations per sample (11 second-order) + two f64->f32 converts, absolute error
+// <= 1.51e-15 before the casts (derivation there).  Every kernel reads its multipliers through these functions and nothing else.
+}  // namespace qd
+#include "qd_nco.h"
+namespace qd {
 
 template <bool SECOND_ORDER>
 __device__ __forceinline__ float2 nco_mul(const RowBase &rb, const LaneRot &lr, double ratio) {
-    const double nf = rb.nf + lr.jf;                     // exact (integers < 2^53)
-    const double place = nf * ratio;                     // == reference `place`
-    const double r = __builtin_fma(nf, ratio, -place);   // exact: n*ratio = place + r
-    const double C = __builtin_fma(-rb.s, lr.s, rb.c * lr.c);      // cos / sin of the exact product
-    const double S = __builtin_fma(rb.s, lr.c, rb.c * lr.s);
-    double c, s;
-    if constexpr (SECOND_ORDER) {
-        const double h = 0.5 * r;
-        c = __builtin_fma(r, __builtin_fma(-h, C, S), C);          // C (1 - r^2/2) + r S
-        s = __builtin_fma(-r, __builtin_fma(h, S, C), S);          // S (1 - r^2/2) - r C
-    } else {
-        c = __builtin_fma(r, S, C);
-        s = __builtin_fma(-r, C, S);
-    }
-    return make_float2((float)c, (float)s);
-}
-
-// The same arithmetic for the N samples a lane owns, written step-by-step across the samples so
-// that the N independent f64 dependency chains are issued interleaved.
-template <bool SECOND_ORDER, int N>
-__device__ __forceinline__ void nco_mul_n(const RowBase &rb, const LaneRot *lr, double ratio, float2 *m) {
-    double nf[N], pl[N], r[N], C[N], S[N], c[N], s[N];
-#pragma unroll
-    for (int u = 0; u < N; ++u) nf[u] = rb.nf + lr[u].jf;
-#pragma unroll
-    for (int u = 0; u < N; ++u) { pl[u] = nf[u] * ratio; C[u] = rb.c * lr[u].c; S[u] = rb.c * lr[u].s; }
-#pragma unroll
-    for (int u = 0; u < N; ++u) { r[u] = __builtin_fma(nf[u], ratio, -pl[u]); C[u] = __builtin_fma(-rb.s, lr[u].s, C[u]); S[u] = __builtin_fma(rb.s, lr[u].c, S[u]); }
-    if constexpr (SECOND_ORDER) {
-        double h[N], uu[N], vv[N];
-#pragma unroll
-        for (int u = 0; u < N; ++u) h[u] = 0.5 * r[u];
-#pragma unroll
-        for (int u = 0; u < N; ++u) { uu[u] = __builtin_fma(-h[u], C[u], S[u]); vv[u] = __builtin_fma(h[u], S[u], C[u]); }
-#pragma unroll
-        for (int u = 0; u < N; ++u) { c[u] = __builtin_fma(r[u], uu[u], C[u]); s[u] = __builtin_fma(-r[u], vv[u], S[u]); }
-    } else {
-#pragma unroll
-        for (int u = 0; u < N; ++u) { c[u] = __builtin_fma(r[u], S[u], C[u]); s[u] = __builtin_fma(-r[u], C[u], S[u]); }
-    }
-#pragma unroll
-    for (int u = 0; u < N; ++u) m[u] = make_float2((float)c[u], (float)s[u]);
+    float2 m;
+    nco_mul<SECOND_ORDER>(rb, lr, ratio, &m.x, &m.y);
+    return m;
 }
 
 }  // namespace qd

@@ -47,6 +47,7 @@ constexpr int kThreads = 256;
 constexpr int kPipe3Threads = 1024, kPipe3Prod = 512;
 constexpr uint32_t kSparkRow = 512;          // samples per NCO row of the wave-local kernels, every format
 constexpr uint32_t kSparkMaxW = 1024;
+constexpr uint32_t kLaneEntryBytes = 24;     // one entry of an NCO lane table (qd_nco.h LaneEntry: c, sum, dif)
 
 enum Family { kFamChain, kFamPipe3, kFamPipe3s, kFamSpark, kFamSpark2, kFamSpark0 };
 
@@ -259,7 +260,7 @@ constexpr uint64_t pipe3_lds_bytes(const FixedRules &g) {
     return 2 * g.lds_raw_alloc * 8 + 4 * g.pipe3_q_pad() * 8 + g.G * g.W * 8 + g.W * 8 + ct_taps_bytes(g.T) + kPipe3QueueBytes;
 }
 // k_spark / k_spark2: twiddles | four waves' transform buffers of ts samples (| the NCO lane table)
-constexpr uint64_t spark_lds_bytes(uint64_t W, uint64_t ts, bool lane_table) { return (ct_max(W, 32) + 4 * ts) * 8 + (lane_table ? kSparkRow * 16 : 0); }
+constexpr uint64_t spark_lds_bytes(uint64_t W, uint64_t ts, bool lane_table) { return (ct_max(W, 32) + 4 * ts) * 8 + (lane_table ? kSparkRow * kLaneEntryBytes : 0); }
 // Historical slack the host adds on top of the layouts above ("where a kernel's geometry lives"): it keeps every plan's
 // LDS size, and with it the workgroups per CU, where they were measured.
 // The streaming layout was sized WITHOUT the transform buffers' alignment padding (Pipe3sRules::FBX_ALIGN, at most 31 elements) plus

@@ -86,25 +86,19 @@ int bps_of(int fmt) { return fmt == QD_FMT_CF32 ? 8 : (fmt == QD_FMT_CS16 ? 4 : 
 
 // ------------------------------------------------------------------ small kernels
 
-// Row bases: (cos, sin) of the exact product (row*ROW) * ratio (qd_device.h, NCO), plus nf itself.
+// Row bases: (cos, sin) of the exact product (row*ROW) * ratio, nf itself and fl(cos + sin) (qd_nco.h, nco_row_entry).
 // (n_off: the row grid of a stream that starts n_off samples into the plan's — the interleaved launches of overlapping lowpass-free windows)
 __global__ void k_rowtab(double ratio, uint32_t row_len, uint64_t row0, uint64_t n_rows, uint64_t n_off, RowBase *out) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows) return;
-    RowBase rb;
-    rb.nf = (double)((row0 + i) * (uint64_t)row_len + n_off);
-    rb.pad_ = 0.0;
-    nco_table_entry(rb.nf, ratio, &rb.c, &rb.s);
-    out[i] = rb;
+    out[i] = nco_row_entry((double)((row0 + i) * (uint64_t)row_len + n_off), ratio);
 }
 
-// Lane table: (cos, sin) of the exact product j * ratio
-__global__ void k_jtab(double ratio, uint32_t n, double2 *out) {
+// Lane table: the lane entries (c, c + s, s - c) of (c, s) = (cos, sin) of the exact product j * ratio (qd_nco.h, nco_lane_entry)
+__global__ void k_jtab(double ratio, uint32_t n, LaneEntry *out) {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    double s, c;
-    nco_table_entry((double)j, ratio, &c, &s);
-    out[j] = make_double2(c, s);
+    out[j] = nco_lane_entry((double)j, ratio);
 }
 
 // FileFormat::to_cf32 per sample (src/lib.rs:231-255)
@@ -124,14 +118,13 @@ __global__ void k_unpack(int fmt, const uint8_t *src, size_t n, float2 *out) {
 // Shift::read_at's loop over an arbitrary block (src/shift.rs:48-52), rows of 512 samples.
 __global__ __launch_bounds__(256) void k_shift(float2 *buf, uint64_t abs_off, uint64_t n, double ratio,
                                                 const RowBase *rowtab, uint64_t row0, uint64_t n_rows,
-                                                const double2 *jtab, int second_order) {
+                                                const LaneEntry *jtab, int second_order) {
     constexpr uint32_t ROW = 512;
     const uint32_t tid = threadIdx.x;
     LaneRot lr[2];
     for (int u = 0; u < 2; ++u) {
         uint32_t j = tid * 2 + u;
-        double2 cs = jtab[j];
-        lr[u].jf = (double)j; lr[u].c = cs.x; lr[u].s = cs.y;
+        lr[u] = nco_lane_rot((double)j, jtab[j]);
     }
     for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
         const RowBase rb = rowtab[r];
@@ -197,7 +190,7 @@ __device__ __forceinline__ double2 zmul(double2 a, double2 b) {
 // unpack_*, nco_mul over the absolute sample index (rows of 512 samples, as k_shift), cmul_pk.  <0, 0> loads cf32 as it always did.
 struct BlueSrc {
     const uint8_t *in; uint64_t in_first;      // raw bytes of source sample in_first
-    double ratio; const RowBase *rowtab; uint64_t rowtab_row0; const double2 *jtab;     // NCO != 0 only
+    double ratio; const RowBase *rowtab; uint64_t rowtab_row0; const LaneEntry *jtab;     // NCO != 0 only
 };
 template <int FMT, int NCO>
 __global__ __launch_bounds__(256) void k_bluestein(const BlueSrc src, const uint64_t *__restrict__ offs,
@@ -222,8 +215,7 @@ __global__ __launch_bounds__(256) void k_bluestein(const BlueSrc src, const uint
             if constexpr (NCO != 0) {
                 const uint32_t j = (uint32_t)(na & 511u);
                 const RowBase rb = src.rowtab[(na >> 9) - src.rowtab_row0];
-                const double2 cs = src.jtab[j];
-                LaneRot lr; lr.jf = (double)j; lr.c = cs.x; lr.s = cs.y;
+                const LaneRot lr = nco_lane_rot((double)j, src.jtab[j]);
                 xv = cmul_pk(xv, nco_mul<NCO == 2>(rb, lr, src.ratio));        // buf[i] *= mul (src/shift.rs:51)
             }
             if (win) xv = cscale(xv, win[n]);         // *sample *= w_val (src/ffts.rs:64-68), Complex<f32> * f32, f32-rounded
@@ -326,10 +318,12 @@ FftLayout fft_layout(uint64_t W) {
 // instead of held across it (k_chain kReloadLane) — no scratch at four waves for the first-order NCO; the second-order kernels (streams
 // past 2^28 rad of phase, which get a plan-time build anyway) are budgeted for three.  Budgeting ALL shifted kernels for three waves
 // removed the scratch too but cost 6-18 % on 256 MiB streams (profiles/r04/generic_rate.log).  tests/test_abi_cpu.py audits every kernel.
-constexpr int dyn_lb(int nco) { return nco == 2 ? 3 : 4; }
+// The three-multiplication rotation keeps a fourth double per sample slot (LaneRot): with cs16's four slots a lane and its two-dword
+// unpack the first-order kernels no longer fit four waves either (6-14 VGPRs of scratch), so cs16 with a shift is budgeted for three.
+constexpr int dyn_lb(int nco, int fmt = 0) { return (nco == 2 || (nco == 1 && fmt == 3)) ? 3 : 4; }
 template <int F, int NCO, bool FI, class G = DynGeo>
 chain_fn pick_dyn(bool aligned) {
-    return aligned ? k_chain<F, NCO, G, FI, 4, false, true, dyn_lb(NCO)> : k_chain<F, NCO, G, FI, 4, false, false, dyn_lb(NCO)>;
+    return aligned ? k_chain<F, NCO, G, FI, 4, false, true, dyn_lb(NCO, F)> : k_chain<F, NCO, G, FI, 4, false, false, dyn_lb(NCO, F)>;
 }
 
 // (windowed plans behind a lowpass: the WinGeo instantiations; without a lowpass the DynGeo kernels test ChainParams::window themselves)
@@ -537,9 +531,9 @@ hipFunction_t jit_chain_kernel(const JitKey &k, std::string *why, bool may_compi
     if (it != g_jit_cache.end()) return it->second;
     if (auto bad = g_jit_failed.find(dk); bad != g_jit_failed.end()) { *why = bad->second; return nullptr; }
     const std::string dir = csrc_dir();
-    std::vector<char> hdrs[3];            // everything a plan-time build includes: the cache key hashes their contents
-    const char *const hdr_names[3] = {"/qd_chain.h", "/qd_device.h", "/qd_geometry.h"};
-    for (int i = 0; i < 3; ++i)
+    std::vector<char> hdrs[4];            // everything a plan-time build includes: the cache key hashes their contents
+    const char *const hdr_names[4] = {"/qd_chain.h", "/qd_device.h", "/qd_geometry.h", "/qd_nco.h"};
+    for (int i = 0; i < 4; ++i)
         if (!read_file(dir + hdr_names[i], &hdrs[i])) {
             *why = "kernel headers not found next to the library (" + dir + ")";
             return nullptr;
@@ -737,7 +731,7 @@ struct qd_plan {
     uint32_t kflags = 0;                 // FixedGeo FLAGS_ of the main kernel
     uint32_t dbg = 0;                    // development builds: ablation bits, read once at plan creation
     // NCO tables: lane tables per plan, row tables per launch context (device path; one per slot of the host ring)
-    double2 *jtab_d = nullptr, *jtab256_d = nullptr;
+    LaneEntry *jtab_d = nullptr, *jtab256_d = nullptr;
     NcoTabs tabs_dev, tabs_slot[2];
     // take_fft mode (generic kernels): per-window start offsets and an f32 window, both on the device
     const uint64_t *row_offsets_d = nullptr;
@@ -769,7 +763,7 @@ struct qd_plan {
     size_t c_lds = 0;
     int c_wg_per_cu = 1;
     float *c_h1 = nullptr, *c_h2 = nullptr;
-    double2 *c_jtab = nullptr;
+    LaneEntry *c_jtab = nullptr;
     // the stage list the plan was made from (qd_plan_create_stages; routed plans too) and each lowpass stage's taps
     std::vector<qd_stage> stages;
     std::vector<std::vector<float>> stage_taps;
@@ -1394,7 +1388,7 @@ std::vector<Candidate> chain_candidates_of(const qd_plan *p, uint32_t T_lds, boo
     Candidate plain;
     plain.G = plain_tiles(p, T_lds);
     Candidate generic = plain;
-    generic.wg_regs = dyn_lb(p->nco);
+    generic.wg_regs = dyn_lb(p->nco, d.format);
     // shape-specialised built-in kernels (kFixed): exact arithmetic; QD_MODE_FAST prefers a fused build of the shape's recipe
     const FixedEntry *fixed = (p->has_fir && !write_sink && policy != QD_KERNEL_GENERIC && !windowed) ? find_fixed(d.format, p->nco, W, S, p->D, p->T) : nullptr;
     const bool fast = d.mode == QD_MODE_FAST && p->has_fir && jit_ok && !write_sink;
@@ -1749,12 +1743,12 @@ static int plan_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t 
     }
     if (p->has_shift) {
         const uint32_t ROW = p->nt * spl_of(d.format);
-        HIPCHK(hipMalloc(&p->jtab_d, ROW * sizeof(double2)));
+        HIPCHK(hipMalloc(&p->jtab_d, ROW * sizeof(LaneEntry)));
         hipLaunchKernelGGL(k_jtab, dim3((ROW + 255) / 256), dim3(256), 0, 0, p->ratio, ROW, p->jtab_d);
         HIPCHK(hipGetLastError());
         if (p->nt != kThreads) {
             const uint32_t ROW256 = kThreads * spl_of(d.format);
-            HIPCHK(hipMalloc(&p->jtab256_d, ROW256 * sizeof(double2)));
+            HIPCHK(hipMalloc(&p->jtab256_d, ROW256 * sizeof(LaneEntry)));
             hipLaunchKernelGGL(k_jtab, dim3((ROW256 + 255) / 256), dim3(256), 0, 0, p->ratio, ROW256, p->jtab256_d);
             HIPCHK(hipGetLastError());
         }
@@ -1975,8 +1969,8 @@ int cascade_init(qd_plan *p, const StageGeo &g, const qd_stage *st) {
         HIPCHK(hipMalloc(&p->c_h2, g.T2 * sizeof(float)));
         HIPCHK(hipMemcpy(p->c_h2, p->stage_taps[g.l2].data(), g.T2 * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMalloc(&p->c_jtab, 3 * kCascadeRow * sizeof(double2)));
-    HIPCHK(hipMemset(p->c_jtab, 0, 3 * kCascadeRow * sizeof(double2)));
+    HIPCHK(hipMalloc(&p->c_jtab, 3 * kCascadeRow * sizeof(LaneEntry)));
+    HIPCHK(hipMemset(p->c_jtab, 0, 3 * kCascadeRow * sizeof(LaneEntry)));
     for (int k = 0; k < 3; ++k)
         if (sidx[k] >= 0) {
             hipLaunchKernelGGL(k_jtab, dim3((kCascadeRow + 255) / 256), dim3(256), 0, 0, p->c_ratio[k], kCascadeRow, p->c_jtab + k * kCascadeRow);
@@ -2083,7 +2077,7 @@ int rows_init(qd_plan *p, const qd_chain_desc &d, uint64_t len, uint64_t rate) {
     }
     if (p->has_shift) {                      // the lane table: entries j < 512 serve k_bluestein's rows of 512 samples as well
         const uint32_t ROW = kThreads * spl_of(fmt);
-        HIPCHK(hipMalloc(&p->jtab_d, ROW * sizeof(double2)));
+        HIPCHK(hipMalloc(&p->jtab_d, ROW * sizeof(LaneEntry)));
         hipLaunchKernelGGL(k_jtab, dim3((ROW + 255) / 256), dim3(256), 0, 0, p->ratio, ROW, p->jtab_d);
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());
@@ -2953,13 +2947,13 @@ int qd_shift(qd_c32 *buf, size_t n, uint64_t abs_off, double ratio, int mem) {
     const uint64_t r0 = abs_off / ROW, r1 = (abs_off + n + ROW - 1) / ROW, rows = r1 - r0;
     void *rt = nullptr, *jt = nullptr;
     int rc = ws.get(2, rows * sizeof(RowBase), &rt); if (rc) return rc;
-    rc = ws.get(3, ROW * sizeof(double2), &jt); if (rc) return rc;
+    rc = ws.get(3, ROW * sizeof(LaneEntry), &jt); if (rc) return rc;
     hipLaunchKernelGGL(k_rowtab, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, ratio, ROW, r0, rows, (uint64_t)0, static_cast<RowBase *>(rt));
-    hipLaunchKernelGGL(k_jtab, dim3(2), dim3(256), 0, st, ratio, ROW, static_cast<double2 *>(jt));
+    hipLaunchKernelGGL(k_jtab, dim3(2), dim3(256), 0, st, ratio, ROW, static_cast<LaneEntry *>(jt));
     const int so = (std::fabs(ratio) * (double)(abs_off + n) > 268435456.0) ? 1 : 0;
     const uint32_t grid = (uint32_t)(rows < 4096 ? rows : 4096);
     hipLaunchKernelGGL(k_shift, dim3(grid), dim3(256), 0, st, d, abs_off, (uint64_t)n, ratio, static_cast<const RowBase *>(rt), r0, rows,
-                       static_cast<const double2 *>(jt), so);
+                       static_cast<const LaneEntry *>(jt), so);
     HIPCHK(hipGetLastError());
     if (mem != QD_MEM_DEVICE) HIPCHK(hipMemcpyAsync(buf, d, n * 8, hipMemcpyDeviceToHost, st));
     return finish_call(mem, st);
@@ -4790,7 +4784,7 @@ static int cuts_run_impl(int fmt, uint64_t sample_rate, uint64_t n_samples, cons
     const size_t jobs_b = (jobs.size() * sizeof(CutJob) + 15) & ~(size_t)15, taps_b = (taps_h.size() * 4 + 15) & ~(size_t)15, ratio_b = (n_lane * 8 + 15) & ~(size_t)15;
     void *tab_d = nullptr, *lane_d = nullptr;
     int rc = ws.get(2, jobs_b + taps_b + ratio_b, &tab_d); if (rc) return rc;
-    rc = ws.get(3, std::max<size_t>(n_lane, 1) * kCutsNcoRow * sizeof(double2), &lane_d); if (rc) return rc;
+    rc = ws.get(3, std::max<size_t>(n_lane, 1) * kCutsNcoRow * sizeof(LaneEntry), &lane_d); if (rc) return rc;
     char *const tab = static_cast<char *>(tab_d);
     HIPCHK(hipMemcpyAsync(tab, jobs.data(), jobs.size() * sizeof(CutJob), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(tab + jobs_b, taps_h.data(), taps_h.size() * 4, hipMemcpyHostToDevice, st));
@@ -4834,9 +4828,9 @@ static int cuts_run_impl(int fmt, uint64_t sample_rate, uint64_t n_samples, cons
         const uint32_t lanes = first_batch ? (uint32_t)n_lane : 0u;
         const uint64_t table_threads = (uint64_t)n_tiles * kCutsTileRows + (uint64_t)lanes * kCutsNcoRow;
         hipLaunchKernelGGL(k_cuts_tables, dim3((uint32_t)((table_threads + 255) / 256)), dim3(256), 0, st, jobs_d, tiles_d, n_tiles, rows_d, ratio_d, lanes,
-                           static_cast<double2 *>(lane_d));
+                           static_cast<LaneEntry *>(lane_d));
         const RowBase *rows_c = rows_d;
-        const double2 *lane_c = static_cast<const double2 *>(lane_d);
+        const LaneEntry *lane_c = static_cast<const LaneEntry *>(lane_d);
         switch (fmt) {
         case 0: hipLaunchKernelGGL(k_cuts<0>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;
         case 1: hipLaunchKernelGGL(k_cuts<1>, dim3(n_tiles), dim3(kCutsThreads), kCutsLdsBytes, st, in, jobs_d, tiles_d, taps_d, rows_c, lane_c, o); break;

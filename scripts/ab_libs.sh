@@ -5,7 +5,9 @@
 wl=$1; shift
 for rep in 1 2 3; do
   for lib in "$@"; do
-    QD_LIB_PATH=$PWD/$lib python bench.py --full --workload $wl --no-cpu-baseline --no-others 2>/dev/null > /tmp/ab_line.json
+    # every run under its own time limit; after a failed or killed run nothing more is started on the GPU
+    QD_LIB_PATH=$PWD/$lib timeout -k 10 ${AB_TIMEOUT:-300} python bench.py --full --workload $wl --no-cpu-baseline --no-others 2>/dev/null > /tmp/ab_line.json
+    rc=$?; if [ $rc -ne 0 ]; then echo "$wl $lib: bench rc=$rc"; exit $rc; fi
     python - "$wl" "$lib" <<'PY'
 import sys, json
 d = json.loads(open("/tmp/ab_line.json").read().strip().splitlines()[-1])
